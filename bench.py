@@ -17,10 +17,17 @@ sum -> Adam on every rank.  The population (pop 5000 = 2500 pairs) is sharded ro
 Inputs (noise table, theta, reference batch) are resident in HBM before the timed region.
 value = sum of episode lengths over all ranks and timed generations / max-over-ranks wall time (es.py:332,341).
 
-After the headline region the same command times BASELINE.json's other configurations (tools/workloads.py: Deep GA on both
-networks, the NS-ES meta-population loop, the six-game loop, the 2-worker CPU reference path) and reports them under "extra",
-each with its own roofline / CPU baseline.  Default: all of them at N = 1; at N > 1 the sharded ones (ga, nses, sweep: BASELINE
-configs 4 and 5 are defined on 4 and 8 GPUs), run over the same ranks on the headline engine's communicator.
+A plain run does only what the headline figure needs: set up, warm up, time --steps generations, write the last one's outputs
+(--dump-outputs DIR: theta after the update and the generation's records as DIR/<name>.npy; the inputs are seeded, so two builds
+run with the same arguments can be compared output for output), print the JSON line.
+
+    python bench.py --full --gpus N --steps K --warmup W
+
+also times, after the headline region, the CPU baseline ("cpu_baseline") and BASELINE.json's other configurations
+(tools/workloads.py: Deep GA on both networks, the NS-ES meta-population loop, the six-game loop, the 2-worker CPU reference
+path) and reports them under "extra", each with its own roofline / CPU baseline.  Default with --full: all of them at N = 1; at
+N > 1 the sharded ones (ga, nses, sweep: BASELINE configs 4 and 5 are defined on 4 and 8 GPUs), run over the same ranks on the
+headline engine's communicator.
 
 The ranks never import torch on the RCCL path: the engine is reached through ctypes, device synchronisation is
 hipDeviceSynchronize inside the C ABI, and the exchange, the barrier and the max / sum over ranks are RCCL calls behind
@@ -308,46 +315,29 @@ def comm_init_bounded(engine, rank, world, uid, timeout):
 def supervise():
     """N = 1 only: run the benchmark proper in a child process.  A GPU memory-access fault is raised by the HSA runtime as an
     abort of the whole process -- no exception, no JSON (the fate of round 1's driver run).  The child's breadcrumbs name the
-    stage it died in; one retry with the engine's own trace on (DNE_TRACE=1) then either yields a complete, separately timed
-    run -- reported with "attempts": 2 and the first attempt's last stage -- or a second, more detailed failure."""
-    first = None
-    for attempt in (1, 2):
-        env = dict(os.environ, DNE_BENCH_CHILD="1")
-        if attempt == 2:
-            env["DNE_TRACE"] = "1"
-        p = subprocess.Popen([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=env, stdout=subprocess.PIPE,
-                             stderr=subprocess.PIPE, text=True)
-        tail = []
+    stage it died in, and the supervisor repeats its last lines and leaves with the child's status.  Nothing is started on the
+    GPU again after such an ending: a device that has just faulted is not handed a second run; rerun by hand with the engine's
+    own trace on (DNE_TRACE=1) once the cause is understood."""
+    env = dict(os.environ, DNE_BENCH_CHILD="1")
+    p = subprocess.Popen([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=env, stdout=subprocess.PIPE,
+                         stderr=subprocess.PIPE, text=True)
+    tail = []
 
-        def pump():
-            for line in p.stderr:
-                sys.stderr.write(line); sys.stderr.flush()
-                tail.append(line.rstrip())
-                del tail[:-6]
-        t = threading.Thread(target=pump, daemon=True)
-        t.start()
-        out = p.stdout.read()
-        rc = p.wait()
-        t.join(5)
-        if rc == 0:
-            if first is not None:
-                lines = out.strip().splitlines()
-                try:
-                    d = json.loads(lines[-1])
-                    d["attempts"], d["first_attempt"] = 2, first
-                    lines[-1] = json.dumps(d)
-                    out = "\n".join(lines) + "\n"
-                except Exception:
-                    pass
-            sys.stdout.write(out); sys.stdout.flush()
-            return 0
-        if rc > 0:      # an ordinary Python failure (bad arguments, no GPU): nothing a retry would change
-            sys.stdout.write(out)
-            return rc
-        first = {"rc": rc, "stderr_tail": tail[-6:]}
-        sys.stderr.write("[bench supervisor] attempt %d ended with rc %d; last lines: %s\n" % (attempt, rc, " | ".join(tail[-3:])))
+    def pump():
+        for line in p.stderr:
+            sys.stderr.write(line); sys.stderr.flush()
+            tail.append(line.rstrip())
+            del tail[:-6]
+    t = threading.Thread(target=pump, daemon=True)
+    t.start()
+    out = p.stdout.read()
+    rc = p.wait()
+    t.join(5)
+    sys.stdout.write(out); sys.stdout.flush()
+    if rc < 0:
+        sys.stderr.write("[bench supervisor] the benchmark ended with signal %d; last lines: %s\n" % (-rc, " | ".join(tail[-3:])))
         sys.stderr.flush()
-    return rc if rc > 0 else 128 - rc
+    return rc if rc >= 0 else 128 - rc
 
 
 def _free_port():
@@ -538,6 +528,21 @@ def _gloo_allgather_bytes(buf, world):
     return out.numpy().view(buf.dtype)
 
 
+def dump_outputs(out_dir, rec, ratio, theta):
+    """--dump-outputs: what the last timed generation handed its caller -- es.es_generation's records (every pair's noise index,
+    returns, sign-returns and episode lengths, in global pair order) and update ratio, and theta after its update -- as
+    <out_dir>/<name>.npy in float32 / float64 (indices and lengths are exact in float64).  About 4 MB at pop 5000."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"theta": np.asarray(theta, np.float32),
+              "noise_idx": rec["noise_idx"].astype(np.float64),
+              "returns": rec["ret"].astype(np.float32),
+              "sign_returns": rec["aux"].astype(np.float32),
+              "lengths": rec["len"].astype(np.float64),
+              "update_ratio": np.array([ratio], np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------ one rank
 def run_rank(args):
     rank = int(os.environ.get("RANK", "0"))
@@ -650,6 +655,7 @@ def run_rank(args):
     fc_kind = 2
     fc_union_ms = 0.0
     stage = {"conv_ms": 0.0, "env_ms": 0.0, "ref_ms": 0.0, "reduce_ms": 0.0, "eval_ms": 0.0}
+    rec = ratio = None
     for _ in range(args.steps):
         crumb("generation %d eval" % gen)
         rec, ratio = es.es_generation(engine, noise.noise.size, config, n_pairs, gen, args.tslimit, EXP["optimizer"], rank, world, transport)
@@ -681,15 +687,18 @@ def run_rank(args):
     crumb("theta sha256 %s" % hashlib.sha256(theta_final.tobytes()).hexdigest())   # identical on every rank (redundant update)
     engine.check_redzones()   # raises if any kernel of the run wrote outside its device buffer
     crumb("red zones intact")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, rec, ratio, theta_final)
+        crumb("outputs of the last timed generation written to %s" % args.dump_outputs)
 
     which = [x for x in (args.extra.split(",") if args.extra not in ("", "none", "all", "default") else
                          (EXTRAS if args.extra == "all" or (args.extra == "default" and world == 1) else
-                          EXTRAS_MULTI if args.extra == "default" else ())) if x]
+                          EXTRAS_MULTI if args.extra == "default" else ())) if x] if args.full else []
     for x in which:
         if x not in EXTRAS:
             raise SystemExit("--extra: unknown workload %r (choose from %s)" % (x, ", ".join(EXTRAS)))
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:      # before the extras: their CPU legs reuse the worker count it finds
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:      # before the extras: their CPU legs reuse the worker count it finds
         crumb("cpu baseline")
         cpu = cpu_baseline(noise.noise, theta0, ref, config.noise_stdev, args.tslimit, 18)
     extra = None
@@ -835,7 +844,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile-events", action="store_true")
     ap.add_argument("--extra", default="default",
-                    help="BASELINE configs timed after the headline region: comma list of %s, or all / none; default = all at N = 1, "
+                    help="with --full: BASELINE configs timed after the headline region: comma list of %s, or all / none; default = all at N = 1, "
                          "%s at N > 1 (configs 4 / 5 are defined on 4 / 8 GPUs)" % (", ".join(EXTRAS), ",".join(EXTRAS_MULTI)))
     ap.add_argument("--extra-small", action="store_true", help="testing aid: the extra workloads at a population of 96")
     ap.add_argument("--transport", default="rccl", choices=["rccl", "gloo"],
@@ -846,10 +855,21 @@ def main():
                     help="--transport rccl: if any rank cannot build the RCCL communicator, carry the records over gloo instead of "
                          "exiting with code %d (the JSON line's comm.carrier then says gloo)" % EXIT_NO_RCCL)
     ap.add_argument("--rccl-init-timeout", type=int, default=int(os.environ.get("DNE_RCCL_INIT_TIMEOUT", "180")))
-    ap.add_argument("--no-supervisor", action="store_true", help="N = 1: run in this process (no child, no retry)")
+    ap.add_argument("--no-supervisor", action="store_true", help="N = 1: run in this process (no child process)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline region also time what the headline figure does not need: the CPU baseline (unless "
+                         "--no-cpu-baseline) and the extra workloads chosen by --extra.  Without it a run sets up, warms up, times "
+                         "--steps generations and prints the JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed generation computed (theta after the update, every pair's noise index, returns, "
+                         "sign-returns and lengths, the update ratio) as DIR/<name>.npy in float32 / float64")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step (--steps >= 1)")
+    if not args.full and args.extra not in ("default", "none", ""):
+        ap.error("--extra %s: the extra workloads run only with --full" % args.extra)
     launched = "WORLD_SIZE" in os.environ or os.environ.get("DNE_BENCH_CHILD")
     if not launched:
         if args.gpus > 1:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Golden fixtures from the REAL reference for the widened rows (transport wire format, GPU-tree genomes and schedules).
-Runs only in the build container (needs /root/reference); writes tests/golden/reference_wire.npz, which is committed.
+Needs a checkout of the reference at REF; writes tests/golden/reference_wire.npz and reference_wire_types.json, which are committed.
 
 Imported from the reference, unmodified (third-party modules absent here -- redis, tensorflow, the gym_tensorflow native op --
 are stubbed ONLY so that the modules import; no value below comes from a stub):
@@ -99,5 +99,21 @@ def main():
     print("wrote", path, "keys:", len(out), "bytes:", os.path.getsize(path))
 
 
+def write_types():
+    """The reference's wire types as its modules define them -- namedtuples: module path, class name, field order -- so that a test
+    without the reference can rebuild what its unpickler resolves (tests/test_transport_cpu.py)."""
+    import json
+    out = {}
+    for cls in (res.Task, res.Result, res.Config, rga.GATask):
+        assert issubclass(cls, tuple) and hasattr(cls, "_fields")
+        out.setdefault(cls.__module__, {})[cls.__name__] = list(cls._fields)
+    path = os.path.join(HERE, "reference_wire_types.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print("wrote", path)
+
+
 if __name__ == "__main__":
     main()
+    write_types()

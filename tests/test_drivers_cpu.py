@@ -291,7 +291,7 @@ def test_gpu_tree_es_first_update_is_the_reference_formula(oracle, tmp_path):
     assert st.tslimit == 8 and not st.adaptive_tslimit
 
 
-def test_gpu_tree_es_sgd_is_the_engine_sgd_at_a_rescaled_stepsize():
+def test_gpu_tree_es_sgd_is_the_engine_sgd_at_a_rescaled_stepsize(tmp_path):
     from dne_hip import es_gpu
     assert es_gpu.engine_optimizer({"type": "sgd", "args": {"stepsize": 0.01, "momentum": 0.9}})[:3] == ("sgd", pytest.approx(0.1), 0.9)
     assert es_gpu.engine_optimizer({"type": "adam", "args": {"stepsize": 0.01}}) == ("adam", 0.01, 0.9, 0.999, 1e-08)
@@ -302,4 +302,4 @@ def test_gpu_tree_es_sgd_is_the_engine_sgd_at_a_rescaled_stepsize():
         u = mu * u + (1 - mu) * g; th_b -= lr / (1 - mu) * u
     assert abs(th_a - th_b) < 1e-12
     with pytest.raises(NotImplementedError):
-        es_gpu.main("/tmp/_dne_es_gpu_nolog", engine=object(), noise=object(), load_from="x", population_size=2)
+        es_gpu.main(str(tmp_path / "nolog"), engine=object(), noise=object(), load_from="x", population_size=2)

@@ -369,6 +369,32 @@ def test_two_ranks_one_gpu_bit_identical_theta():
     assert len(sha1) == 1 and d1["n_gpus"] == 1 and "roofline" in d1 and d1["comm"]["carrier"].startswith("none")
 
 
+def test_plain_run_dumps_the_last_generation(tmp_path):
+    """A plain run (no --full) times the headline alone: no CPU baseline, no extra workloads.  --dump-outputs writes what the last
+    timed generation computed -- theta after its update (the digest the run prints) and the generation's records in pair order --
+    and a second run with the same arguments writes the same arrays, bit for bit."""
+    import hashlib
+    import re
+    import sys
+    b = os.path.join(ROOT, "bench.py")
+    small = [a for a in SMALL if a != "--no-cpu-baseline"]
+    got = []
+    for run in ("a", "b"):
+        d, err = _bench([sys.executable, b, "--dump-outputs", str(tmp_path / run)] + small)
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert "cpu_baseline" not in d and "extra" not in d and "extra:" not in err and "cpu baseline" not in err
+        arrays = {n: np.load(str(tmp_path / run / (n + ".npy"))) for n in ("theta", "noise_idx", "returns", "sign_returns", "lengths", "update_ratio")}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert arrays["theta"].dtype == np.float32 and arrays["theta"].size == 1009058
+        assert arrays["noise_idx"].shape == (48,) and arrays["returns"].shape == arrays["lengths"].shape == (48, 2)
+        assert arrays["lengths"].min() >= 1 and arrays["lengths"].max() <= 40 and np.array_equal(arrays["lengths"], np.rint(arrays["lengths"]))
+        sha = re.findall(r"theta sha256 ([0-9a-f]{64})", err)
+        assert sha == [hashlib.sha256(arrays["theta"].tobytes()).hexdigest()], sha
+        got.append(arrays)
+    for n in got[0]:
+        assert np.array_equal(got[0][n], got[1][n]), n
+
+
 def test_rccl_needs_one_device_per_rank():
     """python bench.py --gpus 2 on this one-GPU box: a clear refusal (RCCL takes one rank per device), not a hang"""
     import subprocess
@@ -387,7 +413,7 @@ def test_extra_workloads_plumbing():
     import sys
     b = os.path.join(ROOT, "bench.py")
     small = ["--steps", "1", "--warmup", "0", "--pop", "96", "--tslimit", "40", "--noise-count", "8000000", "--extra-small"]
-    d1, _ = _bench([sys.executable, b, "--extra", "all"] + small, timeout=1400)
+    d1, _ = _bench([sys.executable, b, "--full", "--extra", "all"] + small, timeout=1400)
     ex = d1["extra"]
     assert sorted(ex) == ["config1", "ga", "ga_large", "nses", "predicted_n2", "shares", "sweep"], ex
     # an N = 2 launch rehearsed on this GPU (tools/workloads.py:simulate_ranks): the sharded generations end on the theta of the one-rank
@@ -400,7 +426,7 @@ def test_extra_workloads_plumbing():
     assert ex["ga"]["cpu_baseline"]["value"] > 0 and ex["config1"]["cores"] == 2 and ex["config1"]["value"] > 0
     assert [g["n_actions"] for g in ex["sweep"]["games"]] == [18, 14]
     assert "cpu_baseline" in d1 and d1["cpu_baseline"]["kind"] == "port"
-    d2, _ = _bench([sys.executable, b, "--gpus", "2", "--single-device", "--transport", "gloo", "--extra", "ga,nses,sweep",
+    d2, _ = _bench([sys.executable, b, "--full", "--gpus", "2", "--single-device", "--transport", "gloo", "--extra", "ga,nses,sweep",
                     "--no-cpu-baseline"] + small, timeout=1400)
     ex2 = d2["extra"]
     assert sorted(ex2) == ["ga", "nses", "sweep"] and all("error" not in v and v["n_gpus"] == 2 for v in ex2.values()), ex2

@@ -1,7 +1,7 @@
 """Policy snapshots in the reference's HDF5 container (es_distributed/policies.py:49-67) written / read through libhdf5
 directly (dne_hip/h5lite.py).  Checked three ways: h5dump's view of a file we wrote against the layout h5py gives the
-reference (recorded below from `h5dump -H` of the snapshot the reference ships), a read of that reference-written file when
-/root/reference is present, and round trips through Policy.save / Load / initialize_from."""
+reference (recorded below from `h5dump -H` of the snapshot the reference ships), a read of that reference-written file (stored
+as tests/golden/reference_snapshot_parent_0097.h5), and round trips through Policy.save / Load / initialize_from."""
 import os
 import pickle
 import shutil
@@ -17,7 +17,8 @@ from dne_hip import h5lite, policies  # noqa: E402
 
 pytestmark = pytest.mark.skipif(not h5lite.available(), reason="no libhdf5 on this machine")
 
-REF_SNAPSHOT = "/root/reference/visual_inspector/sample_data/mujoco/final_xy_bc/snapshots/snapshot_gen_0097/snapshot_parent_0097.h5"
+# the reference's visual_inspector/sample_data/mujoco/final_xy_bc/snapshots/snapshot_gen_0097/snapshot_parent_0097.h5, byte for byte
+REF_SNAPSHOT = os.path.join(ROOT, "tests", "golden", "reference_snapshot_parent_0097.h5")
 
 # `h5dump -H` of REF_SNAPSHOT (written by the reference's Policy.save through h5py): the two root attributes
 REF_ATTR_LAYOUT = '''   ATTRIBUTE "args_and_kwargs" {
@@ -88,7 +89,6 @@ def test_layout_matches_h5py_written_reference_file(tmp_path):
     assert np.allclose(got, want, rtol=1e-5, atol=1e-7)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SNAPSHOT), reason="the reference's sample snapshot is not on this machine")
 def test_reads_reference_written_snapshot():
     h5dump = _h5dump()
     if h5dump is not None:

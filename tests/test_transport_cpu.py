@@ -1,5 +1,6 @@
 """CPU: the Redis carrier of dne_hip/dist.py (es_distributed/dist.py:62-192) against a fake Redis-protocol server, and
-the pickled wire format against the REAL reference modules (imported from /root/reference where that tree exists)."""
+the pickled wire format against the REAL reference modules' payloads and type definitions (recorded from the reference by
+tests/golden/make_wire_golden.py into reference_wire.npz and reference_wire_types.json)."""
 import os
 import pickle
 import subprocess
@@ -10,7 +11,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
 def _exp(pop=8, tslimit=12):
@@ -159,41 +160,46 @@ def test_relay_forwards_its_batch_when_the_list_was_trimmed_under_it():
 
 
 _REF_SIDE = r'''
-import pickle, sys, types
+import json, pickle, sys, types
+from collections import namedtuple
 import numpy as np
-sys.path.insert(0, %(ref)r)
-sys.modules["redis"] = types.ModuleType("redis")            # import-only stubs, as in tests/golden/make_golden.py
-sys.modules["tensorflow"] = types.ModuleType("tensorflow")
+# the reference's wire types as es_distributed/es.py:12-23 and ga.py:4 define them -- namedtuples, resolved by module path, class
+# name and field order -- rebuilt from what tests/golden/make_wire_golden.py recorded of the real modules
+pkg = types.ModuleType("es_distributed"); pkg.__path__ = []
+sys.modules["es_distributed"] = pkg
+for mod_name, classes in json.load(open(%(types)r)).items():
+    mod = types.ModuleType(mod_name)
+    for cls_name, fields in classes.items():
+        cls = namedtuple(cls_name, fields)
+        cls.__module__ = mod_name
+        setattr(mod, cls_name, cls)
+    sys.modules[mod_name] = mod
+    setattr(pkg, mod_name.split(".")[1], mod)
 import es_distributed.es as res
 import es_distributed.ga as rga
 assert "dne_hip" not in sys.modules
-mode, path = sys.argv[1], sys.argv[2]
-if mode == "make":      # what a reference master / worker puts on the wire (dist.py:19-20)
-    task = res.Task(params=np.arange(5, dtype=np.float32), ob_mean=None, ob_std=None, ref_batch=[np.zeros((84, 84, 4), np.float32)], timestep_limit=7)
-    gtask = rga.GATask(params=np.ones(3, np.float32), population=[[1, 2], [3]], ob_mean=None, ob_std=None, timestep_limit=9)
-    result = res.Result(worker_id=3, noise_inds_n=np.array([11, 12]), returns_n2=np.ones((2, 2), np.float32),
-                        signreturns_n2=np.ones((2, 2), np.float32), lengths_n2=np.ones((2, 2), np.int32), eval_return=None,
-                        eval_length=None, ob_sum=None, ob_sumsq=None, ob_count=0)
-    pickle.dump([pickle.dumps(x, protocol=-1) for x in (task, gtask, (4, result))], open(path, "wb"))
-else:                   # what a reference master / worker reads
-    task, gtask, (tid, result), cfg = [pickle.loads(b) for b in pickle.load(open(path, "rb"))]
-    assert type(task) is res.Task and type(gtask) is rga.GATask and type(result) is res.Result and type(cfg) is res.Config
-    assert tid == 9 and result.returns_n2.dtype == np.float32 and result.lengths_n2.shape == (2, 2) and task.timestep_limit == 21
-    assert isinstance(tid, int) and isinstance(result, res.Result)                    # es.py:232 master-side assert
-    assert gtask.population == [[5, 6, 7]] and cfg.noise_stdev == 0.02
-    print("reference side ok")
+path = sys.argv[1]
+# what a reference master / worker reads
+task, gtask, (tid, result), cfg = [pickle.loads(b) for b in pickle.load(open(path, "rb"))]
+assert type(task) is res.Task and type(gtask) is rga.GATask and type(result) is res.Result and type(cfg) is res.Config
+assert tid == 9 and result.returns_n2.dtype == np.float32 and result.lengths_n2.shape == (2, 2) and task.timestep_limit == 21
+assert isinstance(tid, int) and isinstance(result, res.Result)                    # es.py:232 master-side assert
+assert gtask.population == [[5, 6, 7]] and cfg.noise_stdev == 0.02
+print("reference side ok")
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree exists only in the build container")
 def test_pickles_interchange_with_the_reference(tmp_path):
     """A reference master must be able to unpickle a HIP worker's (task_id, Result), and a HIP worker a reference
     master's Task (es_distributed/dist.py:19-24; wire types es.py:12-23, ga.py:4): the namedtuples travel by module path."""
     script = tmp_path / "ref_side.py"
-    script.write_text(_REF_SIDE % {"ref": REF})
-    # reference -> dne_hip (this process has no es_distributed: the stand-in modules resolve the names)
+    script.write_text(_REF_SIDE % {"types": os.path.join(GOLDEN, "reference_wire_types.json")})
+    # reference -> dne_hip (this process has no es_distributed: the stand-in modules resolve the names): the payloads a reference
+    # master / worker put on the wire (dist.py:19-20) for a Task, a GATask and a (task_id, Result), pickled by the reference itself
+    wire = np.load(os.path.join(GOLDEN, "reference_wire.npz"))
     f1 = str(tmp_path / "from_ref.pkl")
-    subprocess.run([sys.executable, str(script), "make", f1], check=True)
+    with open(f1, "wb") as f:
+        pickle.dump([wire[k].tobytes() for k in ("wire_task", "wire_gatask", "wire_result")], f)
     code = r'''
 import pickle, sys
 sys.path.insert(0, %r)
@@ -217,7 +223,7 @@ print("hip side ok")
     r = subprocess.run([sys.executable, "-c", code], check=True, capture_output=True, text=True)
     assert "hip side ok" in r.stdout
     # dne_hip -> reference
-    r = subprocess.run([sys.executable, str(script), "read", str(tmp_path / "from_hip.pkl")], check=True, capture_output=True, text=True)
+    r = subprocess.run([sys.executable, str(script), str(tmp_path / "from_hip.pkl")], check=True, capture_output=True, text=True)
     assert "reference side ok" in r.stdout
 
 

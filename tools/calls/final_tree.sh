@@ -7,7 +7,7 @@ timeout 1500 python -m pytest tests -m gpu -x -q --durations=6 > $O/pytest_gpu.l
 [ $rc -ne 0 ] && exit 1
 timeout 300 python -c "import __graft_entry__ as g; g.build(); g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log | cut -c1-200
 cd /tmp; export TMPDIR=/tmp
-python "$R/bench.py" --steps 20 --warmup 5 > "$O/bench_driver_cmd.json" 2> "$O/bench_driver_cmd.err"
+python "$R/bench.py" --full --steps 20 --warmup 5 > "$O/bench_driver_cmd.json" 2> "$O/bench_driver_cmd.err"
 python "$R/bench.py" --extra none > "$O/bench_default.json" 2> "$O/bench_default.err"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -o bench -- python "$R/bench.py" --no-cpu-baseline --no-supervisor --extra none > "$O/bench_profiled.json" 2> "$O/prof.err"
 cp "$(find "$O/stats" -name '*kernel_stats.csv' | head -1)" "$O/bench_kernel_stats.csv" 2>/dev/null; rm -rf "$O/stats"

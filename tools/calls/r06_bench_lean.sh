@@ -5,7 +5,7 @@
 TAG=${1:-r06d}
 R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd $R
-( time python bench.py --steps 20 --warmup 5 > $O/bench_full.json 2> $O/bench_full.err ) 2> $O/bench_full.time; tail -3 $O/bench_full.time
+( time python bench.py --full --steps 20 --warmup 5 > $O/bench_full.json 2> $O/bench_full.err ) 2> $O/bench_full.time; tail -3 $O/bench_full.time
 python - <<PY
 import json
 d = json.loads(open("$O/bench_full.json").read().strip().splitlines()[-1])

@@ -46,7 +46,7 @@ for leg in ga ga_large; do
 done
 ( cd "$R" && python tools/summarize_pmc_ga.py "$O/pmc_ga" "$PFX" > "$O/pmc_ga_summary.log" 2>&1; cp "profiles/${PFX}_pmc_ga.json" "$O/" 2>/dev/null; cat "$O/pmc_ga_summary.log" )
 cd /tmp
-python "$R/bench.py" --steps 20 --warmup 5 > "$O/bench_driver_cmd.json" 2> "$O/bench_driver_cmd.err"
+python "$R/bench.py" --full --steps 20 --warmup 5 > "$O/bench_driver_cmd.json" 2> "$O/bench_driver_cmd.err"
 python "$R/bench.py" --extra none > "$O/bench_default.json" 2> "$O/bench_default.err"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -o bench -- python "$R/bench.py" --no-cpu-baseline --no-supervisor --extra none > "$O/bench_profiled.json" 2> "$O/prof.err"
 cp "$(find "$O/stats" -name '*kernel_stats.csv' | head -1)" "$O/bench_kernel_stats.csv" 2>/dev/null; rm -rf "$O/stats"
