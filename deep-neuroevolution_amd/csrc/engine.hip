@@ -286,7 +286,7 @@ __device__ __forceinline__ void head_body(HeadLds<RENDER> &H, const FwdArgs &A, 
             wth[a] = a < nact ? wb[a] : 0.0f;
             wep[a] = a < nact ? we[a] : 0.0f;
         }
-        fbt = base[L.fcb + tid]; fbe = noise_slice[L.fcb + tid];
+        fbt = opt_bias(L.fcb, base[opt_off(L.fcb) + tid]); fbe = opt_bias(L.fcb, noise_slice[opt_off(L.fcb) + tid]);
         if (HAS_BN) { s3 = A.bn[(size_t)m * 608 + 96 + tid]; h3 = A.bn[(size_t)m * 608 + 352 + tid]; }
     }
     if constexpr (RENDER) synth_load_tables(s, E.T);
@@ -811,6 +811,10 @@ struct DeviceGuard {
     ~DeviceGuard() { if (prev >= 0) hipSetDevice(prev); }
 };
 
+// ES-like kinds: ESAtariPolicy and the GPU tree's ModelVirtualBN -- the same network, virtual batch norm over a reference batch, antithetic
+// pairs over one theta, the ES reduce and optimizer; they differ only in the flat layout (make_layout)
+static inline bool es_like(int kind) { return kind == DNE_KIND_ES || kind == DNE_KIND_ES_VBN; }
+
 static void make_layout(int kind, int nact, Layout *L) {
     int o = 0;
     memset(L, 0, sizeof(*L));
@@ -821,6 +825,12 @@ static void make_layout(int kind, int nact, Layout *L) {
         L->c2w = take(8192); L->c2b = take(32); L->bn2b = take(32); L->bn2g = take(32);
         L->fcw = take(3872 * 256); L->fcb = take(256); L->bn3b = take(256); L->bn3g = take(256);
         L->ow = take(256 * nact); L->ob = take(nact);
+    } else if (kind == DNE_KIND_ES_VBN) {   // models/batchnorm.py:52-123, creation order (base.py:35-44): w, then BatchNorm/b
+        L->c1w = take(4096); L->bn1b = take(16);
+        L->c2w = take(8192); L->bn2b = take(32);
+        L->fcw = take(3872 * 256); L->bn3b = take(256);
+        L->ow = take(256 * nact); L->ob = take(nact);
+        L->c1b = L->c2b = L->fcb = L->bn1g = L->bn2g = L->bn3g = -1;   // absent: +0.0f biases, 1.0f gammas (opt_bias / opt_gamma)
     } else if (kind == DNE_KIND_GA_LARGE) {   // models/dqn.py:39-47: variables in creation order (models/base.py:35-41)
         L->c1w = take(8 * 8 * 4 * 32); L->c1b = take(32); L->c2w = take(4 * 4 * 32 * 64); L->c2b = take(64);
         L->c3w = take(3 * 3 * 64 * 64); L->c3b = take(64);
@@ -945,7 +955,7 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         return -1;
     }
     if (cfg->max_members <= 0 || cfg->n_actions <= 1 || cfg->n_actions > 32 ||
-        (cfg->policy_kind != DNE_KIND_ES && cfg->policy_kind != DNE_KIND_GA && cfg->policy_kind != DNE_KIND_GA_LARGE)) {
+        (!es_like(cfg->policy_kind) && cfg->policy_kind != DNE_KIND_GA && cfg->policy_kind != DNE_KIND_GA_LARGE)) {
         g_create_error = "dne_create: bad config";
         return -1;
     }
@@ -1028,7 +1038,7 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
     // measured (tools/ga_lockstep_profile.py, tools/ab_inproc.py --pairs 312 / 625): Deep-GA children 97 .. 320
     // alive, two windows, a grid of 512 workgroups at wave priority 3; ES pairs 97 .. 450 alive, three windows, the whole launch
     // resident, no priority (its chain of small kernels must not starve); above those widths the streaming kernels win
-    if (cfg->policy_kind == DNE_KIND_ES) { h->fc_sub = 2; h->fc_sub_max = 450; h->fc_sub_nsub = 3; h->fc_sub_grid = 1 << 20; h->fc_sub_prio = 0; }
+    if (es_like(cfg->policy_kind)) { h->fc_sub = 2; h->fc_sub_max = 450; h->fc_sub_nsub = 3; h->fc_sub_grid = 1 << 20; h->fc_sub_prio = 0; }
     else { h->fc_sub = 1; h->fc_sub_max = 320; h->fc_sub_nsub = 4; h->fc_sub_grid = 512; h->fc_sub_prio = 0; }   // round 6: four windows at wave priority 0 (was two at 3): Deep GA 1.02-1.05 vs 0.98-1.00 M env-steps/s same-box; five / six windows 0.91-0.94
     env_int("DNE_FC_SUB", 0, 2, &h->fc_sub);
     env_int("DNE_FC_SUB_MIN", 1, 1 << 30, &h->fc_sub_min);
@@ -1052,7 +1062,7 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
     for (int s = 1; s < 4; s++) { hipStream_t st; CH(hipStreamCreate(&st)); h->sub_streams.push_back(st); }   // more than four windows measured slower (round 3, 5 / 6 / 8 at full width: +7.5 / +5.4 / +7.2 %; round 4 with one k_fc_duo workgroup per CU: +8.4 / +5.9 / +4.4 %)
     make_layout(cfg->policy_kind, cfg->n_actions, &h->L);
     h->M = cfg->max_members;
-    h->F = cfg->policy_kind == DNE_KIND_ES ? (cfg->ref_count > 0 ? cfg->ref_count : 128) : 0;
+    h->F = es_like(cfg->policy_kind) ? (cfg->ref_count > 0 ? cfg->ref_count : 128) : 0;
     if (h->F % 8) { h->fail("ref_count must be a multiple of 8"); return bail(0); }
     h->ref_chunk = cfg->ref_chunk > 0 ? cfg->ref_chunk : 512;
     h->ref_chunk = std::min(h->ref_chunk, h->M);
@@ -1085,18 +1095,18 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
     CH(h->alloc(&h->len, M, "len")); CH(h->alloc(&h->done, M, "done")); CH(h->alloc(&h->action, M, "action")); CH(h->alloc(&h->seeds, M, "seeds")); CH(h->alloc(&h->stepped, M, "stepped"));
     CH(hipMemset(h->done, 0, M * sizeof(int32_t))); CH(hipMemset(h->len, 0, M * sizeof(int32_t)));
     h->large = cfg->policy_kind == DNE_KIND_GA_LARGE;
-    h->ga_materialize = cfg->policy_kind == DNE_KIND_ES ? 0 : 1;
+    h->ga_materialize = es_like(cfg->policy_kind) ? 0 : 1;
     env_int("DNE_GA_MATERIALIZE", 0, 1, &h->ga_materialize);
     env_int("DNE_LFC_COLS_MAX", 0, 1 << 20, &h->lfc_cols_max);
     env_int("DNE_LFC_PAD", 0, 2, &h->lfc_pad);
     if (h->large) h->fc_rb = 8;      // the streamed LargeModel fc: 8-row batches measured 8 % faster than 4
     env_int("DNE_FC_RB", 2, 8, &h->fc_rb);
-    if (cfg->policy_kind == DNE_KIND_ES) h->ga_materialize = 0;   // ES members are antithetic pairs over one theta: nothing to write out
+    if (es_like(cfg->policy_kind)) h->ga_materialize = 0;   // ES members are antithetic pairs over one theta: nothing to write out
     if (h->large) { CH(h->alloc(&h->y1, M * 14112, "y1")); CH(h->alloc(&h->y2, M * 7744, "y2")); CH(h->alloc(&h->y3, M * 7744, "y3")); CH(h->alloc(&h->y3t, M * 512, "y3t")); }
     else { CH(h->alloc(&h->y1, M * 7056, "y1")); CH(h->alloc(&h->y2, M * 3872 + 64, "y2"));   /* (+ 64: k_fc_ring fetches the eight activations behind a slice's end and never uses them) */ CH(h->alloc(&h->y3, M * 256, "y3")); CH(h->alloc(&h->y3t, M * 4 * 256, "y3t")); }
     CH(h->alloc(&h->unit_order, M * 4, "unit_order"));
     if (!h->large && h->fc_sub) CH(h->alloc(&h->y3s, M * 32 * 256, "y3s"));
-    if (!h->large && h->ring_on && cfg->policy_kind == DNE_KIND_ES) CH(h->alloc(&h->theta_perm, (size_t)(3872 + 16) * 256, "theta_perm"));
+    if (!h->large && h->ring_on && es_like(cfg->policy_kind)) CH(h->alloc(&h->theta_perm, (size_t)(3872 + 16) * 256, "theta_perm"));
     if (cfg->n_actions > SPEC_ACTIONS - 2) h->spec_max = 0;
     if (h->spec_max > 0) {   // candidate outcomes of the speculative tail: [list position][action]
         const size_t rows = (size_t)h->spec_max * SPEC_ACTIONS;
@@ -1116,7 +1126,7 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
     CH(h->alloc(&h->list_a, M, "list_a")); CH(h->alloc(&h->list_b, M, "list_b")); CH(h->alloc(&h->count_dev, 8 + TT_MAX, "count_dev"));
     CH(hipHostMalloc((void **)&h->count_host, (8 + TT_MAX) * sizeof(int), hipHostMallocDefault));
     if (cfg->record_bc) {
-        h->bc_bytes = cfg->policy_kind == DNE_KIND_ES && !cfg->bc_final_only ? M * (size_t)std::max(cfg->bc_max_steps, 1) * 128 : M * 128;
+        h->bc_bytes = es_like(cfg->policy_kind) && !cfg->bc_final_only ? M * (size_t)std::max(cfg->bc_max_steps, 1) * 128 : M * 128;
         CH(h->alloc(&h->bc, h->bc_bytes, "bc"));
         CH(hipMemset(h->bc, 0, h->bc_bytes));   // the emulator writes the RAM_LIVE bytes of a row; the other bytes of the 128 stay zero for good
     }
@@ -1314,7 +1324,7 @@ extern "C" int dne_get_theta(dne_handle *h, int slot, float *out, size_t n) {
 
 extern "C" int dne_set_ref_batch(dne_handle *h, const uint8_t *ref, int count) {
     DeviceGuard dg(h);
-    if (h->L.kind != DNE_KIND_ES) return h->fail("reference batch is an ESAtariPolicy concept");
+    if (!es_like(h->L.kind)) return h->fail("reference batch is an ESAtariPolicy concept");
     if (count != h->F) return h->fail("dne_set_ref_batch: engine was created for %d reference frames, got %d", h->F, count);
     HCHECK(h, hipMemcpy(h->ref, ref, (size_t)count * OB_BYTES, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_ref_to_float, dim3((count * RF_FRAME + 255) / 256), dim3(256), 0, h->stream, (const uint8_t *)h->ref, count, h->ref_f32);
@@ -1459,7 +1469,7 @@ extern "C" int dne_set_members(dne_handle *h, int n, const int32_t *slot, const 
 
 // policies.py:399: the reference batch through every member's perturbed network -> per-member BN scale/shift
 static int ref_pass(dne_handle *h, int n) {
-    if (h->L.kind != DNE_KIND_ES) return 0;
+    if (!es_like(h->L.kind)) return 0;
     if (!h->ref_set) return h->fail("reference batch not set (dne_set_ref_batch)");
     const int F = h->F;
     const FwdArgs A = h->fwd(false);
@@ -1566,7 +1576,7 @@ extern "C" int dne_debug_duo_ticks(dne_handle *h, long long *ticks, long long *p
 extern "C" int dne_ref_pass(dne_handle *h, int n) {
     DeviceGuard dg(h);
     if (check_n(h, n)) return -1;
-    if (h->L.kind != DNE_KIND_ES) return h->fail("dne_ref_pass: GAAtariPolicy has no reference batch");
+    if (!es_like(h->L.kind)) return h->fail("dne_ref_pass: GAAtariPolicy has no reference batch");
     if (ref_pass(h, n)) return -1;
     HCHECK(h, hipStreamSynchronize(h->stream));
     return 0;
@@ -1585,7 +1595,7 @@ extern "C" int dne_get_bn(dne_handle *h, int n, float *out) {
 extern "C" int dne_get_bn_moments(dne_handle *h, int n, float *out) {
     DeviceGuard dg(h);
     if (check_n(h, n)) return -1;
-    if (h->L.kind != DNE_KIND_ES) return h->fail("dne_get_bn_moments: GAAtariPolicy has no batch norm");
+    if (!es_like(h->L.kind)) return h->fail("dne_get_bn_moments: GAAtariPolicy has no batch norm");
     HCHECK(h, hipStreamSynchronize(h->stream));
     HCHECK(h, hipMemcpy(out, h->bn_mom, (size_t)n * 608 * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
@@ -1609,7 +1619,7 @@ static void launch_forward(dne_handle *h, const int *list, int count, int gsize,
         }
         return;
     }
-    const bool es = h->L.kind == DNE_KIND_ES;
+    const bool es = es_like(h->L.kind);
     const int items = count * gsize;
     // few members left: several workgroups per member (conv1: 28 position tiles over 4 or 7 workgroups; conv2: 8 over 2 or 4)
     const int s1 = items <= h->conv_split_max ? 7 : items <= h->conv_split_mid ? 4 : 1, s2 = items <= h->conv_split_max ? 4 : items <= 2 * h->conv_split_mid ? 2 : 1;
@@ -1643,7 +1653,7 @@ static void launch_fc(dne_handle *h, const int *list, int count, int gsize, floa
     // inside an evaluation (no logits requested) groups whose members are all done are skipped: they stay in the list until
     // the next compaction, and streaming their weights would be wasted bandwidth
     const FwdArgs A = h->fwd(logits == nullptr);
-    const bool es = h->L.kind == DNE_KIND_ES;
+    const bool es = es_like(h->L.kind);
     if (h->large) {   // LargeModel: streamed 7744 x 512 fc (two 256-column halves per member), then relu + output layer + argmax
         const dim3 lg(std::min(2 * count, 2 * h->fc_grid));
         if (count <= h->lfc_cols_max) {   // few members: eight workgroups each
@@ -1778,7 +1788,7 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
     if (bc_out && !h->bc) return h->fail("behaviour characterisations requested but the engine was created with record_bc = 0");
     const bool prof = h->cfg.profile_events != 0;
     // record_bc engines always record (the trajectories feed dne_novelty_batch on the device); bc_out only controls the download
-    const int bc_mode = h->bc ? (h->L.kind == DNE_KIND_ES && !h->cfg.bc_final_only ? 1 : 2) : 0;
+    const int bc_mode = h->bc ? (es_like(h->L.kind) && !h->cfg.bc_final_only ? 1 : 2) : 0;
     // rows past an episode's length are never read on the device (dne_novelty_batch takes the lengths); zero them only
     // when the whole buffer is about to be downloaded
     if (bc_mode == 1 && bc_out) HCHECK(h, hipMemsetAsync(h->bc, 0, (size_t)n * h->cfg.bc_max_steps * 128, h->stream));
@@ -1807,7 +1817,7 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
     // the sub-slice fc's range: GA children written out (plain rows), optionally ES pairs (DNE_FC_SUB=2); never the LargeModel
     auto sub_regime = [&](int total) {
         if (h->large || !h->y3s || total < h->fc_sub_min || total > h->fc_sub_max) return false;
-        if (h->L.kind == DNE_KIND_ES) return h->fc_sub >= 2 && gsize == 2 && total < h->fc_duo_min;
+        if (es_like(h->L.kind)) return h->fc_sub >= 2 && gsize == 2 && total < h->fc_duo_min;
         return h->fc_sub >= 1 && gsize == 1 && h->members_materialized;
     };
     auto pick_nsub = [&](int total) {
@@ -1853,14 +1863,14 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
     hipEvent_t last_fc = nullptr;
     size_t fc_ring_pos = 0;
     // the profiled ("full") launches are one kernel: k_fc2 when this evaluation starts wide enough to use it, else k_fc
-    const bool fc2_eval = h->fc_pairs == 2 && gsize == 2 && h->L.kind == DNE_KIND_ES && h->uniform_base && groups >= h->fc2_min_total;
-    const bool duo_eval = !h->large && h->fc_duo && (h->L.kind == DNE_KIND_ES && gsize == 2) && groups >= h->fc_duo_min;
+    const bool fc2_eval = h->fc_pairs == 2 && gsize == 2 && es_like(h->L.kind) && h->uniform_base && groups >= h->fc2_min_total;
+    const bool duo_eval = !h->large && h->fc_duo && (es_like(h->L.kind) && gsize == 2) && groups >= h->fc_duo_min;
     // an evaluation that starts wide enough for k_fc_ring: its bracketed ("full") launches are that kernel's only -- one kernel per
     // roofline line; the k_fc_duo launches of its thinner lock-steps (DNE_FC_DUO_MIN .. DNE_DUO_SOLO_BELOW pairs) are not bracketed
     // the ring's range: pairs as dense in their stretch of the table as DNE_DUO_SOLO_BELOW (1500) pairs over the whole table, and enough of them to
     // fill the chip (DNE_RING_MIN) -- at one GPU "1500 of 2500 active", on a rank of two with its own half of the table "1000 of 1250"
     auto ring_dense = [&](int t) { return (double)t * h->dense_scale >= (double)h->duo_solo_below && t >= h->ring_min; };
-    const bool ring_eval = duo_eval && h->L.kind == DNE_KIND_ES && gsize == 2 && h->theta_perm && h->antithetic_slot0 && h->duo_sweep &&
+    const bool ring_eval = duo_eval && es_like(h->L.kind) && gsize == 2 && h->theta_perm && h->antithetic_slot0 && h->duo_sweep &&
                            (h->ring_on > 1 || ring_dense(groups)) && (ring_dense(groups) || h->duo_sweep > 1);
     // the ring's DMA source: the table scaled by this evaluation's sigma (k_fc_ring<true>), made once per (table, sigma)
     h->ring_pre_now = false;
@@ -1885,12 +1895,12 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
         const int burst = std::min(total <= h->fc_tail_max ? h->burst_tail : h->burst, tslimit - t);   // lock-steps until the next compaction
         const int nsub = pick_nsub(total);
         h->fc2_now = h->fc_pairs == 2 && total >= h->fc2_min_total;
-        h->duo_now = !h->large && h->fc_duo && (h->L.kind == DNE_KIND_ES && gsize == 2) && total >= h->fc_duo_min &&
+        h->duo_now = !h->large && h->fc_duo && (es_like(h->L.kind) && gsize == 2) && total >= h->fc_duo_min &&
                      (size_t)4 * ((total + nsub - 1) / nsub) * sizeof(long long) <= 160 * 1024;   // k_unit_order ranks a window's keys in LDS
         h->duo_solo_now = total < h->duo_solo_below;
         h->sub_now = sub_regime(total);
         if (h->sub_now) h->duo_now = h->fc2_now = false;
-        h->ring_now = h->duo_now && h->L.kind == DNE_KIND_ES && gsize == 2 && h->theta_perm && h->antithetic_slot0 &&
+        h->ring_now = h->duo_now && es_like(h->L.kind) && gsize == 2 && h->theta_perm && h->antithetic_slot0 &&
                       h->duo_sweep && (ring_dense(total) || h->duo_sweep > 1) && (h->ring_on > 1 || ring_dense(total));
         if (h->duo_now)   // the list only changes at a compaction: rank each window's units by table address once per burst
             for (int s = 0; s < nsub; s++) {
@@ -1919,7 +1929,7 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
                 if (spec) {
                     const int items = cnt * gsize, nact = h->cfg.n_actions, nb = h->spec_bands;
                     const FwdArgs A = h->fwd(true);
-                    const bool es = h->L.kind == DNE_KIND_ES;
+                    const bool es = es_like(h->L.kind);
                     const int emu_blocks = (items * nact + 255) / 256;
                     if (st == 0 || !h->spec_conv1) {   // no conv1 candidates from the previous lock-step (a new burst = a new list)
                         hipLaunchKernelGGL(k_conv1_spec, dim3(items * 7 + emu_blocks), dim3(256), 0, sst, A, E, lst, gsize, h->y1, 7, items * 7, items, nact);
@@ -1966,7 +1976,7 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
                     int nb = h->render_bands;
                     while (nb > 1 && items * nb > h->render_wg_max) nb /= 2;
 #define TS(BN, R, THR) hipLaunchKernelGGL((k_tail_step<BN, R>), dim3(items), dim3(THR), 0, sst, A, E, lst, gsize, tslimit, (const float *)h->y3t, h->y3, h->action)
-                    const bool es = h->L.kind == DNE_KIND_ES;
+                    const bool es = es_like(h->L.kind);
                     if (nb > 1) {   // few members left: policy head + emulator, then each frame over nb workgroups
                         if (es) TS(true, false, h->head_threads); else TS(false, false, h->head_threads);
                         hipLaunchKernelGGL(k_env_render, dim3(items * nb), dim3(h->band_threads), 0, sst, E, lst, gsize, 0, nb);
@@ -1977,10 +1987,10 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
                     const int items = cnt * gsize;
                     const float *sums = h->sub_now ? h->y3s : h->y3t;
                     if (h->sub_render_fused && h->sub_now && !(h->dbg_skip & 4)) {   // head + emulator + renderer in one launch
-                        if (h->L.kind == DNE_KIND_ES) hipLaunchKernelGGL((k_tail_step<true, true>), dim3(items), dim3(1024), 0, sst, A, E, lst, gsize, tslimit, sums, h->y3, h->action);
+                        if (es_like(h->L.kind)) hipLaunchKernelGGL((k_tail_step<true, true>), dim3(items), dim3(1024), 0, sst, A, E, lst, gsize, tslimit, sums, h->y3, h->action);
                         else hipLaunchKernelGGL((k_tail_step<false, true>), dim3(items), dim3(1024), 0, sst, A, E, lst, gsize, tslimit, sums, h->y3, h->action);
                     } else {
-                    if (h->L.kind == DNE_KIND_ES) hipLaunchKernelGGL((k_tail_step<true, false>), dim3(items), dim3(h->head_threads), 0, sst, A, E, lst, gsize, tslimit, sums, h->y3, h->action);
+                    if (es_like(h->L.kind)) hipLaunchKernelGGL((k_tail_step<true, false>), dim3(items), dim3(h->head_threads), 0, sst, A, E, lst, gsize, tslimit, sums, h->y3, h->action);
                     else hipLaunchKernelGGL((k_tail_step<false, false>), dim3(items), dim3(h->head_threads), 0, sst, A, E, lst, gsize, tslimit, sums, h->y3, h->action);
                     if (!(h->dbg_skip & 4))
                         hipLaunchKernelGGL(k_env_render, dim3(items), dim3(items <= 192 ? 1024 : h->render_threads), 0, sst, E, lst, gsize, 0, 1);
@@ -2061,7 +2071,7 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
 extern "C" int dne_es_eval(dne_handle *h, const int64_t *idx, int n, float sigma, int tslimit, const uint32_t *env_seed,
                            float *returns_n2, float *signreturns_n2, int32_t *lengths_n2, uint8_t *bc) {
     DeviceGuard dg(h);
-    if (h->L.kind != DNE_KIND_ES) return h->fail("dne_es_eval needs an ESAtariPolicy engine");
+    if (!es_like(h->L.kind)) return h->fail("dne_es_eval needs an ESAtariPolicy engine");
     if (n <= 0 || 2 * n > h->M) return h->fail("%d pairs exceed max_members = %d", n, h->M);
     std::vector<int32_t> slot(2 * n, 0);
     std::vector<int64_t> off(2 * n);
@@ -2150,7 +2160,7 @@ static int build_chain(dne_handle *h, int slot, const int64_t *seeds, const floa
 // dqn.py:24-27, biases 0); with it set, genomes given with per-seed powers start as noise[idx0] * scale_by
 extern "C" int dne_ga_set_init_scale(dne_handle *h, const float *scale_by, size_t n) {
     DeviceGuard dg(h);
-    if (h->L.kind == DNE_KIND_ES) return h->fail("dne_ga_set_init_scale needs a GA engine");
+    if (es_like(h->L.kind)) return h->fail("dne_ga_set_init_scale needs a GA engine");
     if (n != (size_t)h->L.P) return h->fail("dne_ga_set_init_scale: expected %d values, got %zu", h->L.P, n);
     if (!h->init_scale) HCHECK(h, h->alloc(&h->init_scale, n, "init_scale"));
     HCHECK(h, hipMemcpy(h->init_scale, scale_by, n * sizeof(float), hipMemcpyHostToDevice));
@@ -2177,7 +2187,7 @@ extern "C" int dne_ga_rebuild(dne_handle *h, int slot, const int64_t *seeds, int
 // the same for a genome ((idx0,), (idx1, power1), ...) of the gpu tree (base.py:118-139: compute_weights_from_seeds)
 extern "C" int dne_ga_rebuild_powers(dne_handle *h, int slot, const int64_t *seeds, const float *powers, int nseeds, float *out_host) {
     DeviceGuard dg(h);
-    if (h->L.kind == DNE_KIND_ES) return h->fail("dne_ga_rebuild_powers needs a GA engine");
+    if (es_like(h->L.kind)) return h->fail("dne_ga_rebuild_powers needs a GA engine");
     if (slot < 0 || nseeds < 1 || !powers) return h->fail("bad arguments");
     if (grow_bases(h, slot + 1)) return -1;
     h->free_slots.erase(std::remove(h->free_slots.begin(), h->free_slots.end(), slot), h->free_slots.end());
@@ -2194,7 +2204,7 @@ extern "C" int dne_ga_rebuild_powers(dne_handle *h, int slot, const int64_t *see
 // gpu tree's genomes ((idx0,), (idx1, power1), ...) with a scaled-noise root (base.py:118-149).
 static int ga_eval_impl(dne_handle *h, const int32_t *co, const int64_t *seeds, const float *powers, int n, float sigma, int tslimit,
                         const uint32_t *env_seed, float *returns, float *signreturns, int32_t *lengths, uint8_t *bc) {
-    if (h->L.kind == DNE_KIND_ES) return h->fail("dne_ga_eval needs a GA engine");
+    if (es_like(h->L.kind)) return h->fail("dne_ga_eval needs a GA engine");
     if (h->large && !powers) return h->fail("LargeModel genomes are the GPU tree's: per-seed powers over a scaled-noise root (dne_ga_set_init_scale + dne_ga_eval_powers)");
     if (check_n(h, n)) return -1;
     if (powers && !h->init_scale) return h->fail("genomes with per-seed powers need dne_ga_set_init_scale first");
@@ -2651,7 +2661,7 @@ static int check_records_host(dne_handle *h, int n_global) {
 // the gloo tests)
 extern "C" int dne_records_pack(dne_handle *h, int n_local, void *records_out) {
     DeviceGuard dg(h);
-    if (h->L.kind != DNE_KIND_ES || n_local < 1 || 2 * n_local > h->M) return h->fail("dne_records_pack: %d pairs", n_local);
+    if (!es_like(h->L.kind) || n_local < 1 || 2 * n_local > h->M) return h->fail("dne_records_pack: %d pairs", n_local);
     if (rec_reserve(h, n_local, n_local)) return -1;
     hipLaunchKernelGGL(k_records_pack, dim3((n_local + 255) / 256), dim3(256), 0, h->stream, (const int64_t *)h->m_off, (const float *)h->ret,
                        (const float *)h->sign, (const int32_t *)h->len, n_local, n_local, (PairRecord *)h->rec_send);
@@ -2685,7 +2695,7 @@ extern "C" int dne_records_set(dne_handle *h, const void *records, int n_global)
 extern "C" int dne_allgather_results(dne_handle *h, int n_local, int n_global, void *records_out) {
     DeviceGuard dg(h);
     const int world = h->comm ? h->comm_size : 1, rank = h->comm ? h->comm_rank : 0;
-    if (h->L.kind != DNE_KIND_ES) return h->fail("dne_allgather_results needs an ESAtariPolicy engine");
+    if (!es_like(h->L.kind)) return h->fail("dne_allgather_results needs an ESAtariPolicy engine");
     const int mine = n_global > rank ? (n_global - rank + world - 1) / world : 0;
     if (n_global < 1 || n_local != mine || 2 * n_local > h->M)
         return h->fail("dne_allgather_results: rank %d of %d holds %d pairs, a population of %d pairs gives it %d", rank, world, n_local, n_global, mine);
@@ -2900,7 +2910,7 @@ extern "C" int dne_novelty(dne_handle *h, const uint8_t *archive, const int32_t 
 extern "C" int dne_novelty_batch(dne_handle *h, const uint8_t *archive, const int32_t *alen, int narch, int n,
                                  const int32_t *lengths, int k, double *out) {
     DeviceGuard dg(h);
-    if (h->L.kind != DNE_KIND_ES || !h->bc || h->cfg.bc_final_only) return h->fail("dne_novelty_batch needs an ES engine created with record_bc = 1 (full trajectories)");
+    if (!es_like(h->L.kind) || !h->bc || h->cfg.bc_final_only) return h->fail("dne_novelty_batch needs an ES engine created with record_bc = 1 (full trajectories)");
     if (check_n(h, n)) return -1;
     if (k < 1) return h->fail("dne_novelty_batch: bad sizes");
     if (archive && archive_load(h, archive, alen, narch, 128)) return -1;

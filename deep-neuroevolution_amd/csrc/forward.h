@@ -28,6 +28,14 @@ struct Layout {
     int c3w, c3b;   // LargeModel only
 };
 
+// Tensors a layout may lack: ModelVirtualBN (DNE_KIND_ES_VBN) has no conv / fc biases and no batch-norm gamma, their offsets are -1.
+// A site that reads one keeps its loads (from offset 0 when the tensor is absent: never from -1, never past the vector) and then selects,
+// on the uniform offset, what the ES kind computes for a bias of +0.0f / a gamma of 1.0f -- the ES kind's loads and arithmetic are
+// unchanged, its value passes the select.
+__device__ __forceinline__ int opt_off(int off) { return off < 0 ? 0 : off; }
+__device__ __forceinline__ float opt_bias(int off, float v) { return off < 0 ? 0.0f : v; }
+__device__ __forceinline__ float opt_gamma(int off, float v) { return off < 0 ? 1.0f : v; }
+
 // Tail of a generation (at most TT_MAX members left): a lock-step is a chain of short dependent launches, and what each of them
 // does first -- list -> member -> (noise offset, base slot, scale) -> first weight address -- is two dependent memory round trips
 // before the first useful load can be issued.  The host knows all of it (the active list comes back with the active count at
@@ -182,7 +190,7 @@ __device__ __forceinline__ void conv1_body(Conv1Lds &S, const FwdArgs &A, const 
         b[kk] = base[4 * CO * kk + wl] + v;
     }
     float pb = sc * eps[256 * CO + half * 16 + lp];
-    const float bias = base[256 * CO + half * 16 + lp] + pb;
+    const float bias = opt_bias(A.L.c1b, base[256 * CO + half * 16 + lp] + pb);
     lut[tid] = (float)tid / 255.0f;
     {   // stage the frame stack: all 28 loads of a thread are issued before the first LDS write (a rolled loop
         // would pay one L2 round trip per element); the 2-pixel zero border is written separately
@@ -336,7 +344,7 @@ __global__ __launch_bounds__(512) void k_conv1_ref_shared(FwdArgs A, int F, int 
         b[kk] = base[64 * kk + lane] + v;
     }
     float pb = sc * eps[4096 + lp];
-    const float bias = base[4096 + lp] + pb;
+    const float bias = opt_bias(A.L.c1b, base[4096 + lp] + pb);
     stage();
     __syncthreads();
     const float *plane = imgf + ci * RF_PLANE;
@@ -437,7 +445,7 @@ __device__ __forceinline__ void conv2_body(Conv2Lds &S, const FwdArgs &A, const 
         b[kk] = base[o] + v;
     }
     float pb = sc * eps[8192 + nt * 16 + lp];
-    const float bias = base[8192 + nt * 16 + lp] + pb;
+    const float bias = opt_bias(A.L.c2b, base[8192 + nt * 16 + lp] + pb);
     for (int pix = tid; pix < 24 * 24; pix += 256) {   // zero only the SAME-padding ring (disjoint from the fill)
         const int y = pix / 24, x = pix % 24;
         if (y < 1 || y > 21 || x < 1 || x > 21)
@@ -584,7 +592,7 @@ __global__ __launch_bounds__(256, 2) void k_conv2_ref(FwdArgs A, int F, int memb
         b[kk] = base[o] + v;
     }
     float pb = sc * eps[8192 + nt * 16 + lp];
-    const float bias = base[8192 + nt * 16 + lp] + pb;
+    const float bias = opt_bias(A.L.c2b, base[8192 + nt * 16 + lp] + pb);
     for (int pix = tid; pix < 24 * 24; pix += 256) {   // the SAME-padding ring, once: the fills never touch it
         const int y = pix / 24, x = pix % 24;
         if (y < 1 || y > 21 || x < 1 || x > 21)
@@ -800,12 +808,12 @@ __global__ __launch_bounds__(256, 2) void k_conv12(FwdArgs A, const int *__restr
         }
     }
     float pb1 = sc * eps[A.L.c1w + 4096 + lp];
-    const float bias1 = base[A.L.c1w + 4096 + lp] + pb1;
+    const float bias1 = opt_bias(A.L.c1b, base[A.L.c1w + 4096 + lp] + pb1);
     const float s1 = HAS_BN ? bn[lp] : 1.0f, h1 = HAS_BN ? bn[16 + lp] : 0.0f;      // conv1's output channel of this lane = lp
     const int nt = wv & 1, mt0 = 4 * (wv >> 1), lk = ci;
 
     float pb2 = sc * eps[A.L.c2w + 8192 + nt * 16 + lp];
-    const float bias2 = base[A.L.c2w + 8192 + nt * 16 + lp] + pb2;
+    const float bias2 = opt_bias(A.L.c2b, base[A.L.c2w + 8192 + nt * 16 + lp] + pb2);
     S.lut[tid] = (float)tid / 255.0f;
     for (int i = tid; i < 688; i += 256) {                                            // conv1's 2-pixel zero border
         int r, c;
@@ -966,11 +974,11 @@ __device__ __forceinline__ void conv12t_body(Conv12Lds &S, const FwdArgs &A, con
         }
     }
     float pb1 = sc * eps[A.L.c1w + 4096 + lp];
-    const float bias1 = base[A.L.c1w + 4096 + lp] + pb1;
+    const float bias1 = opt_bias(A.L.c1b, base[A.L.c1w + 4096 + lp] + pb1);
     const float s1 = HAS_BN ? bn[lp] : 1.0f, h1 = HAS_BN ? bn[16 + lp] : 0.0f;      // conv1's output channel of this lane = lp
     const int nt = wv & 1, mt = 2 * part + ((wv >> 1) & 1), lk = ci;                  // conv2: waves 0..3, one tile each
     float pb2 = sc * eps[A.L.c2w + 8192 + nt * 16 + lp];
-    const float bias2 = base[A.L.c2w + 8192 + nt * 16 + lp] + pb2;
+    const float bias2 = opt_bias(A.L.c2b, base[A.L.c2w + 8192 + nt * 16 + lp] + pb2);
     if (tid < 256) S.lut[tid] = (float)tid / 255.0f;
     for (int i = tid; i < 688; i += NT) {                                             // conv1's 2-pixel zero border
         int r, c;
@@ -1324,8 +1332,8 @@ __global__ __launch_bounds__(256) void k_fc(FwdArgs A, const int *__restrict__ l
         const float s01 = part[0][v][j] + part[1][v][j];
         const float s23 = part[2][v][j] + part[3][v][j];
         float s = s01 + s23;
-        float pv = scale[v] * A.noise[off + L.fcb + j];
-        const float bias = base[L.fcb + j] + pv;
+        float pv = scale[v] * A.noise[off + opt_off(L.fcb) + j];
+        const float bias = opt_bias(L.fcb, base[opt_off(L.fcb) + j] + pv);
         s = s + bias;
         y3[(size_t)row[v] * 256 + j] = s;
         float t = s;
@@ -2418,8 +2426,8 @@ __global__ __launch_bounds__(256) void k_bn3_partials(FwdArgs A, int member0, in
     const float *base = A.bases + (size_t)A.m_slot[member] * A.base_stride;
     const float *eps = A.noise + A.m_off[member];
     const float sc = A.m_scale[member];
-    float pbias = sc * eps[L.fcb + j];
-    const float bias = base[L.fcb + j] + pbias;
+    float pbias = sc * eps[opt_off(L.fcb) + j];
+    const float bias = opt_bias(L.fcb, base[opt_off(L.fcb) + j] + pbias);
     const float *p = y3p + (size_t)mloc * 4 * F * 256 + j;
     const size_t ss = (size_t)F * 256;
     const float count = (float)F;
@@ -2444,8 +2452,8 @@ __global__ __launch_bounds__(256) void k_bn3_partials(FwdArgs A, int member0, in
     const float var = totq / count;
     float pb = sc * eps[L.bn3b + j];
     const float beta = base[L.bn3b + j] + pb;
-    float pg = sc * eps[L.bn3g + j];
-    const float gamma = base[L.bn3g + j] + pg;
+    float pg = sc * eps[opt_off(L.bn3g) + j];
+    const float gamma = opt_gamma(L.bn3g, base[opt_off(L.bn3g) + j] + pg);
     const float inv = 1.0f / sqrtf(var + 1e-3f);
     const float s = inv * gamma;
     const float ms = mean * s;
@@ -3074,7 +3082,7 @@ __global__ __launch_bounds__(256) void k_out(FwdArgs A, const int *__restrict__ 
     float sc[NV], x3[NV];
 #pragma unroll
     for (int v = 0; v < NV; v++) sc[v] = A.m_scale[m0 + v];
-    const float fb_t = base[L.fcb + tid], fb_e = eps[L.fcb + tid];
+    const float fb_t = opt_bias(L.fcb, base[opt_off(L.fcb) + tid]), fb_e = opt_bias(L.fcb, eps[opt_off(L.fcb) + tid]);
 #pragma unroll
     for (int v = 0; v < NV; v++) {
         const int m = m0 + v;
@@ -3136,8 +3144,8 @@ __global__ __launch_bounds__(256) void k_bn_finalize(FwdArgs A, int member0, int
     const float *base = A.bases + (size_t)A.m_slot[member] * A.base_stride;
     const float *eps = A.noise + A.m_off[member];
     const float sc = A.m_scale[member];
-    float pbias = sc * eps[bias_off + c];
-    const float bias = base[bias_off + c] + pbias;
+    float pbias = sc * eps[opt_off(bias_off) + c];
+    const float bias = opt_bias(bias_off, base[opt_off(bias_off) + c] + pbias);
     const float m = S / count;
     const float mean = bias + m;
     const float q1 = Q / count;
@@ -3146,8 +3154,8 @@ __global__ __launch_bounds__(256) void k_bn_finalize(FwdArgs A, int member0, int
     var = var > 0.0f ? var : 0.0f;
     float pb = sc * eps[beta_off + c];
     const float beta = base[beta_off + c] + pb;
-    float pg = sc * eps[gamma_off + c];
-    const float gamma = base[gamma_off + c] + pg;
+    float pg = sc * eps[opt_off(gamma_off) + c];
+    const float gamma = opt_gamma(gamma_off, base[opt_off(gamma_off) + c] + pg);
     const float inv = 1.0f / sqrtf(var + 1e-3f);
     const float s = inv * gamma;
     const float ms = mean * s;
@@ -3181,8 +3189,8 @@ __global__ __launch_bounds__(256) void k_bn3_rows(FwdArgs A, int member0, int F,
     const float sc = A.m_scale[member];
     float pb = sc * eps[L.bn3b + j];
     const float beta = base[L.bn3b + j] + pb;
-    float pg = sc * eps[L.bn3g + j];
-    const float gamma = base[L.bn3g + j] + pg;
+    float pg = sc * eps[opt_off(L.bn3g) + j];
+    const float gamma = opt_gamma(L.bn3g, base[opt_off(L.bn3g) + j] + pg);
     const float inv = 1.0f / sqrtf(var + 1e-3f);
     const float s = inv * gamma;
     const float ms = mean * s;

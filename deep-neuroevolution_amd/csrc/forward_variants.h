@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void k_conv1_ref(FwdArgs A, int F, int member0
         b[kk] = base[64 * kk + lane] + v;
     }
     float pb = sc * eps[4096 + lp];
-    const float bias = base[4096 + lp] + pb;
+    const float bias = opt_bias(A.L.c1b, base[4096 + lp] + pb);
     lut[tid] = (float)tid / 255.0f;
     for (int i = tid; i < 688; i += 256) {           // the 2-pixel zero border, once
         int r, c;
@@ -256,8 +256,8 @@ __global__ __launch_bounds__(256) void k_fc2(FwdArgs A, const int *__restrict__ 
                 const float s01 = part[0][v][j] + part[1][v][j];
                 const float s23 = part[2][v][j] + part[3][v][j];
                 float s = s01 + s23;
-                float pv = scale[v] * A.noise[off[pr] + L.fcb + j];
-                const float bias = base[L.fcb + j] + pv;
+                float pv = scale[v] * A.noise[off[pr] + opt_off(L.fcb) + j];
+                const float bias = opt_bias(L.fcb, base[opt_off(L.fcb) + j] + pv);
                 s = s + bias;
                 y3[(size_t)member[v] * 256 + j] = s;
                 float t = s;

@@ -13,6 +13,8 @@ _CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("DNE_LIB_PATH") or os.path.join(_CSRC, "libdne_hip.so")   # DNE_LIB_PATH: another build of the same ABI (same-box A/B of whole builds)
 
 KIND_ES, KIND_GA, KIND_GA_LARGE = 0, 1, 2   # DNE_KIND_* (include/dne_hip.h); 2 = the GPU tree's LargeModel (models/dqn.py:39-47)
+KIND_ES_VBN = 3   # the GPU tree's ModelVirtualBN in its own flat layout (models/batchnorm.py:52-123): the ES kind's network and entry points
+ES_KINDS = (KIND_ES, KIND_ES_VBN)   # virtual batch norm over a reference batch, antithetic pairs
 PROC_MODES = {"centered_rank": 0, "sign": 1, "centered_sign_rank": 2}
 OPT_KINDS = {"adam": 0, "sgd": 1}
 OB_SHAPE = (84, 84, 4)
@@ -118,7 +120,7 @@ class Engine:
                  record_bc=False, bc_max_steps=0, profile_events=False, bc_final_only=False):
         self.lib = load()
         self.kind, self.n_actions, self.max_members = int(kind), int(n_actions), int(max_members)
-        self.ref_count = int(ref_count) if kind == KIND_ES else 0
+        self.ref_count = int(ref_count) if kind in ES_KINDS else 0
         self.bc_max_steps = int(bc_max_steps)
         cfg = Config(device_id=device_id, policy_kind=self.kind, n_actions=self.n_actions, max_members=self.max_members,
                      ref_count=self.ref_count, ref_chunk=ref_chunk, record_bc=int(bool(record_bc)),
@@ -265,7 +267,7 @@ class Engine:
     def _bc_buf(self, n, want):
         if not want:
             return None
-        if self.kind == KIND_ES and not self.bc_final_only:
+        if self.kind in ES_KINDS and not self.bc_final_only:
             return np.zeros((n, self.bc_max_steps, RAM_BYTES), np.uint8)
         return np.zeros((n, RAM_BYTES), np.uint8)
 

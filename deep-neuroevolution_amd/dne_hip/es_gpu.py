@@ -4,10 +4,17 @@ adaptive episode cutoff (es.py:52-62, 273-276), the elite's test episodes before
 reference's tabular keys (es.py:206-268).
 
 Model: configurations/es_atari_config.json names `ModelVirtualBN` (models/batchnorm.py:52-123: conv 16 8x8/4, conv 32 4x4/2, fc 256 with
-virtual batch norm from a reference batch).  The engine's ES network IS that architecture in the es_distributed parameterisation
-(policies.py:319-330: conv biases and a learnt BN scale in the flat vector, which ModelVirtualBN fixes at 0 and 1); exp['model'] =
-'ModelVirtualBN' selects it, theta starts from policies.xavier_flat instead of the GPU tree's scaled noise slice (the parity
-target is the CPU path).  What is NOT built: ModelVirtualBN's own flat layout (1 008 450 parameters), `load_from` (ga_legacy genomes).
+virtual batch norm from a reference batch).  The engine runs that architecture in one of two flat layouts, chosen by the optional config
+key exp['flat_layout']:
+  'es_distributed' (default)  the es_distributed parameterisation (DNE_KIND_ES, policies.py:319-330: conv / fc biases and a learnt BN scale
+                              in the flat vector, 1 009 058 parameters at 18 actions); theta starts from policies.xavier_flat (SURVEY Q14:
+                              the parity target is the CPU path).
+  'native'                    ModelVirtualBN's own layout (DNE_KIND_ES_VBN, 1 008 450 parameters: no biases before the normalisation, no
+                              BN scale, each BatchNorm/b a shift after it); theta starts as TrainingState.initialize does (es.py:73-75 ->
+                              base.py:123-141): idx = noise.sample_index(rs, P), the first draw of the run's stream, then
+                              theta = noise.get(idx, P) * scale_by (policies.vbn_scale_by) in fp32.
+An engine passed in by the caller decides the layout by its kind.  The layout and P are recorded in snapshot.pkl; a resume under another
+layout or P fails and names both (snapshots written before the key existed are 'es_distributed').  Not built: `load_from` (ga_legacy genomes).
 
 Where the arithmetic lives: ranks, sum_i w_i * noise[idx_i] / 2N, -g + l2coeff * theta and the optimizer step are dne_es_update on the device
 (the same formulas as es_distributed: es.py:227-246 here = es_distributed/es.py:281-301).  The GPU tree's SGD keeps v = momentum * v + g
@@ -26,6 +33,7 @@ from .es import SharedNoiseTable, get_ref_batch, optimizer_args, parse_cutoff
 from .ga_gpu import Offspring, Schedule
 
 MODEL_KINDS = {'ModelVirtualBN': _lib.KIND_ES}   # neuroevolution/models/batchnorm.py:52 (exp['model'], es.py:144)
+FLAT_LAYOUTS = {'es_distributed': _lib.KIND_ES, 'native': _lib.KIND_ES_VBN}   # exp['flat_layout'] -> the engine kind that runs it
 
 
 class TrainingState(object):
@@ -42,6 +50,8 @@ class TrainingState(object):
         self.incr_tslimit_threshold, self.tslimit_incr_ratio = grow_at, grow_by
         if adaptive:
             self.tslimit_max = limit_max
+        self.flat_layout = 'es_distributed'   # FLAT_LAYOUTS key of the run (main sets it); a snapshot without it predates the choice
+        self.num_params = None
         self.theta = None
         self.optimizer = None          # (m, v, t) of the device optimizer, None before the first update
         self.stream = None             # the index / environment-seed stream's position (an extension: the reference's stream is unseeded,
@@ -92,7 +102,17 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
         raise NotImplementedError("load_from (es.py:164-171: a ga_legacy genome as the first theta) is not built")
     n_pairs = exp['population_size'] // 2
     if engine is None:
-        engine = _lib.Engine(MODEL_KINDS[exp['model']], 18, max_members=2 * n_pairs, ref_count=ref_count)
+        layout = exp.get('flat_layout', 'es_distributed')
+        if layout not in FLAT_LAYOUTS:
+            raise ValueError("flat_layout {!r}: expected one of {}".format(layout, sorted(FLAT_LAYOUTS)))
+        if MODEL_KINDS[exp['model']] != _lib.KIND_ES:                # the one model of this loop, in either layout
+            raise NotImplementedError(exp['model'])
+        engine = _lib.Engine(FLAT_LAYOUTS[layout], 18, max_members=2 * n_pairs, ref_count=ref_count)
+    else:                                                           # the caller's engine decides
+        layout = {k: name for name, k in FLAT_LAYOUTS.items()}.get(engine.kind)
+        if layout is None or exp.get('flat_layout', layout) != layout:
+            raise ValueError("flat_layout {!r} asked for, the engine passed in (kind {}) runs {!r}".format(
+                exp.get('flat_layout'), engine.kind, layout))
     noise = noise if noise is not None else SharedNoiseTable()
     noise.attach(engine)
     rs = np.random.RandomState(seed)
@@ -101,9 +121,18 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
         with open(os.path.join(log_dir, 'snapshot.pkl'), 'rb') as file:
             state = pickle.load(file)
         tlogger.log("Loaded iteration {} from {}".format(state.it, log_dir))
+        was = (getattr(state, 'flat_layout', 'es_distributed'), int(np.asarray(state.theta).size))
+        if was != (layout, engine.P):
+            raise ValueError("snapshot.pkl in {} holds flat_layout {!r} with P = {}; this run is flat_layout {!r} with P = {}".format(
+                log_dir, was[0], was[1], layout, engine.P))
     except FileNotFoundError:
         state = TrainingState(exp)
-        state.theta = policies.xavier_flat(engine.n_actions, seed)   # es.py:173: state.initialize(rs, noise, worker.model)
+        if layout == 'native':                                      # es.py:173 -> es.py:73-75 -> model.randomize(rs, noise), base.py:123-141
+            idx = noise.sample_index(rs, engine.P)
+            state.theta = noise.get(idx, engine.P) * policies.vbn_scale_by(engine.n_actions)
+        else:
+            state.theta = policies.xavier_flat(engine.n_actions, seed)   # es.py:173: state.initialize(rs, noise, worker.model)
+    state.flat_layout, state.num_params = layout, engine.P
     state.push(engine)
     env = policies.HipAtariEnv(engine, seed=seed)                   # ModelVirtualBN.requires_ref_batch (batchnorm.py:60-62)
     ref = np.stack(get_ref_batch(env, batch_size=engine.ref_count, random_stream=np.random.RandomState(seed)))

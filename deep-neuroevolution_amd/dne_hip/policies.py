@@ -16,7 +16,9 @@ from . import _lib
 def flat_layout(kind, nact):
     """Offsets of each trainable variable in the flat vector (policies.py:21-24, tf_util.py:224-246).
     ESAtariPolicy: tf.contrib.layers order (weights, biases, BN beta, BN gamma per layer), policies.py:319-330.
-    GAAtariPolicy: U.conv / U.dense order (w, b), policies.py:449-459 via tf_util.py:133-162."""
+    GAAtariPolicy: U.conv / U.dense order (w, b), policies.py:449-459 via tf_util.py:133-162.
+    ModelVirtualBN (the GPU tree's ES model, models/batchnorm.py:52-123): creation order (base.py:35-44, 166-178) -- conv / fc without
+    bias, each followed by its BatchNorm/b (the shift after normalisation; BN mean / var are not in the vector), then out/w, out/b."""
     spec = OrderedDict()
     o = 0
 
@@ -30,6 +32,11 @@ def flat_layout(kind, nact):
         add("conv2/weights", (4, 4, 16, 32)); add("conv2/biases", (32,)); add("BatchNorm_1/beta", (32,)); add("BatchNorm_1/gamma", (32,))
         add("fc/weights", (3872, 256)); add("fc/biases", (256,)); add("BatchNorm_2/beta", (256,)); add("BatchNorm_2/gamma", (256,))
         add("out/weights", (256, nact)); add("out/biases", (nact,))
+    elif kind == _lib.KIND_ES_VBN:
+        add("layer1/conv1/w", (8, 8, 4, 16)); add("layer1/BatchNorm/b", (1, 1, 1, 16))
+        add("layer2/conv2/w", (4, 4, 16, 32)); add("layer2/BatchNorm/b", (1, 1, 1, 32))
+        add("layer3/fc/w", (3872, 256)); add("layer3/BatchNorm/b", (1, 256))
+        add("layer4/out/w", (256, nact)); add("layer4/out/b", (1, nact))
     elif kind == _lib.KIND_GA_LARGE:   # the GPU tree's LargeModel, gpu_implementation/neuroevolution/models/dqn.py:39-47 (creation order, base.py:35-41)
         add("conv1/w", (8, 8, 4, 32)); add("conv1/b", (1, 1, 1, 32))
         add("conv2/w", (4, 4, 32, 64)); add("conv2/b", (1, 1, 1, 64))
@@ -42,6 +49,18 @@ def flat_layout(kind, nact):
         add("fc/w", (3872, 256)); add("fc/b", (256,))
         add("out/w", (256, nact)); add("out/b", (nact,))
     return spec, o
+
+
+def vbn_scale_by(nact):
+    """scale_by of ModelVirtualBN (models/dqn.py:25-27 via batchnorm.py:52, base.py:166-178): each w gets std / sqrt(prod(shape[:-1]))
+    with std 1.0 -- the out layer included (batchnorm.py:105 passes no std=0.1, unlike Model) --, each b 0.  fp32, in flat_layout order:
+    theta_0 = noise.get(idx, P) * scale_by (base.py:123-141)."""
+    spec, P = flat_layout(_lib.KIND_ES_VBN, nact)
+    sb = np.zeros(P, np.float32)
+    for name, (off, shape) in spec.items():
+        if name.endswith('/w'):
+            sb[off:off + int(np.prod(shape))] = np.float32(1.0 / np.sqrt(np.prod(shape[:-1])))
+    return sb
 
 
 def xavier_flat(nact, seed=0):

@@ -25,6 +25,10 @@ extern "C" {
 #define DNE_KIND_GA 1 /* GAAtariPolicy  es_distributed/policies.py:433-513 */
 #define DNE_KIND_GA_LARGE 2 /* LargeModel of the GPU tree (conv 32/64/64, fc 512): gpu_implementation/neuroevolution/models/dqn.py:39-47.
                                GA entry points only, genomes with per-seed powers (dne_ga_set_init_scale + dne_ga_eval_powers) */
+#define DNE_KIND_ES_VBN 3 /* ModelVirtualBN of the GPU tree in its own flat layout: gpu_implementation/neuroevolution/models/batchnorm.py:52-123
+                             (tensors in creation order, models/base.py:35-44, 166-178).  The ES kind's network, evaluation and entry points
+                             (virtual batch norm, antithetic pairs, dne_es_eval / dne_es_update); no conv / fc biases, no BN gamma: each
+                             BatchNorm/b is the shift after normalisation.  P = 1003824 + 257 * n_actions */
 #define DNE_OB_BYTES (84 * 84 * 4)
 #define DNE_RAM_BYTES 128
 #define DNE_BN_FLOATS 608
