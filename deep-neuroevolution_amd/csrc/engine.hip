@@ -26,6 +26,7 @@
 #include "forward_variants.h"
 #include "forward_large.h"
 #include "reduce.h"
+#include "novelty.h"
 
 using namespace dne;
 
@@ -702,7 +703,12 @@ struct dne_handle {
     uint8_t *arch = nullptr; size_t arch_cap = 0, arch_rows = 0; int arch_dim = 0;
     int64_t *arch_row0 = nullptr; int32_t *arch_len = nullptr; size_t arch_ent_cap = 0;
     std::vector<int64_t> arch_row0_host; std::vector<int32_t> arch_len_host;
-    long long *nov_out = nullptr; size_t nov_out_cap = 0; int32_t *nov_len = nullptr; size_t nov_len_cap = 0;   // GA: the seed offsets of the chain being rebuilt
+    size_t arch_pitch = 0;           // bytes per archive row on the device: the width rounded up to 16, zero-padded (novelty.h)
+    // dne_novelty_knn scratch: the [n][narch] distances + n results, the length-ordered index arrays, host members' rows
+    double *nov_dist = nullptr; size_t nov_dist_cap = 0;
+    uint8_t *nov_idx = nullptr; size_t nov_idx_cap = 0;
+    uint8_t *nov_rows = nullptr; size_t nov_rows_cap = 0;
+    unsigned long long *nov_acc = nullptr; size_t nov_acc_cap = 0;   // [n][narch][2] sums of a row-split distance launch
     // RCCL communicator (dne_comm_init); the library is opened on demand
     void *rccl_lib = nullptr; void *comm = nullptr; int comm_rank = 0, comm_size = 1;
     bool comm_borrowed = false;      // dne_comm_share: the communicator belongs to another handle of this process
@@ -2796,12 +2802,24 @@ extern "C" int dne_ga_select(dne_handle *h, const float *returns, int m, int t, 
 
 // ---- the novelty archive lives on the device: the master's archive only ever grows (nses.py:246-247 appends one BC per
 // iteration), so a worker uploads each entry once instead of the whole archive on every call
+static size_t row_pitch(int dim) { return ((size_t)dim + 15) & ~(size_t)15; }
+
+// rows of `dim` bytes laid out at the device pitch (zero pad bytes add nothing to a squared difference)
+static int upload_rows(dne_handle *h, uint8_t *dst, const uint8_t *src, size_t rows, int dim) {
+    const size_t pitch = row_pitch(dim);
+    if (pitch == (size_t)dim) return copy_h2d(h, dst, src, rows * dim);
+    std::vector<uint8_t> pad(rows * pitch, 0);
+    for (size_t r = 0; r < rows; r++) std::memcpy(pad.data() + r * pitch, src + r * dim, dim);
+    return copy_h2d(h, dst, pad.data(), pad.size());
+}
+
 static int archive_reserve(dne_handle *h, size_t rows, size_t entries, int dim) {
-    if (rows * dim > h->arch_cap) {
+    const size_t pitch = row_pitch(dim);
+    if (rows * pitch > h->arch_cap) {
         uint8_t *nb = nullptr;
-        const size_t cap = std::max<size_t>(2 * rows * dim, 1u << 20);
+        const size_t cap = std::max<size_t>(2 * rows * pitch, 1u << 20);
         HCHECK(h, h->alloc(&nb, cap, "novelty_archive"));
-        if (h->arch && h->arch_rows) HCHECK(h, hipMemcpy(nb, h->arch, h->arch_rows * h->arch_dim, hipMemcpyDeviceToDevice));
+        if (h->arch && h->arch_rows) HCHECK(h, hipMemcpy(nb, h->arch, h->arch_rows * h->arch_pitch, hipMemcpyDeviceToDevice));
         HCHECK(h, h->release(h->arch));
         h->arch = nb; h->arch_cap = cap;
     }
@@ -2821,7 +2839,7 @@ static int archive_reserve(dne_handle *h, size_t rows, size_t entries, int dim) 
 extern "C" int dne_archive_clear(dne_handle *h) {
     DeviceGuard dg(h);
     HCHECK(h, hipStreamSynchronize(h->stream));
-    h->arch_rows = 0; h->arch_dim = 0;
+    h->arch_rows = 0; h->arch_dim = 0; h->arch_pitch = 0;
     h->arch_row0_host.clear(); h->arch_len_host.clear();
     return 0;
 }
@@ -2833,8 +2851,8 @@ extern "C" int dne_archive_append(dne_handle *h, const uint8_t *bc, int bc_len, 
     HCHECK(h, hipStreamSynchronize(h->stream));
     const size_t n = h->arch_len_host.size();
     if (archive_reserve(h, h->arch_rows + bc_len, n + 1, dim)) return -1;
-    h->arch_dim = dim;
-    if (copy_h2d(h, h->arch + h->arch_rows * dim, bc, (size_t)bc_len * dim)) return -1;
+    h->arch_dim = dim; h->arch_pitch = row_pitch(dim);
+    if (upload_rows(h, h->arch + h->arch_rows * h->arch_pitch, bc, bc_len, dim)) return -1;
     const int64_t row0 = (int64_t)h->arch_rows; const int32_t len = bc_len;
     HCHECK(h, hipMemcpy(h->arch_row0 + n, &row0, sizeof(row0), hipMemcpyHostToDevice));
     HCHECK(h, hipMemcpy(h->arch_len + n, &len, sizeof(len), hipMemcpyHostToDevice));
@@ -2852,8 +2870,8 @@ static int archive_load(dne_handle *h, const uint8_t *archive, const int32_t *al
     size_t rows = 0;
     for (int a = 0; a < narch; a++) { if (alen[a] < 1) return h->fail("empty archive entry"); rows += alen[a]; }
     if (archive_reserve(h, rows, narch, dim)) return -1;
-    h->arch_dim = dim;
-    if (copy_h2d(h, h->arch, archive, rows * dim)) return -1;
+    h->arch_dim = dim; h->arch_pitch = row_pitch(dim);
+    if (upload_rows(h, h->arch, archive, rows, dim)) return -1;
     int64_t r0 = 0;
     for (int a = 0; a < narch; a++) { h->arch_row0_host.push_back(r0); h->arch_len_host.push_back(alen[a]); r0 += alen[a]; }
     HCHECK(h, hipMemcpy(h->arch_row0, h->arch_row0_host.data(), narch * sizeof(int64_t), hipMemcpyHostToDevice));
@@ -2862,18 +2880,89 @@ static int archive_load(dne_handle *h, const uint8_t *archive, const int32_t *al
     return 0;
 }
 
-static int novelty_scratch(dne_handle *h, size_t out_words, size_t len_words) {
-    if (out_words > h->nov_out_cap) {
-        HCHECK(h, h->release(h->nov_out));
-        h->nov_out_cap = std::max<size_t>(2 * out_words, 4096);
-        HCHECK(h, h->alloc(&h->nov_out, h->nov_out_cap, "novelty_out"));
-    }
-    if (len_words > h->nov_len_cap) {
-        HCHECK(h, h->release(h->nov_len));
-        h->nov_len_cap = std::max<size_t>(2 * len_words, 4096);
-        HCHECK(h, h->alloc(&h->nov_len, h->nov_len_cap, "novelty_len_in"));
-    }
+template <typename T>
+static int novelty_grow(dne_handle *h, T *&p, size_t &cap, size_t need, const char *name) {
+    if (need <= cap) return 0;
+    HCHECK(h, h->release(p));
+    cap = std::max<size_t>(2 * need, 4096);
+    HCHECK(h, h->alloc(&p, cap, name));
     return 0;
+}
+
+// nses.py:22-32 for n trajectories against the resident archive, whose width the caller has checked against `dim`:
+// bcs == NULL scores the recorded trajectories (member i at row i * bc_max_steps), otherwise the host rows uploaded here.
+// Both sides go to the kernels in length order (novelty.h); only the n results come back.
+static int novelty_run(dne_handle *h, const uint8_t *bcs, const int32_t *lengths, int n, int k, double *out) {
+    const int narch = (int)h->arch_len_host.size(), dim = h->arch_dim, pw = (int)(h->arch_pitch / 4);
+    const uint32_t *mrows = (const uint32_t *)h->bc;
+    std::vector<int64_t> mrow0(n);
+    int64_t rows = 0;
+    for (int i = 0; i < n; i++) { mrow0[i] = bcs ? rows : (int64_t)i * h->cfg.bc_max_steps; rows += lengths[i]; }
+    if (bcs) {
+        if (novelty_grow(h, h->nov_rows, h->nov_rows_cap, (size_t)rows * h->arch_pitch, "novelty_rows")) return -1;
+        if (upload_rows(h, h->nov_rows, bcs, rows, dim)) return -1;
+        mrows = (const uint32_t *)h->nov_rows;
+    }
+    std::vector<int32_t> mo(n), ao(narch);
+    for (int i = 0; i < n; i++) mo[i] = i;
+    for (int a = 0; a < narch; a++) ao[a] = a;
+    std::stable_sort(mo.begin(), mo.end(), [&](int x, int y) { return lengths[x] < lengths[y]; });
+    std::stable_sort(ao.begin(), ao.end(), [&](int x, int y) { return h->arch_len_host[x] < h->arch_len_host[y]; });
+    // one upload: [member row0][archive row0] int64, then [member len][archive len][member order] int32
+    std::vector<int64_t> r0((size_t)n + narch);
+    std::vector<int32_t> ln(2 * (size_t)n + narch);
+    for (int i = 0; i < n; i++) { r0[i] = mrow0[mo[i]]; ln[i] = lengths[mo[i]]; ln[(size_t)n + narch + i] = mo[i]; }
+    for (int a = 0; a < narch; a++) { r0[(size_t)n + a] = h->arch_row0_host[ao[a]]; ln[(size_t)n + a] = h->arch_len_host[ao[a]]; }
+    const size_t b64 = r0.size() * sizeof(int64_t), bytes = b64 + ln.size() * sizeof(int32_t);
+    if (novelty_grow(h, h->nov_idx, h->nov_idx_cap, bytes, "novelty_index")) return -1;
+    if (novelty_grow(h, h->nov_dist, h->nov_dist_cap, (size_t)n * narch + n, "novelty_dist")) return -1;
+    HCHECK(h, hipMemcpyAsync(h->nov_idx, r0.data(), b64, hipMemcpyHostToDevice, h->stream));
+    HCHECK(h, hipMemcpyAsync(h->nov_idx + b64, ln.data(), bytes - b64, hipMemcpyHostToDevice, h->stream));
+    const int64_t *d_r0 = (const int64_t *)h->nov_idx;
+    const int32_t *d_ln = (const int32_t *)(h->nov_idx + b64);
+    double *d_res = h->nov_dist + (size_t)n * narch;
+    // fewer tiles than two per CU: split each tile's rows over more workgroups, up to one per staged step of the longest
+    const int tx = (n + NV_T - 1) / NV_T, ty = (narch + NV_T - 1) / NV_T, tiles = tx * ty;
+    const int maxlen = std::max(lengths[mo[n - 1]], h->arch_len_host[ao[narch - 1]]);
+    const int steps = (int)(((int64_t)maxlen * ((pw + NV_W - 1) / NV_W) + NV_R - 1) / NV_R);
+    const int rsplit = tiles >= 512 ? 1 : std::max(1, std::min((512 + tiles - 1) / tiles, steps));
+    const size_t pairs = (size_t)n * narch;
+    if (rsplit > 1) {
+        if (novelty_grow(h, h->nov_acc, h->nov_acc_cap, 2 * pairs, "novelty_acc")) return -1;
+        HCHECK(h, hipMemsetAsync(h->nov_acc, 0, 2 * pairs * sizeof(unsigned long long), h->stream));
+    }
+    hipLaunchKernelGGL(k_knn_dist, dim3(tx, ty, rsplit), dim3(256), 0, h->stream,
+                       mrows, d_r0, d_ln, n, (const uint32_t *)h->arch, d_r0 + n, d_ln + n, narch, pw, h->nov_acc, h->nov_dist);
+    HCHECK(h, hipGetLastError());
+    if (rsplit > 1) {
+        hipLaunchKernelGGL(k_knn_finish, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, h->stream,
+                           (const unsigned long long *)h->nov_acc, pairs, h->nov_dist);
+        HCHECK(h, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_knn_select, dim3((n + 3) / 4), dim3(256), 0, h->stream, (const double *)h->nov_dist, n, narch,
+                       std::min(k, narch), d_ln + n + narch, d_res);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipMemcpyAsync(out, d_res, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int dne_novelty_knn(dne_handle *h, const uint8_t *bcs, const int32_t *lengths, int n, int dim, int k, double *out) {
+    DeviceGuard dg(h);
+    if (n < 1 || dim < 1 || k < 1) return h->fail("dne_novelty_knn: bad sizes n = %d dim = %d k = %d", n, dim, k);
+    if (!bcs) {
+        if (!es_like(h->L.kind) || !h->bc || h->cfg.bc_final_only) return h->fail("dne_novelty_knn on the recorded trajectories needs an ES engine created with record_bc = 1 (full trajectories)");
+        if (check_n(h, n)) return -1;
+        if (dim != 128) return h->fail("dne_novelty_knn: the recorded trajectories are 128-byte RAM rows, not %d", dim);
+    }
+    const int narch = (int)h->arch_len_host.size();
+    if (narch < 1) return h->fail("dne_novelty_knn: the archive is empty");
+    if (dim != h->arch_dim) return h->fail("dne_novelty_knn: characterisation width %d, archive holds %d", dim, h->arch_dim);
+    for (int i = 0; i < n; i++) {
+        if (lengths[i] < 1 || (!bcs && lengths[i] > h->cfg.bc_max_steps))
+            return h->fail("member %d: trajectory length %d outside [1, %d]", i, lengths[i], bcs ? INT_MAX : h->cfg.bc_max_steps);
+    }
+    return novelty_run(h, bcs, lengths, n, k, out);
 }
 
 // nses.py:12-32.  archive == NULL: score against the device-resident archive (dne_archive_append)
@@ -2885,26 +2974,7 @@ extern "C" int dne_novelty(dne_handle *h, const uint8_t *archive, const int32_t 
     narch = (int)h->arch_len_host.size();
     if (narch < 1) return h->fail("dne_novelty: the archive is empty");
     if (dim != h->arch_dim) return h->fail("dne_novelty: characterisation width %d, archive holds %d", dim, h->arch_dim);
-    if (novelty_scratch(h, 2 * (size_t)narch, ((size_t)bc_len * dim + 3) / 4)) return -1;
-    uint8_t *d_bc = (uint8_t *)h->nov_len;
-    HCHECK(h, hipMemcpyAsync(d_bc, bc, (size_t)bc_len * dim, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_bc_sqdist, dim3(narch), dim3(256), 0, h->stream, (const uint8_t *)h->arch, (const int64_t *)h->arch_row0,
-                       (const int32_t *)h->arch_len, (const uint8_t *)d_bc, bc_len, dim, h->nov_out);
-    HCHECK(h, hipGetLastError());
-    std::vector<long long> ab(2 * (size_t)narch);
-    HCHECK(h, hipMemcpyAsync(ab.data(), h->nov_out, ab.size() * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    std::vector<double> d(narch);
-    for (int a = 0; a < narch; a++) {   // nses.py:20 sqrt(a**2 + b**2) with a, b = the two Frobenius norms
-        const double na = std::sqrt((double)ab[2 * a]), nb = std::sqrt((double)ab[2 * a + 1]);
-        d[a] = std::sqrt(na * na + nb * nb);
-    }
-    std::sort(d.begin(), d.end());        // nses.py:29-31 k nearest, mean
-    const int kk = std::min(k, narch);
-    double s = 0;
-    for (int i = 0; i < kk; i++) s += d[i];
-    *out = s / kk;
-    return 0;
+    return novelty_run(h, bc, &bc_len, 1, k, out);
 }
 
 extern "C" int dne_novelty_batch(dne_handle *h, const uint8_t *archive, const int32_t *alen, int narch, int n,
@@ -2919,25 +2989,5 @@ extern "C" int dne_novelty_batch(dne_handle *h, const uint8_t *archive, const in
     if (h->arch_dim != 128) return h->fail("dne_novelty_batch: the archive must hold 128-byte RAM rows");
     for (int i = 0; i < n; i++)
         if (lengths[i] < 1 || lengths[i] > h->cfg.bc_max_steps) return h->fail("member %d: trajectory length %d outside the recorded capacity %d", i, lengths[i], h->cfg.bc_max_steps);
-    if (novelty_scratch(h, (size_t)n * narch * 2, n)) return -1;
-    HCHECK(h, hipMemcpyAsync(h->nov_len, lengths, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_bc_sqdist_batch, dim3(narch, n), dim3(256), 0, h->stream, (const uint8_t *)h->arch, (const int64_t *)h->arch_row0,
-                       (const int32_t *)h->arch_len, (const uint8_t *)h->bc, (const int32_t *)h->nov_len, h->cfg.bc_max_steps, narch, h->nov_out);
-    HCHECK(h, hipGetLastError());
-    std::vector<long long> ab((size_t)n * narch * 2);
-    HCHECK(h, hipMemcpyAsync(ab.data(), h->nov_out, ab.size() * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    std::vector<double> d(narch);
-    const int kk = std::min(k, narch);
-    for (int i = 0; i < n; i++) {
-        for (int a = 0; a < narch; a++) {   // nses.py:12-20
-            const double na = std::sqrt((double)ab[((size_t)i * narch + a) * 2]), nb = std::sqrt((double)ab[((size_t)i * narch + a) * 2 + 1]);
-            d[a] = std::sqrt(na * na + nb * nb);
-        }
-        std::sort(d.begin(), d.end());      // nses.py:29-31
-        double s = 0;
-        for (int j = 0; j < kk; j++) s += d[j];
-        out[i] = s / kk;
-    }
-    return 0;
+    return novelty_run(h, nullptr, lengths, n, k, out);
 }

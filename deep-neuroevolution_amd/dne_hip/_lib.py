@@ -71,7 +71,7 @@ class Profile(C.Structure):
 
 def build(force=False):
     """Compile libdne_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "env_synth.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dne_hip.h"))
     if os.environ.get("DNE_LIB_PATH"):
         # another build of the same ABI was asked for by name: `make` only knows the in-tree library, so running it here would
@@ -487,6 +487,27 @@ class Engine:
         ln = _arr(np.asarray(lengths).reshape(-1), np.int32)
         out = np.empty(ln.size, np.float64)
         self._ck(self.lib.dne_novelty_batch(self.h, None, None, 0, int(ln.size), _ptr(ln, C.c_int32), int(k), _ptr(out, C.c_double)))
+        return out
+
+    def novelty_knn(self, archive, k, bcs=None, lengths=None):
+        """novelty of a batch on the device (dne_novelty_knn): `bcs` a list of u8[T][dim] host trajectories (lengths from
+        their shapes), or None for the trajectories recorded by the last es_eval / eval_members, `lengths` rows each"""
+        self._sync_archive(archive)
+        if bcs is None:
+            if lengths is None:
+                raise DneError("novelty_knn: the recorded trajectories need their lengths")
+            ln = _arr(np.asarray(lengths).reshape(-1), np.int32)
+            rows, dim = None, RAM_BYTES
+        else:
+            rs = [_arr(b, np.uint8) for b in bcs]
+            rs = [r.reshape(-1, r.shape[-1]) for r in rs]
+            if not rs or len({r.shape[1] for r in rs}) != 1:
+                raise DneError("novelty_knn: bcs must be a non-empty list of trajectories of one width")
+            ln = np.array([r.shape[0] for r in rs], np.int32)
+            rows, dim = np.ascontiguousarray(np.concatenate(rs, axis=0)), rs[0].shape[1]
+        out = np.empty(ln.size, np.float64)
+        self._ck(self.lib.dne_novelty_knn(self.h, _ptr(rows, C.c_uint8), _ptr(ln, C.c_int32), int(ln.size), int(dim), int(k),
+                                          _ptr(out, C.c_double)))
         return out
 
     def profile(self):

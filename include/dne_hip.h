@@ -227,6 +227,14 @@ int dne_novelty(dne_handle *h, const uint8_t *archive /*concatenated rows*/, con
  * never leave the device) against the archive */
 int dne_novelty_batch(dne_handle *h, const uint8_t *archive, const int32_t *archive_len, int narchive, int n,
                       const int32_t *lengths, int k, double *out);
+/* nses.py:22-32 for a batch, on the device: novelty of n trajectories against the resident archive.
+ * bcs == NULL: the n members recorded by the last dne_es_eval / dne_eval_members (record_bc, full trajectories; dim 128,
+ *              lengths[i] in [1, bc_max_steps]);
+ * bcs != NULL: n host trajectories, rows concatenated, lengths[i] >= 1 rows of `dim` bytes each.
+ * A tiled distance kernel (v_dot4_u32_u8 cross terms, exact int64 sums) writes the [n][narchive] distances to device
+ * scratch and a selection kernel sums each member's k smallest in ascending order: only the n results cross PCIe.
+ * dne_novelty (n = 1, host rows) and dne_novelty_batch (the recorded trajectories) are this call behind their own checks. */
+int dne_novelty_knn(dne_handle *h, const uint8_t *bcs, const int32_t *lengths, int n, int dim, int k, double *out);
 
 #ifdef __cplusplus
 }
