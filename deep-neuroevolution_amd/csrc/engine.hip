@@ -558,6 +558,30 @@ __global__ void k_iota(int *p, int n) {
     if (i < n) p[i] = i;
 }
 
+// ------------------------------------------------------------------------------- launch plan
+// The kernel regime of one burst of lock-steps (the active list between two compactions) as a value: plan_step makes it from the
+// handle's knobs, the member set's facts and the active count, and the launchers take it as an argument.  The empty plan is what
+// every caller outside an evaluation passes (dne_act, the reference pass): one window, k_fc or the column-split kernels.
+struct StepPlan {
+    int nsub = 1;            // windows the active list is cut into, each on its own stream
+    bool sub = false;        // every window: k_fc_sub (one wave per sub-slice chain), the head folds its chain sums
+    bool duo = false;        // windows above fc_tail_max groups: table-ordered units (k_unit_order + k_fc_duo + k_out) ...
+    bool duo_solo = false;   // ... one unit per wave instead of two (sparse table: little to share, and twice the waves)
+    bool ring = false;       // ... k_fc_ring instead of k_fc_duo (the windows' convolutions leave activated y2)
+    bool ring_scaled = false; // ... its DMA source the table scaled by the evaluation's sigma (noise_pre)
+    bool fc2 = false;        // else k_fc2 (two pairs per work item share the base rows), else k_fc
+};
+
+// the members of a tail table as arguments of the emulator's kernels (null: no table in force)
+static void set_tail_table(EnvArgs &E, const TailTable *tt) {
+    E.tt_n = tt ? tt->n : 0;
+    if (tt) memcpy(E.tt_member, tt->member, sizeof(E.tt_member));
+}
+
+// a run-time bool as a template argument: f(std::true_type{}) or f(std::false_type{}), so that a launch is written once
+template <class F> static inline void with_bool(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <int V> using int_c = std::integral_constant<int, V>;
+
 // ------------------------------------------------------------------------------- handle
 struct dne_handle {
     dne_config cfg{};
@@ -575,9 +599,7 @@ struct dne_handle {
     int conv_split_mid = 256;        // ... their middle split: conv1 over 4 workgroups up to this many members, conv2 over 2 up to twice as many (DNE_CONV_SPLIT_MID)
     int fc_pairs = 2;                // ES full-width fc: antithetic pairs per work item (DNE_FC_PAIRS, 1 = k_fc<2>)
     int fc2_min_total = 800;         // k_fc2 from this many active groups upwards (DNE_FC2_MIN)
-    bool fc2_now = false;            // decided per burst by eval_core
     int duo_solo_below = 1500;       // DNE_DUO_SOLO_BELOW: with fewer active groups (all windows) every wave takes one unit instead of two (sparse table: little to share, and twice the waves)
-    bool duo_solo_now = false;       // decided per burst by eval_core
     int out_lds_kb = 0;              // DNE_OUT_LDS_KB: an unused LDS reservation that bounds k_out's workgroups per CU (round 2's k_out staged 37 KB of output
                                      // weights and ran best at two workgroups per CU = 64 KB; round 3's stages nothing)
     int duo_head_fused = 0;          // DNE_DUO_HEAD_FUSED: behind k_fc_duo the policy head and the emulator step share a launch (k_tail_step) instead of
@@ -596,7 +618,6 @@ struct dne_handle {
     size_t noise_pre_count = 0;      // entries of the table the copy was made from (0: none)
     float noise_pre_sigma = 0.0f;    // the sigma it holds
     int ring_pre = 1;                // DNE_RING_PRE: 0 = the ring multiplies every row by sigma itself (rounds 5-6a)
-    bool ring_pre_now = false;       // this evaluation's ring launches read noise_pre
     bool pair_sigma_uniform = false; // every pair of the member set is (+s, -s) with ONE s (dne_set_members)
     float pair_sigma = 0.0f;
     float *theta_perm = nullptr;     // [3872 + 16][256]: base slot 0's fc matrix, every row stored as columns l, l+64, l+128, l+192 per lane (k_theta_perm, once per evaluation)
@@ -608,14 +629,12 @@ struct dne_handle {
     int fc_sub_grid = 512;           // DNE_FC_SUB_GRID: workgroups of k_fc_sub at most, 4 waves each (GA 512 = two waves per SIMD; ES: the whole launch resident)
     int fc_sub_prio = 0;             // DNE_FC_SUB_PRIO: s_setprio of k_fc_sub's waves (ES 0: the regime is bound by a window's chain of small kernels, they must not starve; GA: 0 since round 6, 3 on its bounded grid before)
     int fc_sub_head = 1;             // DNE_FC_SUB_HEAD: policy head + emulator step in one launch (k_tail_step) behind k_fc_sub instead of k_out + k_env_logic
-    bool sub_now = false;            // decided per burst by eval_core
     float *y3s = nullptr;            // [member][32][256]: the chain sums k_fc_sub leaves for k_out<.., SUB>
     int duo_grid = 0;                // DNE_DUO_GRID: persistent grid of k_fc_duo (0 = fc_grid)
     int duo_sweep = 2;               // DNE_DUO_SWEEP (0 = off): the four waves of a k_fc_duo workgroup walk one table timeline (1: two units per wave only, 2: also one unit per wave)
     int fc_prio = 3;                 // DNE_FC_PRIO: s_setprio of k_fc_duo's waves (0-3)
     int duo_lag = 0;                 // DNE_DUO_LAG: extra row batches by which the second unit of a duo trails the first
     int fc_duo = 1, fc_duo_min = 451;   // DNE_FC_DUO / DNE_FC_DUO_MIN: table-ordered fc (k_unit_order + k_fc_duo + k_out) from this many active groups (round 4: 451, right above the sub-slice fc's range; 800 before -- with one k_fc_duo workgroup per CU a 625-pair share takes 84.5 instead of 88.4 ms per generation)
-    bool duo_now = false;            // decided per burst by eval_core (the unit order of each window is rebuilt then)
     int *unit_order = nullptr;       // [4 * groups]: per window, its (group, k-slice) units in noise-table order
     int spec_max = 4;                // DNE_SPEC_MAX: a single window of up to this many members (2 antithetic pairs; round 2: 8 -- the faster tail kernels of round 3 beat speculation at 4 pairs, 47 vs 56 us) steps speculatively -- every action's outcome is worked out under the forward pass; 0 = off
     uint8_t *spec_prev = nullptr, *spec_cur = nullptr, *spec_stacks = nullptr;
@@ -623,7 +642,6 @@ struct dne_handle {
     float *spec_y1 = nullptr;
     int spec_bands = 7;              // DNE_SPEC_BANDS: 256-thread workgroups per candidate frame
     int spec_conv1 = 1;              // DNE_SPEC_CONV1: conv1 of every candidate stack in the launch that picks the action
-    bool ring_now = false;           // this burst's table-ordered windows run k_fc_ring (their convolutions leave activated y2)
     bool uniform_base = false;       // every member perturbs the same base slot (dne_set_members checks)
     bool antithetic_slot0 = false;   // what k_theta_perm + k_fc_ring assume, checked member by member in dne_set_members: base slot 0 everywhere and
                                      // members (2i, 2i+1) = (offset, +s), (the same offset, -s) -- es.py:412-419's pairs, nothing else
@@ -647,7 +665,6 @@ struct dne_handle {
     int conv1_shared = 1;            // DNE_CONV1_SHARED: reference-pass conv1 with eight members sharing a frame in LDS
     int32_t *m_slot = nullptr; int64_t *m_off = nullptr; float *m_scale = nullptr;
     std::vector<int32_t> host_slot; std::vector<int64_t> host_off; std::vector<float> host_scale;   // what dne_set_members uploaded
-    TailTable tt{}; bool tt_on = false;   // the current burst's window as kernel arguments (at most TT_MAX members left)
     int tt_enable = 1;               // DNE_TAIL_TABLE
     int head_threads = 320;          // DNE_HEAD_THREADS: 320 = the policy head's four waves + a fifth that steps the emulator for every action meanwhile; 256 = one lane steps it afterwards
     float *bn = nullptr, *bn_mom = nullptr;
@@ -760,23 +777,22 @@ struct dne_handle {
         err = buf;
         return -1;
     }
-    FwdArgs fwd(bool use_done) const {
+    FwdArgs fwd(bool use_done, const StepPlan &p = {}, const TailTable *tt = nullptr) const {
         FwdArgs A;
         A.noise = noise; A.bases = bases; A.base_stride = base_stride;
         A.m_slot = m_slot; A.m_off = m_off; A.m_scale = m_scale; A.bn = bn; A.bn_mom = bn_mom;
         A.done = use_done ? done : nullptr; A.L = L;
-        A.sub_sums = sub_now ? 1 : 0;
-        if (tt_on) A.tt = tt; else A.tt.n = 0;
+        A.sub_sums = p.sub ? 1 : 0;
+        if (tt) A.tt = *tt; else A.tt.n = 0;
         return A;
     }
-    EnvArgs env(int bc_mode) const {
+    EnvArgs env(int bc_mode, const TailTable *tt = nullptr) const {
         EnvArgs E;
         E.ram_prev = ram_prev; E.ram_cur = ram_cur; E.stacks = stacks; E.T = tables;
         E.ret = ret; E.sign = sign; E.step_reward = step_reward; E.len = len; E.done = done; E.stepped = stepped; E.action = action; E.step_counter = nullptr;
         E.bc = bc; E.bc_mode = bc ? bc_mode : 0; E.bc_max_steps = cfg.bc_max_steps; E.immortal = dbg_immortal;
         E.spec_prev = spec_prev; E.spec_cur = spec_cur; E.spec_rw = spec_rw; E.spec_stacks = spec_stacks; E.spec_y1 = spec_y1;
-        E.tt_n = tt_on ? tt.n : 0;
-        if (tt_on) memcpy(E.tt_member, tt.member, sizeof(E.tt_member));
+        set_tail_table(E, tt);
         return E;
     }
     hipEvent_t event(size_t i) {
@@ -1063,7 +1079,6 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
     env_int("DNE_RENDER_BANDS", 1, 84, &h->render_bands);
     env_int("DNE_RENDER_WG_MAX", 1, 1 << 20, &h->render_wg_max);
     env_int("DNE_FC_CHAIN_MIN", 1, 1 << 30, &h->fc_chain_min);
-    env_int("DNE_FC_RB", 2, 8, &h->fc_rb);
     env_int("DNE_FC_GRID", 1, 1 << 16, &h->fc_grid);
     for (int s = 1; s < 4; s++) { hipStream_t st; CH(hipStreamCreate(&st)); h->sub_streams.push_back(st); }   // more than four windows measured slower (round 3, 5 / 6 / 8 at full width: +7.5 / +5.4 / +7.2 %; round 4 with one k_fc_duo workgroup per CU: +8.4 / +5.9 / +4.4 %)
     make_layout(cfg->policy_kind, cfg->n_actions, &h->L);
@@ -1608,37 +1623,34 @@ extern "C" int dne_get_bn_moments(dne_handle *h, int n, float *out) {
 }
 
 // one policy decision for the groups in `list` (count groups of gsize members)
-static void launch_forward(dne_handle *h, const int *list, int count, int gsize, bool use_done, hipStream_t st = nullptr,
-                           bool act2 = false /* leave relu(bn2(y2)) instead of y2: the window's fc is k_fc_ring */) {
+// (p, tt: the burst's plan and tail table inside an evaluation; the empty plan and no table everywhere else)
+static void launch_forward(dne_handle *h, const StepPlan &p, const TailTable *tt, const int *list, int count, int gsize, bool use_done,
+                           hipStream_t st = nullptr) {
     if (!st) st = h->stream;
-    const FwdArgs A = h->fwd(use_done);
+    const FwdArgs A = h->fwd(use_done, p, tt);
     if (h->large) {   // LargeModel: three matrix-core convolutions (forward_large.h); members are single (GA)
         constexpr size_t l2 = lconv_mfma_lds_bytes<32, 4, 2, 11, 34>(), l3 = lconv_mfma_lds_bytes<64, 3, 1, 11, 68>();
         hipLaunchKernelGGL(k_lconv1, dim3(count * 2), dim3(256), 0, st, A, list, (const uint8_t *)h->stacks, h->y1);
         const int ns = count <= 128 ? 4 : count <= 256 ? 2 : 1;   // few members: one workgroup per 16-channel tile
-        if (h->members_materialized) {
-            hipLaunchKernelGGL((k_lconv_mfma<32, 64, 4, 2, 21, 11, 1, 34, false>), dim3(count * ns), dim3(256), l2, st, A, list, A.L.c2w, A.L.c2b, (const float *)h->y1, h->y2, ns);
-            hipLaunchKernelGGL((k_lconv_mfma<64, 64, 3, 1, 11, 11, 1, 68, false>), dim3(count * ns), dim3(256), l3, st, A, list, A.L.c3w, A.L.c3b, (const float *)h->y2, h->y3, ns);
-        } else {
-            hipLaunchKernelGGL((k_lconv_mfma<32, 64, 4, 2, 21, 11, 1, 34, true>), dim3(count * ns), dim3(256), l2, st, A, list, A.L.c2w, A.L.c2b, (const float *)h->y1, h->y2, ns);
-            hipLaunchKernelGGL((k_lconv_mfma<64, 64, 3, 1, 11, 11, 1, 68, true>), dim3(count * ns), dim3(256), l3, st, A, list, A.L.c3w, A.L.c3b, (const float *)h->y2, h->y3, ns);
-        }
+        with_bool(!h->members_materialized, [&](auto NOISE) {
+            hipLaunchKernelGGL((k_lconv_mfma<32, 64, 4, 2, 21, 11, 1, 34, NOISE()>), dim3(count * ns), dim3(256), l2, st, A, list, A.L.c2w, A.L.c2b, (const float *)h->y1, h->y2, ns);
+            hipLaunchKernelGGL((k_lconv_mfma<64, 64, 3, 1, 11, 11, 1, 68, NOISE()>), dim3(count * ns), dim3(256), l3, st, A, list, A.L.c3w, A.L.c3b, (const float *)h->y2, h->y3, ns);
+        });
         return;
     }
     const bool es = es_like(h->L.kind);
+    const bool act2 = p.ring && count > h->fc_tail_max;   // the window's fc is k_fc_ring: leave relu(bn2(y2)) instead of y2 (ES pairs only)
     const int items = count * gsize;
     // few members left: several workgroups per member (conv1: 28 position tiles over 4 or 7 workgroups; conv2: 8 over 2 or 4)
     const int s1 = items <= h->conv_split_max ? 7 : items <= h->conv_split_mid ? 4 : 1, s2 = items <= h->conv_split_max ? 4 : items <= 2 * h->conv_split_mid ? 2 : 1;
     if (h->conv_fused && items >= h->conv_fused_min && !h->dbg_skip) {   // one workgroup per member through both convolutions, y1 stays in LDS
         float *y1 = use_done ? nullptr : h->y1;                           // dne_act / debug_activations want y1; evaluations do not
-        if (es) hipLaunchKernelGGL((k_conv12<true>), dim3(items), dim3(256), sizeof(Conv12Lds), st, A, list, gsize, (const uint8_t *)h->stacks, y1, h->y2, act2 ? 1 : 0);
-        else hipLaunchKernelGGL((k_conv12<false>), dim3(items), dim3(256), sizeof(Conv12Lds), st, A, list, gsize, (const uint8_t *)h->stacks, y1, h->y2, 0);
+        with_bool(es, [&](auto ES) { hipLaunchKernelGGL((k_conv12<ES()>), dim3(items), dim3(256), sizeof(Conv12Lds), st, A, list, gsize, (const uint8_t *)h->stacks, y1, h->y2, act2 ? 1 : 0); });
         return;
     }
     if (items <= h->conv12t_max && !h->dbg_skip) {   // the tail: four workgroups per member through both convolutions, no y1 round trip
         float *y1 = use_done ? nullptr : h->y1;
-        if (es) hipLaunchKernelGGL((k_conv12t<true>), dim3(items * 4), dim3(512), sizeof(Conv12Lds), st, A, list, gsize, (const uint8_t *)h->stacks, y1, h->y2);
-        else hipLaunchKernelGGL((k_conv12t<false>), dim3(items * 4), dim3(512), sizeof(Conv12Lds), st, A, list, gsize, (const uint8_t *)h->stacks, y1, h->y2);
+        with_bool(es, [&](auto ES) { hipLaunchKernelGGL((k_conv12t<ES()>), dim3(items * 4), dim3(512), sizeof(Conv12Lds), st, A, list, gsize, (const uint8_t *)h->stacks, y1, h->y2); });
         if (act2) hipLaunchKernelGGL(k_y2_activate, dim3(items), dim3(256), 0, st, A, list, gsize, h->y2);
         return;
     }
@@ -1646,25 +1658,32 @@ static void launch_forward(dne_handle *h, const int *list, int count, int gsize,
     hipLaunchKernelGGL(k_conv1, dim3(items * s1), dim3(256), 0, st, A, list, gsize, 1, 0,
                        (const uint8_t *)h->stacks, (const uint8_t *)nullptr, h->y1, s1);
     if (h->dbg_skip & 2) return;
-    if (es) hipLaunchKernelGGL((k_conv2<true>), dim3(items * s2), dim3(256), 0, st, A, list, gsize, 1, 0, (const float *)h->y1, h->y2, s2, (float *)nullptr);
-    else hipLaunchKernelGGL((k_conv2<false>), dim3(items * s2), dim3(256), 0, st, A, list, gsize, 1, 0, (const float *)h->y1, h->y2, s2, (float *)nullptr);
+    with_bool(es, [&](auto ES) { hipLaunchKernelGGL((k_conv2<ES()>), dim3(items * s2), dim3(256), 0, st, A, list, gsize, 1, 0, (const float *)h->y1, h->y2, s2, (float *)nullptr); });
     if (act2) hipLaunchKernelGGL(k_y2_activate, dim3(items), dim3(256), 0, st, A, list, gsize, h->y2);
 }
 
-static void launch_fc(dne_handle *h, const int *list, int count, int gsize, float *logits, hipStream_t st = nullptr,
-                      bool out_fused = false /* tail only: the caller runs k_tail_step instead of k_out */,
+// the kernel launch_fc picks for a window of `count` groups (messages only)
+static const char *fc_name(const dne_handle *h, const StepPlan &p, int count) {
+    if (h->large) return count <= h->lfc_cols_max ? "k_lfc_cols" : "k_lfc";
+    if (p.sub) return "k_fc_sub";
+    if (count <= h->fc_tail_max) return "tail";
+    if (p.duo) return p.ring ? "k_fc_ring" : "k_fc_duo";
+    return p.fc2 ? "k_fc2" : "k_fc";
+}
+
+static void launch_fc(dne_handle *h, const StepPlan &p, const TailTable *tt, const int *list, int count, int gsize, float *logits,
+                      hipStream_t st = nullptr, bool out_fused = false /* the caller runs k_tail_step instead of k_out */,
                       const int *order = nullptr /* the window's units in noise-table order (k_unit_order), duo regime only */,
                       hipEvent_t after_stream_kernel = nullptr /* duo regime: recorded between k_fc_duo and k_out (profiling) */) {
     if (!st) st = h->stream;
     // inside an evaluation (no logits requested) groups whose members are all done are skipped: they stay in the list until
     // the next compaction, and streaming their weights would be wasted bandwidth
-    const FwdArgs A = h->fwd(logits == nullptr);
+    const FwdArgs A = h->fwd(logits == nullptr, p, tt);
     const bool es = es_like(h->L.kind);
     if (h->large) {   // LargeModel: streamed 7744 x 512 fc (two 256-column halves per member), then relu + output layer + argmax
         const dim3 lg(std::min(2 * count, 2 * h->fc_grid));
         if (count <= h->lfc_cols_max) {   // few members: eight workgroups each
-            if (h->members_materialized) hipLaunchKernelGGL((k_lfc_cols<false>), dim3(8 * count), dim3(256), 0, st, A, list, (const float *)h->y3, h->y3t);
-            else hipLaunchKernelGGL((k_lfc_cols<true>), dim3(8 * count), dim3(256), 0, st, A, list, (const float *)h->y3, h->y3t);
+            with_bool(!h->members_materialized, [&](auto NOISE) { hipLaunchKernelGGL((k_lfc_cols<NOISE()>), dim3(8 * count), dim3(256), 0, st, A, list, (const float *)h->y3, h->y3t); });
         } else if (h->members_materialized) {
             if (h->fc_rb == 8 && h->lfc_pad == 1) hipLaunchKernelGGL((k_lfc<false, 8, 1>), lg, dim3(256), 0, st, A, list, 2 * count, (const float *)h->y3, h->y3t);
             else if (h->fc_rb == 8 && h->lfc_pad == 2) hipLaunchKernelGGL((k_lfc<false, 8, 2>), lg, dim3(256), 0, st, A, list, 2 * count, (const float *)h->y3, h->y3t);
@@ -1674,46 +1693,45 @@ static void launch_fc(dne_handle *h, const int *list, int count, int gsize, floa
         hipLaunchKernelGGL(k_lout, dim3(count), dim3(256), 0, st, A, list, (const float *)h->y3t, h->action, logits);
         return;
     }
-    if (h->sub_now && !logits && h->y3s) {   // mid range: one wave per sub-slice chain, folded by the head
+    if (p.sub) {   // mid range: one wave per sub-slice chain, folded by the head
         const int total_waves_at_1 = 32 * count;
         // sub-slices per wave: about 8000 waves (one round of the whole machine) whatever the width
         const int spw = h->fc_sub_spw ? h->fc_sub_spw : count * h->fc_sub_nsub <= 320 ? 1 : count * h->fc_sub_nsub <= 640 ? 2 : count * h->fc_sub_nsub <= 1280 ? 4 : 8;
         const int waves = total_waves_at_1 / spw, blocks = std::min((waves + 3) / 4, h->fc_sub_grid);
-        // eval_core's sub_regime admits exactly two populations: ES pairs and GA children written out
-        if (es) hipLaunchKernelGGL((k_fc_sub<2, true, true>), dim3(blocks), dim3(256), 0, st, A, list, count, spw, h->fc_sub_prio, (const float *)h->y2, h->y3s);
-        else hipLaunchKernelGGL((k_fc_sub<1, false, false>), dim3(blocks), dim3(256), 0, st, A, list, count, spw, h->fc_sub_prio, (const float *)h->y2, h->y3s);
-        if (out_fused) return;   // the caller runs k_tail_step (FwdArgs::sub_sums tells it to fold the chain sums)
-        if (es) hipLaunchKernelGGL((k_out<2, true>), dim3(count), dim3(256), 0, st, A, list, (const float *)h->y3s, h->y3, h->action, (float *)nullptr);
-        else hipLaunchKernelGGL((k_out<1, false>), dim3(count), dim3(256), 0, st, A, list, (const float *)h->y3s, h->y3, h->action, (float *)nullptr);
+        // plan_step admits exactly two populations: ES pairs and GA children written out
+        with_bool(es, [&](auto ES) {
+            constexpr int NV = ES() ? 2 : 1;
+            hipLaunchKernelGGL((k_fc_sub<NV, ES(), ES()>), dim3(blocks), dim3(256), 0, st, A, list, count, spw, h->fc_sub_prio, (const float *)h->y2, h->y3s);
+            if (out_fused) return;   // the caller runs k_tail_step (FwdArgs::sub_sums tells it to fold the chain sums)
+            hipLaunchKernelGGL((k_out<NV, ES()>), dim3(count), dim3(256), 0, st, A, list, (const float *)h->y3s, h->y3, h->action, (float *)nullptr);
+        });
         return;
     }
     if (count <= h->fc_tail_max) {   // latency-bound regime: 4 workgroups per group + a separate output-layer kernel
-#define FCT(NV, BN)                                                                                                          \
-    do {                                                                                                                     \
-        if (NV == 1 && !BN && h->members_materialized) {   /* GA children written out: plain rows, no noise stream */        \
-            if (count <= h->fc_quad_max) hipLaunchKernelGGL((k_fc_quad<1, false, false>), dim3(count * 64), dim3(256), 0, st, A, list, (const float *)h->y2, h->y3t); \
-            else hipLaunchKernelGGL((k_fc_tail<1, false, false>), dim3(count * 16), dim3(512), 0, st, A, list, (const float *)h->y2, h->y3t); \
-        } else if (count <= h->fc_quad_max) hipLaunchKernelGGL((k_fc_quad<NV, BN>), dim3(count * 64), dim3(256), 0, st, A, list, (const float *)h->y2, h->y3t); \
-        else if (count <= h->fc_tailk_max) hipLaunchKernelGGL((k_fc_tail<NV, BN>), dim3(count * 16), dim3(512), 0, st, A, list, (const float *)h->y2, h->y3t); \
-        else hipLaunchKernelGGL((k_fc_cols<NV, BN>), dim3(count * 4), dim3(256), 0, st, A, list, (const float *)h->y2, h->y3t); \
-        if (!out_fused) hipLaunchKernelGGL((k_out<NV, BN>), dim3(count), dim3(256), 0, st, A, list, (const float *)h->y3t, h->y3, h->action, logits); \
-    } while (0)
-        if (gsize == 2) { if (es) FCT(2, true); else FCT(2, false); }
-        else { if (es) FCT(1, true); else FCT(1, false); }
-#undef FCT
+        with_bool(gsize == 2, [&](auto PAIRS) { with_bool(es, [&](auto ES) {
+            constexpr int NV = PAIRS() ? 2 : 1;
+            constexpr bool BN = ES();
+            if (NV == 1 && !BN && h->members_materialized) {   // GA children written out: plain rows, no noise stream
+                if (count <= h->fc_quad_max) hipLaunchKernelGGL((k_fc_quad<1, false, false>), dim3(count * 64), dim3(256), 0, st, A, list, (const float *)h->y2, h->y3t);
+                else hipLaunchKernelGGL((k_fc_tail<1, false, false>), dim3(count * 16), dim3(512), 0, st, A, list, (const float *)h->y2, h->y3t);
+            } else if (count <= h->fc_quad_max) hipLaunchKernelGGL((k_fc_quad<NV, BN>), dim3(count * 64), dim3(256), 0, st, A, list, (const float *)h->y2, h->y3t);
+            else if (count <= h->fc_tailk_max) hipLaunchKernelGGL((k_fc_tail<NV, BN>), dim3(count * 16), dim3(512), 0, st, A, list, (const float *)h->y2, h->y3t);
+            else hipLaunchKernelGGL((k_fc_cols<NV, BN>), dim3(count * 4), dim3(256), 0, st, A, list, (const float *)h->y2, h->y3t);
+            if (!out_fused) hipLaunchKernelGGL((k_out<NV, BN>), dim3(count), dim3(256), 0, st, A, list, (const float *)h->y3t, h->y3, h->action, logits);
+        }); });
         return;
     }
-    if (h->duo_now && !logits && order && gsize == 2 && es) {   // table-ordered units: adjacent (pair, k-slice) units share their noise rows
-        const bool solo = h->duo_solo_now;
+    if (p.duo) {   // table-ordered units: adjacent (pair, k-slice) units share their noise rows (ES pairs only: plan_step)
+        const bool solo = p.duo_solo;
         const bool sweep = h->duo_sweep && (!solo || h->duo_sweep > 1);
         const int duo_grid = h->duo_grid ? h->duo_grid : h->fc_grid;
         const int n_units = 4 * count, items = ((solo ? n_units : (n_units + 1) / 2) + 3) / 4, blocks = std::min(items, duo_grid);
         const size_t out_lds = (size_t)h->out_lds_kb * 1024;   // an LDS reservation nobody uses: it only bounds k_out's workgroups per CU next to the streaming fc
         const int flags = h->duo_lag | (solo ? 256 : 0) | (h->fc_prio << 9) | ((h->duo_sync - 1) << 11);
-        if (h->ring_now) {   // one unit per wave, eight units per workgroup whatever the regime
+        if (p.ring) {   // one unit per wave, eight units per workgroup whatever the regime
             const int ring_blocks = std::min((n_units + 7) / 8, duo_grid);
-            if (h->ring_pre_now) hipLaunchKernelGGL((k_fc_ring<true, 8>), dim3(ring_blocks), dim3(576), 0, st, A, order, n_units, (const float *)h->y2, h->y3t, (const float *)h->theta_perm, h->fc_prio << 9, (const float *)h->noise_pre);
-            else hipLaunchKernelGGL((k_fc_ring<false, 8>), dim3(ring_blocks), dim3(576), 0, st, A, order, n_units, (const float *)h->y2, h->y3t, (const float *)h->theta_perm, h->fc_prio << 9, (const float *)A.noise);
+            const float *table = p.ring_scaled ? h->noise_pre : A.noise;
+            with_bool(p.ring_scaled, [&](auto PRE) { hipLaunchKernelGGL((k_fc_ring<PRE(), 8>), dim3(ring_blocks), dim3(576), 0, st, A, order, n_units, (const float *)h->y2, h->y3t, (const float *)h->theta_perm, h->fc_prio << 9, table); });
         }
         else if (sweep && h->duo_fat) hipLaunchKernelGGL((k_fc_duo<2, true, true, 8, true>), dim3(blocks), dim3(256), 0, st, A, order, n_units, (const float *)h->y2, h->y3t, flags);
         else if (sweep) hipLaunchKernelGGL((k_fc_duo<2, true, true>), dim3(blocks), dim3(256), 0, st, A, order, n_units, (const float *)h->y2, h->y3t, flags);
@@ -1723,29 +1741,27 @@ static void launch_fc(dne_handle *h, const int *list, int count, int gsize, floa
         hipLaunchKernelGGL((k_out<2, true>), dim3(count), dim3(256), out_lds, st, A, list, (const float *)h->y3t, h->y3, h->action, (float *)nullptr);
         return;
     }
-    if (gsize == 2 && es && h->uniform_base && h->fc2_now && !logits) {   // two pairs per work item share the base rows
+    if (p.fc2) {   // two pairs per work item share the base rows (ES pairs over one base slot only: plan_step)
         const int items = (count + 1) / 2, blocks = std::min(items, h->fc_grid);
-        if (h->fc_rb == 2) hipLaunchKernelGGL((k_fc2<true, 2>), dim3(blocks), dim3(256), 0, st, A, list, count, (const float *)h->y2, h->y3, h->action);
-        else hipLaunchKernelGGL((k_fc2<true, 4>), dim3(blocks), dim3(256), 0, st, A, list, count, (const float *)h->y2, h->y3, h->action);
+        with_bool(h->fc_rb == 2, [&](auto RB2) { hipLaunchKernelGGL((k_fc2<true, RB2() ? 2 : 4>), dim3(blocks), dim3(256), 0, st, A, list, count, (const float *)h->y2, h->y3, h->action); });
         return;
     }
     const int fc_blocks = std::min(count, h->fc_grid);   // persistent grid (an even groups-per-block split measured slower)
-#define FC(NV, BN, RB) hipLaunchKernelGGL((k_fc<NV, false, BN, RB>), dim3(fc_blocks), dim3(256), 0, st, A, list, count, 1, 0, (const float *)h->y2, h->y3, h->action, logits)
-#define FCR(NV, BN) do { if (h->fc_rb == 2) FC(NV, BN, 2); else if (h->fc_rb == 8) FC(NV, BN, 8); else FC(NV, BN, 4); } while (0)
     if (gsize == 1 && !es && h->members_materialized) {   // GA children written out once per generation: plain rows, no noise stream
-        if (h->fc_rb == 8) hipLaunchKernelGGL((k_fc<1, false, false, 8, false>), dim3(fc_blocks), dim3(256), 0, st, A, list, count, 1, 0, (const float *)h->y2, h->y3, h->action, logits);
-        else hipLaunchKernelGGL((k_fc<1, false, false, 4, false>), dim3(fc_blocks), dim3(256), 0, st, A, list, count, 1, 0, (const float *)h->y2, h->y3, h->action, logits);
-    } else if (gsize == 2) { if (es) FCR(2, true); else FCR(2, false); }
-    else { if (es) FCR(1, true); else FCR(1, false); }
-#undef FCR
-#undef FC
+        with_bool(h->fc_rb == 8, [&](auto RB8) { hipLaunchKernelGGL((k_fc<1, false, false, RB8() ? 8 : 4, false>), dim3(fc_blocks), dim3(256), 0, st, A, list, count, 1, 0, (const float *)h->y2, h->y3, h->action, logits); });
+        return;
+    }
+    with_bool(gsize == 2, [&](auto PAIRS) { with_bool(es, [&](auto ES) {
+        auto fc = [&](auto RB) { hipLaunchKernelGGL((k_fc<PAIRS() ? 2 : 1, false, ES(), RB()>), dim3(fc_blocks), dim3(256), 0, st, A, list, count, 1, 0, (const float *)h->y2, h->y3, h->action, logits); };
+        if (h->fc_rb == 2) fc(int_c<2>{}); else if (h->fc_rb == 8) fc(int_c<8>{}); else fc(int_c<4>{});
+    }); });
 }
 
 extern "C" int dne_act(dne_handle *h, int n, int32_t *actions, float *logits) {
     DeviceGuard dg(h);
     if (check_n(h, n)) return -1;
-    launch_forward(h, nullptr, n, 1, false);
-    launch_fc(h, nullptr, n, 1, h->logits);
+    launch_forward(h, StepPlan{}, nullptr, nullptr, n, 1, false);
+    launch_fc(h, StepPlan{}, nullptr, nullptr, n, 1, h->logits);
     HCHECK(h, hipGetLastError());
     HCHECK(h, hipStreamSynchronize(h->stream));
     if (actions) HCHECK(h, hipMemcpy(actions, h->action, n * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -1778,17 +1794,150 @@ extern "C" int dne_debug_activations_large(dne_handle *h, int member, float *y1,
 }
 
 // ------------------------------------------------------------------------------- batch evaluation
+// The regime of a burst that starts with `total` active groups of `gsize` members.  One global list of active groups, compacted every burst; within a burst
+// the list is cut into nsub equal windows, each stepped on its own stream, so that while one window streams its noise slices (HBM) the others run their MFMA
+// convolutions and emulator frames.  whole_eval: the same conditions classify an evaluation by the width it STARTS with (which launches carry profiling
+// events, dne_profile.fc_full_kind); the two terms that differ between the two uses are marked.
+static StepPlan plan_step(const dne_handle *h, int total, int gsize, bool whole_eval = false) {
+    const bool es = es_like(h->L.kind), pairs = es && gsize == 2;
+    StepPlan p;
+    // the sub-slice fc's range: GA children written out (plain rows), optionally ES pairs (DNE_FC_SUB=2); never the LargeModel
+    if (!h->large && h->y3s && total >= h->fc_sub_min && total <= h->fc_sub_max)
+        p.sub = es ? h->fc_sub >= 2 && gsize == 2 && total < h->fc_duo_min : h->fc_sub >= 1 && gsize == 1 && h->members_materialized;
+    // nsub follows the active count (tools/kbench.py sweeps): k_fc2 wants 3 windows at full width and 4 in the upper mid range; below
+    // ~400 groups the windows are sized to fit the column-split tail kernels (<= fc_tail_max groups each); one when only a handful of episodes are left
+    int k = total >= 1900 ? h->nsub_full : total >= h->fc2_min_total ? h->nsub_mid : total > 4 * h->fc_tail_max ? 3
+          : total >= 48 ? std::max(2, (total + h->fc_tail_max - 1) / h->fc_tail_max) : 1;
+    if (p.sub) k = h->fc_sub_nsub;
+    if (h->nsub_fixed > 0) k = h->nsub_fixed;
+    k = std::min(k, (int)h->sub_streams.size());
+    p.nsub = std::max(1, std::min(k, total));
+    // a burst inside the sub-slice fc's range runs no k_fc2; an evaluation that starts there with k_fc2 enabled at that width
+    // (DNE_FC2_MIN lowered into the range) still counts as a k_fc2 evaluation, whose profiled launches are the k_fc2 ones
+    p.fc2 = h->fc_pairs == 2 && pairs && h->uniform_base && total >= h->fc2_min_total && (whole_eval || !p.sub);
+    // table-ordered units (never inside the sub-slice fc's range, which ends below fc_duo_min).  k_unit_order ranks a window's keys
+    // in LDS: a burst whose windows are too long for it falls back to k_fc2 / k_fc; the evaluation's kind ignores that bound
+    const bool order_fits = (size_t)4 * ((total + p.nsub - 1) / p.nsub) * sizeof(long long) <= 160 * 1024;
+    p.duo = !h->large && h->fc_duo && pairs && total >= h->fc_duo_min && (whole_eval || order_fits);
+    p.duo_solo = total < h->duo_solo_below;
+    // the ring's range: pairs as dense in their stretch of the table as DNE_DUO_SOLO_BELOW (1500) pairs over the whole table, and enough of them to
+    // fill the chip (DNE_RING_MIN) -- at one GPU "1500 of 2500 active", on a rank of two with its own half of the table "1000 of 1250"
+    const bool dense = (double)total * h->dense_scale >= (double)h->duo_solo_below && total >= h->ring_min;
+    p.ring = p.duo && h->theta_perm && h->antithetic_slot0 && h->duo_sweep && (h->ring_on > 1 || dense) && (dense || h->duo_sweep > 1);
+    p.ring_scaled = p.ring && h->ring_pre && h->pair_sigma_uniform && h->noise_pre;   // (ring_scaled_table has filled it: the evaluation started at least as wide)
+    return p;
+}
+
+// tail table: with at most TT_MAX members left, all in one window, the member descriptors ride in the kernel arguments.
+// Fills *tt from the active groups in list order (host_list null = 0, 1, 2, ...) and returns it, or null when no table is in force.
+static const TailTable *make_tail_table(const dne_handle *h, TailTable *tt, const int *host_list, int total, int gsize, int n) {
+    if (!h->tt_enable || h->large || total * gsize > TT_MAX || (int)h->host_off.size() < n || plan_step(h, total, gsize).nsub != 1) return nullptr;
+    tt->n = total * gsize;
+    for (int i = 0; i < total; i++)
+        for (int v = 0; v < gsize; v++) {
+            const int m = (host_list ? host_list[i] : i) * gsize + v, k = i * gsize + v;
+            tt->member[k] = m; tt->slot[k] = h->host_slot[m]; tt->scale[k] = h->host_scale[m]; tt->off[k] = h->host_off[m];
+        }
+    return tt;
+}
+
+// the ring's DMA source: the table scaled by this evaluation's sigma (k_fc_ring<true>), made once per (table, sigma)
+static int ring_scaled_table(dne_handle *h) {
+    if (!h->ring_pre || !h->pair_sigma_uniform) return 0;
+    if (!h->noise_pre && h->alloc(&h->noise_pre, h->noise_count + OVERFETCH_FLOATS, "noise_pre")) {
+        h->trace("no room for the scaled table: the ring scales its rows itself");
+        (void)hipGetLastError(); h->noise_pre = nullptr; h->ring_pre = 0;
+        return 0;
+    }
+    if (h->noise_pre_count != h->noise_count || h->noise_pre_sigma != h->pair_sigma) {
+        static_assert(OVERFETCH_FLOATS % 4 == 0, "k_scale_table moves 16 bytes per step");
+        const size_t n4 = (h->noise_count + OVERFETCH_FLOATS) / 4;   // (a table whose count is not a multiple of four leaves its last 1-3 padding floats unscaled: zeros either way)
+        hipLaunchKernelGGL(k_scale_table, dim3(256 * 8), dim3(256), 0, h->stream, (const float *)h->noise, h->noise_pre, n4, h->pair_sigma);
+        HCHECK(h, hipStreamSynchronize(h->stream));   // the windows' streams start behind the host
+        h->noise_pre_count = h->noise_count; h->noise_pre_sigma = h->pair_sigma;
+        h->trace("noise table scaled by %g for the ring", (double)h->pair_sigma);
+    }
+    return 0;
+}
+
+// speculative tail: the emulator + renderer outcome of every action, inside the launches of this step's forward pass
+// fresh: no conv1 candidates from the previous lock-step (a new burst = a new list); next_conv1: the choice + conv1 of every candidate (not in a burst's last lock-step)
+static void launch_spec_tail(dne_handle *h, const StepPlan &p, const TailTable *tt, const EnvArgs &E, const int *lst, int cnt, int gsize, int tslimit, hipStream_t sst, bool fresh, bool next_conv1) {
+    const int items = cnt * gsize, nact = h->cfg.n_actions, nb = h->spec_bands;
+    const FwdArgs A = h->fwd(true, p, tt);
+    const int emu_blocks = (items * nact + 255) / 256;
+    with_bool(es_like(h->L.kind), [&](auto ES) {
+        if (fresh) {
+            hipLaunchKernelGGL(k_conv1_spec, dim3(items * 7 + emu_blocks), dim3(256), 0, sst, A, E, lst, gsize, h->y1, 7, items * 7, items, nact);
+            hipLaunchKernelGGL((k_conv2<ES()>), dim3(items * 4), dim3(256), 0, sst, A, lst, gsize, 1, 0, (const float *)h->y1, h->y2, 4, (float *)nullptr);
+        } else hipLaunchKernelGGL((k_conv2_spec<ES()>), dim3(items * 4 + emu_blocks), dim3(256), 0, sst, A, E, lst, gsize, (const float *)h->y1, h->y2, 4, items * 4, items, nact, (const int32_t *)h->action);
+        with_bool(gsize == 2, [&](auto PAIRS) { hipLaunchKernelGGL((k_fc_quad_spec<PAIRS() ? 2 : 1, ES()>), dim3(cnt * 64 + items * nact * nb), dim3(256), 0, sst, A, E, lst, gsize, (const float *)h->y2, h->y3t, cnt * 64, nact, nb); });
+        if (next_conv1) hipLaunchKernelGGL((k_tail_select_conv1<ES()>), dim3(items + items * nact * 7), dim3(256), 0, sst, A, E, lst, gsize, tslimit, (const float *)h->y3t, h->y3, h->action, items, nact, 7);
+        else hipLaunchKernelGGL((k_tail_select<ES()>), dim3(items), dim3(256), 0, sst, A, E, lst, gsize, tslimit, (const float *)h->y3t, h->y3, h->action);
+    });
+}
+
+// behind an fc that left partial sums (launch_fc with out_fused): policy head + emulator step in one launch (k_tail_step), and the frames.
+// tail: few members left -- each frame over nb workgroups, or (nb = 1) rendered by that same launch; else behind k_fc_duo / k_fc_sub
+static void launch_head_step(dne_handle *h, const StepPlan &p, const TailTable *tt, const EnvArgs &E, const int *lst, int cnt, int gsize, int tslimit, hipStream_t sst, bool tail) {
+    const FwdArgs A = h->fwd(false, p, tt);
+    const int items = cnt * gsize;
+    const float *sums = p.sub ? h->y3s : h->y3t;
+    int nb = tail ? h->render_bands : 1;
+    while (nb > 1 && items * nb > h->render_wg_max) nb /= 2;
+    const bool render_fused = tail ? nb == 1 : h->sub_render_fused && p.sub && !(h->dbg_skip & 4);   // head + emulator + renderer in one launch
+    with_bool(es_like(h->L.kind), [&](auto ES) { with_bool(render_fused, [&](auto R) { hipLaunchKernelGGL((k_tail_step<ES(), R()>), dim3(items), dim3(R() ? 1024 : h->head_threads), 0, sst, A, E, lst, gsize, tslimit, sums, h->y3, h->action); }); });
+    if (render_fused) return;
+    if (tail) hipLaunchKernelGGL(k_env_render, dim3(items * nb), dim3(h->band_threads), 0, sst, E, lst, gsize, 0, nb);
+    else if (!(h->dbg_skip & 4)) hipLaunchKernelGGL(k_env_render, dim3(items), dim3(items <= 192 ? 1024 : h->render_threads), 0, sst, E, lst, gsize, 0, 1);
+}
+
+// profiling engines: one step counter per bracketed launch set, zeroed
+static int reserve_launch_units(dne_handle *h, int tslimit) {
+    const size_t need = (size_t)h->sub_streams.size() * (size_t)tslimit + 64;
+    if (need > h->launch_units_cap) {
+        HCHECK(h, h->release(h->launch_units));
+        HCHECK(h, h->alloc(&h->launch_units, need, "launch_units"));
+        h->launch_units_cap = need;
+    }
+    HCHECK(h, hipMemsetAsync(h->launch_units, 0, need * sizeof(int32_t), h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// the event pool of a profiled evaluation into dne_profile (evs: per bracketed launch set {before, after conv, after fc, after env})
+static int reduce_profile(dne_handle *h, const std::vector<std::array<size_t, 4>> &evs) {
+    dne_profile &P = h->prof;
+    float ms = 0;
+    HCHECK(h, hipEventElapsedTime(&ms, h->ev_pool[0], h->ev_pool[1]));
+    P.ref_ms = ms;
+    std::vector<int32_t> units(evs.size());
+    if (!evs.empty()) HCHECK(h, hipMemcpy(units.data(), h->launch_units, evs.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::vector<std::pair<float, float>> iv;   // fc intervals relative to the start of the reference pass
+    for (size_t i = 0; i < evs.size(); i++) {
+        const auto &e = evs[i];
+        HCHECK(h, hipEventElapsedTime(&ms, h->ev_pool[e[0]], h->ev_pool[e[1]])); P.conv_ms += ms;
+        HCHECK(h, hipEventElapsedTime(&ms, h->ev_pool[e[1]], h->ev_pool[e[2]])); P.fc_ms += ms;
+        P.fc_full_ms += ms; P.fc_full_launches += 1; P.fc_full_units += units[i];
+        float t0 = 0;
+        HCHECK(h, hipEventElapsedTime(&t0, h->ev_pool[0], h->ev_pool[e[1]]));
+        iv.push_back({t0, t0 + ms});
+        HCHECK(h, hipEventElapsedTime(&ms, h->ev_pool[e[2]], h->ev_pool[e[3]])); P.env_ms += ms;
+    }
+    std::sort(iv.begin(), iv.end());
+    double uni = 0; float hi = -1;
+    for (auto &p : iv) {   // length of the union of the intervals
+        if (p.first > hi) { uni += p.second - p.first; hi = p.second; }
+        else if (p.second > hi) { uni += p.second - hi; hi = p.second; }
+    }
+    P.fc_full_union_ms = uni;
+    return 0;
+}
+
 // policies.py:378-429 / 473-513 for n members at once: reset, (ES) reference pass, then lock-step
 // act -> env.step over the shrinking list of active groups until every episode is done.
-// The active groups are split into `nsub` independent sub-batches, each stepped on its own HIP stream: while
-// one sub-batch streams its noise slices through the HBM-bound fc kernel, another runs its MFMA convolutions
-// and its emulator frames, so the memory system and the matrix/vector pipes are busy at the same time.
 static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_t *env_seed, float *returns,
                      float *signreturns, int32_t *lengths, uint8_t *bc_out) {
-    h->tt_on = false;
-    // per-evaluation launch state (tail table in the kernel arguments, the regime flags) never outlives this call, whichever
-    // return is taken: a later dne_act / dne_debug_activations must not decode members from a stale table
-    struct ClearOnExit { dne_handle *h; ~ClearOnExit() { h->tt_on = false; h->sub_now = false; h->ring_now = false; } } clear_on_exit{h};
     if (n % gsize) return h->fail("member count %d not a multiple of the group size %d", n, gsize);
     if (tslimit <= 0) return h->fail("timestep limit must be positive");
     if (bc_out && !h->bc) return h->fail("behaviour characterisations requested but the engine was created with record_bc = 0");
@@ -1815,100 +1964,27 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
     hipLaunchKernelGGL(k_iota, dim3((groups + 255) / 256), dim3(256), 0, h->stream, h->list_a, groups);
     HCHECK(h, hipStreamSynchronize(h->stream));
 
-    // One global list of active groups, compacted every burst of 32 lock-steps (16 in the tail).  Within a burst the list is cut
-    // into nsub equal windows, each stepped on its own stream, so that while one window streams its noise slices
-    // (HBM) the others run their MFMA convolutions and emulator frames.  nsub follows the active count:
-    // two free-running streams at full width, three in the mid range (where no single kernel fills the chip),
-    // one when only a handful of episodes are left (measured: tools/kbench.py sweeps).
-    // the sub-slice fc's range: GA children written out (plain rows), optionally ES pairs (DNE_FC_SUB=2); never the LargeModel
-    auto sub_regime = [&](int total) {
-        if (h->large || !h->y3s || total < h->fc_sub_min || total > h->fc_sub_max) return false;
-        if (es_like(h->L.kind)) return h->fc_sub >= 2 && gsize == 2 && total < h->fc_duo_min;
-        return h->fc_sub >= 1 && gsize == 1 && h->members_materialized;
-    };
-    auto pick_nsub = [&](int total) {
-        // measured (tools/kbench.py sweeps): k_fc2 wants 3 windows at full width and 4 in the upper mid range; below
-        // ~400 groups the windows are sized to fit the column-split tail kernels (<= fc_tail_max groups each)
-        int k = total >= 1900 ? h->nsub_full : total >= h->fc2_min_total ? h->nsub_mid : total > 4 * h->fc_tail_max ? 3
-              : total >= 48 ? std::max(2, (total + h->fc_tail_max - 1) / h->fc_tail_max) : 1;
-        if (sub_regime(total)) k = h->fc_sub_nsub;
-        if (h->nsub_fixed > 0) k = h->nsub_fixed;
-        k = std::min(k, (int)h->sub_streams.size());
-        return std::max(1, std::min(k, total));
-    };
     int *cur = h->list_a, *nxt = h->list_b;
     int total = groups;
-    // tail table: with at most TT_MAX members left the window's member descriptors ride in the kernel arguments
-    auto set_tail_table = [&](const int *host_list /* the active groups in list order, null = 0, 1, 2, ... */) {
-        h->tt_on = false;
-        if (!h->tt_enable || h->large || total * gsize > TT_MAX || (int)h->host_off.size() < n || pick_nsub(total) != 1) return;
-        h->tt.n = total * gsize;
-        for (int i = 0; i < total; i++)
-            for (int v = 0; v < gsize; v++) {
-                const int m = (host_list ? host_list[i] : i) * gsize + v, k = i * gsize + v;
-                h->tt.member[k] = m; h->tt.slot[k] = h->host_slot[m]; h->tt.scale[k] = h->host_scale[m]; h->tt.off[k] = h->host_off[m];
-            }
-        h->tt_on = true;
-    };
-    set_tail_table(nullptr);
-    EnvArgs E = h->env(bc_mode);
+    TailTable tt_store;
+    const TailTable *tt = make_tail_table(h, &tt_store, nullptr, total, gsize, n);
+    EnvArgs E = h->env(bc_mode, tt);
     int t = 0;
     long long group_steps = 0, launch_sets = 0;
     std::vector<std::array<size_t, 4>> evs;   // per profiled launch set: event indices {before, after conv, after fc, after env}
     size_t ne = 2;
-    if (prof) {
-        const size_t need = (size_t)h->sub_streams.size() * (size_t)tslimit + 64;
-        if (need > h->launch_units_cap) {
-            HCHECK(h, h->release(h->launch_units));
-            HCHECK(h, h->alloc(&h->launch_units, need, "launch_units"));
-            h->launch_units_cap = need;
-        }
-        HCHECK(h, hipMemsetAsync(h->launch_units, 0, need * sizeof(int32_t), h->stream));
-        HCHECK(h, hipStreamSynchronize(h->stream));
-    }
+    if (prof && reserve_launch_units(h, tslimit)) return -1;
     hipEvent_t last_fc = nullptr;
     size_t fc_ring_pos = 0;
-    // the profiled ("full") launches are one kernel: k_fc2 when this evaluation starts wide enough to use it, else k_fc
-    const bool fc2_eval = h->fc_pairs == 2 && gsize == 2 && es_like(h->L.kind) && h->uniform_base && groups >= h->fc2_min_total;
-    const bool duo_eval = !h->large && h->fc_duo && (es_like(h->L.kind) && gsize == 2) && groups >= h->fc_duo_min;
-    // an evaluation that starts wide enough for k_fc_ring: its bracketed ("full") launches are that kernel's only -- one kernel per
-    // roofline line; the k_fc_duo launches of its thinner lock-steps (DNE_FC_DUO_MIN .. DNE_DUO_SOLO_BELOW pairs) are not bracketed
-    // the ring's range: pairs as dense in their stretch of the table as DNE_DUO_SOLO_BELOW (1500) pairs over the whole table, and enough of them to
-    // fill the chip (DNE_RING_MIN) -- at one GPU "1500 of 2500 active", on a rank of two with its own half of the table "1000 of 1250"
-    auto ring_dense = [&](int t) { return (double)t * h->dense_scale >= (double)h->duo_solo_below && t >= h->ring_min; };
-    const bool ring_eval = duo_eval && es_like(h->L.kind) && gsize == 2 && h->theta_perm && h->antithetic_slot0 && h->duo_sweep &&
-                           (h->ring_on > 1 || ring_dense(groups)) && (ring_dense(groups) || h->duo_sweep > 1);
-    // the ring's DMA source: the table scaled by this evaluation's sigma (k_fc_ring<true>), made once per (table, sigma)
-    h->ring_pre_now = false;
-    if (ring_eval && h->ring_pre && h->pair_sigma_uniform) {
-        if (!h->noise_pre && h->alloc(&h->noise_pre, h->noise_count + OVERFETCH_FLOATS, "noise_pre")) {
-            h->trace("no room for the scaled table: the ring scales its rows itself");
-            (void)hipGetLastError(); h->noise_pre = nullptr; h->ring_pre = 0;
-        }
-        if (h->noise_pre) {
-            if (h->noise_pre_count != h->noise_count || h->noise_pre_sigma != h->pair_sigma) {
-                static_assert(OVERFETCH_FLOATS % 4 == 0, "k_scale_table moves 16 bytes per step");
-                const size_t n4 = (h->noise_count + OVERFETCH_FLOATS) / 4;   // (a table whose count is not a multiple of four leaves its last 1-3 padding floats unscaled: zeros either way)
-                hipLaunchKernelGGL(k_scale_table, dim3(256 * 8), dim3(256), 0, h->stream, (const float *)h->noise, h->noise_pre, n4, h->pair_sigma);
-                HCHECK(h, hipStreamSynchronize(h->stream));   // the windows' streams start behind the host
-                h->noise_pre_count = h->noise_count; h->noise_pre_sigma = h->pair_sigma;
-                h->trace("noise table scaled by %g for the ring", (double)h->pair_sigma);
-            }
-            h->ring_pre_now = true;
-        }
-    }
+    // the evaluation as a whole, by the width it starts with: its profiled ("full") launches are one kernel, one roofline line -- k_fc_ring's if it starts in
+    // the ring's range (the k_fc_duo launches of its thinner lock-steps are not bracketed then), else k_fc_duo's, else k_fc2's, else every window above fc_tail_max groups
+    const StepPlan ev = plan_step(h, groups, gsize, true);
+    if (ev.ring && ring_scaled_table(h)) return -1;
     while (total > 0 && t < tslimit) {
         const int burst = std::min(total <= h->fc_tail_max ? h->burst_tail : h->burst, tslimit - t);   // lock-steps until the next compaction
-        const int nsub = pick_nsub(total);
-        h->fc2_now = h->fc_pairs == 2 && total >= h->fc2_min_total;
-        h->duo_now = !h->large && h->fc_duo && (es_like(h->L.kind) && gsize == 2) && total >= h->fc_duo_min &&
-                     (size_t)4 * ((total + nsub - 1) / nsub) * sizeof(long long) <= 160 * 1024;   // k_unit_order ranks a window's keys in LDS
-        h->duo_solo_now = total < h->duo_solo_below;
-        h->sub_now = sub_regime(total);
-        if (h->sub_now) h->duo_now = h->fc2_now = false;
-        h->ring_now = h->duo_now && es_like(h->L.kind) && gsize == 2 && h->theta_perm && h->antithetic_slot0 &&
-                      h->duo_sweep && (ring_dense(total) || h->duo_sweep > 1) && (h->ring_on > 1 || ring_dense(total));
-        if (h->duo_now)   // the list only changes at a compaction: rank each window's units by table address once per burst
+        const StepPlan p = plan_step(h, total, gsize);
+        const int nsub = p.nsub;   // windows of this burst
+        if (p.duo)   // the list only changes at a compaction: rank each window's units by table address once per burst
             for (int s = 0; s < nsub; s++) {
                 const int lo = (int)((long long)total * s / nsub), cnt = (int)((long long)total * (s + 1) / nsub) - lo;
                 if (cnt <= h->fc_tail_max) continue;
@@ -1923,91 +1999,36 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
                 const int *lst = cur + lo;
                 std::array<size_t, 4> e{};
                 // events only around full-width launches: in the latency-bound tail every event packet is a bubble
-                // (with k_fc2 enabled the profiled launches are exactly the k_fc2 ones: the roofline kernel of bench.py)
-                const bool duo_win = h->duo_now && cnt > h->fc_tail_max;
-                const bool pe = prof && (ring_eval ? duo_win && h->ring_now : duo_eval ? duo_win : fc2_eval ? h->fc2_now : cnt > h->fc_tail_max);
+                const bool duo_win = p.duo && cnt > h->fc_tail_max;
+                const bool pe = prof && (ev.ring ? duo_win && p.ring : ev.duo ? duo_win : ev.fc2 ? p.fc2 : cnt > h->fc_tail_max);
                 if (pe) { e[0] = ne++; HCHECK(h, hipEventRecord(h->event(e[0]), sst)); }
                 // fused policy head + emulator (+ render): while all windows together still fit the chip one workgroup per member
-                const bool tail = !h->large && !h->sub_now && cnt <= h->fc_tail_max && total <= h->tail_fused_max;   // (the fused tail kernels are the small networks')
-                // speculative tail: the emulator + renderer outcome of every action, inside the launches of this step's forward pass
+                const bool tail = !h->large && !p.sub && cnt <= h->fc_tail_max && total <= h->tail_fused_max;   // (the fused tail kernels are the small networks')
                 const bool spec = tail && nsub == 1 && h->spec_max > 0 && cnt * gsize <= h->spec_max &&
                                   cnt * gsize <= h->conv_split_max && !h->dbg_skip;
-                if (spec) {
-                    const int items = cnt * gsize, nact = h->cfg.n_actions, nb = h->spec_bands;
-                    const FwdArgs A = h->fwd(true);
-                    const bool es = es_like(h->L.kind);
-                    const int emu_blocks = (items * nact + 255) / 256;
-                    if (st == 0 || !h->spec_conv1) {   // no conv1 candidates from the previous lock-step (a new burst = a new list)
-                        hipLaunchKernelGGL(k_conv1_spec, dim3(items * 7 + emu_blocks), dim3(256), 0, sst, A, E, lst, gsize, h->y1, 7, items * 7, items, nact);
-                        if (es) hipLaunchKernelGGL((k_conv2<true>), dim3(items * 4), dim3(256), 0, sst, A, lst, gsize, 1, 0, (const float *)h->y1, h->y2, 4, (float *)nullptr);
-                        else hipLaunchKernelGGL((k_conv2<false>), dim3(items * 4), dim3(256), 0, sst, A, lst, gsize, 1, 0, (const float *)h->y1, h->y2, 4, (float *)nullptr);
-                    } else if (es) {
-                        hipLaunchKernelGGL((k_conv2_spec<true>), dim3(items * 4 + emu_blocks), dim3(256), 0, sst, A, E, lst, gsize, (const float *)h->y1, h->y2, 4, items * 4, items, nact, (const int32_t *)h->action);
-                    } else {
-                        hipLaunchKernelGGL((k_conv2_spec<false>), dim3(items * 4 + emu_blocks), dim3(256), 0, sst, A, E, lst, gsize, (const float *)h->y1, h->y2, 4, items * 4, items, nact, (const int32_t *)h->action);
-                    }
-#define FQS(NV, BN) hipLaunchKernelGGL((k_fc_quad_spec<NV, BN>), dim3(cnt * 64 + items * nact * nb), dim3(256), 0, sst, A, E, lst, gsize, (const float *)h->y2, h->y3t, cnt * 64, nact, nb)
-                    if (gsize == 2) { if (es) FQS(2, true); else FQS(2, false); }
-                    else { if (es) FQS(1, true); else FQS(1, false); }
-#undef FQS
-                    if (h->spec_conv1 && st + 1 < burst) {   // the choice + conv1 of every candidate (the last lock-step of a burst has no successor to use them)
-                        if (es) hipLaunchKernelGGL((k_tail_select_conv1<true>), dim3(items + items * nact * 7), dim3(256), 0, sst, A, E, lst, gsize, tslimit, (const float *)h->y3t, h->y3, h->action, items, nact, 7);
-                        else hipLaunchKernelGGL((k_tail_select_conv1<false>), dim3(items + items * nact * 7), dim3(256), 0, sst, A, E, lst, gsize, tslimit, (const float *)h->y3t, h->y3, h->action, items, nact, 7);
-                    } else if (es) hipLaunchKernelGGL((k_tail_select<true>), dim3(items), dim3(256), 0, sst, A, E, lst, gsize, tslimit, (const float *)h->y3t, h->y3, h->action);
-                    else hipLaunchKernelGGL((k_tail_select<false>), dim3(items), dim3(256), 0, sst, A, E, lst, gsize, tslimit, (const float *)h->y3t, h->y3, h->action);
-                    if (h->debug_sync) {
-                        hipError_t de = hipStreamSynchronize(sst);
-                        if (de == hipSuccess) de = hipGetLastError();
-                        if (de != hipSuccess) return h->fail("lock-step %d (speculative tail, %d active groups): %s", t + st, cnt, hipGetErrorString(de));
-                    }
-                    group_steps += cnt;
-                    launch_sets++;
-                    continue;
+                if (spec) launch_spec_tail(h, p, tt, E, lst, cnt, gsize, tslimit, sst, st == 0 || !h->spec_conv1, h->spec_conv1 && st + 1 < burst);
+                else {
+                    launch_forward(h, p, tt, lst, cnt, gsize, true, sst);
+                    // optional: serialise the fc kernels of the windows (anti-phase); off by default, free-running measured faster
+                    const bool chain = nsub > 1 && cnt >= h->fc_chain_min;
+                    if (chain && last_fc) HCHECK(h, hipStreamWaitEvent(sst, last_fc, 0));
+                    if (pe) { e[1] = ne++; HCHECK(h, hipEventRecord(h->event(e[1]), sst)); }   // after the wait: brackets fc only
+                    if (pe) e[2] = ne++;
+                    const bool head_fused = tail || (duo_win && h->duo_head_fused) || (p.sub && h->fc_sub_head);   // the fc leaves partial sums: head + emulator in one launch
+                    launch_fc(h, p, tt, lst, cnt, gsize, nullptr, sst, head_fused, p.duo ? h->unit_order + 4 * lo : nullptr,
+                              pe && duo_win ? h->event(e[2]) : nullptr);   // duo: the bracket ends behind k_fc_duo, before k_out
+                    if (chain) { last_fc = h->fc_ring[fc_ring_pos++ % h->fc_ring.size()]; HCHECK(h, hipEventRecord(last_fc, sst)); }
+                    if (pe && !duo_win) HCHECK(h, hipEventRecord(h->event(e[2]), sst));
+                    E.step_counter = pe ? h->launch_units + evs.size() : nullptr;
+                    if (head_fused) launch_head_step(h, p, tt, E, lst, cnt, gsize, tslimit, sst, tail);
+                    else launch_env_step(h, E, lst, cnt, gsize, tslimit, sst);
+                    if (pe) { e[3] = ne++; HCHECK(h, hipEventRecord(h->event(e[3]), sst)); evs.push_back(e); }
                 }
-                launch_forward(h, lst, cnt, gsize, true, sst, h->ring_now && duo_win);
-                // optional: serialise the fc kernels of the windows (anti-phase); off by default, free-running measured faster
-                const bool chain = nsub > 1 && cnt >= h->fc_chain_min;
-                if (chain && last_fc) HCHECK(h, hipStreamWaitEvent(sst, last_fc, 0));
-                if (pe) { e[1] = ne++; HCHECK(h, hipEventRecord(h->event(e[1]), sst)); }   // after the wait: brackets fc only
-                if (pe) e[2] = ne++;
-                const bool duo_head = (duo_win && h->duo_head_fused) || (h->sub_now && h->fc_sub_head);   // the fc leaves partial sums: head + emulator in one launch
-                launch_fc(h, lst, cnt, gsize, nullptr, sst, tail || duo_head, h->duo_now ? h->unit_order + 4 * lo : nullptr,
-                          pe && duo_win ? h->event(e[2]) : nullptr);   // duo: the bracket ends behind k_fc_duo, before k_out
-                if (chain) { last_fc = h->fc_ring[fc_ring_pos++ % h->fc_ring.size()]; HCHECK(h, hipEventRecord(last_fc, sst)); }
-                if (pe && !duo_win) HCHECK(h, hipEventRecord(h->event(e[2]), sst));
-                E.step_counter = pe ? h->launch_units + evs.size() : nullptr;
-                if (tail) {
-                    const FwdArgs A = h->fwd(false);
-                    const int items = cnt * gsize;
-                    int nb = h->render_bands;
-                    while (nb > 1 && items * nb > h->render_wg_max) nb /= 2;
-#define TS(BN, R, THR) hipLaunchKernelGGL((k_tail_step<BN, R>), dim3(items), dim3(THR), 0, sst, A, E, lst, gsize, tslimit, (const float *)h->y3t, h->y3, h->action)
-                    const bool es = es_like(h->L.kind);
-                    if (nb > 1) {   // few members left: policy head + emulator, then each frame over nb workgroups
-                        if (es) TS(true, false, h->head_threads); else TS(false, false, h->head_threads);
-                        hipLaunchKernelGGL(k_env_render, dim3(items * nb), dim3(h->band_threads), 0, sst, E, lst, gsize, 0, nb);
-                    } else if (es) TS(true, true, 1024); else TS(false, true, 1024);
-#undef TS
-                } else if (duo_head) {
-                    const FwdArgs A = h->fwd(false);
-                    const int items = cnt * gsize;
-                    const float *sums = h->sub_now ? h->y3s : h->y3t;
-                    if (h->sub_render_fused && h->sub_now && !(h->dbg_skip & 4)) {   // head + emulator + renderer in one launch
-                        if (es_like(h->L.kind)) hipLaunchKernelGGL((k_tail_step<true, true>), dim3(items), dim3(1024), 0, sst, A, E, lst, gsize, tslimit, sums, h->y3, h->action);
-                        else hipLaunchKernelGGL((k_tail_step<false, true>), dim3(items), dim3(1024), 0, sst, A, E, lst, gsize, tslimit, sums, h->y3, h->action);
-                    } else {
-                    if (es_like(h->L.kind)) hipLaunchKernelGGL((k_tail_step<true, false>), dim3(items), dim3(h->head_threads), 0, sst, A, E, lst, gsize, tslimit, sums, h->y3, h->action);
-                    else hipLaunchKernelGGL((k_tail_step<false, false>), dim3(items), dim3(h->head_threads), 0, sst, A, E, lst, gsize, tslimit, sums, h->y3, h->action);
-                    if (!(h->dbg_skip & 4))
-                        hipLaunchKernelGGL(k_env_render, dim3(items), dim3(items <= 192 ? 1024 : h->render_threads), 0, sst, E, lst, gsize, 0, 1);
-                    }
-                } else launch_env_step(h, E, lst, cnt, gsize, tslimit, sst);
-                if (pe) { e[3] = ne++; HCHECK(h, hipEventRecord(h->event(e[3]), sst)); evs.push_back(e); }
                 if (h->debug_sync) {
                     hipError_t de = hipStreamSynchronize(sst);
                     if (de == hipSuccess) de = hipGetLastError();
-                    if (de != hipSuccess) return h->fail("lock-step %d window %d/%d (%d of %d active groups, %s fc): %s", t + st, s, nsub, cnt, total,
-                                                         cnt <= h->fc_tail_max ? "tail" : h->fc2_now ? "k_fc2" : "k_fc", hipGetErrorString(de));
+                    if (de != hipSuccess && spec) return h->fail("lock-step %d (speculative tail, %d active groups): %s", t + st, cnt, hipGetErrorString(de));
+                    if (de != hipSuccess) return h->fail("lock-step %d window %d/%d (%d of %d active groups, %s fc): %s", t + st, s, nsub, cnt, total, fc_name(h, p, cnt), hipGetErrorString(de));
                 }
                 group_steps += cnt;
                 launch_sets++;
@@ -2021,13 +2042,10 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
         HCHECK(h, hipStreamSynchronize(h->stream));
         total = *h->count_host;
         std::swap(cur, nxt);
-        set_tail_table(h->count_host + 8);
-        E.tt_n = h->tt_on ? h->tt.n : 0;
-        if (h->tt_on) memcpy(E.tt_member, h->tt.member, sizeof(E.tt_member));
+        tt = make_tail_table(h, &tt_store, h->count_host + 8, total, gsize, n);
+        set_tail_table(E, tt);
         h->trace("eval: lock-step %d, %d active groups", t, total);
     }
-    h->tt_on = false;
-    h->sub_now = false;
     HCHECK(h, hipGetLastError());
     HCHECK(h, hipEventRecord(h->ev_b, h->stream));
     HCHECK(h, hipMemcpyAsync(returns, h->ret, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -2045,32 +2063,9 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
     P.env_steps = 0;
     for (int i = 0; i < n; i++) P.env_steps += lengths[i];
     P.fc_full_ms = P.fc_full_launches = P.fc_full_units = 0;
-    P.fc_full_kind = ring_eval ? 5 : duo_eval ? 3 : fc2_eval ? 2 : sub_regime(groups) ? 4 : 1;   // (an evaluation that STARTS in the sub-slice fc's range: its bracketed launches are k_fc_sub's)
+    P.fc_full_kind = ev.ring ? 5 : ev.duo ? 3 : ev.fc2 ? 2 : ev.sub ? 4 : 1;   // (an evaluation that STARTS in the sub-slice fc's range: its bracketed launches are k_fc_sub's)
     P.fc_full_union_ms = 0;
-    if (prof) {
-        HCHECK(h, hipEventElapsedTime(&ms, h->ev_pool[0], h->ev_pool[1]));
-        P.ref_ms = ms;
-        std::vector<int32_t> units(evs.size());
-        if (!evs.empty()) HCHECK(h, hipMemcpy(units.data(), h->launch_units, evs.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        std::vector<std::pair<float, float>> iv;   // fc intervals relative to the start of the reference pass
-        for (size_t i = 0; i < evs.size(); i++) {
-            const auto &e = evs[i];
-            HCHECK(h, hipEventElapsedTime(&ms, h->ev_pool[e[0]], h->ev_pool[e[1]])); P.conv_ms += ms;
-            HCHECK(h, hipEventElapsedTime(&ms, h->ev_pool[e[1]], h->ev_pool[e[2]])); P.fc_ms += ms;
-            P.fc_full_ms += ms; P.fc_full_launches += 1; P.fc_full_units += units[i];
-            float t0 = 0;
-            HCHECK(h, hipEventElapsedTime(&t0, h->ev_pool[0], h->ev_pool[e[1]]));
-            iv.push_back({t0, t0 + ms});
-            HCHECK(h, hipEventElapsedTime(&ms, h->ev_pool[e[2]], h->ev_pool[e[3]])); P.env_ms += ms;
-        }
-        std::sort(iv.begin(), iv.end());
-        double uni = 0; float hi = -1;
-        for (auto &p : iv) {   // length of the union of the intervals
-            if (p.first > hi) { uni += p.second - p.first; hi = p.second; }
-            else if (p.second > hi) { uni += p.second - hi; hi = p.second; }
-        }
-        P.fc_full_union_ms = uni;
-    }
+    if (prof && reduce_profile(h, evs)) return -1;
     return 0;
 }
 
