@@ -976,9 +976,15 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         g_create_error = "dne_create: no HIP device visible (this engine has no CPU fallback)";
         return -1;
     }
-    if (cfg->max_members <= 0 || cfg->n_actions <= 1 || cfg->n_actions > 32 ||
+    if (cfg->max_members <= 0 || cfg->n_actions <= 1 ||
         (!es_like(cfg->policy_kind) && cfg->policy_kind != DNE_KIND_GA && cfg->policy_kind != DNE_KIND_GA_LARGE)) {
         g_create_error = "dne_create: bad config";
+        return -1;
+    }
+    // SynthAtari defines 18 actions (ALE order; a narrower engine uses the first n_actions of them), and the oracle's tables end there: a
+    // wider head could pick an action nothing defines and no parity covers
+    if (cfg->n_actions > 18) {
+        g_create_error = "dne_create: n_actions " + std::to_string(cfg->n_actions) + " is outside 2..18: the SynthAtari fixture defines 18 actions";
         return -1;
     }
     dne_handle *h = new dne_handle();

@@ -114,7 +114,10 @@ def _arr(a, dtype):
 
 
 class Engine:
-    """One engine = one GPU.  Thin, typed wrapper; every method maps 1:1 onto a dne_* entry point."""
+    """One engine = one GPU.  Thin, typed wrapper; every method maps 1:1 onto a dne_* entry point.
+
+    n_actions: 2..18 (env.action_space.n).  The SynthAtari fixture defines 18 actions in ALE order; an engine with fewer uses the first
+    n_actions of them, and dne_create refuses a wider one (DneError)."""
 
     def __init__(self, kind, n_actions=18, max_members=256, ref_count=128, device_id=0, ref_chunk=0,
                  record_bc=False, bc_max_steps=0, profile_events=False, bc_final_only=False):

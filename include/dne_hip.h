@@ -45,7 +45,8 @@ typedef struct dne_handle dne_handle;
 typedef struct {
     int32_t device_id;
     int32_t policy_kind;  /* DNE_KIND_* */
-    int32_t n_actions;    /* env.action_space.n (18 for Frostbite) */
+    int32_t n_actions;    /* env.action_space.n: 2..18 (18 for Frostbite).  The SynthAtari fixture defines 18 actions in ALE order; an
+                             engine with fewer uses the first n_actions of them.  dne_create refuses any other width. */
     int32_t max_members;  /* episode slots evaluated concurrently (ES: 2 * pairs per call) */
     int32_t ref_count;    /* size of the virtual-batch-norm reference batch (es.py:160-162: 128); multiple of 8 */
     int32_t ref_chunk;    /* members per reference-pass chunk (bounds scratch memory); 0 = default */

@@ -16,8 +16,21 @@ import oracle as O
 NACT, NREF = 18, 16
 TAP_STEPS = (1, 3, 9)              # first lock-step of a burst, inside a burst, and (DNE_BURST=4) behind two compactions
 NOISE_LEN = 4_000_000              # conftest.small_noise
-KIND_ES, KIND_GA, KIND_ES_VBN = 0, 1, 3
+KIND_ES, KIND_GA, KIND_GA_LARGE, KIND_ES_VBN = 0, 1, 2, 3
 P_ES, P_GA, P_VBN = 1009058, 1008450, 1008450
+LARGE_NOISE_LEN = 9_000_000        # big_noise of tests/test_gpu_large.py and tests/test_gpu_step_taps.py
+
+
+def num_params(kind, nact=NACT):
+    """P of a kind at an action-set width: the output layer is [256][nact] weights + nact biases (LargeModel: [512][nact] + nact), so P moves
+    by 257 (513) per action; the rest of the flat vector does not depend on the width.  tests/test_step_tap_cpu.py holds these against
+    oracle.layout and policies.flat_layout at every width the tests use."""
+    if kind == KIND_GA_LARGE:
+        return 4043424 + 513 * nact
+    return (1004432 if kind == KIND_ES else 1003824) + 257 * nact
+
+
+assert (num_params(KIND_ES), num_params(KIND_GA), num_params(KIND_ES_VBN)) == (P_ES, P_GA, P_VBN)
 
 
 def tap_seeds(n):
@@ -113,54 +126,111 @@ def small_noise():
 
 
 @functools.lru_cache(maxsize=None)
-def ref_batch():
-    return O.get_ref_batch(seed=0, batch_size=NREF, nact=NACT)
+def _ref_batch(nact):
+    return O.get_ref_batch(seed=0, batch_size=NREF, nact=nact)
+
+
+def ref_batch(nact=NACT):
+    """the reference batch of a width: its frames come from random play over that width's actions (es.py:105-113)"""
+    return _ref_batch(int(nact))
 
 
 @functools.lru_cache(maxsize=None)
-def base_theta(kind):
-    """the vector an engine of that kind gets with set_theta (native layout)"""
+def _base_theta(kind, nact):
     if kind == KIND_ES:
-        return O.es_init_theta(O.layout(O.KIND_ES, NACT), 0)
+        return O.es_init_theta(O.layout(O.KIND_ES, nact), 0)
     assert kind == KIND_ES_VBN
     from dne_hip import policies
+    P = num_params(KIND_ES_VBN, nact)
     rs = np.random.RandomState(11)                      # a ModelVirtualBN start point moved off it so that every BatchNorm/b is nonzero
-    return small_noise()[777:777 + P_VBN] * policies.vbn_scale_by(NACT) + (0.01 * rs.randn(P_VBN)).astype(np.float32)
+    return small_noise()[777:777 + P] * policies.vbn_scale_by(nact) + (0.01 * rs.randn(P)).astype(np.float32)
 
 
-def es_member_theta(kind, idx, scale):
+def base_theta(kind, nact=NACT):
+    """the vector an engine of that kind and width gets with set_theta (native layout)"""
+    return _base_theta(int(kind), int(nact))
+
+
+def es_member_theta(kind, idx, scale, nact=NACT):
     """member = base + fl(scale * noise[idx : idx + P]) in the kind's own layout, then (ModelVirtualBN) expanded onto the ES layout the oracle runs"""
-    th = base_theta(kind)
+    th = base_theta(kind, nact)
     v = (np.float32(scale) * small_noise()[idx:idx + th.size]).astype(np.float32)
     m = (th + v).astype(np.float32)
     if kind == KIND_ES_VBN:
         from vbn_support import expand
-        m = expand(m, NACT)
+        m = expand(m, nact)
     return m
 
 
 @functools.lru_cache(maxsize=None)
-def es_member_taps(kind, idx, scale, seed):
-    """{T: tap} for T in TAP_STEPS of one ES / ES_VBN member, cached: the regimes share their populations"""
-    L = O.layout(O.KIND_ES, NACT)
-    return oracle_taps(L, es_member_theta(kind, int(idx), float(scale)), ref_batch(), int(seed), TAP_STEPS)
+def _es_member_taps(kind, idx, scale, seed, nact):
+    L = O.layout(O.KIND_ES, nact)
+    return oracle_taps(L, es_member_theta(kind, idx, scale, nact), ref_batch(nact), seed, TAP_STEPS)
+
+
+def es_member_taps(kind, idx, scale, seed, nact=NACT):
+    """{T: tap} for T in TAP_STEPS of one ES / ES_VBN member, cached per width: the regimes share their populations"""
+    return _es_member_taps(int(kind), int(idx), float(scale), int(seed), int(nact))
 
 
 @functools.lru_cache(maxsize=None)
-def ga_member_taps(chain, sigma, seed, taps):
-    L = O.layout(O.KIND_GA, NACT)
-    return oracle_taps(L, O.ga_rebuild(L, small_noise(), list(chain), sigma), None, int(seed), taps)
+def _ga_member_taps(chain, sigma, seed, taps, nact):
+    L = O.layout(O.KIND_GA, nact)
+    return oracle_taps(L, O.ga_rebuild(L, small_noise(), list(chain), sigma), None, seed, taps)
+
+
+def ga_member_taps(chain, sigma, seed, taps, nact=NACT):
+    return _ga_member_taps(tuple(chain), float(sigma), int(seed), tuple(taps), int(nact))
 
 
 # ---- GA (GAAtariPolicy): 7 fresh genomes, then 7 children of two of them; roots and mutation seeds from the edge set ------------------------
 GA_SIGMA = 0.005
 GA_TAP_STEPS = (1, 6)
-_HI = NOISE_LEN - P_GA                                  # the last legal slice
-GA_GEN0 = [(0,), (_HI,), (4,), (1_000_001,), (64,), (127,), (1_000_000,)]
-GA_MUTATIONS = (0, _HI, 4, 1_000_001, 1_000_001, 3, 1_000_000 + P_GA)   # first / last slice, a multiple of 4, odd, one seed for both parents
+def ga_gen0(nact=NACT):
+    hi = NOISE_LEN - num_params(KIND_GA, nact)          # the last legal slice
+    return [(0,), (hi,), (4,), (1_000_001,), (64,), (127,), (1_000_000,)]
+
+
+def ga_mutations(nact=NACT):
+    """first / last slice, a multiple of 4, odd, one seed for both parents, a slice that abuts another"""
+    P = num_params(KIND_GA, nact)
+    return (0, NOISE_LEN - P, 4, 1_000_001, 1_000_001, 3, 1_000_000 + P)
+
+
+GA_GEN0 = ga_gen0()
+GA_MUTATIONS = ga_mutations()
 GA_SEEDS = (tap_seeds(14)[:7], tap_seeds(14)[7:])
 
 
-def ga_gen1():
-    parents = (GA_GEN0[1], GA_GEN0[3])
-    return [parents[i % 2] + (GA_MUTATIONS[i],) for i in range(7)]
+def ga_gen1(nact=NACT):
+    gen0, mut = ga_gen0(nact), ga_mutations(nact)
+    parents = (gen0[1], gen0[3])
+    return [parents[i % 2] + (mut[i],) for i in range(7)]
+
+
+# ---- LargeModel: the genomes of test_large_model_taps ------------------------------------------------------------------------------------
+LARGE_TAP_STEPS = (1, 3)
+
+
+@functools.lru_cache(maxsize=None)
+def big_noise():
+    """first 9M entries of the reference noise stream (a LargeModel slice is 4.05M floats)"""
+    return np.random.RandomState(123).randn(LARGE_NOISE_LEN).astype(np.float32)
+
+
+def large_genomes(n, nact=NACT, noise_len=LARGE_NOISE_LEN):
+    """n members: four roots (slice 0, the last legal slice, an odd and a 16-byte aligned start) unmutated, the rest their children with one
+    mutation each (seeded indices, powers 0.002 / 0.004)"""
+    hi = noise_len - num_params(KIND_GA_LARGE, nact)
+    roots = [(0,), (hi,), (1_234_567,), (2_000_000,)]
+    rs = np.random.RandomState(n)
+    return roots + [roots[i % 4] + ((int(rs.randint(0, hi + 1)), 0.002 if i % 2 else 0.004),) for i in range(n - 4)]
+
+
+@functools.lru_cache(maxsize=None)
+def large_member_taps(n, m, nact=NACT):
+    """{T: tap} for T in LARGE_TAP_STEPS of member m of large_genomes(n, nact) on episode tap_seeds(n)[m]"""
+    from dne_hip import ga_gpu
+    L = O.layout(O.KIND_GA_LARGE, nact)
+    th = O.ga_gpu_rebuild(big_noise(), large_genomes(n, nact)[m], ga_gpu.model_scale_by(nact, KIND_GA_LARGE))
+    return oracle_taps(L, th, None, int(tap_seeds(n)[m]), LARGE_TAP_STEPS, large=True)

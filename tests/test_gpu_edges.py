@@ -64,6 +64,12 @@ def test_refusals(eng, small_noise):
         es.centered_ranks(np.zeros(1, np.float32))            # es.py:83 divides by size - 1
     with pytest.raises(_lib.DneError):
         es.ga_select(np.zeros(3, np.float32), 4)
+    for kind in (_lib.KIND_ES, _lib.KIND_GA, _lib.KIND_GA_LARGE, _lib.KIND_ES_VBN):
+        for nact in (19, 32):                                  # wider than the fixture's action set: refused at creation, by name
+            with pytest.raises(_lib.DneError, match="18 actions"):
+                _lib.Engine(kind, nact, max_members=2, ref_count=NREF)
+    with pytest.raises(_lib.DneError):                         # narrower than a choice
+        _lib.Engine(_lib.KIND_ES, 1, max_members=2, ref_count=NREF)
     with pytest.raises(_lib.DneError):                         # BCs requested from an engine without record_bc
         ga2 = None
         from dne_hip import _lib as L2

@@ -14,7 +14,10 @@ path), 3 lies inside a burst, 9 with DNE_BURST / DNE_BURST_TAIL = 4 lies behind 
 
 In the ring regime the y2 row holds relu(bn2(y2)) (k_conv12 with act2, or k_y2_activate); y1 is written inside an evaluation only by the
 unfused k_conv1.  The logits are not tapped inside an evaluation (that would add an argument to the hot kernels): the head's arithmetic
-behind y3 stays covered by dne_act's tests and by the outcome checks (returns / sign-returns / lengths), which are repeated here."""
+behind y3 stays covered by dne_act's tests and by the outcome checks (returns / sign-returns / lengths), which are repeated here.
+
+Every population here is 18 actions wide.  The helpers take the width (nact) and, on engines that record RAM trajectories, compare every
+step's RAM: tests/test_gpu_action_widths.py runs the regimes through them at 3, 4, 9 and 17 actions."""
 import numpy as np
 import pytest
 
@@ -117,20 +120,27 @@ def _activated_pairs(n_pairs, knobs):
     return out
 
 
-def _es_engine(kind, knobs, n_pairs, monkeypatch, profile):
+def _es_engine(kind, knobs, n_pairs, monkeypatch, profile, nact=NACT, record_ram=False):
+    """record_ram: the engine keeps every member's RAM trajectory (record_bc), max(TAP_STEPS) rows each"""
     from dne_hip import _lib
     for k, v in knobs.items():
         monkeypatch.setenv(k, v)
-    e = _lib.Engine(kind, NACT, max_members=2 * n_pairs, ref_count=NREF, profile_events=profile)
+    e = _lib.Engine(kind, nact, max_members=2 * n_pairs, ref_count=NREF, profile_events=profile,
+                    record_bc=record_ram, bc_max_steps=max(S.TAP_STEPS) if record_ram else 0)
     e.noise_upload(S.small_noise())
-    e.set_ref_batch(S.ref_batch())
-    e.set_theta(S.base_theta(kind))
+    e.set_ref_batch(S.ref_batch(nact))
+    e.set_theta(S.base_theta(kind, nact))
     return e
 
 
-def _check_es_eval(e, kind, knobs, idx, seeds, sigma, T, members, y1_written, fc_kind, ctx):
+def _check_es_eval(e, kind, knobs, idx, seeds, sigma, T, members, y1_written, fc_kind, ctx, nact=NACT, check_ram=False):
+    """check_ram (an engine made with record_ram): every compared member's RAM after each of its T steps equals the oracle's -- byte 38 is
+    the action of that step's frames, so this pins the argmax of EVERY lock-step, not only what the last one's y3 implies"""
     n = len(idx)
-    ret, sg, ln = e.es_eval(idx, sigma, T, seeds)
+    if check_ram:
+        ret, sg, ln, bc = e.es_eval(idx, sigma, T, seeds, want_bc=True)
+    else:
+        ret, sg, ln = e.es_eval(idx, sigma, T, seeds)
     assert (ln == T).all(), (ctx, ln.tolist())                      # asserted, not filtered: every tap is a lock-step at the full width
     if fc_kind is not None:
         assert e.profile()["fc_full_kind"] == fc_kind, ctx          # the forced regime really ran (5 ring, 4 sub, 3 duo)
@@ -139,8 +149,11 @@ def _check_es_eval(e, kind, knobs, idx, seeds, sigma, T, members, y1_written, fc
     ret, sg = ret.reshape(-1), sg.reshape(-1)
     for m in members:
         sc = np.float32(sigma) if m % 2 == 0 else -np.float32(sigma)
-        tap = S.es_member_taps(kind, int(idx[m // 2]), float(sc), int(seeds[m]))[T]
+        tap = S.es_member_taps(kind, int(idx[m // 2]), float(sc), int(seeds[m]), nact)[T]
         assert (ret[m], sg[m]) == (tap["ret"], tap["sign"]) and tap["length"] == T, (ctx, m)
+        if check_ram:
+            assert tap["ram"].shape == (T, 128) and np.array_equal(tap["ram"][:, 38], tap["actions"]), (ctx, m)
+            assert np.array_equal(bc[m, :T], tap["ram"]), (ctx, m, "RAM trajectory", bc[m, :T, 38].tolist(), tap["actions"].tolist())
         _same(bn[m], tap["bn"], ctx, m, "bn")
         o1, o2, o3 = tap["y"]
         g1, g2, g3 = e.debug_activations(m)
@@ -156,17 +169,19 @@ def _check_es_eval(e, kind, knobs, idx, seeds, sigma, T, members, y1_written, fc
             assert np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]), (ctx, p)
 
 
-def _run_es_regime(kind, name, monkeypatch):
-    knobs, fc_kind, y1_written, sigmas = ES_REGIMES[name]
-    idx = S.edge_indices(S.P_ES if kind == KIND_ES else S.P_VBN)
+def _run_es_regime(kind, name, monkeypatch, nact=NACT, sigmas=None, check_ram=False):
+    """sigmas: None = the regime's own list"""
+    knobs, fc_kind, y1_written, own_sigmas = ES_REGIMES[name]
+    idx = S.edge_indices(S.num_params(kind, nact))
     n = len(idx)
     assert not _activated_pairs(n, knobs).any() or _activated_pairs(n, knobs).all()   # 11 pairs: no window of this population falls to the tail kernels
-    e = _es_engine(kind, knobs, n, monkeypatch, fc_kind is not None)
+    e = _es_engine(kind, knobs, n, monkeypatch, fc_kind is not None, nact, check_ram)
     try:
-        for sigma in sigmas:
+        for sigma in own_sigmas if sigmas is None else sigmas:
             seeds = np.repeat(S.tap_seeds(n), 2) if sigma == 0.0 else S.tap_seeds(2 * n)
             for T in S.TAP_STEPS:
-                _check_es_eval(e, kind, knobs, idx, seeds, sigma, T, range(2 * n), y1_written, fc_kind, (name, sigma, T))
+                _check_es_eval(e, kind, knobs, idx, seeds, sigma, T, range(2 * n), y1_written, fc_kind, (name, nact, sigma, T), nact, check_ram)
+        assert e.check_redzones() == 0
     finally:
         e.close()
 
@@ -200,16 +215,20 @@ def test_es_width_taps(width, name, monkeypatch):
     default: two windows of 32 / 33 pairs -- k_conv12t + k_fc_tail and k_conv1 / k_conv2 + k_fc_cols; in ONE window, DNE_NSUB=1, the 130
     members reach k_conv12 through its default gate, no DNE_CONV_FUSED_MIN; under the ring knobs three windows).  Up to 11 pairs every
     member is compared, above them step_tap_support.sampled_members (>= 16)."""
+    _run_es_width(width, name, monkeypatch)
+
+
+def _run_es_width(width, name, monkeypatch, nact=NACT, check_ram=False):
     knobs, fc_kind, _, _ = ES_REGIMES[name]
-    idx = S.width_indices(width, S.P_ES)
+    idx = S.width_indices(width, S.num_params(KIND_ES, nact))
     seeds = S.tap_seeds(2 * width)
     y1_written = name == "tail_default" and width == 33              # 65..128 members: the unfused k_conv1 (4 workgroups per member)
     if name == "tail_one_window" and width == 65:                    # 130 members in one window: above k_conv12t's range (64), so a y1 row
         y1_written = None                                            # nobody wrote means k_conv12 ran, through its default gate
-    e = _es_engine(KIND_ES, knobs, width, monkeypatch, fc_kind is not None)
+    e = _es_engine(KIND_ES, knobs, width, monkeypatch, fc_kind is not None, nact, check_ram)
     try:
         for T in S.TAP_STEPS:
-            _check_es_eval(e, KIND_ES, knobs, idx, seeds, 0.02, T, S.sampled_members(idx), y1_written, fc_kind, (name, width, T))
+            _check_es_eval(e, KIND_ES, knobs, idx, seeds, 0.02, T, S.sampled_members(idx), y1_written, fc_kind, (name, nact, width, T), nact, check_ram)
     finally:
         e.close()
 
@@ -309,19 +328,23 @@ def test_ga_regime_taps(knobs, monkeypatch):
     by default it groups the children by parent slot, a schedule: the default path is run that way too and its rows must be the oracle's
     up to that order) (its comments name the kernels: the noise-free k_fc_quad / k_fc_tail / k_fc_cols
     <1, false, false> on written-out children, parent + noise rows on the fly, k_fc_sub<1, false, false>, the streaming k_fc<1>)"""
+    _run_ga_regime(knobs, monkeypatch)
+
+
+def _run_ga_regime(knobs, monkeypatch, nact=NACT):
     from dne_hip import _lib
     for k, v in knobs.items():
         monkeypatch.setenv(k, v)
     for sort in ("0", "1") if not knobs else ("0",):
         monkeypatch.setenv("DNE_GA_SORT", sort)
-        e = _lib.Engine(_lib.KIND_GA, NACT, max_members=16, record_bc=True)
+        e = _lib.Engine(_lib.KIND_GA, nact, max_members=16, record_bc=True)
         try:
             e.noise_upload(S.small_noise())
-            for gen, seeds in zip((S.GA_GEN0, S.ga_gen1()), S.GA_SEEDS):
+            for gen, seeds in zip((S.ga_gen0(nact), S.ga_gen1(nact)), S.GA_SEEDS):
                 for T in S.GA_TAP_STEPS:
                     ret, sg, ln, bc = e.ga_eval([list(c) for c in gen], S.GA_SIGMA, T, seeds, want_bc=True)
                     assert (ln == T).all(), (knobs, T, ln.tolist())
-                    taps = [S.ga_member_taps(tuple(chain), S.GA_SIGMA, int(seeds[m]), S.GA_TAP_STEPS)[T] for m, chain in enumerate(gen)]
+                    taps = [S.ga_member_taps(tuple(chain), S.GA_SIGMA, int(seeds[m]), S.GA_TAP_STEPS, nact)[T] for m, chain in enumerate(gen)]
                     for m, tap in enumerate(taps):
                         assert (ret[m], sg[m]) == (tap["ret"], tap["sign"]) and np.array_equal(bc[m], tap["ram"][-1]), (knobs, T, m)
                     rows = [e.debug_activations(m)[1:] for m in range(len(gen))]
@@ -331,27 +354,13 @@ def test_ga_regime_taps(knobs, monkeypatch):
                     for m, tap in enumerate(taps):
                         _same(rows[m][0], tap["y"][1], knobs, T, gen[m], "y2")
                         _same(rows[m][1], tap["y"][2], knobs, T, gen[m], "y3")
+            assert e.check_redzones() == 0
         finally:
             e.close()
 
 
 # ---- LargeModel ------------------------------------------------------------------------------------------------------------------------
-LARGE_TAP_STEPS = (1, 3)
-
-
-@pytest.fixture(scope="module")
-def big_noise():
-    """first 9M entries of the reference noise stream, as in tests/test_gpu_large.py"""
-    return np.random.RandomState(123).randn(9_000_000).astype(np.float32)
-
-
-def _large_genomes(n, noise_len, P):
-    """n members: four roots (slice 0, the last legal slice, an odd and a 16-byte aligned start) unmutated, the rest their children with one
-    mutation each (seeded indices, powers 0.002 / 0.004)"""
-    hi = noise_len - P
-    roots = [(0,), (hi,), (1_234_567,), (2_000_000,)]
-    rs = np.random.RandomState(n)
-    return roots + [roots[i % 4] + ((int(rs.randint(0, hi + 1)), 0.002 if i % 2 else 0.004),) for i in range(n - 4)]
+LARGE_TAP_STEPS = S.LARGE_TAP_STEPS
 
 
 _LARGE_CASES = [
@@ -370,26 +379,30 @@ _LARGE_CASES = [
 
 
 @pytest.mark.parametrize("n,knobs", _LARGE_CASES)
-def test_large_model_taps(n, knobs, oracle, big_noise, monkeypatch):
+def test_large_model_taps(n, knobs, oracle, monkeypatch):
     """KIND_GA_LARGE: raw conv1 / conv2 / conv3 outputs and the fc's 512 sums (y1..y4 of debug_activations_large) after ga_eval_powers against
     forward_large_debug on the oracle's episode, for the first, the last and six sampled members (all six at n = 6).  Inside an evaluation the
     active list is cut into windows (plan_step): the tilings ns = 2 / 1 of k_lconv_mfma need more than 128 / 256 members in ONE window,
     which below ~400 members only DNE_NSUB=1 gives."""
+    _run_large(n, knobs, monkeypatch)
+
+
+def _run_large(n, knobs, monkeypatch, nact=NACT):
+    """(the genomes, their 9M-entry noise table and the oracle's side: step_tap_support.large_genomes / big_noise / large_member_taps)"""
     from dne_hip import _lib, ga_gpu
     for k, v in knobs.items():
         monkeypatch.setenv(k, v)
-    O = oracle
-    L = O.layout(O.KIND_GA_LARGE, NACT)
-    sb = ga_gpu.model_scale_by(NACT, _lib.KIND_GA_LARGE)
-    genomes = _large_genomes(n, big_noise.size, L.P)
+    big_noise = S.big_noise()
+    sb = ga_gpu.model_scale_by(nact, _lib.KIND_GA_LARGE)
+    genomes = S.large_genomes(n, nact)
     seeds = S.tap_seeds(n)
     pick = sorted({0, n - 1} | set(np.random.RandomState(n).permutation(n)[:6].tolist()))
-    taps = {m: S.oracle_taps(L, O.ga_gpu_rebuild(big_noise, genomes[m], sb), None, int(seeds[m]), LARGE_TAP_STEPS, large=True) for m in pick}
+    taps = {m: S.large_member_taps(n, m, nact) for m in pick}
     # DNE_GA_SORT=0: rows in the caller's member order; the default order (children grouped by parent, a schedule) once, at n = 6 where every
     # member has its oracle rows: the engine's rows must be the oracle's up to that order
     for sort in ("0", "1") if n == 6 and not knobs else ("0",):
         monkeypatch.setenv("DNE_GA_SORT", sort)
-        e = _lib.Engine(_lib.KIND_GA_LARGE, NACT, max_members=n)
+        e = _lib.Engine(_lib.KIND_GA_LARGE, nact, max_members=n)
         try:
             e.noise_upload(big_noise)
             e.ga_set_init_scale(sb)
@@ -405,5 +418,6 @@ def test_large_model_taps(n, knobs, oracle, big_noise, monkeypatch):
                 for m in pick:
                     for name, got, want in zip(("y1", "y2", "y3", "y4"), e.debug_activations_large(m), taps[m][T]["y"]):
                         _same(got, want, n, knobs, T, m, name)
+            assert e.check_redzones() == 0
         finally:
             e.close()
