@@ -27,6 +27,7 @@
 #include "forward_large.h"
 #include "reduce.h"
 #include "novelty.h"
+#include "plan.h"
 
 using namespace dne;
 
@@ -559,18 +560,9 @@ __global__ void k_iota(int *p, int n) {
 }
 
 // ------------------------------------------------------------------------------- launch plan
-// The kernel regime of one burst of lock-steps (the active list between two compactions) as a value: plan_step makes it from the
-// handle's knobs, the member set's facts and the active count, and the launchers take it as an argument.  The empty plan is what
-// every caller outside an evaluation passes (dne_act, the reference pass): one window, k_fc or the column-split kernels.
-struct StepPlan {
-    int nsub = 1;            // windows the active list is cut into, each on its own stream
-    bool sub = false;        // every window: k_fc_sub (one wave per sub-slice chain), the head folds its chain sums
-    bool duo = false;        // windows above fc_tail_max groups: table-ordered units (k_unit_order + k_fc_duo + k_out) ...
-    bool duo_solo = false;   // ... one unit per wave instead of two (sparse table: little to share, and twice the waves)
-    bool ring = false;       // ... k_fc_ring instead of k_fc_duo (the windows' convolutions leave activated y2)
-    bool ring_scaled = false; // ... its DMA source the table scaled by the evaluation's sigma (noise_pre)
-    bool fc2 = false;        // else k_fc2 (two pairs per work item share the base rows), else k_fc
-};
+// plan.h decides what a lock-step launches (Knobs + PlanFacts + the active count -> StepPlan per burst -> WindowPlan per window); the launchers
+// below take those values as arguments.  The empty StepPlan is what every caller outside an evaluation passes (dne_act).
+constexpr int N_STREAMS = 4;   // the main stream + 3 window streams: more than four windows measured slower (round 3, 5 / 6 / 8 at full width: +7.5 / +5.4 / +7.2 %; round 4 with one k_fc_duo workgroup per CU: +8.4 / +5.9 / +4.4 %)
 
 // the members of a tail table as arguments of the emulator's kernels (null: no table in force)
 static void set_tail_table(EnvArgs &E, const TailTable *tt) {
@@ -589,70 +581,25 @@ struct dne_handle {
     std::string err;
     hipStream_t stream = nullptr;
     std::vector<hipStream_t> sub_streams;   // sub-batch streams (sub_streams[0] == stream)
-    int dbg_skip = 0;   // DNE_DEBUG_SKIP bitmask (timing experiments only): 1 conv1, 2 conv2, 4 render
-    int dbg_immortal = 0;   // DNE_DEBUG_IMMORTAL (timing experiments only): every member lives until tslimit -- a lock-step keeps its width
-    int render_threads = 512;        // DNE_RENDER_THREADS: threads per k_env_render workgroup above 192 members (one workgroup per member).  Round 5: 512 -- beside k_fc_ring a generation takes 216.8 instead of 223.1 ms same-box (768: 217.2, 1024: 235.3); rounds 1-4: 256 (beside k_fc_duo 512 measured +1 %)
-    int conv1_fpw = 8;               // reference pass: frames per conv1 workgroup (DNE_CONV1_FPW: 1, 2, 4, 8)
-    int conv_fused = 1, conv_fused_min = 129;   // DNE_CONV_FUSED / DNE_CONV_FUSED_MIN: conv1 + conv2 in one kernel from this many members
-    int conv12t_max = 64;            // members up to which conv1 -> conv2 is one launch of four workgroups per member (DNE_CONV12T_MAX, 0 = off)
-    int conv_split_max = 32;         // members up to which the convolutions use their finest split (DNE_CONV_SPLIT_MAX)
-    int conv_split_mid = 256;        // ... their middle split: conv1 over 4 workgroups up to this many members, conv2 over 2 up to twice as many (DNE_CONV_SPLIT_MID)
-    int fc_pairs = 2;                // ES full-width fc: antithetic pairs per work item (DNE_FC_PAIRS, 1 = k_fc<2>)
-    int fc2_min_total = 800;         // k_fc2 from this many active groups upwards (DNE_FC2_MIN)
-    int duo_solo_below = 1500;       // DNE_DUO_SOLO_BELOW: with fewer active groups (all windows) every wave takes one unit instead of two (sparse table: little to share, and twice the waves)
-    int out_lds_kb = 0;              // DNE_OUT_LDS_KB: an unused LDS reservation that bounds k_out's workgroups per CU (round 2's k_out staged 37 KB of output
-                                     // weights and ran best at two workgroups per CU = 64 KB; round 3's stages nothing)
-    int duo_head_fused = 0;          // DNE_DUO_HEAD_FUSED: behind k_fc_duo the policy head and the emulator step share a launch (k_tail_step) instead of
-                                     // k_out + k_env_logic; same-box A/B: 402.7 ms fused, 403.3 separate, 399.8 separate with k_out at two workgroups per CU -> off
-    int conv2_ref_fpw = 8;           // DNE_CONV2_REF_FPW: reference frames per conv2 workgroup (8, 4, or 1 = the lock-step kernel)
-    int duo_sync = 1;                // DNE_DUO_SYNC: row blocks per barrier of the sweep (1-8)
-    int burst = 32, burst_tail = 16; // DNE_BURST / DNE_BURST_TAIL: lock-steps between two compactions of the active list (a host round trip each), at large / with at most fc_tail_max groups alive (round 4: 32 at large, 16 before; 24 / 32 / 48 measured -0.5 .. -0.9 %, 8 +2.3 %, 64 +0.2 %; the tail indifferent)
+    Knobs k;                         // the DNE_* scheduling and tuning knobs (plan.h: one table), read once by dne_create
     double dense_scale = 1.0;        // table length / the stretch of the table this evaluation's noise slices cover (dne_es_eval; 1 for every other caller): a rank that draws
                                      // its indices from its own 1/N of the table (es.py shard 'table') holds pairs as dense as N times as many over the whole table
-    int sub_render_fused = 0;        // DNE_SUB_RENDER_FUSED (round 6): behind the sub-slice fc the policy head, the emulator AND the renderer in one launch (k_tail_step<.., true>, 1024 threads per member): three launches per window and lock-step instead of four
-    int ring_min = 1000;             // DNE_RING_MIN: k_fc_ring needs this many active pairs on the rank whatever their density (below, its workgroups -- eight units, one per CU --
-                                     // no longer fill the chip: a 625-pair share measured 61.6 ms per generation on the ring against 57.8 on k_fc_duo, profiles/r06_shard_ab.jsonl)
-    int ring_on = 1;                 // DNE_FC_RING (round 5): k_fc_ring instead of k_fc_duo -- the workgroup's noise rows through an LDS ring filled by LDS-DMA, the base rows from a column-permuted copy of the fc matrix; 1: from DNE_DUO_SOLO_BELOW active pairs (1500) upwards, 2: in the whole k_fc_duo range (measured slower in the sparse part: 239 vs 233 ms), 0: k_fc_duo everywhere
     float *noise_pre = nullptr;      // the noise table scaled by the evaluation's sigma, fl(sigma * eps) entry by entry (k_scale_table): k_fc_ring<true>'s DMA source.  Built the first
                                      // time an evaluation enters the ring's range at that sigma (ES runs keep one sigma: once per run, 0.4 ms), dropped with the table
     size_t noise_pre_count = 0;      // entries of the table the copy was made from (0: none)
     float noise_pre_sigma = 0.0f;    // the sigma it holds
-    int ring_pre = 1;                // DNE_RING_PRE: 0 = the ring multiplies every row by sigma itself (rounds 5-6a)
+    bool noise_pre_no_room = false;  // the copy did not fit once: the ring scales its rows itself from then on
     bool pair_sigma_uniform = false; // every pair of the member set is (+s, -s) with ONE s (dne_set_members)
     float pair_sigma = 0.0f;
     float *theta_perm = nullptr;     // [3872 + 16][256]: base slot 0's fc matrix, every row stored as columns l, l+64, l+128, l+192 per lane (k_theta_perm, once per evaluation)
-    int duo_fat = 1;                 // DNE_DUO_FAT: k_fc_duo with a register footprint past 256 per lane = at most one of its workgroups per CU (it streams as fast from one), so the other windows' kernels always find room beside it
-    int fc_sub = 1;                  // DNE_FC_SUB (ES 2, GA 1): the sub-slice fc (k_fc_sub: one wave per 128 / 120-row chain) in the mid range -- 0 off, 1 GA children (materialised), 2 also ES pairs
-    int fc_sub_min = 97, fc_sub_max = 320;   // DNE_FC_SUB_MIN / _MAX: active groups (all windows) between which it runs (max: 450 for ES pairs, 320 for GA children)
-    int fc_sub_nsub = 2;             // DNE_FC_SUB_NSUB: windows of that regime (ES 3, GA 4 since round 6)
-    int fc_sub_spw = 0;              // DNE_FC_SUB_SPW: sub-slices per wave (1, 2, 4, 8; 0 = by width)
-    int fc_sub_grid = 512;           // DNE_FC_SUB_GRID: workgroups of k_fc_sub at most, 4 waves each (GA 512 = two waves per SIMD; ES: the whole launch resident)
-    int fc_sub_prio = 0;             // DNE_FC_SUB_PRIO: s_setprio of k_fc_sub's waves (ES 0: the regime is bound by a window's chain of small kernels, they must not starve; GA: 0 since round 6, 3 on its bounded grid before)
-    int fc_sub_head = 1;             // DNE_FC_SUB_HEAD: policy head + emulator step in one launch (k_tail_step) behind k_fc_sub instead of k_out + k_env_logic
     float *y3s = nullptr;            // [member][32][256]: the chain sums k_fc_sub leaves for k_out<.., SUB>
-    int duo_grid = 0;                // DNE_DUO_GRID: persistent grid of k_fc_duo (0 = fc_grid)
-    int duo_sweep = 2;               // DNE_DUO_SWEEP (0 = off): the four waves of a k_fc_duo workgroup walk one table timeline (1: two units per wave only, 2: also one unit per wave)
-    int fc_prio = 3;                 // DNE_FC_PRIO: s_setprio of k_fc_duo's waves (0-3)
-    int duo_lag = 0;                 // DNE_DUO_LAG: extra row batches by which the second unit of a duo trails the first
-    int fc_duo = 1, fc_duo_min = 451;   // DNE_FC_DUO / DNE_FC_DUO_MIN: table-ordered fc (k_unit_order + k_fc_duo + k_out) from this many active groups (round 4: 451, right above the sub-slice fc's range; 800 before -- with one k_fc_duo workgroup per CU a 625-pair share takes 84.5 instead of 88.4 ms per generation)
     int *unit_order = nullptr;       // [4 * groups]: per window, its (group, k-slice) units in noise-table order
-    int spec_max = 4;                // DNE_SPEC_MAX: a single window of up to this many members (2 antithetic pairs; round 2: 8 -- the faster tail kernels of round 3 beat speculation at 4 pairs, 47 vs 56 us) steps speculatively -- every action's outcome is worked out under the forward pass; 0 = off
-    uint8_t *spec_prev = nullptr, *spec_cur = nullptr, *spec_stacks = nullptr;
+    uint8_t *spec_prev = nullptr, *spec_cur = nullptr, *spec_stacks = nullptr;   // candidate outcomes of the speculative tail (DNE_SPEC_MAX)
     int32_t *spec_rw = nullptr;
     float *spec_y1 = nullptr;
-    int spec_bands = 7;              // DNE_SPEC_BANDS: 256-thread workgroups per candidate frame
-    int spec_conv1 = 1;              // DNE_SPEC_CONV1: conv1 of every candidate stack in the launch that picks the action
     bool uniform_base = false;       // every member perturbs the same base slot (dne_set_members checks)
     bool antithetic_slot0 = false;   // what k_theta_perm + k_fc_ring assume, checked member by member in dne_set_members: base slot 0 everywhere and
                                      // members (2i, 2i+1) = (offset, +s), (the same offset, -s) -- es.py:412-419's pairs, nothing else
-    int render_bands = 8, band_threads = 512;   // tail: workgroups per frame (DNE_RENDER_BANDS, 1 = render inside k_tail_step) and their size
-    int render_wg_max = 512;         // ... halved until members x bands fits this many workgroups (DNE_RENDER_WG_MAX)
-    int tail_fused_max = 200;        // up to this many active groups (all windows) k_out + k_env_logic + k_env_render run as one kernel (DNE_TAIL_FUSED_MAX)
-    int nsub_mid = 4;                // DNE_NSUB_MID: windows between 800 and 1899 active groups
-    int nsub_full = 4;               // DNE_NSUB_FULL: windows at full width (>= 1900 active groups)
-    int nsub_fixed = 0, fc_grid = 512, fc_tail_max = 96, fc_rb = 4, fc_chain_min = 1 << 30;
-    int fc_tailk_max = 32;           // DNE_FC_TAILK_MAX: up to this many groups per window k_fc_tail (16 workgroups per group), above it k_fc_cols (4 lean ones)
-    int fc_quad_max = 4;             // DNE_FC_QUAD_MAX: up to this many groups per window the 64-workgroups-per-group fc (k_fc_quad); above it k_fc_tail
     int M = 0, F = 0, ref_chunk = 0;
     size_t base_stride = 0;
     // device memory
@@ -662,11 +609,8 @@ struct dne_handle {
     double *partial = nullptr;
     uint8_t *ref = nullptr; bool ref_set = false;
     float *ref_f32 = nullptr;        // the reference frames as padded planar floats (k_conv1_ref_shared)
-    int conv1_shared = 1;            // DNE_CONV1_SHARED: reference-pass conv1 with eight members sharing a frame in LDS
     int32_t *m_slot = nullptr; int64_t *m_off = nullptr; float *m_scale = nullptr;
     std::vector<int32_t> host_slot; std::vector<int64_t> host_off; std::vector<float> host_scale;   // what dne_set_members uploaded
-    int tt_enable = 1;               // DNE_TAIL_TABLE
-    int head_threads = 320;          // DNE_HEAD_THREADS: 320 = the policy head's four waves + a fifth that steps the emulator for every action meanwhile; 256 = one lane steps it afterwards
     float *bn = nullptr, *bn_mom = nullptr;
     uint8_t *ram_prev = nullptr, *ram_cur = nullptr, *stacks = nullptr;
     ResizeLds *tables = nullptr;
@@ -675,11 +619,8 @@ struct dne_handle {
     int32_t *launch_units = nullptr; size_t launch_units_cap = 0;
     uint32_t *seeds = nullptr;
     float *y1 = nullptr, *y2 = nullptr, *y3 = nullptr, *y3t = nullptr;   // step mode: one row per member (y3t: 4 k-slice partials)
-    int ga_materialize = 0;          // DNE_GA_MATERIALIZE: GA children written out once per generation, the streaming fc then reads plain rows (default: on for GA engines)
     bool members_materialized = false;   // the current members are plain vectors (scale 0 everywhere): kernels that have one skip the noise stream
     std::vector<int> child_slots;    // base slots set aside for materialised children
-    int lfc_pad = 2;                 // DNE_LFC_PAD: LargeModel's streamed fc with a padded register footprint -- 1: at most two of its workgroups per CU, 2: one (0: as many as fit, five); same-box 282.5 / 285.2 / 291.2 k env-steps/s at 0 / 1 / 2
-    int lfc_cols_max = 96;           // DNE_LFC_COLS_MAX: LargeModel windows of up to this many members use the column-split fc
     bool large = false;              // DNE_KIND_GA_LARGE: y1 [441][32], y2 / y3 [121][64] (conv3 output), y3t = the 512 fc outputs
     float *y1r[2] = {nullptr, nullptr}, *y2r[2] = {nullptr, nullptr}, *y3pr[2] = {nullptr, nullptr};   // reference pass scratch, two ways
     float *fr1[2] = {nullptr, nullptr}, *fr2[2] = {nullptr, nullptr};   // per-frame batch-norm moments of conv1 / conv2 ([rows][2][C])
@@ -697,7 +638,6 @@ struct dne_handle {
     dne_profile prof{};
     // GA parent cache: prefix chain -> base slot
     std::map<std::vector<int64_t>, int> ga_cache;
-    int ga_sort = 1;                 // DNE_GA_SORT: evaluate a generation's children grouped by parent
     int ga_cache_mode = 0; float ga_cache_sigma = 0.0f;   // what the cached parents were built with (1 sigma / 2 per-seed powers)
     std::vector<int> free_slots;
     // every device allocation of the handle, each between two poisoned red zones (dne_check_redzones)
@@ -790,10 +730,18 @@ struct dne_handle {
         EnvArgs E;
         E.ram_prev = ram_prev; E.ram_cur = ram_cur; E.stacks = stacks; E.T = tables;
         E.ret = ret; E.sign = sign; E.step_reward = step_reward; E.len = len; E.done = done; E.stepped = stepped; E.action = action; E.step_counter = nullptr;
-        E.bc = bc; E.bc_mode = bc ? bc_mode : 0; E.bc_max_steps = cfg.bc_max_steps; E.immortal = dbg_immortal;
+        E.bc = bc; E.bc_mode = bc ? bc_mode : 0; E.bc_max_steps = cfg.bc_max_steps; E.immortal = k.dbg_immortal;
         E.spec_prev = spec_prev; E.spec_cur = spec_cur; E.spec_rw = spec_rw; E.spec_stacks = spec_stacks; E.spec_y1 = spec_y1;
         set_tail_table(E, tt);
         return E;
+    }
+    // what plan.h reads beyond the knobs
+    PlanFacts facts() const {
+        PlanFacts f{};
+        f.dense_scale = dense_scale; f.kind = L.kind; f.members_materialized = members_materialized; f.uniform_base = uniform_base;
+        f.antithetic_slot0 = antithetic_slot0; f.pair_sigma_uniform = pair_sigma_uniform; f.n_streams = (int)sub_streams.size();
+        f.has_y3s = y3s != nullptr; f.has_theta_perm = theta_perm != nullptr; f.has_scaled_table = noise_pre != nullptr;
+        return f;
     }
     hipEvent_t event(size_t i) {
         while (ev_pool.size() <= i) {
@@ -832,10 +780,6 @@ struct DeviceGuard {
     }
     ~DeviceGuard() { if (prev >= 0) hipSetDevice(prev); }
 };
-
-// ES-like kinds: ESAtariPolicy and the GPU tree's ModelVirtualBN -- the same network, virtual batch norm over a reference batch, antithetic
-// pairs over one theta, the ES reduce and optimizer; they differ only in the flat layout (make_layout)
-static inline bool es_like(int kind) { return kind == DNE_KIND_ES || kind == DNE_KIND_ES_VBN; }
 
 static void make_layout(int kind, int nact, Layout *L) {
     int o = 0;
@@ -950,6 +894,32 @@ extern "C" int dne_num_params(int kind, int nact) {
     return L.P;
 }
 
+// the engine's knobs as dne_create reads them
+static Knobs engine_knobs(int kind, int nact) { return knobs_from_env(kind, nact, SPEC_ACTIONS - 2); }
+
+extern "C" int dne_debug_plan(int kind, int n_actions, const dne_plan_facts *facts, int total, int gsize, dne_window_plan *out, int cap,
+                              int *nsub, int whole_eval) {
+    const Knobs k = engine_knobs(kind, n_actions);
+    PlanFacts f = *facts;
+    f.kind = kind;
+    const StepPlan p = plan_step(k, f, total, gsize, whole_eval != 0);
+    if (nsub) *nsub = p.nsub;
+    if (whole_eval) return fc_full_kind(p);
+    for (int s = 0; s < p.nsub && s < cap; s++) {
+        const Window c = window(total, p.nsub, s);
+        out[s] = plan_window(k, f, p, total, c.cnt, gsize, true);
+        out[s].lo = c.lo;
+    }
+    return 0;
+}
+
+extern "C" int dne_debug_knob(int kind, int n_actions, const char *name) {
+    const Knobs k = engine_knobs(kind, n_actions);
+    for (const KnobRow &r : KNOBS)
+        if (!strcmp(r.env, name)) return k.*r.field;
+    return -1;
+}
+
 extern "C" const char *dne_last_error(dne_handle *h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
 constexpr size_t OVERFETCH_FLOATS = 2 * 8 * 256 + 64;   // one row block of the streaming fc + the 64 floats of slack the table always had
@@ -995,11 +965,10 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
     CH(hipSetDevice(cfg->device_id));
     CH(hipStreamCreate(&h->stream));
     h->sub_streams.push_back(h->stream);
-    // tuning knobs (measurement only; every value is clamped to what the kernels support)
+    // the diagnosis switches (the scheduling and tuning knobs: plan.h)
     auto env_int = [](const char *name, int lo, int hi, int *dst) {
         if (const char *e = getenv(name)) *dst = std::max(lo, std::min(hi, atoi(e)));
     };
-    auto wg_size = [](int v) { return v >= 1024 ? 1024 : v >= 512 ? 512 : 256; };   // the renderer needs >= 210 threads, whole waves
     {
         int rz = 1, tr = 0, ds = 0;
         env_int("DNE_REDZONE", 0, 1, &rz); env_int("DNE_TRACE", 0, 1, &tr); env_int("DNE_DEBUG_SYNC", 0, 1, &ds);
@@ -1008,9 +977,7 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         env_int("DNE_STAGED_COPY", 0, 1, &sc);
         h->staged_copies = sc != 0;
     }
-    env_int("DNE_GA_SORT", 0, 1, &h->ga_sort);
-    env_int("DNE_CONV_FUSED", 0, 1, &h->conv_fused);
-    env_int("DNE_CONV_FUSED_MIN", 1, 1 << 20, &h->conv_fused_min);
+    h->k = engine_knobs(cfg->policy_kind, cfg->n_actions);
     CH(hipFuncSetAttribute((const void *)k_conv12<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Conv12Lds)));
     CH(hipFuncSetAttribute((const void *)k_conv12<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Conv12Lds)));
     CH(hipFuncSetAttribute((const void *)k_conv12t<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Conv12Lds)));
@@ -1025,14 +992,6 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
     CH(hipFuncSetAttribute((const void *)k_out<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
     CH(hipFuncSetAttribute((const void *)k_out<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
     CH(hipFuncSetAttribute((const void *)k_out<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    env_int("DNE_NSUB", 1, 4, &h->nsub_fixed);
-    env_int("DNE_NSUB_FULL", 1, 4, &h->nsub_full);
-    env_int("DNE_NSUB_MID", 1, 4, &h->nsub_mid);
-    env_int("DNE_FC_TAIL_MAX", 1, 1 << 20, &h->fc_tail_max);
-    env_int("DNE_FC_QUAD_MAX", 0, 1 << 20, &h->fc_quad_max);
-    env_int("DNE_FC_TAILK_MAX", 0, 1 << 20, &h->fc_tailk_max);
-    env_int("DNE_DEBUG_SKIP", 0, 7, &h->dbg_skip);
-    env_int("DNE_DEBUG_IMMORTAL", 0, 1, &h->dbg_immortal);
 #ifdef DNE_PHASE_CLOCK
     {
         int burn = 0;
@@ -1040,53 +999,7 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         CH(hipMemcpyToSymbol(HIP_SYMBOL(g_env_burn), &burn, sizeof(int)));
     }
 #endif
-    env_int("DNE_TAIL_TABLE", 0, 1, &h->tt_enable);
-    env_int("DNE_HEAD_THREADS", 256, 320, &h->head_threads); h->head_threads = h->head_threads >= 320 ? 320 : 256;
-    env_int("DNE_RENDER_THREADS", 256, 1024, &h->render_threads); h->render_threads = wg_size(h->render_threads);
-    env_int("DNE_BAND_THREADS", 256, 1024, &h->band_threads); h->band_threads = wg_size(h->band_threads);
-    env_int("DNE_TAIL_FUSED_MAX", 0, 1 << 20, &h->tail_fused_max);
-    env_int("DNE_FC_PAIRS", 1, 2, &h->fc_pairs);
-    env_int("DNE_CONV1_FPW", 1, 8, &h->conv1_fpw);
-    env_int("DNE_CONV_SPLIT_MAX", 0, 1 << 20, &h->conv_split_max);
-    env_int("DNE_CONV12T_MAX", 0, 1 << 20, &h->conv12t_max);
-    env_int("DNE_CONV_SPLIT_MID", 0, 1 << 20, &h->conv_split_mid);
-    env_int("DNE_FC2_MIN", 2, 1 << 30, &h->fc2_min_total);
-    env_int("DNE_SPEC_MAX", 0, 64, &h->spec_max);
-    env_int("DNE_SPEC_BANDS", 1, 12, &h->spec_bands);
-    env_int("DNE_SPEC_CONV1", 0, 1, &h->spec_conv1);
-    env_int("DNE_FC_DUO", 0, 1, &h->fc_duo);
-    env_int("DNE_DUO_LAG", 0, 64, &h->duo_lag);
-    env_int("DNE_FC_PRIO", 0, 3, &h->fc_prio);
-    env_int("DNE_DUO_SWEEP", 0, 2, &h->duo_sweep);
-    env_int("DNE_DUO_SYNC", 1, 8, &h->duo_sync);
-    env_int("DNE_DUO_FAT", 0, 1, &h->duo_fat); env_int("DNE_FC_RING", 0, 2, &h->ring_on); env_int("DNE_RING_MIN", 0, 1 << 30, &h->ring_min); env_int("DNE_RING_PRE", 0, 1, &h->ring_pre); env_int("DNE_SUB_RENDER_FUSED", 0, 1, &h->sub_render_fused);
-    env_int("DNE_BURST", 1, 256, &h->burst);
-    env_int("DNE_BURST_TAIL", 1, 256, &h->burst_tail);
-    env_int("DNE_DUO_GRID", 0, 1 << 16, &h->duo_grid);
-    // measured (tools/ga_lockstep_profile.py, tools/ab_inproc.py --pairs 312 / 625): Deep-GA children 97 .. 320
-    // alive, two windows, a grid of 512 workgroups at wave priority 3; ES pairs 97 .. 450 alive, three windows, the whole launch
-    // resident, no priority (its chain of small kernels must not starve); above those widths the streaming kernels win
-    if (es_like(cfg->policy_kind)) { h->fc_sub = 2; h->fc_sub_max = 450; h->fc_sub_nsub = 3; h->fc_sub_grid = 1 << 20; h->fc_sub_prio = 0; }
-    else { h->fc_sub = 1; h->fc_sub_max = 320; h->fc_sub_nsub = 4; h->fc_sub_grid = 512; h->fc_sub_prio = 0; }   // round 6: four windows at wave priority 0 (was two at 3): Deep GA 1.02-1.05 vs 0.98-1.00 M env-steps/s same-box; five / six windows 0.91-0.94
-    env_int("DNE_FC_SUB", 0, 2, &h->fc_sub);
-    env_int("DNE_FC_SUB_MIN", 1, 1 << 30, &h->fc_sub_min);
-    env_int("DNE_FC_SUB_MAX", 1, 1 << 30, &h->fc_sub_max);
-    env_int("DNE_FC_SUB_NSUB", 1, 4, &h->fc_sub_nsub);
-    env_int("DNE_FC_SUB_SPW", 0, 8, &h->fc_sub_spw);
-    env_int("DNE_FC_SUB_PRIO", 0, 3, &h->fc_sub_prio);
-    env_int("DNE_FC_SUB_GRID", 1, 1 << 20, &h->fc_sub_grid);
-    env_int("DNE_FC_SUB_HEAD", 0, 1, &h->fc_sub_head);
-    if (h->fc_sub_spw != 1 && h->fc_sub_spw != 2 && h->fc_sub_spw != 4 && h->fc_sub_spw != 8) h->fc_sub_spw = 0;
-    env_int("DNE_CONV2_REF_FPW", 1, 8, &h->conv2_ref_fpw);
-    env_int("DNE_DUO_SOLO_BELOW", 0, 1 << 30, &h->duo_solo_below);
-    env_int("DNE_DUO_HEAD_FUSED", 0, 1, &h->duo_head_fused);
-    env_int("DNE_OUT_LDS_KB", 0, 64, &h->out_lds_kb);
-    env_int("DNE_FC_DUO_MIN", 2, 1 << 30, &h->fc_duo_min);
-    env_int("DNE_RENDER_BANDS", 1, 84, &h->render_bands);
-    env_int("DNE_RENDER_WG_MAX", 1, 1 << 20, &h->render_wg_max);
-    env_int("DNE_FC_CHAIN_MIN", 1, 1 << 30, &h->fc_chain_min);
-    env_int("DNE_FC_GRID", 1, 1 << 16, &h->fc_grid);
-    for (int s = 1; s < 4; s++) { hipStream_t st; CH(hipStreamCreate(&st)); h->sub_streams.push_back(st); }   // more than four windows measured slower (round 3, 5 / 6 / 8 at full width: +7.5 / +5.4 / +7.2 %; round 4 with one k_fc_duo workgroup per CU: +8.4 / +5.9 / +4.4 %)
+    for (int s = 1; s < N_STREAMS; s++) { hipStream_t st; CH(hipStreamCreate(&st)); h->sub_streams.push_back(st); }
     make_layout(cfg->policy_kind, cfg->n_actions, &h->L);
     h->M = cfg->max_members;
     h->F = es_like(cfg->policy_kind) ? (cfg->ref_count > 0 ? cfg->ref_count : 128) : 0;
@@ -1102,7 +1015,6 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
     CH(h->alloc(&h->partial, 2 * ((size_t)h->L.P / 256 + 1), "partial"));
     if (h->F) CH(h->alloc(&h->ref, (size_t)h->F * OB_BYTES, "ref"));
     if (h->F) CH(h->alloc(&h->ref_f32, (size_t)h->F * RF_FRAME, "ref_f32"));
-    env_int("DNE_CONV1_SHARED", 0, 1, &h->conv1_shared);
     CH(hipFuncSetAttribute((const void *)k_conv1_ref_shared<16>, hipFuncAttributeMaxDynamicSharedMemorySize, RF_FRAME * (int)sizeof(float)));
     CH(hipFuncSetAttribute((const void *)k_conv1_ref_shared<8>, hipFuncAttributeMaxDynamicSharedMemorySize, RF_FRAME * (int)sizeof(float)));
     CH(h->alloc(&h->m_slot, M, "m_slot")); CH(h->alloc(&h->m_off, M, "m_off")); CH(h->alloc(&h->m_scale, M, "m_scale"));
@@ -1122,21 +1034,13 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
     CH(h->alloc(&h->len, M, "len")); CH(h->alloc(&h->done, M, "done")); CH(h->alloc(&h->action, M, "action")); CH(h->alloc(&h->seeds, M, "seeds")); CH(h->alloc(&h->stepped, M, "stepped"));
     CH(hipMemset(h->done, 0, M * sizeof(int32_t))); CH(hipMemset(h->len, 0, M * sizeof(int32_t)));
     h->large = cfg->policy_kind == DNE_KIND_GA_LARGE;
-    h->ga_materialize = es_like(cfg->policy_kind) ? 0 : 1;
-    env_int("DNE_GA_MATERIALIZE", 0, 1, &h->ga_materialize);
-    env_int("DNE_LFC_COLS_MAX", 0, 1 << 20, &h->lfc_cols_max);
-    env_int("DNE_LFC_PAD", 0, 2, &h->lfc_pad);
-    if (h->large) h->fc_rb = 8;      // the streamed LargeModel fc: 8-row batches measured 8 % faster than 4
-    env_int("DNE_FC_RB", 2, 8, &h->fc_rb);
-    if (es_like(cfg->policy_kind)) h->ga_materialize = 0;   // ES members are antithetic pairs over one theta: nothing to write out
     if (h->large) { CH(h->alloc(&h->y1, M * 14112, "y1")); CH(h->alloc(&h->y2, M * 7744, "y2")); CH(h->alloc(&h->y3, M * 7744, "y3")); CH(h->alloc(&h->y3t, M * 512, "y3t")); }
     else { CH(h->alloc(&h->y1, M * 7056, "y1")); CH(h->alloc(&h->y2, M * 3872 + 64, "y2"));   /* (+ 64: k_fc_ring fetches the eight activations behind a slice's end and never uses them) */ CH(h->alloc(&h->y3, M * 256, "y3")); CH(h->alloc(&h->y3t, M * 4 * 256, "y3t")); }
     CH(h->alloc(&h->unit_order, M * 4, "unit_order"));
-    if (!h->large && h->fc_sub) CH(h->alloc(&h->y3s, M * 32 * 256, "y3s"));
-    if (!h->large && h->ring_on && es_like(cfg->policy_kind)) CH(h->alloc(&h->theta_perm, (size_t)(3872 + 16) * 256, "theta_perm"));
-    if (cfg->n_actions > SPEC_ACTIONS - 2) h->spec_max = 0;
-    if (h->spec_max > 0) {   // candidate outcomes of the speculative tail: [list position][action]
-        const size_t rows = (size_t)h->spec_max * SPEC_ACTIONS;
+    if (!h->large && h->k.fc_sub) CH(h->alloc(&h->y3s, M * 32 * 256, "y3s"));
+    if (!h->large && h->k.ring_on && es_like(cfg->policy_kind)) CH(h->alloc(&h->theta_perm, (size_t)(3872 + 16) * 256, "theta_perm"));
+    if (h->k.spec_max > 0) {   // candidate outcomes of the speculative tail: [list position][action]
+        const size_t rows = (size_t)h->k.spec_max * SPEC_ACTIONS;
         CH(h->alloc(&h->spec_prev, rows * 128, "spec_prev")); CH(h->alloc(&h->spec_cur, rows * 128, "spec_cur"));
         CH(h->alloc(&h->spec_rw, rows * 2, "spec_rw")); CH(h->alloc(&h->spec_stacks, rows * OB_BYTES, "spec_stacks"));
         CH(h->alloc(&h->spec_y1, rows * 7056, "spec_y1"));
@@ -1391,13 +1295,13 @@ static void launch_env_reset(dne_handle *h, int n) {
     hipLaunchKernelGGL(k_env_render, dim3(n), dim3(256), 0, h->stream, E, (const int *)nullptr, 1, 1, 1);   // FrameStack reset: 4 copies
 }
 
-static void launch_env_step(dne_handle *h, const EnvArgs &E, const int *list, int count, int gsize, int tslimit,
+static void launch_env_step(dne_handle *h, const WindowPlan &w, const EnvArgs &E, const int *list, int gsize, int tslimit,
                             hipStream_t st = nullptr) {
     if (!st) st = h->stream;
-    const int items = count * gsize;
+    const int items = w.cnt * gsize;
     hipLaunchKernelGGL(k_env_logic, dim3((items + 63) / 64), dim3(64), 0, st, E, list, gsize, items, tslimit);
-    if (h->dbg_skip & 4) return;
-    hipLaunchKernelGGL(k_env_render, dim3(items), dim3(items <= 192 ? 1024 : h->render_threads), 0, st, E, list, gsize, 0, 1);
+    if (w.skip & 4) return;
+    hipLaunchKernelGGL(k_env_render, dim3(items), dim3(w.render_wg), 0, st, E, list, gsize, 0, 1);
 }
 
 // ------------------------------------------------------------------------------- env ABI
@@ -1423,7 +1327,7 @@ extern "C" int dne_env_step(dne_handle *h, int n, const int32_t *actions, float 
         if (actions[i] < 0 || actions[i] >= h->cfg.n_actions) return h->fail("action %d out of range", actions[i]);
     HCHECK(h, hipMemcpyAsync(h->action, actions, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HCHECK(h, hipMemsetAsync(h->step_reward, 0, n * sizeof(float), h->stream));
-    launch_env_step(h, h->env(0), nullptr, n, 1, 0x7fffffff);
+    launch_env_step(h, plan_window(h->k, h->facts(), StepPlan{}, n, n, 1, false), h->env(0), nullptr, 1, 0x7fffffff);
     HCHECK(h, hipGetLastError());
     if (reward) HCHECK(h, hipMemcpyAsync(reward, h->step_reward, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     if (done) HCHECK(h, hipMemcpyAsync(done, h->done, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -1513,11 +1417,11 @@ static int ref_pass(dne_handle *h, int n) {
         hipStream_t st = h->sub_streams[w];
         float *y1 = h->y1r[w], *y2 = h->y2r[w], *y3p = h->y3pr[w];
         float *fr1 = h->fr1[w], *fr2 = h->fr2[w];
-        const int fpw = h->conv1_fpw >= 8 ? 8 : h->conv1_fpw >= 4 ? 4 : h->conv1_fpw >= 2 ? 2 : 1;   // F is a multiple of 8
+        const int fpw = h->k.conv1_fpw >= 8 ? 8 : h->k.conv1_fpw >= 4 ? 4 : h->k.conv1_fpw >= 2 ? 2 : 1;   // F is a multiple of 8
 #define C1R(FPW) hipLaunchKernelGGL(k_conv1_ref<FPW>, dim3(nc * F / FPW), dim3(256), 0, st, A, F, m0, (const uint8_t *)h->ref, y1, fr1)
 #define C1S(FPW) hipLaunchKernelGGL(k_conv1_ref_shared<FPW>, dim3((nc + 7) / 8 * (F / FPW)), dim3(512), RF_FRAME * sizeof(float), st, A, F, m0, nc, (const float *)h->ref_f32, y1, fr1)
-        if (h->conv1_shared && fpw == 8 && F % 16 == 0) C1S(16);
-        else if (h->conv1_shared && fpw == 8) C1S(8);
+        if (h->k.conv1_shared && fpw == 8 && F % 16 == 0) C1S(16);
+        else if (h->k.conv1_shared && fpw == 8) C1S(8);
         else if (fpw == 8) C1R(8); else if (fpw == 4) C1R(4); else if (fpw == 2) C1R(2); else C1R(1);
 #undef C1S
 #undef C1R
@@ -1527,9 +1431,9 @@ static int ref_pass(dne_handle *h, int n) {
         const bool mc_fc = F == 16 || F == 32 || F == 64 || F == 128;   // fc on the matrix cores: y2 rows padded to 128 positions
         if (mc_fc)   // 16 frames per workgroup (32 / 64 measured the same: 11.46 / 11.42 / 11.50 ms per 5000 members)
             hipLaunchKernelGGL((k_conv2_ref<16, true>), dim3(nc * (F / 16)), dim3(256), 0, st, A, F, m0, (const float *)y1, y2, fr2);
-        else if (F % 8 == 0 && h->conv2_ref_fpw == 8)
+        else if (F % 8 == 0 && h->k.conv2_ref_fpw == 8)
             hipLaunchKernelGGL((k_conv2_ref<8, false>), dim3(nc * (F / 8)), dim3(256), 0, st, A, F, m0, (const float *)y1, y2, fr2);
-        else if (F % 4 == 0 && h->conv2_ref_fpw >= 4)
+        else if (F % 4 == 0 && h->k.conv2_ref_fpw >= 4)
             hipLaunchKernelGGL((k_conv2_ref<4, false>), dim3(nc * (F / 4)), dim3(256), 0, st, A, F, m0, (const float *)y1, y2, fr2);
         else
             hipLaunchKernelGGL((k_conv2<true>), dim3(nc * F), dim3(256), 0, st, A, (const int *)nullptr, 1, F, m0,
@@ -1628,146 +1532,133 @@ extern "C" int dne_get_bn_moments(dne_handle *h, int n, float *out) {
     return 0;
 }
 
-// one policy decision for the groups in `list` (count groups of gsize members)
-// (p, tt: the burst's plan and tail table inside an evaluation; the empty plan and no table everywhere else)
-static void launch_forward(dne_handle *h, const StepPlan &p, const TailTable *tt, const int *list, int count, int gsize, bool use_done,
+// one policy decision for the groups in `list` (w.cnt groups of gsize members)
+// (p, w, tt: the burst's plan, the window's and the tail table inside an evaluation; the empty plan and no table everywhere else)
+static void launch_forward(dne_handle *h, const StepPlan &p, const WindowPlan &w, const TailTable *tt, const int *list, int gsize, bool use_done,
                            hipStream_t st = nullptr) {
     if (!st) st = h->stream;
     const FwdArgs A = h->fwd(use_done, p, tt);
-    if (h->large) {   // LargeModel: three matrix-core convolutions (forward_large.h); members are single (GA)
+    const int count = w.cnt, items = count * gsize;
+    const bool es = es_like(h->L.kind);
+    float *y1 = use_done ? nullptr : h->y1;   // the fused kernels: dne_act / debug_activations want y1; evaluations do not
+    switch (w.conv) {
+    case DNE_CONV_LARGE: {   // LargeModel: three matrix-core convolutions (forward_large.h); members are single (GA)
         constexpr size_t l2 = lconv_mfma_lds_bytes<32, 4, 2, 11, 34>(), l3 = lconv_mfma_lds_bytes<64, 3, 1, 11, 68>();
         hipLaunchKernelGGL(k_lconv1, dim3(count * 2), dim3(256), 0, st, A, list, (const uint8_t *)h->stacks, h->y1);
-        const int ns = count <= 128 ? 4 : count <= 256 ? 2 : 1;   // few members: one workgroup per 16-channel tile
+        const int ns = w.s2;
         with_bool(!h->members_materialized, [&](auto NOISE) {
             hipLaunchKernelGGL((k_lconv_mfma<32, 64, 4, 2, 21, 11, 1, 34, NOISE()>), dim3(count * ns), dim3(256), l2, st, A, list, A.L.c2w, A.L.c2b, (const float *)h->y1, h->y2, ns);
             hipLaunchKernelGGL((k_lconv_mfma<64, 64, 3, 1, 11, 11, 1, 68, NOISE()>), dim3(count * ns), dim3(256), l3, st, A, list, A.L.c3w, A.L.c3b, (const float *)h->y2, h->y3, ns);
         });
         return;
     }
-    const bool es = es_like(h->L.kind);
-    const bool act2 = p.ring && count > h->fc_tail_max;   // the window's fc is k_fc_ring: leave relu(bn2(y2)) instead of y2 (ES pairs only)
-    const int items = count * gsize;
-    // few members left: several workgroups per member (conv1: 28 position tiles over 4 or 7 workgroups; conv2: 8 over 2 or 4)
-    const int s1 = items <= h->conv_split_max ? 7 : items <= h->conv_split_mid ? 4 : 1, s2 = items <= h->conv_split_max ? 4 : items <= 2 * h->conv_split_mid ? 2 : 1;
-    if (h->conv_fused && items >= h->conv_fused_min && !h->dbg_skip) {   // one workgroup per member through both convolutions, y1 stays in LDS
-        float *y1 = use_done ? nullptr : h->y1;                           // dne_act / debug_activations want y1; evaluations do not
-        with_bool(es, [&](auto ES) { hipLaunchKernelGGL((k_conv12<ES()>), dim3(items), dim3(256), sizeof(Conv12Lds), st, A, list, gsize, (const uint8_t *)h->stacks, y1, h->y2, act2 ? 1 : 0); });
+    case DNE_CONV_FUSED:   // one workgroup per member through both convolutions, y1 stays in LDS
+        with_bool(es, [&](auto ES) { hipLaunchKernelGGL((k_conv12<ES()>), dim3(items), dim3(256), sizeof(Conv12Lds), st, A, list, gsize, (const uint8_t *)h->stacks, y1, h->y2, w.act2 ? 1 : 0); });
         return;
-    }
-    if (items <= h->conv12t_max && !h->dbg_skip) {   // the tail: four workgroups per member through both convolutions, no y1 round trip
-        float *y1 = use_done ? nullptr : h->y1;
+    case DNE_CONV_TAIL4:   // the tail: four workgroups per member through both convolutions, no y1 round trip
         with_bool(es, [&](auto ES) { hipLaunchKernelGGL((k_conv12t<ES()>), dim3(items * 4), dim3(512), sizeof(Conv12Lds), st, A, list, gsize, (const uint8_t *)h->stacks, y1, h->y2); });
-        if (act2) hipLaunchKernelGGL(k_y2_activate, dim3(items), dim3(256), 0, st, A, list, gsize, h->y2);
-        return;
+        break;
+    default:
+        if (!(w.skip & 1))
+            hipLaunchKernelGGL(k_conv1, dim3(items * w.s1), dim3(256), 0, st, A, list, gsize, 1, 0,
+                               (const uint8_t *)h->stacks, (const uint8_t *)nullptr, h->y1, w.s1);
+        if (w.skip & 2) return;
+        with_bool(es, [&](auto ES) { hipLaunchKernelGGL((k_conv2<ES()>), dim3(items * w.s2), dim3(256), 0, st, A, list, gsize, 1, 0, (const float *)h->y1, h->y2, w.s2, (float *)nullptr); });
     }
-    if (!(h->dbg_skip & 1))
-    hipLaunchKernelGGL(k_conv1, dim3(items * s1), dim3(256), 0, st, A, list, gsize, 1, 0,
-                       (const uint8_t *)h->stacks, (const uint8_t *)nullptr, h->y1, s1);
-    if (h->dbg_skip & 2) return;
-    with_bool(es, [&](auto ES) { hipLaunchKernelGGL((k_conv2<ES()>), dim3(items * s2), dim3(256), 0, st, A, list, gsize, 1, 0, (const float *)h->y1, h->y2, s2, (float *)nullptr); });
-    if (act2) hipLaunchKernelGGL(k_y2_activate, dim3(items), dim3(256), 0, st, A, list, gsize, h->y2);
+    if (w.act2) hipLaunchKernelGGL(k_y2_activate, dim3(items), dim3(256), 0, st, A, list, gsize, h->y2);
 }
 
-// the kernel launch_fc picks for a window of `count` groups (messages only)
-static const char *fc_name(const dne_handle *h, const StepPlan &p, int count) {
-    if (h->large) return count <= h->lfc_cols_max ? "k_lfc_cols" : "k_lfc";
-    if (p.sub) return "k_fc_sub";
-    if (count <= h->fc_tail_max) return "tail";
-    if (p.duo) return p.ring ? "k_fc_ring" : "k_fc_duo";
-    return p.fc2 ? "k_fc2" : "k_fc";
-}
-
-static void launch_fc(dne_handle *h, const StepPlan &p, const TailTable *tt, const int *list, int count, int gsize, float *logits,
-                      hipStream_t st = nullptr, bool out_fused = false /* the caller runs k_tail_step instead of k_out */,
+// the window's fc (w.fc) and, unless the caller runs k_tail_step behind it (w.head_fused), the output layer
+static void launch_fc(dne_handle *h, const StepPlan &p, const WindowPlan &w, const TailTable *tt, const int *list, int gsize, float *logits,
+                      hipStream_t st = nullptr,
                       const int *order = nullptr /* the window's units in noise-table order (k_unit_order), duo regime only */,
                       hipEvent_t after_stream_kernel = nullptr /* duo regime: recorded between k_fc_duo and k_out (profiling) */) {
     if (!st) st = h->stream;
     // inside an evaluation (no logits requested) groups whose members are all done are skipped: they stay in the list until
     // the next compaction, and streaming their weights would be wasted bandwidth
     const FwdArgs A = h->fwd(logits == nullptr, p, tt);
-    const bool es = es_like(h->L.kind);
-    if (h->large) {   // LargeModel: streamed 7744 x 512 fc (two 256-column halves per member), then relu + output layer + argmax
-        const dim3 lg(std::min(2 * count, 2 * h->fc_grid));
-        if (count <= h->lfc_cols_max) {   // few members: eight workgroups each
+    const Knobs &k = h->k;
+    const bool es = es_like(h->L.kind), out_fused = w.head_fused;
+    const int count = w.cnt;
+    switch (w.fc) {
+    case DNE_FC_LFC_COLS: case DNE_FC_LFC: {   // LargeModel: streamed 7744 x 512 fc (two 256-column halves per member), then relu + output layer + argmax
+        const dim3 lg(std::min(2 * count, 2 * k.fc_grid));
+        if (w.fc == DNE_FC_LFC_COLS) {   // few members: eight workgroups each
             with_bool(!h->members_materialized, [&](auto NOISE) { hipLaunchKernelGGL((k_lfc_cols<NOISE()>), dim3(8 * count), dim3(256), 0, st, A, list, (const float *)h->y3, h->y3t); });
         } else if (h->members_materialized) {
-            if (h->fc_rb == 8 && h->lfc_pad == 1) hipLaunchKernelGGL((k_lfc<false, 8, 1>), lg, dim3(256), 0, st, A, list, 2 * count, (const float *)h->y3, h->y3t);
-            else if (h->fc_rb == 8 && h->lfc_pad == 2) hipLaunchKernelGGL((k_lfc<false, 8, 2>), lg, dim3(256), 0, st, A, list, 2 * count, (const float *)h->y3, h->y3t);
-            else if (h->fc_rb == 8) hipLaunchKernelGGL((k_lfc<false, 8>), lg, dim3(256), 0, st, A, list, 2 * count, (const float *)h->y3, h->y3t);
+            if (k.fc_rb == 8 && k.lfc_pad == 1) hipLaunchKernelGGL((k_lfc<false, 8, 1>), lg, dim3(256), 0, st, A, list, 2 * count, (const float *)h->y3, h->y3t);
+            else if (k.fc_rb == 8 && k.lfc_pad == 2) hipLaunchKernelGGL((k_lfc<false, 8, 2>), lg, dim3(256), 0, st, A, list, 2 * count, (const float *)h->y3, h->y3t);
+            else if (k.fc_rb == 8) hipLaunchKernelGGL((k_lfc<false, 8>), lg, dim3(256), 0, st, A, list, 2 * count, (const float *)h->y3, h->y3t);
             else hipLaunchKernelGGL((k_lfc<false, 4>), lg, dim3(256), 0, st, A, list, 2 * count, (const float *)h->y3, h->y3t);
         } else hipLaunchKernelGGL((k_lfc<true, 4>), lg, dim3(256), 0, st, A, list, 2 * count, (const float *)h->y3, h->y3t);
         hipLaunchKernelGGL(k_lout, dim3(count), dim3(256), 0, st, A, list, (const float *)h->y3t, h->action, logits);
         return;
     }
-    if (p.sub) {   // mid range: one wave per sub-slice chain, folded by the head
-        const int total_waves_at_1 = 32 * count;
-        // sub-slices per wave: about 8000 waves (one round of the whole machine) whatever the width
-        const int spw = h->fc_sub_spw ? h->fc_sub_spw : count * h->fc_sub_nsub <= 320 ? 1 : count * h->fc_sub_nsub <= 640 ? 2 : count * h->fc_sub_nsub <= 1280 ? 4 : 8;
-        const int waves = total_waves_at_1 / spw, blocks = std::min((waves + 3) / 4, h->fc_sub_grid);
-        // plan_step admits exactly two populations: ES pairs and GA children written out
+    case DNE_FC_SUB:   // mid range: one wave per sub-slice chain, folded by the head.  plan_step admits exactly two populations: ES pairs and GA children written out
         with_bool(es, [&](auto ES) {
             constexpr int NV = ES() ? 2 : 1;
-            hipLaunchKernelGGL((k_fc_sub<NV, ES(), ES()>), dim3(blocks), dim3(256), 0, st, A, list, count, spw, h->fc_sub_prio, (const float *)h->y2, h->y3s);
+            hipLaunchKernelGGL((k_fc_sub<NV, ES(), ES()>), dim3(w.sub_blocks), dim3(256), 0, st, A, list, count, w.sub_spw, k.fc_sub_prio, (const float *)h->y2, h->y3s);
             if (out_fused) return;   // the caller runs k_tail_step (FwdArgs::sub_sums tells it to fold the chain sums)
             hipLaunchKernelGGL((k_out<NV, ES()>), dim3(count), dim3(256), 0, st, A, list, (const float *)h->y3s, h->y3, h->action, (float *)nullptr);
         });
         return;
-    }
-    if (count <= h->fc_tail_max) {   // latency-bound regime: 4 workgroups per group + a separate output-layer kernel
+    case DNE_FC_QUAD: case DNE_FC_TAIL: case DNE_FC_COLS:   // latency-bound regime: 64 / 16 / 4 workgroups per group + a separate output-layer kernel
         with_bool(gsize == 2, [&](auto PAIRS) { with_bool(es, [&](auto ES) {
             constexpr int NV = PAIRS() ? 2 : 1;
             constexpr bool BN = ES();
             if (NV == 1 && !BN && h->members_materialized) {   // GA children written out: plain rows, no noise stream
-                if (count <= h->fc_quad_max) hipLaunchKernelGGL((k_fc_quad<1, false, false>), dim3(count * 64), dim3(256), 0, st, A, list, (const float *)h->y2, h->y3t);
+                if (w.fc == DNE_FC_QUAD) hipLaunchKernelGGL((k_fc_quad<1, false, false>), dim3(count * 64), dim3(256), 0, st, A, list, (const float *)h->y2, h->y3t);
                 else hipLaunchKernelGGL((k_fc_tail<1, false, false>), dim3(count * 16), dim3(512), 0, st, A, list, (const float *)h->y2, h->y3t);
-            } else if (count <= h->fc_quad_max) hipLaunchKernelGGL((k_fc_quad<NV, BN>), dim3(count * 64), dim3(256), 0, st, A, list, (const float *)h->y2, h->y3t);
-            else if (count <= h->fc_tailk_max) hipLaunchKernelGGL((k_fc_tail<NV, BN>), dim3(count * 16), dim3(512), 0, st, A, list, (const float *)h->y2, h->y3t);
+            } else if (w.fc == DNE_FC_QUAD) hipLaunchKernelGGL((k_fc_quad<NV, BN>), dim3(count * 64), dim3(256), 0, st, A, list, (const float *)h->y2, h->y3t);
+            else if (w.fc == DNE_FC_TAIL) hipLaunchKernelGGL((k_fc_tail<NV, BN>), dim3(count * 16), dim3(512), 0, st, A, list, (const float *)h->y2, h->y3t);
             else hipLaunchKernelGGL((k_fc_cols<NV, BN>), dim3(count * 4), dim3(256), 0, st, A, list, (const float *)h->y2, h->y3t);
             if (!out_fused) hipLaunchKernelGGL((k_out<NV, BN>), dim3(count), dim3(256), 0, st, A, list, (const float *)h->y3t, h->y3, h->action, logits);
         }); });
         return;
-    }
-    if (p.duo) {   // table-ordered units: adjacent (pair, k-slice) units share their noise rows (ES pairs only: plan_step)
-        const bool solo = p.duo_solo;
-        const bool sweep = h->duo_sweep && (!solo || h->duo_sweep > 1);
-        const int duo_grid = h->duo_grid ? h->duo_grid : h->fc_grid;
+    case DNE_FC_RING: case DNE_FC_DUO: {   // table-ordered units: adjacent (pair, k-slice) units share their noise rows (ES pairs only: plan_step)
+        const bool solo = w.solo;
+        const int duo_grid = k.duo_grid ? k.duo_grid : k.fc_grid;
         const int n_units = 4 * count, items = ((solo ? n_units : (n_units + 1) / 2) + 3) / 4, blocks = std::min(items, duo_grid);
-        const size_t out_lds = (size_t)h->out_lds_kb * 1024;   // an LDS reservation nobody uses: it only bounds k_out's workgroups per CU next to the streaming fc
-        const int flags = h->duo_lag | (solo ? 256 : 0) | (h->fc_prio << 9) | ((h->duo_sync - 1) << 11);
-        if (p.ring) {   // one unit per wave, eight units per workgroup whatever the regime
+        const size_t out_lds = (size_t)k.out_lds_kb * 1024;   // an LDS reservation nobody uses: it only bounds k_out's workgroups per CU next to the streaming fc
+        const int flags = k.duo_lag | (solo ? 256 : 0) | (k.fc_prio << 9) | ((k.duo_sync - 1) << 11);
+        if (w.fc == DNE_FC_RING) {   // one unit per wave, eight units per workgroup whatever the regime
             const int ring_blocks = std::min((n_units + 7) / 8, duo_grid);
-            const float *table = p.ring_scaled ? h->noise_pre : A.noise;
-            with_bool(p.ring_scaled, [&](auto PRE) { hipLaunchKernelGGL((k_fc_ring<PRE(), 8>), dim3(ring_blocks), dim3(576), 0, st, A, order, n_units, (const float *)h->y2, h->y3t, (const float *)h->theta_perm, h->fc_prio << 9, table); });
+            const float *table = w.ring_scaled ? h->noise_pre : A.noise;
+            with_bool(w.ring_scaled, [&](auto PRE) { hipLaunchKernelGGL((k_fc_ring<PRE(), 8>), dim3(ring_blocks), dim3(576), 0, st, A, order, n_units, (const float *)h->y2, h->y3t, (const float *)h->theta_perm, k.fc_prio << 9, table); });
         }
-        else if (sweep && h->duo_fat) hipLaunchKernelGGL((k_fc_duo<2, true, true, 8, true>), dim3(blocks), dim3(256), 0, st, A, order, n_units, (const float *)h->y2, h->y3t, flags);
-        else if (sweep) hipLaunchKernelGGL((k_fc_duo<2, true, true>), dim3(blocks), dim3(256), 0, st, A, order, n_units, (const float *)h->y2, h->y3t, flags);
+        else if (w.sweep && w.fat) hipLaunchKernelGGL((k_fc_duo<2, true, true, 8, true>), dim3(blocks), dim3(256), 0, st, A, order, n_units, (const float *)h->y2, h->y3t, flags);
+        else if (w.sweep) hipLaunchKernelGGL((k_fc_duo<2, true, true>), dim3(blocks), dim3(256), 0, st, A, order, n_units, (const float *)h->y2, h->y3t, flags);
         else hipLaunchKernelGGL((k_fc_duo<2, true>), dim3(blocks), dim3(256), 0, st, A, order, n_units, (const float *)h->y2, h->y3t, flags);
         if (after_stream_kernel) hipEventRecord(after_stream_kernel, st);
         if (out_fused) return;   // the caller runs k_tail_step: policy head + emulator step in one launch
         hipLaunchKernelGGL((k_out<2, true>), dim3(count), dim3(256), out_lds, st, A, list, (const float *)h->y3t, h->y3, h->action, (float *)nullptr);
         return;
     }
-    if (p.fc2) {   // two pairs per work item share the base rows (ES pairs over one base slot only: plan_step)
-        const int items = (count + 1) / 2, blocks = std::min(items, h->fc_grid);
-        with_bool(h->fc_rb == 2, [&](auto RB2) { hipLaunchKernelGGL((k_fc2<true, RB2() ? 2 : 4>), dim3(blocks), dim3(256), 0, st, A, list, count, (const float *)h->y2, h->y3, h->action); });
+    case DNE_FC_FC2: {   // two pairs per work item share the base rows (ES pairs over one base slot only: plan_step)
+        const int items = (count + 1) / 2, blocks = std::min(items, k.fc_grid);
+        with_bool(k.fc_rb == 2, [&](auto RB2) { hipLaunchKernelGGL((k_fc2<true, RB2() ? 2 : 4>), dim3(blocks), dim3(256), 0, st, A, list, count, (const float *)h->y2, h->y3, h->action); });
         return;
     }
-    const int fc_blocks = std::min(count, h->fc_grid);   // persistent grid (an even groups-per-block split measured slower)
-    if (gsize == 1 && !es && h->members_materialized) {   // GA children written out once per generation: plain rows, no noise stream
-        with_bool(h->fc_rb == 8, [&](auto RB8) { hipLaunchKernelGGL((k_fc<1, false, false, RB8() ? 8 : 4, false>), dim3(fc_blocks), dim3(256), 0, st, A, list, count, 1, 0, (const float *)h->y2, h->y3, h->action, logits); });
-        return;
+    default: {   // DNE_FC_FC
+        const int fc_blocks = std::min(count, k.fc_grid);   // persistent grid (an even groups-per-block split measured slower)
+        if (gsize == 1 && !es && h->members_materialized) {   // GA children written out once per generation: plain rows, no noise stream
+            with_bool(k.fc_rb == 8, [&](auto RB8) { hipLaunchKernelGGL((k_fc<1, false, false, RB8() ? 8 : 4, false>), dim3(fc_blocks), dim3(256), 0, st, A, list, count, 1, 0, (const float *)h->y2, h->y3, h->action, logits); });
+            return;
+        }
+        with_bool(gsize == 2, [&](auto PAIRS) { with_bool(es, [&](auto ES) {
+            auto fc = [&](auto RB) { hipLaunchKernelGGL((k_fc<PAIRS() ? 2 : 1, false, ES(), RB()>), dim3(fc_blocks), dim3(256), 0, st, A, list, count, 1, 0, (const float *)h->y2, h->y3, h->action, logits); };
+            if (k.fc_rb == 2) fc(int_c<2>{}); else if (k.fc_rb == 8) fc(int_c<8>{}); else fc(int_c<4>{});
+        }); });
     }
-    with_bool(gsize == 2, [&](auto PAIRS) { with_bool(es, [&](auto ES) {
-        auto fc = [&](auto RB) { hipLaunchKernelGGL((k_fc<PAIRS() ? 2 : 1, false, ES(), RB()>), dim3(fc_blocks), dim3(256), 0, st, A, list, count, 1, 0, (const float *)h->y2, h->y3, h->action, logits); };
-        if (h->fc_rb == 2) fc(int_c<2>{}); else if (h->fc_rb == 8) fc(int_c<8>{}); else fc(int_c<4>{});
-    }); });
+    }
 }
 
 extern "C" int dne_act(dne_handle *h, int n, int32_t *actions, float *logits) {
     DeviceGuard dg(h);
     if (check_n(h, n)) return -1;
-    launch_forward(h, StepPlan{}, nullptr, nullptr, n, 1, false);
-    launch_fc(h, StepPlan{}, nullptr, nullptr, n, 1, h->logits);
+    const WindowPlan w = plan_window(h->k, h->facts(), StepPlan{}, n, n, 1, false);
+    launch_forward(h, StepPlan{}, w, nullptr, nullptr, 1, false);
+    launch_fc(h, StepPlan{}, w, nullptr, nullptr, 1, h->logits);
     HCHECK(h, hipGetLastError());
     HCHECK(h, hipStreamSynchronize(h->stream));
     if (actions) HCHECK(h, hipMemcpy(actions, h->action, n * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -1800,44 +1691,10 @@ extern "C" int dne_debug_activations_large(dne_handle *h, int member, float *y1,
 }
 
 // ------------------------------------------------------------------------------- batch evaluation
-// The regime of a burst that starts with `total` active groups of `gsize` members.  One global list of active groups, compacted every burst; within a burst
-// the list is cut into nsub equal windows, each stepped on its own stream, so that while one window streams its noise slices (HBM) the others run their MFMA
-// convolutions and emulator frames.  whole_eval: the same conditions classify an evaluation by the width it STARTS with (which launches carry profiling
-// events, dne_profile.fc_full_kind); the two terms that differ between the two uses are marked.
-static StepPlan plan_step(const dne_handle *h, int total, int gsize, bool whole_eval = false) {
-    const bool es = es_like(h->L.kind), pairs = es && gsize == 2;
-    StepPlan p;
-    // the sub-slice fc's range: GA children written out (plain rows), optionally ES pairs (DNE_FC_SUB=2); never the LargeModel
-    if (!h->large && h->y3s && total >= h->fc_sub_min && total <= h->fc_sub_max)
-        p.sub = es ? h->fc_sub >= 2 && gsize == 2 && total < h->fc_duo_min : h->fc_sub >= 1 && gsize == 1 && h->members_materialized;
-    // nsub follows the active count (tools/kbench.py sweeps): k_fc2 wants 3 windows at full width and 4 in the upper mid range; below
-    // ~400 groups the windows are sized to fit the column-split tail kernels (<= fc_tail_max groups each); one when only a handful of episodes are left
-    int k = total >= 1900 ? h->nsub_full : total >= h->fc2_min_total ? h->nsub_mid : total > 4 * h->fc_tail_max ? 3
-          : total >= 48 ? std::max(2, (total + h->fc_tail_max - 1) / h->fc_tail_max) : 1;
-    if (p.sub) k = h->fc_sub_nsub;
-    if (h->nsub_fixed > 0) k = h->nsub_fixed;
-    k = std::min(k, (int)h->sub_streams.size());
-    p.nsub = std::max(1, std::min(k, total));
-    // a burst inside the sub-slice fc's range runs no k_fc2; an evaluation that starts there with k_fc2 enabled at that width
-    // (DNE_FC2_MIN lowered into the range) still counts as a k_fc2 evaluation, whose profiled launches are the k_fc2 ones
-    p.fc2 = h->fc_pairs == 2 && pairs && h->uniform_base && total >= h->fc2_min_total && (whole_eval || !p.sub);
-    // table-ordered units (never inside the sub-slice fc's range, which ends below fc_duo_min).  k_unit_order ranks a window's keys
-    // in LDS: a burst whose windows are too long for it falls back to k_fc2 / k_fc; the evaluation's kind ignores that bound
-    const bool order_fits = (size_t)4 * ((total + p.nsub - 1) / p.nsub) * sizeof(long long) <= 160 * 1024;
-    p.duo = !h->large && h->fc_duo && pairs && total >= h->fc_duo_min && (whole_eval || order_fits);
-    p.duo_solo = total < h->duo_solo_below;
-    // the ring's range: pairs as dense in their stretch of the table as DNE_DUO_SOLO_BELOW (1500) pairs over the whole table, and enough of them to
-    // fill the chip (DNE_RING_MIN) -- at one GPU "1500 of 2500 active", on a rank of two with its own half of the table "1000 of 1250"
-    const bool dense = (double)total * h->dense_scale >= (double)h->duo_solo_below && total >= h->ring_min;
-    p.ring = p.duo && h->theta_perm && h->antithetic_slot0 && h->duo_sweep && (h->ring_on > 1 || dense) && (dense || h->duo_sweep > 1);
-    p.ring_scaled = p.ring && h->ring_pre && h->pair_sigma_uniform && h->noise_pre;   // (ring_scaled_table has filled it: the evaluation started at least as wide)
-    return p;
-}
-
 // tail table: with at most TT_MAX members left, all in one window, the member descriptors ride in the kernel arguments.
 // Fills *tt from the active groups in list order (host_list null = 0, 1, 2, ...) and returns it, or null when no table is in force.
 static const TailTable *make_tail_table(const dne_handle *h, TailTable *tt, const int *host_list, int total, int gsize, int n) {
-    if (!h->tt_enable || h->large || total * gsize > TT_MAX || (int)h->host_off.size() < n || plan_step(h, total, gsize).nsub != 1) return nullptr;
+    if (!tail_table_allowed(h->k, h->facts(), total, gsize) || total * gsize > TT_MAX || (int)h->host_off.size() < n) return nullptr;
     tt->n = total * gsize;
     for (int i = 0; i < total; i++)
         for (int v = 0; v < gsize; v++) {
@@ -1849,10 +1706,10 @@ static const TailTable *make_tail_table(const dne_handle *h, TailTable *tt, cons
 
 // the ring's DMA source: the table scaled by this evaluation's sigma (k_fc_ring<true>), made once per (table, sigma)
 static int ring_scaled_table(dne_handle *h) {
-    if (!h->ring_pre || !h->pair_sigma_uniform) return 0;
+    if (!h->k.ring_pre || !h->pair_sigma_uniform || h->noise_pre_no_room) return 0;
     if (!h->noise_pre && h->alloc(&h->noise_pre, h->noise_count + OVERFETCH_FLOATS, "noise_pre")) {
         h->trace("no room for the scaled table: the ring scales its rows itself");
-        (void)hipGetLastError(); h->noise_pre = nullptr; h->ring_pre = 0;
+        (void)hipGetLastError(); h->noise_pre = nullptr; h->noise_pre_no_room = true;
         return 0;
     }
     if (h->noise_pre_count != h->noise_count || h->noise_pre_sigma != h->pair_sigma) {
@@ -1869,7 +1726,7 @@ static int ring_scaled_table(dne_handle *h) {
 // speculative tail: the emulator + renderer outcome of every action, inside the launches of this step's forward pass
 // fresh: no conv1 candidates from the previous lock-step (a new burst = a new list); next_conv1: the choice + conv1 of every candidate (not in a burst's last lock-step)
 static void launch_spec_tail(dne_handle *h, const StepPlan &p, const TailTable *tt, const EnvArgs &E, const int *lst, int cnt, int gsize, int tslimit, hipStream_t sst, bool fresh, bool next_conv1) {
-    const int items = cnt * gsize, nact = h->cfg.n_actions, nb = h->spec_bands;
+    const int items = cnt * gsize, nact = h->cfg.n_actions, nb = h->k.spec_bands;
     const FwdArgs A = h->fwd(true, p, tt);
     const int emu_blocks = (items * nact + 255) / 256;
     with_bool(es_like(h->L.kind), [&](auto ES) {
@@ -1883,19 +1740,16 @@ static void launch_spec_tail(dne_handle *h, const StepPlan &p, const TailTable *
     });
 }
 
-// behind an fc that left partial sums (launch_fc with out_fused): policy head + emulator step in one launch (k_tail_step), and the frames.
-// tail: few members left -- each frame over nb workgroups, or (nb = 1) rendered by that same launch; else behind k_fc_duo / k_fc_sub
-static void launch_head_step(dne_handle *h, const StepPlan &p, const TailTable *tt, const EnvArgs &E, const int *lst, int cnt, int gsize, int tslimit, hipStream_t sst, bool tail) {
+// behind an fc that left partial sums (w.head_fused): policy head + emulator step in one launch (k_tail_step), and the frames.
+// w.tail: few members left -- each frame over w.render_bands workgroups, or (one band) rendered by that same launch; else behind k_fc_duo / k_fc_sub
+static void launch_head_step(dne_handle *h, const StepPlan &p, const WindowPlan &w, const TailTable *tt, const EnvArgs &E, const int *lst, int gsize, int tslimit, hipStream_t sst) {
     const FwdArgs A = h->fwd(false, p, tt);
-    const int items = cnt * gsize;
+    const int items = w.cnt * gsize, nb = w.render_bands;
     const float *sums = p.sub ? h->y3s : h->y3t;
-    int nb = tail ? h->render_bands : 1;
-    while (nb > 1 && items * nb > h->render_wg_max) nb /= 2;
-    const bool render_fused = tail ? nb == 1 : h->sub_render_fused && p.sub && !(h->dbg_skip & 4);   // head + emulator + renderer in one launch
-    with_bool(es_like(h->L.kind), [&](auto ES) { with_bool(render_fused, [&](auto R) { hipLaunchKernelGGL((k_tail_step<ES(), R()>), dim3(items), dim3(R() ? 1024 : h->head_threads), 0, sst, A, E, lst, gsize, tslimit, sums, h->y3, h->action); }); });
-    if (render_fused) return;
-    if (tail) hipLaunchKernelGGL(k_env_render, dim3(items * nb), dim3(h->band_threads), 0, sst, E, lst, gsize, 0, nb);
-    else if (!(h->dbg_skip & 4)) hipLaunchKernelGGL(k_env_render, dim3(items), dim3(items <= 192 ? 1024 : h->render_threads), 0, sst, E, lst, gsize, 0, 1);
+    with_bool(es_like(h->L.kind), [&](auto ES) { with_bool(w.render_fused, [&](auto R) { hipLaunchKernelGGL((k_tail_step<ES(), R()>), dim3(items), dim3(R() ? 1024 : h->k.head_threads), 0, sst, A, E, lst, gsize, tslimit, sums, h->y3, h->action); }); });
+    if (w.render_fused) return;   // head + emulator + renderer in one launch
+    if (w.tail) hipLaunchKernelGGL(k_env_render, dim3(items * nb), dim3(w.render_wg), 0, sst, E, lst, gsize, 0, nb);
+    else if (!(w.skip & 4)) hipLaunchKernelGGL(k_env_render, dim3(items), dim3(w.render_wg), 0, sst, E, lst, gsize, 0, 1);
 }
 
 // profiling engines: one step counter per bracketed launch set, zeroed
@@ -1982,59 +1836,53 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
     if (prof && reserve_launch_units(h, tslimit)) return -1;
     hipEvent_t last_fc = nullptr;
     size_t fc_ring_pos = 0;
-    // the evaluation as a whole, by the width it starts with: its profiled ("full") launches are one kernel, one roofline line -- k_fc_ring's if it starts in
-    // the ring's range (the k_fc_duo launches of its thinner lock-steps are not bracketed then), else k_fc_duo's, else k_fc2's, else every window above fc_tail_max groups
-    const StepPlan ev = plan_step(h, groups, gsize, true);
+    // the evaluation as a whole, by the width it starts with: its profiled ("full") launches are one kernel, one roofline line (plan.h: window_profiled)
+    const StepPlan ev = plan_step(h->k, h->facts(), groups, gsize, true);
     if (ev.ring && ring_scaled_table(h)) return -1;
+    const PlanFacts facts = h->facts();   // (behind ring_scaled_table: nothing changes them before the evaluation ends)
     while (total > 0 && t < tslimit) {
-        const int burst = std::min(total <= h->fc_tail_max ? h->burst_tail : h->burst, tslimit - t);   // lock-steps until the next compaction
-        const StepPlan p = plan_step(h, total, gsize);
+        const int burst = std::min(burst_length(h->k, total), tslimit - t);   // lock-steps until the next compaction
+        const StepPlan p = plan_step(h->k, facts, total, gsize);
         const int nsub = p.nsub;   // windows of this burst
-        if (p.duo)   // the list only changes at a compaction: rank each window's units by table address once per burst
-            for (int s = 0; s < nsub; s++) {
-                const int lo = (int)((long long)total * s / nsub), cnt = (int)((long long)total * (s + 1) / nsub) - lo;
-                if (cnt <= h->fc_tail_max) continue;
-                hipLaunchKernelGGL(k_unit_order, dim3((4 * cnt + 255) / 256), dim3(256), (size_t)4 * cnt * sizeof(long long), h->sub_streams[s],
-                                   (const int64_t *)h->m_off, (const int *)(cur + lo), cnt, gsize, h->unit_order + 4 * lo);
-            }
+        std::array<WindowPlan, N_STREAMS> win;
+        for (int s = 0; s < nsub; s++) {
+            const Window c = window(total, nsub, s);
+            win[s] = plan_window(h->k, facts, p, total, c.cnt, gsize, true);
+            win[s].lo = c.lo;
+            if (is_duo(win[s]))   // the list only changes at a compaction: rank each window's units by table address once per burst
+                hipLaunchKernelGGL(k_unit_order, dim3((4 * c.cnt + 255) / 256), dim3(256), (size_t)4 * c.cnt * sizeof(long long), h->sub_streams[s],
+                                   (const int64_t *)h->m_off, (const int *)(cur + c.lo), c.cnt, gsize, h->unit_order + 4 * c.lo);
+        }
         for (int st = 0; st < burst; st++) {
             for (int s = 0; s < nsub; s++) {
-                const int lo = (int)((long long)total * s / nsub), cnt = (int)((long long)total * (s + 1) / nsub) - lo;
+                const WindowPlan &w = win[s];
+                const int lo = w.lo, cnt = w.cnt;
                 if (cnt == 0) continue;
                 hipStream_t sst = h->sub_streams[s];
                 const int *lst = cur + lo;
                 std::array<size_t, 4> e{};
-                // events only around full-width launches: in the latency-bound tail every event packet is a bubble
-                const bool duo_win = p.duo && cnt > h->fc_tail_max;
-                const bool pe = prof && (ev.ring ? duo_win && p.ring : ev.duo ? duo_win : ev.fc2 ? p.fc2 : cnt > h->fc_tail_max);
+                const bool pe = prof && window_profiled(ev, p, w);   // events only around full-width launches
                 if (pe) { e[0] = ne++; HCHECK(h, hipEventRecord(h->event(e[0]), sst)); }
-                // fused policy head + emulator (+ render): while all windows together still fit the chip one workgroup per member
-                const bool tail = !h->large && !p.sub && cnt <= h->fc_tail_max && total <= h->tail_fused_max;   // (the fused tail kernels are the small networks')
-                const bool spec = tail && nsub == 1 && h->spec_max > 0 && cnt * gsize <= h->spec_max &&
-                                  cnt * gsize <= h->conv_split_max && !h->dbg_skip;
-                if (spec) launch_spec_tail(h, p, tt, E, lst, cnt, gsize, tslimit, sst, st == 0 || !h->spec_conv1, h->spec_conv1 && st + 1 < burst);
+                if (w.spec) launch_spec_tail(h, p, tt, E, lst, cnt, gsize, tslimit, sst, st == 0 || !h->k.spec_conv1, h->k.spec_conv1 && st + 1 < burst);
                 else {
-                    launch_forward(h, p, tt, lst, cnt, gsize, true, sst);
-                    // optional: serialise the fc kernels of the windows (anti-phase); off by default, free-running measured faster
-                    const bool chain = nsub > 1 && cnt >= h->fc_chain_min;
-                    if (chain && last_fc) HCHECK(h, hipStreamWaitEvent(sst, last_fc, 0));
+                    launch_forward(h, p, w, tt, lst, gsize, true, sst);
+                    if (w.chain && last_fc) HCHECK(h, hipStreamWaitEvent(sst, last_fc, 0));
                     if (pe) { e[1] = ne++; HCHECK(h, hipEventRecord(h->event(e[1]), sst)); }   // after the wait: brackets fc only
                     if (pe) e[2] = ne++;
-                    const bool head_fused = tail || (duo_win && h->duo_head_fused) || (p.sub && h->fc_sub_head);   // the fc leaves partial sums: head + emulator in one launch
-                    launch_fc(h, p, tt, lst, cnt, gsize, nullptr, sst, head_fused, p.duo ? h->unit_order + 4 * lo : nullptr,
-                              pe && duo_win ? h->event(e[2]) : nullptr);   // duo: the bracket ends behind k_fc_duo, before k_out
-                    if (chain) { last_fc = h->fc_ring[fc_ring_pos++ % h->fc_ring.size()]; HCHECK(h, hipEventRecord(last_fc, sst)); }
-                    if (pe && !duo_win) HCHECK(h, hipEventRecord(h->event(e[2]), sst));
+                    launch_fc(h, p, w, tt, lst, gsize, nullptr, sst, is_duo(w) ? h->unit_order + 4 * lo : nullptr,
+                              pe && is_duo(w) ? h->event(e[2]) : nullptr);   // duo: the bracket ends behind k_fc_duo, before k_out
+                    if (w.chain) { last_fc = h->fc_ring[fc_ring_pos++ % h->fc_ring.size()]; HCHECK(h, hipEventRecord(last_fc, sst)); }
+                    if (pe && !is_duo(w)) HCHECK(h, hipEventRecord(h->event(e[2]), sst));
                     E.step_counter = pe ? h->launch_units + evs.size() : nullptr;
-                    if (head_fused) launch_head_step(h, p, tt, E, lst, cnt, gsize, tslimit, sst, tail);
-                    else launch_env_step(h, E, lst, cnt, gsize, tslimit, sst);
+                    if (w.head_fused) launch_head_step(h, p, w, tt, E, lst, gsize, tslimit, sst);
+                    else launch_env_step(h, w, E, lst, gsize, tslimit, sst);
                     if (pe) { e[3] = ne++; HCHECK(h, hipEventRecord(h->event(e[3]), sst)); evs.push_back(e); }
                 }
                 if (h->debug_sync) {
                     hipError_t de = hipStreamSynchronize(sst);
                     if (de == hipSuccess) de = hipGetLastError();
-                    if (de != hipSuccess && spec) return h->fail("lock-step %d (speculative tail, %d active groups): %s", t + st, cnt, hipGetErrorString(de));
-                    if (de != hipSuccess) return h->fail("lock-step %d window %d/%d (%d of %d active groups, %s fc): %s", t + st, s, nsub, cnt, total, fc_name(h, p, cnt), hipGetErrorString(de));
+                    if (de != hipSuccess && w.spec) return h->fail("lock-step %d (speculative tail, %d active groups): %s", t + st, cnt, hipGetErrorString(de));
+                    if (de != hipSuccess) return h->fail("lock-step %d window %d/%d (%d of %d active groups, %s): %s", t + st, s, nsub, cnt, total, fc_name(w.fc), hipGetErrorString(de));
                 }
                 group_steps += cnt;
                 launch_sets++;
@@ -2069,7 +1917,7 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
     P.env_steps = 0;
     for (int i = 0; i < n; i++) P.env_steps += lengths[i];
     P.fc_full_ms = P.fc_full_launches = P.fc_full_units = 0;
-    P.fc_full_kind = ev.ring ? 5 : ev.duo ? 3 : ev.fc2 ? 2 : ev.sub ? 4 : 1;   // (an evaluation that STARTS in the sub-slice fc's range: its bracketed launches are k_fc_sub's)
+    P.fc_full_kind = fc_full_kind(ev);
     P.fc_full_union_ms = 0;
     if (prof && reduce_profile(h, evs)) return -1;
     return 0;
@@ -2330,11 +2178,11 @@ static int ga_eval_impl(dne_handle *h, const int32_t *co, const int64_t *seeds, 
     // are the same in any order; they are handed back in the caller's.
     std::vector<int> order(n);
     for (int i = 0; i < n; i++) order[i] = i;
-    if (h->ga_sort) std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return slot[a] < slot[b]; });
+    if (h->k.ga_sort) std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return slot[a] < slot[b]; });
     std::vector<int32_t> pslot(n); std::vector<int64_t> poff(n); std::vector<float> psc(n); std::vector<uint32_t> pseed(n);
     for (int j = 0; j < n; j++) { const int i = order[j]; pslot[j] = slot[i]; poff[j] = off[i]; psc[j] = sc[i]; pseed[j] = env_seed[i]; }
     h->members_materialized = false;
-    if (h->ga_materialize) {
+    if (h->k.ga_materialize) {
         // Every child's vector written out once (parent + power * noise, the forward kernels' own two roundings): a member-step then
         // reads its rows as they are instead of streaming a parent row and a noise row -- for the LargeModel, whose 20 parents
         // (318 MB) do not fit the Infinity Cache, half the HBM bytes of the fc.  Roots (no mutation) are their own vector already.
@@ -2365,7 +2213,7 @@ static int ga_eval_impl(dne_handle *h, const int32_t *co, const int64_t *seeds, 
         for (int j = 0; j < n; j++) { pslot[j] = cs[j]; psc[j] = 0.0f; }
     }
     if (dne_set_members(h, n, pslot.data(), poff.data(), psc.data())) return -1;
-    h->members_materialized = h->ga_materialize != 0;   // (dne_set_members clears it: a caller's own members carry noise)
+    h->members_materialized = h->k.ga_materialize != 0;   // (dne_set_members clears it: a caller's own members carry noise)
     std::vector<float> pret(n), psg(n); std::vector<int32_t> plen(n); std::vector<uint8_t> pbc(bc ? (size_t)n * 128 : 0);
     if (eval_core(h, n, 1, tslimit, pseed.data(), pret.data(), psg.data(), plen.data(), bc ? pbc.data() : nullptr)) return -1;
     for (int j = 0; j < n; j++) {

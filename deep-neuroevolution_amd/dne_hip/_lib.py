@@ -71,7 +71,7 @@ class Profile(C.Structure):
 
 def build(force=False):
     """Compile libdne_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dne_hip.h"))
     if os.environ.get("DNE_LIB_PATH"):
         # another build of the same ABI was asked for by name: `make` only knows the in-tree library, so running it here would
@@ -103,6 +103,39 @@ def load():
 
 def num_params(kind, nact=18):
     return load().dne_num_params(int(kind), int(nact))
+
+
+class PlanFacts(C.Structure):
+    _fields_ = [("dense_scale", C.c_double)] + \
+               [(n, C.c_int32) for n in ("kind", "members_materialized", "uniform_base", "antithetic_slot0", "pair_sigma_uniform", "n_streams",
+                                         "has_y3s", "has_theta_perm", "has_scaled_table")] + [("reserved", C.c_int32 * 3)]
+
+
+class WindowPlan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("lo", "cnt", "wide", "skip", "conv", "s1", "s2", "act2", "fc", "sub_spw", "sub_blocks", "solo", "sweep",
+                                         "fat", "ring_scaled", "tail", "spec", "head_fused", "render_fused", "render_bands", "render_wg",
+                                         "chain")] + [("reserved", C.c_int32 * 2)]
+
+
+CONV_NAMES = ("lconv", "k_conv12", "k_conv12t", "split")                                  # DNE_CONV_*
+FC_NAMES = ("k_lfc_cols", "k_lfc", "k_fc_sub", "k_fc_quad", "k_fc_tail", "k_fc_cols", "k_fc_ring", "k_fc_duo", "k_fc2", "k_fc")   # DNE_FC_*
+
+
+def debug_plan(kind, nact, total, gsize, whole_eval=False, **facts):
+    """dne_debug_plan (no GPU needed): the windows of a burst that starts with `total` active groups, knobs from the environment.  facts: the
+    fields of PlanFacts (default: four streams, dense_scale 1, nothing else).  Returns the list of WindowPlan rows, or with whole_eval the
+    evaluation's fc_full_kind."""
+    f = PlanFacts(dense_scale=1.0, n_streams=4)
+    for k, v in facts.items():
+        setattr(f, k, v)
+    rows, nsub = (WindowPlan * 4)(), C.c_int(0)
+    rc = load().dne_debug_plan(int(kind), int(nact), C.byref(f), int(total), int(gsize), rows, 4, C.byref(nsub), int(bool(whole_eval)))
+    return rc if whole_eval else list(rows[:nsub.value])
+
+
+def debug_knob(kind, nact, name):
+    """the value dne_create would read for one DNE_* knob under the current environment (-1: no such knob)"""
+    return load().dne_debug_knob(int(kind), int(nact), name.encode())
 
 
 def _ptr(a, t):

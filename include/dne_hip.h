@@ -130,6 +130,43 @@ int dne_debug_activations(dne_handle *h, int member, float *y1 /*7056*/, float *
    dne_act -- kernel-level parity against the oracle's orc_forward_large_debug (models/dqn.py:39-47). */
 int dne_debug_activations_large(dne_handle *h, int member, float *y1, float *y2, float *y3, float *y4);
 
+/* ---- the lock-step planner without a device (csrc/plan.h) ------------------------------------------------
+ * Which kernels an evaluation launches is decided on the host from the DNE_* knobs, a few facts about the member set and the active
+ * count.  dne_debug_plan runs that decision for one burst: it needs no GPU and no handle (like dne_num_params). */
+typedef struct { /* what the planner reads beyond the knobs */
+    double dense_scale;           /* table length / the stretch of it the evaluation's noise slices cover (1 unless a rank draws from its own share) */
+    int32_t kind;                 /* DNE_KIND_* (dne_debug_plan takes it from its own argument) */
+    int32_t members_materialized; /* the members are plain vectors (GA children written out) */
+    int32_t uniform_base;         /* every member perturbs the same base slot */
+    int32_t antithetic_slot0;     /* base slot 0 everywhere, members (2i, 2i+1) = (offset, +s), (the same offset, -s) */
+    int32_t pair_sigma_uniform;   /* ... with ONE s */
+    int32_t n_streams;            /* window streams (the engine has 4) */
+    int32_t has_y3s, has_theta_perm, has_scaled_table; /* the buffers of k_fc_sub, k_fc_ring and the ring's sigma-scaled table exist */
+    int32_t reserved[3];
+} dne_plan_facts;
+enum { DNE_CONV_LARGE, DNE_CONV_FUSED /* k_conv12 */, DNE_CONV_TAIL4 /* k_conv12t */, DNE_CONV_SPLIT /* k_conv1 + k_conv2 */ };
+enum { DNE_FC_LFC_COLS, DNE_FC_LFC, DNE_FC_SUB, DNE_FC_QUAD, DNE_FC_TAIL, DNE_FC_COLS, DNE_FC_RING, DNE_FC_DUO, DNE_FC_FC2, DNE_FC_FC };
+typedef struct { /* one window of a burst: groups [lo, lo + cnt) of the active list */
+    int32_t lo, cnt;
+    int32_t wide;                 /* more than DNE_FC_TAIL_MAX groups: a streaming fc */
+    int32_t skip;                 /* DNE_DEBUG_SKIP */
+    int32_t conv, s1, s2, act2;   /* DNE_CONV_*; workgroups per member of conv1 / conv2 (LargeModel: of conv2 / conv3); y2 left as relu(bn2(y2)) */
+    int32_t fc;                   /* DNE_FC_* */
+    int32_t sub_spw, sub_blocks;  /* k_fc_sub: sub-slices per wave, workgroups */
+    int32_t solo, sweep, fat, ring_scaled; /* k_fc_duo / k_fc_ring: one unit per wave, common table timeline, DNE_DUO_FAT, the scaled table */
+    int32_t tail, spec, head_fused, render_fused; /* fused tail; speculative tail; k_tail_step behind the fc; ... rendering too */
+    int32_t render_bands, render_wg; /* k_env_render: workgroups per frame, threads per workgroup */
+    int32_t chain;                /* DNE_FC_CHAIN_MIN: the fc waits for the previous window's */
+    int32_t reserved[2];
+} dne_window_plan;
+/* The burst that starts with `total` active groups of `gsize` members on an engine of `kind` with `n_actions` actions, knobs read from the
+ * environment exactly as dne_create reads them: writes one row per window (at most cap), *nsub = the number of windows; returns 0.
+ * whole_eval != 0: writes no rows and returns dne_profile.fc_full_kind of an evaluation that STARTS at that width. */
+int dne_debug_plan(int kind, int n_actions, const dne_plan_facts *facts, int total, int gsize, dne_window_plan *out, int cap, int *nsub,
+                   int whole_eval);
+/* the value of one knob (by its DNE_* name) after defaults, environment and clamping, as dne_create would see it; -1: no such knob */
+int dne_debug_knob(int kind, int n_actions, const char *name);
+
 /* ---- A1-A7: whole-batch evaluation ------------------------------------------------------------------ */
 /* es.py:411-426 for n pairs at once: returns_n2/signreturns_n2/lengths_n2 are [n][2] like Result (es.py:18-23).
  * env_seed[2n]: per-episode environment seed (noop count = 1 + seed % 30).  bc (may be NULL, needs record_bc):
