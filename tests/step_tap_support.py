@@ -151,10 +151,11 @@ def base_theta(kind, nact=NACT):
     return _base_theta(int(kind), int(nact))
 
 
-def es_member_theta(kind, idx, scale, nact=NACT):
-    """member = base + fl(scale * noise[idx : idx + P]) in the kind's own layout, then (ModelVirtualBN) expanded onto the ES layout the oracle runs"""
+def es_member_theta(kind, idx, scale, nact=NACT, noise=None):
+    """member = base + fl(scale * noise[idx : idx + P]) in the kind's own layout, then (ModelVirtualBN) expanded onto the ES layout the oracle runs
+    (noise: another table than small_noise())"""
     th = base_theta(kind, nact)
-    v = (np.float32(scale) * small_noise()[idx:idx + th.size]).astype(np.float32)
+    v = (np.float32(scale) * (small_noise() if noise is None else noise)[idx:idx + th.size]).astype(np.float32)
     m = (th + v).astype(np.float32)
     if kind == KIND_ES_VBN:
         from vbn_support import expand

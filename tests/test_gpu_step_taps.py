@@ -14,7 +14,9 @@ path), 3 lies inside a burst, 9 with DNE_BURST / DNE_BURST_TAIL = 4 lies behind 
 
 In the ring regime the y2 row holds relu(bn2(y2)) (k_conv12 with act2, or k_y2_activate); y1 is written inside an evaluation only by the
 unfused k_conv1.  The logits are not tapped inside an evaluation (that would add an argument to the hot kernels): the head's arithmetic
-behind y3 stays covered by dne_act's tests and by the outcome checks (returns / sign-returns / lengths), which are repeated here.
+behind y3 (bn3 + relu, the output layer's summation order, the bias, the first-maximum argmax and the lane that commits it) is pinned to one
+ulp, ties included, by tests/test_gpu_knife_edge.py -- every regime of this file on members whose step-T decision flips between two
+noise tables one float32 ulp apart.  The outcome checks (returns / sign-returns / lengths) are repeated here.
 
 Every population here is 18 actions wide.  The helpers take the width (nact) and, on engines that record RAM trajectories, compare every
 step's RAM: tests/test_gpu_action_widths.py runs the regimes through them at 3, 4, 9 and 17 actions."""
@@ -120,14 +122,14 @@ def _activated_pairs(n_pairs, knobs):
     return out
 
 
-def _es_engine(kind, knobs, n_pairs, monkeypatch, profile, nact=NACT, record_ram=False):
-    """record_ram: the engine keeps every member's RAM trajectory (record_bc), max(TAP_STEPS) rows each"""
+def _es_engine(kind, knobs, n_pairs, monkeypatch, profile, nact=NACT, record_ram=False, noise=None):
+    """record_ram: the engine keeps every member's RAM trajectory (record_bc), max(TAP_STEPS) rows each; noise: another table than small_noise()"""
     from dne_hip import _lib
     for k, v in knobs.items():
         monkeypatch.setenv(k, v)
     e = _lib.Engine(kind, nact, max_members=2 * n_pairs, ref_count=NREF, profile_events=profile,
                     record_bc=record_ram, bc_max_steps=max(S.TAP_STEPS) if record_ram else 0)
-    e.noise_upload(S.small_noise())
+    e.noise_upload(S.small_noise() if noise is None else noise)
     e.set_ref_batch(S.ref_batch(nact))
     e.set_theta(S.base_theta(kind, nact))
     return e
