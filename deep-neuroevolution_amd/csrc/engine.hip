@@ -1542,13 +1542,13 @@ static void launch_forward(dne_handle *h, const StepPlan &p, const WindowPlan &w
     const bool es = es_like(h->L.kind);
     float *y1 = use_done ? nullptr : h->y1;   // the fused kernels: dne_act / debug_activations want y1; evaluations do not
     switch (w.conv) {
-    case DNE_CONV_LARGE: {   // LargeModel: three matrix-core convolutions (forward_large.h); members are single (GA)
+    case DNE_CONV_LARGE: {   // LargeModel: three matrix-core convolutions (forward_large.h), one member at a time (GA children, or the two of an ES pair)
         constexpr size_t l2 = lconv_mfma_lds_bytes<32, 4, 2, 11, 34>(), l3 = lconv_mfma_lds_bytes<64, 3, 1, 11, 68>();
-        hipLaunchKernelGGL(k_lconv1, dim3(count * 2), dim3(256), 0, st, A, list, (const uint8_t *)h->stacks, h->y1);
+        hipLaunchKernelGGL(k_lconv1, dim3(items * 2), dim3(256), 0, st, A, list, gsize, (const uint8_t *)h->stacks, h->y1);
         const int ns = w.s2;
         with_bool(!h->members_materialized, [&](auto NOISE) {
-            hipLaunchKernelGGL((k_lconv_mfma<32, 64, 4, 2, 21, 11, 1, 34, NOISE()>), dim3(count * ns), dim3(256), l2, st, A, list, A.L.c2w, A.L.c2b, (const float *)h->y1, h->y2, ns);
-            hipLaunchKernelGGL((k_lconv_mfma<64, 64, 3, 1, 11, 11, 1, 68, NOISE()>), dim3(count * ns), dim3(256), l3, st, A, list, A.L.c3w, A.L.c3b, (const float *)h->y2, h->y3, ns);
+            hipLaunchKernelGGL((k_lconv_mfma<32, 64, 4, 2, 21, 11, 1, 34, NOISE()>), dim3(items * ns), dim3(256), l2, st, A, list, gsize, A.L.c2w, A.L.c2b, (const float *)h->y1, h->y2, ns);
+            hipLaunchKernelGGL((k_lconv_mfma<64, 64, 3, 1, 11, 11, 1, 68, NOISE()>), dim3(items * ns), dim3(256), l3, st, A, list, gsize, A.L.c3w, A.L.c3b, (const float *)h->y2, h->y3, ns);
         });
         return;
     }
@@ -1581,17 +1581,21 @@ static void launch_fc(dne_handle *h, const StepPlan &p, const WindowPlan &w, con
     const bool es = es_like(h->L.kind), out_fused = w.head_fused;
     const int count = w.cnt;
     switch (w.fc) {
-    case DNE_FC_LFC_COLS: case DNE_FC_LFC: {   // LargeModel: streamed 7744 x 512 fc (two 256-column halves per member), then relu + output layer + argmax
-        const dim3 lg(std::min(2 * count, 2 * k.fc_grid));
+    case DNE_FC_LFC_COLS: case DNE_FC_LFC: case DNE_FC_LFC_PAIR: {   // LargeModel: streamed 7744 x 512 fc (two 256-column halves per member), then relu + output layer + argmax
+        const int members = count * gsize;
+        const dim3 lg(std::min(2 * members, 2 * k.fc_grid));
         if (w.fc == DNE_FC_LFC_COLS) {   // few members: eight workgroups each
-            with_bool(!h->members_materialized, [&](auto NOISE) { hipLaunchKernelGGL((k_lfc_cols<NOISE()>), dim3(8 * count), dim3(256), 0, st, A, list, (const float *)h->y3, h->y3t); });
+            with_bool(!h->members_materialized, [&](auto NOISE) { hipLaunchKernelGGL((k_lfc_cols<NOISE()>), dim3(8 * members), dim3(256), 0, st, A, list, gsize, (const float *)h->y3, h->y3t); });
+        } else if (w.fc == DNE_FC_LFC_PAIR) {   // antithetic pairs over base slot 0 (plan_window): work item = (pair, half), the pair's rows fetched once
+            const dim3 pg(std::min(2 * count, 2 * k.fc_grid));
+            with_bool(k.fc_rb == 8, [&](auto RB8) { hipLaunchKernelGGL((k_lfc_pair<RB8() ? 8 : 4>), pg, dim3(256), 0, st, A, list, 2 * count, (const float *)h->y3, h->y3t); });
         } else if (h->members_materialized) {
-            if (k.fc_rb == 8 && k.lfc_pad == 1) hipLaunchKernelGGL((k_lfc<false, 8, 1>), lg, dim3(256), 0, st, A, list, 2 * count, (const float *)h->y3, h->y3t);
-            else if (k.fc_rb == 8 && k.lfc_pad == 2) hipLaunchKernelGGL((k_lfc<false, 8, 2>), lg, dim3(256), 0, st, A, list, 2 * count, (const float *)h->y3, h->y3t);
-            else if (k.fc_rb == 8) hipLaunchKernelGGL((k_lfc<false, 8>), lg, dim3(256), 0, st, A, list, 2 * count, (const float *)h->y3, h->y3t);
-            else hipLaunchKernelGGL((k_lfc<false, 4>), lg, dim3(256), 0, st, A, list, 2 * count, (const float *)h->y3, h->y3t);
-        } else hipLaunchKernelGGL((k_lfc<true, 4>), lg, dim3(256), 0, st, A, list, 2 * count, (const float *)h->y3, h->y3t);
-        hipLaunchKernelGGL(k_lout, dim3(count), dim3(256), 0, st, A, list, (const float *)h->y3t, h->action, logits);
+            if (k.fc_rb == 8 && k.lfc_pad == 1) hipLaunchKernelGGL((k_lfc<false, 8, 1>), lg, dim3(256), 0, st, A, list, gsize, 2 * members, (const float *)h->y3, h->y3t);
+            else if (k.fc_rb == 8 && k.lfc_pad == 2) hipLaunchKernelGGL((k_lfc<false, 8, 2>), lg, dim3(256), 0, st, A, list, gsize, 2 * members, (const float *)h->y3, h->y3t);
+            else if (k.fc_rb == 8) hipLaunchKernelGGL((k_lfc<false, 8>), lg, dim3(256), 0, st, A, list, gsize, 2 * members, (const float *)h->y3, h->y3t);
+            else hipLaunchKernelGGL((k_lfc<false, 4>), lg, dim3(256), 0, st, A, list, gsize, 2 * members, (const float *)h->y3, h->y3t);
+        } else hipLaunchKernelGGL((k_lfc<true, 4>), lg, dim3(256), 0, st, A, list, gsize, 2 * members, (const float *)h->y3, h->y3t);
+        hipLaunchKernelGGL(k_lout, dim3(members), dim3(256), 0, st, A, list, gsize, (const float *)h->y3t, h->action, logits);
         return;
     }
     case DNE_FC_SUB:   // mid range: one wave per sub-slice chain, folded by the head.  plan_step admits exactly two populations: ES pairs and GA children written out
@@ -1926,7 +1930,10 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
 extern "C" int dne_es_eval(dne_handle *h, const int64_t *idx, int n, float sigma, int tslimit, const uint32_t *env_seed,
                            float *returns_n2, float *signreturns_n2, int32_t *lengths_n2, uint8_t *bc) {
     DeviceGuard dg(h);
-    if (!es_like(h->L.kind)) return h->fail("dne_es_eval needs an ESAtariPolicy engine");
+    // antithetic pairs over base slot 0: the ES kinds, and the GPU tree's LargeModel (its es.py runs over any model; no reference pass).
+    // GAAtariPolicy's kernels take one member per group.
+    if (!es_like(h->L.kind) && !h->large)
+        return h->fail("dne_es_eval needs an engine of kind DNE_KIND_ES, DNE_KIND_ES_VBN or DNE_KIND_GA_LARGE (this one: %d)", h->L.kind);
     if (n <= 0 || 2 * n > h->M) return h->fail("%d pairs exceed max_members = %d", n, h->M);
     std::vector<int32_t> slot(2 * n, 0);
     std::vector<int64_t> off(2 * n);
@@ -2516,7 +2523,7 @@ static int check_records_host(dne_handle *h, int n_global) {
 // the gloo tests)
 extern "C" int dne_records_pack(dne_handle *h, int n_local, void *records_out) {
     DeviceGuard dg(h);
-    if (!es_like(h->L.kind) || n_local < 1 || 2 * n_local > h->M) return h->fail("dne_records_pack: %d pairs", n_local);
+    if ((!es_like(h->L.kind) && !h->large) || n_local < 1 || 2 * n_local > h->M) return h->fail("dne_records_pack: %d pairs", n_local);
     if (rec_reserve(h, n_local, n_local)) return -1;
     hipLaunchKernelGGL(k_records_pack, dim3((n_local + 255) / 256), dim3(256), 0, h->stream, (const int64_t *)h->m_off, (const float *)h->ret,
                        (const float *)h->sign, (const int32_t *)h->len, n_local, n_local, (PairRecord *)h->rec_send);
@@ -2550,7 +2557,7 @@ extern "C" int dne_records_set(dne_handle *h, const void *records, int n_global)
 extern "C" int dne_allgather_results(dne_handle *h, int n_local, int n_global, void *records_out) {
     DeviceGuard dg(h);
     const int world = h->comm ? h->comm_size : 1, rank = h->comm ? h->comm_rank : 0;
-    if (!es_like(h->L.kind)) return h->fail("dne_allgather_results needs an ESAtariPolicy engine");
+    if (!es_like(h->L.kind) && !h->large) return h->fail("dne_allgather_results needs an engine dne_es_eval accepts (DNE_KIND_ES, DNE_KIND_ES_VBN, DNE_KIND_GA_LARGE)");
     const int mine = n_global > rank ? (n_global - rank + world - 1) / world : 0;
     if (n_global < 1 || n_local != mine || 2 * n_local > h->M)
         return h->fail("dne_allgather_results: rank %d of %d holds %d pairs, a population of %d pairs gives it %d", rank, world, n_local, n_global, mine);

@@ -8,16 +8,19 @@
 //
 // 98 % of a member's 16.2 MB are the 7744 x 512 fc matrix: the step is HBM-bound on k_lfc (15.9 MB of noise per member-step); the
 // convolutions (12 M MAC per member-step) run on the fp32 matrix cores from LDS-staged images.
+//
+// Every kernel but k_lfc_pair walks MEMBERS: position b of a window of groups of gsize members (dne_es_eval's antithetic pairs: 2) is member
+// list[b / gsize] * gsize + b % gsize, decode_item's expansion (forward.h: window_member).
 #pragma once
 #include "forward.h"
 
 namespace dne {
 
 // conv1 (8x8 stride 4, 4 -> 32 channels): forward.h's matrix-core conv1, one workgroup per (member, 16-channel half).
-__global__ __launch_bounds__(256) void k_lconv1(FwdArgs A, const int *__restrict__ list, const uint8_t *__restrict__ stacks,
+__global__ __launch_bounds__(256) void k_lconv1(FwdArgs A, const int *__restrict__ list, int gsize, const uint8_t *__restrict__ stacks,
                                                 float *__restrict__ y1) {
     __shared__ Conv1Lds S;
-    const Item it = decode_item(A, blockIdx.x >> 1, list, 1, 1, 0, stacks, nullptr, A.done);
+    const Item it = decode_item(A, blockIdx.x >> 1, list, gsize, 1, 0, stacks, nullptr, A.done);
     if (it.skip) return;
     conv1_body<32>(S, A, it, y1, 0, 1, blockIdx.x & 1);
 }
@@ -29,7 +32,7 @@ __global__ __launch_bounds__(256) void k_lconv1(FwdArgs A, const int *__restrict
 // 64 different banks (S * PS = 4 mod 64: bank = 4 lp + kq); the member's perturbed 16-column weight tile sits next to it.
 // Each wave owns two position tiles (two independent accumulators cover the dependent-MFMA latency).
 template <int CIN, int COUT, int K, int S, int HIN, int HOUT, int PAD, int PS, bool NOISE>
-__global__ __launch_bounds__(256) void k_lconv_mfma(FwdArgs A, const int *__restrict__ list, int w_off, int b_off,
+__global__ __launch_bounds__(256) void k_lconv_mfma(FwdArgs A, const int *__restrict__ list, int gsize, int w_off, int b_off,
                                                     const float *__restrict__ in_all, float *__restrict__ out_all,
                                                     int nsplit /* workgroups per member (1, 2 or 4): each takes NT / nsplit of the 16-channel tiles */) {
     constexpr int HP = (HOUT - 1) * S + K, NPOS = HOUT * HOUT, KK = K * K * CIN, NT = COUT / 16;
@@ -40,7 +43,7 @@ __global__ __launch_bounds__(256) void k_lconv_mfma(FwdArgs A, const int *__rest
     float *xf = wt + KK * 16;                          // [HP][HP][PS]: the image, staged once for all NT tiles
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, lp = lane & 15, kq = lane >> 4;
     const int item = blockIdx.x / nsplit, part = blockIdx.x % nsplit;
-    const int m = list ? list[item] : item;
+    const int m = window_member<false>(A, list, gsize, item);
     if (A.done && A.done[m]) return;
     const float sc = A.m_scale[m];
     const int64_t off = A.m_off[m];
@@ -117,7 +120,7 @@ constexpr size_t lconv_mfma_lds_bytes() {
 // instead of running beside the HBM stream.  PAD = 1 / 2 touches a high accumulation register so that at most two / one of its
 // workgroups fit a CU.
 template <bool NOISE, int RB, int PAD = 0>
-__global__ __launch_bounds__(256) void k_lfc(FwdArgs A, const int *__restrict__ list, int n_items, const float *__restrict__ y3,
+__global__ __launch_bounds__(256) void k_lfc(FwdArgs A, const int *__restrict__ list, int gsize, int n_items, const float *__restrict__ y3,
                                              float *__restrict__ y4) {
     if constexpr (PAD == 1) asm volatile("v_accvgpr_write_b32 a79, %0" : : "v"(0) : "a79");
     if constexpr (PAD == 2) asm volatile("v_accvgpr_write_b32 a167, %0" : : "v"(0) : "a167");
@@ -128,7 +131,7 @@ __global__ __launch_bounds__(256) void k_lfc(FwdArgs A, const int *__restrict__ 
     constexpr int ROWS = 1936, PITCH = 512, NB = ROWS / RB, BPC = 64 / RB;
     for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
         const int mi = item >> 1, half = item & 1;
-        const int m = list ? list[mi] : mi;
+        const int m = window_member<false>(A, list, gsize, mi);
         if (A.done && A.done[m]) continue;
         const float sc = A.m_scale[m];
         const int64_t off = A.m_off[m];
@@ -203,10 +206,111 @@ __global__ __launch_bounds__(256) void k_lfc(FwdArgs A, const int *__restrict__ 
     }
 }
 
+// The streamed fc for antithetic pairs (dne_es_eval on a LargeModel engine: members 2g and 2g + 1 are theta + s * eps and theta - s * eps over ONE
+// eps slice and ONE theta, plan.h: antithetic_slot0).  Work item = (pair, 256-column half), wave = k-slice of 1936 rows, lane = 4 columns, two
+// row batches in flight -- k_lfc's shape -- but every theta row batch and every eps row batch is loaded ONCE and feeds two accumulator sets,
+// one per member: 15.9 MB of eps (and of theta) per pair-step instead of per member-step.  Each member's weight is base + fl(m_scale[m] * eps)
+// with its OWN scale (nothing is derived from the sign: sigma = 0 pairs and any two scales come out right), its activations are its own
+// relu'd y3 row; the sums are k_lfc's bit for bit (fmaf chain in k order from +0, ((s0+s1)+(s2+s3)) + bias, the product in its own variable).
+// A member whose done flag is set loads no activations and writes no y4 row; an item whose two members are both done fetches nothing.
+// (A done member of a live pair still runs its fmaf chain, on x = 0, and keeps its registers: the kernel is bound by the row stream, not the VALU.)
+// Compiler's report (gfx950, -O3, no scratch):  RB = 4: 112 VGPRs, 0 AGPRs, 8192 B LDS, 4 waves per SIMD = 4 workgroups per CU;
+//                                                RB = 8: 176 VGPRs, 0 AGPRs, 8192 B LDS, 2 waves per SIMD = 2 workgroups per CU
+// (k_lfc<true, 4>: 96 VGPRs, 4096 B, 5 workgroups per CU).
+template <int RB>
+__global__ __launch_bounds__(256) void k_lfc_pair(FwdArgs A, const int *__restrict__ list, int n_items, const float *__restrict__ y3,
+                                                  float *__restrict__ y4) {
+    __shared__ float part[2][4][256];
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const Layout &L = A.L;
+    __builtin_amdgcn_s_setprio(3);
+    constexpr int ROWS = 1936, PITCH = 512, NB = ROWS / RB, BPC = 64 / RB;
+    for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const int gi = item >> 1, half = item & 1;
+        const int m0 = 2 * (list ? list[gi] : gi), m1 = m0 + 1;
+        const bool live0 = !(A.done && A.done[m0]), live1 = !(A.done && A.done[m1]);
+        if (!live0 && !live1) continue;
+        const float sc0 = A.m_scale[m0], sc1 = A.m_scale[m1];
+        const int64_t off = A.m_off[m0];                                       // the pair's one eps slice ...
+        const float *base = A.bases + (size_t)A.m_slot[m0] * A.base_stride;   // ... over one theta
+        const int kbeg = ROWS * wv;
+        const float *eps = A.noise + off + L.fcw + (size_t)kbeg * PITCH + half * 256 + lane * 4;
+        const float *th = base + L.fcw + (size_t)kbeg * PITCH + half * 256 + lane * 4;
+        const float *xs0 = y3 + (size_t)m0 * 7744 + kbeg, *xs1 = y3 + (size_t)m1 * 7744 + kbeg;
+        auto load_x = [&](const float *xs, bool live, int c) {   // rows 64c .. 64c+63 of the slice (the last chunk has 16)
+            float t = 0.0f;
+            if (live && 64 * c + lane < ROWS) {
+                t = xs[64 * c + lane];
+                t = t > 0.0f ? t : 0.0f;
+            }
+            return t;
+        };
+        float acc0[4] = {0.0f, 0.0f, 0.0f, 0.0f}, acc1[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        f4u e_cur[RB] = {}, e_nxt[RB] = {};
+        f4a t_cur[RB], t_nxt[RB];
+        float xv0 = load_x(xs0, live0, 0), xn0 = load_x(xs0, live0, 1);
+        float xv1 = load_x(xs1, live1, 0), xn1 = load_x(xs1, live1, 1);
+#pragma unroll
+        for (int i = 0; i < RB; i++) {
+            e_cur[i] = *(const f4u *)(eps + (size_t)i * PITCH);
+            t_cur[i] = *(const f4a *)(th + (size_t)i * PITCH);
+        }
+        for (int bt = 0; bt < NB; bt++) {
+            if (bt + 1 < NB) {
+#pragma unroll
+                for (int i = 0; i < RB; i++) {
+                    const size_t ro = (size_t)((bt + 1) * RB + i) * PITCH;
+                    e_nxt[i] = *(const f4u *)(eps + ro);
+                    t_nxt[i] = *(const f4a *)(th + ro);
+                }
+            }
+            const int li = (bt % BPC) * RB;
+#pragma unroll
+            for (int i = 0; i < RB; i++) {
+                const float x0 = lane_bcast(xv0, li + i), x1 = lane_bcast(xv1, li + i);
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    float pv0 = sc0 * e_cur[i][q];
+                    float w0 = t_cur[i][q] + pv0;
+                    acc0[q] = __builtin_fmaf(x0, w0, acc0[q]);
+                    float pv1 = sc1 * e_cur[i][q];
+                    float w1 = t_cur[i][q] + pv1;
+                    acc1[q] = __builtin_fmaf(x1, w1, acc1[q]);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < RB; i++) { e_cur[i] = e_nxt[i]; t_cur[i] = t_nxt[i]; }
+            if (bt % BPC == BPC - 1) {
+                xv0 = xn0; xv1 = xn1;
+                xn0 = load_x(xs0, live0, bt / BPC + 2);
+                xn1 = load_x(xs1, live1, bt / BPC + 2);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++) { part[0][wv][lane * 4 + q] = acc0[q]; part[1][wv][lane * 4 + q] = acc1[q]; }
+        __syncthreads();
+        {
+            const int j = tid, col = half * 256 + j;
+            const float bt0 = base[L.fcb + col], be = A.noise[off + L.fcb + col];
+#pragma unroll
+            for (int v = 0; v < 2; v++) {
+                if (!(v ? live1 : live0)) continue;
+                const float s01 = part[v][0][j] + part[v][1][j];
+                const float s23 = part[v][2][j] + part[v][3][j];
+                float s = s01 + s23;
+                float pv = (v ? sc1 : sc0) * be;
+                float bias = bt0 + pv;
+                y4[(size_t)(m0 + v) * 512 + col] = s + bias;
+            }
+        }
+        __syncthreads();   // part is reused by the next item
+    }
+}
+
 // The same fc for a handful of members (the tail of a generation): eight workgroups per member, one per 64-column block,
 // wave = k-slice, lane = ONE column with 2 x 16 rows in flight -- eight times the workgroups pulling on one member's 15.9 MB.
 template <bool NOISE>
-__global__ __launch_bounds__(256) void k_lfc_cols(FwdArgs A, const int *__restrict__ list, const float *__restrict__ y3,
+__global__ __launch_bounds__(256) void k_lfc_cols(FwdArgs A, const int *__restrict__ list, int gsize, const float *__restrict__ y3,
                                                   float *__restrict__ y4) {
     __shared__ float part[4][64];
     __shared__ float xs[4][1936];
@@ -214,7 +318,7 @@ __global__ __launch_bounds__(256) void k_lfc_cols(FwdArgs A, const int *__restri
     const Layout &L = A.L;
     constexpr int ROWS = 1936, PITCH = 512, RB = 16, NB = ROWS / RB;
     const int mi = blockIdx.x >> 3, cb = blockIdx.x & 7;
-    const int m = list ? list[mi] : mi;
+    const int m = window_member<false>(A, list, gsize, mi);
     if (A.done && A.done[m]) return;
     const float sc = A.m_scale[m];
     const int64_t off = A.m_off[m];
@@ -272,14 +376,14 @@ __global__ __launch_bounds__(256) void k_lfc_cols(FwdArgs A, const int *__restri
 
 // relu + out layer (512 x nact: thread = inputs k = tid and 256 + tid, forward.h's out_products / out_wave_sums; the eight groups
 // of 64 combined ((S0+S1)+(S2+S3)) + ((S4+S5)+(S6+S7))) + first-max argmax, one workgroup per member
-__global__ __launch_bounds__(256) void k_lout(FwdArgs A, const int *__restrict__ list, const float *__restrict__ y4,
+__global__ __launch_bounds__(256) void k_lout(FwdArgs A, const int *__restrict__ list, int gsize, const float *__restrict__ y4,
                                               int32_t *__restrict__ actions, float *__restrict__ logits_out) {
     __shared__ float red[4][2][OUT_NA];   // [wave][half of k][action]
     __shared__ float lg[32];
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
     const Layout &L = A.L;
     const int nact = L.nact;
-    const int m = list ? list[blockIdx.x] : blockIdx.x;
+    const int m = window_member<false>(A, list, gsize, blockIdx.x);
     if (A.done && A.done[m]) return;
     const float sc[1] = {A.m_scale[m]};
     const int64_t off = A.m_off[m];

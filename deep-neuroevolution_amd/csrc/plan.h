@@ -152,6 +152,7 @@ struct StepPlan {
     bool ring = false;       // ... k_fc_ring instead of k_fc_duo (the windows' convolutions leave activated y2)
     bool ring_scaled = false; // ... its DMA source the table scaled by the evaluation's sigma (noise_pre)
     bool fc2 = false;        // else k_fc2 (two pairs per work item share the base rows), else k_fc
+    bool lpair = false;      // LargeModel, antithetic pairs, windows above lfc_cols_max MEMBERS: k_lfc_pair (a pair's eps and theta rows fetched once)
 };
 
 // The regime of a burst that starts with `total` active groups of `gsize` members.  One global list of active groups, compacted every burst; within a burst
@@ -185,12 +186,14 @@ static inline StepPlan plan_step(const Knobs &k, const PlanFacts &f, int total, 
     const bool dense = (double)total * f.dense_scale >= (double)k.duo_solo_below && total >= k.ring_min;
     p.ring = p.duo && f.has_theta_perm && f.antithetic_slot0 && k.duo_sweep && (k.ring_on > 1 || dense) && (dense || k.duo_sweep > 1);
     p.ring_scaled = p.ring && k.ring_pre && f.pair_sigma_uniform && f.has_scaled_table;   // (the evaluation started at least as wide and filled the copy)
+    // the LargeModel's pairs (dne_es_eval over base slot 0): the windows of a burst differ by at most one pair, the widest decides the regime
+    p.lpair = large && gsize == 2 && f.antithetic_slot0 && 2 * ((total + p.nsub - 1) / p.nsub) > k.lfc_cols_max;
     return p;
 }
 
 // dne_profile.fc_full_kind of an evaluation whose starting width gives plan_step(.., whole_eval = true) = ev
 // (one that STARTS in the sub-slice fc's range: its bracketed launches are k_fc_sub's)
-static inline int fc_full_kind(const StepPlan &ev) { return ev.ring ? 5 : ev.duo ? 3 : ev.fc2 ? 2 : ev.sub ? 4 : 1; }
+static inline int fc_full_kind(const StepPlan &ev) { return ev.lpair ? 6 : ev.ring ? 5 : ev.duo ? 3 : ev.fc2 ? 2 : ev.sub ? 4 : 1; }
 
 // lock-steps until the next compaction of the active list
 static inline int burst_length(const Knobs &k, int total) { return total <= k.fc_tail_max ? k.burst_tail : k.burst; }
@@ -210,7 +213,7 @@ static inline Window window(int total, int nsub, int s) {
 
 using WindowPlan = dne_window_plan;
 static inline const char *fc_name(int fc) {
-    static const char *const names[] = {"k_lfc_cols", "k_lfc", "k_fc_sub", "k_fc_quad", "k_fc_tail", "k_fc_cols", "k_fc_ring", "k_fc_duo", "k_fc2", "k_fc"};
+    static const char *const names[] = {"k_lfc_cols", "k_lfc", "k_fc_sub", "k_fc_quad", "k_fc_tail", "k_fc_cols", "k_fc_ring", "k_fc_duo", "k_fc2", "k_fc", "k_lfc_pair"};
     return names[fc];
 }
 static inline bool is_duo(const WindowPlan &w) { return w.fc == DNE_FC_RING || w.fc == DNE_FC_DUO; }   // table-ordered units: the window has a unit order
@@ -225,9 +228,11 @@ static inline WindowPlan plan_window(const Knobs &k, const PlanFacts &f, const S
     w.cnt = cnt;
     w.wide = cnt > k.fc_tail_max;
     w.skip = k.dbg_skip;
-    if (large) {   // LargeModel: three matrix-core convolutions; few members: one workgroup per 16-channel tile
-        w.conv = DNE_CONV_LARGE;
-        w.s1 = w.s2 = cnt <= 128 ? 4 : cnt <= 256 ? 2 : 1;
+    if (large) {   // LargeModel: three matrix-core convolutions; few members: one workgroup per 16-channel tile.  Its kernels walk members
+        w.conv = DNE_CONV_LARGE;   // (a pair is two of them), so the thresholds of THIS function (s1 / s2, wide, lfc_cols_max) count MEMBERS;
+                                   // plan_step's cut into windows and burst_length count groups for every kind, pairs included
+        w.s1 = w.s2 = items <= 128 ? 4 : items <= 256 ? 2 : 1;
+        w.wide = items > k.fc_tail_max;
     } else {
         w.act2 = p.ring && w.wide;   // the window's fc is k_fc_ring: leave relu(bn2(y2)) instead of y2 (ES pairs only)
         // few members left: several workgroups per member (conv1: 28 position tiles over 4 or 7 workgroups; conv2: 8 over 2 or 4)
@@ -238,7 +243,8 @@ static inline WindowPlan plan_window(const Knobs &k, const PlanFacts &f, const S
                                                          : DNE_CONV_SPLIT;                     // k_conv1 + k_conv2
     }
     const bool duo_win = p.duo && w.wide;
-    if (large) w.fc = cnt <= k.lfc_cols_max ? DNE_FC_LFC_COLS : DNE_FC_LFC;   // few members: eight workgroups each
+    if (large)   // few members: eight workgroups each; antithetic pairs over base slot 0: k_lfc_pair; else one streamed pass per member
+        w.fc = items <= k.lfc_cols_max ? DNE_FC_LFC_COLS : gsize == 2 && f.antithetic_slot0 ? DNE_FC_LFC_PAIR : DNE_FC_LFC;
     else if (p.sub) {   // mid range: one wave per sub-slice chain, folded by the head
         w.fc = DNE_FC_SUB;
         // sub-slices per wave: about 8000 waves (one round of the whole machine) whatever the width
@@ -270,6 +276,8 @@ static inline WindowPlan plan_window(const Knobs &k, const PlanFacts &f, const S
     return w;
 }
 
+// (LargeModel: the kind of an evaluation -- 1, or 6 for pairs -- follows lfc_cols_max, the brackets follow w.wide = fc_tail_max.  Both default to 96
+// members; set apart, an evaluation of kind 6 / 1 may bracket no launch (DNE_LFC_COLS_MAX=0 with few members) or count a window of k_lfc_cols launches.)
 // a profiled evaluation brackets the launches of ONE kernel, the one it starts with (ev = plan_step(.., whole_eval = true)): k_fc_ring's, else k_fc_duo's,
 // else k_fc2's, else every window above fc_tail_max groups -- in the latency-bound tail every event packet is a bubble
 static inline bool window_profiled(const StepPlan &ev, const StepPlan &p, const WindowPlan &w) {

@@ -118,7 +118,7 @@ class WindowPlan(C.Structure):
 
 
 CONV_NAMES = ("lconv", "k_conv12", "k_conv12t", "split")                                  # DNE_CONV_*
-FC_NAMES = ("k_lfc_cols", "k_lfc", "k_fc_sub", "k_fc_quad", "k_fc_tail", "k_fc_cols", "k_fc_ring", "k_fc_duo", "k_fc2", "k_fc")   # DNE_FC_*
+FC_NAMES = ("k_lfc_cols", "k_lfc", "k_fc_sub", "k_fc_quad", "k_fc_tail", "k_fc_cols", "k_fc_ring", "k_fc_duo", "k_fc2", "k_fc", "k_lfc_pair")   # DNE_FC_*
 
 
 def debug_plan(kind, nact, total, gsize, whole_eval=False, **facts):

@@ -16,6 +16,15 @@ key exp['flat_layout']:
 An engine passed in by the caller decides the layout by its kind.  The layout and P are recorded in snapshot.pkl; a resume under another
 layout or P fails and names both (snapshots written before the key existed are 'es_distributed').  Not built: `load_from` (ga_legacy genomes).
 
+es.py:144 takes exp['model'] from any of neuroevolution.models; `LargeModel` (models/dqn.py:39-47: conv 32/64/64, fc 512, 4 052 658 parameters at
+18 actions, no batch norm) runs here too, on a DNE_KIND_GA_LARGE engine: theta is base slot 0, the pairs go through dne_es_eval (the streamed
+fc shares a pair's theta and noise rows, csrc/forward_large.h: k_lfc_pair), there is no reference batch, and theta starts as
+TrainingState.initialize does: idx = noise.sample_index(rs, P), the first draw, then noise.get(idx, P) * scale_by (ga_gpu.model_scale_by) in fp32.
+flat_layout does not apply to it (only 'native', its one layout, is accepted).  The model's name is recorded in snapshot.pkl (a snapshot without
+it is ModelVirtualBN); a resume under another model or P fails and names both.  A caller's engine of kind KIND_GA_LARGE selects this path.
+Not built: every other model.  `Model` (dqn.py:24-36) is the network of DNE_KIND_GA, whose kernels take one member per group: dne_es_eval on
+that kind is a tested refusal (tests/test_gpu_edges.py::test_refusals).  `ModelBN`, `SmallDQN` and the rest have no engine kind.
+
 Where the arithmetic lives: ranks, sum_i w_i * noise[idx_i] / 2N, -g + l2coeff * theta and the optimizer step are dne_es_update on the device
 (the same formulas as es_distributed: es.py:227-246 here = es_distributed/es.py:281-301).  The GPU tree's SGD keeps v = momentum * v + g
 (neuroevolution/optimizers.py:49-51) where es_distributed keeps (1 - momentum) * g: with u = (1 - momentum) * v that is the engine's SGD at
@@ -30,9 +39,10 @@ import numpy as np
 
 from . import _lib
 from .es import SharedNoiseTable, get_ref_batch, optimizer_args, parse_cutoff
-from .ga_gpu import Offspring, Schedule
+from .ga_gpu import Offspring, Schedule, model_scale_by
 
-MODEL_KINDS = {'ModelVirtualBN': _lib.KIND_ES}   # neuroevolution/models/batchnorm.py:52 (exp['model'], es.py:144)
+# exp['model'] (es.py:144): neuroevolution/models/batchnorm.py:52 (in either flat layout, FLAT_LAYOUTS) and models/dqn.py:39
+MODEL_KINDS = {'ModelVirtualBN': _lib.KIND_ES, 'LargeModel': _lib.KIND_GA_LARGE}
 FLAT_LAYOUTS = {'es_distributed': _lib.KIND_ES, 'native': _lib.KIND_ES_VBN}   # exp['flat_layout'] -> the engine kind that runs it
 
 
@@ -51,6 +61,7 @@ class TrainingState(object):
         if adaptive:
             self.tslimit_max = limit_max
         self.flat_layout = 'es_distributed'   # FLAT_LAYOUTS key of the run (main sets it); a snapshot without it predates the choice
+        self.model = 'ModelVirtualBN'         # MODEL_KINDS key of the run (main sets it); a snapshot without it predates LargeModel
         self.num_params = None
         self.theta = None
         self.optimizer = None          # (m, v, t) of the device optimizer, None before the first update
@@ -75,6 +86,8 @@ def engine_optimizer(opt):
     """(kind, stepsize, beta1-or-momentum, beta2, epsilon) for dne_es_update; the GPU tree's SGD mapped as the module docstring says"""
     step, first, beta2, eps = optimizer_args(opt)
     if opt['type'] == 'sgd':
+        if first >= 1.0:
+            raise ValueError("sgd momentum {!r}: the engine's SGD runs at stepsize / (1 - momentum), momentum must be below 1".format(first))
         step = step / (1.0 - first)
     return opt['type'], step, first, beta2, eps
 
@@ -101,12 +114,25 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
     if 'load_from' in exp:
         raise NotImplementedError("load_from (es.py:164-171: a ga_legacy genome as the first theta) is not built")
     n_pairs = exp['population_size'] // 2
-    if engine is None:
+    asked = exp['model'] if engine is None else exp.get('model')   # the caller's engine decides; a name given with it must agree
+    if asked is not None and asked not in MODEL_KINDS:
+        raise NotImplementedError("model {!r}: this loop runs {}".format(asked, sorted(MODEL_KINDS)))
+    large = (engine.kind if engine is not None else MODEL_KINDS[asked]) == _lib.KIND_GA_LARGE
+    model = 'LargeModel' if large else 'ModelVirtualBN'
+    if asked is not None and asked != model:
+        raise ValueError("model {!r} asked for, the engine passed in (kind {}) runs {!r}".format(asked, engine.kind, model))
+    if large:                                                       # one flat layout, the model's own; no reference batch
+        layout = 'native'
+        if exp.get('flat_layout', layout) != layout:
+            raise ValueError("flat_layout {!r}: LargeModel has one layout, 'native'".format(exp['flat_layout']))
+        if engine is None:
+            engine = _lib.Engine(_lib.KIND_GA_LARGE, 18, max_members=2 * n_pairs)
+        scale_by = model_scale_by(engine.n_actions, _lib.KIND_GA_LARGE)
+        engine.ga_set_init_scale(scale_by)
+    elif engine is None:
         layout = exp.get('flat_layout', 'es_distributed')
         if layout not in FLAT_LAYOUTS:
             raise ValueError("flat_layout {!r}: expected one of {}".format(layout, sorted(FLAT_LAYOUTS)))
-        if MODEL_KINDS[exp['model']] != _lib.KIND_ES:                # the one model of this loop, in either layout
-            raise NotImplementedError(exp['model'])
         engine = _lib.Engine(FLAT_LAYOUTS[layout], 18, max_members=2 * n_pairs, ref_count=ref_count)
     else:                                                           # the caller's engine decides
         layout = {k: name for name, k in FLAT_LAYOUTS.items()}.get(engine.kind)
@@ -121,22 +147,27 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
         with open(os.path.join(log_dir, 'snapshot.pkl'), 'rb') as file:
             state = pickle.load(file)
         tlogger.log("Loaded iteration {} from {}".format(state.it, log_dir))
+        was_model = getattr(state, 'model', 'ModelVirtualBN')
+        if was_model != model or (large and int(np.asarray(state.theta).size) != engine.P):
+            raise ValueError("snapshot.pkl in {} holds model {!r} with P = {}; this run is model {!r} with P = {}".format(
+                log_dir, was_model, int(np.asarray(state.theta).size), model, engine.P))
         was = (getattr(state, 'flat_layout', 'es_distributed'), int(np.asarray(state.theta).size))
-        if was != (layout, engine.P):
+        if not large and was != (layout, engine.P):
             raise ValueError("snapshot.pkl in {} holds flat_layout {!r} with P = {}; this run is flat_layout {!r} with P = {}".format(
                 log_dir, was[0], was[1], layout, engine.P))
     except FileNotFoundError:
         state = TrainingState(exp)
-        if layout == 'native':                                      # es.py:173 -> es.py:73-75 -> model.randomize(rs, noise), base.py:123-141
+        if large or layout == 'native':                             # es.py:173 -> es.py:73-75 -> model.randomize(rs, noise), base.py:123-141
             idx = noise.sample_index(rs, engine.P)
-            state.theta = noise.get(idx, engine.P) * policies.vbn_scale_by(engine.n_actions)
+            state.theta = noise.get(idx, engine.P) * (scale_by if large else policies.vbn_scale_by(engine.n_actions))
         else:
             state.theta = policies.xavier_flat(engine.n_actions, seed)   # es.py:173: state.initialize(rs, noise, worker.model)
-    state.flat_layout, state.num_params = layout, engine.P
+    state.flat_layout, state.num_params, state.model = layout, engine.P, model
     state.push(engine)
-    env = policies.HipAtariEnv(engine, seed=seed)                   # ModelVirtualBN.requires_ref_batch (batchnorm.py:60-62)
-    ref = np.stack(get_ref_batch(env, batch_size=engine.ref_count, random_stream=np.random.RandomState(seed)))
-    engine.set_ref_batch(np.rint(ref * 255.0).astype(np.uint8))
+    if not large:                                                   # ModelVirtualBN.requires_ref_batch (batchnorm.py:60-62); LargeModel has none
+        env = policies.HipAtariEnv(engine, seed=seed)
+        ref = np.stack(get_ref_batch(env, batch_size=engine.ref_count, random_stream=np.random.RandomState(seed)))
+        engine.set_ref_batch(np.rint(ref * 255.0).astype(np.uint8))
     opt = engine_optimizer(exp['optimizer'])
     initial_performance, _ = _episodes_of_theta(engine, exp['num_test_episodes'], None, rs)   # es.py:190
     if getattr(state, 'stream', None) is not None:

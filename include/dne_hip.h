@@ -24,7 +24,9 @@ extern "C" {
 #define DNE_KIND_ES 0 /* ESAtariPolicy  es_distributed/policies.py:305-429 */
 #define DNE_KIND_GA 1 /* GAAtariPolicy  es_distributed/policies.py:433-513 */
 #define DNE_KIND_GA_LARGE 2 /* LargeModel of the GPU tree (conv 32/64/64, fc 512): gpu_implementation/neuroevolution/models/dqn.py:39-47.
-                               GA entry points only, genomes with per-seed powers (dne_ga_set_init_scale + dne_ga_eval_powers) */
+                               Deep-GA: genomes with per-seed powers (dne_ga_set_init_scale + dne_ga_eval_powers).  ES as the GPU tree's es.py runs it
+                               over any of its models: dne_set_theta (base slot 0, never handed to GA parents or children) + dne_es_eval
+                               (antithetic pairs, no reference batch) + dne_es_update; a shard travels with dne_records_pack / dne_allgather_results */
 #define DNE_KIND_ES_VBN 3 /* ModelVirtualBN of the GPU tree in its own flat layout: gpu_implementation/neuroevolution/models/batchnorm.py:52-123
                              (tensors in creation order, models/base.py:35-44, 166-178).  The ES kind's network, evaluation and entry points
                              (virtual batch norm, antithetic pairs, dne_es_eval / dne_es_update); no conv / fc biases, no BN gamma: each
@@ -71,7 +73,7 @@ typedef struct { /* filled by dne_get_profile; times from HIP events on the engi
     double fc_full_ms;
     double fc_full_launches;
     double fc_full_units; /* env-steps (member-steps actually taken) processed by those launches */
-    double fc_full_kind;  /* which kernel those launches were: 5 = k_fc_ring (the workgroup's noise rows through an LDS ring), 4 = k_fc_sub (one wave per sub-slice chain), 3 = k_fc_duo (table-ordered units), 2 = k_fc2 (two pairs per work item), 1 = k_fc */
+    double fc_full_kind;  /* which kernel those launches were: 6 = k_lfc_pair (LargeModel: an antithetic pair's theta and eps rows fetched once for both members), 5 = k_fc_ring (the workgroup's noise rows through an LDS ring), 4 = k_fc_sub (one wave per sub-slice chain), 3 = k_fc_duo (table-ordered units), 2 = k_fc2 (two pairs per work item), 1 = k_fc */
     double fc_full_union_ms; /* time during which at least one of those launches was running (windows run them concurrently) */
     double reserved[1];
 } dne_profile;
@@ -145,10 +147,11 @@ typedef struct { /* what the planner reads beyond the knobs */
     int32_t reserved[3];
 } dne_plan_facts;
 enum { DNE_CONV_LARGE, DNE_CONV_FUSED /* k_conv12 */, DNE_CONV_TAIL4 /* k_conv12t */, DNE_CONV_SPLIT /* k_conv1 + k_conv2 */ };
-enum { DNE_FC_LFC_COLS, DNE_FC_LFC, DNE_FC_SUB, DNE_FC_QUAD, DNE_FC_TAIL, DNE_FC_COLS, DNE_FC_RING, DNE_FC_DUO, DNE_FC_FC2, DNE_FC_FC };
+enum { DNE_FC_LFC_COLS, DNE_FC_LFC, DNE_FC_SUB, DNE_FC_QUAD, DNE_FC_TAIL, DNE_FC_COLS, DNE_FC_RING, DNE_FC_DUO, DNE_FC_FC2, DNE_FC_FC,
+       DNE_FC_LFC_PAIR /* k_lfc_pair: the LargeModel's streamed fc over antithetic pairs */ };
 typedef struct { /* one window of a burst: groups [lo, lo + cnt) of the active list */
     int32_t lo, cnt;
-    int32_t wide;                 /* more than DNE_FC_TAIL_MAX groups: a streaming fc */
+    int32_t wide;                 /* more than DNE_FC_TAIL_MAX groups (LargeModel: members): a streaming fc */
     int32_t skip;                 /* DNE_DEBUG_SKIP */
     int32_t conv, s1, s2, act2;   /* DNE_CONV_*; workgroups per member of conv1 / conv2 (LargeModel: of conv2 / conv3); y2 left as relu(bn2(y2)) */
     int32_t fc;                   /* DNE_FC_* */
@@ -169,6 +172,8 @@ int dne_debug_knob(int kind, int n_actions, const char *name);
 
 /* ---- A1-A7: whole-batch evaluation ------------------------------------------------------------------ */
 /* es.py:411-426 for n pairs at once: returns_n2/signreturns_n2/lengths_n2 are [n][2] like Result (es.py:18-23).
+ * Engines: DNE_KIND_ES, DNE_KIND_ES_VBN (reference pass first) and DNE_KIND_GA_LARGE (theta = base slot 0, no reference pass);
+ * DNE_KIND_GA refuses (its kernels take one member per group).  DNE_KIND_GA_LARGE has no behaviour trajectories: bc = final RAM [2n][128].
  * env_seed[2n]: per-episode environment seed (noop count = 1 + seed % 30).  bc (may be NULL, needs record_bc):
  * [2n][bc_max_steps][128] RAM trajectories (policies.py:410,418) */
 int dne_es_eval(dne_handle *h, const int64_t *noise_idx, int n, float sigma, int tslimit,
@@ -236,12 +241,12 @@ int dne_comm_allreduce(dne_handle *h, double *inout, int n, int op);
 /* generic all-gather of `bytes` host bytes per rank (the GA's 32-byte child records: parent index, fresh seed, return,
  * length -- the per-child content of a GA Result, ga.py:266-271); recv holds nranks * bytes in rank order */
 int dne_comm_allgather(dne_handle *h, const void *send, size_t bytes, void *recv);
-/* all-gather of the records of the n_local pairs this rank evaluated in its last dne_es_eval, taken from the device
+/* all-gather of the records of the n_local pairs this rank evaluated in its last dne_es_eval (any kind dne_es_eval accepts), taken from the device
  * accumulators; the gathered set stays on the device in global pair order.  records_out: [n_global] records or NULL */
 int dne_allgather_results(dne_handle *h, int n_local, int n_global, void *records_out);
 /* test hook: un-shard a [nranks][ceil(n_global / nranks)] all-gather result (host copy) into global pair order on the device */
 int dne_debug_unshard(dne_handle *h, const void *gathered, int n_global, int nranks, void *ordered_out);
-/* other transports (the redis Result path, gloo in the CPU tests): this rank's shard out / the gathered set in */
+/* other transports (the redis Result path, gloo in the CPU tests): this rank's shard of its last dne_es_eval out / the gathered set in */
 int dne_records_pack(dne_handle *h, int n_local, void *records_out /*[n_local]*/);
 int dne_records_set(dne_handle *h, const void *records /*[n_global], global pair order*/, int n_global);
 /* es.py:281-298 on the gathered device-resident records (identical on every rank -> bit-identical theta) */
