@@ -28,6 +28,7 @@
 #include "reduce.h"
 #include "novelty.h"
 #include "plan.h"
+#include "maze.h"
 
 using namespace dne;
 
@@ -37,6 +38,12 @@ static thread_local std::string g_create_error;
     do {                                                                                        \
         hipError_t _e = (expr);                                                                 \
         if (_e != hipSuccess) return (h)->fail("%s:%d %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
+    } while (0)
+
+// the Atari-only entry points on a hard-maze engine: an error that names the kind
+#define MAZE_REFUSE(h, call)                                                                    \
+    do {                                                                                        \
+        if ((h)->maze) return (h)->fail("%s is not available on a DNE_KIND_MAZE engine (kind %d): the hard maze has no Atari frames, reference batch, genomes or byte BCs", call, DNE_KIND_MAZE); \
     } while (0)
 
 // ------------------------------------------------------------------------------- env kernels
@@ -621,6 +628,9 @@ struct dne_handle {
     float *y1 = nullptr, *y2 = nullptr, *y3 = nullptr, *y3t = nullptr;   // step mode: one row per member (y3t: 4 k-slice partials)
     bool members_materialized = false;   // the current members are plain vectors (scale 0 everywhere): kernels that have one skip the noise stream
     std::vector<int> child_slots;    // base slots set aside for materialised children
+    bool maze = false;               // DNE_KIND_MAZE: whole episodes in k_maze_rollout (csrc/maze.h); none of the Atari buffers exist
+    maze::Header maze_hdr{}; float *maze_walls = nullptr; int maze_nw = 0;   // dne_maze_set_walls
+    float *maze_xy = nullptr; int maze_last_n = 0;   // final (x, y) per member of the last evaluation, and how many members that was
     bool large = false;              // DNE_KIND_GA_LARGE: y1 [441][32], y2 / y3 [121][64] (conv3 output), y3t = the 512 fc outputs
     float *y1r[2] = {nullptr, nullptr}, *y2r[2] = {nullptr, nullptr}, *y3pr[2] = {nullptr, nullptr};   // reference pass scratch, two ways
     float *fr1[2] = {nullptr, nullptr}, *fr2[2] = {nullptr, nullptr};   // per-frame batch-norm moments of conv1 / conv2 ([rows][2][C])
@@ -786,7 +796,11 @@ static void make_layout(int kind, int nact, Layout *L) {
     memset(L, 0, sizeof(*L));
     L->kind = kind; L->nact = nact;
     auto take = [&](int n) { int r = o; o += n; return r; };
-    if (kind == DNE_KIND_ES) {   // creation order of trainable variables, policies.py:319-330
+    if (kind == DNE_KIND_MAZE) {   // SimpleClassifier (models/simple.py:29-35): csrc/maze.h holds its offsets
+        L->c1w = L->c1b = L->c2w = L->c2b = L->c3w = L->c3b = L->fcw = L->fcb = L->ow = L->ob = -1;
+        L->bn1b = L->bn1g = L->bn2b = L->bn2g = L->bn3b = L->bn3g = -1;
+        o = maze::NPARAMS;
+    } else if (kind == DNE_KIND_ES) {   // creation order of trainable variables, policies.py:319-330
         L->c1w = take(4096); L->c1b = take(16); L->bn1b = take(16); L->bn1g = take(16);
         L->c2w = take(8192); L->c2b = take(32); L->bn2b = take(32); L->bn2g = take(32);
         L->fcw = take(3872 * 256); L->fcb = take(256); L->bn3b = take(256); L->bn3g = take(256);
@@ -889,6 +903,7 @@ struct DevBuf {
 };
 
 extern "C" int dne_num_params(int kind, int nact) {
+    if (kind == DNE_KIND_MAZE && nact != maze::ACT) return -1;   // the maze policy has two raw outputs, nothing else
     Layout L;
     make_layout(kind, nact, &L);
     return L.P;
@@ -899,6 +914,10 @@ static Knobs engine_knobs(int kind, int nact) { return knobs_from_env(kind, nact
 
 extern "C" int dne_debug_plan(int kind, int n_actions, const dne_plan_facts *facts, int total, int gsize, dne_window_plan *out, int cap,
                               int *nsub, int whole_eval) {
+    if (kind == DNE_KIND_MAZE) {   // no lock-step to plan: one launch per evaluation
+        g_create_error = "dne_debug_plan: a DNE_KIND_MAZE engine (kind 4) has no lock-step windows, an evaluation is one k_maze_rollout launch";
+        return -1;
+    }
     const Knobs k = engine_knobs(kind, n_actions);
     PlanFacts f = *facts;
     f.kind = kind;
@@ -947,7 +966,7 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         return -1;
     }
     if (cfg->max_members <= 0 || cfg->n_actions <= 1 ||
-        (!es_like(cfg->policy_kind) && cfg->policy_kind != DNE_KIND_GA && cfg->policy_kind != DNE_KIND_GA_LARGE)) {
+        (!es_like(cfg->policy_kind) && cfg->policy_kind != DNE_KIND_GA && cfg->policy_kind != DNE_KIND_GA_LARGE && cfg->policy_kind != DNE_KIND_MAZE)) {
         g_create_error = "dne_create: bad config";
         return -1;
     }
@@ -955,6 +974,10 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
     // wider head could pick an action nothing defines and no parity covers
     if (cfg->n_actions > 18) {
         g_create_error = "dne_create: n_actions " + std::to_string(cfg->n_actions) + " is outside 2..18: the SynthAtari fixture defines 18 actions";
+        return -1;
+    }
+    if (cfg->policy_kind == DNE_KIND_MAZE && cfg->n_actions != maze::ACT) {
+        g_create_error = "dne_create: DNE_KIND_MAZE has 2 outputs (the navigator's turn and speed), n_actions " + std::to_string(cfg->n_actions) + " is refused";
         return -1;
     }
     dne_handle *h = new dne_handle();
@@ -976,6 +999,37 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         int sc = 1;
         env_int("DNE_STAGED_COPY", 0, 1, &sc);
         h->staged_copies = sc != 0;
+    }
+    if (cfg->policy_kind == DNE_KIND_MAZE) {
+        // theta slots, member descriptors and accumulators, the walls, the reduce and optimizer buffers: no frame, activation or ring buffer
+        h->maze = true;
+        make_layout(cfg->policy_kind, cfg->n_actions, &h->L);
+        h->M = cfg->max_members;
+        h->base_stride = ((size_t)h->L.P + 63) / 64 * 64;
+        const size_t M = h->M;
+        CCHECK(grow_bases(h, 1));
+        CH(hipMemset(h->bases, 0, h->base_stride * sizeof(float)));
+        CH(h->alloc(&h->opt_m, h->L.P, "opt_m")); CH(h->alloc(&h->opt_v, h->L.P, "opt_v")); CH(h->alloc(&h->g, h->L.P, "g"));
+        CH(hipMemset(h->opt_m, 0, h->L.P * sizeof(float))); CH(hipMemset(h->opt_v, 0, h->L.P * sizeof(float)));
+        CH(h->alloc(&h->partial, 2 * ((size_t)h->L.P / 256 + 1), "partial"));
+        CH(h->alloc(&h->m_slot, M, "m_slot")); CH(h->alloc(&h->m_off, M, "m_off")); CH(h->alloc(&h->m_scale, M, "m_scale"));
+        CH(hipMemset(h->m_slot, 0, M * sizeof(int32_t))); CH(hipMemset(h->m_off, 0, M * sizeof(int64_t))); CH(hipMemset(h->m_scale, 0, M * sizeof(float)));
+        CH(h->alloc(&h->ret, M, "ret")); CH(h->alloc(&h->sign, M, "sign")); CH(h->alloc(&h->len, M, "len"));
+        CH(hipMemset(h->ret, 0, M * sizeof(float))); CH(hipMemset(h->sign, 0, M * sizeof(float))); CH(hipMemset(h->len, 0, M * sizeof(int32_t)));
+        CH(h->alloc(&h->maze_xy, 2 * M, "maze_xy")); CH(h->alloc(&h->maze_walls, maze::MAX_WALLS * 4, "maze_walls"));
+        CH(hipMemset(h->maze_xy, 0, 2 * M * sizeof(float)));
+        if (cfg->record_bc) {   // behaviour: the navigator's (x, y) after every step, [member][bc_max_steps][2] floats
+            h->bc_bytes = M * (size_t)std::max(cfg->bc_max_steps, 1) * 2 * sizeof(float);
+            CH(h->alloc(&h->bc, h->bc_bytes, "bc"));
+            CH(hipMemset(h->bc, 0, h->bc_bytes));
+        }
+        h->scratch_cap = std::max<size_t>(4 * M + 64, 65536);
+        CH(h->alloc(&h->scratch_f, h->scratch_cap, "scratch_f")); CH(h->alloc(&h->scratch_i, h->scratch_cap, "scratch_i"));
+        CH(hipEventCreate(&h->ev_a)); CH(hipEventCreate(&h->ev_b));
+        CH(hipDeviceSynchronize());
+        h->trace("engine created: kind %d (hard maze), %d members, %zu device buffers", cfg->policy_kind, h->M, h->blocks.size());
+        *out = h;
+        return 0;
     }
     h->k = engine_knobs(cfg->policy_kind, cfg->n_actions);
     CH(hipFuncSetAttribute((const void *)k_conv12<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Conv12Lds)));
@@ -1255,6 +1309,7 @@ extern "C" int dne_get_theta(dne_handle *h, int slot, float *out, size_t n) {
 
 extern "C" int dne_set_ref_batch(dne_handle *h, const uint8_t *ref, int count) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_set_ref_batch");
     if (!es_like(h->L.kind)) return h->fail("reference batch is an ESAtariPolicy concept");
     if (count != h->F) return h->fail("dne_set_ref_batch: engine was created for %d reference frames, got %d", h->F, count);
     HCHECK(h, hipMemcpy(h->ref, ref, (size_t)count * OB_BYTES, hipMemcpyHostToDevice));
@@ -1312,6 +1367,7 @@ static int check_n(dne_handle *h, int n) {
 
 extern "C" int dne_env_reset(dne_handle *h, int n, const uint32_t *seeds) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_env_reset");
     if (check_n(h, n)) return -1;
     HCHECK(h, hipMemcpyAsync(h->seeds, seeds, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     launch_env_reset(h, n);
@@ -1322,6 +1378,7 @@ extern "C" int dne_env_reset(dne_handle *h, int n, const uint32_t *seeds) {
 
 extern "C" int dne_env_step(dne_handle *h, int n, const int32_t *actions, float *reward, int32_t *done) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_env_step");
     if (check_n(h, n)) return -1;
     for (int i = 0; i < n; i++)
         if (actions[i] < 0 || actions[i] >= h->cfg.n_actions) return h->fail("action %d out of range", actions[i]);
@@ -1337,6 +1394,7 @@ extern "C" int dne_env_step(dne_handle *h, int n, const int32_t *actions, float 
 
 extern "C" int dne_env_observation(dne_handle *h, int n, uint8_t *out) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_env_observation");
     if (check_n(h, n)) return -1;
     HCHECK(h, hipStreamSynchronize(h->stream));
     HCHECK(h, hipMemcpy(out, h->stacks, (size_t)n * OB_BYTES, hipMemcpyDeviceToHost));
@@ -1345,6 +1403,7 @@ extern "C" int dne_env_observation(dne_handle *h, int n, uint8_t *out) {
 
 extern "C" int dne_env_ram(dne_handle *h, int n, uint8_t *out) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_env_ram");
     if (check_n(h, n)) return -1;
     HCHECK(h, hipStreamSynchronize(h->stream));
     HCHECK(h, hipMemcpy(out, h->ram_cur, (size_t)n * 128, hipMemcpyDeviceToHost));
@@ -1353,6 +1412,7 @@ extern "C" int dne_env_ram(dne_handle *h, int n, uint8_t *out) {
 
 extern "C" int dne_env_set_observation(dne_handle *h, int n, const uint8_t *obs) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_env_set_observation");
     if (check_n(h, n)) return -1;
     HCHECK(h, hipMemcpy(h->stacks, obs, (size_t)n * OB_BYTES, hipMemcpyHostToDevice));
     return 0;
@@ -1360,6 +1420,7 @@ extern "C" int dne_env_set_observation(dne_handle *h, int n, const uint8_t *obs)
 
 extern "C" int dne_env_set_ram(dne_handle *h, int n, const uint8_t *ram_prev, const uint8_t *ram_cur) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_env_set_ram");
     if (check_n(h, n)) return -1;
     HCHECK(h, hipMemcpyAsync(h->ram_prev, ram_prev, (size_t)n * 128, hipMemcpyHostToDevice, h->stream));
     HCHECK(h, hipMemcpyAsync(h->ram_cur, ram_cur, (size_t)n * 128, hipMemcpyHostToDevice, h->stream));
@@ -1506,6 +1567,7 @@ extern "C" int dne_debug_duo_ticks(dne_handle *h, long long *ticks, long long *p
 
 extern "C" int dne_ref_pass(dne_handle *h, int n) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_ref_pass");
     if (check_n(h, n)) return -1;
     if (!es_like(h->L.kind)) return h->fail("dne_ref_pass: GAAtariPolicy has no reference batch");
     if (ref_pass(h, n)) return -1;
@@ -1515,6 +1577,7 @@ extern "C" int dne_ref_pass(dne_handle *h, int n) {
 
 extern "C" int dne_get_bn(dne_handle *h, int n, float *out) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_get_bn");
     if (check_n(h, n)) return -1;
     HCHECK(h, hipStreamSynchronize(h->stream));
     HCHECK(h, hipMemcpy(out, h->bn, (size_t)n * 608 * sizeof(float), hipMemcpyDeviceToHost));
@@ -1525,6 +1588,7 @@ extern "C" int dne_get_bn(dne_handle *h, int n, float *out) {
 // moving_mean / moving_variance, policies.py:322-328): [n][608] = mean1[16] var1[16] mean2[32] var2[32] mean3[256] var3[256]
 extern "C" int dne_get_bn_moments(dne_handle *h, int n, float *out) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_get_bn_moments");
     if (check_n(h, n)) return -1;
     if (!es_like(h->L.kind)) return h->fail("dne_get_bn_moments: GAAtariPolicy has no batch norm");
     HCHECK(h, hipStreamSynchronize(h->stream));
@@ -1659,6 +1723,7 @@ static void launch_fc(dne_handle *h, const StepPlan &p, const WindowPlan &w, con
 
 extern "C" int dne_act(dne_handle *h, int n, int32_t *actions, float *logits) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_act");
     if (check_n(h, n)) return -1;
     const WindowPlan w = plan_window(h->k, h->facts(), StepPlan{}, n, n, 1, false);
     launch_forward(h, StepPlan{}, w, nullptr, nullptr, 1, false);
@@ -1672,6 +1737,7 @@ extern "C" int dne_act(dne_handle *h, int n, int32_t *actions, float *logits) {
 
 extern "C" int dne_debug_activations(dne_handle *h, int member, float *y1, float *y2, float *y3) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_debug_activations");
     if (member < 0 || member >= h->M) return h->fail("bad member");
     if (h->large) return h->fail("dne_debug_activations: LargeModel engines use dne_debug_activations_large");
     HCHECK(h, hipStreamSynchronize(h->stream));
@@ -1684,6 +1750,7 @@ extern "C" int dne_debug_activations(dne_handle *h, int member, float *y1, float
 // LargeModel: raw (bias added, pre-relu) outputs of conv1 [441][32], conv2 / conv3 [121][64] and the fc [512] after dne_act
 extern "C" int dne_debug_activations_large(dne_handle *h, int member, float *y1, float *y2, float *y3, float *y4) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_debug_activations_large");
     if (member < 0 || member >= h->M) return h->fail("bad member");
     if (!h->large) return h->fail("dne_debug_activations_large needs a DNE_KIND_GA_LARGE engine");
     HCHECK(h, hipStreamSynchronize(h->stream));
@@ -1927,12 +1994,138 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
     return 0;
 }
 
+
+// ------------------------------------------------------------------------------- the hard maze (csrc/maze.h)
+static int maze_check(std::string *err, const float *header8, const float *lines, int n_walls) {
+    if (!header8 || !lines) { *err = "maze: header or lines missing"; return -1; }
+    if (n_walls < 1 || n_walls > maze::MAX_WALLS) { *err = "maze: " + std::to_string(n_walls) + " walls, the kernel and the host function take 1.." + std::to_string(maze::MAX_WALLS); return -1; }
+    return 0;
+}
+
+static maze::Header maze_header(const float *h8) {
+    maze::Header m;
+    m.disable = h8[0]; m.steps = h8[1]; m.sx = h8[2]; m.sy = h8[3]; m.heading = h8[4]; m.gx = h8[5]; m.gy = h8[6]; m.reserved = h8[7];
+    return m;
+}
+
+extern "C" int dne_maze_set_walls(dne_handle *h, const float *header8, const float *lines, int n) {
+    DeviceGuard dg(h);
+    if (!h->maze) return h->fail("dne_maze_set_walls needs a DNE_KIND_MAZE engine (this one: kind %d)", h->L.kind);
+    if (maze_check(&h->err, header8, lines, n)) return -1;
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(h->maze_walls, lines, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice));
+    h->maze_hdr = maze_header(header8);
+    h->maze_nw = n;
+    return 0;
+}
+
+static maze::RolloutArgs maze_args(dne_handle *h, int first, int count, int tslimit) {
+    maze::RolloutArgs A{};
+    A.noise = h->noise; A.bases = h->bases; A.base_stride = h->base_stride;
+    A.m_slot = h->m_slot; A.m_off = h->m_off; A.m_scale = h->m_scale;
+    A.first = first; A.count = count; A.hdr = h->maze_hdr; A.walls = h->maze_walls; A.nw = h->maze_nw; A.tslimit = tslimit;
+    return A;
+}
+
+// members [0, n) set by dne_set_members, one whole episode each, one launch
+static int maze_eval(dne_handle *h, int n, int tslimit, float *returns, float *signreturns, int32_t *lengths, uint8_t *bc_out) {
+    if (h->maze_nw < 1) return h->fail("DNE_KIND_MAZE: no maze loaded (dne_maze_set_walls comes before an evaluation)");
+    if (tslimit <= 0) return h->fail("timestep limit must be positive");
+    if (bc_out && !h->bc) return h->fail("behaviour characterisations requested but the engine was created with record_bc = 0");
+    if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
+    const size_t bc_floats = (size_t)n * std::max(h->cfg.bc_max_steps, 1) * 2;
+    if (h->bc && bc_out) HCHECK(h, hipMemsetAsync(h->bc, 0, bc_floats * sizeof(float), h->stream));   // rows past an episode's length read as zero
+    maze::RolloutArgs A = maze_args(h, 0, n, tslimit);
+    A.ret = h->ret; A.sign = h->sign; A.len = h->len; A.xy = h->maze_xy;
+    A.bc = (float *)h->bc; A.bc_max_steps = h->bc ? std::max(h->cfg.bc_max_steps, 1) : 0;
+    HCHECK(h, hipEventRecord(h->ev_a, h->stream));
+    hipLaunchKernelGGL(maze::k_maze_rollout, dim3((n + 3) / 4), dim3(64), 0, h->stream, A);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipEventRecord(h->ev_b, h->stream));
+    HCHECK(h, hipMemcpyAsync(returns, h->ret, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (signreturns) HCHECK(h, hipMemcpyAsync(signreturns, h->sign, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipMemcpyAsync(lengths, h->len, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    if (bc_out) HCHECK(h, hipMemcpy(bc_out, h->bc, bc_floats * sizeof(float), hipMemcpyDeviceToHost));
+    h->maze_last_n = n;
+    float ms = 0;
+    HCHECK(h, hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
+    dne_profile &P = h->prof;
+    P = dne_profile{};
+    P.eval_ms = P.env_ms = ms;
+    P.fc_launches = 1;
+    for (int i = 0; i < n; i++) P.env_steps += lengths[i];
+    return 0;
+}
+
+extern "C" int dne_maze_final_state(dne_handle *h, int n, float *xy) {
+    DeviceGuard dg(h);
+    if (!h->maze) return h->fail("dne_maze_final_state needs a DNE_KIND_MAZE engine (this one: kind %d)", h->L.kind);
+    if (n < 1 || n > h->maze_last_n) return h->fail("dne_maze_final_state: %d members asked for, the last evaluation ran %d", n, h->maze_last_n);
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(xy, h->maze_xy, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the kernel once more for ONE of the current members, with every step written out: trace [min(tslimit, 400)][16] as dne_maze_rollout_host
+// writes it.  The accumulators of the last evaluation are left alone.
+extern "C" int dne_maze_debug_trace(dne_handle *h, int member, int tslimit, float *trace) {
+    DeviceGuard dg(h);
+    if (!h->maze) return h->fail("dne_maze_debug_trace needs a DNE_KIND_MAZE engine (this one: kind %d)", h->L.kind);
+    if (h->maze_nw < 1) return h->fail("DNE_KIND_MAZE: no maze loaded (dne_maze_set_walls comes before an evaluation)");
+    if (member < 0 || member >= (int)h->host_slot.size()) return h->fail("dne_maze_debug_trace: member %d, dne_set_members set %zu", member, h->host_slot.size());
+    if (tslimit <= 0 || !trace) return h->fail("dne_maze_debug_trace: bad arguments");
+    if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
+    const int steps = std::min(tslimit, (int)maze::EPISODE_STEPS);
+    DevBuf<float> d;
+    HCHECK(h, d.alloc((size_t)steps * maze::TRACE_W));
+    maze::RolloutArgs A = maze_args(h, member, 1, tslimit);
+    A.trace = d;
+    hipLaunchKernelGGL(maze::k_maze_rollout, dim3(1), dim3(64), 0, h->stream, A);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(trace, d, (size_t)steps * maze::TRACE_W * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the same header on the CPU: no handle, no GPU (like dne_debug_plan).  trace rows past an episode's length are not written.
+extern "C" int dne_maze_rollout_host(const float *theta, int n, const float *header8, const float *lines, int n_walls, int tslimit,
+                                     float *returns, int32_t *lengths, float *xy, float *trace) {
+    if (maze_check(&g_create_error, header8, lines, n_walls)) return -1;
+    if (n < 1 || tslimit <= 0 || !theta || !returns || !lengths || !xy) { g_create_error = "dne_maze_rollout_host: bad arguments"; return -1; }
+    const maze::Header m = maze_header(header8);
+    for (int i = 0; i < n; i++)
+        maze::rollout_host(theta + (size_t)i * maze::NPARAMS, m, lines, n_walls, tslimit, returns + i, lengths + i, xy + 2 * i,
+                           trace ? trace + (size_t)i * tslimit * maze::TRACE_W : nullptr);
+    return 0;
+}
+
+// test hooks on the CPU: the environment alone under n open-loop action sequences of T steps (rows [n][T][18], obs0 [n][11] or NULL), and
+// the forward pass alone for n (theta, observation) pairs (h1, h2 [n][16] after their relus, out [n][2])
+extern "C" int dne_maze_actions_host(const float *actions, int n, int T, const float *header8, const float *lines, int n_walls, float *rows,
+                                     float *obs0) {
+    if (maze_check(&g_create_error, header8, lines, n_walls)) return -1;
+    if (n < 1 || T < 1 || !actions || !rows) { g_create_error = "dne_maze_actions_host: bad arguments"; return -1; }
+    const maze::Header m = maze_header(header8);
+    for (int i = 0; i < n; i++)
+        maze::actions_host(actions + (size_t)i * T * 2, T, m, lines, n_walls, rows + (size_t)i * T * 18, obs0 ? obs0 + (size_t)i * maze::OBS : nullptr);
+    return 0;
+}
+
+extern "C" int dne_maze_forward_host(const float *theta, const float *obs, int n, float *h1, float *h2, float *out) {
+    if (n < 1 || !theta || !obs || !h1 || !h2 || !out) { g_create_error = "dne_maze_forward_host: bad arguments"; return -1; }
+    for (int i = 0; i < n; i++)
+        maze::forward_host(theta + (size_t)i * maze::NPARAMS, obs + (size_t)i * maze::OBS, h1 + (size_t)i * maze::HID, h2 + (size_t)i * maze::HID,
+                           out + (size_t)i * maze::ACT);
+    return 0;
+}
+
 extern "C" int dne_es_eval(dne_handle *h, const int64_t *idx, int n, float sigma, int tslimit, const uint32_t *env_seed,
                            float *returns_n2, float *signreturns_n2, int32_t *lengths_n2, uint8_t *bc) {
     DeviceGuard dg(h);
     // antithetic pairs over base slot 0: the ES kinds, and the GPU tree's LargeModel (its es.py runs over any model; no reference pass).
     // GAAtariPolicy's kernels take one member per group.
-    if (!es_like(h->L.kind) && !h->large)
+    if (!es_like(h->L.kind) && !h->large && !h->maze)
         return h->fail("dne_es_eval needs an engine of kind DNE_KIND_ES, DNE_KIND_ES_VBN or DNE_KIND_GA_LARGE (this one: %d)", h->L.kind);
     if (n <= 0 || 2 * n > h->M) return h->fail("%d pairs exceed max_members = %d", n, h->M);
     std::vector<int32_t> slot(2 * n, 0);
@@ -1950,6 +2143,7 @@ extern "C" int dne_es_eval(dne_handle *h, const int64_t *idx, int n, float sigma
         const double span = (double)(hi - lo) + (double)h->L.P;
         h->dense_scale = std::min(16.0, std::max(1.0, (double)h->noise_count / std::max(span, 1.0)));
     }
+    if (h->maze) return maze_eval(h, 2 * n, tslimit, returns_n2, signreturns_n2, lengths_n2, bc);   // (the episode is deterministic: env_seed is not read)
     return eval_core(h, 2 * n, 2, tslimit, env_seed, returns_n2, signreturns_n2, lengths_n2, bc);
 }
 
@@ -1957,6 +2151,10 @@ extern "C" int dne_eval_members(dne_handle *h, int n, int tslimit, const uint32_
                                 float *signreturns, int32_t *lengths, uint8_t *bc) {
     DeviceGuard dg(h);
     if (check_n(h, n)) return -1;
+    if (h->maze) {
+        if ((int)h->host_slot.size() < n) return h->fail("dne_eval_members: %d members asked for, dne_set_members set %zu", n, h->host_slot.size());
+        return maze_eval(h, n, tslimit, returns, signreturns, lengths, bc);
+    }
     return eval_core(h, n, 1, tslimit, env_seed, returns, signreturns, lengths, bc);
 }
 
@@ -2022,6 +2220,7 @@ static int build_chain(dne_handle *h, int slot, const int64_t *seeds, const floa
 // dqn.py:24-27, biases 0); with it set, genomes given with per-seed powers start as noise[idx0] * scale_by
 extern "C" int dne_ga_set_init_scale(dne_handle *h, const float *scale_by, size_t n) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_ga_set_init_scale");
     if (es_like(h->L.kind)) return h->fail("dne_ga_set_init_scale needs a GA engine");
     if (n != (size_t)h->L.P) return h->fail("dne_ga_set_init_scale: expected %d values, got %zu", h->L.P, n);
     if (!h->init_scale) HCHECK(h, h->alloc(&h->init_scale, n, "init_scale"));
@@ -2035,6 +2234,7 @@ extern "C" int dne_ga_set_init_scale(dne_handle *h, const float *scale_by, size_
 
 extern "C" int dne_ga_rebuild(dne_handle *h, int slot, const int64_t *seeds, int nseeds, float sigma, float *out_host) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_ga_rebuild");
     if (h->L.kind != DNE_KIND_GA) return h->fail("dne_ga_rebuild needs a GAAtariPolicy engine (LargeModel genomes carry per-seed powers: dne_ga_rebuild_powers)");
     if (slot < 0 || nseeds < 1) return h->fail("bad arguments");
     if (grow_bases(h, slot + 1)) return -1;
@@ -2049,6 +2249,7 @@ extern "C" int dne_ga_rebuild(dne_handle *h, int slot, const int64_t *seeds, int
 // the same for a genome ((idx0,), (idx1, power1), ...) of the gpu tree (base.py:118-139: compute_weights_from_seeds)
 extern "C" int dne_ga_rebuild_powers(dne_handle *h, int slot, const int64_t *seeds, const float *powers, int nseeds, float *out_host) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_ga_rebuild_powers");
     if (es_like(h->L.kind)) return h->fail("dne_ga_rebuild_powers needs a GA engine");
     if (slot < 0 || nseeds < 1 || !powers) return h->fail("bad arguments");
     if (grow_bases(h, slot + 1)) return -1;
@@ -2235,6 +2436,7 @@ static int ga_eval_impl(dne_handle *h, const int32_t *co, const int64_t *seeds, 
 extern "C" int dne_ga_eval(dne_handle *h, const int32_t *co, const int64_t *seeds, int n, float sigma, int tslimit,
                            const uint32_t *env_seed, float *returns, float *signreturns, int32_t *lengths, uint8_t *bc) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_ga_eval");
     return ga_eval_impl(h, co, seeds, nullptr, n, sigma, tslimit, env_seed, returns, signreturns, lengths, bc);
 }
 
@@ -2243,6 +2445,7 @@ extern "C" int dne_ga_eval(dne_handle *h, const int32_t *co, const int64_t *seed
 extern "C" int dne_ga_eval_powers(dne_handle *h, const int32_t *co, const int64_t *seeds, const float *powers, int n, int tslimit,
                                   const uint32_t *env_seed, float *returns, float *signreturns, int32_t *lengths, uint8_t *bc) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_ga_eval_powers");
     if (!powers) return h->fail("dne_ga_eval_powers: powers missing");
     return ga_eval_impl(h, co, seeds, powers, n, 0.0f, tslimit, env_seed, returns, signreturns, lengths, bc);
 }
@@ -2523,7 +2726,7 @@ static int check_records_host(dne_handle *h, int n_global) {
 // the gloo tests)
 extern "C" int dne_records_pack(dne_handle *h, int n_local, void *records_out) {
     DeviceGuard dg(h);
-    if ((!es_like(h->L.kind) && !h->large) || n_local < 1 || 2 * n_local > h->M) return h->fail("dne_records_pack: %d pairs", n_local);
+    if ((!es_like(h->L.kind) && !h->large && !h->maze) || n_local < 1 || 2 * n_local > h->M) return h->fail("dne_records_pack: %d pairs", n_local);
     if (rec_reserve(h, n_local, n_local)) return -1;
     hipLaunchKernelGGL(k_records_pack, dim3((n_local + 255) / 256), dim3(256), 0, h->stream, (const int64_t *)h->m_off, (const float *)h->ret,
                        (const float *)h->sign, (const int32_t *)h->len, n_local, n_local, (PairRecord *)h->rec_send);
@@ -2557,7 +2760,7 @@ extern "C" int dne_records_set(dne_handle *h, const void *records, int n_global)
 extern "C" int dne_allgather_results(dne_handle *h, int n_local, int n_global, void *records_out) {
     DeviceGuard dg(h);
     const int world = h->comm ? h->comm_size : 1, rank = h->comm ? h->comm_rank : 0;
-    if (!es_like(h->L.kind) && !h->large) return h->fail("dne_allgather_results needs an engine dne_es_eval accepts (DNE_KIND_ES, DNE_KIND_ES_VBN, DNE_KIND_GA_LARGE)");
+    if (!es_like(h->L.kind) && !h->large && !h->maze) return h->fail("dne_allgather_results needs an engine dne_es_eval accepts (DNE_KIND_ES, DNE_KIND_ES_VBN, DNE_KIND_GA_LARGE)");
     const int mine = n_global > rank ? (n_global - rank + world - 1) / world : 0;
     if (n_global < 1 || n_local != mine || 2 * n_local > h->M)
         return h->fail("dne_allgather_results: rank %d of %d holds %d pairs, a population of %d pairs gives it %d", rank, world, n_local, n_global, mine);
@@ -2702,6 +2905,7 @@ extern "C" int dne_archive_clear(dne_handle *h) {
 
 extern "C" int dne_archive_append(dne_handle *h, const uint8_t *bc, int bc_len, int dim) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_archive_append");
     if (bc_len < 1 || dim < 1) return h->fail("dne_archive_append: empty entry");
     if (h->arch_dim && dim != h->arch_dim) return h->fail("dne_archive_append: entry width %d, archive holds %d", dim, h->arch_dim);
     HCHECK(h, hipStreamSynchronize(h->stream));
@@ -2805,6 +3009,7 @@ static int novelty_run(dne_handle *h, const uint8_t *bcs, const int32_t *lengths
 
 extern "C" int dne_novelty_knn(dne_handle *h, const uint8_t *bcs, const int32_t *lengths, int n, int dim, int k, double *out) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_novelty_knn");
     if (n < 1 || dim < 1 || k < 1) return h->fail("dne_novelty_knn: bad sizes n = %d dim = %d k = %d", n, dim, k);
     if (!bcs) {
         if (!es_like(h->L.kind) || !h->bc || h->cfg.bc_final_only) return h->fail("dne_novelty_knn on the recorded trajectories needs an ES engine created with record_bc = 1 (full trajectories)");
@@ -2825,6 +3030,7 @@ extern "C" int dne_novelty_knn(dne_handle *h, const uint8_t *bcs, const int32_t 
 extern "C" int dne_novelty(dne_handle *h, const uint8_t *archive, const int32_t *alen, int narch, const uint8_t *bc,
                            int bc_len, int dim, int k, double *out) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_novelty");
     if (bc_len < 1 || dim < 1 || k < 1) return h->fail("dne_novelty: bad sizes");
     if (archive && archive_load(h, archive, alen, narch, dim)) return -1;
     narch = (int)h->arch_len_host.size();
@@ -2836,6 +3042,7 @@ extern "C" int dne_novelty(dne_handle *h, const uint8_t *archive, const int32_t 
 extern "C" int dne_novelty_batch(dne_handle *h, const uint8_t *archive, const int32_t *alen, int narch, int n,
                                  const int32_t *lengths, int k, double *out) {
     DeviceGuard dg(h);
+    MAZE_REFUSE(h, "dne_novelty_batch");
     if (!es_like(h->L.kind) || !h->bc || h->cfg.bc_final_only) return h->fail("dne_novelty_batch needs an ES engine created with record_bc = 1 (full trajectories)");
     if (check_n(h, n)) return -1;
     if (k < 1) return h->fail("dne_novelty_batch: bad sizes");

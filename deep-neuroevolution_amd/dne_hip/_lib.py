@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("DNE_LIB_PATH") or os.path.join(_CSRC, "libdne_hip.so"
 
 KIND_ES, KIND_GA, KIND_GA_LARGE = 0, 1, 2   # DNE_KIND_* (include/dne_hip.h); 2 = the GPU tree's LargeModel (models/dqn.py:39-47)
 KIND_ES_VBN = 3   # the GPU tree's ModelVirtualBN in its own flat layout (models/batchnorm.py:52-123): the ES kind's network and entry points
+KIND_MAZE = 4     # the GPU tree's hard maze under SimpleClassifier (gym_tensorflow/maze/, models/simple.py:29-35): whole episodes in one kernel (csrc/maze.h)
+MAZE_OBS, MAZE_STEPS, MAZE_TRACE_W, MAZE_MAX_WALLS = 11, 400, 16, 64   # observation width, tf_maze.cpp's episode length, floats per trace row, walls the kernel takes
 ES_KINDS = (KIND_ES, KIND_ES_VBN)   # virtual batch norm over a reference batch, antithetic pairs
 PROC_MODES = {"centered_rank": 0, "sign": 1, "centered_sign_rank": 2}
 OPT_KINDS = {"adam": 0, "sgd": 1}
@@ -71,7 +73,7 @@ class Profile(C.Structure):
 
 def build(force=False):
     """Compile libdne_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dne_hip.h"))
     if os.environ.get("DNE_LIB_PATH"):
         # another build of the same ABI was asked for by name: `make` only knows the in-tree library, so running it here would
@@ -130,12 +132,77 @@ def debug_plan(kind, nact, total, gsize, whole_eval=False, **facts):
         setattr(f, k, v)
     rows, nsub = (WindowPlan * 4)(), C.c_int(0)
     rc = load().dne_debug_plan(int(kind), int(nact), C.byref(f), int(total), int(gsize), rows, 4, C.byref(nsub), int(bool(whole_eval)))
+    if rc < 0:
+        raise DneError(load().dne_last_error(None).decode())
     return rc if whole_eval else list(rows[:nsub.value])
 
 
 def debug_knob(kind, nact, name):
     """the value dne_create would read for one DNE_* knob under the current environment (-1: no such knob)"""
     return load().dne_debug_knob(int(kind), int(nact), name.encode())
+
+
+def load_maze(path):
+    """A maze file of the reference (maze.h:468-495: disable, steps, number of lines, start x y, heading, goal x y, poi x y, then the lines)
+    -> (header8 float32 [8] = disable, steps, start x, start y, heading, goal x, goal y, 0; lines float32 [n][4]).  The point of interest
+    feeds a radar the policy never observes and is dropped."""
+    with open(path) as f:
+        tok = f.read().split()
+    if len(tok) < 10:
+        raise DneError("%s: not a maze file (%d numbers)" % (path, len(tok)))
+    vals = [float(t) for t in tok]
+    n = int(vals[2])
+    if n < 1 or len(vals) != 10 + 4 * n:
+        raise DneError("%s: announces %d lines and holds %d numbers (10 + 4 per line expected)" % (path, n, len(vals)))
+    header = np.array([vals[0], vals[1], vals[3], vals[4], vals[5], vals[6], vals[7], 0.0], np.float32)
+    return header, np.array(vals[10:], np.float32).reshape(n, 4)
+
+
+def _maze_args(header, lines):
+    header = _arr(header, np.float32).reshape(-1); lines = _arr(lines, np.float32).reshape(-1, 4)
+    if header.size != 8:
+        raise DneError("maze header: 8 floats expected, got %d" % header.size)
+    return header, lines
+
+
+def _ck_host(rc):
+    if rc != 0:
+        raise DneError(load().dne_last_error(None).decode())
+
+
+def maze_rollout_host(theta, header, lines, tslimit=MAZE_STEPS, want_trace=False):
+    """dne_maze_rollout_host: csrc/maze.h on the CPU (no GPU, no handle) for thetas [n][498] -> returns [n], lengths [n], final xy [n][2]
+    (+ trace [n][tslimit][16] with want_trace: the observation after each step, then x, y, heading, speed, ang_vel; rows past the length are 0)"""
+    theta = _arr(theta, np.float32).reshape(-1, 498)
+    header, lines = _maze_args(header, lines)
+    n = theta.shape[0]
+    ret = np.empty(n, np.float32); ln = np.empty(n, np.int32); xy = np.empty((n, 2), np.float32)
+    trace = np.zeros((n, int(tslimit), MAZE_TRACE_W), np.float32) if want_trace else None
+    _ck_host(load().dne_maze_rollout_host(_ptr(theta, C.c_float), n, _ptr(header, C.c_float), _ptr(lines, C.c_float), int(lines.shape[0]),
+                                          int(tslimit), _ptr(ret, C.c_float), _ptr(ln, C.c_int32), _ptr(xy, C.c_float), _ptr(trace, C.c_float)))
+    return (ret, ln, xy, trace) if want_trace else (ret, ln, xy)
+
+
+def maze_actions_host(actions, header, lines):
+    """dne_maze_actions_host: the environment alone under open-loop actions [n][T][2] -> (rows [n][T][18] = obs[11], x, y, heading, speed,
+    ang_vel, collisions, reward after each step; obs0 [n][11] after reset)"""
+    actions = _arr(actions, np.float32)
+    n, T = actions.shape[0], actions.shape[1]
+    header, lines = _maze_args(header, lines)
+    rows = np.empty((n, T, 18), np.float32); obs0 = np.empty((n, MAZE_OBS), np.float32)
+    _ck_host(load().dne_maze_actions_host(_ptr(actions, C.c_float), n, T, _ptr(header, C.c_float), _ptr(lines, C.c_float), int(lines.shape[0]),
+                                          _ptr(rows, C.c_float), _ptr(obs0, C.c_float)))
+    return rows, obs0
+
+
+def maze_forward_host(theta, obs):
+    """dne_maze_forward_host: the policy alone, thetas [n][498] on observations [n][11] -> (h1 [n][16], h2 [n][16], out [n][2])"""
+    theta = _arr(theta, np.float32).reshape(-1, 498); obs = _arr(obs, np.float32).reshape(-1, MAZE_OBS)
+    n = theta.shape[0]
+    assert obs.shape[0] == n
+    h1 = np.empty((n, 16), np.float32); h2 = np.empty((n, 16), np.float32); out = np.empty((n, 2), np.float32)
+    _ck_host(load().dne_maze_forward_host(_ptr(theta, C.c_float), _ptr(obs, C.c_float), n, _ptr(h1, C.c_float), _ptr(h2, C.c_float), _ptr(out, C.c_float)))
+    return h1, h2, out
 
 
 def _ptr(a, t):
@@ -168,6 +235,7 @@ class Engine:
         if rc != 0:
             raise DneError(self.lib.dne_last_error(None).decode())
         self.P = self.lib.dne_num_params(self.kind, self.n_actions)
+        self.record_bc = bool(record_bc)
         self.noise_count = 0
         self.comm_size = 1
 
@@ -303,6 +371,8 @@ class Engine:
     def _bc_buf(self, n, want):
         if not want:
             return None
+        if self.kind == KIND_MAZE:   # the navigator's (x, y) after every step
+            return np.zeros((n, max(self.bc_max_steps, 1), 2), np.float32)
         if self.kind in ES_KINDS and not self.bc_final_only:
             return np.zeros((n, self.bc_max_steps, RAM_BYTES), np.uint8)
         return np.zeros((n, RAM_BYTES), np.uint8)
@@ -339,6 +409,24 @@ class Engine:
                                       _ptr(seeds, C.c_uint32), _ptr(ret, C.c_float), _ptr(sg, C.c_float), _ptr(ln, C.c_int32),
                                       _ptr(bc, C.c_uint8)))
         return (ret, sg, ln, bc) if want_bc else (ret, sg, ln)
+
+    # ---- the hard maze (KIND_MAZE)
+    def maze_set_walls(self, header, lines):
+        """the maze every later evaluation runs in: load_maze(path)'s header [8] and lines [n][4], 1 <= n <= 64"""
+        header, lines = _maze_args(header, lines)
+        self._ck(self.lib.dne_maze_set_walls(self.h, _ptr(header, C.c_float), _ptr(lines, C.c_float), int(lines.shape[0])))
+
+    def maze_final_state(self, n):
+        """MazeFinalState: final (x, y) of the first n members of the last evaluation, [n][2]"""
+        xy = np.empty((int(n), 2), np.float32)
+        self._ck(self.lib.dne_maze_final_state(self.h, int(n), _ptr(xy, C.c_float)))
+        return xy
+
+    def maze_debug_trace(self, member, tslimit=MAZE_STEPS):
+        """the kernel once more for one current member, every step written out: [min(tslimit, 400)][16] as maze_rollout_host's trace"""
+        out = np.empty((min(int(tslimit), MAZE_STEPS), MAZE_TRACE_W), np.float32)
+        self._ck(self.lib.dne_maze_debug_trace(self.h, int(member), int(tslimit), _ptr(out, C.c_float)))
+        return out
 
     # ---- gpu-tree genomes: ((idx0,), (idx1, power1), ...)
     def ga_set_init_scale(self, scale_by):

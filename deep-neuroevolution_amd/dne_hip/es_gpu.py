@@ -25,6 +25,13 @@ it is ModelVirtualBN); a resume under another model or P fails and names both.  
 Not built: every other model.  `Model` (dqn.py:24-36) is the network of DNE_KIND_GA, whose kernels take one member per group: dne_es_eval on
 that kind is a tested refusal (tests/test_gpu_edges.py::test_refusals).  `ModelBN`, `SmallDQN` and the rest have no engine kind.
 
+exp['game'] == 'maze' (gym_tensorflow.make's second environment, gym_tensorflow/maze/) with exp['model'] == 'SimpleClassifier' (models/simple.py:29-35)
+runs on a DNE_KIND_MAZE engine: a whole 400-step episode per member inside one kernel (csrc/maze.h), no reference batch, no environment seeds (the
+episode is deterministic; the seeds are still drawn, so the stream stays in step with the other kinds).  The maze file is exp['maze_file'], else hard_maze.txt
+in the working directory (tf_maze.py:28), else the copy of the reference's file under tests/golden; theta starts as TrainingState.initialize does, noise.get(idx, 498) * policies.simple_scale_by() with
+idx the stream's first draw; 'env_default' means 400 steps (tf_maze.py:32-33).  The game is recorded in snapshot.pkl (a snapshot without it is an Atari
+run); a resume under another game fails and names both.  SimpleClassifier on an Atari game and the Atari models on the maze are refused.
+
 Where the arithmetic lives: ranks, sum_i w_i * noise[idx_i] / 2N, -g + l2coeff * theta and the optimizer step are dne_es_update on the device
 (the same formulas as es_distributed: es.py:227-246 here = es_distributed/es.py:281-301).  The GPU tree's SGD keeps v = momentum * v + g
 (neuroevolution/optimizers.py:49-51) where es_distributed keeps (1 - momentum) * g: with u = (1 - momentum) * v that is the engine's SGD at
@@ -43,6 +50,19 @@ from .ga_gpu import Offspring, Schedule, model_scale_by
 
 # exp['model'] (es.py:144): neuroevolution/models/batchnorm.py:52 (in either flat layout, FLAT_LAYOUTS) and models/dqn.py:39
 MODEL_KINDS = {'ModelVirtualBN': _lib.KIND_ES, 'LargeModel': _lib.KIND_GA_LARGE}
+MAZE_MODEL = 'SimpleClassifier'          # the one model of exp['game'] == 'maze' (neuroevolution/models/simple.py:29-35)
+MAZE_FILE = 'hard_maze.txt'              # tf_maze.py:28 names the file so, relative to the working directory; exp['maze_file'] overrides it
+_MAZE_FIXTURE = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), 'tests', 'golden', 'hard_maze.txt')
+
+
+def maze_file(exp):
+    """the maze of a run: exp['maze_file'], else MAZE_FILE in the working directory, else the copy of the reference's file among the test fixtures"""
+    path = exp.get('maze_file', MAZE_FILE)
+    if os.path.exists(path):
+        return path
+    if 'maze_file' not in exp and os.path.exists(_MAZE_FIXTURE):
+        return _MAZE_FIXTURE
+    raise FileNotFoundError("maze file {!r} not found (exp['maze_file'] names it; the reference ships gym_tensorflow/maze/hard_maze.txt)".format(path))
 FLAT_LAYOUTS = {'es_distributed': _lib.KIND_ES, 'native': _lib.KIND_ES_VBN}   # exp['flat_layout'] -> the engine kind that runs it
 
 
@@ -61,6 +81,7 @@ class TrainingState(object):
         if adaptive:
             self.tslimit_max = limit_max
         self.flat_layout = 'es_distributed'   # FLAT_LAYOUTS key of the run (main sets it); a snapshot without it predates the choice
+        self.game = None                      # exp['game'] of a maze run ('maze'); None: an Atari game (a snapshot without it predates the maze)
         self.model = 'ModelVirtualBN'         # MODEL_KINDS key of the run (main sets it); a snapshot without it predates LargeModel
         self.num_params = None
         self.theta = None
@@ -92,10 +113,15 @@ def engine_optimizer(opt):
     return opt['type'], step, first, beta2, eps
 
 
+def _env_limit(engine):
+    """the environment's own episode bound: env_default_timestep_cutoff of the maze (tf_maze.py:32-33), gym's TimeLimit for Atari"""
+    return _lib.MAZE_STEPS if engine.kind == _lib.KIND_MAZE else _lib.ENV_MAX_EPISODE_STEPS
+
+
 def _episodes_of_theta(engine, n, tslimit, rs):
     """n episodes of the unperturbed theta (monitor_eval_repeated([(theta, 0)], ...), es.py:190, 249): pairs at mutation power 0 --
     theta + 0 * eps twice, every episode under its own environment seed"""
-    limit = _lib.ENV_MAX_EPISODE_STEPS if tslimit is None else min(int(tslimit), _lib.ENV_MAX_EPISODE_STEPS)
+    limit = _env_limit(engine) if tslimit is None else min(int(tslimit), _env_limit(engine))
     rets, lens = [], []
     left = int(n)
     while left > 0:
@@ -115,13 +141,31 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
         raise NotImplementedError("load_from (es.py:164-171: a ga_legacy genome as the first theta) is not built")
     n_pairs = exp['population_size'] // 2
     asked = exp['model'] if engine is None else exp.get('model')   # the caller's engine decides; a name given with it must agree
-    if asked is not None and asked not in MODEL_KINDS:
+    maze = exp.get('game') == 'maze' or (engine is not None and engine.kind == _lib.KIND_MAZE)
+    if maze:                                                        # gym_tensorflow.make(game='maze'): the hard maze under SimpleClassifier
+        if exp.get('game') != 'maze':
+            raise ValueError("game {!r} asked for, the engine passed in (kind {}) runs 'maze'".format(exp.get('game'), engine.kind))
+        if engine is not None and engine.kind != _lib.KIND_MAZE:
+            raise ValueError("game 'maze' asked for, the engine passed in is of kind {} (KIND_MAZE is {})".format(engine.kind, _lib.KIND_MAZE))
+        if asked is not None and asked != MAZE_MODEL:
+            raise NotImplementedError("model {!r} on game 'maze': this loop runs {!r} there".format(asked, MAZE_MODEL))
+    elif asked == MAZE_MODEL:
+        raise NotImplementedError("model {!r} on game {!r}: it runs on game 'maze' only".format(asked, exp.get('game')))
+    if not maze and asked is not None and asked not in MODEL_KINDS:
         raise NotImplementedError("model {!r}: this loop runs {}".format(asked, sorted(MODEL_KINDS)))
-    large = (engine.kind if engine is not None else MODEL_KINDS[asked]) == _lib.KIND_GA_LARGE
-    model = 'LargeModel' if large else 'ModelVirtualBN'
+    large = not maze and (engine.kind if engine is not None else MODEL_KINDS[asked]) == _lib.KIND_GA_LARGE
+    model = MAZE_MODEL if maze else 'LargeModel' if large else 'ModelVirtualBN'
     if asked is not None and asked != model:
         raise ValueError("model {!r} asked for, the engine passed in (kind {}) runs {!r}".format(asked, engine.kind, model))
-    if large:                                                       # one flat layout, the model's own; no reference batch
+    if maze:                                                        # one flat layout, no reference batch, the walls instead
+        layout = 'native'
+        if exp.get('flat_layout', layout) != layout:
+            raise ValueError("flat_layout {!r}: SimpleClassifier has one layout, 'native'".format(exp['flat_layout']))
+        if engine is None:
+            engine = _lib.Engine(_lib.KIND_MAZE, 2, max_members=2 * n_pairs)
+        scale_by = policies.simple_scale_by()
+        engine.maze_set_walls(*_lib.load_maze(maze_file(exp)))
+    elif large:                                                       # one flat layout, the model's own; no reference batch
         layout = 'native'
         if exp.get('flat_layout', layout) != layout:
             raise ValueError("flat_layout {!r}: LargeModel has one layout, 'native'".format(exp['flat_layout']))
@@ -147,24 +191,29 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
         with open(os.path.join(log_dir, 'snapshot.pkl'), 'rb') as file:
             state = pickle.load(file)
         tlogger.log("Loaded iteration {} from {}".format(state.it, log_dir))
+        was_game = getattr(state, 'game', None)
+        if (was_game == 'maze') != maze:
+            raise ValueError("snapshot.pkl in {} holds game {!r}; this run is game {!r}".format(
+                log_dir, was_game if was_game is not None else 'an Atari game', exp.get('game')))
         was_model = getattr(state, 'model', 'ModelVirtualBN')
-        if was_model != model or (large and int(np.asarray(state.theta).size) != engine.P):
+        if was_model != model or ((large or maze) and int(np.asarray(state.theta).size) != engine.P):
             raise ValueError("snapshot.pkl in {} holds model {!r} with P = {}; this run is model {!r} with P = {}".format(
                 log_dir, was_model, int(np.asarray(state.theta).size), model, engine.P))
         was = (getattr(state, 'flat_layout', 'es_distributed'), int(np.asarray(state.theta).size))
-        if not large and was != (layout, engine.P):
+        if not large and not maze and was != (layout, engine.P):
             raise ValueError("snapshot.pkl in {} holds flat_layout {!r} with P = {}; this run is flat_layout {!r} with P = {}".format(
                 log_dir, was[0], was[1], layout, engine.P))
     except FileNotFoundError:
         state = TrainingState(exp)
-        if large or layout == 'native':                             # es.py:173 -> es.py:73-75 -> model.randomize(rs, noise), base.py:123-141
+        if maze or large or layout == 'native':                             # es.py:173 -> es.py:73-75 -> model.randomize(rs, noise), base.py:123-141
             idx = noise.sample_index(rs, engine.P)
-            state.theta = noise.get(idx, engine.P) * (scale_by if large else policies.vbn_scale_by(engine.n_actions))
+            state.theta = noise.get(idx, engine.P) * (scale_by if large or maze else policies.vbn_scale_by(engine.n_actions))
         else:
             state.theta = policies.xavier_flat(engine.n_actions, seed)   # es.py:173: state.initialize(rs, noise, worker.model)
     state.flat_layout, state.num_params, state.model = layout, engine.P, model
+    state.game = 'maze' if maze else None
     state.push(engine)
-    if not large:                                                   # ModelVirtualBN.requires_ref_batch (batchnorm.py:60-62); LargeModel has none
+    if not large and not maze:                                                   # ModelVirtualBN.requires_ref_batch (batchnorm.py:60-62); LargeModel has none
         env = policies.HipAtariEnv(engine, seed=seed)
         ref = np.stack(get_ref_batch(env, batch_size=engine.ref_count, random_stream=np.random.RandomState(seed)))
         engine.set_ref_batch(np.rint(ref * 255.0).astype(np.uint8))
@@ -182,10 +231,10 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
         power = state.sample(state.mutation_power)
         idx = np.array([noise.sample_index(rs, engine.P) for _ in range(n_pairs)], np.int64)
         seeds = rs.randint(0, 2 ** 32, size=2 * n_pairs, dtype=np.uint64).astype(np.uint32)
-        limit = _lib.ENV_MAX_EPISODE_STEPS if state.tslimit is None else min(int(state.tslimit), _lib.ENV_MAX_EPISODE_STEPS)
+        limit = _env_limit(engine) if state.tslimit is None else min(int(state.tslimit), _env_limit(engine))
         rets, sgn, lens = engine.es_eval(idx, power, limit, seeds)
         results = [Offspring(int(i), [float(r[0]), float(r[1])], [int(l[0]), int(l[1])]) for i, r, l in zip(idx, rets, lens)]
-        state.num_frames += int(np.sum(lens)) * 4
+        state.num_frames += int(np.sum(lens)) * (1 if maze else 4)                  # (the maze has no frame skip: a step is a frame)
         state.it += 1
         rewards = np.array([b for a in results for b in a.rewards])
         timesteps_this_iter = int(sum(a.training_steps for a in results))

@@ -37,6 +37,10 @@ def flat_layout(kind, nact):
         add("layer2/conv2/w", (4, 4, 16, 32)); add("layer2/BatchNorm/b", (1, 1, 1, 32))
         add("layer3/fc/w", (3872, 256)); add("layer3/BatchNorm/b", (1, 256))
         add("layer4/out/w", (256, nact)); add("layer4/out/b", (1, nact))
+    elif kind == _lib.KIND_MAZE:       # the GPU tree's SimpleClassifier on the maze's 11 inputs, models/simple.py:29-35 (nact = 2: the raw outputs are the action)
+        add("fc1/w", (11, 16)); add("fc1/b", (1, 16))
+        add("fc2/w", (16, 16)); add("fc2/b", (1, 16))
+        add("out/w", (16, nact)); add("out/b", (1, nact))
     elif kind == _lib.KIND_GA_LARGE:   # the GPU tree's LargeModel, gpu_implementation/neuroevolution/models/dqn.py:39-47 (creation order, base.py:35-41)
         add("conv1/w", (8, 8, 4, 32)); add("conv1/b", (1, 1, 1, 32))
         add("conv2/w", (4, 4, 32, 64)); add("conv2/b", (1, 1, 1, 64))
@@ -60,6 +64,18 @@ def vbn_scale_by(nact):
     for name, (off, shape) in spec.items():
         if name.endswith('/w'):
             sb[off:off + int(np.prod(shape))] = np.float32(1.0 / np.sqrt(np.prod(shape[:-1])))
+    return sb
+
+
+def simple_scale_by():
+    """scale_by of SimpleClassifier on the hard maze (models/simple.py:29-35 over dqn.Model, dqn.py:25-27): std / sqrt(prod(shape[:-1])) for each
+    w -- 1/sqrt(11), 1/4 and (std = 0.1 for the out layer) 0.1/4 --, 0 for each b.  fp32, in flat order; theta_0 = noise.get(idx, 498) * scale_by."""
+    spec, P = flat_layout(_lib.KIND_MAZE, 2)
+    sb = np.zeros(P, np.float32)
+    for name, (off, shape) in spec.items():
+        if name.endswith('/w'):
+            std = 0.1 if name.startswith('out') else 1.0
+            sb[off:off + int(np.prod(shape))] = np.float32(std / np.sqrt(np.prod(shape[:-1])))
     return sb
 
 

@@ -31,6 +31,13 @@ extern "C" {
                              (tensors in creation order, models/base.py:35-44, 166-178).  The ES kind's network, evaluation and entry points
                              (virtual batch norm, antithetic pairs, dne_es_eval / dne_es_update); no conv / fc biases, no BN gamma: each
                              BatchNorm/b is the shift after normalisation.  P = 1003824 + 257 * n_actions */
+#define DNE_KIND_MAZE 4 /* the GPU tree's hard maze (gym_tensorflow/maze/) under SimpleClassifier (models/simple.py:29-35: dense 11 -> 16 -> 16 -> 2,
+                           498 parameters); n_actions = 2, the raw outputs are the action.  A whole episode (400 steps) runs inside one kernel
+                           (csrc/maze.h): dne_maze_set_walls, then dne_set_members + dne_eval_members or dne_es_eval (pairs (2i, 2i+1) over base slot 0,
+                           no reference pass; env_seed is accepted and ignored: the episode is deterministic).  returns = -distance to the goal after
+                           step 400, 0 under a shorter tslimit; bc (record_bc): float (x, y) after every step, [members][bc_max_steps][2].
+                           The P-generic calls work unchanged (dne_es_update, dne_weighted_sum, the optimizer calls, dne_records_pack / _set,
+                           dne_es_update_gathered); dne_ga_*, dne_ref_pass, dne_env_*, dne_novelty*, dne_act and dne_debug_plan refuse the kind. */
 #define DNE_OB_BYTES (84 * 84 * 4)
 #define DNE_RAM_BYTES 128
 #define DNE_BN_FLOATS 608
@@ -172,7 +179,7 @@ int dne_debug_knob(int kind, int n_actions, const char *name);
 
 /* ---- A1-A7: whole-batch evaluation ------------------------------------------------------------------ */
 /* es.py:411-426 for n pairs at once: returns_n2/signreturns_n2/lengths_n2 are [n][2] like Result (es.py:18-23).
- * Engines: DNE_KIND_ES, DNE_KIND_ES_VBN (reference pass first) and DNE_KIND_GA_LARGE (theta = base slot 0, no reference pass);
+ * Engines: DNE_KIND_ES, DNE_KIND_ES_VBN (reference pass first), DNE_KIND_GA_LARGE (theta = base slot 0, no reference pass) and DNE_KIND_MAZE (see there);
  * DNE_KIND_GA refuses (its kernels take one member per group).  DNE_KIND_GA_LARGE has no behaviour trajectories: bc = final RAM [2n][128].
  * env_seed[2n]: per-episode environment seed (noop count = 1 + seed % 30).  bc (may be NULL, needs record_bc):
  * [2n][bc_max_steps][128] RAM trajectories (policies.py:410,418) */
@@ -278,6 +285,27 @@ int dne_novelty_batch(dne_handle *h, const uint8_t *archive, const int32_t *arch
  * scratch and a selection kernel sums each member's k smallest in ascending order: only the n results cross PCIe.
  * dne_novelty (n = 1, host rows) and dne_novelty_batch (the recorded trajectories) are this call behind their own checks. */
 int dne_novelty_knn(dne_handle *h, const uint8_t *bcs, const int32_t *lengths, int n, int dim, int k, double *out);
+
+/* ---- the hard maze (DNE_KIND_MAZE; csrc/maze.h) ---------------------------------------------------------------
+ * header8 = disable, steps, start x, start y, heading, goal x, goal y, 0 as the maze file gives them (`steps` and `heading` travel with the file
+ * and are not read: tf_maze.cpp ends an episode after 400 steps and reset() starts at heading 0); lines [n][4] = wall segments ax, ay, bx, by.
+ * n outside 1..64 is refused.  An evaluation before dne_maze_set_walls is an error. */
+int dne_maze_set_walls(dne_handle *h, const float *header8, const float *lines, int n);
+/* MazeFinalState (tf_maze.cpp:154-200): the navigators' final (x, y) of the last evaluation's first n members -- the behaviour characterisation of NS-ES on the maze */
+int dne_maze_final_state(dne_handle *h, int n, float *xy /*[n][2]*/);
+/* The same source on the CPU: n thetas, one episode each.  Needs no handle and no GPU (like dne_debug_plan; dne_last_error(NULL) has the text of a
+ * failure).  trace: [n][tslimit][16] or NULL; row t = the observation after step t (11 floats: what the policy sees next), then x, y, heading, speed,
+ * ang_vel.  Rows past an episode's length (min(tslimit, 400)) are not written. */
+int dne_maze_rollout_host(const float *theta /*[n][498]*/, int n, const float *header8, const float *lines, int n_walls, int tslimit,
+                          float *returns, int32_t *lengths, float *xy /*[n][2]*/, float *trace);
+/* the device twin of that trace for one of the current members (dne_set_members / dne_es_eval): the kernel once more, every step written out;
+ * trace [min(tslimit, 400)][16].  The last evaluation's results stay as they are. */
+int dne_maze_debug_trace(dne_handle *h, int member, int tslimit, float *trace);
+/* CPU test hooks, no handle: the environment alone under n open-loop action sequences (actions [n][T][2]; rows [n][T][18] = obs[11], x, y, heading,
+ * speed, ang_vel, collisions, reward after each step; obs0 [n][11] or NULL = the observation after reset), and the forward pass alone for n
+ * (theta, observation) pairs (h1, h2 [n][16] after their relus, out [n][2]) */
+int dne_maze_actions_host(const float *actions, int n, int T, const float *header8, const float *lines, int n_walls, float *rows, float *obs0);
+int dne_maze_forward_host(const float *theta, const float *obs, int n, float *h1, float *h2, float *out);
 
 #ifdef __cplusplus
 }
