@@ -980,6 +980,11 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         g_create_error = "dne_create: DNE_KIND_MAZE has 2 outputs (the navigator's turn and speed), n_actions " + std::to_string(cfg->n_actions) + " is refused";
         return -1;
     }
+    if (cfg->policy_kind == DNE_KIND_MAZE && cfg->bc_final_only) {
+        g_create_error = "dne_create: bc_final_only is not available on a DNE_KIND_MAZE engine (kind 4): its bc rows are (x, y) after every step; "
+                         "dne_maze_final_state has the final position of every member";
+        return -1;
+    }
     dne_handle *h = new dne_handle();
     h->cfg = *cfg;
     auto bail = [&](int) { g_create_error = h->err; delete h; return -1; };
@@ -2117,6 +2122,27 @@ extern "C" int dne_maze_forward_host(const float *theta, const float *obs, int n
     for (int i = 0; i < n; i++)
         maze::forward_host(theta + (size_t)i * maze::NPARAMS, obs + (size_t)i * maze::OBS, h1 + (size_t)i * maze::HID, h2 + (size_t)i * maze::HID,
                            out + (size_t)i * maze::ACT);
+    return 0;
+}
+
+// the math probe (maze.h: math_probe) on the CPU and, one thread per input, on the device: out [n][2] doubles
+extern "C" int dne_maze_math_host(int fn, const double *x, int n, double *out) {
+    if (fn < 0 || fn >= maze::MATH_FNS || n < 1 || !x || !out) { g_create_error = "dne_maze_math_host: bad arguments (fn 0..3, n >= 1)"; return -1; }
+    for (int i = 0; i < n; i++) maze::math_probe(fn, x[i], out + 2 * (size_t)i);
+    return 0;
+}
+
+extern "C" int dne_maze_debug_math(dne_handle *h, int fn, const double *x, int n, double *out) {
+    DeviceGuard dg(h);
+    if (!h->maze) return h->fail("dne_maze_debug_math needs a DNE_KIND_MAZE engine (this one: kind %d)", h->L.kind);
+    if (fn < 0 || fn >= maze::MATH_FNS || n < 1 || !x || !out) return h->fail("dne_maze_debug_math: bad arguments (fn 0..3, n >= 1)");
+    DevBuf<double> dx, dout;
+    HCHECK(h, dx.alloc((size_t)n)); HCHECK(h, dout.alloc(2 * (size_t)n));
+    HCHECK(h, hipMemcpy(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(maze::k_maze_math, dim3((n + 255) / 256), dim3(256), 0, h->stream, fn, (const double *)dx, n, (double *)dout);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(out, dout, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 

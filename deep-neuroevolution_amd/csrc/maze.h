@@ -35,10 +35,12 @@ struct State { float x, y, heading, speed, ang_vel; int collide, collisions; };
 // ---- trigonometry ---------------------------------------------------------------------------------------------------------------------
 // sin and cos of |x| <= 3 pi: k = round(x * 2 / pi), r = x - k * pi/2 in two fma steps (the first product is exact: PIO2_HI keeps 33 bits and
 // |k| <= 6), then the Taylor series of sin and cos on |r| <= pi/4 (truncation below 1e-19 and 3e-18), Horner in fma.
+// Outside the contract (a NaN heading after a NaN action, an infinity) k is 0 and the result is NaN through r: a NaN or an infinity is never
+// cast to int, which C++ leaves undefined and on which x86 (INT_MIN) and gfx950 (0, saturation) answer differently.
 MZ_HD SinCosD sincos_d(double x) {
     const double PIO2_HI = 1.57079632673412561417e+00, PIO2_LO = 6.07710050650619224932e-11;
     const double t = x * 6.36619772367581382433e-01;
-    const int k = (int)(t + (t < 0.0 ? -0.5 : 0.5));
+    const int k = fabs(t) < 7.0 ? (int)(t + (t < 0.0 ? -0.5 : 0.5)) : 0;
     const double kd = (double)k;
     double r = fma(-kd, PIO2_HI, x);
     r = fma(-kd, PIO2_LO, r);
@@ -108,6 +110,8 @@ MZ_HD double atan_d(double t) {
     return t < 0.0 ? -r : r;
 }
 MZ_HD float atan_f(float t) { return (float)atan_d((double)t); }
+// `float ang=atan(y/x)/3.1415926*180.0` (maze.h:151) from the quotient: float atan, double quotient and product, rounded on assignment
+MZ_HD float quotient_angle_f(float q) { return (float)((double)atan_f(q) / PI_REF * 180.0); }
 
 // `float rad = angle/180.0*3.1415926` (maze.h:166, 714): the quotient and the product are double, the assignment rounds
 MZ_HD float to_rad_f(float angle) { return (float)((double)angle / 180.0 * PI_REF); }
@@ -202,7 +206,7 @@ MZ_HD void radar_bits(const State &s, const Header &m, float *radar) {
     float angle;
     if (tx == 0.0f) angle = ty > 0.0f ? 90.0f : 270.0f;
     else {
-        const float ang = (float)((double)atan_f(ty / tx) / PI_REF * 180.0);   // float atan, double quotient and product, rounded on assignment
+        const float ang = quotient_angle_f(ty / tx);
         angle = tx > 0.0f ? ang : (float)((double)ang + 180.0);
     }
     const float a1[4] = {315.0f, 45.0f, 135.0f, 225.0f}, a2[4] = {405.0f, 135.0f, 225.0f, 315.0f};
@@ -366,7 +370,23 @@ inline void actions_host(const float *actions, int T, const Header &m, const flo
     }
 }
 
+// ---- the math probe (tests): the trigonometry outside an episode, on both sides ------------------------------------------------------------
+// fn: 0 sincos_d(x) -> (sin, cos); 1 atan_d(x) -> (atan, 0); 2 (float)x degrees -> to_rad_f -> sincos_f -> (sin, cos);
+// 3 (float)x = ty / tx -> the goal's angle in degrees as radar_bits forms it -> (tx > 0, tx < 0).  Values travel as doubles, out [2] per input.
+constexpr int MATH_FNS = 4;
+MZ_HD void math_probe(int fn, double x, double *out) {
+    if (fn == 0) { const SinCosD r = sincos_d(x); out[0] = r.s; out[1] = r.c; }
+    else if (fn == 1) { out[0] = atan_d(x); out[1] = 0.0; }
+    else if (fn == 2) { const SinCosF r = sincos_f(to_rad_f((float)x)); out[0] = (double)r.s; out[1] = (double)r.c; }
+    else { const float ang = quotient_angle_f((float)x); out[0] = (double)ang; out[1] = (double)(float)((double)ang + 180.0); }
+}
+
 #if defined(__HIPCC__)
+__global__ __launch_bounds__(256) void k_maze_math(int fn, const double *x, int n, double *out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) math_probe(fn, x[i], out + 2 * (size_t)i);
+}
+
 // ---- the device side: whole episodes in one launch ------------------------------------------------------------------------------------------
 // 16 lanes (one DPP row) per member, four members per wave, one wave per workgroup.  Lane j owns hidden unit j of fc1 and of fc2 -- its
 // weight columns are built once from base slot and noise table and stay in registers -- and output unit j & 1; activations travel inside

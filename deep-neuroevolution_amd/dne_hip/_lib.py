@@ -205,6 +205,15 @@ def maze_forward_host(theta, obs):
     return h1, h2, out
 
 
+def maze_math_host(fn, x):
+    """dne_maze_math_host: csrc/maze.h's trigonometry on the CPU for doubles x [n] -> [n][2] doubles.  fn 0 sincos_d -> (sin, cos); 1 atan_d ->
+    (atan, 0); 2 float degrees -> to_rad_f -> sincos_f; 3 float quotient ty / tx -> the radar's angle in degrees (tx > 0, tx < 0)"""
+    x = _arr(x, np.float64).reshape(-1)
+    out = np.empty((x.size, 2), np.float64)
+    _ck_host(load().dne_maze_math_host(int(fn), _ptr(x, C.c_double), int(x.size), _ptr(out, C.c_double)))
+    return out
+
+
 def _ptr(a, t):
     return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
 
@@ -426,6 +435,13 @@ class Engine:
         """the kernel once more for one current member, every step written out: [min(tslimit, 400)][16] as maze_rollout_host's trace"""
         out = np.empty((min(int(tslimit), MAZE_STEPS), MAZE_TRACE_W), np.float32)
         self._ck(self.lib.dne_maze_debug_trace(self.h, int(member), int(tslimit), _ptr(out, C.c_float)))
+        return out
+
+    def maze_debug_math(self, fn, x):
+        """maze_math_host's device twin (k_maze_math, one thread per input): [n][2] doubles"""
+        x = _arr(x, np.float64).reshape(-1)
+        out = np.empty((x.size, 2), np.float64)
+        self._ck(self.lib.dne_maze_debug_math(self.h, int(fn), _ptr(x, C.c_double), int(x.size), _ptr(out, C.c_double)))
         return out
 
     # ---- gpu-tree genomes: ((idx0,), (idx1, power1), ...)

@@ -36,6 +36,7 @@ extern "C" {
                            (csrc/maze.h): dne_maze_set_walls, then dne_set_members + dne_eval_members or dne_es_eval (pairs (2i, 2i+1) over base slot 0,
                            no reference pass; env_seed is accepted and ignored: the episode is deterministic).  returns = -distance to the goal after
                            step 400, 0 under a shorter tslimit; bc (record_bc): float (x, y) after every step, [members][bc_max_steps][2].
+                           bc_final_only = 1 is refused by dne_create: dne_maze_final_state has every member's final (x, y).
                            The P-generic calls work unchanged (dne_es_update, dne_weighted_sum, the optimizer calls, dne_records_pack / _set,
                            dne_es_update_gathered); dne_ga_*, dne_ref_pass, dne_env_*, dne_novelty*, dne_act and dne_debug_plan refuse the kind. */
 #define DNE_OB_BYTES (84 * 84 * 4)
@@ -306,6 +307,12 @@ int dne_maze_debug_trace(dne_handle *h, int member, int tslimit, float *trace);
  * (theta, observation) pairs (h1, h2 [n][16] after their relus, out [n][2]) */
 int dne_maze_actions_host(const float *actions, int n, int T, const float *header8, const float *lines, int n_walls, float *rows, float *obs0);
 int dne_maze_forward_host(const float *theta, const float *obs, int n, float *h1, float *h2, float *out);
+/* The header's trigonometry outside an episode, for n inputs travelling as doubles; out [n][2].  fn 0: sincos_d(x) -> (sin, cos); 1: atan_d(x) ->
+ * (atan, 0); 2: (float)x degrees -> to_rad_f -> sincos_f -> (sin, cos); 3: (float)x = ty / tx -> the goal's angle in degrees exactly as the radar
+ * forms it -> (the tx > 0 value, the tx < 0 value).  dne_maze_math_host runs on the CPU (no handle), dne_maze_debug_math one thread per input on
+ * the device; every kind but DNE_KIND_MAZE refuses the device call. */
+int dne_maze_math_host(int fn, const double *x, int n, double *out);
+int dne_maze_debug_math(dne_handle *h, int fn, const double *x, int n, double *out);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,9 @@
 // Stand-alone host program over csrc/maze.h for tests/test_maze_cpu.py, which builds it with -fsanitize=address,undefined and runs it:
 // the host rollout (with and without a trace) and the open-loop stepper on the maze file given as argv[1], on thetas from a small
 // generator, with exactly sized heap buffers so that any access past a wall array, a theta or a trace row is reported.
-// Prints one line "ok <episodes> <checksum>"; a sanitizer finding aborts it.
+// Then thetas outside every contract -- output biases NaN, +-inf, +-1e30, weights near FLT_MAX -- and the math probe on NaN, infinities and
+// huge arguments: built with -fsanitize=float-cast-overflow as well, so a NaN or an infinity reaching a cast to int is reported.
+// Prints one line "ok <episodes> <checksum> nan <episodes outside the contract> <how many of them returned -500>"; a sanitizer finding aborts it.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -54,6 +56,26 @@ int main(int argc, char **argv) {
         sum += rows[(size_t)(T - 1) * 18 + 17];
         episodes++;
     }
-    printf("ok %d %.6f\n", episodes, sum);
+    int wild = 0, lost = 0;
+    {   // outside the contract: the actions are NaN, infinite or huge on every step, or become so when the fmaf chains overflow
+        const float bias[6][2] = {{NAN, NAN}, {NAN, 0.7f}, {0.0f, NAN}, {INFINITY, -INFINITY}, {-1e30f, 1e30f}, {0.0f, 0.0f}};
+        for (int e = 0; e < 6; e++) {
+            std::vector<float> theta(NPARAMS, e == 5 ? 3e38f : 0.0f);
+            theta[B3] = bias[e][0]; theta[B3 + 1] = bias[e][1];
+            for (int tslimit : {7, 400}) {
+                std::vector<float> trace((size_t)tslimit * TRACE_W);
+                float ret, xy[2];
+                int32_t len;
+                rollout_host(theta.data(), m, walls.data(), nlines, tslimit, &ret, &len, xy, trace.data());
+                wild++;
+                lost += ret == -500.0f;
+            }
+        }
+        const double xs[10] = {NAN, -NAN, INFINITY, -INFINITY, 1e300, -1e300, 1e10, -4.4e9, 3e38, -0.0};
+        std::vector<double> out(2);
+        for (int fn = 0; fn < MATH_FNS; fn++)
+            for (double x : xs) math_probe(fn, x, out.data());
+    }
+    printf("ok %d %.6f nan %d %d\n", episodes, sum, wild, lost);
     return 0;
 }

@@ -1,5 +1,5 @@
 """TEST-ONLY support for the hard maze (DNE_KIND_MAZE, csrc/maze.h): the fixtures, the tolerances of the comparison with the reference's
-recording, synthetic mazes, member sets, a float32 numpy statement of the policy, and MazeHostEngine -- dne_maze_rollout_host (the same
+two recordings, the edge mazes, the math probe's inputs and measured bounds, a NaN-aware bit comparison, synthetic mazes, member sets, a float32 numpy statement of the policy, and MazeHostEngine -- dne_maze_rollout_host (the same
 header compiled for the CPU) behind the Engine method surface, as tests/oracle_engine.py puts the oracle behind it."""
 import os
 
@@ -26,6 +26,101 @@ TOL_RANGEFINDER = 4 * MEASURED_RANGEFINDER          # 2.86e-06
 TOL_STATE = 4 * 0.0                                 # x, y, heading, speed, ang_vel, reward: exact
 # No wall comparison flipped (every collision count and every rangefinder hit agrees on every step), so no sequence is set aside:
 SET_ASIDE = {}                                      # sequence -> step index of the flipped comparison; at most one entry is allowed
+
+
+# ---- the edge recording (tests/golden/maze_reference_edges.npz: six edge mazes x eleven sequences, NaN / inf / 1e30 / denormal actions included) --
+# Measured between dne_maze_actions_host and that recording over its 66 sequences x 400 steps:
+#   x, y, heading, speed, ang_vel, reward        NaN where the reference has NaN, bit-identical elsewhere (-0.0 == 0.0 for the reward)
+#   collision counts, radar bits, reward's step  identical
+#   rangefinder observations (range / 100)       largest difference MEASURED_RANGEFINDER_EDGES
+# which is below MEASURED_RANGEFINDER, so the edge recording is held to the same TOL_RANGEFINDER.
+EDGE_RECORDING = os.path.join(ROOT, "tests", "golden", "maze_reference_edges.npz")
+EDGE_MAZES = ("disable", "zero_wall", "dist_8", "dist_7_99", "goal_on_start", "ray_endpoint")
+EDGE_SEQS = ("still", "straight", "spin", "mixed", "wait_then_straight", "nan_turn_from_10", "nan_speed_from_50", "inf_inf", "ninf_1e30",
+             "n1e30_ninf", "denormal")
+MEASURED_RANGEFINDER_EDGES = 2.384185791015625e-07
+SET_ASIDE_EDGES = {}                                # (maze, sequence) -> step index of a flipped wall comparison; at most one entry is allowed
+
+
+def edge_maze_file(name):
+    return os.path.join(ROOT, "tests", "golden", "maze_edge_%s.txt" % name)
+
+
+def edge_maze(name):
+    from dne_hip import _lib
+    return _lib.load_maze(edge_maze_file(name))
+
+
+def same_nan(a, b):
+    """equal shapes, NaN exactly where the other has NaN (payload and sign of a NaN are free), equal bits everywhere else"""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    u = {4: np.uint32, 8: np.uint64}[a.dtype.itemsize]
+    na, nb = np.isnan(a), np.isnan(b)
+    return bool(np.array_equal(na, nb) and np.array_equal(a.view(u)[~na], b.view(u)[~nb]))
+
+
+# ---- the math probe (dne_maze_math_host / dne_maze_debug_math: sincos_d, atan_d and their float forms outside an episode) ---------------------
+# Measured on math_inputs(fn) against the high-precision reference (tests/test_maze_cpu.py says how it is formed):
+#   sincos_d, atan_d          largest ABSOLUTE error of the double result (relative error means nothing next to a zero of the sine)
+#   all four, as floats       equal to the correctly rounded float of the reference value on every input: no double-rounding case in the set
+MEASURED_ABS_SINCOS_D = 1.4414467883194781e-16
+MEASURED_ABS_ATAN_D = 1.691355389077387e-16
+TOL_ABS_SINCOS_D = 4 * MEASURED_ABS_SINCOS_D
+TOL_ABS_ATAN_D = 4 * MEASURED_ABS_ATAN_D
+DOUBLE_ROUNDING = {}                                # fn -> (input, this header's float, the correctly rounded float); at most one per function
+MATH_SINCOS_D, MATH_ATAN_D, MATH_SINCOS_F, MATH_ANGLE_F = 0, 1, 2, 3
+PI_REF = 3.1415926
+
+
+def _neighbours(centres, k=50):
+    """each centre and its k nearest doubles on either side"""
+    out = []
+    for c in centres:
+        lo = hi = np.float64(c)
+        out.append(lo)
+        for _ in range(k):
+            lo = np.nextafter(lo, -np.inf); hi = np.nextafter(hi, np.inf)
+            out += [lo, hi]
+    return np.array(out, np.float64)
+
+
+_math_cache = {}
+
+
+def math_inputs(fn):
+    """the probe's fixed inputs (doubles; for the float functions every value is a float), at least 10^6 per function, without NaN"""
+    if fn in _math_cache:
+        return _math_cache[fn]
+    rs = np.random.RandomState(4000 + fn)
+    headings = rs.uniform(-363, 363, 500_000).astype(np.float32)
+    if fn == MATH_SINCOS_D:
+        x = np.concatenate([rs.uniform(-3 * np.pi, 3 * np.pi, 1_000_000), _neighbours(np.arange(-12, 13) * (np.pi / 4)),
+                            headings.astype(np.float64) / 180.0 * PI_REF,                     # what propose_move hands over
+                            [0.0, -0.0, 3 * np.pi, -3 * np.pi, 5e-324, -5e-324, 1e-300, 1e-8]])
+    elif fn == MATH_SINCOS_F:
+        more = rs.uniform(-363, 363, 1_000_000).astype(np.float32)
+        grid = np.arange(-362, 363, dtype=np.float32)
+        near = np.stack([np.nextafter(grid, np.float32(-np.inf)), np.nextafter(grid, np.float32(np.inf))]).reshape(-1)   # every whole degree's two float neighbours
+        x = np.concatenate([headings, more, grid, near, np.float32([0.0, -0.0, 1e-40, -1e-40])]).astype(np.float64)
+    else:
+        tx, ty = rs.uniform(-200, 200, (2, 500_000)).astype(np.float32)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            quot = (ty / tx).astype(np.float32)
+        quot = quot[np.isfinite(quot)]
+        mag = 10.0 ** rs.uniform(-300, 300, 300_000)
+        x = np.concatenate([quot.astype(np.float64), mag, -mag, rs.uniform(-4, 4, 500_000),
+                            _neighbours([0.4375, 0.6875, 1.1875, 2.4375, 0.5, 1.0, 1.5]), -_neighbours([0.4375, 0.6875, 1.1875, 2.4375, 0.5, 1.0, 1.5]),
+                            [np.inf, -np.inf, 0.0, -0.0, np.finfo(np.float64).max, -np.finfo(np.float64).max, 5e-324, -5e-324]])
+        if fn == MATH_ANGLE_F:                                                                 # the radar divides floats: every quotient is a float
+            with np.errstate(over="ignore", under="ignore"):
+                x = x.astype(np.float32).astype(np.float64)
+    x = np.ascontiguousarray(x, np.float64)
+    assert x.size >= 1_000_000 and not np.any(np.isnan(x))
+    x.setflags(write=False)
+    _math_cache[fn] = x
+    return x
 
 
 def fixture_maze():

@@ -198,6 +198,8 @@ def test_refusals(eng):
     from dne_hip import _lib
     with pytest.raises(_lib.DneError, match="n_actions 18"):
         _lib.Engine(_lib.KIND_MAZE, 18, max_members=4)
+    with pytest.raises(_lib.DneError, match=r"bc_final_only is not available on a DNE_KIND_MAZE engine \(kind 4\).*dne_maze_final_state"):
+        _lib.Engine(_lib.KIND_MAZE, 2, max_members=4, record_bc=True, bc_max_steps=400, bc_final_only=True)
     fresh = _lib.Engine(_lib.KIND_MAZE, 2, max_members=4)
     try:
         fresh.noise_upload(noise())
@@ -252,6 +254,8 @@ def test_refusals(eng):
             other.maze_set_walls(*maze(13))
         with pytest.raises(_lib.DneError, match="DNE_KIND_MAZE"):
             other.maze_final_state(1)
+        with pytest.raises(_lib.DneError, match="dne_maze_debug_math needs a DNE_KIND_MAZE engine"):
+            other.maze_debug_math(0, [0.5])
     finally:
         other.close()
     assert eng.check_redzones() == 0

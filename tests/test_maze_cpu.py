@@ -1,7 +1,9 @@
 """CPU: the hard maze outside the kernel -- csrc/maze.h compiled for the host (dne_maze_actions_host / _forward_host / _rollout_host, no GPU and
 no handle) against the recording of the reference's own maze.h and against numpy / torch statements of the policy; policies.simple_scale_by,
-_lib.load_maze, P = 498; the es_gpu.py driver with exp['game'] = 'maze' on MazeHostEngine; and the header under AddressSanitizer + UBSan in a
-stand-alone program."""
+_lib.load_maze, P = 498; the es_gpu.py driver with exp['game'] = 'maze' on MazeHostEngine; the header under AddressSanitizer + UBSan in a
+stand-alone program, on the fixture and on every edge maze, NaN and infinite actions included; the second recording of the reference
+(tests/golden/maze_reference_edges.npz: the branches and comparisons at equality the fixture maze never reaches); and the math probe
+(dne_maze_math_host: sincos_d, atan_d and their float forms against a higher-precision reference)."""
 import os
 import pickle
 import shutil
@@ -280,12 +282,248 @@ def test_driver_on_the_maze(oracle, tmp_path):
 
 
 # ---- 5. the header under AddressSanitizer and UBSan, in a program of its own ---------------------------------------------------------------------
-def test_header_under_sanitizers_in_a_stand_alone_program(tmp_path):
+@pytest.fixture(scope="module")
+def sanitizer_program(tmp_path_factory):
+    """tests/maze_asan_main.cpp, built once: address, undefined and float-cast-overflow (a NaN or an infinity reaching a cast to int)"""
     cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
     src = os.path.join(M.ROOT, "tests", "maze_asan_main.cpp")
-    exe = str(tmp_path / "maze_asan")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(M.ROOT, "deep-neuroevolution_amd", "csrc"), src, "-o", exe, "-lm"])
-    out = subprocess.run([exe, M.MAZE_FILE], capture_output=True, text=True, timeout=120)
+    exe = str(tmp_path_factory.mktemp("maze_asan") / "maze_asan")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined,float-cast-overflow",
+                           "-fno-sanitize-recover=all", "-I", os.path.join(M.ROOT, "deep-neuroevolution_amd", "csrc"), src, "-o", exe, "-lm"])
+    return exe
+
+
+def test_header_under_sanitizers_in_a_stand_alone_program(sanitizer_program):
+    out = subprocess.run([sanitizer_program, M.MAZE_FILE], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr[-2000:]
     assert out.stdout.split()[:2] == ["ok", "25"], out.stdout
+    # the thetas outside the contract: 6 x (limit 7, limit 400); the three whose bias is NaN end at -500 under limit 400 (infinite and huge
+    # actions are clamped, and all-positive weights overflow to +inf, never to NaN)
+    assert out.stdout.split()[3:] == ["nan", "12", "3"], out.stdout
+
+
+@pytest.mark.parametrize("name", M.EDGE_MAZES)
+def test_header_under_sanitizers_on_the_edge_mazes(sanitizer_program, name):
+    out = subprocess.run([sanitizer_program, M.edge_maze_file(name)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    tok = out.stdout.split()
+    assert tok[0] == "ok" and tok[3:5] == ["nan", "12"], out.stdout
+    # where every step collides the position never becomes NaN (zero_wall: d = 0 whatever the position) ...
+    assert int(tok[5]) == (0 if name == "zero_wall" else 3), out.stdout
+
+
+# ---- 6. the edge recording: branches and comparisons at equality that the fixture maze never reaches -------------------------------------------
+@pytest.fixture(scope="module")
+def edges():
+    return np.load(M.EDGE_RECORDING)
+
+
+@pytest.fixture(scope="module")
+def edge_replay(edges):
+    """the host restatement under the edge recording's actions on each edge maze, once: name -> (rows, obs0)"""
+    from dne_hip import _lib
+    return {name: _lib.maze_actions_host(edges["actions"], *M.edge_maze(name)) for name in M.EDGE_MAZES}
+
+
+def test_edge_recording_is_what_the_issue_asks_for(edges):
+    act, rows, obs0 = edges["actions"], edges["rows"], edges["obs0"]
+    assert tuple(edges["mazes"]) == M.EDGE_MAZES and tuple(edges["sequences"]) == M.EDGE_SEQS
+    assert act.shape == (11, 400, 2) and rows.shape == (6, 11, 400, 18) and obs0.shape == (6, 11, 11)
+    assert os.path.getsize(M.EDGE_RECORDING) <= os.path.getsize(M.RECORDING)
+    q = {s: k for k, s in enumerate(M.EDGE_SEQS)}
+    mz = {s: k for k, s in enumerate(M.EDGE_MAZES)}
+    for s, a in (("still", (0, 0)), ("straight", (0, 0.7)), ("spin", (0.7, 0)), ("mixed", (-0.3, 0.5)), ("inf_inf", (np.inf, np.inf)),
+                 ("ninf_1e30", (-np.inf, 1e30)), ("n1e30_ninf", (-1e30, -np.inf)), ("denormal", (1e-40, -1e-40))):
+        assert np.all(act[q[s]] == np.asarray(a, np.float32)), s
+    assert not np.any(act[q["wait_then_straight"], :20]) and np.all(act[q["wait_then_straight"], 20:] == np.float32([0, 0.7]))
+    assert np.all(np.isnan(act[q["nan_turn_from_10"], 10:, 0])) and np.all(np.isfinite(act[q["nan_turn_from_10"], :10]))
+    assert np.all(np.isnan(act[q["nan_speed_from_50"], 50:, 1])) and np.all(np.isfinite(act[q["nan_speed_from_50"], :50]))
+    x, y, speed, coll, reward = rows[..., 11], rows[..., 12], rows[..., 14], rows[..., 16], rows[..., 17]
+    steps = np.arange(1, 401)
+    headers = {name: M.edge_maze(name)[0] for name in M.EDGE_MAZES}
+    assert [headers[n][0] for n in M.EDGE_MAZES] == [1, 0, 0, 0, 1, 0]
+    # disable 1: frozen from the first collision on, one more collision per step, the speed not 0
+    for name in ("disable", "goal_on_start"):
+        for k in range(11):
+            if coll[mz[name], k, -1] > 0 and np.all(np.isfinite(rows[mz[name], k])):
+                t0 = int(np.flatnonzero(coll[mz[name], k] > 0)[0])
+                assert np.all(x[mz[name], k, t0:] == x[mz[name], k, t0]) and np.all(y[mz[name], k, t0:] == y[mz[name], k, t0])
+                assert np.array_equal(coll[mz[name], k, t0:], np.arange(1, 401 - t0))
+        assert 0 < coll[mz[name], q["straight"], -1] < 400 and speed[mz[name], q["straight"], -1] != 0
+    # the zero-length wall: every step of every sequence collides
+    assert np.all(coll[mz["zero_wall"]] == steps) and np.all(x[mz["zero_wall"]] == headers["zero_wall"][2])
+    # d < radius at exactly 8.0 and at 7.99
+    assert np.all(coll[mz["dist_8"], q["still"]] == 0) and np.all(coll[mz["dist_8"], q["spin"]] == 0)
+    assert np.all(coll[mz["dist_7_99"], q["still"]] == steps) and coll[mz["dist_7_99"], q["still"], -1] == 400
+    # tx == 0: the goal straight above, straight below and on the start
+    for name, want in (("dist_8", [0, 0, 0, 1]), ("dist_7_99", [0, 1, 0, 0]), ("goal_on_start", [0, 0, 0, 1])):
+        assert obs0[mz[name], q["still"], 7:].tolist() == want and np.all(rows[mz[name], q["still"], :, 7:11] == want), name
+    # r == 0, r == 1, s == 1: the heading-0 ray ends on two wall ends and on a wall with its own tip, and reports nothing
+    assert obs0[mz["ray_endpoint"], q["still"], 3] == 1.0 and obs0[mz["ray_endpoint"], q["still"], 4] < 1.0
+    # NaN actions: NaN rows; -500 exactly where the position became NaN (a navigator frozen or colliding on every step keeps a finite one)
+    for s in ("nan_turn_from_10", "nan_speed_from_50"):
+        assert np.all(np.isnan(rows[:, q[s]]).any(axis=(1, 2)))
+        assert np.array_equal(reward[:, q[s], -1] == -500, np.isnan(x[:, q[s], -1]))
+        assert reward[mz["dist_8"], q[s], -1] == -500 and reward[mz["ray_endpoint"], q[s], -1] == -500
+    finite = [k for k, s in enumerate(M.EDGE_SEQS) if not s.startswith("nan")]
+    assert np.all(np.isfinite(rows[:, finite]))
+
+
+@pytest.mark.parametrize("name", M.EDGE_MAZES)
+def test_host_restatement_matches_the_edge_recording(edges, edge_replay, name):
+    k = M.EDGE_MAZES.index(name)
+    rows, obs0 = edge_replay[name]
+    ref, ref0 = edges["rows"][k], edges["obs0"][k]
+    assert len(M.SET_ASIDE_EDGES) <= 1
+    keep = [i for i in range(ref.shape[0]) if (name, M.EDGE_SEQS[i]) not in M.SET_ASIDE_EDGES]
+    rows, obs0, ref, ref0 = rows[keep], obs0[keep], ref[keep], ref0[keep]
+    assert np.array_equal(rows[..., 16], ref[..., 16]), "collision counts"
+    assert np.array_equal(rows[..., 7:11], ref[..., 7:11]) and np.array_equal(obs0[:, 7:], ref0[:, 7:]), "radar bits"
+    assert np.array_equal(rows[..., 17] != 0, ref[..., 17] != 0) and np.all(ref[:, :-1, 17] == 0), "the reward's step"
+    assert np.all(rows[..., 0] == 1) and np.all(ref[..., 0] == 1)
+    for col_name, sl in (("x", 11), ("y", 12), ("heading", 13), ("speed", 14), ("ang_vel", 15)):
+        assert M.same_nan(rows[..., sl], ref[..., sl]), col_name
+    assert M.same_nan(rows[..., 17] + np.float32(0.0), ref[..., 17] + np.float32(0.0)), "reward (-0.0 + 0.0 = 0.0)"
+    assert np.all(np.isfinite(rows[..., 1:7])) and np.all(np.isfinite(ref[..., 1:7]))                 # a rangefinder is never NaN: it stays at 100
+    worst = float(max(np.abs(rows[..., 1:7].astype(np.float64) - ref[..., 1:7]).max(), np.abs(obs0[:, 1:7].astype(np.float64) - ref0[:, 1:7]).max()))
+    print("largest rangefinder difference from the edge recording on %s: %r" % (name, worst))
+    assert M.MEASURED_RANGEFINDER_EDGES <= M.MEASURED_RANGEFINDER and worst <= M.TOL_RANGEFINDER, worst
+
+
+def test_same_nan():
+    nan, nan2 = np.float32(np.nan), np.array([0xFFC00001], np.uint32).view(np.float32)[0]
+    a = np.array([1.0, nan, -0.0, np.inf], np.float32)
+    assert M.same_nan(a, np.array([1.0, nan2, -0.0, np.inf], np.float32))
+    assert not M.same_nan(a, np.array([1.0, nan, 0.0, np.inf], np.float32))       # the sign of a zero is a bit like any other
+    assert not M.same_nan(a, np.array([1.0, 2.0, -0.0, np.inf], np.float32)) and not M.same_nan(a, np.array([nan, nan, -0.0, np.inf], np.float32))
+    assert not M.same_nan(a, a[:3]) and M.same_nan(a.astype(np.float64), a.astype(np.float64))
+
+
+# ---- 7. the math probe: sincos_d, atan_d and their float forms outside an episode ----------------------------------------------------------------
+# The reference value of every input is formed in more than double precision.  numpy's 80-bit long double functions (64 significant bits, error
+# about 1e-19 relative) carry the bulk: against them the double results are judged in ABSOLUTE error, and the float results must equal the
+# reference rounded once to float.  Wherever that rounding could depend on the long double's own last bits -- the value lies within 2^-55
+# (relative) of the midpoint of two floats -- and on the inputs with the largest double error, mpmath at 60 digits decides instead, when it
+# imports; where long double is no wider than double, mpmath decides every input.
+LD = np.longdouble
+_LD_FN = {"sin": np.sin, "cos": np.cos, "atan": np.arctan}
+
+
+def _mp(name, v):
+    import mpmath
+    mpmath.mp.dps = 60
+    return getattr(mpmath, name)(mpmath.mpf(float(v)))
+
+
+def _have_mpmath():
+    try:
+        import mpmath  # noqa: F401
+        return True
+    except ImportError:
+        return False
+
+
+def _rounded_float(name, x):
+    """(the reference value of name(x) as long double [n], the same correctly rounded to float [n])"""
+    with np.errstate(all="ignore"):
+        L = _LD_FN[name](x.astype(LD))
+        f = L.astype(np.float32)
+        up, dn = np.nextafter(f, np.float32(np.inf)).astype(LD), np.nextafter(f, np.float32(-np.inf)).astype(LD)
+        fl = f.astype(LD)
+        gap = np.minimum(np.abs(L - (fl + up) / 2), np.abs(L - (fl + dn) / 2))
+        unsure = np.isfinite(L) & (L != 0) & (gap <= np.abs(L) * LD(2.0) ** -55)
+        if np.finfo(LD).nmant < 63:
+            unsure = np.isfinite(L) & (L != 0)
+    if _have_mpmath():
+        import mpmath
+        for i in np.flatnonzero(unsure):
+            v = _mp(name, x[i])
+            cands = [f[i], np.nextafter(f[i], np.float32(np.inf)), np.nextafter(f[i], np.float32(-np.inf))]
+            f[i] = min(cands, key=lambda c: abs(v - mpmath.mpf(float(c))))
+    return L, f
+
+
+def _abs_error(name, x, got, L):
+    """largest |got - reference| over finite references, the worst inputs re-measured with mpmath"""
+    with np.errstate(all="ignore"):
+        err = np.abs(got.astype(LD) - L)
+    err = np.where(np.isfinite(L), err, 0)
+    worst = float(err.max())
+    if _have_mpmath():
+        import mpmath
+        pick = np.concatenate([np.argsort(err)[-100:], np.random.RandomState(1).randint(0, x.size, 2000)])
+        for i in pick:
+            e = abs(mpmath.mpf(float(got[i])) - _mp(name, x[i]))
+            assert abs(float(e) - float(err[i])) <= 1e-18, (name, x[i], float(e), float(err[i]))   # the long double reference is that good
+            worst = max(worst, float(e))
+    return worst
+
+
+@pytest.fixture(scope="module")
+def probe():
+    from dne_hip import _lib
+    return {fn: _lib.maze_math_host(fn, M.math_inputs(fn)) for fn in range(4)}
+
+
+def test_math_probe_doubles_in_absolute_error_and_floats_correctly_rounded(probe):
+    figures = {}
+    # sincos_d
+    x, out = M.math_inputs(M.MATH_SINCOS_D), probe[M.MATH_SINCOS_D]
+    assert np.abs(x).max() <= 3 * np.pi + 1e-12
+    worst = 0.0
+    for col, name in enumerate(("sin", "cos")):
+        L, f = _rounded_float(name, x)
+        worst = max(worst, _abs_error(name, x, out[:, col], L))
+        bad = np.flatnonzero(out[:, col].astype(np.float32) != f)
+        assert set(x[bad]) <= {v[0] for k, v in M.DOUBLE_ROUNDING.items() if k == M.MATH_SINCOS_D}, (name, x[bad][:5])
+    figures["sincos_d"] = worst
+    # atan_d
+    x, out = M.math_inputs(M.MATH_ATAN_D), probe[M.MATH_ATAN_D]
+    L, f = _rounded_float("atan", x)
+    figures["atan_d"] = _abs_error("atan", x, out[:, 0], L)
+    with np.errstate(over="ignore"):
+        bad = np.flatnonzero(out[:, 0].astype(np.float32) != f)
+    assert set(x[bad]) <= {v[0] for k, v in M.DOUBLE_ROUNDING.items() if k == M.MATH_ATAN_D}, x[bad][:5]
+    assert np.all(out[:, 1] == 0) and np.array_equal(np.signbit(out[:, 0]), x < 0)          # odd, except that atan_d(-0.0) is +0.0 (pinned below)
+    print("math probe, largest absolute errors of the double results:", figures)
+    assert M.TOL_ABS_SINCOS_D == 4 * M.MEASURED_ABS_SINCOS_D and M.TOL_ABS_ATAN_D == 4 * M.MEASURED_ABS_ATAN_D
+    assert figures["sincos_d"] <= M.TOL_ABS_SINCOS_D and figures["atan_d"] <= M.TOL_ABS_ATAN_D
+    assert len(M.DOUBLE_ROUNDING) <= 4 and all(k in range(4) for k in M.DOUBLE_ROUNDING)     # (a dict: at most one input per function)
+
+
+def test_math_probe_float_forms_equal_the_correctly_rounded_reference(probe):
+    # float degrees -> to_rad_f -> sincos_f: the radians are plain IEEE operations (restated here), sine and cosine round once
+    x, out = M.math_inputs(M.MATH_SINCOS_F), probe[M.MATH_SINCOS_F]
+    assert np.array_equal(x, x.astype(np.float32).astype(np.float64)) and np.abs(x).max() <= 363
+    rad = (x / 180.0 * M.PI_REF).astype(np.float32).astype(np.float64)
+    for col, name in enumerate(("sin", "cos")):
+        _, f = _rounded_float(name, rad)
+        bad = np.flatnonzero(out[:, col] != f.astype(np.float64))
+        assert set(x[bad]) <= {v[0] for k, v in M.DOUBLE_ROUNDING.items() if k == M.MATH_SINCOS_F}, (name, x[bad][:5])
+    # float quotient -> the radar's angle: float atan, then / 3.1415926 * 180 in double rounded to float, + 180.0 likewise
+    x, out = M.math_inputs(M.MATH_ANGLE_F), probe[M.MATH_ANGLE_F]
+    assert np.array_equal(x, x.astype(np.float32).astype(np.float64))
+    _, a = _rounded_float("atan", x)
+    ang = (a.astype(np.float64) / M.PI_REF * 180.0).astype(np.float32)
+    ang180 = (ang.astype(np.float64) + 180.0).astype(np.float32)
+    bad = np.flatnonzero((out[:, 0] != ang.astype(np.float64)) | (out[:, 1] != ang180.astype(np.float64)))
+    assert set(x[bad]) <= {v[0] for k, v in M.DOUBLE_ROUNDING.items() if k == M.MATH_ANGLE_F}, x[bad][:5]
+    # (the reference's short pi puts atan = pi / 2 at 90.00000763 degrees: the angle may pass 90 and 270 by one float)
+    assert np.abs(out[:, 0]).max() == np.float32(np.float32(np.pi / 2) / M.PI_REF * 180.0)
+
+
+def test_math_probe_pins_and_refusals():
+    from dne_hip import _lib
+    pin = _lib.maze_math_host(M.MATH_ATAN_D, [-0.0, 0.0, np.inf, -np.inf])[:, 0]
+    assert not np.signbit(pin[0]) and pin[0] == 0                 # atan_d(-0.0) is +0.0 where libm answers -0.0: as it is, no radar bit can tell
+    assert not np.signbit(pin[1]) and pin[2] == np.pi / 2 and pin[3] == -np.pi / 2
+    # outside the contract no cast to int is made (k = 0): NaN from NaN, nothing finite from an infinity
+    wild = _lib.maze_math_host(M.MATH_SINCOS_D, [np.nan, np.inf, -np.inf, 1e300])
+    assert np.all(np.isnan(wild[0])) and not np.any(np.isfinite(wild))
+    assert np.all(np.isnan(_lib.maze_math_host(M.MATH_SINCOS_F, [np.nan])))
+    assert np.all(np.isnan(_lib.maze_math_host(M.MATH_ATAN_D, [np.nan])[:, 0])) and np.all(np.isnan(_lib.maze_math_host(M.MATH_ANGLE_F, [np.nan])))
+    for fn in (-1, 4):
+        with pytest.raises(_lib.DneError, match="fn 0..3"):
+            _lib.maze_math_host(fn, [0.0])
+    with pytest.raises(_lib.DneError, match="n >= 1"):
+        _lib.maze_math_host(0, [])
