@@ -158,6 +158,50 @@ def test_run_master_run_worker_in_process(oracle, small_noise, tmp_path):
     assert os.path.exists(os.path.join(str(tmp_path), "log.txt"))
 
 
+def test_run_master_run_worker_with_evaluations_adaptive_cutoff_and_snapshots(oracle, tmp_path):
+    """Everything the two-iteration test above leaves off, in one run: eval_prob 1.0 (an unlimited evaluation episode before every
+    shard, es.py:388-405), an adaptive time limit that grows three times (es.py:308-311) and snapshot_freq 2 (es.py:345-353, named
+    after the mean evaluation return).  Four iterations finish and equal a hand-rolled oracle loop on the worker's stream."""
+    import es_driver_support as S
+    from oracle_engine import OracleEngine
+    from dne_hip import _lib, es, policies
+    noise = es.SharedNoiseTable(count=2_500_000)
+    exp = S.es_exp(pop=8, cutoff="adaptive:12,0.5,1.5,40", eval_prob=1.0, snapshot_freq=2)
+    run = S.run_driver(es, exp, OracleEngine(0, ref_count=16), OracleEngine(0, ref_count=16), noise, tmp_path, 4)
+    assert [t.timestep_limit for t in run.tasks] == [12, 18, 27, 40]
+    assert [(t, r.eval_length is not None) for t, r in run.pushed] == [(it, ev) for it in range(4) for ev in (True, False)]
+    assert all(c[1] == _lib.ENV_MAX_EPISODE_STEPS for c in run.evals) and len(S.episodes_ended_by_game_over(oracle, run)) == 4
+    # the hand-rolled loop: per worker iteration the coin, the evaluation's seed, four indices, eight seeds (es.py:398-408)
+    L, th, ref = oracle.layout(0, 18), policies.xavier_flat(18, 0), run.tasks[0].ref_batch
+    rs = np.random.RandomState(7); rs.randint(2 ** 31)
+    opt, limit, evals = oracle.Adam(th, 0.01), 12, []
+    for it in range(4):
+        assert np.array_equal(run.tasks[it].params, th), it
+        assert rs.rand() < 1.0
+        ev_seed = rs.randint(0, 2 ** 32, size=1, dtype=np.uint64).astype(np.uint32)[0]
+        evals.append(oracle.rollout(L, th, ref, ev_seed, _lib.ENV_MAX_EPISODE_STEPS)[:3])
+        idx = np.sort(np.array([noise.sample_index(rs, L.P) for _ in range(4)], np.int64))
+        seeds = rs.randint(0, 2 ** 32, size=8, dtype=np.uint64).astype(np.uint32)
+        rets, sg, ln = oracle.es_eval(L, th, noise.noise, idx, 0.02, limit, ref, seeds)
+        res = run.pushed[2 * it + 1][1]
+        assert np.array_equal(res.noise_inds_n, idx) and np.array_equal(res.returns_n2, rets) and np.array_equal(res.lengths_n2, ln), it
+        opt.theta = th.copy()
+        _, th = opt.update(oracle.es_gradient(noise.noise, idx, rets, L.P), 0.005)
+        th = th.copy()
+        if (ln == limit).mean() >= 0.5:
+            limit = min(int(1.5 * limit), 40)
+    assert np.array_equal(run.theta, th)
+    assert [(r.eval_return, r.eval_length) for _, r in run.pushed[0::2]] == [(e[0], e[2]) for e in evals]
+    assert all(100 <= e[2] < 1000 for e in evals)
+    # snapshots of iterations 0 and 2, written after the update: each holds the theta the next task carries
+    ext = policies.snapshot_extension()
+    snaps = sorted(f for f in os.listdir(str(tmp_path)) if f.startswith("snapshot_iter"))
+    assert snaps == ["snapshot_iter%05d_rew%d%s" % (it, int(evals[it][0]), ext) for it in (0, 2)]
+    for it, fn in zip((0, 2), snaps):
+        pol = policies.ESAtariPolicy.Load(os.path.join(str(tmp_path), fn), engine=OracleEngine(0, ref_count=16))
+        assert np.array_equal(pol.get_trainable_flat(), run.tasks[it + 1].params), it
+
+
 def test_policy_surface(oracle, small_noise, tmp_path):
     from oracle_engine import OracleEngine
     from dne_hip import policies
