@@ -932,6 +932,21 @@ extern "C" int dne_debug_plan(int kind, int n_actions, const dne_plan_facts *fac
     return 0;
 }
 
+extern "C" int dne_debug_plan_act(int kind, int n_actions, const dne_plan_facts *facts, int n, dne_window_plan *out) {
+    if (kind == DNE_KIND_MAZE) {   // dne_act refuses the kind
+        g_create_error = "dne_debug_plan_act: a DNE_KIND_MAZE engine (kind 4) has no dne_act";
+        return -1;
+    }
+    if (n < 1) {
+        g_create_error = "dne_debug_plan_act: n must be at least 1";
+        return -1;
+    }
+    PlanFacts f = *facts;
+    f.kind = kind;
+    *out = act_window(engine_knobs(kind, n_actions), f, n);
+    return 0;
+}
+
 extern "C" int dne_debug_knob(int kind, int n_actions, const char *name) {
     const Knobs k = engine_knobs(kind, n_actions);
     for (const KnobRow &r : KNOBS)
@@ -1389,7 +1404,7 @@ extern "C" int dne_env_step(dne_handle *h, int n, const int32_t *actions, float 
         if (actions[i] < 0 || actions[i] >= h->cfg.n_actions) return h->fail("action %d out of range", actions[i]);
     HCHECK(h, hipMemcpyAsync(h->action, actions, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HCHECK(h, hipMemsetAsync(h->step_reward, 0, n * sizeof(float), h->stream));
-    launch_env_step(h, plan_window(h->k, h->facts(), StepPlan{}, n, n, 1, false), h->env(0), nullptr, 1, 0x7fffffff);
+    launch_env_step(h, act_window(h->k, h->facts(), n), h->env(0), nullptr, 1, 0x7fffffff);
     HCHECK(h, hipGetLastError());
     if (reward) HCHECK(h, hipMemcpyAsync(reward, h->step_reward, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     if (done) HCHECK(h, hipMemcpyAsync(done, h->done, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -1730,7 +1745,7 @@ extern "C" int dne_act(dne_handle *h, int n, int32_t *actions, float *logits) {
     DeviceGuard dg(h);
     MAZE_REFUSE(h, "dne_act");
     if (check_n(h, n)) return -1;
-    const WindowPlan w = plan_window(h->k, h->facts(), StepPlan{}, n, n, 1, false);
+    const WindowPlan w = act_window(h->k, h->facts(), n);
     launch_forward(h, StepPlan{}, w, nullptr, nullptr, 1, false);
     launch_fc(h, StepPlan{}, w, nullptr, nullptr, 1, h->logits);
     HCHECK(h, hipGetLastError());

@@ -276,6 +276,10 @@ static inline WindowPlan plan_window(const Knobs &k, const PlanFacts &f, const S
     return w;
 }
 
+// dne_act / dne_env_step: the n members as ONE window of single members under the empty plan, outside any evaluation.  dne_debug_plan_act
+// answers from this very function, so a test can name the kernels an act at a given width launches before it launches them.
+static inline WindowPlan act_window(const Knobs &k, const PlanFacts &f, int n) { return plan_window(k, f, StepPlan{}, n, n, 1, false); }
+
 // (LargeModel: the kind of an evaluation -- 1, or 6 for pairs -- follows lfc_cols_max, the brackets follow w.wide = fc_tail_max.  Both default to 96
 // members; set apart, an evaluation of kind 6 / 1 may bracket no launch (DNE_LFC_COLS_MAX=0 with few members) or count a window of k_lfc_cols launches.)
 // a profiled evaluation brackets the launches of ONE kernel, the one it starts with (ev = plan_step(.., whole_eval = true)): k_fc_ring's, else k_fc_duo's,

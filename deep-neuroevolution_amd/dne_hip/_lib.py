@@ -137,6 +137,17 @@ def debug_plan(kind, nact, total, gsize, whole_eval=False, **facts):
     return rc if whole_eval else list(rows[:nsub.value])
 
 
+def debug_plan_act(kind, nact, n, **facts):
+    """dne_debug_plan_act (no GPU needed): the one WindowPlan row of dne_act / dne_env_step over n members, knobs from the environment"""
+    f = PlanFacts(dense_scale=1.0, n_streams=4)
+    for k, v in facts.items():
+        setattr(f, k, v)
+    row = WindowPlan()
+    if load().dne_debug_plan_act(int(kind), int(nact), C.byref(f), int(n), C.byref(row)) != 0:
+        raise DneError(load().dne_last_error(None).decode())
+    return row
+
+
 def debug_knob(kind, nact, name):
     """the value dne_create would read for one DNE_* knob under the current environment (-1: no such knob)"""
     return load().dne_debug_knob(int(kind), int(nact), name.encode())

@@ -175,6 +175,10 @@ typedef struct { /* one window of a burst: groups [lo, lo + cnt) of the active l
  * whole_eval != 0: writes no rows and returns dne_profile.fc_full_kind of an evaluation that STARTS at that width. */
 int dne_debug_plan(int kind, int n_actions, const dne_plan_facts *facts, int total, int gsize, dne_window_plan *out, int cap, int *nsub,
                    int whole_eval);
+/* What dne_act (and dne_env_step) of n members launches on such an engine: outside an evaluation the members are one window of single
+ * members under no burst regime (csrc/plan.h: act_window).  Writes that one row (lo = 0, cnt = n); returns 0, or -1 for DNE_KIND_MAZE
+ * and n < 1.  Of the facts only kind and members_materialized matter (dne_set_members clears the latter).  No GPU, no handle. */
+int dne_debug_plan_act(int kind, int n_actions, const dne_plan_facts *facts, int n, dne_window_plan *out);
 /* the value of one knob (by its DNE_* name) after defaults, environment and clamping, as dne_create would see it; -1: no such knob */
 int dne_debug_knob(int kind, int n_actions, const char *name);
 

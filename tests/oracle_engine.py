@@ -19,6 +19,8 @@ class OracleEngine:
         self.opt = None
         self.envs = [O.WrappedEnv() for _ in range(4)]
         self.members = None
+        self.bases = {}          # base slots above 0 (ga_rebuild / ga_rebuild_powers into a slot); slot 0 is self.theta
+        self._frames = None      # env_set_observation's frames, until the environments move again
         self.calls = []
 
     def close(self):
@@ -58,7 +60,15 @@ class OracleEngine:
 
     def _member_theta(self, i):
         slot, off, scale = self.members
-        return self.theta + np.float32(scale[i]) * self.noise[off[i]:off[i] + self.P]
+        base = self.theta if int(slot[i]) == 0 or int(slot[i]) not in self.bases else self.bases[int(slot[i])]
+        return base + np.float32(scale[i]) * self.noise[off[i]:off[i] + self.P]
+
+    def _oracle_theta(self, i):
+        """member i's vector in the layout the oracle's network reads (subclasses with a layout of their own expand it)"""
+        return self._member_theta(i)
+
+    def _has_ref_pass(self):
+        return self.kind == O.KIND_ES
 
     def es_eval(self, idx, sigma, tslimit, seeds, want_bc=False):
         self.calls.append(("es_eval", len(idx)))
@@ -141,6 +151,8 @@ class OracleEngine:
         th = O.ga_rebuild(self.L, self.noise, seeds, sigma)
         if slot == 0:
             self.theta = th.copy()
+        else:
+            self.bases[int(slot)] = th.copy()
         return th
 
     def ga_eval(self, chains, sigma, tslimit, seeds, want_bc=False):
@@ -154,7 +166,10 @@ class OracleEngine:
         self.scale_by = np.asarray(scale_by, np.float32)
 
     def ga_rebuild_powers(self, slot, seeds, copy_out=True):
-        return O.ga_gpu_rebuild(self.noise, seeds, self.scale_by)
+        th = O.ga_gpu_rebuild(self.noise, seeds, self.scale_by)
+        if slot != 0:
+            self.bases[int(slot)] = th.copy()
+        return th
 
     def ga_eval_powers(self, genomes, tslimit, seeds, want_bc=False):
         self.calls.append(("ga_eval_powers", len(genomes)))
@@ -208,14 +223,18 @@ class OracleEngine:
 
     # single-env ABI (slot 0) used by HipAtariEnv / Policy.rollout
     def env_reset(self, seeds):
+        self._frames = None
         for e, s in zip(self.envs, seeds):
             e.reset(int(s))
 
     def env_step(self, actions):
+        self._frames = None
         out = [self.envs[i].step(int(a)) for i, a in enumerate(np.atleast_1d(actions))]
         return np.array([o[1] for o in out], np.float32), np.array([o[2] for o in out], bool)
 
     def env_observation(self, n):
+        if self._frames is not None:
+            return self._frames[:n].copy()
         return np.stack([self.envs[i].ob() for i in range(n)])
 
     def env_ram(self, n):
@@ -223,22 +242,37 @@ class OracleEngine:
 
     def env_set_observation(self, obs):
         self._obs = np.asarray(obs, np.uint8)
+        self._frames = self._obs.copy()
 
     def ref_pass(self, n):
-        if self.kind != O.KIND_ES:
+        if not self._has_ref_pass():
             self._bn = [None] * n
             return
-        both = [O.es_ref_pass_moments(self.L, self._member_theta(i), self.ref) for i in range(n)]
+        both = [O.es_ref_pass_moments(self.L, self._oracle_theta(i), self.ref) for i in range(n)]
         self._bn, self._mom = [b for b, _ in both], [m for _, m in both]
+
+    def get_bn(self, n):
+        return np.stack(self._bn[:n])
 
     def get_bn_moments(self, n):
         return np.stack(self._mom[:n])
 
     def act(self, n):
         acts, lgs = [], []
+        self._acted = []         # (member, bn, frame) of every decision, for debug_activations
         for i in range(n):
             ob = self._obs[i] if getattr(self, "_obs", None) is not None else self.envs[i].ob()
-            a, lg = O.act(self.L, self._member_theta(i), self._bn[i] if self.kind == O.KIND_ES else None, ob)
+            bn = self._bn[i] if self._has_ref_pass() else None
+            a, lg = O.act(self.L, self._oracle_theta(i), bn, ob)
             acts.append(a); lgs.append(lg)
+            self._acted.append((i, bn, ob))
         self._obs = None
         return np.array(acts, np.int32), np.stack(lgs)
+
+    def debug_activations(self, member):
+        i, bn, ob = self._acted[member]
+        return O.forward_debug(self.L, self._oracle_theta(i), bn, ob)[:3]
+
+    def debug_activations_large(self, member):
+        i, _, ob = self._acted[member]
+        return O.forward_large_debug(self.L, self._oracle_theta(i), ob)[:4]

@@ -2,7 +2,8 @@
 
 plan.h decides, from the DNE_* knobs (one table), a few facts about the member set and the active count, everything engine.hip's launchers
 do for a window of a burst.  Here: the default regime table, the GPU suite's own mirror of the window cut (test_gpu_step_taps._windows),
-that every knob set the GPU suite forces reaches the kernel its comment names, and the knob table's clamping and normalisations."""
+that every knob set the GPU suite forces reaches the kernel its comment names, the knob table's clamping and normalisations, and the plan of
+dne_act / dne_env_step by member count (dne_debug_plan_act), whose rows tests/test_gpu_frames.py asserts before it launches."""
 import os
 
 import pytest
@@ -409,3 +410,74 @@ def test_knob_normalisations_and_their_order(monkeypatch):
     monkeypatch.setenv("DNE_SPEC_MAX", "64")
     assert [knob(KIND_ES, "DNE_SPEC_MAX", nact) for nact in (18, 31)] == [64, 0]
     assert _plan(KIND_ES, 2, **ES_FACTS)[0].spec == 1 and _lib.debug_plan(KIND_ES, 31, 2, 2, **ES_FACTS)[0].spec == 0
+
+
+# ---- 5. the plan of dne_act / dne_env_step (act_window: one window of single members, outside any evaluation) -----------------------------------
+def _act(kind, n, nact=NACT, **facts):
+    w = _lib.debug_plan_act(kind, nact, n, **facts)
+    assert (w.lo, w.cnt, w.tail, w.spec, w.head_fused, w.render_fused, w.act2, w.chain) == (0, n, 0, 0, 0, 0, 0, 0), n   # no fused tail of any kind, raw y2
+    return w
+
+
+def _act_row(kind, n, **facts):
+    w = _act(kind, n, **facts)
+    return (n, _conv(w), (w.s1, w.s2) if _conv(w) == "split" else None, _fc(w))
+
+
+def test_act_plan_default_rows():
+    """the member counts at which an act changes kernels, READ from the knobs; the rows they give are frames_support.ACT_ROWS, the literals
+    tests/test_gpu_frames.py asserts before it launches anything"""
+    import frames_support as F
+    knob = lambda name: _lib.debug_knob(KIND_ES, NACT, name)
+    tailk, c12t, tail, fused = knob("DNE_FC_TAILK_MAX"), knob("DNE_CONV12T_MAX"), knob("DNE_FC_TAIL_MAX"), knob("DNE_CONV_FUSED_MIN")
+    assert tailk < c12t < tail < fused - 1 <= knob("DNE_CONV_SPLIT_MID") and knob("DNE_CONV_SPLIT_MAX") < c12t and knob("DNE_FC_QUAD_MAX") < tailk
+    counts = (tailk, tailk + 1, c12t, c12t + 1, tail, tail + 1, fused - 1, fused, fused + 2)
+    want = ((counts[0], "k_conv12t", None, "k_fc_tail"), (counts[1], "k_conv12t", None, "k_fc_cols"), (counts[2], "k_conv12t", None, "k_fc_cols"),
+            (counts[3], "split", (4, 2), "k_fc_cols"), (counts[4], "split", (4, 2), "k_fc_cols"), (counts[5], "split", (4, 2), "k_fc"),
+            (counts[6], "split", (4, 2), "k_fc"), (counts[7], "k_conv12", None, "k_fc"), (counts[8], "k_conv12", None, "k_fc"))
+    assert want == F.ACT_ROWS                                        # (the defaults are the ones the GPU cases were written for)
+    for kind in (KIND_ES, _lib.KIND_ES_VBN, KIND_GA):
+        assert tuple(_act_row(kind, n, **F.act_facts()) for n in counts) == want, kind
+        assert [_fc(_act(kind, n)) for n in (1, knob("DNE_FC_QUAD_MAX"), knob("DNE_FC_QUAD_MAX") + 1)] == ["k_fc_quad", "k_fc_quad", "k_fc_tail"]
+        assert _act_row(kind, 131, nact=3, **F.act_facts()) == (131, "k_conv12", None, "k_fc")
+    # the act plan is plan_window under the empty plan: facts an evaluation's burst reads (pairs, the ring's buffers) change nothing ...
+    for n in counts:
+        a, b = _act(KIND_ES, n), _act(KIND_ES, n, **ES_FACTS)
+        assert all(getattr(a, f) == getattr(b, f) for f, _ in _lib.WindowPlan._fields_ if f != "reserved"), n
+    # ... and GA children written out (an act right behind dne_ga_eval, before any dne_set_members) have no k_fc_cols form
+    assert [_fc(_act(KIND_GA, n, **GA_FACTS)) for n in (tailk, tailk + 1, tail, tail + 1)] == ["k_fc_tail", "k_fc_tail", "k_fc_tail", "k_fc"]
+    # the render side of dne_env_step: one workgroup per member, 1024 threads up to 192 members
+    assert [(_act(KIND_ES, n).render_bands, _act(KIND_ES, n).render_wg) for n in (32, 192, 193)] == [(1, 1024), (1, 1024), (1, 512)]
+
+
+def test_act_plan_knob_rows(monkeypatch):
+    import frames_support as F
+    assert [(k, n) for k, n, *_ in F.ACT_KNOB_ROWS] == [({"DNE_CONV12T_MAX": "0"}, 32), ({"DNE_CONV_FUSED": "0"}, 257)]
+    for knobs, n, conv, split, fc in F.ACT_KNOB_ROWS:
+        assert _act_row(KIND_ES, n, **F.act_facts())[1] != conv     # (without the knob: k_conv12t / k_conv12)
+        with monkeypatch.context() as m:
+            _set(m, knobs)
+            assert _act_row(KIND_ES, n, **F.act_facts()) == (n, conv, split, fc), knobs
+    assert [(r[2], r[3]) for r in F.ACT_KNOB_ROWS] == [("split", (7, 4)), ("split", (1, 2))]
+
+
+def test_act_plan_large_rows():
+    import frames_support as F
+    cols = _lib.debug_knob(KIND_LARGE, NACT, "DNE_LFC_COLS_MAX")
+    counts = (cols, cols + 1, 129, 257)                             # (k_lconv1 / k_lconv_mfma's 128 and 256 are no knobs)
+    rows = []
+    for n in counts:
+        w = _act(KIND_LARGE, n, **F.act_facts())
+        assert _conv(w) == "lconv" and w.s1 == w.s2
+        rows.append((n, w.s1, _fc(w)))
+    assert tuple(rows) == F.ACT_LARGE_ROWS == ((96, 4, "k_lfc_cols"), (97, 4, "k_lfc"), (129, 2, "k_lfc"), (257, 1, "k_lfc"))
+    assert [_act(KIND_LARGE, n).s1 for n in (128, 256)] == [4, 2]
+    # single members never take the pair kernel, whatever the member set looks like
+    assert _fc(_act(KIND_LARGE, 98, antithetic_slot0=1, uniform_base=1)) == "k_lfc"
+
+
+def test_act_plan_refuses_what_dne_act_refuses():
+    with pytest.raises(_lib.DneError, match="MAZE"):
+        _lib.debug_plan_act(_lib.KIND_MAZE, 2, 8)
+    with pytest.raises(_lib.DneError, match="at least 1"):
+        _lib.debug_plan_act(KIND_ES, NACT, 0)

@@ -65,6 +65,12 @@ class OracleVBNEngine(OracleEngine):
         self.P = layouts(n_actions)[0][1]
         self.theta = np.zeros(self.P, np.float32)
 
+    def _oracle_theta(self, i):
+        return expand(self._member_theta(i), self.n_actions)
+
+    def _has_ref_pass(self):
+        return True
+
     def es_eval(self, idx, sigma, tslimit, seeds, want_bc=False):
         assert not want_bc
         self.calls.append(("es_eval", len(idx)))
