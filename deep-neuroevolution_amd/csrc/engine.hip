@@ -618,6 +618,7 @@ struct dne_handle {
     float *ref_f32 = nullptr;        // the reference frames as padded planar floats (k_conv1_ref_shared)
     int32_t *m_slot = nullptr; int64_t *m_off = nullptr; float *m_scale = nullptr;
     std::vector<int32_t> host_slot; std::vector<int64_t> host_off; std::vector<float> host_scale;   // what dne_set_members uploaded
+    std::vector<int32_t> host_caller;   // the caller's index of each of those members (dne_ga_eval* reorders them; otherwise the identity)
     float *bn = nullptr, *bn_mom = nullptr;
     uint8_t *ram_prev = nullptr, *ram_cur = nullptr, *stacks = nullptr;
     ResizeLds *tables = nullptr;
@@ -973,6 +974,20 @@ static int grow_bases(dne_handle *h, int cap) {
     return 0;
 }
 
+// A base slot above 0 the caller writes (dne_set_theta, dne_ga_rebuild, dne_ga_rebuild_powers) is the caller's from then on: the GA store
+// neither hands it out again nor goes on believing that it holds what the store once put there.  A parent cached in it is forgotten
+// (its chain is rebuilt elsewhere when next needed), and it is no longer a slot for materialised children.  dne_ga_set_init_scale
+// takes every slot but 0 back.
+static void claim_slot(dne_handle *h, int slot) {
+    if (slot < 1) return;
+    h->free_slots.erase(std::remove(h->free_slots.begin(), h->free_slots.end(), slot), h->free_slots.end());
+    h->child_slots.erase(std::remove(h->child_slots.begin(), h->child_slots.end(), slot), h->child_slots.end());
+    for (auto it = h->ga_cache.begin(); it != h->ga_cache.end();) {
+        if (it->second == slot) it = h->ga_cache.erase(it);
+        else ++it;
+    }
+}
+
 extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
     *out = nullptr;
     int ndev = 0;
@@ -1314,6 +1329,7 @@ extern "C" int dne_set_theta(dne_handle *h, int slot, const float *theta, size_t
     if (n != (size_t)h->L.P) return h->fail("dne_set_theta: expected %d parameters, got %zu", h->L.P, n);
     if (slot < 0) return h->fail("bad slot");
     if (grow_bases(h, slot + 1)) return -1;
+    claim_slot(h, slot);
     HCHECK(h, hipMemcpy(h->bases + (size_t)slot * h->base_stride, theta, n * sizeof(float), hipMemcpyHostToDevice));
     return 0;
 }
@@ -1476,7 +1492,21 @@ extern "C" int dne_set_members(dne_handle *h, int n, const int32_t *slot, const 
     for (int i = 0; i < n && h->pair_sigma_uniform; i += 2) h->pair_sigma_uniform = scale[i] == scale[0];
     h->members_materialized = false;
     h->host_slot.assign(slot, slot + n); h->host_off.assign(off, off + n); h->host_scale.assign(scale, scale + n);
+    h->host_caller.resize(n);
+    for (int i = 0; i < n; i++) h->host_caller[i] = i;
     return 0;
+}
+
+// the member table as the kernels will read it (the engine's order), and whose member each row is; no kernel is launched
+extern "C" int dne_debug_members(dne_handle *h, int cap, int32_t *slot, int64_t *off, float *scale, int32_t *caller_index) {
+    const int n = (int)h->host_slot.size();
+    for (int i = 0; i < n && i < cap; i++) {
+        if (slot) slot[i] = h->host_slot[i];
+        if (off) off[i] = h->host_off[i];
+        if (scale) scale[i] = h->host_scale[i];
+        if (caller_index) caller_index[i] = h->host_caller[i];
+    }
+    return n;
 }
 
 // policies.py:399: the reference batch through every member's perturbed network -> per-member BN scale/shift
@@ -2279,7 +2309,7 @@ extern "C" int dne_ga_rebuild(dne_handle *h, int slot, const int64_t *seeds, int
     if (h->L.kind != DNE_KIND_GA) return h->fail("dne_ga_rebuild needs a GAAtariPolicy engine (LargeModel genomes carry per-seed powers: dne_ga_rebuild_powers)");
     if (slot < 0 || nseeds < 1) return h->fail("bad arguments");
     if (grow_bases(h, slot + 1)) return -1;
-    h->free_slots.erase(std::remove(h->free_slots.begin(), h->free_slots.end(), slot), h->free_slots.end());
+    claim_slot(h, slot);
     if (build_chain(h, slot, seeds, nullptr, nseeds, sigma, -1, 0)) return -1;
     HCHECK(h, hipGetLastError());
     HCHECK(h, hipStreamSynchronize(h->stream));
@@ -2294,7 +2324,7 @@ extern "C" int dne_ga_rebuild_powers(dne_handle *h, int slot, const int64_t *see
     if (es_like(h->L.kind)) return h->fail("dne_ga_rebuild_powers needs a GA engine");
     if (slot < 0 || nseeds < 1 || !powers) return h->fail("bad arguments");
     if (grow_bases(h, slot + 1)) return -1;
-    h->free_slots.erase(std::remove(h->free_slots.begin(), h->free_slots.end(), slot), h->free_slots.end());
+    claim_slot(h, slot);
     if (build_chain(h, slot, seeds, powers, nseeds, 0.0f, -1, 0)) return -1;
     HCHECK(h, hipGetLastError());
     HCHECK(h, hipStreamSynchronize(h->stream));
@@ -2314,11 +2344,6 @@ static int ga_eval_impl(dne_handle *h, const int32_t *co, const int64_t *seeds, 
     if (powers && !h->init_scale) return h->fail("genomes with per-seed powers need dne_ga_set_init_scale first");
     const int stride = powers ? 2 : 1;   // cache key: the seeds, interleaved with the bit patterns of their powers
     const int mode = powers ? 2 : 1;
-    if (h->ga_cache_mode != mode || (!powers && h->ga_cache_sigma != sigma)) {   // cached parents were built under other rules
-        for (auto &kv : h->ga_cache) h->free_slots.push_back(kv.second);
-        h->ga_cache.clear();
-        h->ga_cache_mode = mode; h->ga_cache_sigma = sigma;
-    }
     auto key_of = [&](const int64_t *c, const float *pw, int len) {
         std::vector<int64_t> k((size_t)len * stride);
         for (int j = 0; j < len; j++) {
@@ -2341,6 +2366,12 @@ static int ga_eval_impl(dne_handle *h, const int32_t *co, const int64_t *seeds, 
         if (len == 1) { prefix[i] = key_of(c, pw, 1); off[i] = c[0]; sc[i] = 0.0f; }
         else { prefix[i] = key_of(c, pw, len - 1); off[i] = c[len - 1]; sc[i] = powers ? pw[len - 1] : sigma; }
         needed[prefix[i]] = -1;
+    }
+    // (only now: a call refused above leaves the store as it was)
+    if (h->ga_cache_mode != mode || (!powers && h->ga_cache_sigma != sigma)) {   // cached parents were built under other rules
+        for (auto &kv : h->ga_cache) h->free_slots.push_back(kv.second);
+        h->ga_cache.clear();
+        h->ga_cache_mode = mode; h->ga_cache_sigma = sigma;
     }
     size_t fresh = 0;
     for (auto &kv : needed) fresh += h->ga_cache.count(kv.first) ? 0 : 1;
@@ -2463,6 +2494,7 @@ static int ga_eval_impl(dne_handle *h, const int32_t *co, const int64_t *seeds, 
     }
     if (dne_set_members(h, n, pslot.data(), poff.data(), psc.data())) return -1;
     h->members_materialized = h->k.ga_materialize != 0;   // (dne_set_members clears it: a caller's own members carry noise)
+    h->host_caller.assign(order.begin(), order.end());
     std::vector<float> pret(n), psg(n); std::vector<int32_t> plen(n); std::vector<uint8_t> pbc(bc ? (size_t)n * 128 : 0);
     if (eval_core(h, n, 1, tslimit, pseed.data(), pret.data(), psg.data(), plen.data(), bc ? pbc.data() : nullptr)) return -1;
     for (int j = 0; j < n; j++) {

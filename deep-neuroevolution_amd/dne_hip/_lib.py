@@ -376,6 +376,18 @@ class Engine:
         self._ck(self.lib.dne_act(self.h, int(n), _ptr(actions, C.c_int32), _ptr(logits, C.c_float)))
         return actions, logits
 
+    def debug_members(self):
+        """dne_debug_members: the current members in the engine's order, as the kernels will read them -> (slot int32 [n], off int64 [n],
+        scale float32 [n], caller_index int32 [n]); caller_index[j] = the caller's index of engine member j (ga_eval* may reorder)"""
+        n = self.lib.dne_debug_members(self.h, 0, None, None, None, None)
+        if n < 0:
+            raise DneError(self.lib.dne_last_error(self.h).decode())
+        slot = np.empty(n, np.int32); off = np.empty(n, np.int64); scale = np.empty(n, np.float32); who = np.empty(n, np.int32)
+        got = self.lib.dne_debug_members(self.h, n, _ptr(slot, C.c_int32), _ptr(off, C.c_int64), _ptr(scale, C.c_float), _ptr(who, C.c_int32))
+        if got != n:
+            raise DneError("dne_debug_members: %d members, then %d" % (n, got))
+        return slot, off, scale, who
+
     def debug_activations_large(self, member):
         """LargeModel: raw conv1 [441*32], conv2 / conv3 [121*64] and fc [512] outputs of one member after act()"""
         y1 = np.empty(14112, np.float32); y2 = np.empty(7744, np.float32); y3 = np.empty(7744, np.float32); y4 = np.empty(512, np.float32)

@@ -106,6 +106,10 @@ int dne_noise_write(dne_handle *h, size_t offset, const float *host, size_t coun
 int dne_noise_get(dne_handle *h, int64_t idx, int dim, float *out_host);        /* es.py:63-64 get(i, dim) */
 
 /* ---- flat parameters (tf_util.py:224-246 SetFromFlat/GetFlat; policies.py:99-103) -------------------- */
+/* Base slots are shared with the GA store: dne_ga_eval* keeps its parents (and, with DNE_GA_MATERIALIZE, its children) in slots above 0
+ * of its own choosing.  A slot above 0 that the caller writes -- dne_set_theta, dne_ga_rebuild, dne_ga_rebuild_powers -- stays the caller's
+ * until dne_ga_set_init_scale, which frees every slot but 0: the store never hands it out or overwrites it, and a parent it had cached
+ * there is forgotten and rebuilt in another slot when next needed. */
 int dne_set_theta(dne_handle *h, int slot, const float *theta, size_t n); /* slot 0 = the ES parent theta */
 int dne_get_theta(dne_handle *h, int slot, float *out, size_t n);
 int dne_set_ref_batch(dne_handle *h, const uint8_t *ref /*[ref_count][84][84][4]*/, int count); /* policies.py:332-335 */
@@ -136,6 +140,12 @@ int dne_get_bn(dne_handle *h, int n, float *out /*[n][608] scale,shift per layer
 int dne_get_bn_moments(dne_handle *h, int n, float *out);
 int dne_act(dne_handle *h, int n, int32_t *actions, float *logits /*[n][n_actions] or NULL*/);
 int dne_debug_activations(dne_handle *h, int member, float *y1 /*7056*/, float *y2 /*3872*/, float *y3 /*256*/);
+/* The current members as the kernels will read them, in the engine's order: base slot, noise offset and scale of each (member i uses
+ * base[slot[i]] + scale[i] * noise[off[i]:], as under dne_set_members), and caller_index[i] = the caller's index of engine member i.
+ * dne_ga_eval* may reorder its members (DNE_GA_SORT) and, with DNE_GA_MATERIALIZE, points them at written-out vectors with scale 0;
+ * after dne_set_members and dne_es_eval caller_index is the identity.  Returns the number of current members and fills at most cap
+ * entries of each array (any may be NULL).  Launches no kernel; every kind. */
+int dne_debug_members(dne_handle *h, int cap, int32_t *slot, int64_t *off, float *scale, int32_t *caller_index);
 /* LargeModel engines (DNE_KIND_GA_LARGE): raw outputs of conv1 [441*32], conv2 / conv3 [121*64] and the fc [512] of one member after
    dne_act -- kernel-level parity against the oracle's orc_forward_large_debug (models/dqn.py:39-47). */
 int dne_debug_activations_large(dne_handle *h, int member, float *y1, float *y2, float *y3, float *y4);
@@ -199,7 +209,7 @@ int dne_eval_members(dne_handle *h, int n, int tslimit, const uint32_t *env_seed
 int dne_ga_eval(dne_handle *h, const int32_t *chain_offsets /*n+1*/, const int64_t *seeds, int n, float sigma,
                 int tslimit, const uint32_t *env_seed, float *returns, float *signreturns, int32_t *lengths,
                 uint8_t *bc);
-/* ga.py:151-158 / 256-264: rebuild one genome into base slot `slot` (and optionally copy it out) */
+/* ga.py:151-158 / 256-264: rebuild one genome into base slot `slot` (and optionally copy it out); a slot above 0 becomes the caller's (see dne_set_theta) */
 int dne_ga_rebuild(dne_handle *h, int slot, const int64_t *seeds, int nseeds, float sigma, float *out_host);
 
 /* The gpu tree's genome form (gpu_implementation/neuroevolution/models/base.py:118-149, ga.py:161-166): seeds =
