@@ -29,6 +29,7 @@
 #include "novelty.h"
 #include "plan.h"
 #include "maze.h"
+#include "maze_novelty.h"
 
 using namespace dne;
 
@@ -632,6 +633,11 @@ struct dne_handle {
     bool maze = false;               // DNE_KIND_MAZE: whole episodes in k_maze_rollout (csrc/maze.h); none of the Atari buffers exist
     maze::Header maze_hdr{}; float *maze_walls = nullptr; int maze_nw = 0;   // dne_maze_set_walls
     float *maze_xy = nullptr; int maze_last_n = 0;   // final (x, y) per member of the last evaluation, and how many members that was
+    // novelty on the maze (csrc/maze_novelty.h): the archive of (x, y) points in insertion order, host members' points, the n results
+    float *mzn_arch = nullptr; size_t mzn_arch_cap = 0; int mzn_arch_n = 0;
+    float *mzn_xy = nullptr; size_t mzn_xy_cap = 0;
+    double *mzn_out = nullptr; size_t mzn_out_cap = 0;
+    double mzn_last_ms = -1.0;
     bool large = false;              // DNE_KIND_GA_LARGE: y1 [441][32], y2 / y3 [121][64] (conv3 output), y3t = the 512 fc outputs
     float *y1r[2] = {nullptr, nullptr}, *y2r[2] = {nullptr, nullptr}, *y3pr[2] = {nullptr, nullptr};   // reference pass scratch, two ways
     float *fr1[2] = {nullptr, nullptr}, *fr2[2] = {nullptr, nullptr};   // per-frame batch-norm moments of conv1 / conv2 ([rows][2][C])
@@ -2188,6 +2194,116 @@ extern "C" int dne_maze_debug_math(dne_handle *h, int fn, const double *x, int n
     HCHECK(h, hipGetLastError());
     HCHECK(h, hipStreamSynchronize(h->stream));
     HCHECK(h, hipMemcpy(out, dout, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------- novelty on the hard maze (csrc/maze_novelty.h)
+constexpr size_t MZN_ARCH_CAP0 = 64;   // points of the archive's first allocation; it doubles from there
+
+// the buffer holds at least `need` elements afterwards; the first `keep` survive a reallocation (copied on the engine's stream)
+template <typename T>
+static int mzn_reserve(dne_handle *h, T *&p, size_t &cap, size_t need, size_t keep, size_t floor, const char *name) {
+    if (need <= cap) return 0;
+    const size_t ncap = std::max(std::max(2 * cap, need), floor);
+    T *q = nullptr;
+    HCHECK(h, h->alloc(&q, ncap, name));
+    if (p && keep) HCHECK(h, hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));   // whatever still reads or fills the old buffer has finished
+    HCHECK(h, h->release(p));
+    p = q; cap = ncap;
+    return 0;
+}
+
+#define MZN_NEEDS_MAZE(h, call)                                                                 \
+    do {                                                                                        \
+        if (!(h)->maze) return (h)->fail("%s needs a DNE_KIND_MAZE engine (this one: kind %d)", call, (h)->L.kind); \
+    } while (0)
+
+// xy == NULL: the last evaluation's members where k_maze_rollout left them
+static int mzn_check_members(dne_handle *h, const char *call, const float *xy, int n) {
+    if (n < 1) return h->fail("%s: n = %d, at least one point is needed", call, n);
+    if (!xy && n > h->maze_last_n) return h->fail("%s: %d members asked for, the last evaluation ran %d", call, n, h->maze_last_n);
+    return 0;
+}
+
+extern "C" int dne_maze_archive_append(dne_handle *h, const float *xy, int n) {
+    DeviceGuard dg(h);
+    MZN_NEEDS_MAZE(h, "dne_maze_archive_append");
+    if (mzn_check_members(h, "dne_maze_archive_append", xy, n)) return -1;
+    const size_t have = (size_t)h->mzn_arch_n;
+    if (have + (size_t)n > (size_t)INT_MAX / 2) return h->fail("dne_maze_archive_append: %zu points would not fit an int", have + (size_t)n);
+    if (mzn_reserve(h, h->mzn_arch, h->mzn_arch_cap, 2 * (have + n), 2 * have, 2 * MZN_ARCH_CAP0, "maze_archive")) return -1;
+    if (xy) {
+        HCHECK(h, hipMemcpyAsync(h->mzn_arch + 2 * have, xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HCHECK(h, hipStreamSynchronize(h->stream));   // the caller's buffer is free again
+    } else {
+        HCHECK(h, hipMemcpyAsync(h->mzn_arch + 2 * have, h->maze_xy, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    }
+    h->mzn_arch_n += n;
+    return 0;
+}
+
+extern "C" int dne_maze_archive_clear(dne_handle *h) {
+    DeviceGuard dg(h);
+    MZN_NEEDS_MAZE(h, "dne_maze_archive_clear");
+    h->mzn_arch_n = 0;   // (the buffer stays; a later append lands behind every call already on the stream)
+    return 0;
+}
+
+extern "C" int dne_maze_archive_size(dne_handle *h) {
+    MZN_NEEDS_MAZE(h, "dne_maze_archive_size");
+    return h->mzn_arch_n;
+}
+
+extern "C" int dne_maze_archive_get(dne_handle *h, float *xy, int cap) {
+    DeviceGuard dg(h);
+    MZN_NEEDS_MAZE(h, "dne_maze_archive_get");
+    if (cap < h->mzn_arch_n) return h->fail("dne_maze_archive_get: room for %d points, the archive holds %d", cap, h->mzn_arch_n);
+    if (h->mzn_arch_n > 0) {
+        if (!xy) return h->fail("dne_maze_archive_get: no buffer");
+        HCHECK(h, hipMemcpyAsync(xy, h->mzn_arch, (size_t)h->mzn_arch_n * 2 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HCHECK(h, hipStreamSynchronize(h->stream));
+    }
+    return 0;
+}
+
+extern "C" int dne_maze_novelty(dne_handle *h, const float *xy, int n, int k, double *out) {
+    DeviceGuard dg(h);
+    MZN_NEEDS_MAZE(h, "dne_maze_novelty");
+    if (mzn_check_members(h, "dne_maze_novelty", xy, n)) return -1;
+    if (k < 1) return h->fail("dne_maze_novelty: k = %d, at least one neighbour is needed", k);
+    if (k > DNE_MAZE_NOVELTY_KMAX) return h->fail("dne_maze_novelty: k = %d, the kernel keeps at most DNE_MAZE_NOVELTY_KMAX = %d neighbours", k, DNE_MAZE_NOVELTY_KMAX);
+    if (h->mzn_arch_n < 1) return h->fail("dne_maze_novelty: the archive is empty (dne_maze_archive_append)");
+    if (!out) return h->fail("dne_maze_novelty: no output buffer");
+    const float *pts = h->maze_xy;
+    if (xy) {
+        if (mzn_reserve(h, h->mzn_xy, h->mzn_xy_cap, 2 * (size_t)n, 0, 4096, "maze_novelty_xy")) return -1;
+        HCHECK(h, hipMemcpyAsync(h->mzn_xy, xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        pts = h->mzn_xy;
+    }
+    if (mzn_reserve(h, h->mzn_out, h->mzn_out_cap, (size_t)n, 0, 4096, "maze_novelty_out")) return -1;
+    HCHECK(h, hipEventRecord(h->ev_a, h->stream));
+    hipLaunchKernelGGL(maze_novelty::k_maze_novelty, dim3((n + 3) / 4), dim3(256), 0, h->stream, pts, n, (const float *)h->mzn_arch, h->mzn_arch_n,
+                       std::min(k, h->mzn_arch_n), h->mzn_out);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipEventRecord(h->ev_b, h->stream));
+    HCHECK(h, hipMemcpyAsync(out, h->mzn_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    float ms = 0;
+    HCHECK(h, hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
+    h->mzn_last_ms = ms;
+    return 0;
+}
+
+extern "C" double dne_maze_novelty_last_ms(dne_handle *h) { return h->mzn_last_ms; }
+
+// the same header on the CPU: no handle, no GPU
+extern "C" int dne_maze_novelty_host(const float *xy, int n, const float *archive, int narch, int k, double *out) {
+    if (!xy || !archive || !out) { g_create_error = "dne_maze_novelty_host: a buffer is missing"; return -1; }
+    if (n < 1) { g_create_error = "dne_maze_novelty_host: n = " + std::to_string(n) + ", at least one point is needed"; return -1; }
+    if (narch < 1) { g_create_error = "dne_maze_novelty_host: the archive is empty"; return -1; }
+    if (k < 1) { g_create_error = "dne_maze_novelty_host: k = " + std::to_string(k) + ", at least one neighbour is needed"; return -1; }
+    maze_novelty::novelty_host(xy, n, archive, narch, k, out);
     return 0;
 }
 

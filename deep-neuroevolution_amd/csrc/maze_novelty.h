@@ -1,0 +1,143 @@
+// maze_novelty.h -- nses.py:12-32 for the hard maze's behaviour characterisation, ONE float32 point (x, y) per member (MazeFinalState,
+// tf_maze.py:64-66): the mean distance of a member to its k nearest archive points, as ONE __host__ __device__ text for the arithmetic, a
+// CPU twin (novelty_host, behind dne_maze_novelty_host) and k_maze_novelty for gfx950, which agree bit for bit.  DESIGN.md section 12
+// ("Novelty on the maze") holds the contract:
+//   * d(p, a) = sqrt(dx * dx + dy * dy) with dx = (double)ax - (double)px, dy likewise: IEEE double operations, the sum unfused
+//     (-ffp-contract=off on both passes), sqrt the correctly rounded one (as nv_distance of novelty.h relies on).  nses.py:12-20 on
+//     trajectories of length 1 is this followed by sqrt(d**2 + 0**2), which is dropped;
+//   * the order is (isnan, value, archive slot): every number, +inf included, before every NaN, ties to the lower slot.  A distance is
+//     never negative and never -0.0, so its bit pattern as an unsigned integer orders as the value does; a NaN is sent to one pattern
+//     above +inf's.  That integer is the key both sides sort by (sort_key);
+//   * novelty = (the kk = min(k, narch) first distances of that order, added one by one in that order into a double that starts at 0.0) / kk.
+// No [n][narch] matrix exists on either side.  A plain C++ compiler can include this file (the kernel is behind __HIPCC__):
+// tests/maze_novelty_asan_main.cpp does.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <utility>
+#include <vector>
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define MZN_HD __host__ __device__ __forceinline__
+#else
+#define MZN_HD inline
+#endif
+
+namespace dne {
+namespace maze_novelty {
+
+constexpr int KMAX = 32;          // DNE_MAZE_NOVELTY_KMAX: neighbours a lane keeps in registers
+constexpr int TILE = 1024;        // archive points staged in LDS at a time (8 KiB), shared by a workgroup's four members
+constexpr uint64_t KEY_NAN = 0x7FF8000000000000ull;   // every NaN: above +inf (0x7FF0...), below KEY_NONE
+constexpr uint64_t KEY_NONE = ~0ull;                  // an empty place of a lane's list: after every distance
+
+MZN_HD double distance(float px, float py, float ax, float ay) {
+    const double dx = (double)ax - (double)px, dy = (double)ay - (double)py;
+    return sqrt(dx * dx + dy * dy);
+}
+
+MZN_HD uint64_t sort_key(double d) {
+    if (d != d) return KEY_NAN;
+    uint64_t u;
+#if defined(__HIP_DEVICE_COMPILE__)
+    u = (uint64_t)__double_as_longlong(d);
+#else
+    memcpy(&u, &d, sizeof(u));
+#endif
+    return u;
+}
+
+MZN_HD double key_value(uint64_t key) {
+    double d;
+#if defined(__HIP_DEVICE_COMPILE__)
+    d = __longlong_as_double((long long)key);
+#else
+    memcpy(&d, &key, sizeof(d));
+#endif
+    return d;
+}
+
+// ---- the CPU side: a plain partial sort on (key, slot), then the sum in that order ----------------------------------------------------------
+inline void novelty_host(const float *xy, int n, const float *archive, int narch, int k, double *out) {
+    const int kk = k < narch ? k : narch;
+    std::vector<std::pair<uint64_t, int32_t>> e((size_t)narch);
+    for (int p = 0; p < n; p++) {
+        for (int a = 0; a < narch; a++)
+            e[a] = std::make_pair(sort_key(distance(xy[2 * p], xy[2 * p + 1], archive[2 * (size_t)a], archive[2 * (size_t)a + 1])), (int32_t)a);
+        std::partial_sort(e.begin(), e.begin() + kk, e.end());
+        double s = 0.0;
+        for (int t = 0; t < kk; t++) s += key_value(e[t].first);
+        out[p] = s / (double)kk;
+    }
+}
+
+#if defined(__HIPCC__)
+// ---- the device side --------------------------------------------------------------------------------------------------------------------------
+// grid ceil(n / 4), 256 threads: wave w of block b scores member 4b + w against the whole archive.  The archive goes through LDS in tiles of
+// TILE points that the four waves share; a lane walks points lane, lane + 64, ... of each tile, so what it sees comes in ascending slot
+// order, and keeps its KMAX best (key, slot) pairs sorted in registers: every index below is a compile-time constant after unrolling
+// (a run-time index would send the list to scratch).  `worst` is the list's place kk - 1: a point that does not come before it can be
+// none of this lane's kk best, so none of the wave's, and skips the insert.  After the last tile, kk rounds: the wave-wide minimum over
+// (key, slot) of the lanes' heads is the next distance of the order; the lane that holds it drops its head; every lane adds the value to
+// its own copy of the sum.  Spare waves of a partial last workgroup shadow the last member and write nothing; no wave leaves ahead of a barrier.
+__global__ __launch_bounds__(256) void k_maze_novelty(const float *__restrict__ xy, int n, const float *__restrict__ archive, int narch, int kk,
+                                                      double *__restrict__ out) {
+    __shared__ float2 s_pts[TILE];
+    const int lane = threadIdx.x & 63;
+    int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const bool live = m < n;
+    if (!live) m = n - 1;
+    const float px = xy[2 * (size_t)m], py = xy[2 * (size_t)m + 1];
+    uint64_t key[KMAX];
+    int slot[KMAX];
+#pragma unroll
+    for (int i = 0; i < KMAX; i++) { key[i] = KEY_NONE; slot[i] = INT_MAX; }
+    uint64_t worst = KEY_NONE;
+    for (int t0 = 0; t0 < narch; t0 += TILE) {
+        const int cnt = narch - t0 < TILE ? narch - t0 : TILE;
+        __syncthreads();                            // the tile before this one has been read by every wave
+        for (int i = threadIdx.x; i < cnt; i += 256) s_pts[i] = ((const float2 *)archive)[(size_t)t0 + i];
+        __syncthreads();
+        for (int j = lane; j < cnt; j += 64) {
+            const float2 a = s_pts[j];
+            const uint64_t ck = sort_key(distance(px, py, a.x, a.y));
+            if (ck < worst) {                       // (the candidate's slot is above every slot of the list: on equal keys it comes after)
+                const int cs = t0 + j;
+#pragma unroll
+                for (int i = KMAX - 1; i >= 1; i--) {
+                    const bool shift = key[i - 1] > ck, here = key[i] > ck;
+                    key[i] = shift ? key[i - 1] : here ? ck : key[i];
+                    slot[i] = shift ? slot[i - 1] : here ? cs : slot[i];
+                }
+                if (key[0] > ck) { key[0] = ck; slot[0] = cs; }
+#pragma unroll
+                for (int i = 0; i < KMAX; i++) worst = i == kk - 1 ? key[i] : worst;
+            }
+        }
+    }
+    double sum = 0.0;
+    for (int t = 0; t < kk; t++) {
+        uint64_t bk = key[0];
+        int bs = slot[0];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint64_t ok = (uint64_t)__shfl_xor((long long)bk, o);
+            const int os = __shfl_xor(bs, o);
+            if (ok < bk || (ok == bk && os < bs)) { bk = ok; bs = os; }
+        }
+        if (slot[0] == bs) {                        // an archive slot lives in one lane
+#pragma unroll
+            for (int i = 0; i < KMAX - 1; i++) { key[i] = key[i + 1]; slot[i] = slot[i + 1]; }
+            key[KMAX - 1] = KEY_NONE; slot[KMAX - 1] = INT_MAX;
+        }
+        sum += key_value(bk);
+    }
+    if (lane == 0 && live) out[m] = sum / (double)kk;
+}
+#endif
+
+}  // namespace maze_novelty
+}  // namespace dne

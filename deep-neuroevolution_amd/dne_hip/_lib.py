@@ -16,6 +16,7 @@ KIND_ES, KIND_GA, KIND_GA_LARGE = 0, 1, 2   # DNE_KIND_* (include/dne_hip.h); 2 
 KIND_ES_VBN = 3   # the GPU tree's ModelVirtualBN in its own flat layout (models/batchnorm.py:52-123): the ES kind's network and entry points
 KIND_MAZE = 4     # the GPU tree's hard maze under SimpleClassifier (gym_tensorflow/maze/, models/simple.py:29-35): whole episodes in one kernel (csrc/maze.h)
 MAZE_OBS, MAZE_STEPS, MAZE_TRACE_W, MAZE_MAX_WALLS = 11, 400, 16, 64   # observation width, tf_maze.cpp's episode length, floats per trace row, walls the kernel takes
+MAZE_NOVELTY_KMAX, MAZE_NOVELTY_TILE, MAZE_ARCHIVE_CAP0 = 32, 1024, 64   # csrc/maze_novelty.h: neighbours a lane keeps, archive points per LDS tile; the archive's first allocation (engine.hip)
 ES_KINDS = (KIND_ES, KIND_ES_VBN)   # virtual batch norm over a reference batch, antithetic pairs
 PROC_MODES = {"centered_rank": 0, "sign": 1, "centered_sign_rank": 2}
 OPT_KINDS = {"adam": 0, "sgd": 1}
@@ -73,7 +74,7 @@ class Profile(C.Structure):
 
 def build(force=False):
     """Compile libdne_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dne_hip.h"))
     if os.environ.get("DNE_LIB_PATH"):
         # another build of the same ABI was asked for by name: `make` only knows the in-tree library, so running it here would
@@ -225,6 +226,15 @@ def maze_math_host(fn, x):
     return out
 
 
+def maze_novelty_host(xy, archive, k):
+    """dne_maze_novelty_host: csrc/maze_novelty.h on the CPU (no GPU, no handle) for points xy [n][2] against archive [narch][2] -> float64 [n]"""
+    xy = _arr(xy, np.float32).reshape(-1, 2); archive = _arr(archive, np.float32).reshape(-1, 2)
+    out = np.empty(xy.shape[0], np.float64)
+    _ck_host(load().dne_maze_novelty_host(_ptr(xy, C.c_float), int(xy.shape[0]), _ptr(archive, C.c_float), int(archive.shape[0]), int(k),
+                                          _ptr(out, C.c_double)))
+    return out
+
+
 def _ptr(a, t):
     return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
 
@@ -257,6 +267,7 @@ class Engine:
         self.P = self.lib.dne_num_params(self.kind, self.n_actions)
         self.record_bc = bool(record_bc)
         self.noise_count = 0
+        self._last_eval_n = 0   # members of the last es_eval / eval_members (what the maze's xy=None forms score or append by default)
         self.comm_size = 1
 
     def close(self):
@@ -417,6 +428,7 @@ class Engine:
         bc = self._bc_buf(2 * n, want_bc)
         self._ck(self.lib.dne_es_eval(self.h, _ptr(idx, C.c_int64), n, C.c_float(sigma), int(tslimit), _ptr(seeds, C.c_uint32),
                                       _ptr(ret, C.c_float), _ptr(sg, C.c_float), _ptr(ln, C.c_int32), _ptr(bc, C.c_uint8)))
+        self._last_eval_n = 2 * n
         return (ret, sg, ln, bc) if want_bc else (ret, sg, ln)
 
     def eval_members(self, n, tslimit, env_seed, want_bc=False):
@@ -426,6 +438,7 @@ class Engine:
         bc = self._bc_buf(n, want_bc)
         self._ck(self.lib.dne_eval_members(self.h, int(n), int(tslimit), _ptr(seeds, C.c_uint32), _ptr(ret, C.c_float),
                                            _ptr(sg, C.c_float), _ptr(ln, C.c_int32), _ptr(bc, C.c_uint8)))
+        self._last_eval_n = int(n)
         return (ret, sg, ln, bc) if want_bc else (ret, sg, ln)
 
     def ga_eval(self, chains, sigma, tslimit, env_seed, want_bc=False):
@@ -466,6 +479,51 @@ class Engine:
         out = np.empty((x.size, 2), np.float64)
         self._ck(self.lib.dne_maze_debug_math(self.h, int(fn), _ptr(x, C.c_double), int(x.size), _ptr(out, C.c_double)))
         return out
+
+    # ---- novelty on the hard maze (csrc/maze_novelty.h): BCs are final (x, y) points, the archive lives on the device
+    def _maze_points(self, xy, n):
+        """(host points or None, count): xy=None means the first n members of the last evaluation (all of them without n), read on the device"""
+        if xy is None:
+            return None, int(self._last_eval_n if n is None else n)
+        xy = _arr(xy, np.float32).reshape(-1, 2)
+        if n is not None and int(n) != xy.shape[0]:
+            raise DneError("%d points given, n = %d" % (xy.shape[0], int(n)))
+        return xy, int(xy.shape[0])
+
+    def maze_archive_append(self, xy=None, n=None):
+        """append points [n][2] to the device-resident archive, in order; xy=None: the final positions of the last evaluation's first n
+        members, device to device"""
+        xy, n = self._maze_points(xy, n)
+        self._ck(self.lib.dne_maze_archive_append(self.h, _ptr(xy, C.c_float), n))
+
+    def maze_archive_clear(self):
+        self._ck(self.lib.dne_maze_archive_clear(self.h))
+
+    def maze_archive_size(self):
+        n = self.lib.dne_maze_archive_size(self.h)
+        if n < 0:
+            self._ck(n)
+        return n
+
+    def maze_archive(self):
+        """the archive's points in insertion order, [size][2] float32"""
+        n = self.maze_archive_size()
+        out = np.empty((n, 2), np.float32)
+        self._ck(self.lib.dne_maze_archive_get(self.h, _ptr(out, C.c_float), n))
+        return out
+
+    def maze_novelty(self, k, xy=None, n=None):
+        """nses.py:22-32 on (x, y) points: the mean distance of each point to its min(k, archive size) nearest archive points, float64 [n]
+        (k_maze_novelty; 1 <= k <= MAZE_NOVELTY_KMAX).  xy=None scores the last evaluation's first n members where the rollout left them."""
+        xy, n = self._maze_points(xy, n)
+        out = np.empty(max(n, 0), np.float64)
+        self._ck(self.lib.dne_maze_novelty(self.h, _ptr(xy, C.c_float), n, int(k), _ptr(out, C.c_double)))
+        return out
+
+    def maze_novelty_last_ms(self):
+        """k_maze_novelty of the last maze_novelty call between two device events, milliseconds"""
+        self.lib.dne_maze_novelty_last_ms.restype = C.c_double
+        return float(self.lib.dne_maze_novelty_last_ms(self.h))
 
     # ---- gpu-tree genomes: ((idx0,), (idx1, power1), ...)
     def ga_set_init_scale(self, scale_by):

@@ -328,6 +328,28 @@ int dne_maze_forward_host(const float *theta, const float *obs, int n, float *h1
 int dne_maze_math_host(int fn, const double *x, int n, double *out);
 int dne_maze_debug_math(dne_handle *h, int fn, const double *x, int n, double *out);
 
+/* ---- novelty on the hard maze (csrc/maze_novelty.h) -------------------------------------------
+ * A behaviour characterisation is one float32 point (x, y): a navigator's final position.  nses.py:12-32 on such points: for member p and
+ * archive point a, d = sqrt(dx*dx + dy*dy) in double with dx = (double)ax - (double)px (unfused, correctly rounded sqrt); novelty = the
+ * kk = min(k, archive size) smallest d, ordered by (isnan, value, archive slot), added one by one in that order into a double that starts at
+ * 0.0, divided by kk.  Every number sorts before every NaN; ties go to the lower slot.
+ * The archive is a device buffer of float pairs in insertion order (the slot is the position); it grows geometrically.  Appends, clears and
+ * scoring are ordered on the engine's stream.  xy == NULL means the first n members of the last evaluation, read on the device where
+ * k_maze_rollout left them (1 <= n <= the members the last evaluation ran, as dne_maze_final_state); a host xy takes any n >= 1.
+ * Refused by name: an engine of another kind, an empty archive, k < 1, k > DNE_MAZE_NOVELTY_KMAX, n < 1, cap below the archive's size.  A
+ * refused call leaves the archive as it was.  The byte-trajectory calls above (dne_archive_*, dne_novelty*) keep refusing this kind.
+ * dne_maze_archive_size returns the number of points (-1 on an engine of another kind); dne_maze_archive_get copies them out in order.
+ * dne_maze_novelty_host is the same header on the CPU: no handle, no GPU, any k >= 1.
+ * dne_maze_novelty_last_ms: k_maze_novelty of the last dne_maze_novelty between two device events, in milliseconds (-1 before the first). */
+#define DNE_MAZE_NOVELTY_KMAX 32
+int dne_maze_archive_append(dne_handle *h, const float *xy /*[n][2], or NULL*/, int n);
+int dne_maze_archive_clear(dne_handle *h);
+int dne_maze_archive_size(dne_handle *h);
+int dne_maze_archive_get(dne_handle *h, float *xy /*[cap][2]*/, int cap);
+int dne_maze_novelty(dne_handle *h, const float *xy /*[n][2], or NULL*/, int n, int k, double *out /*[n]*/);
+int dne_maze_novelty_host(const float *xy, int n, const float *archive /*[narch][2]*/, int narch, int k, double *out);
+double dne_maze_novelty_last_ms(dne_handle *h);
+
 #ifdef __cplusplus
 }
 #endif
