@@ -30,6 +30,7 @@
 #include "plan.h"
 #include "maze.h"
 #include "maze_novelty.h"
+#include "maze_ga.h"
 
 using namespace dne;
 
@@ -638,6 +639,13 @@ struct dne_handle {
     float *mzn_xy = nullptr; size_t mzn_xy_cap = 0;
     double *mzn_out = nullptr; size_t mzn_out_cap = 0;
     double mzn_last_ms = -1.0;
+    // Deep-GA on the maze (csrc/maze_ga.h): 3 M slots of base_stride floats apart from `bases` -- the parents' bank as a double buffer
+    // (halves of M slots, mzg_half the live one, mzg_T parents in it), then one scratch slot per member for an evaluation's roots -- and
+    // the member descriptors of dne_maze_ga_eval / dne_maze_ga_promote, apart from dne_set_members' own
+    float *mzg_mem = nullptr; int mzg_half = 0, mzg_T = 0;
+    int32_t *mzg_slot = nullptr; int64_t *mzg_off = nullptr; float *mzg_scale = nullptr;
+    int32_t *mzg_chain_offs = nullptr; int64_t *mzg_seeds = nullptr; float *mzg_powers = nullptr; size_t mzg_chain_cap = 0;
+    std::vector<int32_t> mzg_host_slot; std::vector<float> mzg_host_scale;   // what dne_maze_ga_eval uploaded
     bool large = false;              // DNE_KIND_GA_LARGE: y1 [441][32], y2 / y3 [121][64] (conv3 output), y3t = the 512 fc outputs
     float *y1r[2] = {nullptr, nullptr}, *y2r[2] = {nullptr, nullptr}, *y3pr[2] = {nullptr, nullptr};   // reference pass scratch, two ways
     float *fr1[2] = {nullptr, nullptr}, *fr2[2] = {nullptr, nullptr};   // per-frame batch-norm moments of conv1 / conv2 ([rows][2][C])
@@ -2083,15 +2091,15 @@ static maze::RolloutArgs maze_args(dne_handle *h, int first, int count, int tsli
     return A;
 }
 
-// members [0, n) set by dne_set_members, one whole episode each, one launch
-static int maze_eval(dne_handle *h, int n, int tslimit, float *returns, float *signreturns, int32_t *lengths, uint8_t *bc_out) {
+// members [0, n) of A's descriptors, one whole episode each, one launch
+static int maze_eval_args(dne_handle *h, maze::RolloutArgs A, int n, int tslimit, float *returns, float *signreturns, int32_t *lengths, uint8_t *bc_out) {
     if (h->maze_nw < 1) return h->fail("DNE_KIND_MAZE: no maze loaded (dne_maze_set_walls comes before an evaluation)");
     if (tslimit <= 0) return h->fail("timestep limit must be positive");
     if (bc_out && !h->bc) return h->fail("behaviour characterisations requested but the engine was created with record_bc = 0");
     if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
     const size_t bc_floats = (size_t)n * std::max(h->cfg.bc_max_steps, 1) * 2;
     if (h->bc && bc_out) HCHECK(h, hipMemsetAsync(h->bc, 0, bc_floats * sizeof(float), h->stream));   // rows past an episode's length read as zero
-    maze::RolloutArgs A = maze_args(h, 0, n, tslimit);
+    A.first = 0; A.count = n; A.hdr = h->maze_hdr; A.walls = h->maze_walls; A.nw = h->maze_nw; A.tslimit = tslimit;
     A.ret = h->ret; A.sign = h->sign; A.len = h->len; A.xy = h->maze_xy;
     A.bc = (float *)h->bc; A.bc_max_steps = h->bc ? std::max(h->cfg.bc_max_steps, 1) : 0;
     HCHECK(h, hipEventRecord(h->ev_a, h->stream));
@@ -2112,6 +2120,11 @@ static int maze_eval(dne_handle *h, int n, int tslimit, float *returns, float *s
     P.fc_launches = 1;
     for (int i = 0; i < n; i++) P.env_steps += lengths[i];
     return 0;
+}
+
+// members [0, n) set by dne_set_members
+static int maze_eval(dne_handle *h, int n, int tslimit, float *returns, float *signreturns, int32_t *lengths, uint8_t *bc_out) {
+    return maze_eval_args(h, maze_args(h, 0, n, tslimit), n, tslimit, returns, signreturns, lengths, bc_out);
 }
 
 extern "C" int dne_maze_final_state(dne_handle *h, int n, float *xy) {
@@ -2194,6 +2207,178 @@ extern "C" int dne_maze_debug_math(dne_handle *h, int fn, const double *x, int n
     HCHECK(h, hipGetLastError());
     HCHECK(h, hipStreamSynchronize(h->stream));
     HCHECK(h, hipMemcpy(out, dout, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------- Deep-GA on the hard maze (csrc/maze_ga.h)
+#define MZG_NEEDS_MAZE(h, call)                                                                 \
+    do {                                                                                        \
+        if (!(h)->maze) return (h)->fail("%s needs a DNE_KIND_MAZE engine (this one: kind %d)", call, (h)->L.kind); \
+    } while (0)
+
+static float *mzg_bank(dne_handle *h, int half) { return h->mzg_mem + (size_t)half * h->M * h->base_stride; }
+
+extern "C" int dne_maze_ga_set_init_scale(dne_handle *h, const float *scale_by, size_t n) {
+    DeviceGuard dg(h);
+    MZG_NEEDS_MAZE(h, "dne_maze_ga_set_init_scale");
+    if (n != (size_t)maze_ga::P || !scale_by) return h->fail("dne_maze_ga_set_init_scale: expected %d values, got %zu", maze_ga::P, n);
+    if (!h->mzg_mem) {
+        const size_t M = h->M;
+        HCHECK(h, h->alloc(&h->init_scale, n, "maze_ga_init_scale"));
+        HCHECK(h, h->alloc(&h->mzg_slot, M, "maze_ga_slot")); HCHECK(h, h->alloc(&h->mzg_off, M, "maze_ga_off")); HCHECK(h, h->alloc(&h->mzg_scale, M, "maze_ga_scale"));
+        float *mem = nullptr;
+        HCHECK(h, h->alloc(&mem, 3 * M * h->base_stride, "maze_ga_bank"));
+        HCHECK(h, hipMemset(mem, 0, 3 * M * h->base_stride * sizeof(float)));
+        h->mzg_mem = mem;
+    }
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(h->init_scale, scale_by, n * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// what every call that reads the table or the bank needs first
+static int mzg_ready(dne_handle *h, const char *call, bool walls) {
+    if (!h->mzg_mem) return h->fail("%s: no init scale (dne_maze_ga_set_init_scale comes first)", call);
+    if (!h->noise) return h->fail("%s: noise table not uploaded (dne_noise_upload)", call);
+    if (walls && h->maze_nw < 1) return h->fail("%s: no maze loaded (dne_maze_set_walls comes before an evaluation)", call);
+    return 0;
+}
+
+static int mzg_upload_members(dne_handle *h, int n, const int32_t *a, const int64_t *b, const float *c) {
+    HCHECK(h, hipMemcpyAsync(h->mzg_slot, a, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HCHECK(h, hipMemcpyAsync(h->mzg_off, b, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    HCHECK(h, hipMemcpyAsync(h->mzg_scale, c, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+
+extern "C" int dne_maze_ga_build(dne_handle *h, int T, const int32_t *chain_offsets, const int64_t *seeds, const float *powers) {
+    DeviceGuard dg(h);
+    MZG_NEEDS_MAZE(h, "dne_maze_ga_build");
+    if (mzg_ready(h, "dne_maze_ga_build", false)) return -1;
+    if (T < 1 || T > h->M) return h->fail("dne_maze_ga_build: T = %d outside [1, max_members = %d]", T, h->M);
+    if (!chain_offsets || !seeds || !powers) return h->fail("dne_maze_ga_build: a buffer is missing");
+    if (chain_offsets[0] != 0) return h->fail("dne_maze_ga_build: chain_offsets starts at %d, not 0", chain_offsets[0]);
+    const std::string bad = maze_ga::check_genomes(T, chain_offsets, seeds, h->noise_count);
+    if (!bad.empty()) return h->fail("dne_maze_ga_build: %s", bad.c_str());
+    const size_t total = (size_t)chain_offsets[T];
+    if (total > h->mzg_chain_cap || !h->mzg_chain_offs) {
+        HCHECK(h, hipStreamSynchronize(h->stream));
+        HCHECK(h, h->release(h->mzg_chain_offs)); HCHECK(h, h->release(h->mzg_seeds)); HCHECK(h, h->release(h->mzg_powers));
+        h->mzg_chain_cap = std::max<size_t>(2 * total, 4096);
+        HCHECK(h, h->alloc(&h->mzg_chain_offs, (size_t)h->M + 1, "maze_ga_chain_offs"));
+        HCHECK(h, h->alloc(&h->mzg_seeds, h->mzg_chain_cap, "maze_ga_seeds")); HCHECK(h, h->alloc(&h->mzg_powers, h->mzg_chain_cap, "maze_ga_powers"));
+    }
+    HCHECK(h, hipMemcpyAsync(h->mzg_chain_offs, chain_offsets, ((size_t)T + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HCHECK(h, hipMemcpyAsync(h->mzg_seeds, seeds, total * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    HCHECK(h, hipMemcpyAsync(h->mzg_powers, powers, total * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    const int other = 1 - h->mzg_half;
+    hipLaunchKernelGGL(maze_ga::k_maze_ga_build, dim3(T, 2), dim3(256), 0, h->stream, (const float *)h->noise, (const float *)h->init_scale,
+                       (const int32_t *)h->mzg_chain_offs, (const int64_t *)h->mzg_seeds, (const float *)h->mzg_powers, mzg_bank(h, other), h->base_stride);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipStreamSynchronize(h->stream));   // the caller's arrays may go away
+    h->mzg_half = other; h->mzg_T = T;
+    return 0;
+}
+
+extern "C" int dne_maze_ga_promote(dne_handle *h, int T_new, const int32_t *parent, const int64_t *idx, const float *power) {
+    DeviceGuard dg(h);
+    MZG_NEEDS_MAZE(h, "dne_maze_ga_promote");
+    if (mzg_ready(h, "dne_maze_ga_promote", false)) return -1;
+    if (T_new < 1 || T_new > h->M) return h->fail("dne_maze_ga_promote: T = %d outside [1, max_members = %d]", T_new, h->M);
+    if (!parent || !idx || !power) return h->fail("dne_maze_ga_promote: a buffer is missing");
+    for (int j = 0; j < T_new; j++) {
+        const std::string bad = maze_ga::check_member(j, h->mzg_T, h->noise_count, parent[j], idx[j], true);
+        if (!bad.empty()) return h->fail("dne_maze_ga_promote: %s", bad.c_str());
+    }
+    if (mzg_upload_members(h, T_new, parent, idx, power)) return -1;
+    const int other = 1 - h->mzg_half;
+    hipLaunchKernelGGL(maze_ga::k_maze_ga_promote, dim3(T_new, 2), dim3(256), 0, h->stream, (const float *)h->noise, (const float *)h->init_scale,
+                       (const float *)mzg_bank(h, h->mzg_half), mzg_bank(h, other), h->base_stride, (const int32_t *)h->mzg_slot,
+                       (const int64_t *)h->mzg_off, (const float *)h->mzg_scale);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    h->mzg_half = other; h->mzg_T = T_new;
+    return 0;
+}
+
+extern "C" int dne_maze_ga_eval(dne_handle *h, int n, const int32_t *parent, const int64_t *idx, const float *power, int tslimit,
+                                float *returns, float *signreturns, int32_t *lengths) {
+    DeviceGuard dg(h);
+    MZG_NEEDS_MAZE(h, "dne_maze_ga_eval");
+    if (mzg_ready(h, "dne_maze_ga_eval", true)) return -1;
+    if (n < 1 || n > h->M) return h->fail("dne_maze_ga_eval: n = %d outside [1, max_members = %d]", n, h->M);
+    if (!parent || !idx || !power || !returns || !lengths) return h->fail("dne_maze_ga_eval: a buffer is missing");
+    if (tslimit <= 0) return h->fail("dne_maze_ga_eval: timestep limit must be positive");
+    // a child is the rollout kernel's own member: (its parent's bank slot, idx, power); a root runs from scratch slot 2 M + i at scale 0
+    const int bank0 = h->mzg_half * h->M, root0 = 2 * h->M;
+    std::vector<int32_t> &slot = h->mzg_host_slot;
+    std::vector<float> &scale = h->mzg_host_scale;
+    slot.resize(n); scale.resize(n);
+    bool roots = false;
+    for (int i = 0; i < n; i++) {
+        const std::string bad = maze_ga::check_member(i, h->mzg_T, h->noise_count, parent[i], idx[i], false);
+        if (!bad.empty()) return h->fail("dne_maze_ga_eval: %s", bad.c_str());
+        const bool root = parent[i] < 0;
+        slot[i] = root ? root0 + i : bank0 + parent[i];
+        scale[i] = root ? 0.0f : power[i];
+        roots = roots || root;
+    }
+    if (mzg_upload_members(h, n, slot.data(), idx, scale.data())) return -1;
+    if (roots) {
+        hipLaunchKernelGGL(maze_ga::k_maze_ga_roots, dim3(n, 2), dim3(256), 0, h->stream, (const float *)h->noise, (const float *)h->init_scale,
+                           (const int32_t *)h->mzg_slot, (const int64_t *)h->mzg_off, root0, h->mzg_mem, h->base_stride);
+        HCHECK(h, hipGetLastError());
+    }
+    maze::RolloutArgs A{};
+    A.noise = h->noise; A.bases = h->mzg_mem; A.base_stride = h->base_stride;
+    A.m_slot = h->mzg_slot; A.m_off = h->mzg_off; A.m_scale = h->mzg_scale;
+    return maze_eval_args(h, A, n, tslimit, returns, signreturns, lengths, nullptr);
+}
+
+extern "C" int dne_maze_ga_parents(dne_handle *h) {
+    MZG_NEEDS_MAZE(h, "dne_maze_ga_parents");
+    return h->mzg_T;
+}
+
+extern "C" int dne_maze_ga_get_parent(dne_handle *h, int j, float *out) {
+    DeviceGuard dg(h);
+    MZG_NEEDS_MAZE(h, "dne_maze_ga_get_parent");
+    if (j < 0 || j >= h->mzg_T) return h->fail("dne_maze_ga_get_parent: parent %d, the bank holds %d", j, h->mzg_T);
+    if (!out) return h->fail("dne_maze_ga_get_parent: no output buffer");
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(out, mzg_bank(h, h->mzg_half) + (size_t)j * h->base_stride, maze_ga::P * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the same header on the CPU: no handle, no GPU
+static int mzg_host_table(const char *call, const float *noise, size_t count, const float *scale_by) {
+    if (!noise || !scale_by) { g_create_error = std::string(call) + ": a buffer is missing"; return -1; }
+    if (count < (size_t)maze_ga::P) { g_create_error = std::string(call) + ": a table of " + std::to_string(count) + " floats holds no 498 parameters"; return -1; }
+    return 0;
+}
+
+extern "C" int dne_maze_ga_theta_host(const float *noise, size_t count, const float *scale_by, const int64_t *seeds, const float *powers, int nseeds,
+                                      float *out) {
+    if (mzg_host_table("dne_maze_ga_theta_host", noise, count, scale_by)) return -1;
+    if (!seeds || !powers || !out) { g_create_error = "dne_maze_ga_theta_host: a buffer is missing"; return -1; }
+    const int32_t co[2] = {0, nseeds};
+    const std::string bad = maze_ga::check_genomes(1, co, seeds, count);
+    if (!bad.empty()) { g_create_error = "dne_maze_ga_theta_host: " + bad; return -1; }
+    maze_ga::genome_host(noise, scale_by, seeds, powers, nseeds, out);
+    return 0;
+}
+
+extern "C" int dne_maze_ga_members_host(const float *noise, size_t count, const float *scale_by, const float *bank, int T, const int32_t *parent,
+                                        const int64_t *idx, const float *power, int n, float *out) {
+    if (mzg_host_table("dne_maze_ga_members_host", noise, count, scale_by)) return -1;
+    if (n < 1) { g_create_error = "dne_maze_ga_members_host: n = " + std::to_string(n) + ", at least one member is needed"; return -1; }
+    if (T < 0 || (T > 0 && !bank)) { g_create_error = "dne_maze_ga_members_host: T = " + std::to_string(T) + " parents without a bank"; return -1; }
+    if (!parent || !idx || !power || !out) { g_create_error = "dne_maze_ga_members_host: a buffer is missing"; return -1; }
+    for (int i = 0; i < n; i++) {
+        const std::string bad = maze_ga::check_member(i, T, count, parent[i], idx[i], true);
+        if (!bad.empty()) { g_create_error = "dne_maze_ga_members_host: " + bad; return -1; }
+    }
+    maze_ga::members_host(noise, scale_by, bank, parent, idx, power, n, out);
     return 0;
 }
 

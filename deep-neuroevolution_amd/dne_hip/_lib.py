@@ -74,7 +74,7 @@ class Profile(C.Structure):
 
 def build(force=False):
     """Compile libdne_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dne_hip.h"))
     if os.environ.get("DNE_LIB_PATH"):
         # another build of the same ABI was asked for by name: `make` only knows the in-tree library, so running it here would
@@ -232,6 +232,48 @@ def maze_novelty_host(xy, archive, k):
     out = np.empty(xy.shape[0], np.float64)
     _ck_host(load().dne_maze_novelty_host(_ptr(xy, C.c_float), int(xy.shape[0]), _ptr(archive, C.c_float), int(archive.shape[0]), int(k),
                                           _ptr(out, C.c_double)))
+    return out
+
+
+def split_genome(genome):
+    """a gpu-tree genome (idx0, (idx1, power1), ...) -- the root as a bare index or a 1-tuple -- as (int64 indices, float32 powers); the root's power is 0"""
+    idx = np.array([c[0] if isinstance(c, (tuple, list)) else c for c in genome], np.int64)
+    pw = np.array([c[1] if isinstance(c, (tuple, list)) and len(c) > 1 else 0.0 for c in genome], np.float32)
+    return idx, pw
+
+
+def _maze_ga_members(parent, idx, power):
+    parent = _arr(parent, np.int32).reshape(-1); idx = _arr(idx, np.int64).reshape(-1)
+    power = _arr(np.broadcast_to(np.asarray(power, np.float32), parent.shape), np.float32)
+    if idx.size != parent.size:
+        raise DneError("member descriptors: %d parents, %d indices" % (parent.size, idx.size))
+    return parent, idx, power
+
+
+def maze_ga_theta_host(noise, scale_by, genome):
+    """dne_maze_ga_theta_host: csrc/maze_ga.h on the CPU (no GPU, no handle): theta [498] of one genome (idx0, (idx1, power1), ...)"""
+    noise = _arr(noise, np.float32).reshape(-1); scale_by = _arr(scale_by, np.float32).reshape(-1)
+    if scale_by.size != 498:
+        raise DneError("maze_ga_theta_host: scale_by holds %d values, 498 expected" % scale_by.size)
+    idx, pw = split_genome(genome)
+    out = np.empty(498, np.float32)
+    _ck_host(load().dne_maze_ga_theta_host(_ptr(noise, C.c_float), C.c_size_t(noise.size), _ptr(scale_by, C.c_float), _ptr(idx, C.c_int64),
+                                           _ptr(pw, C.c_float), int(idx.size), _ptr(out, C.c_float)))
+    return out
+
+
+def maze_ga_members_host(noise, scale_by, bank, parent, idx, power):
+    """dne_maze_ga_members_host: the theta [n][498] of n member descriptors (parent, idx, power) against a host bank [T][498] (None: empty):
+    parent -1 a root, idx < 0 the parent itself, otherwise bank[parent] + fl(power * noise[idx:idx + 498])"""
+    noise = _arr(noise, np.float32).reshape(-1); scale_by = _arr(scale_by, np.float32).reshape(-1)
+    if scale_by.size != 498:
+        raise DneError("maze_ga_members_host: scale_by holds %d values, 498 expected" % scale_by.size)
+    bank = np.zeros((0, 498), np.float32) if bank is None else _arr(bank, np.float32).reshape(-1, 498)
+    parent, idx, power = _maze_ga_members(parent, idx, power)
+    out = np.empty((parent.size, 498), np.float32)
+    _ck_host(load().dne_maze_ga_members_host(_ptr(noise, C.c_float), C.c_size_t(noise.size), _ptr(scale_by, C.c_float),
+                                             _ptr(bank, C.c_float) if bank.shape[0] else None, int(bank.shape[0]), _ptr(parent, C.c_int32),
+                                             _ptr(idx, C.c_int64), _ptr(power, C.c_float), int(parent.size), _ptr(out, C.c_float)))
     return out
 
 
@@ -524,6 +566,47 @@ class Engine:
         """k_maze_novelty of the last maze_novelty call between two device events, milliseconds"""
         self.lib.dne_maze_novelty_last_ms.restype = C.c_double
         return float(self.lib.dne_maze_novelty_last_ms(self.h))
+
+    # ---- Deep-GA on the hard maze (csrc/maze_ga.h): the parents live in a bank on the device, a member is (parent, idx, power)
+    def maze_ga_set_init_scale(self, scale_by):
+        sb = _arr(scale_by, np.float32)
+        self._ck(self.lib.dne_maze_ga_set_init_scale(self.h, _ptr(sb, C.c_float), C.c_size_t(sb.size)))
+
+    def maze_ga_build(self, genomes):
+        """the bank = these genomes' thetas, parent j from genomes[j] = (idx0, (idx1, power1), ...)"""
+        T = len(genomes)
+        co = np.zeros(T + 1, np.int32)
+        parts = [split_genome(g) for g in genomes]
+        co[1:] = np.cumsum([p[0].size for p in parts])
+        flat = _arr(np.concatenate([p[0] for p in parts]) if parts else np.zeros(0), np.int64)
+        pw = _arr(np.concatenate([p[1] for p in parts]) if parts else np.zeros(0), np.float32)
+        self._ck(self.lib.dne_maze_ga_build(self.h, T, _ptr(co, C.c_int32), _ptr(flat, C.c_int64), _ptr(pw, C.c_float)))
+
+    def maze_ga_eval(self, parent, idx, power, tslimit=MAZE_STEPS):
+        """one episode per member (parent -1: a root at idx; otherwise bank[parent] + fl(power * noise[idx])) -> (returns, signs, lengths)"""
+        parent, idx, power = _maze_ga_members(parent, idx, power)
+        n = parent.size
+        ret = np.empty(n, np.float32); sg = np.empty(n, np.float32); ln = np.empty(n, np.int32)
+        self._ck(self.lib.dne_maze_ga_eval(self.h, n, _ptr(parent, C.c_int32), _ptr(idx, C.c_int64), _ptr(power, C.c_float), int(tslimit),
+                                           _ptr(ret, C.c_float), _ptr(sg, C.c_float), _ptr(ln, C.c_int32)))
+        self._last_eval_n = n
+        return ret, sg, ln
+
+    def maze_ga_promote(self, parent, idx, power):
+        """new parent j = the theta of descriptor j over the bank as it is (idx < 0: parent[j] itself), all at once"""
+        parent, idx, power = _maze_ga_members(parent, idx, power)
+        self._ck(self.lib.dne_maze_ga_promote(self.h, int(parent.size), _ptr(parent, C.c_int32), _ptr(idx, C.c_int64), _ptr(power, C.c_float)))
+
+    def maze_ga_parents(self):
+        n = self.lib.dne_maze_ga_parents(self.h)
+        if n < 0:
+            self._ck(n)
+        return n
+
+    def maze_ga_get_parent(self, j):
+        out = np.empty(self.P, np.float32)
+        self._ck(self.lib.dne_maze_ga_get_parent(self.h, int(j), _ptr(out, C.c_float)))
+        return out
 
     # ---- gpu-tree genomes: ((idx0,), (idx1, power1), ...)
     def ga_set_init_scale(self, scale_by):

@@ -9,6 +9,11 @@ DNE_KIND_GA_LARGE (csrc/forward_large.h); exp['model'] picks one like ga.py:110.
 The reference evaluates through TensorFlow workers (ConcurrentWorkers.monitor_eval); here a generation is one
 dne_ga_eval_powers call and the validation / test episodes are batched calls of the same entry point.
 Unseeded streams of the reference (np.random.RandomState() in ga.py:127, the environments' own seeds) are seeded here.
+
+exp['game'] == 'maze' with exp['model'] == 'SimpleClassifier' (gym_tensorflow.make's first branch, models/simple.py:29-35) runs maze_main below on
+a DNE_KIND_MAZE engine: the parents live in a bank on the device, a member is a (parent, noise index, power) triple that k_maze_rollout
+evaluates as it stands, selected children become parents device to device (dne_maze_ga_promote), and genomes are written out only for the
+few individuals that survive a generation.  SimpleClassifier on an Atari game and the Atari models on the maze are refused.
 """
 import math
 import numbers
@@ -159,6 +164,8 @@ def model_scale_by(nact, kind=None):
 
 
 MODEL_KINDS = {'Model': _lib.KIND_GA, 'LargeModel': _lib.KIND_GA_LARGE}   # neuroevolution/models/dqn.py:24-47 (exp['model'], ga.py:110)
+MAZE_MODEL = 'SimpleClassifier'          # the one model of exp['game'] == 'maze' (neuroevolution/models/simple.py:29-35)
+ALGO = 'ga'                              # what maze_main's snapshot.pkl says wrote it
 
 
 class HipModel(object):
@@ -190,10 +197,26 @@ def _evaluate(engine, genomes, tslimit, rs):
     return np.concatenate(out_r), np.concatenate(out_l)
 
 
+def parents_of(state, T):
+    """ga.py:147-156, 263-274: the genomes of the next parents -- the top T, the elite first in place of the last if it is not among them"""
+    if not state.population or T <= 0:
+        return []
+    top = [o.seeds for o in state.population[:T]]
+    if state.elite is None or state.elite.seeds in top:
+        return top
+    return [state.elite.seeds] + top[:T - 1]
+
+
 def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
     """gpu_implementation/ga.py:114-275.  Returns (curr_solution_test, {'val': curr_solution_val}, state)."""
     from . import tabular_logger as tlogger
     from .es import SharedNoiseTable
+    maze, asked = exp.get('game') == 'maze', exp.get('model', 'Model')
+    if maze != (asked == MAZE_MODEL):                               # ga.py:110-114 takes any pair; the engine has these
+        raise NotImplementedError("model {!r} on game {!r}: {!r} runs on game 'maze' only, and 'maze' runs nothing else".format(
+            asked, exp.get('game'), MAZE_MODEL))
+    if maze:
+        return maze_main(log_dir, engine=engine, noise=noise, seed=seed, max_iters=max_iters, **exp)
     tlogger.start(log_dir)
     if engine is None:
         engine = _lib.Engine(MODEL_KINDS[exp.get('model', 'Model')], 18, max_members=exp['population_size'])
@@ -206,21 +229,15 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
         with open(os.path.join(log_dir, 'snapshot.pkl'), 'rb+') as file:
             state = pickle.load(file)
         tlogger.log("Loaded iteration {} from {}".format(state.it, log_dir))
+        if getattr(state, 'game', None) == 'maze':
+            raise ValueError("snapshot.pkl in {} holds game 'maze' under model {!r}; this run is game {!r} under model {!r}".format(
+                log_dir, getattr(state, 'model', None), exp.get('game'), asked))
     except FileNotFoundError:
         state = TrainingState(exp)
     if 'load_population' in exp:
         state.copy_population(exp['load_population'])
 
-    def parents_of(state):                                         # ga.py:147-156, 263-274: the elite first, then the top selection_threshold
-        T = exp['selection_threshold']
-        if not state.population or T <= 0:
-            return []
-        top = [o.seeds for o in state.population[:T]]
-        if state.elite is None or state.elite.seeds in top:
-            return top
-        return [state.elite.seeds] + top[:T - 1]
-
-    cached_parents = parents_of(state)
+    cached_parents = parents_of(state, exp['selection_threshold'])
     iters = 0
     while max_iters is None or iters < max_iters:
         iters += 1
@@ -283,5 +300,169 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
             pickle.dump(state, file)
         if state.timesteps_so_far >= exp['timesteps']:
             break
-        cached_parents = parents_of(state)                                                      # ga.py:261-274
+        cached_parents = parents_of(state, exp['selection_threshold'])                          # ga.py:261-274
+    return float(state.curr_solution_test), {'val': float(state.curr_solution_val)}, state
+
+
+# ---------------------------------------------------------------------------------------------- the hard maze
+KEPT = -1          # a descriptor's noise index that means "the parent itself" (dne_maze_ga_promote)
+
+
+def _maze_evaluate(engine, members, tslimit):
+    """(returns, lengths) of one episode per (parent, idx, power) member, in calls of at most max_members"""
+    limit = _lib.MAZE_STEPS if tslimit is None else min(int(tslimit), _lib.MAZE_STEPS)
+    out_r, out_l = [], []
+    for s in range(0, len(members), engine.max_members):
+        parent, idx, power = zip(*members[s:s + engine.max_members])
+        ret, _, ln = engine.maze_ga_eval(np.array(parent, np.int32), np.array(idx, np.int64), np.array(power, np.float32), limit)
+        out_r.append(ret); out_l.append(ln)
+    return np.concatenate(out_r), np.concatenate(out_l)
+
+
+def maze_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
+    """gpu_implementation/ga.py:114-275 with game 'maze' and model 'SimpleClassifier'.  Returns (curr_solution_test, {'val': ...}, state).
+
+    A generation's member i is the triple (parent p_i, noise index idx_i, power) over the device's bank of T parents -- a root (-1, idx_i)
+    while there are none -- so a generation is ONE maze_ga_eval of three small arrays.  Its genome, parents[p_i] + ((idx_i, power),), is only
+    written out for the top max(selection_threshold, validation_threshold) and the elite: state.population holds just those (the reference
+    reads no more of it, ga.py:150-154, 188).  The next parents are made on the device from this generation's descriptors by one
+    maze_ga_promote (a retained elite as the kept form); maze_ga_build from whole genomes runs once per call of main: for the first
+    bank after generation 0, or before the loop when load_population or a snapshot brought a population.
+    Decisions of ours: the reference's stream is unseeded (ga.py:117) and drawn from one offspring at a time; here a generation takes
+    rs.randint(T, size=n) for the parents (if there are any), then rs.randint(0, len(noise) - P + 1, size=n) for the indices, as two
+    whole-array draws from RandomState(seed), and no environment seeds (the episode is deterministic).  The stream's position is kept in
+    snapshot.pkl with game, model and algo = 'ga', so a resumed run continues bit for bit; a resume under another game or model, or from
+    a snapshot of es_gpu.main / nses_gpu.main, raises and names both.  A previous elite is evaluated again as (its bank index, idx 0,
+    power 0): the child formula, bank + fl(0 * noise).  The elite's test episodes are num_test_episodes identical deterministic episodes
+    at the 400-step default, as the reference runs them.  num_frames counts steps (the maze has no frame skip)."""
+    from . import policies, tabular_logger as tlogger
+    from .es import SharedNoiseTable
+    from .es_gpu import maze_file
+    tlogger.start(log_dir)
+    n, T, V = exp['population_size'], exp['selection_threshold'], exp['validation_threshold']
+    if engine is None:
+        engine = _lib.Engine(_lib.KIND_MAZE, 2, max_members=n)
+    elif engine.kind != _lib.KIND_MAZE:
+        raise ValueError("game 'maze' asked for, the engine passed in is of kind {} (KIND_MAZE is {})".format(engine.kind, _lib.KIND_MAZE))
+    engine.maze_set_walls(*_lib.load_maze(maze_file(exp)))
+    noise = noise if noise is not None else SharedNoiseTable()
+    noise.attach(engine)
+    engine.maze_ga_set_init_scale(policies.simple_scale_by())
+    P = engine.P
+    rs = np.random.RandomState(seed)
+    all_tstart = time.time()
+    try:                                                           # ga.py:135-143: resume
+        with open(os.path.join(log_dir, 'snapshot.pkl'), 'rb') as file:
+            state = pickle.load(file)
+        tlogger.log("Loaded iteration {} from {}".format(state.it, log_dir))
+        was_algo = getattr(state, 'algo', ALGO if isinstance(state, TrainingState) else 'es_gpu')
+        if was_algo != ALGO:
+            raise ValueError("snapshot.pkl in {} was written by {!r}; this run is {!r}".format(log_dir, was_algo, ALGO))
+        was = (getattr(state, 'game', None) or 'an Atari game', getattr(state, 'model', 'Model'))
+        if was != ('maze', MAZE_MODEL):
+            raise ValueError("snapshot.pkl in {} holds game {!r} under model {!r}; this run is game 'maze' under model {!r}".format(
+                log_dir, was[0], was[1], MAZE_MODEL))
+        if getattr(state, 'stream', None) is not None:
+            rs.set_state(state.stream)
+    except FileNotFoundError:
+        state = TrainingState(exp)
+    state.game, state.model, state.algo = 'maze', MAZE_MODEL, ALGO
+    if 'load_population' in exp:
+        state.copy_population(exp['load_population'])
+    parents = parents_of(state, T)                                  # the genomes of the bank's parents, kept beside it
+    if parents:
+        engine.maze_ga_build(parents)
+    iters = 0
+    while max_iters is None or iters < max_iters:
+        iters += 1
+        tstart_iteration = time.time()
+        if state.timesteps_so_far >= exp['timesteps']:
+            break
+        assert (len(parents) == 0 and state.it == 0) or len(parents) == T
+        power = state.sample(state.mutation_power)
+        if parents:
+            of = rs.randint(len(parents), size=n).astype(np.int32)
+        else:
+            of = np.full(n, -1, np.int32)
+        idx = rs.randint(0, len(noise.noise) - P + 1, size=n).astype(np.int64)
+        limit = _lib.MAZE_STEPS if state.tslimit is None else min(int(state.tslimit), _lib.MAZE_STEPS)
+        rets, _, lens = engine.maze_ga_eval(of, idx, np.full(n, power, np.float32), limit)
+        state.num_frames += int(lens.sum())
+        state.it += 1
+        rewards = np.asarray(rets, np.float64)
+        population_timesteps = int(lens.sum())
+        order = engine.ga_select(np.asarray(rets, np.float32), n)   # (-fitness, arrival index): a stable sort, ties at -500 keep arrival order
+
+        def member(i):                                              # the descriptor of this generation's member i, and its genome
+            i = int(i)
+            if of[i] < 0:
+                return (-1, int(idx[i]), 0.0), (int(idx[i]), )
+            return (int(of[i]), int(idx[i]), float(power)), tuple(parents[of[i]]) + ((int(idx[i]), power), )
+
+        descriptor = {}                                             # id(Offspring) -> its descriptor over the bank as it is now
+        state.population = []
+        for i in order[:max(T, V)]:
+            d, genome = member(i)
+            o = Offspring(genome, [float(rets[i])], [int(lens[i])])
+            descriptor[id(o)] = d
+            state.population.append(o)
+        validation_population = state.population[:V]                # ga.py:184-186
+        if state.elite is not None:
+            if state.elite.seeds in parents:
+                descriptor[id(state.elite)] = (parents.index(state.elite.seeds), 0, 0.0)
+            elif len(state.elite.seeds) == 1:                       # selection_threshold 0: no bank, every individual is a root
+                root = state.elite.seeds[0]
+                descriptor[id(state.elite)] = (-1, int(root[0] if isinstance(root, (tuple, list)) else root), 0.0)
+            else:
+                raise NotImplementedError("the elite {!r} is not among the {} parents of the bank".format(state.elite.seeds, len(parents)))
+            validation_population = [state.elite] + validation_population[:-1]
+        k = exp['num_validation_episodes']
+        vr, vl = _maze_evaluate(engine, [descriptor[id(o)] for o in validation_population for _ in range(k)], state.tslimit)   # ga.py:188-192
+        population_validation = [float(np.mean(vr[i * k:(i + 1) * k])) for i in range(len(validation_population))]
+        population_validation_len = [int(np.sum(vl[i * k:(i + 1) * k])) for i in range(len(validation_population))]
+        old_elite = state.elite
+        state.elite = validation_population[int(np.argmax(population_validation))]            # ga.py:198-199
+        er, el = _maze_evaluate(engine, [descriptor[id(state.elite)]] * exp['num_test_episodes'], None)   # ga.py:200-201 (max_frames=None)
+        validation_timesteps = sum(population_validation_len)
+        timesteps_this_iter = population_timesteps + validation_timesteps
+        state.timesteps_so_far += timesteps_this_iter
+        state.validation_timesteps_so_far += validation_timesteps
+        if np.mean(population_validation) > state.curr_solution_val:                           # ga.py:223-226
+            state.curr_solution = state.elite.seeds
+            state.curr_solution_val = float(np.mean(population_validation))
+            state.curr_solution_test = float(np.mean(er))
+        dt = time.time() - tstart_iteration
+        state.time_elapsed += dt
+        for key, val in (('Iteration', state.it), ('MutationPower', power), ('PopulationEpRewMax', np.max(rewards)),
+                         ('PopulationEpRewMean', np.mean(rewards)), ('PopulationEpCount', len(rewards)),
+                         ('PopulationTimesteps', population_timesteps), ('NumSelectedIndividuals', T),
+                         ('TruncatedPopulationRewMean', np.mean([a.fitness for a in validation_population])),
+                         ('TruncatedPopulationValidationRewMean', np.mean(population_validation)),
+                         ('TruncatedPopulationEliteValidationRewMean', np.max(population_validation)),
+                         ('TruncatedPopulationEliteTestRewMean', np.mean(er)), ('TruncatedPopulationEliteTestEpCount', len(er)),
+                         ('TruncatedPopulationEliteTestEpLenSum', int(np.sum(el))), ('ValidationTimestepsThisIter', validation_timesteps),
+                         ('TimestepsThisIter', timesteps_this_iter), ('TimestepsPerSecondThisIter', timesteps_this_iter / dt),
+                         ('TimestepsSoFar', state.timesteps_so_far), ('TimeElapsedThisIter', dt), ('TimeElapsed', state.time_elapsed),
+                         ('TimeElapsedTotal', time.time() - all_tstart)):
+            tlogger.record_tabular(key, val)
+        tlogger.dump_tabular()
+        if state.adaptive_tslimit:                                                              # ga.py:244-247
+            if np.mean(lens >= state.tslimit) > state.incr_tslimit_threshold:
+                state.tslimit = min(state.tslimit * state.tslimit_incr_ratio, state.tslimit_max)
+        # ga.py:261-274 on the device: the next parents from this generation's descriptors, the retained elite as it stands
+        new_parents = parents_of(state, T)
+        if new_parents and not parents:                             # the start: generation 0's roots become the first bank
+            engine.maze_ga_build(new_parents)
+        elif new_parents:
+            by_genome = {o.seeds: descriptor[id(o)] for o in state.population}
+            if old_elite is not None and state.elite is old_elite and state.elite.seeds in parents:
+                by_genome[state.elite.seeds] = (parents.index(state.elite.seeds), KEPT, 0.0)
+            engine.maze_ga_promote(*(np.array(c, t) for c, t in zip(zip(*(by_genome[g] for g in new_parents)), (np.int32, np.int64, np.float32))))
+        parents = new_parents
+        state.stream = rs.get_state()
+        os.makedirs(log_dir, exist_ok=True)                                                     # ga.py:249-254
+        with open(os.path.join(log_dir, 'snapshot.pkl'), 'wb') as file:
+            pickle.dump(state, file)
+        if state.timesteps_so_far >= exp['timesteps']:
+            break
     return float(state.curr_solution_test), {'val': float(state.curr_solution_val)}, state

@@ -350,6 +350,36 @@ int dne_maze_novelty(dne_handle *h, const float *xy /*[n][2], or NULL*/, int n, 
 int dne_maze_novelty_host(const float *xy, int n, const float *archive /*[narch][2]*/, int narch, int k, double *out);
 double dne_maze_novelty_last_ms(dne_handle *h);
 
+/* ---- Deep-GA on the hard maze (csrc/maze_ga.h) -----------------------------------------------
+ * gpu_implementation/ga.py on SimpleClassifier.  A genome is (idx0, (idx1, power1), ...) as seeds[] / powers[] (powers[0] is not read):
+ * theta_p = fl(noise[idx0 + p] * scale_by[p]), then per mutation, in order, theta_p = theta_p + fl(power_j * noise[idx_j + p]), never fused.
+ * The parents live in a bank on the device (T of them, at most max_members), apart from the base slots of dne_set_theta, which no call here
+ * reads or writes.  A member descriptor (parent, idx, power) against the bank is one of
+ *   root   parent == -1, idx >= 0      theta_p = fl(noise[idx + p] * scale_by[p]); power is not read
+ *   child  0 <= parent < T, idx >= 0   theta_p = bank[parent][p] + fl(power * noise[idx + p])   (power 0: the parent evaluated again)
+ *   kept   0 <= parent < T, idx < 0    bank[parent] bit for bit: dne_maze_ga_promote only
+ * dne_maze_ga_build fills the bank with T parents from their genomes (chain_offsets [T + 1] into seeds / powers, from 0).
+ * dne_maze_ga_eval runs one episode per root / child member in one k_maze_rollout launch; dne_maze_final_state, dne_maze_novelty(xy = NULL)
+ * and dne_get_profile follow it as they follow any evaluation.  dne_maze_ga_promote makes the theta of descriptor j the new parent j, for
+ * all T_new at once, reading the old bank and writing the other half of a double buffer: a kept parent may change its index and two
+ * descriptors may name one source.  dne_maze_ga_parents returns T (-1 on another kind), dne_maze_ga_get_parent copies one parent out.
+ * All calls are ordered on the engine's stream.  Refused by name, the bank staying as it was: an engine of another kind; no init scale; no
+ * noise table (for an evaluation: no walls); parent >= T, or any parent >= 0 on an empty bank; the kept form in an evaluation; idx + 498
+ * past the table; n or T outside 1 .. max_members; an empty chain.  dne_ga_* keep refusing this kind.
+ * dne_maze_ga_theta_host / dne_maze_ga_members_host are the same header on the CPU (no handle, no GPU): the theta of one genome, and of n
+ * descriptors (all three forms) against a host bank [T][498]. */
+int dne_maze_ga_set_init_scale(dne_handle *h, const float *scale_by, size_t n /*498*/);
+int dne_maze_ga_build(dne_handle *h, int T, const int32_t *chain_offsets /*T+1*/, const int64_t *seeds, const float *powers);
+int dne_maze_ga_eval(dne_handle *h, int n, const int32_t *parent, const int64_t *idx, const float *power, int tslimit, float *returns,
+                     float *signreturns /*or NULL*/, int32_t *lengths);
+int dne_maze_ga_promote(dne_handle *h, int T_new, const int32_t *parent, const int64_t *idx, const float *power);
+int dne_maze_ga_parents(dne_handle *h);
+int dne_maze_ga_get_parent(dne_handle *h, int j, float *out /*498*/);
+int dne_maze_ga_theta_host(const float *noise, size_t count, const float *scale_by, const int64_t *seeds, const float *powers, int nseeds,
+                           float *out /*498*/);
+int dne_maze_ga_members_host(const float *noise, size_t count, const float *scale_by, const float *bank /*[T][498]*/, int T,
+                             const int32_t *parent, const int64_t *idx, const float *power, int n, float *out /*[n][498]*/);
+
 #ifdef __cplusplus
 }
 #endif
