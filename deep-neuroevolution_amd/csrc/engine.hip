@@ -638,6 +638,7 @@ struct dne_handle {
     float *mzn_arch = nullptr; size_t mzn_arch_cap = 0; int mzn_arch_n = 0;
     float *mzn_xy = nullptr; size_t mzn_xy_cap = 0;
     double *mzn_out = nullptr; size_t mzn_out_cap = 0;
+    int32_t *mzn_idx = nullptr; size_t mzn_idx_cap = 0;   // member indices of dne_maze_archive_append_members
     double mzn_last_ms = -1.0;
     // Deep-GA on the maze (csrc/maze_ga.h): 3 M slots of base_stride floats apart from `bases` -- the parents' bank as a double buffer
     // (halves of M slots, mzg_half the live one, mzg_T parents in it), then one scratch slot per member for an evaluation's roots -- and
@@ -2480,6 +2481,58 @@ extern "C" int dne_maze_novelty(dne_handle *h, const float *xy, int n, int k, do
     return 0;
 }
 
+// pool novelty (GA-NS): every member against the archive and the other members
+extern "C" int dne_maze_novelty_pool(dne_handle *h, const float *xy, int n, int k, double *out) {
+    DeviceGuard dg(h);
+    MZN_NEEDS_MAZE(h, "dne_maze_novelty_pool");
+    if (mzn_check_members(h, "dne_maze_novelty_pool", xy, n)) return -1;
+    if (k < 1) return h->fail("dne_maze_novelty_pool: k = %d, at least one neighbour is needed", k);
+    if (k > DNE_MAZE_NOVELTY_KMAX) return h->fail("dne_maze_novelty_pool: k = %d, the kernel keeps at most DNE_MAZE_NOVELTY_KMAX = %d neighbours", k, DNE_MAZE_NOVELTY_KMAX);
+    if (h->mzn_arch_n + (n - 1) < 1) return h->fail("dne_maze_novelty_pool: the pool is empty (one member, no archive point)");
+    if ((size_t)h->mzn_arch_n + (size_t)n > (size_t)INT_MAX / 2) return h->fail("dne_maze_novelty_pool: %zu combined slots would not fit an int", (size_t)h->mzn_arch_n + (size_t)n);
+    if (!out) return h->fail("dne_maze_novelty_pool: no output buffer");
+    const float *pts = h->maze_xy;
+    if (xy) {
+        if (mzn_reserve(h, h->mzn_xy, h->mzn_xy_cap, 2 * (size_t)n, 0, 4096, "maze_novelty_xy")) return -1;
+        HCHECK(h, hipMemcpyAsync(h->mzn_xy, xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        pts = h->mzn_xy;
+    }
+    if (mzn_reserve(h, h->mzn_out, h->mzn_out_cap, (size_t)n, 0, 4096, "maze_novelty_out")) return -1;
+    HCHECK(h, hipEventRecord(h->ev_a, h->stream));
+    hipLaunchKernelGGL(maze_novelty::k_maze_novelty_pool, dim3((n + 3) / 4), dim3(256), 0, h->stream, pts, n, (const float *)h->mzn_arch, h->mzn_arch_n,
+                       std::min(k, h->mzn_arch_n + n - 1), h->mzn_out);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipEventRecord(h->ev_b, h->stream));
+    HCHECK(h, hipMemcpyAsync(out, h->mzn_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    float ms = 0;
+    HCHECK(h, hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
+    h->mzn_last_ms = ms;
+    return 0;
+}
+
+// archive slot A + i = the final position of the last evaluation's member members[i], device to device (k_maze_archive_gather)
+extern "C" int dne_maze_archive_append_members(dne_handle *h, const int32_t *members, int count) {
+    DeviceGuard dg(h);
+    MZN_NEEDS_MAZE(h, "dne_maze_archive_append_members");
+    if (count < 1) return h->fail("dne_maze_archive_append_members: count = %d, at least one member is needed", count);
+    if (!members) return h->fail("dne_maze_archive_append_members: no member indices");
+    for (int i = 0; i < count; i++)
+        if (members[i] < 0 || members[i] >= h->maze_last_n)
+            return h->fail("dne_maze_archive_append_members: index %d is member %d, the last evaluation ran %d", i, members[i], h->maze_last_n);
+    const size_t have = (size_t)h->mzn_arch_n;
+    if (have + (size_t)count > (size_t)INT_MAX / 2) return h->fail("dne_maze_archive_append_members: %zu points would not fit an int", have + (size_t)count);
+    if (mzn_reserve(h, h->mzn_arch, h->mzn_arch_cap, 2 * (have + count), 2 * have, 2 * MZN_ARCH_CAP0, "maze_archive")) return -1;
+    if (mzn_reserve(h, h->mzn_idx, h->mzn_idx_cap, (size_t)count, 0, 4096, "maze_archive_members")) return -1;
+    HCHECK(h, hipMemcpyAsync(h->mzn_idx, members, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(maze_novelty::k_maze_archive_gather, dim3((count + 255) / 256), dim3(256), 0, h->stream, (const float *)h->maze_xy,
+                       (const int32_t *)h->mzn_idx, count, h->mzn_arch + 2 * have);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipStreamSynchronize(h->stream));   // the caller's buffer is free again
+    h->mzn_arch_n += count;
+    return 0;
+}
+
 extern "C" double dne_maze_novelty_last_ms(dne_handle *h) { return h->mzn_last_ms; }
 
 // the same header on the CPU: no handle, no GPU
@@ -2489,6 +2542,16 @@ extern "C" int dne_maze_novelty_host(const float *xy, int n, const float *archiv
     if (narch < 1) { g_create_error = "dne_maze_novelty_host: the archive is empty"; return -1; }
     if (k < 1) { g_create_error = "dne_maze_novelty_host: k = " + std::to_string(k) + ", at least one neighbour is needed"; return -1; }
     maze_novelty::novelty_host(xy, n, archive, narch, k, out);
+    return 0;
+}
+
+extern "C" int dne_maze_novelty_pool_host(const float *xy, int n, const float *archive, int narch, int k, double *out) {
+    if (!xy || !out || (narch > 0 && !archive)) { g_create_error = "dne_maze_novelty_pool_host: a buffer is missing"; return -1; }
+    if (n < 1) { g_create_error = "dne_maze_novelty_pool_host: n = " + std::to_string(n) + ", at least one point is needed"; return -1; }
+    if (narch < 0) { g_create_error = "dne_maze_novelty_pool_host: narch = " + std::to_string(narch); return -1; }
+    if (k < 1) { g_create_error = "dne_maze_novelty_pool_host: k = " + std::to_string(k) + ", at least one neighbour is needed"; return -1; }
+    if ((long long)narch + n - 1 < 1) { g_create_error = "dne_maze_novelty_pool_host: the pool is empty (one member, no archive point)"; return -1; }
+    maze_novelty::novelty_pool_host(xy, n, archive, narch, k, out);
     return 0;
 }
 

@@ -11,6 +11,14 @@
 //   * novelty = (the kk = min(k, narch) first distances of that order, added one by one in that order into a double that starts at 0.0) / kk.
 // No [n][narch] matrix exists on either side.  A plain C++ compiler can include this file (the kernel is behind __HIPCC__):
 // tests/maze_novelty_asan_main.cpp does.
+//
+// Pool novelty (GA-NS): member p of n members is scored against the archive AND the population it belongs to.  Its pool is
+// the archive's points at combined slots 0 .. narch - 1 followed by the population's points at combined slots narch .. narch + n - 1, with the
+// combined slot narch + p left out -- by index, not by value: another member, or an archive point, at exactly p's position stays in the pool
+// at distance 0.  distance and sort_key are the ones above; the order is (key, combined slot), so on equal distances an archive point comes
+// before a population point; kk = min(k, narch + n - 1); the novelty is the kk first distances of that order added one by one into a double
+// that starts at 0.0, divided by kk.  A NaN member gets a NaN novelty and sorts last in the pools of the others.  An empty pool (n = 1,
+// narch = 0) has no novelty: the callers refuse it.  novelty_pool_host and k_maze_novelty_pool agree bit for bit; no [n][narch + n] matrix exists.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -67,6 +75,24 @@ inline void novelty_host(const float *xy, int n, const float *archive, int narch
     for (int p = 0; p < n; p++) {
         for (int a = 0; a < narch; a++)
             e[a] = std::make_pair(sort_key(distance(xy[2 * p], xy[2 * p + 1], archive[2 * (size_t)a], archive[2 * (size_t)a + 1])), (int32_t)a);
+        std::partial_sort(e.begin(), e.begin() + kk, e.end());
+        double s = 0.0;
+        for (int t = 0; t < kk; t++) s += key_value(e[t].first);
+        out[p] = s / (double)kk;
+    }
+}
+
+// the pool form: member p against the archive and the other n - 1 members, on (key, combined slot).  narch may be 0; narch + n - 1 >= 1.
+inline void novelty_pool_host(const float *xy, int n, const float *archive, int narch, int k, double *out) {
+    const int pool = narch + n - 1, kk = k < pool ? k : pool;
+    std::vector<std::pair<uint64_t, int32_t>> e((size_t)pool);
+    for (int p = 0; p < n; p++) {
+        size_t at = 0;
+        for (int c = 0; c < narch + n; c++) {
+            if (c == narch + p) continue;
+            const float *q = c < narch ? archive + 2 * (size_t)c : xy + 2 * (size_t)(c - narch);
+            e[at++] = std::make_pair(sort_key(distance(xy[2 * p], xy[2 * p + 1], q[0], q[1])), (int32_t)c);
+        }
         std::partial_sort(e.begin(), e.begin() + kk, e.end());
         double s = 0.0;
         for (int t = 0; t < kk; t++) s += key_value(e[t].first);
@@ -136,6 +162,76 @@ __global__ __launch_bounds__(256) void k_maze_novelty(const float *__restrict__ 
         sum += key_value(bk);
     }
     if (lane == 0 && live) out[m] = sum / (double)kk;
+}
+
+// k_maze_novelty's scheme over the pool: the tiles run over the COMBINED slots 0 .. narch + n - 1, the archive first and the population behind
+// it (a tile may hold the end of one and the start of the other), so a lane still sees its points in ascending combined slot and a candidate
+// still comes after everything already in its list.  The member's own combined slot narch + m is passed over, by index.  kk <= narch + n - 1,
+// so the kk rounds never reach an empty place.  archive is not read when narch == 0 (it may be null).  Same list, same compile-time indices.
+__global__ __launch_bounds__(256) void k_maze_novelty_pool(const float *__restrict__ xy, int n, const float *__restrict__ archive, int narch, int kk,
+                                                           double *__restrict__ out) {
+    __shared__ float2 s_pts[TILE];
+    const int lane = threadIdx.x & 63;
+    int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const bool live = m < n;
+    if (!live) m = n - 1;
+    const float px = xy[2 * (size_t)m], py = xy[2 * (size_t)m + 1];
+    const int total = narch + n, self = narch + m;
+    uint64_t key[KMAX];
+    int slot[KMAX];
+#pragma unroll
+    for (int i = 0; i < KMAX; i++) { key[i] = KEY_NONE; slot[i] = INT_MAX; }
+    uint64_t worst = KEY_NONE;
+    for (int t0 = 0; t0 < total; t0 += TILE) {
+        const int cnt = total - t0 < TILE ? total - t0 : TILE;
+        __syncthreads();                            // the tile before this one has been read by every wave
+        for (int i = threadIdx.x; i < cnt; i += 256) {
+            const int c = t0 + i;
+            s_pts[i] = c < narch ? ((const float2 *)archive)[(size_t)c] : ((const float2 *)xy)[(size_t)(c - narch)];
+        }
+        __syncthreads();
+        for (int j = lane; j < cnt; j += 64) {
+            const float2 a = s_pts[j];
+            const uint64_t ck = sort_key(distance(px, py, a.x, a.y));
+            const int cs = t0 + j;
+            if (ck < worst && cs != self) {         // (the candidate's combined slot is above every slot of the list: on equal keys it comes after)
+#pragma unroll
+                for (int i = KMAX - 1; i >= 1; i--) {
+                    const bool shift = key[i - 1] > ck, here = key[i] > ck;
+                    key[i] = shift ? key[i - 1] : here ? ck : key[i];
+                    slot[i] = shift ? slot[i - 1] : here ? cs : slot[i];
+                }
+                if (key[0] > ck) { key[0] = ck; slot[0] = cs; }
+#pragma unroll
+                for (int i = 0; i < KMAX; i++) worst = i == kk - 1 ? key[i] : worst;
+            }
+        }
+    }
+    double sum = 0.0;
+    for (int t = 0; t < kk; t++) {
+        uint64_t bk = key[0];
+        int bs = slot[0];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint64_t ok = (uint64_t)__shfl_xor((long long)bk, o);
+            const int os = __shfl_xor(bs, o);
+            if (ok < bk || (ok == bk && os < bs)) { bk = ok; bs = os; }
+        }
+        if (slot[0] == bs) {                        // a combined slot lives in one lane
+#pragma unroll
+            for (int i = 0; i < KMAX - 1; i++) { key[i] = key[i + 1]; slot[i] = slot[i + 1]; }
+            key[KMAX - 1] = KEY_NONE; slot[KMAX - 1] = INT_MAX;
+        }
+        sum += key_value(bk);
+    }
+    if (lane == 0 && live) out[m] = sum / (double)kk;
+}
+
+// archive slot have + i = the last evaluation's member members[i], in the order given (indices may repeat); one thread per point
+__global__ __launch_bounds__(256) void k_maze_archive_gather(const float *__restrict__ xy, const int32_t *__restrict__ members, int count,
+                                                             float *__restrict__ dst) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < count) ((float2 *)dst)[i] = ((const float2 *)xy)[members[i]];
 }
 #endif
 

@@ -235,6 +235,17 @@ def maze_novelty_host(xy, archive, k):
     return out
 
 
+def maze_novelty_pool_host(xy, archive, k):
+    """dne_maze_novelty_pool_host: csrc/maze_novelty.h's pool form on the CPU (no GPU, no handle): each of the points xy [n][2] against the
+    archive [narch][2] (None or empty: no archive) and the other n - 1 points -> float64 [n]"""
+    xy = _arr(xy, np.float32).reshape(-1, 2)
+    archive = _arr(np.zeros((0, 2)) if archive is None else archive, np.float32).reshape(-1, 2)
+    out = np.empty(xy.shape[0], np.float64)
+    _ck_host(load().dne_maze_novelty_pool_host(_ptr(xy, C.c_float), int(xy.shape[0]), _ptr(archive, C.c_float) if archive.size else None,
+                                               int(archive.shape[0]), int(k), _ptr(out, C.c_double)))
+    return out
+
+
 def split_genome(genome):
     """a gpu-tree genome (idx0, (idx1, power1), ...) -- the root as a bare index or a 1-tuple -- as (int64 indices, float32 powers); the root's power is 0"""
     idx = np.array([c[0] if isinstance(c, (tuple, list)) else c for c in genome], np.int64)
@@ -562,8 +573,23 @@ class Engine:
         self._ck(self.lib.dne_maze_novelty(self.h, _ptr(xy, C.c_float), n, int(k), _ptr(out, C.c_double)))
         return out
 
+    def maze_novelty_pool(self, k, xy=None, n=None):
+        """GA-NS's novelty: the mean distance of each point to its min(k, archive size + n - 1) nearest among the archive's points and the
+        OTHER n - 1 points, float64 [n] (k_maze_novelty_pool; 1 <= k <= MAZE_NOVELTY_KMAX).  xy=None scores the last evaluation's first n
+        members where the rollout left them."""
+        xy, n = self._maze_points(xy, n)
+        out = np.empty(max(n, 0), np.float64)
+        self._ck(self.lib.dne_maze_novelty_pool(self.h, _ptr(xy, C.c_float), n, int(k), _ptr(out, C.c_double)))
+        return out
+
+    def maze_archive_append_members(self, members):
+        """append the final positions of the last evaluation's members `members` (indices, in this order, repeats allowed) to the archive,
+        device to device"""
+        members = _arr(members, np.int32).reshape(-1)
+        self._ck(self.lib.dne_maze_archive_append_members(self.h, _ptr(members, C.c_int32), int(members.size)))
+
     def maze_novelty_last_ms(self):
-        """k_maze_novelty of the last maze_novelty call between two device events, milliseconds"""
+        """the scoring kernel of the last maze_novelty / maze_novelty_pool call between two device events, milliseconds"""
         self.lib.dne_maze_novelty_last_ms.restype = C.c_double
         return float(self.lib.dne_maze_novelty_last_ms(self.h))
 

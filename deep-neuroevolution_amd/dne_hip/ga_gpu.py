@@ -14,6 +14,8 @@ exp['game'] == 'maze' with exp['model'] == 'SimpleClassifier' (gym_tensorflow.ma
 a DNE_KIND_MAZE engine: the parents live in a bank on the device, a member is a (parent, noise index, power) triple that k_maze_rollout
 evaluates as it stands, selected children become parents device to device (dne_maze_ga_promote), and genomes are written out only for the
 few individuals that survive a generation.  SimpleClassifier on an Atari game and the Atari models on the maze are refused.
+With exp['novelty_search'] = {'k': ..., 'archive_prob': ...} the maze loop is GA-NS (maze_ns_main): the same GA selecting on novelty against the
+archive and the current population, scored on the device (k_maze_novelty_pool).  The key on an Atari game is refused.
 """
 import math
 import numbers
@@ -166,6 +168,8 @@ def model_scale_by(nact, kind=None):
 MODEL_KINDS = {'Model': _lib.KIND_GA, 'LargeModel': _lib.KIND_GA_LARGE}   # neuroevolution/models/dqn.py:24-47 (exp['model'], ga.py:110)
 MAZE_MODEL = 'SimpleClassifier'          # the one model of exp['game'] == 'maze' (neuroevolution/models/simple.py:29-35)
 ALGO = 'ga'                              # what maze_main's snapshot.pkl says wrote it
+ALGO_NS = 'ga_ns'                        # ... and maze_ns_main's
+NS_KEY = 'novelty_search'                # exp[NS_KEY] = {'k': neighbours, 'archive_prob': chance of a member to enter the archive}
 
 
 class HipModel(object):
@@ -217,6 +221,8 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
             asked, exp.get('game'), MAZE_MODEL))
     if maze:
         return maze_main(log_dir, engine=engine, noise=noise, seed=seed, max_iters=max_iters, **exp)
+    if NS_KEY in exp:
+        raise NotImplementedError("game {!r} with exp[{!r}]: GA-NS runs on game 'maze' only".format(exp.get('game'), NS_KEY))
     tlogger.start(log_dir)
     if engine is None:
         engine = _lib.Engine(MODEL_KINDS[exp.get('model', 'Model')], 18, max_members=exp['population_size'])
@@ -335,6 +341,8 @@ def maze_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
     a snapshot of es_gpu.main / nses_gpu.main, raises and names both.  A previous elite is evaluated again as (its bank index, idx 0,
     power 0): the child formula, bank + fl(0 * noise).  The elite's test episodes are num_test_episodes identical deterministic episodes
     at the 400-step default, as the reference runs them.  num_frames counts steps (the maze has no frame skip)."""
+    if NS_KEY in exp:
+        return maze_ns_main(log_dir, engine=engine, noise=noise, seed=seed, max_iters=max_iters, **exp)
     from . import policies, tabular_logger as tlogger
     from .es import SharedNoiseTable
     from .es_gpu import maze_file
@@ -461,6 +469,175 @@ def maze_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
         parents = new_parents
         state.stream = rs.get_state()
         os.makedirs(log_dir, exist_ok=True)                                                     # ga.py:249-254
+        with open(os.path.join(log_dir, 'snapshot.pkl'), 'wb') as file:
+            pickle.dump(state, file)
+        if state.timesteps_so_far >= exp['timesteps']:
+            break
+    return float(state.curr_solution_test), {'val': float(state.curr_solution_val)}, state
+
+
+# ---------------------------------------------------------------------------------------------- GA-NS on the hard maze
+def maze_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
+    """GA-NS (the Deep-GA paper's novelty-search GA, Lehman and Stanley's novelty) on game 'maze' under 'SimpleClassifier': maze_main's loop with
+    novelty as the fitness.  exp['novelty_search'] = {'k': 1 .. MAZE_NOVELTY_KMAX, 'archive_prob': 0 .. 1}.  Returns what maze_main returns.
+
+    The reference has no GA-NS code (gpu_implementation/README.md leaves it for later), so every decision here is ours:
+      draws        maze_main's two whole-array draws first, then rs.random_sample(n) < archive_prob: this generation's archive mask.
+      scoring      one maze_ga_eval, then maze_novelty_pool(k) where k_maze_rollout left the final positions: each member against the
+                   archive and the other members of its generation (csrc/maze_novelty.h).  The n doubles are all that comes back.
+      non-finite   a novelty that is not finite counts as 0.0 (nses_gpu's rule): the lowest there is, so a NaN policy is never selected
+                   ahead of a finite one.
+      order        descending novelty, then arrival index, by a stable host sort of the doubles (ga_select is float32 and would make
+                   ties the doubles do not have).
+      parents      the top T by novelty.  No reward elite enters the bank: every parent of the next generation is a child descriptor of
+                   this one (maze_ga_promote never takes the kept form); generation 0's roots are built once by maze_ga_build.
+      archive      after scoring, the masked members are appended in arrival order by one maze_archive_append_members, device to device:
+                   a generation is never scored against its own entries.
+      reporting    the validation set is this generation's top V by reward (ga_select), without the [elite] + carry; elite, test episodes
+                   and curr_solution_* follow ga.py's rules on that set.  The reward is never used for selection.
+      genomes      Offspring objects exist for the union of the top T by novelty and the top V by reward: state.population holds the
+                   former in novelty order, then the rest of the latter in reward order.
+      snapshot     algo = 'ga_ns', the archive, k, archive_prob and the stream; a resume pushes the archive back and continues bit for
+                   bit.  A resume from a 'ga', es_gpu or nses_gpu snapshot, or under another k or archive_prob, raises and names both.
+      T == 0       allowed: random search, with an archive that still fills.
+    Tabular keys: maze_main's, plus NoveltyMean, NoveltyMax (after the non-finite rule), ArchiveSize, BestDistanceToGoal = -max reward."""
+    from . import policies, tabular_logger as tlogger
+    from .es import SharedNoiseTable
+    from .es_gpu import maze_file
+    ns = exp[NS_KEY]
+    k, prob = int(ns['k']), float(ns['archive_prob'])
+    if not 1 <= k <= _lib.MAZE_NOVELTY_KMAX:
+        raise ValueError("novelty_search k = {}: expected 1 .. MAZE_NOVELTY_KMAX = {}".format(k, _lib.MAZE_NOVELTY_KMAX))
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError("novelty_search archive_prob = {!r}: expected a probability".format(ns['archive_prob']))
+    tlogger.start(log_dir)
+    n, T, V = exp['population_size'], exp['selection_threshold'], exp['validation_threshold']
+    if engine is None:
+        engine = _lib.Engine(_lib.KIND_MAZE, 2, max_members=n)
+    elif engine.kind != _lib.KIND_MAZE:
+        raise ValueError("game 'maze' asked for, the engine passed in is of kind {} (KIND_MAZE is {})".format(engine.kind, _lib.KIND_MAZE))
+    engine.maze_set_walls(*_lib.load_maze(maze_file(exp)))
+    noise = noise if noise is not None else SharedNoiseTable()
+    noise.attach(engine)
+    engine.maze_ga_set_init_scale(policies.simple_scale_by())
+    P = engine.P
+    rs = np.random.RandomState(seed)
+    all_tstart = time.time()
+    engine.maze_archive_clear()
+    try:
+        with open(os.path.join(log_dir, 'snapshot.pkl'), 'rb') as file:
+            state = pickle.load(file)
+        tlogger.log("Loaded iteration {} from {}".format(state.it, log_dir))
+        was_algo = getattr(state, 'algo', ALGO if isinstance(state, TrainingState) else 'es_gpu')
+        if was_algo != ALGO_NS:
+            raise ValueError("snapshot.pkl in {} was written by {!r}; this run is {!r}".format(log_dir, was_algo, ALGO_NS))
+        was = (getattr(state, 'game', None) or 'an Atari game', getattr(state, 'model', 'Model'))
+        if was != ('maze', MAZE_MODEL):
+            raise ValueError("snapshot.pkl in {} holds game {!r} under model {!r}; this run is game 'maze' under model {!r}".format(
+                log_dir, was[0], was[1], MAZE_MODEL))
+        if (state.k, state.archive_prob) != (k, prob):
+            raise ValueError("snapshot.pkl in {} holds k {}, archive_prob {!r}; this run is k {}, archive_prob {!r}".format(
+                log_dir, state.k, state.archive_prob, k, prob))
+        if len(state.archive):
+            engine.maze_archive_append(state.archive)
+        rs.set_state(state.stream)
+    except FileNotFoundError:
+        state = TrainingState(exp)
+        state.archive, state.stream = np.zeros((0, 2), np.float32), None
+    state.game, state.model, state.algo, state.k, state.archive_prob = 'maze', MAZE_MODEL, ALGO_NS, k, prob
+    if 'load_population' in exp:
+        state.copy_population(exp['load_population'])
+    parents = [o.seeds for o in state.population[:T]]               # the genomes of the bank's parents: the top T by novelty, no elite carried
+    if parents:
+        engine.maze_ga_build(parents)
+    iters = 0
+    while max_iters is None or iters < max_iters:
+        iters += 1
+        tstart_iteration = time.time()
+        if state.timesteps_so_far >= exp['timesteps']:
+            break
+        assert (len(parents) == 0 and (state.it == 0 or T == 0)) or len(parents) == T
+        power = state.sample(state.mutation_power)
+        if parents:
+            of = rs.randint(len(parents), size=n).astype(np.int32)
+        else:
+            of = np.full(n, -1, np.int32)
+        idx = rs.randint(0, len(noise.noise) - P + 1, size=n).astype(np.int64)
+        archived = np.flatnonzero(rs.random_sample(n) < prob).astype(np.int32)
+        limit = _lib.MAZE_STEPS if state.tslimit is None else min(int(state.tslimit), _lib.MAZE_STEPS)
+        rets, _, lens = engine.maze_ga_eval(of, idx, np.full(n, power, np.float32), limit)
+        raw = np.asarray(engine.maze_novelty_pool(k), np.float64)   # against the archive as it was before this generation, and the generation
+        novelty = np.where(np.isfinite(raw), raw, 0.0)
+        if archived.size:
+            engine.maze_archive_append_members(archived)
+        state.num_frames += int(lens.sum())
+        state.it += 1
+        rewards = np.asarray(rets, np.float64)
+        population_timesteps = int(lens.sum())
+        by_novelty = np.argsort(-novelty, kind='stable')            # (-novelty, arrival index)
+        by_reward = engine.ga_select(np.asarray(rets, np.float32), n)
+
+        def member(i):                                              # the descriptor of this generation's member i, and its genome
+            i = int(i)
+            if of[i] < 0:
+                return (-1, int(idx[i]), 0.0), (int(idx[i]), )
+            return (int(of[i]), int(idx[i]), float(power)), tuple(parents[of[i]]) + ((int(idx[i]), power), )
+
+        offspring, descriptor = {}, {}                              # member index -> its Offspring; id(Offspring) -> descriptor over the bank as it is
+        for i in list(by_novelty[:T]) + list(by_reward[:V]):
+            i = int(i)
+            if i not in offspring:
+                d, genome = member(i)
+                offspring[i] = Offspring(genome, [float(rets[i])], [int(lens[i])])
+                offspring[i].novelty = float(novelty[i])
+                descriptor[id(offspring[i])] = d
+        selected = [offspring[int(i)] for i in by_novelty[:T]]
+        validation_population = [offspring[int(i)] for i in by_reward[:V]]
+        state.population = selected + [o for o in validation_population if not any(o is s for s in selected)]
+        ve = exp['num_validation_episodes']
+        vr, vl = _maze_evaluate(engine, [descriptor[id(o)] for o in validation_population for _ in range(ve)], state.tslimit)
+        population_validation = [float(np.mean(vr[i * ve:(i + 1) * ve])) for i in range(len(validation_population))]
+        population_validation_len = [int(np.sum(vl[i * ve:(i + 1) * ve])) for i in range(len(validation_population))]
+        state.elite = validation_population[int(np.argmax(population_validation))]
+        er, el = _maze_evaluate(engine, [descriptor[id(state.elite)]] * exp['num_test_episodes'], None)
+        validation_timesteps = sum(population_validation_len)
+        timesteps_this_iter = population_timesteps + validation_timesteps
+        state.timesteps_so_far += timesteps_this_iter
+        state.validation_timesteps_so_far += validation_timesteps
+        if np.mean(population_validation) > state.curr_solution_val:
+            state.curr_solution = state.elite.seeds
+            state.curr_solution_val = float(np.mean(population_validation))
+            state.curr_solution_test = float(np.mean(er))
+        # the next parents on the device: the top T by novelty, every one a root (generation 0) or a child of the bank as it is
+        new_parents = [o.seeds for o in selected]
+        if new_parents and not parents:
+            engine.maze_ga_build(new_parents)
+        elif new_parents:
+            engine.maze_ga_promote(*(np.array(c, t) for c, t in zip(zip(*(descriptor[id(o)] for o in selected)), (np.int32, np.int64, np.float32))))
+        parents = new_parents
+        state.archive = engine.maze_archive()
+        dt = time.time() - tstart_iteration
+        state.time_elapsed += dt
+        for key, val in (('Iteration', state.it), ('MutationPower', power), ('PopulationEpRewMax', np.max(rewards)),
+                         ('PopulationEpRewMean', np.mean(rewards)), ('PopulationEpCount', len(rewards)),
+                         ('PopulationTimesteps', population_timesteps), ('NumSelectedIndividuals', T),
+                         ('TruncatedPopulationRewMean', np.mean([a.fitness for a in validation_population])),
+                         ('TruncatedPopulationValidationRewMean', np.mean(population_validation)),
+                         ('TruncatedPopulationEliteValidationRewMean', np.max(population_validation)),
+                         ('TruncatedPopulationEliteTestRewMean', np.mean(er)), ('TruncatedPopulationEliteTestEpCount', len(er)),
+                         ('TruncatedPopulationEliteTestEpLenSum', int(np.sum(el))), ('ValidationTimestepsThisIter', validation_timesteps),
+                         ('TimestepsThisIter', timesteps_this_iter), ('TimestepsPerSecondThisIter', timesteps_this_iter / dt),
+                         ('TimestepsSoFar', state.timesteps_so_far), ('TimeElapsedThisIter', dt), ('TimeElapsed', state.time_elapsed),
+                         ('TimeElapsedTotal', time.time() - all_tstart), ('NoveltyMean', float(np.mean(novelty))),
+                         ('NoveltyMax', float(np.max(novelty))), ('ArchiveSize', int(state.archive.shape[0])),
+                         ('BestDistanceToGoal', -float(np.max(rewards)))):
+            tlogger.record_tabular(key, val)
+        tlogger.dump_tabular()
+        if state.adaptive_tslimit:
+            if np.mean(lens >= state.tslimit) > state.incr_tslimit_threshold:
+                state.tslimit = min(state.tslimit * state.tslimit_incr_ratio, state.tslimit_max)
+        state.stream = rs.get_state()
+        os.makedirs(log_dir, exist_ok=True)
         with open(os.path.join(log_dir, 'snapshot.pkl'), 'wb') as file:
             pickle.dump(state, file)
         if state.timesteps_so_far >= exp['timesteps']:

@@ -349,6 +349,19 @@ int dne_maze_archive_get(dne_handle *h, float *xy /*[cap][2]*/, int cap);
 int dne_maze_novelty(dne_handle *h, const float *xy /*[n][2], or NULL*/, int n, int k, double *out /*[n]*/);
 int dne_maze_novelty_host(const float *xy, int n, const float *archive /*[narch][2]*/, int narch, int k, double *out);
 double dne_maze_novelty_last_ms(dne_handle *h);
+/* Pool novelty (GA-NS): member p of the n members is scored against the archive's A points at combined slots 0 .. A - 1
+ * followed by the n members at combined slots A .. A + n - 1, the combined slot A + p left out -- by index, not by value.  Distances, keys and
+ * the sequential sum are the ones above; the order is (key, combined slot), so an archive point comes before a population point at the same
+ * distance; kk = min(k, A + n - 1).  A NaN member gets a NaN novelty.  xy == NULL reads the last evaluation's first n members on the device
+ * (dne_maze_final_state's rule for n); a host xy takes any n >= 1.  dne_maze_novelty_pool_host is the same header on the CPU (narch may be
+ * 0, any k >= 1).  dne_maze_archive_append_members appends the final positions of the last evaluation's members members[0 .. count - 1], in
+ * that order, device to device (k_maze_archive_gather); indices may repeat.
+ * Refused by name, the archive left as it was: an engine of another kind, k < 1, k > DNE_MAZE_NOVELTY_KMAX, n < 1, an empty pool (n = 1 and
+ * A = 0), the NULL form beyond the last evaluation's members; for the gather count < 1 and an index outside the last evaluation's members.
+ * dne_maze_novelty_last_ms reports the scoring kernel of the last dne_maze_novelty or dne_maze_novelty_pool. */
+int dne_maze_novelty_pool(dne_handle *h, const float *xy /*[n][2], or NULL*/, int n, int k, double *out /*[n]*/);
+int dne_maze_novelty_pool_host(const float *xy, int n, const float *archive /*[narch][2]*/, int narch, int k, double *out);
+int dne_maze_archive_append_members(dne_handle *h, const int32_t *members /*[count]*/, int count);
 
 /* ---- Deep-GA on the hard maze (csrc/maze_ga.h) -----------------------------------------------
  * gpu_implementation/ga.py on SimpleClassifier.  A genome is (idx0, (idx1, power1), ...) as seeds[] / powers[] (powers[0] is not read):
