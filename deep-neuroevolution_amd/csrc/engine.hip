@@ -2073,9 +2073,14 @@ static maze::Header maze_header(const float *h8) {
     return m;
 }
 
+// what every entry point of the three maze sections asks first
+static int needs_maze(dne_handle *h, const char *call) {
+    return h->maze ? 0 : h->fail("%s needs a DNE_KIND_MAZE engine (this one: kind %d)", call, h->L.kind);
+}
+
 extern "C" int dne_maze_set_walls(dne_handle *h, const float *header8, const float *lines, int n) {
     DeviceGuard dg(h);
-    if (!h->maze) return h->fail("dne_maze_set_walls needs a DNE_KIND_MAZE engine (this one: kind %d)", h->L.kind);
+    if (needs_maze(h, "dne_maze_set_walls")) return -1;
     if (maze_check(&h->err, header8, lines, n)) return -1;
     HCHECK(h, hipStreamSynchronize(h->stream));
     HCHECK(h, hipMemcpy(h->maze_walls, lines, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice));
@@ -2084,23 +2089,30 @@ extern "C" int dne_maze_set_walls(dne_handle *h, const float *header8, const flo
     return 0;
 }
 
-static maze::RolloutArgs maze_args(dne_handle *h, int first, int count, int tslimit) {
+// where a rollout's members come from: descriptors (slot, off, scale) over the rows of `bases`
+struct MazeMembers { const float *bases; const int32_t *slot; const int64_t *off; const float *scale; };
+
+// the members set by dne_set_members
+static MazeMembers maze_set_members(dne_handle *h) { return {h->bases, h->m_slot, h->m_off, h->m_scale}; }
+
+// what k_maze_rollout reads for members [first, first + count) of M; its outputs are left null (maze_eval_members and the trace set theirs)
+static maze::RolloutArgs maze_args(dne_handle *h, const MazeMembers &M, int first, int count, int tslimit) {
     maze::RolloutArgs A{};
-    A.noise = h->noise; A.bases = h->bases; A.base_stride = h->base_stride;
-    A.m_slot = h->m_slot; A.m_off = h->m_off; A.m_scale = h->m_scale;
+    A.noise = h->noise; A.bases = M.bases; A.base_stride = h->base_stride;
+    A.m_slot = M.slot; A.m_off = M.off; A.m_scale = M.scale;
     A.first = first; A.count = count; A.hdr = h->maze_hdr; A.walls = h->maze_walls; A.nw = h->maze_nw; A.tslimit = tslimit;
     return A;
 }
 
-// members [0, n) of A's descriptors, one whole episode each, one launch
-static int maze_eval_args(dne_handle *h, maze::RolloutArgs A, int n, int tslimit, float *returns, float *signreturns, int32_t *lengths, uint8_t *bc_out) {
+// members [0, n) of M, one whole episode each, one launch
+static int maze_eval_members(dne_handle *h, const MazeMembers &M, int n, int tslimit, float *returns, float *signreturns, int32_t *lengths, uint8_t *bc_out) {
     if (h->maze_nw < 1) return h->fail("DNE_KIND_MAZE: no maze loaded (dne_maze_set_walls comes before an evaluation)");
     if (tslimit <= 0) return h->fail("timestep limit must be positive");
     if (bc_out && !h->bc) return h->fail("behaviour characterisations requested but the engine was created with record_bc = 0");
     if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
     const size_t bc_floats = (size_t)n * std::max(h->cfg.bc_max_steps, 1) * 2;
     if (h->bc && bc_out) HCHECK(h, hipMemsetAsync(h->bc, 0, bc_floats * sizeof(float), h->stream));   // rows past an episode's length read as zero
-    A.first = 0; A.count = n; A.hdr = h->maze_hdr; A.walls = h->maze_walls; A.nw = h->maze_nw; A.tslimit = tslimit;
+    maze::RolloutArgs A = maze_args(h, M, 0, n, tslimit);
     A.ret = h->ret; A.sign = h->sign; A.len = h->len; A.xy = h->maze_xy;
     A.bc = (float *)h->bc; A.bc_max_steps = h->bc ? std::max(h->cfg.bc_max_steps, 1) : 0;
     HCHECK(h, hipEventRecord(h->ev_a, h->stream));
@@ -2123,14 +2135,13 @@ static int maze_eval_args(dne_handle *h, maze::RolloutArgs A, int n, int tslimit
     return 0;
 }
 
-// members [0, n) set by dne_set_members
 static int maze_eval(dne_handle *h, int n, int tslimit, float *returns, float *signreturns, int32_t *lengths, uint8_t *bc_out) {
-    return maze_eval_args(h, maze_args(h, 0, n, tslimit), n, tslimit, returns, signreturns, lengths, bc_out);
+    return maze_eval_members(h, maze_set_members(h), n, tslimit, returns, signreturns, lengths, bc_out);
 }
 
 extern "C" int dne_maze_final_state(dne_handle *h, int n, float *xy) {
     DeviceGuard dg(h);
-    if (!h->maze) return h->fail("dne_maze_final_state needs a DNE_KIND_MAZE engine (this one: kind %d)", h->L.kind);
+    if (needs_maze(h, "dne_maze_final_state")) return -1;
     if (n < 1 || n > h->maze_last_n) return h->fail("dne_maze_final_state: %d members asked for, the last evaluation ran %d", n, h->maze_last_n);
     HCHECK(h, hipStreamSynchronize(h->stream));
     HCHECK(h, hipMemcpy(xy, h->maze_xy, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost));
@@ -2141,7 +2152,7 @@ extern "C" int dne_maze_final_state(dne_handle *h, int n, float *xy) {
 // writes it.  The accumulators of the last evaluation are left alone.
 extern "C" int dne_maze_debug_trace(dne_handle *h, int member, int tslimit, float *trace) {
     DeviceGuard dg(h);
-    if (!h->maze) return h->fail("dne_maze_debug_trace needs a DNE_KIND_MAZE engine (this one: kind %d)", h->L.kind);
+    if (needs_maze(h, "dne_maze_debug_trace")) return -1;
     if (h->maze_nw < 1) return h->fail("DNE_KIND_MAZE: no maze loaded (dne_maze_set_walls comes before an evaluation)");
     if (member < 0 || member >= (int)h->host_slot.size()) return h->fail("dne_maze_debug_trace: member %d, dne_set_members set %zu", member, h->host_slot.size());
     if (tslimit <= 0 || !trace) return h->fail("dne_maze_debug_trace: bad arguments");
@@ -2149,7 +2160,7 @@ extern "C" int dne_maze_debug_trace(dne_handle *h, int member, int tslimit, floa
     const int steps = std::min(tslimit, (int)maze::EPISODE_STEPS);
     DevBuf<float> d;
     HCHECK(h, d.alloc((size_t)steps * maze::TRACE_W));
-    maze::RolloutArgs A = maze_args(h, member, 1, tslimit);
+    maze::RolloutArgs A = maze_args(h, maze_set_members(h), member, 1, tslimit);
     A.trace = d;
     hipLaunchKernelGGL(maze::k_maze_rollout, dim3(1), dim3(64), 0, h->stream, A);
     HCHECK(h, hipGetLastError());
@@ -2199,7 +2210,7 @@ extern "C" int dne_maze_math_host(int fn, const double *x, int n, double *out) {
 
 extern "C" int dne_maze_debug_math(dne_handle *h, int fn, const double *x, int n, double *out) {
     DeviceGuard dg(h);
-    if (!h->maze) return h->fail("dne_maze_debug_math needs a DNE_KIND_MAZE engine (this one: kind %d)", h->L.kind);
+    if (needs_maze(h, "dne_maze_debug_math")) return -1;
     if (fn < 0 || fn >= maze::MATH_FNS || n < 1 || !x || !out) return h->fail("dne_maze_debug_math: bad arguments (fn 0..3, n >= 1)");
     DevBuf<double> dx, dout;
     HCHECK(h, dx.alloc((size_t)n)); HCHECK(h, dout.alloc(2 * (size_t)n));
@@ -2212,16 +2223,11 @@ extern "C" int dne_maze_debug_math(dne_handle *h, int fn, const double *x, int n
 }
 
 // ------------------------------------------------------------------------------- Deep-GA on the hard maze (csrc/maze_ga.h)
-#define MZG_NEEDS_MAZE(h, call)                                                                 \
-    do {                                                                                        \
-        if (!(h)->maze) return (h)->fail("%s needs a DNE_KIND_MAZE engine (this one: kind %d)", call, (h)->L.kind); \
-    } while (0)
-
 static float *mzg_bank(dne_handle *h, int half) { return h->mzg_mem + (size_t)half * h->M * h->base_stride; }
 
 extern "C" int dne_maze_ga_set_init_scale(dne_handle *h, const float *scale_by, size_t n) {
     DeviceGuard dg(h);
-    MZG_NEEDS_MAZE(h, "dne_maze_ga_set_init_scale");
+    if (needs_maze(h, "dne_maze_ga_set_init_scale")) return -1;
     if (n != (size_t)maze_ga::P || !scale_by) return h->fail("dne_maze_ga_set_init_scale: expected %d values, got %zu", maze_ga::P, n);
     if (!h->mzg_mem) {
         const size_t M = h->M;
@@ -2254,7 +2260,7 @@ static int mzg_upload_members(dne_handle *h, int n, const int32_t *a, const int6
 
 extern "C" int dne_maze_ga_build(dne_handle *h, int T, const int32_t *chain_offsets, const int64_t *seeds, const float *powers) {
     DeviceGuard dg(h);
-    MZG_NEEDS_MAZE(h, "dne_maze_ga_build");
+    if (needs_maze(h, "dne_maze_ga_build")) return -1;
     if (mzg_ready(h, "dne_maze_ga_build", false)) return -1;
     if (T < 1 || T > h->M) return h->fail("dne_maze_ga_build: T = %d outside [1, max_members = %d]", T, h->M);
     if (!chain_offsets || !seeds || !powers) return h->fail("dne_maze_ga_build: a buffer is missing");
@@ -2283,7 +2289,7 @@ extern "C" int dne_maze_ga_build(dne_handle *h, int T, const int32_t *chain_offs
 
 extern "C" int dne_maze_ga_promote(dne_handle *h, int T_new, const int32_t *parent, const int64_t *idx, const float *power) {
     DeviceGuard dg(h);
-    MZG_NEEDS_MAZE(h, "dne_maze_ga_promote");
+    if (needs_maze(h, "dne_maze_ga_promote")) return -1;
     if (mzg_ready(h, "dne_maze_ga_promote", false)) return -1;
     if (T_new < 1 || T_new > h->M) return h->fail("dne_maze_ga_promote: T = %d outside [1, max_members = %d]", T_new, h->M);
     if (!parent || !idx || !power) return h->fail("dne_maze_ga_promote: a buffer is missing");
@@ -2305,7 +2311,7 @@ extern "C" int dne_maze_ga_promote(dne_handle *h, int T_new, const int32_t *pare
 extern "C" int dne_maze_ga_eval(dne_handle *h, int n, const int32_t *parent, const int64_t *idx, const float *power, int tslimit,
                                 float *returns, float *signreturns, int32_t *lengths) {
     DeviceGuard dg(h);
-    MZG_NEEDS_MAZE(h, "dne_maze_ga_eval");
+    if (needs_maze(h, "dne_maze_ga_eval")) return -1;
     if (mzg_ready(h, "dne_maze_ga_eval", true)) return -1;
     if (n < 1 || n > h->M) return h->fail("dne_maze_ga_eval: n = %d outside [1, max_members = %d]", n, h->M);
     if (!parent || !idx || !power || !returns || !lengths) return h->fail("dne_maze_ga_eval: a buffer is missing");
@@ -2330,20 +2336,17 @@ extern "C" int dne_maze_ga_eval(dne_handle *h, int n, const int32_t *parent, con
                            (const int32_t *)h->mzg_slot, (const int64_t *)h->mzg_off, root0, h->mzg_mem, h->base_stride);
         HCHECK(h, hipGetLastError());
     }
-    maze::RolloutArgs A{};
-    A.noise = h->noise; A.bases = h->mzg_mem; A.base_stride = h->base_stride;
-    A.m_slot = h->mzg_slot; A.m_off = h->mzg_off; A.m_scale = h->mzg_scale;
-    return maze_eval_args(h, A, n, tslimit, returns, signreturns, lengths, nullptr);
+    return maze_eval_members(h, MazeMembers{h->mzg_mem, h->mzg_slot, h->mzg_off, h->mzg_scale}, n, tslimit, returns, signreturns, lengths, nullptr);
 }
 
 extern "C" int dne_maze_ga_parents(dne_handle *h) {
-    MZG_NEEDS_MAZE(h, "dne_maze_ga_parents");
+    if (needs_maze(h, "dne_maze_ga_parents")) return -1;
     return h->mzg_T;
 }
 
 extern "C" int dne_maze_ga_get_parent(dne_handle *h, int j, float *out) {
     DeviceGuard dg(h);
-    MZG_NEEDS_MAZE(h, "dne_maze_ga_get_parent");
+    if (needs_maze(h, "dne_maze_ga_get_parent")) return -1;
     if (j < 0 || j >= h->mzg_T) return h->fail("dne_maze_ga_get_parent: parent %d, the bank holds %d", j, h->mzg_T);
     if (!out) return h->fail("dne_maze_ga_get_parent: no output buffer");
     HCHECK(h, hipStreamSynchronize(h->stream));
@@ -2400,11 +2403,6 @@ static int mzn_reserve(dne_handle *h, T *&p, size_t &cap, size_t need, size_t ke
     return 0;
 }
 
-#define MZN_NEEDS_MAZE(h, call)                                                                 \
-    do {                                                                                        \
-        if (!(h)->maze) return (h)->fail("%s needs a DNE_KIND_MAZE engine (this one: kind %d)", call, (h)->L.kind); \
-    } while (0)
-
 // xy == NULL: the last evaluation's members where k_maze_rollout left them
 static int mzn_check_members(dne_handle *h, const char *call, const float *xy, int n) {
     if (n < 1) return h->fail("%s: n = %d, at least one point is needed", call, n);
@@ -2412,13 +2410,19 @@ static int mzn_check_members(dne_handle *h, const char *call, const float *xy, i
     return 0;
 }
 
+// room behind the archive's points for `more` of them; the points already there survive a reallocation
+static int mzn_archive_room(dne_handle *h, const char *call, int more) {
+    const size_t have = (size_t)h->mzn_arch_n;
+    if (have + (size_t)more > (size_t)INT_MAX / 2) return h->fail("%s: %zu points would not fit an int", call, have + (size_t)more);
+    return mzn_reserve(h, h->mzn_arch, h->mzn_arch_cap, 2 * (have + more), 2 * have, 2 * MZN_ARCH_CAP0, "maze_archive");
+}
+
 extern "C" int dne_maze_archive_append(dne_handle *h, const float *xy, int n) {
     DeviceGuard dg(h);
-    MZN_NEEDS_MAZE(h, "dne_maze_archive_append");
+    if (needs_maze(h, "dne_maze_archive_append")) return -1;
     if (mzn_check_members(h, "dne_maze_archive_append", xy, n)) return -1;
+    if (mzn_archive_room(h, "dne_maze_archive_append", n)) return -1;
     const size_t have = (size_t)h->mzn_arch_n;
-    if (have + (size_t)n > (size_t)INT_MAX / 2) return h->fail("dne_maze_archive_append: %zu points would not fit an int", have + (size_t)n);
-    if (mzn_reserve(h, h->mzn_arch, h->mzn_arch_cap, 2 * (have + n), 2 * have, 2 * MZN_ARCH_CAP0, "maze_archive")) return -1;
     if (xy) {
         HCHECK(h, hipMemcpyAsync(h->mzn_arch + 2 * have, xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
         HCHECK(h, hipStreamSynchronize(h->stream));   // the caller's buffer is free again
@@ -2431,19 +2435,19 @@ extern "C" int dne_maze_archive_append(dne_handle *h, const float *xy, int n) {
 
 extern "C" int dne_maze_archive_clear(dne_handle *h) {
     DeviceGuard dg(h);
-    MZN_NEEDS_MAZE(h, "dne_maze_archive_clear");
+    if (needs_maze(h, "dne_maze_archive_clear")) return -1;
     h->mzn_arch_n = 0;   // (the buffer stays; a later append lands behind every call already on the stream)
     return 0;
 }
 
 extern "C" int dne_maze_archive_size(dne_handle *h) {
-    MZN_NEEDS_MAZE(h, "dne_maze_archive_size");
+    if (needs_maze(h, "dne_maze_archive_size")) return -1;
     return h->mzn_arch_n;
 }
 
 extern "C" int dne_maze_archive_get(dne_handle *h, float *xy, int cap) {
     DeviceGuard dg(h);
-    MZN_NEEDS_MAZE(h, "dne_maze_archive_get");
+    if (needs_maze(h, "dne_maze_archive_get")) return -1;
     if (cap < h->mzn_arch_n) return h->fail("dne_maze_archive_get: room for %d points, the archive holds %d", cap, h->mzn_arch_n);
     if (h->mzn_arch_n > 0) {
         if (!xy) return h->fail("dne_maze_archive_get: no buffer");
@@ -2453,14 +2457,19 @@ extern "C" int dne_maze_archive_get(dne_handle *h, float *xy, int cap) {
     return 0;
 }
 
-extern "C" int dne_maze_novelty(dne_handle *h, const float *xy, int n, int k, double *out) {
-    DeviceGuard dg(h);
-    MZN_NEEDS_MAZE(h, "dne_maze_novelty");
-    if (mzn_check_members(h, "dne_maze_novelty", xy, n)) return -1;
-    if (k < 1) return h->fail("dne_maze_novelty: k = %d, at least one neighbour is needed", k);
-    if (k > DNE_MAZE_NOVELTY_KMAX) return h->fail("dne_maze_novelty: k = %d, the kernel keeps at most DNE_MAZE_NOVELTY_KMAX = %d neighbours", k, DNE_MAZE_NOVELTY_KMAX);
-    if (h->mzn_arch_n < 1) return h->fail("dne_maze_novelty: the archive is empty (dne_maze_archive_append)");
-    if (!out) return h->fail("dne_maze_novelty: no output buffer");
+// what both scoring calls refuse alike, before the refusals of their own
+static int mzn_score_args(dne_handle *h, const char *call, const float *xy, int n, int k) {
+    if (needs_maze(h, call)) return -1;
+    if (mzn_check_members(h, call, xy, n)) return -1;
+    if (k < 1) return h->fail("%s: k = %d, at least one neighbour is needed", call, k);
+    if (k > DNE_MAZE_NOVELTY_KMAX) return h->fail("%s: k = %d, the kernel keeps at most DNE_MAZE_NOVELTY_KMAX = %d neighbours", call, k, DNE_MAZE_NOVELTY_KMAX);
+    return 0;
+}
+
+// ... and what both do behind them: xy staged (or the last evaluation's positions), the form's kernel over the kk <= k nearest between two
+// events, the n novelties back
+static int mzn_score(dne_handle *h, const char *call, bool pool, const float *xy, int n, int kk, double *out) {
+    if (!out) return h->fail("%s: no output buffer", call);
     const float *pts = h->maze_xy;
     if (xy) {
         if (mzn_reserve(h, h->mzn_xy, h->mzn_xy_cap, 2 * (size_t)n, 0, 4096, "maze_novelty_xy")) return -1;
@@ -2469,8 +2478,8 @@ extern "C" int dne_maze_novelty(dne_handle *h, const float *xy, int n, int k, do
     }
     if (mzn_reserve(h, h->mzn_out, h->mzn_out_cap, (size_t)n, 0, 4096, "maze_novelty_out")) return -1;
     HCHECK(h, hipEventRecord(h->ev_a, h->stream));
-    hipLaunchKernelGGL(maze_novelty::k_maze_novelty, dim3((n + 3) / 4), dim3(256), 0, h->stream, pts, n, (const float *)h->mzn_arch, h->mzn_arch_n,
-                       std::min(k, h->mzn_arch_n), h->mzn_out);
+    hipLaunchKernelGGL((pool ? maze_novelty::k_maze_novelty_pool : maze_novelty::k_maze_novelty), dim3((n + 3) / 4), dim3(256), 0, h->stream, pts, n,
+                       (const float *)h->mzn_arch, h->mzn_arch_n, kk, h->mzn_out);
     HCHECK(h, hipGetLastError());
     HCHECK(h, hipEventRecord(h->ev_b, h->stream));
     HCHECK(h, hipMemcpyAsync(out, h->mzn_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2479,50 +2488,35 @@ extern "C" int dne_maze_novelty(dne_handle *h, const float *xy, int n, int k, do
     HCHECK(h, hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
     h->mzn_last_ms = ms;
     return 0;
+}
+
+extern "C" int dne_maze_novelty(dne_handle *h, const float *xy, int n, int k, double *out) {
+    DeviceGuard dg(h);
+    if (mzn_score_args(h, "dne_maze_novelty", xy, n, k)) return -1;
+    if (h->mzn_arch_n < 1) return h->fail("dne_maze_novelty: the archive is empty (dne_maze_archive_append)");
+    return mzn_score(h, "dne_maze_novelty", false, xy, n, std::min(k, h->mzn_arch_n), out);
 }
 
 // pool novelty (GA-NS): every member against the archive and the other members
 extern "C" int dne_maze_novelty_pool(dne_handle *h, const float *xy, int n, int k, double *out) {
     DeviceGuard dg(h);
-    MZN_NEEDS_MAZE(h, "dne_maze_novelty_pool");
-    if (mzn_check_members(h, "dne_maze_novelty_pool", xy, n)) return -1;
-    if (k < 1) return h->fail("dne_maze_novelty_pool: k = %d, at least one neighbour is needed", k);
-    if (k > DNE_MAZE_NOVELTY_KMAX) return h->fail("dne_maze_novelty_pool: k = %d, the kernel keeps at most DNE_MAZE_NOVELTY_KMAX = %d neighbours", k, DNE_MAZE_NOVELTY_KMAX);
+    if (mzn_score_args(h, "dne_maze_novelty_pool", xy, n, k)) return -1;
     if (h->mzn_arch_n + (n - 1) < 1) return h->fail("dne_maze_novelty_pool: the pool is empty (one member, no archive point)");
     if ((size_t)h->mzn_arch_n + (size_t)n > (size_t)INT_MAX / 2) return h->fail("dne_maze_novelty_pool: %zu combined slots would not fit an int", (size_t)h->mzn_arch_n + (size_t)n);
-    if (!out) return h->fail("dne_maze_novelty_pool: no output buffer");
-    const float *pts = h->maze_xy;
-    if (xy) {
-        if (mzn_reserve(h, h->mzn_xy, h->mzn_xy_cap, 2 * (size_t)n, 0, 4096, "maze_novelty_xy")) return -1;
-        HCHECK(h, hipMemcpyAsync(h->mzn_xy, xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        pts = h->mzn_xy;
-    }
-    if (mzn_reserve(h, h->mzn_out, h->mzn_out_cap, (size_t)n, 0, 4096, "maze_novelty_out")) return -1;
-    HCHECK(h, hipEventRecord(h->ev_a, h->stream));
-    hipLaunchKernelGGL(maze_novelty::k_maze_novelty_pool, dim3((n + 3) / 4), dim3(256), 0, h->stream, pts, n, (const float *)h->mzn_arch, h->mzn_arch_n,
-                       std::min(k, h->mzn_arch_n + n - 1), h->mzn_out);
-    HCHECK(h, hipGetLastError());
-    HCHECK(h, hipEventRecord(h->ev_b, h->stream));
-    HCHECK(h, hipMemcpyAsync(out, h->mzn_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    float ms = 0;
-    HCHECK(h, hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
-    h->mzn_last_ms = ms;
-    return 0;
+    return mzn_score(h, "dne_maze_novelty_pool", true, xy, n, std::min(k, h->mzn_arch_n + n - 1), out);
 }
 
 // archive slot A + i = the final position of the last evaluation's member members[i], device to device (k_maze_archive_gather)
 extern "C" int dne_maze_archive_append_members(dne_handle *h, const int32_t *members, int count) {
     DeviceGuard dg(h);
-    MZN_NEEDS_MAZE(h, "dne_maze_archive_append_members");
+    if (needs_maze(h, "dne_maze_archive_append_members")) return -1;
     if (count < 1) return h->fail("dne_maze_archive_append_members: count = %d, at least one member is needed", count);
     if (!members) return h->fail("dne_maze_archive_append_members: no member indices");
     for (int i = 0; i < count; i++)
         if (members[i] < 0 || members[i] >= h->maze_last_n)
             return h->fail("dne_maze_archive_append_members: index %d is member %d, the last evaluation ran %d", i, members[i], h->maze_last_n);
+    if (mzn_archive_room(h, "dne_maze_archive_append_members", count)) return -1;
     const size_t have = (size_t)h->mzn_arch_n;
-    if (have + (size_t)count > (size_t)INT_MAX / 2) return h->fail("dne_maze_archive_append_members: %zu points would not fit an int", have + (size_t)count);
-    if (mzn_reserve(h, h->mzn_arch, h->mzn_arch_cap, 2 * (have + count), 2 * have, 2 * MZN_ARCH_CAP0, "maze_archive")) return -1;
     if (mzn_reserve(h, h->mzn_idx, h->mzn_idx_cap, (size_t)count, 0, 4096, "maze_archive_members")) return -1;
     HCHECK(h, hipMemcpyAsync(h->mzn_idx, members, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(maze_novelty::k_maze_archive_gather, dim3((count + 255) / 256), dim3(256), 0, h->stream, (const float *)h->maze_xy,
@@ -2555,6 +2549,7 @@ extern "C" int dne_maze_novelty_pool_host(const float *xy, int n, const float *a
     return 0;
 }
 
+// ------------------------------------------------------------------------------- evaluations by descriptor: antithetic pairs, members as set
 extern "C" int dne_es_eval(dne_handle *h, const int64_t *idx, int n, float sigma, int tslimit, const uint32_t *env_seed,
                            float *returns_n2, float *signreturns_n2, int32_t *lengths_n2, uint8_t *bc) {
     DeviceGuard dg(h);

@@ -1,6 +1,6 @@
 // maze_novelty.h -- nses.py:12-32 for the hard maze's behaviour characterisation, ONE float32 point (x, y) per member (MazeFinalState,
 // tf_maze.py:64-66): the mean distance of a member to its k nearest archive points, as ONE __host__ __device__ text for the arithmetic, a
-// CPU twin (novelty_host, behind dne_maze_novelty_host) and k_maze_novelty for gfx950, which agree bit for bit.  DESIGN.md section 12
+// CPU twin (behind dne_maze_novelty_host) and a kernel for gfx950, which agree bit for bit.  DESIGN.md section 12
 // ("Novelty on the maze") holds the contract:
 //   * d(p, a) = sqrt(dx * dx + dy * dy) with dx = (double)ax - (double)px, dy likewise: IEEE double operations, the sum unfused
 //     (-ffp-contract=off on both passes), sqrt the correctly rounded one (as nv_distance of novelty.h relies on).  nses.py:12-20 on
@@ -9,16 +9,20 @@
 //     never negative and never -0.0, so its bit pattern as an unsigned integer orders as the value does; a NaN is sent to one pattern
 //     above +inf's.  That integer is the key both sides sort by (sort_key);
 //   * novelty = (the kk = min(k, narch) first distances of that order, added one by one in that order into a double that starts at 0.0) / kk.
-// No [n][narch] matrix exists on either side.  A plain C++ compiler can include this file (the kernel is behind __HIPCC__):
-// tests/maze_novelty_asan_main.cpp does.
+// A plain C++ compiler can include this file (the kernels are behind __HIPCC__): tests/maze_novelty_asan_main.cpp does.
 //
-// Pool novelty (GA-NS): member p of n members is scored against the archive AND the population it belongs to.  Its pool is
-// the archive's points at combined slots 0 .. narch - 1 followed by the population's points at combined slots narch .. narch + n - 1, with the
-// combined slot narch + p left out -- by index, not by value: another member, or an archive point, at exactly p's position stays in the pool
-// at distance 0.  distance and sort_key are the ones above; the order is (key, combined slot), so on equal distances an archive point comes
-// before a population point; kk = min(k, narch + n - 1); the novelty is the kk first distances of that order added one by one into a double
-// that starts at 0.0, divided by kk.  A NaN member gets a NaN novelty and sorts last in the pools of the others.  An empty pool (n = 1,
-// narch = 0) has no novelty: the callers refuse it.  novelty_pool_host and k_maze_novelty_pool agree bit for bit; no [n][narch + n] matrix exists.
+// The text has two forms.  The archive form (NS-ES, section 12) is the one above.  The pool form (GA-NS) scores member p of n
+// members against the archive AND the population it belongs to, and differs in three things:
+//   * the slots are the combined ones: the archive's points at 0 .. narch - 1, then the population's points at narch .. narch + n - 1, so on
+//     equal distances an archive point comes before a population point;
+//   * a point at combined slot c >= narch is member c - narch's;
+//   * p's own combined slot narch + p is left out -- by index, not by value: another member, or an archive point, at exactly p's position
+//     stays in at distance 0.
+// Hence kk = min(k, narch + n - 1); a NaN member gets a NaN novelty and sorts last for the others; narch may be 0, and a pool with nothing in it
+// (n = 1, narch = 0) has no novelty: the callers refuse it.  On the CPU the two forms are one body (novelty_host_body behind novelty_host /
+// novelty_pool_host); on the device they are two kernels with the same scheme, k_maze_novelty and k_maze_novelty_pool -- one templated body
+// behind both compiled to a slower k_maze_novelty, so the kernels stay as they were.  Host and device agree bit for
+// bit; no [n][narch] or [n][narch + n] matrix exists on either side.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -69,27 +73,15 @@ MZN_HD double key_value(uint64_t key) {
 }
 
 // ---- the CPU side: a plain partial sort on (key, slot), then the sum in that order ----------------------------------------------------------
-inline void novelty_host(const float *xy, int n, const float *archive, int narch, int k, double *out) {
-    const int kk = k < narch ? k : narch;
-    std::vector<std::pair<uint64_t, int32_t>> e((size_t)narch);
-    for (int p = 0; p < n; p++) {
-        for (int a = 0; a < narch; a++)
-            e[a] = std::make_pair(sort_key(distance(xy[2 * p], xy[2 * p + 1], archive[2 * (size_t)a], archive[2 * (size_t)a + 1])), (int32_t)a);
-        std::partial_sort(e.begin(), e.begin() + kk, e.end());
-        double s = 0.0;
-        for (int t = 0; t < kk; t++) s += key_value(e[t].first);
-        out[p] = s / (double)kk;
-    }
-}
-
-// the pool form: member p against the archive and the other n - 1 members, on (key, combined slot).  narch may be 0; narch + n - 1 >= 1.
-inline void novelty_pool_host(const float *xy, int n, const float *archive, int narch, int k, double *out) {
-    const int pool = narch + n - 1, kk = k < pool ? k : pool;
+// POOL: the entries are the combined slots 0 .. narch + n - 1 without narch + p (narch may be 0; narch + n - 1 >= 1), else the archive's slots
+template <bool POOL>
+inline void novelty_host_body(const float *xy, int n, const float *archive, int narch, int k, double *out) {
+    const int total = POOL ? narch + n : narch, pool = POOL ? total - 1 : total, kk = k < pool ? k : pool;
     std::vector<std::pair<uint64_t, int32_t>> e((size_t)pool);
     for (int p = 0; p < n; p++) {
         size_t at = 0;
-        for (int c = 0; c < narch + n; c++) {
-            if (c == narch + p) continue;
+        for (int c = 0; c < total; c++) {
+            if (POOL && c == narch + p) continue;
             const float *q = c < narch ? archive + 2 * (size_t)c : xy + 2 * (size_t)(c - narch);
             e[at++] = std::make_pair(sort_key(distance(xy[2 * p], xy[2 * p + 1], q[0], q[1])), (int32_t)c);
         }
@@ -99,6 +91,9 @@ inline void novelty_pool_host(const float *xy, int n, const float *archive, int 
         out[p] = s / (double)kk;
     }
 }
+
+inline void novelty_host(const float *xy, int n, const float *archive, int narch, int k, double *out) { novelty_host_body<false>(xy, n, archive, narch, k, out); }
+inline void novelty_pool_host(const float *xy, int n, const float *archive, int narch, int k, double *out) { novelty_host_body<true>(xy, n, archive, narch, k, out); }
 
 #if defined(__HIPCC__)
 // ---- the device side --------------------------------------------------------------------------------------------------------------------------

@@ -47,22 +47,10 @@ import numpy as np
 from . import _lib
 from .es import SharedNoiseTable, get_ref_batch, optimizer_args, parse_cutoff
 from .ga_gpu import Offspring, Schedule, model_scale_by
+from .maze_run import MAZE_FILE, MAZE_MODEL, check_engine, maze_file, open_engine   # noqa: F401 (MAZE_FILE, maze_file: read as es_gpu's by callers)
 
 # exp['model'] (es.py:144): neuroevolution/models/batchnorm.py:52 (in either flat layout, FLAT_LAYOUTS) and models/dqn.py:39
 MODEL_KINDS = {'ModelVirtualBN': _lib.KIND_ES, 'LargeModel': _lib.KIND_GA_LARGE}
-MAZE_MODEL = 'SimpleClassifier'          # the one model of exp['game'] == 'maze' (neuroevolution/models/simple.py:29-35)
-MAZE_FILE = 'hard_maze.txt'              # tf_maze.py:28 names the file so, relative to the working directory; exp['maze_file'] overrides it
-_MAZE_FIXTURE = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), 'tests', 'golden', 'hard_maze.txt')
-
-
-def maze_file(exp):
-    """the maze of a run: exp['maze_file'], else MAZE_FILE in the working directory, else the copy of the reference's file among the test fixtures"""
-    path = exp.get('maze_file', MAZE_FILE)
-    if os.path.exists(path):
-        return path
-    if 'maze_file' not in exp and os.path.exists(_MAZE_FIXTURE):
-        return _MAZE_FIXTURE
-    raise FileNotFoundError("maze file {!r} not found (exp['maze_file'] names it; the reference ships gym_tensorflow/maze/hard_maze.txt)".format(path))
 FLAT_LAYOUTS = {'es_distributed': _lib.KIND_ES, 'native': _lib.KIND_ES_VBN}   # exp['flat_layout'] -> the engine kind that runs it
 
 
@@ -145,8 +133,7 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
     if maze:                                                        # gym_tensorflow.make(game='maze'): the hard maze under SimpleClassifier
         if exp.get('game') != 'maze':
             raise ValueError("game {!r} asked for, the engine passed in (kind {}) runs 'maze'".format(exp.get('game'), engine.kind))
-        if engine is not None and engine.kind != _lib.KIND_MAZE:
-            raise ValueError("game 'maze' asked for, the engine passed in is of kind {} (KIND_MAZE is {})".format(engine.kind, _lib.KIND_MAZE))
+        check_engine(engine)
         if asked is not None and asked != MAZE_MODEL:
             raise NotImplementedError("model {!r} on game 'maze': this loop runs {!r} there".format(asked, MAZE_MODEL))
     elif asked == MAZE_MODEL:
@@ -161,10 +148,8 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
         layout = 'native'
         if exp.get('flat_layout', layout) != layout:
             raise ValueError("flat_layout {!r}: SimpleClassifier has one layout, 'native'".format(exp['flat_layout']))
-        if engine is None:
-            engine = _lib.Engine(_lib.KIND_MAZE, 2, max_members=2 * n_pairs)
+        engine, noise = open_engine(exp, engine, noise, 2 * n_pairs)
         scale_by = policies.simple_scale_by()
-        engine.maze_set_walls(*_lib.load_maze(maze_file(exp)))
     elif large:                                                       # one flat layout, the model's own; no reference batch
         layout = 'native'
         if exp.get('flat_layout', layout) != layout:
@@ -183,8 +168,9 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
         if layout is None or exp.get('flat_layout', layout) != layout:
             raise ValueError("flat_layout {!r} asked for, the engine passed in (kind {}) runs {!r}".format(
                 exp.get('flat_layout'), engine.kind, layout))
-    noise = noise if noise is not None else SharedNoiseTable()
-    noise.attach(engine)
+    if not maze:                                                    # (open_engine attached the maze's)
+        noise = noise if noise is not None else SharedNoiseTable()
+        noise.attach(engine)
     rs = np.random.RandomState(seed)
     all_tstart = tstart = time.time()
     try:                                                            # es.py:155-162: resume

@@ -16,6 +16,8 @@ evaluates as it stands, selected children become parents device to device (dne_m
 few individuals that survive a generation.  SimpleClassifier on an Atari game and the Atari models on the maze are refused.
 With exp['novelty_search'] = {'k': ..., 'archive_prob': ...} the maze loop is GA-NS (maze_ns_main): the same GA selecting on novelty against the
 archive and the current population, scored on the device (k_maze_novelty_pool).  The key on an Atari game is refused.
+The three loops share what is the same in them as plain functions (_validate_and_test, _record_rows, _end_generation; the two maze loops also
+_open_maze_run, _resume_maze, _draw_generation, _member, _promote); the engine, walls and noise table come from maze_run.open_engine.
 """
 import math
 import numbers
@@ -25,7 +27,9 @@ import time
 
 import numpy as np
 
-from . import _lib
+from . import _lib, policies, tabular_logger as tlogger
+from .es import SharedNoiseTable, parse_cutoff
+from .maze_run import MAZE_MODEL, open_engine, step_limit
 from .policies import flat_layout
 
 
@@ -126,7 +130,6 @@ class TrainingState(object):
     COUNTERS = ('num_frames', 'timesteps_so_far', 'time_elapsed', 'validation_timesteps_so_far', 'it')
 
     def __init__(self, exp):
-        from .es import parse_cutoff
         for name in self.COUNTERS:
             setattr(self, name, 0)
         self.population, self.elite = [], None
@@ -166,7 +169,6 @@ def model_scale_by(nact, kind=None):
 
 
 MODEL_KINDS = {'Model': _lib.KIND_GA, 'LargeModel': _lib.KIND_GA_LARGE}   # neuroevolution/models/dqn.py:24-47 (exp['model'], ga.py:110)
-MAZE_MODEL = 'SimpleClassifier'          # the one model of exp['game'] == 'maze' (neuroevolution/models/simple.py:29-35)
 ALGO = 'ga'                              # what maze_main's snapshot.pkl says wrote it
 ALGO_NS = 'ga_ns'                        # ... and maze_ns_main's
 NS_KEY = 'novelty_search'                # exp[NS_KEY] = {'k': neighbours, 'archive_prob': chance of a member to enter the archive}
@@ -211,10 +213,59 @@ def parents_of(state, T):
     return [state.elite.seeds] + top[:T - 1]
 
 
+# ---------------------------------------------------------------------------------------------- what the three loops below share
+def _validate_and_test(state, exp, validation_population, evaluate, population_timesteps):
+    """ga.py:184-201, 223-226 behind a generation's evaluation: the validation episodes of validation_population, the best of them as the
+    new state.elite, its test episodes (max_frames=None), the timestep counters and curr_solution_*.  evaluate(individuals, tslimit) ->
+    (returns, lengths), one episode per Offspring of the list.  Returns what the tabular rows need."""
+    k = exp['num_validation_episodes']
+    vr, vl = evaluate([o for o in validation_population for _ in range(k)], state.tslimit)        # ga.py:188-192
+    population_validation = [float(np.mean(vr[i * k:(i + 1) * k])) for i in range(len(validation_population))]
+    validation_timesteps = sum(int(np.sum(vl[i * k:(i + 1) * k])) for i in range(len(validation_population)))
+    state.elite = validation_population[int(np.argmax(population_validation))]                    # ga.py:198-199
+    er, el = evaluate([state.elite] * exp['num_test_episodes'], None)                             # ga.py:200-201
+    timesteps_this_iter = population_timesteps + validation_timesteps
+    state.timesteps_so_far += timesteps_this_iter
+    state.validation_timesteps_so_far += validation_timesteps
+    if np.mean(population_validation) > state.curr_solution_val:                                  # ga.py:223-226
+        state.curr_solution = state.elite.seeds
+        state.curr_solution_val = float(np.mean(population_validation))
+        state.curr_solution_test = float(np.mean(er))
+    return dict(validation_population=validation_population, population_validation=population_validation, validation_timesteps=validation_timesteps,
+                timesteps_this_iter=timesteps_this_iter, population_timesteps=population_timesteps, er=er, el=el)
+
+
+def _record_rows(state, power, rewards, T, v, dt, all_tstart):
+    """the tabular rows of a GA generation (ga.py:206-241), recorded and not yet dumped; v is what _validate_and_test returned"""
+    for key, val in (('Iteration', state.it), ('MutationPower', power), ('PopulationEpRewMax', np.max(rewards)),
+                     ('PopulationEpRewMean', np.mean(rewards)), ('PopulationEpCount', len(rewards)),
+                     ('PopulationTimesteps', v['population_timesteps']), ('NumSelectedIndividuals', T),
+                     ('TruncatedPopulationRewMean', np.mean([a.fitness for a in v['validation_population']])),
+                     ('TruncatedPopulationValidationRewMean', np.mean(v['population_validation'])),
+                     ('TruncatedPopulationEliteValidationRewMean', np.max(v['population_validation'])),
+                     ('TruncatedPopulationEliteTestRewMean', np.mean(v['er'])), ('TruncatedPopulationEliteTestEpCount', len(v['er'])),
+                     ('TruncatedPopulationEliteTestEpLenSum', int(np.sum(v['el']))), ('ValidationTimestepsThisIter', v['validation_timesteps']),
+                     ('TimestepsThisIter', v['timesteps_this_iter']), ('TimestepsPerSecondThisIter', v['timesteps_this_iter'] / dt),
+                     ('TimestepsSoFar', state.timesteps_so_far), ('TimeElapsedThisIter', dt), ('TimeElapsed', state.time_elapsed),
+                     ('TimeElapsedTotal', time.time() - all_tstart)):
+        tlogger.record_tabular(key, val)
+
+
+def _end_generation(state, log_dir, lens, rs=None):
+    """ga.py:244-254: the adaptive cutoff's step on this generation's episode lengths, then snapshot.pkl -- with the position of rs, where
+    the loop's stream is seeded and a resume continues it"""
+    if state.adaptive_tslimit:
+        if np.mean(np.asarray(lens) >= state.tslimit) > state.incr_tslimit_threshold:
+            state.tslimit = min(state.tslimit * state.tslimit_incr_ratio, state.tslimit_max)
+    if rs is not None:
+        state.stream = rs.get_state()
+    os.makedirs(log_dir, exist_ok=True)
+    with open(os.path.join(log_dir, 'snapshot.pkl'), 'wb') as file:
+        pickle.dump(state, file)
+
+
 def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
     """gpu_implementation/ga.py:114-275.  Returns (curr_solution_test, {'val': curr_solution_val}, state)."""
-    from . import tabular_logger as tlogger
-    from .es import SharedNoiseTable
     maze, asked = exp.get('game') == 'maze', exp.get('model', 'Model')
     if maze != (asked == MAZE_MODEL):                               # ga.py:110-114 takes any pair; the engine has these
         raise NotImplementedError("model {!r} on game {!r}: {!r} runs on game 'maze' only, and 'maze' runs nothing else".format(
@@ -243,6 +294,9 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
     if 'load_population' in exp:
         state.copy_population(exp['load_population'])
 
+    def evaluate(individuals, tslimit):
+        return _evaluate(engine, [o.seeds for o in individuals], tslimit, rs)
+
     cached_parents = parents_of(state, exp['selection_threshold'])
     iters = 0
     while max_iters is None or iters < max_iters:
@@ -260,7 +314,6 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
         state.num_frames += int(lens.sum()) * 4
         state.it += 1
         rewards = np.array([a.fitness for a in results])
-        population_timesteps = sum(a.training_steps for a in results)
         # ga.py:176: sorted(..., reverse=True) is stable, so equal fitness keeps arrival order -- the engine's selection
         # order (-fitness, arrival index)
         order = engine.ga_select(rewards.astype(np.float32), len(results))
@@ -268,42 +321,12 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
         validation_population = state.population[:exp['validation_threshold']]                # ga.py:184-186
         if state.elite is not None:
             validation_population = [state.elite] + validation_population[:-1]
-        vt = [o.seeds for o in validation_population for _ in range(exp['num_validation_episodes'])]
-        vr, vl = _evaluate(engine, vt, state.tslimit, rs)                                      # ga.py:188-192
-        k = exp['num_validation_episodes']
-        population_validation = [float(np.mean(vr[i * k:(i + 1) * k])) for i in range(len(validation_population))]
-        population_validation_len = [int(np.sum(vl[i * k:(i + 1) * k])) for i in range(len(validation_population))]
-        state.elite = validation_population[int(np.argmax(population_validation))]            # ga.py:198-199
-        er, el = _evaluate(engine, [state.elite.seeds] * exp['num_test_episodes'], None, rs)   # ga.py:200-201 (max_frames=None)
-        validation_timesteps = sum(population_validation_len)
-        timesteps_this_iter = population_timesteps + validation_timesteps
-        state.timesteps_so_far += timesteps_this_iter
-        state.validation_timesteps_so_far += validation_timesteps
-        if np.mean(population_validation) > state.curr_solution_val:                           # ga.py:223-226
-            state.curr_solution = state.elite.seeds
-            state.curr_solution_val = float(np.mean(population_validation))
-            state.curr_solution_test = float(np.mean(er))
+        v = _validate_and_test(state, exp, validation_population, evaluate, sum(a.training_steps for a in results))
         dt = time.time() - tstart_iteration
         state.time_elapsed += dt
-        for key, val in (('Iteration', state.it), ('MutationPower', power), ('PopulationEpRewMax', np.max(rewards)),
-                         ('PopulationEpRewMean', np.mean(rewards)), ('PopulationEpCount', len(rewards)),
-                         ('PopulationTimesteps', population_timesteps), ('NumSelectedIndividuals', exp['selection_threshold']),
-                         ('TruncatedPopulationRewMean', np.mean([a.fitness for a in validation_population])),
-                         ('TruncatedPopulationValidationRewMean', np.mean(population_validation)),
-                         ('TruncatedPopulationEliteValidationRewMean', np.max(population_validation)),
-                         ('TruncatedPopulationEliteTestRewMean', np.mean(er)), ('TruncatedPopulationEliteTestEpCount', len(er)),
-                         ('TruncatedPopulationEliteTestEpLenSum', int(np.sum(el))), ('ValidationTimestepsThisIter', validation_timesteps),
-                         ('TimestepsThisIter', timesteps_this_iter), ('TimestepsPerSecondThisIter', timesteps_this_iter / dt),
-                         ('TimestepsSoFar', state.timesteps_so_far), ('TimeElapsedThisIter', dt), ('TimeElapsed', state.time_elapsed),
-                         ('TimeElapsedTotal', time.time() - all_tstart)):
-            tlogger.record_tabular(key, val)
+        _record_rows(state, power, rewards, exp['selection_threshold'], v, dt, all_tstart)
         tlogger.dump_tabular()
-        if state.adaptive_tslimit:                                                              # ga.py:244-247
-            if np.mean([a.training_steps >= state.tslimit for a in results]) > state.incr_tslimit_threshold:
-                state.tslimit = min(state.tslimit * state.tslimit_incr_ratio, state.tslimit_max)
-        os.makedirs(log_dir, exist_ok=True)                                                     # ga.py:249-254
-        with open(os.path.join(log_dir, 'snapshot.pkl'), 'wb+') as file:
-            pickle.dump(state, file)
+        _end_generation(state, log_dir, lens)
         if state.timesteps_so_far >= exp['timesteps']:
             break
         cached_parents = parents_of(state, exp['selection_threshold'])                          # ga.py:261-274
@@ -316,13 +339,61 @@ KEPT = -1          # a descriptor's noise index that means "the parent itself" (
 
 def _maze_evaluate(engine, members, tslimit):
     """(returns, lengths) of one episode per (parent, idx, power) member, in calls of at most max_members"""
-    limit = _lib.MAZE_STEPS if tslimit is None else min(int(tslimit), _lib.MAZE_STEPS)
+    limit = step_limit(tslimit)
     out_r, out_l = [], []
     for s in range(0, len(members), engine.max_members):
         parent, idx, power = zip(*members[s:s + engine.max_members])
         ret, _, ln = engine.maze_ga_eval(np.array(parent, np.int32), np.array(idx, np.int64), np.array(power, np.float32), limit)
         out_r.append(ret); out_l.append(ln)
     return np.concatenate(out_r), np.concatenate(out_l)
+
+
+def _open_maze_run(log_dir, engine, noise, seed, exp):
+    """what maze_main and maze_ns_main do before they look for a snapshot: the log, the engine with walls, table and init scale, the stream"""
+    tlogger.start(log_dir)
+    engine, noise = open_engine(exp, engine, noise, exp['population_size'])
+    engine.maze_ga_set_init_scale(policies.simple_scale_by())
+    return engine, noise, np.random.RandomState(seed)
+
+
+def _resume_maze(log_dir, algo, rs):
+    """ga.py:135-143 for a maze GA run of `algo`: the state in log_dir's snapshot.pkl with the position of its stream restored into rs, or
+    None if there is no such file.  A snapshot of another driver, game or model is refused, naming both."""
+    try:
+        with open(os.path.join(log_dir, 'snapshot.pkl'), 'rb') as file:
+            state = pickle.load(file)
+    except FileNotFoundError:
+        return None
+    tlogger.log("Loaded iteration {} from {}".format(state.it, log_dir))
+    was_algo = getattr(state, 'algo', ALGO if isinstance(state, TrainingState) else 'es_gpu')
+    if was_algo != algo:
+        raise ValueError("snapshot.pkl in {} was written by {!r}; this run is {!r}".format(log_dir, was_algo, algo))
+    was = (getattr(state, 'game', None) or 'an Atari game', getattr(state, 'model', 'Model'))
+    if was != ('maze', MAZE_MODEL):
+        raise ValueError("snapshot.pkl in {} holds game {!r} under model {!r}; this run is game 'maze' under model {!r}".format(
+            log_dir, was[0], was[1], MAZE_MODEL))
+    if getattr(state, 'stream', None) is not None:
+        rs.set_state(state.stream)
+    return state
+
+
+def _draw_generation(rs, n, n_parents, indices):
+    """a generation's two whole-array draws: the parent of every member (-1: a root, while there are no parents), then its noise index"""
+    of = rs.randint(n_parents, size=n).astype(np.int32) if n_parents else np.full(n, -1, np.int32)
+    return of, rs.randint(0, indices, size=n).astype(np.int64)
+
+
+def _member(i, of, idx, power, parents):
+    """the descriptor of a generation's member i over the bank as it is, and its genome"""
+    i = int(i)
+    if of[i] < 0:
+        return (-1, int(idx[i]), 0.0), (int(idx[i]), )
+    return (int(of[i]), int(idx[i]), float(power)), tuple(parents[of[i]]) + ((int(idx[i]), power), )
+
+
+def _promote(engine, descriptors):
+    """the next bank from descriptors over this one, device to device"""
+    engine.maze_ga_promote(*(np.array(c, t) for c, t in zip(zip(*descriptors), (np.int32, np.int64, np.float32))))
 
 
 def maze_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
@@ -340,39 +411,15 @@ def maze_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
     snapshot.pkl with game, model and algo = 'ga', so a resumed run continues bit for bit; a resume under another game or model, or from
     a snapshot of es_gpu.main / nses_gpu.main, raises and names both.  A previous elite is evaluated again as (its bank index, idx 0,
     power 0): the child formula, bank + fl(0 * noise).  The elite's test episodes are num_test_episodes identical deterministic episodes
-    at the 400-step default, as the reference runs them.  num_frames counts steps (the maze has no frame skip)."""
+    at the 400-step default, as the reference runs them.  num_frames counts steps (the maze has no frame skip).
+    maze_ns_main below is the same scaffold (the _helpers above) around another selection."""
     if NS_KEY in exp:
         return maze_ns_main(log_dir, engine=engine, noise=noise, seed=seed, max_iters=max_iters, **exp)
-    from . import policies, tabular_logger as tlogger
-    from .es import SharedNoiseTable
-    from .es_gpu import maze_file
-    tlogger.start(log_dir)
     n, T, V = exp['population_size'], exp['selection_threshold'], exp['validation_threshold']
-    if engine is None:
-        engine = _lib.Engine(_lib.KIND_MAZE, 2, max_members=n)
-    elif engine.kind != _lib.KIND_MAZE:
-        raise ValueError("game 'maze' asked for, the engine passed in is of kind {} (KIND_MAZE is {})".format(engine.kind, _lib.KIND_MAZE))
-    engine.maze_set_walls(*_lib.load_maze(maze_file(exp)))
-    noise = noise if noise is not None else SharedNoiseTable()
-    noise.attach(engine)
-    engine.maze_ga_set_init_scale(policies.simple_scale_by())
-    P = engine.P
-    rs = np.random.RandomState(seed)
+    engine, noise, rs = _open_maze_run(log_dir, engine, noise, seed, exp)
     all_tstart = time.time()
-    try:                                                           # ga.py:135-143: resume
-        with open(os.path.join(log_dir, 'snapshot.pkl'), 'rb') as file:
-            state = pickle.load(file)
-        tlogger.log("Loaded iteration {} from {}".format(state.it, log_dir))
-        was_algo = getattr(state, 'algo', ALGO if isinstance(state, TrainingState) else 'es_gpu')
-        if was_algo != ALGO:
-            raise ValueError("snapshot.pkl in {} was written by {!r}; this run is {!r}".format(log_dir, was_algo, ALGO))
-        was = (getattr(state, 'game', None) or 'an Atari game', getattr(state, 'model', 'Model'))
-        if was != ('maze', MAZE_MODEL):
-            raise ValueError("snapshot.pkl in {} holds game {!r} under model {!r}; this run is game 'maze' under model {!r}".format(
-                log_dir, was[0], was[1], MAZE_MODEL))
-        if getattr(state, 'stream', None) is not None:
-            rs.set_state(state.stream)
-    except FileNotFoundError:
+    state = _resume_maze(log_dir, ALGO, rs)
+    if state is None:
         state = TrainingState(exp)
     state.game, state.model, state.algo = 'maze', MAZE_MODEL, ALGO
     if 'load_population' in exp:
@@ -380,6 +427,11 @@ def maze_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
     parents = parents_of(state, T)                                  # the genomes of the bank's parents, kept beside it
     if parents:
         engine.maze_ga_build(parents)
+    descriptor = {}                                                 # id(Offspring) -> its descriptor over the bank as it is now
+
+    def evaluate(individuals, tslimit):
+        return _maze_evaluate(engine, [descriptor[id(o)] for o in individuals], tslimit)
+
     iters = 0
     while max_iters is None or iters < max_iters:
         iters += 1
@@ -388,29 +440,16 @@ def maze_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
             break
         assert (len(parents) == 0 and state.it == 0) or len(parents) == T
         power = state.sample(state.mutation_power)
-        if parents:
-            of = rs.randint(len(parents), size=n).astype(np.int32)
-        else:
-            of = np.full(n, -1, np.int32)
-        idx = rs.randint(0, len(noise.noise) - P + 1, size=n).astype(np.int64)
-        limit = _lib.MAZE_STEPS if state.tslimit is None else min(int(state.tslimit), _lib.MAZE_STEPS)
-        rets, _, lens = engine.maze_ga_eval(of, idx, np.full(n, power, np.float32), limit)
+        of, idx = _draw_generation(rs, n, len(parents), len(noise.noise) - engine.P + 1)
+        rets, _, lens = engine.maze_ga_eval(of, idx, np.full(n, power, np.float32), step_limit(state.tslimit))
         state.num_frames += int(lens.sum())
         state.it += 1
         rewards = np.asarray(rets, np.float64)
-        population_timesteps = int(lens.sum())
         order = engine.ga_select(np.asarray(rets, np.float32), n)   # (-fitness, arrival index): a stable sort, ties at -500 keep arrival order
-
-        def member(i):                                              # the descriptor of this generation's member i, and its genome
-            i = int(i)
-            if of[i] < 0:
-                return (-1, int(idx[i]), 0.0), (int(idx[i]), )
-            return (int(of[i]), int(idx[i]), float(power)), tuple(parents[of[i]]) + ((int(idx[i]), power), )
-
-        descriptor = {}                                             # id(Offspring) -> its descriptor over the bank as it is now
+        descriptor.clear()
         state.population = []
         for i in order[:max(T, V)]:
-            d, genome = member(i)
+            d, genome = _member(i, of, idx, power, parents)
             o = Offspring(genome, [float(rets[i])], [int(lens[i])])
             descriptor[id(o)] = d
             state.population.append(o)
@@ -424,39 +463,12 @@ def maze_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
             else:
                 raise NotImplementedError("the elite {!r} is not among the {} parents of the bank".format(state.elite.seeds, len(parents)))
             validation_population = [state.elite] + validation_population[:-1]
-        k = exp['num_validation_episodes']
-        vr, vl = _maze_evaluate(engine, [descriptor[id(o)] for o in validation_population for _ in range(k)], state.tslimit)   # ga.py:188-192
-        population_validation = [float(np.mean(vr[i * k:(i + 1) * k])) for i in range(len(validation_population))]
-        population_validation_len = [int(np.sum(vl[i * k:(i + 1) * k])) for i in range(len(validation_population))]
         old_elite = state.elite
-        state.elite = validation_population[int(np.argmax(population_validation))]            # ga.py:198-199
-        er, el = _maze_evaluate(engine, [descriptor[id(state.elite)]] * exp['num_test_episodes'], None)   # ga.py:200-201 (max_frames=None)
-        validation_timesteps = sum(population_validation_len)
-        timesteps_this_iter = population_timesteps + validation_timesteps
-        state.timesteps_so_far += timesteps_this_iter
-        state.validation_timesteps_so_far += validation_timesteps
-        if np.mean(population_validation) > state.curr_solution_val:                           # ga.py:223-226
-            state.curr_solution = state.elite.seeds
-            state.curr_solution_val = float(np.mean(population_validation))
-            state.curr_solution_test = float(np.mean(er))
+        v = _validate_and_test(state, exp, validation_population, evaluate, int(lens.sum()))
         dt = time.time() - tstart_iteration
         state.time_elapsed += dt
-        for key, val in (('Iteration', state.it), ('MutationPower', power), ('PopulationEpRewMax', np.max(rewards)),
-                         ('PopulationEpRewMean', np.mean(rewards)), ('PopulationEpCount', len(rewards)),
-                         ('PopulationTimesteps', population_timesteps), ('NumSelectedIndividuals', T),
-                         ('TruncatedPopulationRewMean', np.mean([a.fitness for a in validation_population])),
-                         ('TruncatedPopulationValidationRewMean', np.mean(population_validation)),
-                         ('TruncatedPopulationEliteValidationRewMean', np.max(population_validation)),
-                         ('TruncatedPopulationEliteTestRewMean', np.mean(er)), ('TruncatedPopulationEliteTestEpCount', len(er)),
-                         ('TruncatedPopulationEliteTestEpLenSum', int(np.sum(el))), ('ValidationTimestepsThisIter', validation_timesteps),
-                         ('TimestepsThisIter', timesteps_this_iter), ('TimestepsPerSecondThisIter', timesteps_this_iter / dt),
-                         ('TimestepsSoFar', state.timesteps_so_far), ('TimeElapsedThisIter', dt), ('TimeElapsed', state.time_elapsed),
-                         ('TimeElapsedTotal', time.time() - all_tstart)):
-            tlogger.record_tabular(key, val)
+        _record_rows(state, power, rewards, T, v, dt, all_tstart)
         tlogger.dump_tabular()
-        if state.adaptive_tslimit:                                                              # ga.py:244-247
-            if np.mean(lens >= state.tslimit) > state.incr_tslimit_threshold:
-                state.tslimit = min(state.tslimit * state.tslimit_incr_ratio, state.tslimit_max)
         # ga.py:261-274 on the device: the next parents from this generation's descriptors, the retained elite as it stands
         new_parents = parents_of(state, T)
         if new_parents and not parents:                             # the start: generation 0's roots become the first bank
@@ -465,12 +477,9 @@ def maze_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
             by_genome = {o.seeds: descriptor[id(o)] for o in state.population}
             if old_elite is not None and state.elite is old_elite and state.elite.seeds in parents:
                 by_genome[state.elite.seeds] = (parents.index(state.elite.seeds), KEPT, 0.0)
-            engine.maze_ga_promote(*(np.array(c, t) for c, t in zip(zip(*(by_genome[g] for g in new_parents)), (np.int32, np.int64, np.float32))))
+            _promote(engine, [by_genome[g] for g in new_parents])
         parents = new_parents
-        state.stream = rs.get_state()
-        os.makedirs(log_dir, exist_ok=True)                                                     # ga.py:249-254
-        with open(os.path.join(log_dir, 'snapshot.pkl'), 'wb') as file:
-            pickle.dump(state, file)
+        _end_generation(state, log_dir, lens, rs)
         if state.timesteps_so_far >= exp['timesteps']:
             break
     return float(state.curr_solution_test), {'val': float(state.curr_solution_val)}, state
@@ -484,7 +493,7 @@ def maze_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp
     The reference has no GA-NS code (gpu_implementation/README.md leaves it for later), so every decision here is ours:
       draws        maze_main's two whole-array draws first, then rs.random_sample(n) < archive_prob: this generation's archive mask.
       scoring      one maze_ga_eval, then maze_novelty_pool(k) where k_maze_rollout left the final positions: each member against the
-                   archive and the other members of its generation (csrc/maze_novelty.h).  The n doubles are all that comes back.
+                   archive and the other members of its generation (csrc/maze_novelty.h, the pool form).  The n doubles are all that comes back.
       non-finite   a novelty that is not finite counts as 0.0 (nses_gpu's rule): the lowest there is, so a NaN policy is never selected
                    ahead of a finite one.
       order        descending novelty, then arrival index, by a stable host sort of the doubles (ga_select is float32 and would make
@@ -501,55 +510,37 @@ def maze_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp
                    bit.  A resume from a 'ga', es_gpu or nses_gpu snapshot, or under another k or archive_prob, raises and names both.
       T == 0       allowed: random search, with an archive that still fills.
     Tabular keys: maze_main's, plus NoveltyMean, NoveltyMax (after the non-finite rule), ArchiveSize, BestDistanceToGoal = -max reward."""
-    from . import policies, tabular_logger as tlogger
-    from .es import SharedNoiseTable
-    from .es_gpu import maze_file
     ns = exp[NS_KEY]
     k, prob = int(ns['k']), float(ns['archive_prob'])
     if not 1 <= k <= _lib.MAZE_NOVELTY_KMAX:
         raise ValueError("novelty_search k = {}: expected 1 .. MAZE_NOVELTY_KMAX = {}".format(k, _lib.MAZE_NOVELTY_KMAX))
     if not 0.0 <= prob <= 1.0:
         raise ValueError("novelty_search archive_prob = {!r}: expected a probability".format(ns['archive_prob']))
-    tlogger.start(log_dir)
     n, T, V = exp['population_size'], exp['selection_threshold'], exp['validation_threshold']
-    if engine is None:
-        engine = _lib.Engine(_lib.KIND_MAZE, 2, max_members=n)
-    elif engine.kind != _lib.KIND_MAZE:
-        raise ValueError("game 'maze' asked for, the engine passed in is of kind {} (KIND_MAZE is {})".format(engine.kind, _lib.KIND_MAZE))
-    engine.maze_set_walls(*_lib.load_maze(maze_file(exp)))
-    noise = noise if noise is not None else SharedNoiseTable()
-    noise.attach(engine)
-    engine.maze_ga_set_init_scale(policies.simple_scale_by())
-    P = engine.P
-    rs = np.random.RandomState(seed)
+    engine, noise, rs = _open_maze_run(log_dir, engine, noise, seed, exp)
     all_tstart = time.time()
     engine.maze_archive_clear()
-    try:
-        with open(os.path.join(log_dir, 'snapshot.pkl'), 'rb') as file:
-            state = pickle.load(file)
-        tlogger.log("Loaded iteration {} from {}".format(state.it, log_dir))
-        was_algo = getattr(state, 'algo', ALGO if isinstance(state, TrainingState) else 'es_gpu')
-        if was_algo != ALGO_NS:
-            raise ValueError("snapshot.pkl in {} was written by {!r}; this run is {!r}".format(log_dir, was_algo, ALGO_NS))
-        was = (getattr(state, 'game', None) or 'an Atari game', getattr(state, 'model', 'Model'))
-        if was != ('maze', MAZE_MODEL):
-            raise ValueError("snapshot.pkl in {} holds game {!r} under model {!r}; this run is game 'maze' under model {!r}".format(
-                log_dir, was[0], was[1], MAZE_MODEL))
+    state = _resume_maze(log_dir, ALGO_NS, rs)
+    if state is None:
+        state = TrainingState(exp)
+        state.archive, state.stream = np.zeros((0, 2), np.float32), None
+    else:
         if (state.k, state.archive_prob) != (k, prob):
             raise ValueError("snapshot.pkl in {} holds k {}, archive_prob {!r}; this run is k {}, archive_prob {!r}".format(
                 log_dir, state.k, state.archive_prob, k, prob))
         if len(state.archive):
             engine.maze_archive_append(state.archive)
-        rs.set_state(state.stream)
-    except FileNotFoundError:
-        state = TrainingState(exp)
-        state.archive, state.stream = np.zeros((0, 2), np.float32), None
     state.game, state.model, state.algo, state.k, state.archive_prob = 'maze', MAZE_MODEL, ALGO_NS, k, prob
     if 'load_population' in exp:
         state.copy_population(exp['load_population'])
     parents = [o.seeds for o in state.population[:T]]               # the genomes of the bank's parents: the top T by novelty, no elite carried
     if parents:
         engine.maze_ga_build(parents)
+    descriptor = {}                                                 # id(Offspring) -> its descriptor over the bank as it is now
+
+    def evaluate(individuals, tslimit):
+        return _maze_evaluate(engine, [descriptor[id(o)] for o in individuals], tslimit)
+
     iters = 0
     while max_iters is None or iters < max_iters:
         iters += 1
@@ -558,14 +549,9 @@ def maze_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp
             break
         assert (len(parents) == 0 and (state.it == 0 or T == 0)) or len(parents) == T
         power = state.sample(state.mutation_power)
-        if parents:
-            of = rs.randint(len(parents), size=n).astype(np.int32)
-        else:
-            of = np.full(n, -1, np.int32)
-        idx = rs.randint(0, len(noise.noise) - P + 1, size=n).astype(np.int64)
+        of, idx = _draw_generation(rs, n, len(parents), len(noise.noise) - engine.P + 1)
         archived = np.flatnonzero(rs.random_sample(n) < prob).astype(np.int32)
-        limit = _lib.MAZE_STEPS if state.tslimit is None else min(int(state.tslimit), _lib.MAZE_STEPS)
-        rets, _, lens = engine.maze_ga_eval(of, idx, np.full(n, power, np.float32), limit)
+        rets, _, lens = engine.maze_ga_eval(of, idx, np.full(n, power, np.float32), step_limit(state.tslimit))
         raw = np.asarray(engine.maze_novelty_pool(k), np.float64)   # against the archive as it was before this generation, and the generation
         novelty = np.where(np.isfinite(raw), raw, 0.0)
         if archived.size:
@@ -573,73 +559,37 @@ def maze_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp
         state.num_frames += int(lens.sum())
         state.it += 1
         rewards = np.asarray(rets, np.float64)
-        population_timesteps = int(lens.sum())
         by_novelty = np.argsort(-novelty, kind='stable')            # (-novelty, arrival index)
         by_reward = engine.ga_select(np.asarray(rets, np.float32), n)
-
-        def member(i):                                              # the descriptor of this generation's member i, and its genome
-            i = int(i)
-            if of[i] < 0:
-                return (-1, int(idx[i]), 0.0), (int(idx[i]), )
-            return (int(of[i]), int(idx[i]), float(power)), tuple(parents[of[i]]) + ((int(idx[i]), power), )
-
-        offspring, descriptor = {}, {}                              # member index -> its Offspring; id(Offspring) -> descriptor over the bank as it is
+        offspring = {}                                              # member index -> its Offspring
+        descriptor.clear()
         for i in list(by_novelty[:T]) + list(by_reward[:V]):
             i = int(i)
             if i not in offspring:
-                d, genome = member(i)
+                d, genome = _member(i, of, idx, power, parents)
                 offspring[i] = Offspring(genome, [float(rets[i])], [int(lens[i])])
                 offspring[i].novelty = float(novelty[i])
                 descriptor[id(offspring[i])] = d
         selected = [offspring[int(i)] for i in by_novelty[:T]]
         validation_population = [offspring[int(i)] for i in by_reward[:V]]
         state.population = selected + [o for o in validation_population if not any(o is s for s in selected)]
-        ve = exp['num_validation_episodes']
-        vr, vl = _maze_evaluate(engine, [descriptor[id(o)] for o in validation_population for _ in range(ve)], state.tslimit)
-        population_validation = [float(np.mean(vr[i * ve:(i + 1) * ve])) for i in range(len(validation_population))]
-        population_validation_len = [int(np.sum(vl[i * ve:(i + 1) * ve])) for i in range(len(validation_population))]
-        state.elite = validation_population[int(np.argmax(population_validation))]
-        er, el = _maze_evaluate(engine, [descriptor[id(state.elite)]] * exp['num_test_episodes'], None)
-        validation_timesteps = sum(population_validation_len)
-        timesteps_this_iter = population_timesteps + validation_timesteps
-        state.timesteps_so_far += timesteps_this_iter
-        state.validation_timesteps_so_far += validation_timesteps
-        if np.mean(population_validation) > state.curr_solution_val:
-            state.curr_solution = state.elite.seeds
-            state.curr_solution_val = float(np.mean(population_validation))
-            state.curr_solution_test = float(np.mean(er))
+        v = _validate_and_test(state, exp, validation_population, evaluate, int(lens.sum()))
         # the next parents on the device: the top T by novelty, every one a root (generation 0) or a child of the bank as it is
         new_parents = [o.seeds for o in selected]
         if new_parents and not parents:
             engine.maze_ga_build(new_parents)
         elif new_parents:
-            engine.maze_ga_promote(*(np.array(c, t) for c, t in zip(zip(*(descriptor[id(o)] for o in selected)), (np.int32, np.int64, np.float32))))
+            _promote(engine, [descriptor[id(o)] for o in selected])
         parents = new_parents
         state.archive = engine.maze_archive()
         dt = time.time() - tstart_iteration
         state.time_elapsed += dt
-        for key, val in (('Iteration', state.it), ('MutationPower', power), ('PopulationEpRewMax', np.max(rewards)),
-                         ('PopulationEpRewMean', np.mean(rewards)), ('PopulationEpCount', len(rewards)),
-                         ('PopulationTimesteps', population_timesteps), ('NumSelectedIndividuals', T),
-                         ('TruncatedPopulationRewMean', np.mean([a.fitness for a in validation_population])),
-                         ('TruncatedPopulationValidationRewMean', np.mean(population_validation)),
-                         ('TruncatedPopulationEliteValidationRewMean', np.max(population_validation)),
-                         ('TruncatedPopulationEliteTestRewMean', np.mean(er)), ('TruncatedPopulationEliteTestEpCount', len(er)),
-                         ('TruncatedPopulationEliteTestEpLenSum', int(np.sum(el))), ('ValidationTimestepsThisIter', validation_timesteps),
-                         ('TimestepsThisIter', timesteps_this_iter), ('TimestepsPerSecondThisIter', timesteps_this_iter / dt),
-                         ('TimestepsSoFar', state.timesteps_so_far), ('TimeElapsedThisIter', dt), ('TimeElapsed', state.time_elapsed),
-                         ('TimeElapsedTotal', time.time() - all_tstart), ('NoveltyMean', float(np.mean(novelty))),
-                         ('NoveltyMax', float(np.max(novelty))), ('ArchiveSize', int(state.archive.shape[0])),
-                         ('BestDistanceToGoal', -float(np.max(rewards)))):
+        _record_rows(state, power, rewards, T, v, dt, all_tstart)
+        for key, val in (('NoveltyMean', float(np.mean(novelty))), ('NoveltyMax', float(np.max(novelty))),
+                         ('ArchiveSize', int(state.archive.shape[0])), ('BestDistanceToGoal', -float(np.max(rewards)))):
             tlogger.record_tabular(key, val)
         tlogger.dump_tabular()
-        if state.adaptive_tslimit:
-            if np.mean(lens >= state.tslimit) > state.incr_tslimit_threshold:
-                state.tslimit = min(state.tslimit * state.tslimit_incr_ratio, state.tslimit_max)
-        state.stream = rs.get_state()
-        os.makedirs(log_dir, exist_ok=True)
-        with open(os.path.join(log_dir, 'snapshot.pkl'), 'wb') as file:
-            pickle.dump(state, file)
+        _end_generation(state, log_dir, lens, rs)
         if state.timesteps_so_far >= exp['timesteps']:
             break
     return float(state.curr_solution_test), {'val': float(state.curr_solution_val)}, state

@@ -1,5 +1,5 @@
 """NS-ES and NSR-ES on the hard maze: the meta-population loop of es_distributed/nses.py:58-316 as ONE process on a DNE_KIND_MAZE engine, with
-the conventions of es_gpu.py (seeded streams, `snapshot.pkl` resume, tabular keys, maze_file(exp), Schedule).
+the conventions of es_gpu.py (seeded streams, `snapshot.pkl` resume, tabular keys, Schedule; the engine through maze_run.open_engine).
 
 The maze is the reference's deceptive domain: the behaviour characterisation (BC) of a policy is where its navigator ended, MazeFinalState
 (gym_tensorflow/maze/tf_maze.py:64-66), one float32 point (x, y).  Novelty is nses.py:12-32 on such points -- the mean distance to the k
@@ -39,9 +39,10 @@ import time
 import numpy as np
 
 from . import _lib, nses
-from .es import SharedNoiseTable, pack_records, parse_cutoff
-from .es_gpu import MAZE_MODEL, _episodes_of_theta, maze_file
+from .es import pack_records, parse_cutoff
+from .es_gpu import _episodes_of_theta
 from .ga_gpu import Schedule
+from .maze_run import MAZE_MODEL, check_engine, open_engine, step_limit
 
 ALGO = 'nses'
 ALGO_TYPES = ('ns', 'nsr')
@@ -103,8 +104,7 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
     tlogger.start(log_dir)
     if exp.get('game') != 'maze' or exp.get('model') != MAZE_MODEL:
         raise NotImplementedError("game {!r} with model {!r}: this loop runs game 'maze' with model {!r}".format(exp.get('game'), exp.get('model'), MAZE_MODEL))
-    if engine is not None and engine.kind != _lib.KIND_MAZE:
-        raise ValueError("game 'maze' asked for, the engine passed in is of kind {} (KIND_MAZE is {})".format(engine.kind, _lib.KIND_MAZE))
+    check_engine(engine)
     algo_type = exp['algo_type']
     if algo_type not in ALGO_TYPES:
         raise ValueError("algo_type {!r}: expected one of {}".format(algo_type, ALGO_TYPES))
@@ -119,11 +119,7 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
     if M < 1 or not 1 <= k <= _lib.MAZE_NOVELTY_KMAX:
         raise ValueError("novelty_search: population_size {} and k {} (1 <= k <= {})".format(M, k, _lib.MAZE_NOVELTY_KMAX))
     n_pairs = exp['population_size'] // 2
-    if engine is None:
-        engine = _lib.Engine(_lib.KIND_MAZE, 2, max_members=max(2 * n_pairs, M, 2))
-    engine.maze_set_walls(*_lib.load_maze(maze_file(exp)))
-    noise = noise if noise is not None else SharedNoiseTable()
-    noise.attach(engine)
+    engine, noise = open_engine(exp, engine, noise, max(2 * n_pairs, M, 2))
     rs = np.random.RandomState(seed)
     all_tstart = time.time()
     _, _, _, tslimit_max, _ = parse_cutoff(exp['episode_cutoff_mode'])
@@ -166,7 +162,7 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
         power = state.mutation_power.value(iteration=state.it, timesteps_so_far=state.timesteps_so_far)
         idx = np.array([noise.sample_index(rs, engine.P) for _ in range(n_pairs)], np.int64)
         seeds = rs.randint(0, 2 ** 32, size=2 * n_pairs, dtype=np.uint64).astype(np.uint32)
-        limit = _lib.MAZE_STEPS if state.tslimit is None else min(int(state.tslimit), _lib.MAZE_STEPS)
+        limit = step_limit(state.tslimit)
         rets, _, lens = engine.es_eval(idx, power, limit, seeds)
         novelty = sanitized(engine.maze_novelty(k, n=2 * n_pairs))
         aux = novelty.astype(np.float32)

@@ -120,9 +120,9 @@ def test_contract_against_the_dense_formulation_within_the_derived_bound():
 # ---- 3. the header's host side under sanitizers, in a program of its own ---------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def sanitizer_program(tmp_path_factory):
-    """tests/maze_gans_asan_main.cpp, built once: address, undefined and float-cast-overflow"""
+    """tests/maze_novelty_asan_main.cpp, built once: address, undefined and float-cast-overflow"""
     cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
-    src = os.path.join(M.ROOT, "tests", "maze_gans_asan_main.cpp")
+    src = os.path.join(M.ROOT, "tests", "maze_novelty_asan_main.cpp")
     exe = str(tmp_path_factory.mktemp("maze_gans_asan") / "maze_gans_asan")
     subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined,float-cast-overflow",
                            "-fno-sanitize-recover=all", "-I", os.path.join(M.ROOT, "deep-neuroevolution_amd", "csrc"), src, "-o", exe, "-lm"])
@@ -141,7 +141,7 @@ def test_header_under_sanitizers_in_a_stand_alone_program(sanitizer_program, tmp
     cases.append((S.members()[:1], S.archive(1), 1))                                             # the smallest pool there is
     path = tmp_path / "cases.txt"
     path.write_text("".join(_case_text(*c) for c in cases))
-    out = subprocess.run([sanitizer_program, str(path)], capture_output=True, text=True, timeout=120)
+    out = subprocess.run([sanitizer_program, "pool", str(path)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = out.stdout.strip().split("\n")
     assert lines[-1] == "ok %d" % len(cases) and len(lines) == len(cases) + 1

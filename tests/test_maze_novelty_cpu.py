@@ -114,7 +114,7 @@ def test_header_under_sanitizers_in_a_stand_alone_program(sanitizer_program, tmp
     cases += [(S.members(), S.sized_archive(n), k) for n in (1, 2, 63, 64, 65, S.TILE + 1) for k in (1, 10, 32)]
     path = tmp_path / "cases.txt"
     path.write_text("".join(_case_text(*c) for c in cases))
-    out = subprocess.run([sanitizer_program, str(path)], capture_output=True, text=True, timeout=120)
+    out = subprocess.run([sanitizer_program, "archive", str(path)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = out.stdout.strip().split("\n")
     assert lines[-1] == "ok %d" % len(cases) and len(lines) == len(cases) + 1
