@@ -28,6 +28,7 @@
 #include "reduce.h"
 #include "novelty.h"
 #include "plan.h"
+#include "ref_index.h"
 #include "maze.h"
 #include "maze_novelty.h"
 #include "maze_ga.h"
@@ -583,6 +584,9 @@ static void set_tail_table(EnvArgs &E, const TailTable *tt) {
 template <class F> static inline void with_bool(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
 template <int V> using int_c = std::integral_constant<int, V>;
 
+// the default reference route (k_conv1_ref_shared<16>, k_conv2_ref<16, true>, the matrix-core fc): the one the dedup route may replace
+static bool ref_default_route(const Knobs &k, int F) { return k.conv1_shared && k.conv1_fpw >= 8 && (F == 16 || F == 32 || F == 64 || F == 128); }
+
 // ------------------------------------------------------------------------------- handle
 struct dne_handle {
     dne_config cfg{};
@@ -618,6 +622,15 @@ struct dne_handle {
     double *partial = nullptr;
     uint8_t *ref = nullptr; bool ref_set = false;
     float *ref_f32 = nullptr;        // the reference frames as padded planar floats (k_conv1_ref_shared)
+    // the reference batch as unique convolution operands (ref_index.h), uploaded by dne_set_ref_batch when the engine's knobs take the
+    // default reference route; ref_dedup says whether this batch has few enough distinct rows for that route to pay
+    float *ref_tab1 = nullptr;       // [ref_cap1][256]: the unique conv1 patches as floats, k = (kh, kw, c); rows past U1 are zeros
+    int32_t *ref_idx1 = nullptr;     // [F][448]: patch id per conv1 position (positions past 441: id 0, never counted)
+    int32_t *ref_win = nullptr;      // [ref_cap2][16]: the unique conv2 windows as patch ids, -1 = SAME padding; rows past U2 are all -1
+    int32_t *ref_idx2 = nullptr;     // [F][128]: window id per conv2 position (positions past 120 repeat position 120)
+    int ref_cap1 = 0, ref_cap2 = 0;  // rows the two tables can hold (0: the knobs name another route)
+    int ref_U1 = 0, ref_U2 = 0, ref_U1p = 0, ref_U2p = 0;
+    bool ref_dedup = false;
     int32_t *m_slot = nullptr; int64_t *m_off = nullptr; float *m_scale = nullptr;
     std::vector<int32_t> host_slot; std::vector<int64_t> host_off; std::vector<float> host_scale;   // what dne_set_members uploaded
     std::vector<int32_t> host_caller;   // the caller's index of each of those members (dne_ga_eval* reorders them; otherwise the identity)
@@ -1121,6 +1134,13 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
     if (h->F) CH(h->alloc(&h->ref_f32, (size_t)h->F * RF_FRAME, "ref_f32"));
     CH(hipFuncSetAttribute((const void *)k_conv1_ref_shared<16>, hipFuncAttributeMaxDynamicSharedMemorySize, RF_FRAME * (int)sizeof(float)));
     CH(hipFuncSetAttribute((const void *)k_conv1_ref_shared<8>, hipFuncAttributeMaxDynamicSharedMemorySize, RF_FRAME * (int)sizeof(float)));
+    CH(hipFuncSetAttribute((const void *)k_conv2_ref_uniq, hipFuncAttributeMaxDynamicSharedMemorySize, C2U_LDS));
+    if (ref_default_route(h->k, h->F)) {   // room for every batch the dedup route takes (ref_dedup_pays)
+        h->ref_cap1 = ref_pad(h->F * RI_N1, REF_U1_PAD);
+        h->ref_cap2 = ref_pad(h->F * RI_N2, REF_U2_PAD);
+        CH(h->alloc(&h->ref_tab1, (size_t)h->ref_cap1 * 256, "ref_tab1")); CH(h->alloc(&h->ref_idx1, (size_t)h->F * 448, "ref_idx1"));
+        CH(h->alloc(&h->ref_win, (size_t)h->ref_cap2 * 16, "ref_win")); CH(h->alloc(&h->ref_idx2, (size_t)h->F * 128, "ref_idx2"));
+    }
     CH(h->alloc(&h->m_slot, M, "m_slot")); CH(h->alloc(&h->m_off, M, "m_off")); CH(h->alloc(&h->m_scale, M, "m_scale"));
     CH(hipMemset(h->m_slot, 0, M * sizeof(int32_t))); CH(hipMemset(h->m_off, 0, M * sizeof(int64_t)));
     CH(hipMemset(h->m_scale, 0, M * sizeof(float)));
@@ -1367,8 +1387,59 @@ extern "C" int dne_set_ref_batch(dne_handle *h, const uint8_t *ref, int count) {
     hipLaunchKernelGGL(k_ref_to_float, dim3((count * RF_FRAME + 255) / 256), dim3(256), 0, h->stream, (const uint8_t *)h->ref, count, h->ref_f32);
     HCHECK(h, hipGetLastError());
     HCHECK(h, hipStreamSynchronize(h->stream));
+    h->ref_dedup = false;
+    if (h->ref_cap1) {
+        RefIndex R;
+        build_ref_index(ref, count, &R);
+        const int U1p = ref_pad(R.U1, REF_U1_PAD), U2p = ref_pad(R.U2, REF_U2_PAD);
+        // (ref_dedup_pays: few enough distinct rows, and y1u and y2u of a chunk fit beside each other in its y1r)
+        const bool dedup = ref_dedup_pays(count, R.U1, R.U2) && U1p <= h->ref_cap1 && U2p <= h->ref_cap2;
+        h->trace("reference batch: conv1 U1/N1 = %d/%d (%.1f %%), conv2 U2/N2 = %d/%d (%.1f %%): %s route", R.U1, count * RI_N1,
+                 100.0 * R.U1 / (count * RI_N1), R.U2, count * RI_N2, 100.0 * R.U2 / (count * RI_N2), dedup ? "dedup" : "dense");
+        h->ref_U1 = R.U1; h->ref_U2 = R.U2; h->ref_U1p = U1p; h->ref_U2p = U2p;
+        if (dedup) {
+            float lut[256];
+            for (int i = 0; i < 256; i++) lut[i] = (float)i / 255.0f;   // k_ref_to_float's conversion
+            std::vector<float> tab((size_t)U1p * 256, 0.0f);
+            for (size_t i = 0; i < (size_t)R.U1 * 256; i++) tab[i] = lut[R.patches[i]];
+            std::vector<int32_t> i1((size_t)count * 448, 0), win((size_t)U2p * 16, -1), i2((size_t)count * 128, 0);
+            for (int f = 0; f < count; f++) {
+                memcpy(&i1[(size_t)f * 448], &R.idx1[(size_t)f * RI_N1], RI_N1 * sizeof(int32_t));
+                for (int p = 0; p < 128; p++) i2[(size_t)f * 128 + p] = R.idx2[(size_t)f * RI_N2 + std::min(p, RI_N2 - 1)];
+            }
+            memcpy(win.data(), R.windows.data(), R.windows.size() * sizeof(int32_t));
+            HCHECK(h, hipMemcpy(h->ref_tab1, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+            HCHECK(h, hipMemcpy(h->ref_idx1, i1.data(), i1.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            HCHECK(h, hipMemcpy(h->ref_win, win.data(), win.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            HCHECK(h, hipMemcpy(h->ref_idx2, i2.data(), i2.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            h->ref_dedup = true;
+        }
+    }
     h->ref_set = true;
     return 0;
+}
+
+extern "C" int dne_ref_dedup_active(dne_handle *h, int *U1, int *U2) {
+    if (!h->ref_set) return h->fail("reference batch not set (dne_set_ref_batch)");
+    if (U1) *U1 = h->ref_cap1 ? h->ref_U1 : 0;
+    if (U2) *U2 = h->ref_cap1 ? h->ref_U2 : 0;
+    return h->ref_dedup ? 1 : 0;
+}
+
+// the index dne_set_ref_batch builds, on the CPU: no handle, no GPU (like dne_debug_plan)
+extern "C" int dne_debug_ref_index(const uint8_t *ref, int count, int32_t *idx1, uint8_t *patches, int cap1, int32_t *idx2, int32_t *windows,
+                                   int cap2, int *U1, int *U2) {
+    if (!ref || count < 1) { g_create_error = "dne_debug_ref_index: no frames"; return -1; }
+    RefIndex R;
+    build_ref_index(ref, count, &R);
+    if (U1) *U1 = R.U1;
+    if (U2) *U2 = R.U2;
+    if ((patches && cap1 < R.U1) || (windows && cap2 < R.U2)) { g_create_error = "dne_debug_ref_index: a table does not fit its capacity"; return -1; }
+    if (idx1) memcpy(idx1, R.idx1.data(), R.idx1.size() * sizeof(int32_t));
+    if (patches) memcpy(patches, R.patches.data(), R.patches.size());
+    if (idx2) memcpy(idx2, R.idx2.data(), R.idx2.size() * sizeof(int32_t));
+    if (windows) memcpy(windows, R.windows.data(), R.windows.size() * sizeof(int32_t));
+    return ref_dedup_pays(count, R.U1, R.U2) ? 1 : 0;
 }
 
 extern "C" int dne_materialize(dne_handle *h, const int64_t *idx, int n, float sigma, float *out_host) {
@@ -1546,7 +1617,16 @@ static int ref_pass(dne_handle *h, int n) {
         const int fpw = h->k.conv1_fpw >= 8 ? 8 : h->k.conv1_fpw >= 4 ? 4 : h->k.conv1_fpw >= 2 ? 2 : 1;   // F is a multiple of 8
 #define C1R(FPW) hipLaunchKernelGGL(k_conv1_ref<FPW>, dim3(nc * F / FPW), dim3(256), 0, st, A, F, m0, (const uint8_t *)h->ref, y1, fr1)
 #define C1S(FPW) hipLaunchKernelGGL(k_conv1_ref_shared<FPW>, dim3((nc + 7) / 8 * (F / FPW)), dim3(512), RF_FRAME * sizeof(float), st, A, F, m0, nc, (const float *)h->ref_f32, y1, fr1)
-        if (h->k.conv1_shared && fpw == 8 && F % 16 == 0) C1S(16);
+        const bool dedup = h->ref_dedup && ref_default_route(h->k, F);
+        // dedup route: y1u [nc][U1p][16] and behind it y2u [nc][U2p][32] in this way's y1r (dne_set_ref_batch checked the room)
+        const int U1p = h->ref_U1p, U2p = h->ref_U2p;
+        float *y2u = y1 + (size_t)h->ref_chunk * U1p * 16;
+        if (dedup) {
+            const int spw = 32, nseg = (U1p / C1U_ROWS + spw - 1) / spw;
+            hipLaunchKernelGGL(k_conv1_ref_uniq, dim3((nc + 7) / 8 * nseg), dim3(512), 0, st, A, m0, nc, (const float *)h->ref_tab1, U1p, spw, y1);
+            hipLaunchKernelGGL(k_bn1_gather, dim3(nc * (F / 8)), dim3(448), 0, st, F, 8, (const int32_t *)h->ref_idx1, (const float *)y1, U1p, fr1);
+        }
+        else if (h->k.conv1_shared && fpw == 8 && F % 16 == 0) C1S(16);
         else if (h->k.conv1_shared && fpw == 8) C1S(8);
         else if (fpw == 8) C1R(8); else if (fpw == 4) C1R(4); else if (fpw == 2) C1R(2); else C1R(1);
 #undef C1S
@@ -1555,7 +1635,12 @@ static int ref_pass(dne_handle *h, int n) {
         hipLaunchKernelGGL((k_bn_finalize<16>), dim3((nc * 16 + 255) / 256), dim3(256), 0, st, A, m0, nc, F, (const float *)fr1, 441, 0,
                            h->L.c1b, h->L.bn1b, h->L.bn1g);
         const bool mc_fc = F == 16 || F == 32 || F == 64 || F == 128;   // fc on the matrix cores: y2 rows padded to 128 positions
-        if (mc_fc)   // 16 frames per workgroup (32 / 64 measured the same: 11.46 / 11.42 / 11.50 ms per 5000 members)
+        if (dedup) {
+            const int spw = 16, nseg = (U2p / C2U_ROWS + spw - 1) / spw;
+            hipLaunchKernelGGL(k_conv2_ref_uniq, dim3(nc * nseg), dim3(256), C2U_LDS, st, A, m0, (const int32_t *)h->ref_win, U2p, spw, (const float *)y1, U1p, y2u);
+            hipLaunchKernelGGL(k_y2_expand, dim3(nc * (F / 8)), dim3(256), 0, st, A, m0, F, 8, (const int32_t *)h->ref_idx2, (const float *)y2u, U2p, y2, fr2);
+        }
+        else if (mc_fc)   // 16 frames per workgroup (32 / 64 measured the same: 11.46 / 11.42 / 11.50 ms per 5000 members)
             hipLaunchKernelGGL((k_conv2_ref<16, true>), dim3(nc * (F / 16)), dim3(256), 0, st, A, F, m0, (const float *)y1, y2, fr2);
         else if (F % 8 == 0 && h->k.conv2_ref_fpw == 8)
             hipLaunchKernelGGL((k_conv2_ref<8, false>), dim3(nc * (F / 8)), dim3(256), 0, st, A, F, m0, (const float *)y1, y2, fr2);

@@ -177,6 +177,23 @@ def _maze_args(header, lines):
     return header, lines
 
 
+def debug_ref_index(ref):
+    """dne_debug_ref_index (no GPU needed): the reference batch [F][84][84][4] u8 as unique convolution operands, as dne_set_ref_batch
+    builds it.  Returns (idx1 [F][441], patches [U1][256] u8, idx2 [F][121], windows [U2][16], dedup route taken on the default knobs)."""
+    ref = np.ascontiguousarray(ref, dtype=np.uint8)
+    assert ref.ndim == 4 and ref.shape[1:] == OB_SHAPE
+    F = ref.shape[0]
+    idx1, idx2 = np.empty((F, 441), np.int32), np.empty((F, 121), np.int32)
+    patches, windows = np.empty((F * 441, 256), np.uint8), np.empty((F * 121, 16), np.int32)
+    u1, u2 = C.c_int(0), C.c_int(0)
+    rc = load().dne_debug_ref_index(ref.ctypes.data_as(C.POINTER(C.c_uint8)), int(F), idx1.ctypes.data_as(C.POINTER(C.c_int32)),
+                                    patches.ctypes.data_as(C.POINTER(C.c_uint8)), int(F * 441), idx2.ctypes.data_as(C.POINTER(C.c_int32)),
+                                    windows.ctypes.data_as(C.POINTER(C.c_int32)), int(F * 121), C.byref(u1), C.byref(u2))
+    if rc < 0:
+        raise DneError(load().dne_last_error(None).decode())
+    return idx1, patches[:u1.value].copy(), idx2, windows[:u2.value].copy(), bool(rc)
+
+
 def _ck_host(rc):
     if rc != 0:
         raise DneError(load().dne_last_error(None).decode())
@@ -377,6 +394,14 @@ class Engine:
         ref = _arr(ref, np.uint8)
         assert ref.shape[1:] == OB_SHAPE
         self._ck(self.lib.dne_set_ref_batch(self.h, _ptr(ref, C.c_uint8), int(ref.shape[0])))
+
+    def ref_dedup_active(self):
+        """(the reference pass runs on the batch's unique operands, U1, U2) -- see dne_ref_dedup_active"""
+        u1, u2 = C.c_int(0), C.c_int(0)
+        rc = self.lib.dne_ref_dedup_active(self.h, C.byref(u1), C.byref(u2))
+        if rc < 0:
+            raise DneError(self.lib.dne_last_error(self.h).decode())
+        return bool(rc), u1.value, u2.value
 
     def materialize(self, idx, sigma, copy_out=True):
         idx = _arr(idx, np.int64)

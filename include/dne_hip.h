@@ -189,6 +189,17 @@ int dne_debug_plan(int kind, int n_actions, const dne_plan_facts *facts, int tot
  * members under no burst regime (csrc/plan.h: act_window).  Writes that one row (lo = 0, cnt = n); returns 0, or -1 for DNE_KIND_MAZE
  * and n < 1.  Of the facts only kind and members_materialized matter (dne_set_members clears the latter).  No GPU, no handle. */
 int dne_debug_plan_act(int kind, int n_actions, const dne_plan_facts *facts, int n, dne_window_plan *out);
+/* The reference batch as unique convolution operands (csrc/ref_index.h), as dne_set_ref_batch builds it.  ref: [count][84][84][4] u8.
+ * idx1 [count][441]: id of each conv1 patch (8x8x4 bytes of the zero-padded 88x88 image) among the distinct ones; patches [cap1][256]:
+ * those, k = (kh * 8 + kw) * 4 + c; idx2 [count][121]: id of each conv2 window among the distinct ones; windows [cap2][16]: those, as
+ * sixteen conv1 patch ids in (kh, kw) order, -1 = SAME padding.  Any output may be null; *U1 / *U2 = the numbers of distinct rows.
+ * Returns 1 when the reference pass would take the dedup route on such a batch, 0 for the dense one, -1 when a table does not fit.
+ * No GPU, no handle. */
+int dne_debug_ref_index(const uint8_t *ref, int count, int32_t *idx1, uint8_t *patches, int cap1, int32_t *idx2, int32_t *windows, int cap2,
+                        int *U1, int *U2);
+/* 1: the reference pass of this engine runs on the unique operands of the batch last set, 0: on the dense kernels (the knobs name
+ * another route, or the batch has too many distinct rows); *U1 / *U2 (may be null) as above, 0 when the engine builds no index. */
+int dne_ref_dedup_active(dne_handle *h, int *U1, int *U2);
 /* the value of one knob (by its DNE_* name) after defaults, environment and clamping, as dne_create would see it; -1: no such knob */
 int dne_debug_knob(int kind, int n_actions, const char *name);
 
