@@ -32,6 +32,7 @@
 #include "maze.h"
 #include "maze_novelty.h"
 #include "maze_ga.h"
+#include "cartpole.h"
 
 using namespace dne;
 
@@ -43,10 +44,11 @@ static thread_local std::string g_create_error;
         if (_e != hipSuccess) return (h)->fail("%s:%d %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
     } while (0)
 
-// the Atari-only entry points on a hard-maze engine: an error that names the kind
+// the Atari-only entry points on a hard-maze or cart-pole engine: an error that names the kind
 #define MAZE_REFUSE(h, call)                                                                    \
     do {                                                                                        \
         if ((h)->maze) return (h)->fail("%s is not available on a DNE_KIND_MAZE engine (kind %d): the hard maze has no Atari frames, reference batch, genomes or byte BCs", call, DNE_KIND_MAZE); \
+        if ((h)->cartpole) return (h)->fail("%s is not available on a DNE_KIND_CARTPOLE engine (kind %d): the cart-pole has no Atari frames, reference batch, genomes or byte BCs", call, DNE_KIND_CARTPOLE); \
     } while (0)
 
 // ------------------------------------------------------------------------------- env kernels
@@ -660,6 +662,9 @@ struct dne_handle {
     int32_t *mzg_slot = nullptr; int64_t *mzg_off = nullptr; float *mzg_scale = nullptr;
     int32_t *mzg_chain_offs = nullptr; int64_t *mzg_seeds = nullptr; float *mzg_powers = nullptr; size_t mzg_chain_cap = 0;
     std::vector<int32_t> mzg_host_slot; std::vector<float> mzg_host_scale;   // what dne_maze_ga_eval uploaded
+    bool cartpole = false;           // DNE_KIND_CARTPOLE: whole episodes in k_cartpole_rollout (csrc/cartpole.h); the maze's create path without walls
+    double *cp_state = nullptr; int cp_last_n = 0;   // final (x, x_dot, theta, theta_dot) per member of the last evaluation, and how many members that was
+    bool episodic() const { return maze || cartpole; }   // a whole episode per member in one launch: what dne_es_eval and the record calls accept beside the Atari kinds
     bool large = false;              // DNE_KIND_GA_LARGE: y1 [441][32], y2 / y3 [121][64] (conv3 output), y3t = the 512 fc outputs
     float *y1r[2] = {nullptr, nullptr}, *y2r[2] = {nullptr, nullptr}, *y3pr[2] = {nullptr, nullptr};   // reference pass scratch, two ways
     float *fr1[2] = {nullptr, nullptr}, *fr2[2] = {nullptr, nullptr};   // per-frame batch-norm moments of conv1 / conv2 ([rows][2][C])
@@ -825,10 +830,10 @@ static void make_layout(int kind, int nact, Layout *L) {
     memset(L, 0, sizeof(*L));
     L->kind = kind; L->nact = nact;
     auto take = [&](int n) { int r = o; o += n; return r; };
-    if (kind == DNE_KIND_MAZE) {   // SimpleClassifier (models/simple.py:29-35): csrc/maze.h holds its offsets
+    if (kind == DNE_KIND_MAZE || kind == DNE_KIND_CARTPOLE) {   // SimpleClassifier (models/simple.py:29-35): csrc/maze.h and csrc/cartpole.h hold its offsets
         L->c1w = L->c1b = L->c2w = L->c2b = L->c3w = L->c3b = L->fcw = L->fcb = L->ow = L->ob = -1;
         L->bn1b = L->bn1g = L->bn2b = L->bn2g = L->bn3b = L->bn3g = -1;
-        o = maze::NPARAMS;
+        o = kind == DNE_KIND_MAZE ? maze::NPARAMS : cartpole::NPARAMS;
     } else if (kind == DNE_KIND_ES) {   // creation order of trainable variables, policies.py:319-330
         L->c1w = take(4096); L->c1b = take(16); L->bn1b = take(16); L->bn1g = take(16);
         L->c2w = take(8192); L->c2b = take(32); L->bn2b = take(32); L->bn2g = take(32);
@@ -933,6 +938,7 @@ struct DevBuf {
 
 extern "C" int dne_num_params(int kind, int nact) {
     if (kind == DNE_KIND_MAZE && nact != maze::ACT) return -1;   // the maze policy has two raw outputs, nothing else
+    if (kind == DNE_KIND_CARTPOLE && nact != cartpole::ACT) return -1;   // CartPole-v1 has two actions
     Layout L;
     make_layout(kind, nact, &L);
     return L.P;
@@ -945,6 +951,10 @@ extern "C" int dne_debug_plan(int kind, int n_actions, const dne_plan_facts *fac
                               int *nsub, int whole_eval) {
     if (kind == DNE_KIND_MAZE) {   // no lock-step to plan: one launch per evaluation
         g_create_error = "dne_debug_plan: a DNE_KIND_MAZE engine (kind 4) has no lock-step windows, an evaluation is one k_maze_rollout launch";
+        return -1;
+    }
+    if (kind == DNE_KIND_CARTPOLE) {
+        g_create_error = "dne_debug_plan: a DNE_KIND_CARTPOLE engine (kind 5) has no lock-step windows, an evaluation is one k_cartpole_rollout launch";
         return -1;
     }
     const Knobs k = engine_knobs(kind, n_actions);
@@ -964,6 +974,10 @@ extern "C" int dne_debug_plan(int kind, int n_actions, const dne_plan_facts *fac
 extern "C" int dne_debug_plan_act(int kind, int n_actions, const dne_plan_facts *facts, int n, dne_window_plan *out) {
     if (kind == DNE_KIND_MAZE) {   // dne_act refuses the kind
         g_create_error = "dne_debug_plan_act: a DNE_KIND_MAZE engine (kind 4) has no dne_act";
+        return -1;
+    }
+    if (kind == DNE_KIND_CARTPOLE) {
+        g_create_error = "dne_debug_plan_act: a DNE_KIND_CARTPOLE engine (kind 5) has no dne_act";
         return -1;
     }
     if (n < 1) {
@@ -1024,7 +1038,8 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         return -1;
     }
     if (cfg->max_members <= 0 || cfg->n_actions <= 1 ||
-        (!es_like(cfg->policy_kind) && cfg->policy_kind != DNE_KIND_GA && cfg->policy_kind != DNE_KIND_GA_LARGE && cfg->policy_kind != DNE_KIND_MAZE)) {
+        (!es_like(cfg->policy_kind) && cfg->policy_kind != DNE_KIND_GA && cfg->policy_kind != DNE_KIND_GA_LARGE && cfg->policy_kind != DNE_KIND_MAZE &&
+         cfg->policy_kind != DNE_KIND_CARTPOLE)) {
         g_create_error = "dne_create: bad config";
         return -1;
     }
@@ -1041,6 +1056,15 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
     if (cfg->policy_kind == DNE_KIND_MAZE && cfg->bc_final_only) {
         g_create_error = "dne_create: bc_final_only is not available on a DNE_KIND_MAZE engine (kind 4): its bc rows are (x, y) after every step; "
                          "dne_maze_final_state has the final position of every member";
+        return -1;
+    }
+    if (cfg->policy_kind == DNE_KIND_CARTPOLE && cfg->n_actions != cartpole::ACT) {
+        g_create_error = "dne_create: DNE_KIND_CARTPOLE has 2 actions (push the cart left or right), n_actions " + std::to_string(cfg->n_actions) + " is refused";
+        return -1;
+    }
+    if (cfg->policy_kind == DNE_KIND_CARTPOLE && cfg->bc_final_only) {
+        g_create_error = "dne_create: bc_final_only is not available on a DNE_KIND_CARTPOLE engine (kind 5): it records no behaviour; "
+                         "dne_cartpole_final_state has the final state of every member";
         return -1;
     }
     dne_handle *h = new dne_handle();
@@ -1063,9 +1087,11 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         env_int("DNE_STAGED_COPY", 0, 1, &sc);
         h->staged_copies = sc != 0;
     }
-    if (cfg->policy_kind == DNE_KIND_MAZE) {
-        // theta slots, member descriptors and accumulators, the walls, the reduce and optimizer buffers: no frame, activation or ring buffer
-        h->maze = true;
+    if (cfg->policy_kind == DNE_KIND_MAZE || cfg->policy_kind == DNE_KIND_CARTPOLE) {
+        // theta slots, member descriptors and accumulators, the walls (the cart-pole: seeds and final states), the reduce and optimizer
+        // buffers: no frame, activation or ring buffer
+        h->maze = cfg->policy_kind == DNE_KIND_MAZE;
+        h->cartpole = !h->maze;
         make_layout(cfg->policy_kind, cfg->n_actions, &h->L);
         h->M = cfg->max_members;
         h->base_stride = ((size_t)h->L.P + 63) / 64 * 64;
@@ -1079,9 +1105,14 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         CH(hipMemset(h->m_slot, 0, M * sizeof(int32_t))); CH(hipMemset(h->m_off, 0, M * sizeof(int64_t))); CH(hipMemset(h->m_scale, 0, M * sizeof(float)));
         CH(h->alloc(&h->ret, M, "ret")); CH(h->alloc(&h->sign, M, "sign")); CH(h->alloc(&h->len, M, "len"));
         CH(hipMemset(h->ret, 0, M * sizeof(float))); CH(hipMemset(h->sign, 0, M * sizeof(float))); CH(hipMemset(h->len, 0, M * sizeof(int32_t)));
-        CH(h->alloc(&h->maze_xy, 2 * M, "maze_xy")); CH(h->alloc(&h->maze_walls, maze::MAX_WALLS * 4, "maze_walls"));
-        CH(hipMemset(h->maze_xy, 0, 2 * M * sizeof(float)));
-        if (cfg->record_bc) {   // behaviour: the navigator's (x, y) after every step, [member][bc_max_steps][2] floats
+        if (h->maze) {
+            CH(h->alloc(&h->maze_xy, 2 * M, "maze_xy")); CH(h->alloc(&h->maze_walls, maze::MAX_WALLS * 4, "maze_walls"));
+            CH(hipMemset(h->maze_xy, 0, 2 * M * sizeof(float)));
+        } else {
+            CH(h->alloc(&h->cp_state, 4 * M, "cartpole_state")); CH(h->alloc(&h->seeds, M, "seeds"));
+            CH(hipMemset(h->cp_state, 0, 4 * M * sizeof(double))); CH(hipMemset(h->seeds, 0, M * sizeof(uint32_t)));
+        }
+        if (h->maze && cfg->record_bc) {   // behaviour: the navigator's (x, y) after every step, [member][bc_max_steps][2] floats
             h->bc_bytes = M * (size_t)std::max(cfg->bc_max_steps, 1) * 2 * sizeof(float);
             CH(h->alloc(&h->bc, h->bc_bytes, "bc"));
             CH(hipMemset(h->bc, 0, h->bc_bytes));
@@ -1090,7 +1121,7 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         CH(h->alloc(&h->scratch_f, h->scratch_cap, "scratch_f")); CH(h->alloc(&h->scratch_i, h->scratch_cap, "scratch_i"));
         CH(hipEventCreate(&h->ev_a)); CH(hipEventCreate(&h->ev_b));
         CH(hipDeviceSynchronize());
-        h->trace("engine created: kind %d (hard maze), %d members, %zu device buffers", cfg->policy_kind, h->M, h->blocks.size());
+        h->trace("engine created: kind %d (%s), %d members, %zu device buffers", cfg->policy_kind, h->maze ? "hard maze" : "cart-pole", h->M, h->blocks.size());
         *out = h;
         return 0;
     }
@@ -2159,7 +2190,7 @@ static maze::Header maze_header(const float *h8) {
 }
 
 // what every entry point of the three maze sections asks first
-static int needs_maze(dne_handle *h, const char *call) {
+static int needs_maze(dne_handle *h, const char *call) {   // (a DNE_KIND_CARTPOLE engine is refused here like every other kind)
     return h->maze ? 0 : h->fail("%s needs a DNE_KIND_MAZE engine (this one: kind %d)", call, h->L.kind);
 }
 
@@ -2634,13 +2665,127 @@ extern "C" int dne_maze_novelty_pool_host(const float *xy, int n, const float *a
     return 0;
 }
 
+// ------------------------------------------------------------------------------- gym.CartPole-v1 (csrc/cartpole.h)
+static int needs_cartpole(dne_handle *h, const char *call) {
+    return h->cartpole ? 0 : h->fail("%s needs a DNE_KIND_CARTPOLE engine (this one: kind %d)", call, h->L.kind);
+}
+
+// what k_cartpole_rollout reads for the members [first, first + count) set by dne_set_members; its outputs are left null
+static cartpole::RolloutArgs cartpole_args(dne_handle *h, int first, int count, int tslimit) {
+    cartpole::RolloutArgs A{};
+    A.noise = h->noise; A.bases = h->bases; A.base_stride = h->base_stride;
+    A.m_slot = h->m_slot; A.m_off = h->m_off; A.m_scale = h->m_scale;
+    A.first = first; A.count = count; A.seed = h->seeds; A.tslimit = tslimit;
+    return A;
+}
+
+// members [0, n), one whole episode each under its own reset seed, one launch
+static int cartpole_eval(dne_handle *h, const char *call, int n, int tslimit, const uint32_t *env_seed, float *returns, float *signreturns,
+                         int32_t *lengths, uint8_t *bc_out) {
+    if (bc_out) return h->fail("%s: behaviour characterisations are not available on a DNE_KIND_CARTPOLE engine (kind %d): bc must be NULL; "
+                               "dne_cartpole_final_state has the final state of every member", call, DNE_KIND_CARTPOLE);
+    if (tslimit <= 0) return h->fail("timestep limit must be positive");
+    if (!env_seed) return h->fail("%s: a DNE_KIND_CARTPOLE engine resets every member from its environment seed, env_seed is NULL", call);
+    if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
+    HCHECK(h, hipMemcpyAsync(h->seeds, env_seed, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    cartpole::RolloutArgs A = cartpole_args(h, 0, n, tslimit);
+    A.ret = h->ret; A.sign = h->sign; A.len = h->len; A.state = h->cp_state;
+    HCHECK(h, hipEventRecord(h->ev_a, h->stream));
+    hipLaunchKernelGGL(cartpole::k_cartpole_rollout, dim3((n + 3) / 4), dim3(64), 0, h->stream, A);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipEventRecord(h->ev_b, h->stream));
+    HCHECK(h, hipMemcpyAsync(returns, h->ret, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (signreturns) HCHECK(h, hipMemcpyAsync(signreturns, h->sign, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipMemcpyAsync(lengths, h->len, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    h->cp_last_n = n;
+    float ms = 0;
+    HCHECK(h, hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
+    dne_profile &P = h->prof;
+    P = dne_profile{};
+    P.eval_ms = P.env_ms = ms;
+    P.fc_launches = 1;
+    for (int i = 0; i < n; i++) P.env_steps += lengths[i];
+    return 0;
+}
+
+extern "C" int dne_cartpole_final_state(dne_handle *h, int n, double *state) {
+    DeviceGuard dg(h);
+    if (needs_cartpole(h, "dne_cartpole_final_state")) return -1;
+    if (n < 1 || n > h->cp_last_n) return h->fail("dne_cartpole_final_state: %d members asked for, the last evaluation ran %d", n, h->cp_last_n);
+    if (!state) return h->fail("dne_cartpole_final_state: no output buffer");
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(state, h->cp_state, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the kernel once more for ONE of the current members, with every step written out: trace [min(tslimit, 500)][8] as
+// dne_cartpole_rollout_host writes it.  The accumulators of the last evaluation are left alone.
+extern "C" int dne_cartpole_debug_trace(dne_handle *h, int member, int tslimit, const double *init4, double *trace, int32_t *steps) {
+    DeviceGuard dg(h);
+    if (needs_cartpole(h, "dne_cartpole_debug_trace")) return -1;
+    if (member < 0 || member >= (int)h->host_slot.size()) return h->fail("dne_cartpole_debug_trace: member %d, dne_set_members set %zu", member, h->host_slot.size());
+    if (tslimit <= 0 || !trace || !steps) return h->fail("dne_cartpole_debug_trace: bad arguments");
+    if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
+    const int cap = std::min(tslimit, (int)cartpole::EPISODE_STEPS);
+    DevBuf<double> d;
+    DevBuf<int32_t> dn;
+    HCHECK(h, d.alloc((size_t)cap * cartpole::TRACE_W));
+    HCHECK(h, dn.alloc(1));
+    cartpole::RolloutArgs A = cartpole_args(h, member, 1, tslimit);
+    if (init4) { A.has_init = 1; for (int i = 0; i < 4; i++) A.init4[i] = init4[i]; }
+    A.trace = d; A.trace_steps = dn;
+    hipLaunchKernelGGL(cartpole::k_cartpole_rollout, dim3(1), dim3(64), 0, h->stream, A);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(steps, dn, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (*steps < 0 || *steps > cap) return h->fail("dne_cartpole_debug_trace: the kernel reports %d steps under a limit of %d", *steps, cap);
+    HCHECK(h, hipMemcpy(trace, d, (size_t)*steps * cartpole::TRACE_W * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the same header on the CPU: no handle, no GPU (like dne_maze_rollout_host)
+extern "C" int dne_cartpole_reset_host(uint32_t seed, double *out4) {
+    if (!out4) { g_create_error = "dne_cartpole_reset_host: no output buffer"; return -1; }
+    const cartpole::State s = cartpole::reset_state(seed);
+    out4[0] = s.x; out4[1] = s.x_dot; out4[2] = s.theta; out4[3] = s.theta_dot;
+    return 0;
+}
+
+extern "C" int dne_cartpole_rollout_host(const float *theta, int n, const uint32_t *seeds, const double *init4, int tslimit, float *returns,
+                                         int32_t *lengths, double *state, double *trace) {
+    if (n < 1 || tslimit <= 0 || !theta || !seeds || !returns || !lengths || !state) { g_create_error = "dne_cartpole_rollout_host: bad arguments"; return -1; }
+    for (int i = 0; i < n; i++) {
+        lengths[i] = cartpole::rollout_host(theta + (size_t)i * cartpole::NPARAMS, seeds[i], init4 ? init4 + 4 * (size_t)i : nullptr, tslimit,
+                                            state + 4 * (size_t)i, trace ? trace + (size_t)i * tslimit * cartpole::TRACE_W : nullptr);
+        returns[i] = (float)lengths[i];
+    }
+    return 0;
+}
+
+extern "C" int dne_cartpole_actions_host(const int32_t *actions, int n, int T, const double *init4, double *rows) {
+    if (n < 1 || T < 1 || !actions || !init4 || !rows) { g_create_error = "dne_cartpole_actions_host: bad arguments"; return -1; }
+    for (size_t i = 0; i < (size_t)n * T; i++)
+        if (actions[i] != 0 && actions[i] != 1) { g_create_error = "dne_cartpole_actions_host: action " + std::to_string(actions[i]) + ", CartPole-v1 has actions 0 and 1"; return -1; }
+    for (int i = 0; i < n; i++) cartpole::actions_host(actions + (size_t)i * T, T, init4 + 4 * (size_t)i, rows + (size_t)i * T * 5);
+    return 0;
+}
+
+extern "C" int dne_cartpole_forward_host(const float *theta, const float *obs, int n, float *h1, float *h2, float *out) {
+    if (n < 1 || !theta || !obs || !h1 || !h2 || !out) { g_create_error = "dne_cartpole_forward_host: bad arguments"; return -1; }
+    for (int i = 0; i < n; i++)
+        cartpole::forward_host(theta + (size_t)i * cartpole::NPARAMS, obs + (size_t)i * cartpole::OBS, h1 + (size_t)i * cartpole::HID,
+                               h2 + (size_t)i * cartpole::HID, out + (size_t)i * cartpole::ACT);
+    return 0;
+}
+
 // ------------------------------------------------------------------------------- evaluations by descriptor: antithetic pairs, members as set
 extern "C" int dne_es_eval(dne_handle *h, const int64_t *idx, int n, float sigma, int tslimit, const uint32_t *env_seed,
                            float *returns_n2, float *signreturns_n2, int32_t *lengths_n2, uint8_t *bc) {
     DeviceGuard dg(h);
     // antithetic pairs over base slot 0: the ES kinds, and the GPU tree's LargeModel (its es.py runs over any model; no reference pass).
     // GAAtariPolicy's kernels take one member per group.
-    if (!es_like(h->L.kind) && !h->large && !h->maze)
+    if (!es_like(h->L.kind) && !h->large && !h->episodic())
         return h->fail("dne_es_eval needs an engine of kind DNE_KIND_ES, DNE_KIND_ES_VBN or DNE_KIND_GA_LARGE (this one: %d)", h->L.kind);
     if (n <= 0 || 2 * n > h->M) return h->fail("%d pairs exceed max_members = %d", n, h->M);
     std::vector<int32_t> slot(2 * n, 0);
@@ -2659,6 +2804,7 @@ extern "C" int dne_es_eval(dne_handle *h, const int64_t *idx, int n, float sigma
         h->dense_scale = std::min(16.0, std::max(1.0, (double)h->noise_count / std::max(span, 1.0)));
     }
     if (h->maze) return maze_eval(h, 2 * n, tslimit, returns_n2, signreturns_n2, lengths_n2, bc);   // (the episode is deterministic: env_seed is not read)
+    if (h->cartpole) return cartpole_eval(h, "dne_es_eval", 2 * n, tslimit, env_seed, returns_n2, signreturns_n2, lengths_n2, bc);
     return eval_core(h, 2 * n, 2, tslimit, env_seed, returns_n2, signreturns_n2, lengths_n2, bc);
 }
 
@@ -2669,6 +2815,10 @@ extern "C" int dne_eval_members(dne_handle *h, int n, int tslimit, const uint32_
     if (h->maze) {
         if ((int)h->host_slot.size() < n) return h->fail("dne_eval_members: %d members asked for, dne_set_members set %zu", n, h->host_slot.size());
         return maze_eval(h, n, tslimit, returns, signreturns, lengths, bc);
+    }
+    if (h->cartpole) {
+        if ((int)h->host_slot.size() < n) return h->fail("dne_eval_members: %d members asked for, dne_set_members set %zu", n, h->host_slot.size());
+        return cartpole_eval(h, "dne_eval_members", n, tslimit, env_seed, returns, signreturns, lengths, bc);
     }
     return eval_core(h, n, 1, tslimit, env_seed, returns, signreturns, lengths, bc);
 }
@@ -3243,7 +3393,7 @@ static int check_records_host(dne_handle *h, int n_global) {
 // the gloo tests)
 extern "C" int dne_records_pack(dne_handle *h, int n_local, void *records_out) {
     DeviceGuard dg(h);
-    if ((!es_like(h->L.kind) && !h->large && !h->maze) || n_local < 1 || 2 * n_local > h->M) return h->fail("dne_records_pack: %d pairs", n_local);
+    if ((!es_like(h->L.kind) && !h->large && !h->episodic()) || n_local < 1 || 2 * n_local > h->M) return h->fail("dne_records_pack: %d pairs", n_local);
     if (rec_reserve(h, n_local, n_local)) return -1;
     hipLaunchKernelGGL(k_records_pack, dim3((n_local + 255) / 256), dim3(256), 0, h->stream, (const int64_t *)h->m_off, (const float *)h->ret,
                        (const float *)h->sign, (const int32_t *)h->len, n_local, n_local, (PairRecord *)h->rec_send);
@@ -3277,7 +3427,7 @@ extern "C" int dne_records_set(dne_handle *h, const void *records, int n_global)
 extern "C" int dne_allgather_results(dne_handle *h, int n_local, int n_global, void *records_out) {
     DeviceGuard dg(h);
     const int world = h->comm ? h->comm_size : 1, rank = h->comm ? h->comm_rank : 0;
-    if (!es_like(h->L.kind) && !h->large && !h->maze) return h->fail("dne_allgather_results needs an engine dne_es_eval accepts (DNE_KIND_ES, DNE_KIND_ES_VBN, DNE_KIND_GA_LARGE)");
+    if (!es_like(h->L.kind) && !h->large && !h->episodic()) return h->fail("dne_allgather_results needs an engine dne_es_eval accepts (DNE_KIND_ES, DNE_KIND_ES_VBN, DNE_KIND_GA_LARGE)");
     const int mine = n_global > rank ? (n_global - rank + world - 1) / world : 0;
     if (n_global < 1 || n_local != mine || 2 * n_local > h->M)
         return h->fail("dne_allgather_results: rank %d of %d holds %d pairs, a population of %d pairs gives it %d", rank, world, n_local, n_global, mine);

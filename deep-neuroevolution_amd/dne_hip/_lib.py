@@ -17,6 +17,8 @@ KIND_ES_VBN = 3   # the GPU tree's ModelVirtualBN in its own flat layout (models
 KIND_MAZE = 4     # the GPU tree's hard maze under SimpleClassifier (gym_tensorflow/maze/, models/simple.py:29-35): whole episodes in one kernel (csrc/maze.h)
 MAZE_OBS, MAZE_STEPS, MAZE_TRACE_W, MAZE_MAX_WALLS = 11, 400, 16, 64   # observation width, tf_maze.cpp's episode length, floats per trace row, walls the kernel takes
 MAZE_NOVELTY_KMAX, MAZE_NOVELTY_TILE, MAZE_ARCHIVE_CAP0 = 32, 1024, 64   # csrc/maze_novelty.h: neighbours a lane keeps, archive points per LDS tile; the archive's first allocation (engine.hip)
+KIND_CARTPOLE = 5   # the GPU tree's gym configuration: gym.CartPole-v1 under SimpleClassifier on 4 inputs, whole episodes in one kernel (csrc/cartpole.h)
+CARTPOLE_OBS, CARTPOLE_STEPS, CARTPOLE_TRACE_W, CARTPOLE_P = 4, 500, 8, 386   # observation width, CartPole-v1's max_episode_steps, doubles per trace row, parameters
 ES_KINDS = (KIND_ES, KIND_ES_VBN)   # virtual batch norm over a reference batch, antithetic pairs
 PROC_MODES = {"centered_rank": 0, "sign": 1, "centered_sign_rank": 2}
 OPT_KINDS = {"adam": 0, "sgd": 1}
@@ -74,7 +76,7 @@ class Profile(C.Structure):
 
 def build(force=False):
     """Compile libdne_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h", "cartpole.h")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dne_hip.h"))
     if os.environ.get("DNE_LIB_PATH"):
         # another build of the same ABI was asked for by name: `make` only knows the in-tree library, so running it here would
@@ -303,6 +305,57 @@ def maze_ga_members_host(noise, scale_by, bank, parent, idx, power):
                                              _ptr(bank, C.c_float) if bank.shape[0] else None, int(bank.shape[0]), _ptr(parent, C.c_int32),
                                              _ptr(idx, C.c_int64), _ptr(power, C.c_float), int(parent.size), _ptr(out, C.c_float)))
     return out
+
+
+def cartpole_reset_host(seed):
+    """dne_cartpole_reset_host: the reset state (x, x_dot, theta, theta_dot) of one uint32 environment seed, float64 [4]"""
+    out = np.empty(4, np.float64)
+    _ck_host(load().dne_cartpole_reset_host(C.c_uint32(int(seed)), _ptr(out, C.c_double)))
+    return out
+
+
+def cartpole_rollout_host(theta, seeds, tslimit=CARTPOLE_STEPS, init=None, want_trace=False):
+    """dne_cartpole_rollout_host: csrc/cartpole.h on the CPU (no GPU, no handle) for thetas [n][386] under environment seeds [n] (init [n][4]:
+    explicit initial states instead) -> returns [n], lengths [n], final states float64 [n][4] (, trace float64 [n][tslimit][8] = the
+    observation after each step as doubles, then the state; rows past an episode's length stay zero)"""
+    theta = _arr(theta, np.float32).reshape(-1, CARTPOLE_P)
+    n = theta.shape[0]
+    seeds = _arr(seeds, np.uint32).reshape(-1)
+    if seeds.size != n:
+        raise DneError("cartpole_rollout_host: %d thetas, %d seeds" % (n, seeds.size))
+    if init is not None:
+        init = _arr(init, np.float64).reshape(-1, 4)
+        if init.shape[0] != n:
+            raise DneError("cartpole_rollout_host: %d thetas, %d initial states" % (n, init.shape[0]))
+    ret = np.empty(n, np.float32); ln = np.empty(n, np.int32); state = np.empty((n, 4), np.float64)
+    trace = np.zeros((n, int(tslimit), CARTPOLE_TRACE_W), np.float64) if want_trace else None
+    _ck_host(load().dne_cartpole_rollout_host(_ptr(theta, C.c_float), n, _ptr(seeds, C.c_uint32), _ptr(init, C.c_double), int(tslimit),
+                                              _ptr(ret, C.c_float), _ptr(ln, C.c_int32), _ptr(state, C.c_double), _ptr(trace, C.c_double)))
+    return (ret, ln, state, trace) if want_trace else (ret, ln, state)
+
+
+def cartpole_actions_host(actions, init):
+    """dne_cartpole_actions_host: the environment alone under open-loop actions [n][T] (0 / 1) from initial states [n][4] -> rows float64
+    [n][T][5] = the state after each step, then done (1 / 0); the stepping goes on past done"""
+    actions = _arr(actions, np.int32); actions = actions.reshape(-1, actions.shape[-1])
+    n, T = actions.shape
+    init = _arr(init, np.float64).reshape(-1, 4)
+    if init.shape[0] != n:
+        raise DneError("cartpole_actions_host: %d sequences, %d initial states" % (n, init.shape[0]))
+    rows = np.empty((n, T, 5), np.float64)
+    _ck_host(load().dne_cartpole_actions_host(_ptr(actions, C.c_int32), n, T, _ptr(init, C.c_double), _ptr(rows, C.c_double)))
+    return rows
+
+
+def cartpole_forward_host(theta, obs):
+    """dne_cartpole_forward_host: the policy alone, thetas [n][386] on observations [n][4] -> (h1 [n][16], h2 [n][16], out [n][2])"""
+    theta = _arr(theta, np.float32).reshape(-1, CARTPOLE_P); obs = _arr(obs, np.float32).reshape(-1, CARTPOLE_OBS)
+    n = theta.shape[0]
+    if obs.shape[0] != n:
+        raise DneError("cartpole_forward_host: %d thetas, %d observations" % (n, obs.shape[0]))
+    h1 = np.empty((n, 16), np.float32); h2 = np.empty((n, 16), np.float32); out = np.empty((n, 2), np.float32)
+    _ck_host(load().dne_cartpole_forward_host(_ptr(theta, C.c_float), _ptr(obs, C.c_float), n, _ptr(h1, C.c_float), _ptr(h2, C.c_float), _ptr(out, C.c_float)))
+    return h1, h2, out
 
 
 def _ptr(a, t):
@@ -557,6 +610,22 @@ class Engine:
         out = np.empty((x.size, 2), np.float64)
         self._ck(self.lib.dne_maze_debug_math(self.h, int(fn), _ptr(x, C.c_double), int(x.size), _ptr(out, C.c_double)))
         return out
+
+    # ---- gym.CartPole-v1 (KIND_CARTPOLE)
+    def cartpole_final_state(self, n):
+        """final (x, x_dot, theta, theta_dot) of the first n members of the last evaluation, float64 [n][4]"""
+        state = np.empty((int(n), 4), np.float64)
+        self._ck(self.lib.dne_cartpole_final_state(self.h, int(n), _ptr(state, C.c_double)))
+        return state
+
+    def cartpole_debug_trace(self, member, tslimit=CARTPOLE_STEPS, init=None):
+        """the kernel once more for one current member, every step written out: float64 [steps][8] as cartpole_rollout_host's trace, cut at the
+        episode's length.  init [4]: the initial state; None: the reset of the seed that member had in the last evaluation."""
+        out = np.zeros((min(int(tslimit), CARTPOLE_STEPS), CARTPOLE_TRACE_W), np.float64)
+        init = None if init is None else _arr(init, np.float64).reshape(4)
+        steps = C.c_int32(0)
+        self._ck(self.lib.dne_cartpole_debug_trace(self.h, int(member), int(tslimit), _ptr(init, C.c_double), _ptr(out, C.c_double), C.byref(steps)))
+        return out[:steps.value]
 
     # ---- novelty on the hard maze (csrc/maze_novelty.h): BCs are final (x, y) points, the archive lives on the device
     def _maze_points(self, xy, n):

@@ -32,6 +32,13 @@ in the working directory (tf_maze.py:28), else the copy of the reference's file 
 idx the stream's first draw; 'env_default' means 400 steps (tf_maze.py:32-33).  The game is recorded in snapshot.pkl (a snapshot without it is an Atari
 run); a resume under another game fails and names both.  SimpleClassifier on an Atari game and the Atari models on the maze are refused.
 
+exp['game'] == 'gym.CartPole-v1' (configurations/es_gym_config.json; gym_tensorflow.make sends every 'gym.*' name to GymEnv, a Python list of gym
+environments stepped on the CPU) with exp['model'] == 'SimpleClassifier' runs on a DNE_KIND_CARTPOLE engine: a whole episode of at most 500 steps per
+member inside one kernel (csrc/cartpole.h), no reference batch, every episode reset from its own environment seed of the run's stream (test
+episodes included, as on Atari); theta starts as noise.get(idx, 386) * policies.simple_scale_by(KIND_CARTPOLE) with idx the stream's first draw;
+'env_default' means 500 steps, and a larger cutoff (the shipped 5000) leaves gym's own 500 in force (GymEnv.reset ignores max_frames, tf_env.py:47-52).
+A step is a frame.  The game is recorded in snapshot.pkl like the maze's.  Every other 'gym.*' name is refused by name: no other gym environment is built.
+
 Where the arithmetic lives: ranks, sum_i w_i * noise[idx_i] / 2N, -g + l2coeff * theta and the optimizer step are dne_es_update on the device
 (the same formulas as es_distributed: es.py:227-246 here = es_distributed/es.py:281-301).  The GPU tree's SGD keeps v = momentum * v + g
 (neuroevolution/optimizers.py:49-51) where es_distributed keeps (1 - momentum) * g: with u = (1 - momentum) * v that is the engine's SGD at
@@ -47,6 +54,8 @@ import numpy as np
 from . import _lib
 from .es import SharedNoiseTable, get_ref_batch, optimizer_args, parse_cutoff
 from .ga_gpu import Offspring, Schedule, model_scale_by
+from . import cartpole_run
+from .cartpole_run import CARTPOLE_GAME
 from .maze_run import MAZE_FILE, MAZE_MODEL, check_engine, maze_file, open_engine   # noqa: F401 (MAZE_FILE, maze_file: read as es_gpu's by callers)
 
 # exp['model'] (es.py:144): neuroevolution/models/batchnorm.py:52 (in either flat layout, FLAT_LAYOUTS) and models/dqn.py:39
@@ -69,7 +78,7 @@ class TrainingState(object):
         if adaptive:
             self.tslimit_max = limit_max
         self.flat_layout = 'es_distributed'   # FLAT_LAYOUTS key of the run (main sets it); a snapshot without it predates the choice
-        self.game = None                      # exp['game'] of a maze run ('maze'); None: an Atari game (a snapshot without it predates the maze)
+        self.game = None                      # exp['game'] of a maze or cart-pole run ('maze', 'gym.CartPole-v1'); None: an Atari game (a snapshot without it predates the maze)
         self.model = 'ModelVirtualBN'         # MODEL_KINDS key of the run (main sets it); a snapshot without it predates LargeModel
         self.num_params = None
         self.theta = None
@@ -102,7 +111,9 @@ def engine_optimizer(opt):
 
 
 def _env_limit(engine):
-    """the environment's own episode bound: env_default_timestep_cutoff of the maze (tf_maze.py:32-33), gym's TimeLimit for Atari"""
+    """the environment's own episode bound: env_default_timestep_cutoff of the maze (tf_maze.py:32-33), CartPole-v1's 500, gym's TimeLimit for Atari"""
+    if engine.kind == _lib.KIND_CARTPOLE:
+        return _lib.CARTPOLE_STEPS
     return _lib.MAZE_STEPS if engine.kind == _lib.KIND_MAZE else _lib.ENV_MAX_EPISODE_STEPS
 
 
@@ -129,8 +140,18 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
         raise NotImplementedError("load_from (es.py:164-171: a ga_legacy genome as the first theta) is not built")
     n_pairs = exp['population_size'] // 2
     asked = exp['model'] if engine is None else exp.get('model')   # the caller's engine decides; a name given with it must agree
-    maze = exp.get('game') == 'maze' or (engine is not None and engine.kind == _lib.KIND_MAZE)
-    if maze:                                                        # gym_tensorflow.make(game='maze'): the hard maze under SimpleClassifier
+    game = exp.get('game')
+    if isinstance(game, str) and game.startswith('gym.') and game != CARTPOLE_GAME:
+        raise NotImplementedError("game {!r}: of gym_tensorflow's 'gym.*' environments this loop runs {!r} only".format(game, CARTPOLE_GAME))
+    cart = game == CARTPOLE_GAME or (engine is not None and engine.kind == _lib.KIND_CARTPOLE)
+    maze = not cart and (game == 'maze' or (engine is not None and engine.kind == _lib.KIND_MAZE))
+    if cart:                                                        # gym_tensorflow.make(game='gym.CartPole-v1'): GymEnv's cart-pole under SimpleClassifier
+        if game != CARTPOLE_GAME:
+            raise ValueError("game {!r} asked for, the engine passed in (kind {}) runs {!r}".format(game, engine.kind, CARTPOLE_GAME))
+        cartpole_run.check_engine(engine)
+        if asked is not None and asked != MAZE_MODEL:
+            raise NotImplementedError("model {!r} on game {!r}: this loop runs {!r} there".format(asked, CARTPOLE_GAME, MAZE_MODEL))
+    elif maze:                                                        # gym_tensorflow.make(game='maze'): the hard maze under SimpleClassifier
         if exp.get('game') != 'maze':
             raise ValueError("game {!r} asked for, the engine passed in (kind {}) runs 'maze'".format(exp.get('game'), engine.kind))
         check_engine(engine)
@@ -138,18 +159,22 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
             raise NotImplementedError("model {!r} on game 'maze': this loop runs {!r} there".format(asked, MAZE_MODEL))
     elif asked == MAZE_MODEL:
         raise NotImplementedError("model {!r} on game {!r}: it runs on game 'maze' only".format(asked, exp.get('game')))
-    if not maze and asked is not None and asked not in MODEL_KINDS:
+    episodic = maze or cart                                         # a whole episode per member in one kernel: one layout, no reference batch, no frame skip
+    if not episodic and asked is not None and asked not in MODEL_KINDS:
         raise NotImplementedError("model {!r}: this loop runs {}".format(asked, sorted(MODEL_KINDS)))
-    large = not maze and (engine.kind if engine is not None else MODEL_KINDS[asked]) == _lib.KIND_GA_LARGE
-    model = MAZE_MODEL if maze else 'LargeModel' if large else 'ModelVirtualBN'
+    large = not episodic and (engine.kind if engine is not None else MODEL_KINDS[asked]) == _lib.KIND_GA_LARGE
+    model = MAZE_MODEL if episodic else 'LargeModel' if large else 'ModelVirtualBN'
     if asked is not None and asked != model:
         raise ValueError("model {!r} asked for, the engine passed in (kind {}) runs {!r}".format(asked, engine.kind, model))
-    if maze:                                                        # one flat layout, no reference batch, the walls instead
+    if episodic:                                                    # one flat layout, no reference batch; the maze: the walls instead
         layout = 'native'
         if exp.get('flat_layout', layout) != layout:
             raise ValueError("flat_layout {!r}: SimpleClassifier has one layout, 'native'".format(exp['flat_layout']))
-        engine, noise = open_engine(exp, engine, noise, 2 * n_pairs)
-        scale_by = policies.simple_scale_by()
+        if maze:
+            engine, noise = open_engine(exp, engine, noise, 2 * n_pairs)
+        else:
+            engine, noise = cartpole_run.open_engine(engine, noise, 2 * n_pairs)
+        scale_by = policies.simple_scale_by(engine.kind)
     elif large:                                                       # one flat layout, the model's own; no reference batch
         layout = 'native'
         if exp.get('flat_layout', layout) != layout:
@@ -168,7 +193,7 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
         if layout is None or exp.get('flat_layout', layout) != layout:
             raise ValueError("flat_layout {!r} asked for, the engine passed in (kind {}) runs {!r}".format(
                 exp.get('flat_layout'), engine.kind, layout))
-    if not maze:                                                    # (open_engine attached the maze's)
+    if not episodic:                                                # (open_engine attached the maze's and the cart-pole's)
         noise = noise if noise is not None else SharedNoiseTable()
         noise.attach(engine)
     rs = np.random.RandomState(seed)
@@ -178,28 +203,28 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
             state = pickle.load(file)
         tlogger.log("Loaded iteration {} from {}".format(state.it, log_dir))
         was_game = getattr(state, 'game', None)
-        if (was_game == 'maze') != maze:
+        if was_game != ('maze' if maze else CARTPOLE_GAME if cart else None):
             raise ValueError("snapshot.pkl in {} holds game {!r}; this run is game {!r}".format(
                 log_dir, was_game if was_game is not None else 'an Atari game', exp.get('game')))
         was_model = getattr(state, 'model', 'ModelVirtualBN')
-        if was_model != model or ((large or maze) and int(np.asarray(state.theta).size) != engine.P):
+        if was_model != model or ((large or episodic) and int(np.asarray(state.theta).size) != engine.P):
             raise ValueError("snapshot.pkl in {} holds model {!r} with P = {}; this run is model {!r} with P = {}".format(
                 log_dir, was_model, int(np.asarray(state.theta).size), model, engine.P))
         was = (getattr(state, 'flat_layout', 'es_distributed'), int(np.asarray(state.theta).size))
-        if not large and not maze and was != (layout, engine.P):
+        if not large and not episodic and was != (layout, engine.P):
             raise ValueError("snapshot.pkl in {} holds flat_layout {!r} with P = {}; this run is flat_layout {!r} with P = {}".format(
                 log_dir, was[0], was[1], layout, engine.P))
     except FileNotFoundError:
         state = TrainingState(exp)
-        if maze or large or layout == 'native':                             # es.py:173 -> es.py:73-75 -> model.randomize(rs, noise), base.py:123-141
+        if episodic or large or layout == 'native':                             # es.py:173 -> es.py:73-75 -> model.randomize(rs, noise), base.py:123-141
             idx = noise.sample_index(rs, engine.P)
-            state.theta = noise.get(idx, engine.P) * (scale_by if large or maze else policies.vbn_scale_by(engine.n_actions))
+            state.theta = noise.get(idx, engine.P) * (scale_by if large or episodic else policies.vbn_scale_by(engine.n_actions))
         else:
             state.theta = policies.xavier_flat(engine.n_actions, seed)   # es.py:173: state.initialize(rs, noise, worker.model)
     state.flat_layout, state.num_params, state.model = layout, engine.P, model
-    state.game = 'maze' if maze else None
+    state.game = 'maze' if maze else CARTPOLE_GAME if cart else None
     state.push(engine)
-    if not large and not maze:                                                   # ModelVirtualBN.requires_ref_batch (batchnorm.py:60-62); LargeModel has none
+    if not large and not episodic:                                               # ModelVirtualBN.requires_ref_batch (batchnorm.py:60-62); LargeModel has none
         env = policies.HipAtariEnv(engine, seed=seed)
         ref = np.stack(get_ref_batch(env, batch_size=engine.ref_count, random_stream=np.random.RandomState(seed)))
         engine.set_ref_batch(np.rint(ref * 255.0).astype(np.uint8))
@@ -220,7 +245,7 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
         limit = _env_limit(engine) if state.tslimit is None else min(int(state.tslimit), _env_limit(engine))
         rets, sgn, lens = engine.es_eval(idx, power, limit, seeds)
         results = [Offspring(int(i), [float(r[0]), float(r[1])], [int(l[0]), int(l[1])]) for i, r, l in zip(idx, rets, lens)]
-        state.num_frames += int(np.sum(lens)) * (1 if maze else 4)                  # (the maze has no frame skip: a step is a frame)
+        state.num_frames += int(np.sum(lens)) * (1 if episodic else 4)              # (the maze and the cart-pole have no frame skip: a step is a frame)
         state.it += 1
         rewards = np.array([b for a in results for b in a.rewards])
         timesteps_this_iter = int(sum(a.training_steps for a in results))

@@ -25,10 +25,22 @@ def step_limit(tslimit):
     return _lib.MAZE_STEPS if tslimit is None else min(int(tslimit), _lib.MAZE_STEPS)
 
 
+def check_engine_kind(engine, game, kind, kind_name):
+    """a caller's engine has to be of the kind that runs the game (None: the driver makes one); shared with cartpole_run"""
+    if engine is not None and engine.kind != kind:
+        raise ValueError("game {!r} asked for, the engine passed in is of kind {} ({} is {})".format(game, engine.kind, kind_name, kind))
+
+
+def attach_table(engine, noise):
+    """the run's noise table (the caller's, or a new SharedNoiseTable) attached to the engine; shared with cartpole_run"""
+    noise = noise if noise is not None else SharedNoiseTable()
+    noise.attach(engine)
+    return noise
+
+
 def check_engine(engine):
     """a caller's engine has to be of the maze's kind (None: open_engine makes one)"""
-    if engine is not None and engine.kind != _lib.KIND_MAZE:
-        raise ValueError("game 'maze' asked for, the engine passed in is of kind {} (KIND_MAZE is {})".format(engine.kind, _lib.KIND_MAZE))
+    check_engine_kind(engine, 'maze', _lib.KIND_MAZE, 'KIND_MAZE')
 
 
 def open_engine(exp, engine, noise, max_members):
@@ -37,6 +49,4 @@ def open_engine(exp, engine, noise, max_members):
     if engine is None:
         engine = _lib.Engine(_lib.KIND_MAZE, 2, max_members=max_members)
     engine.maze_set_walls(*_lib.load_maze(maze_file(exp)))
-    noise = noise if noise is not None else SharedNoiseTable()
-    noise.attach(engine)
-    return engine, noise
+    return engine, attach_table(engine, noise)

@@ -41,6 +41,10 @@ def flat_layout(kind, nact):
         add("fc1/w", (11, 16)); add("fc1/b", (1, 16))
         add("fc2/w", (16, 16)); add("fc2/b", (1, 16))
         add("out/w", (16, nact)); add("out/b", (1, nact))
+    elif kind == _lib.KIND_CARTPOLE:   # the same SimpleClassifier on CartPole-v1's 4 inputs (nact = 2: the first maximum of the outputs is the action)
+        add("fc1/w", (4, 16)); add("fc1/b", (1, 16))
+        add("fc2/w", (16, 16)); add("fc2/b", (1, 16))
+        add("out/w", (16, nact)); add("out/b", (1, nact))
     elif kind == _lib.KIND_GA_LARGE:   # the GPU tree's LargeModel, gpu_implementation/neuroevolution/models/dqn.py:39-47 (creation order, base.py:35-41)
         add("conv1/w", (8, 8, 4, 32)); add("conv1/b", (1, 1, 1, 32))
         add("conv2/w", (4, 4, 32, 64)); add("conv2/b", (1, 1, 1, 64))
@@ -67,10 +71,14 @@ def vbn_scale_by(nact):
     return sb
 
 
-def simple_scale_by():
+def simple_scale_by(kind=_lib.KIND_MAZE):
     """scale_by of SimpleClassifier on the hard maze (models/simple.py:29-35 over dqn.Model, dqn.py:25-27): std / sqrt(prod(shape[:-1])) for each
-    w -- 1/sqrt(11), 1/4 and (std = 0.1 for the out layer) 0.1/4 --, 0 for each b.  fp32, in flat order; theta_0 = noise.get(idx, 498) * scale_by."""
-    spec, P = flat_layout(_lib.KIND_MAZE, 2)
+    w -- 1/sqrt(11), 1/4 and (std = 0.1 for the out layer) 0.1/4 --, 0 for each b.  fp32, in flat order; theta_0 = noise.get(idx, 498) * scale_by.
+    kind = KIND_CARTPOLE: the same model on 4 inputs -- 1/sqrt(4), 1/4, 0.1/4 --, 386 values."""
+    if kind not in (_lib.KIND_MAZE, _lib.KIND_CARTPOLE):
+        raise ValueError("simple_scale_by: kind {} does not run SimpleClassifier (KIND_MAZE {} and KIND_CARTPOLE {} do)".format(
+            kind, _lib.KIND_MAZE, _lib.KIND_CARTPOLE))
+    spec, P = flat_layout(kind, 2)
     sb = np.zeros(P, np.float32)
     for name, (off, shape) in spec.items():
         if name.endswith('/w'):

@@ -39,6 +39,13 @@ extern "C" {
                            bc_final_only = 1 is refused by dne_create: dne_maze_final_state has every member's final (x, y).
                            The P-generic calls work unchanged (dne_es_update, dne_weighted_sum, the optimizer calls, dne_records_pack / _set,
                            dne_es_update_gathered); dne_ga_*, dne_ref_pass, dne_env_*, dne_novelty*, dne_act and dne_debug_plan refuse the kind. */
+#define DNE_KIND_CARTPOLE 5 /* the GPU tree's gym configuration (configurations/es_gym_config.json): gym.CartPole-v1 under SimpleClassifier on 4 inputs
+                           (dense 4 -> 16 -> 16 -> 2, 386 parameters); n_actions = 2, action = the first maximum of the two logits.  A whole episode
+                           (at most 500 steps) runs inside one kernel (csrc/cartpole.h): dne_set_members + dne_eval_members or dne_es_eval (pairs
+                           (2i, 2i+1) over base slot 0, no reference pass); env_seed[i] is member i's reset seed.  returns = signreturns = the
+                           episode's length (reward 1 per step); a non-NULL bc and bc_final_only = 1 are refused: dne_cartpole_final_state has
+                           every member's final state.  The P-generic calls work as on DNE_KIND_MAZE; every Atari-only, maze-only and GA-only
+                           call, dne_debug_plan and dne_debug_plan_act refuse the kind. */
 #define DNE_OB_BYTES (84 * 84 * 4)
 #define DNE_RAM_BYTES 128
 #define DNE_BN_FLOATS 608
@@ -338,6 +345,28 @@ int dne_maze_forward_host(const float *theta, const float *obs, int n, float *h1
  * the device; every kind but DNE_KIND_MAZE refuses the device call. */
 int dne_maze_math_host(int fn, const double *x, int n, double *out);
 int dne_maze_debug_math(dne_handle *h, int fn, const double *x, int n, double *out);
+
+/* ---- gym.CartPole-v1 (DNE_KIND_CARTPOLE; csrc/cartpole.h) ---------------------------------
+ * The state is four doubles: x, x_dot, theta, theta_dot.
+ * dne_cartpole_final_state: the final states of the last evaluation's first n members (1 <= n <= the members that evaluation ran).
+ * dne_cartpole_debug_trace: the kernel once more for ONE of the current members (dne_set_members / dne_es_eval), every step written out:
+ * trace [min(tslimit, 500)][8] = the observation after the step (four float32 values as doubles), then the state; *steps = the episode's
+ * length, rows past it are not written.  init4 != NULL is the initial state; NULL resets from the environment seed that member had in the
+ * last evaluation (0 before any).  The accumulators of the last evaluation are left alone.  Every other kind refuses both calls.
+ * The _host calls are the same header on the CPU (no handle, no GPU):
+ *   dne_cartpole_reset_host    the reset state of one seed;
+ *   dne_cartpole_rollout_host  one episode for each of n thetas [n][386] under seeds [n] (init4 [n][4] or NULL as above) -> returns, lengths,
+ *                              final states [n][4], trace [n][tslimit][8] or NULL;
+ *   dne_cartpole_actions_host  the environment alone: n sequences of T actions (0 / 1) from init4 [n][4] -> rows [n][T][5] = the state
+ *                              after the step, then done (1 / 0); stepping goes on past done;
+ *   dne_cartpole_forward_host  the policy alone: thetas [n][386] on observations [n][4] -> h1 [n][16], h2 [n][16], out [n][2]. */
+int dne_cartpole_final_state(dne_handle *h, int n, double *state /*[n][4]*/);
+int dne_cartpole_debug_trace(dne_handle *h, int member, int tslimit, const double *init4 /*[4] or NULL*/, double *trace, int32_t *steps);
+int dne_cartpole_reset_host(uint32_t seed, double *out4);
+int dne_cartpole_rollout_host(const float *theta, int n, const uint32_t *seeds, const double *init4, int tslimit, float *returns,
+                              int32_t *lengths, double *state, double *trace);
+int dne_cartpole_actions_host(const int32_t *actions, int n, int T, const double *init4, double *rows);
+int dne_cartpole_forward_host(const float *theta, const float *obs, int n, float *h1, float *h2, float *out);
 
 /* ---- novelty on the hard maze (csrc/maze_novelty.h) -------------------------------------------
  * A behaviour characterisation is one float32 point (x, y): a navigator's final position.  nses.py:12-32 on such points: for member p and
