@@ -33,6 +33,7 @@
 #include "maze_novelty.h"
 #include "maze_ga.h"
 #include "cartpole.h"
+#include "pendulum.h"
 
 using namespace dne;
 
@@ -49,6 +50,7 @@ static thread_local std::string g_create_error;
     do {                                                                                        \
         if ((h)->maze) return (h)->fail("%s is not available on a DNE_KIND_MAZE engine (kind %d): the hard maze has no Atari frames, reference batch, genomes or byte BCs", call, DNE_KIND_MAZE); \
         if ((h)->cartpole) return (h)->fail("%s is not available on a DNE_KIND_CARTPOLE engine (kind %d): the cart-pole has no Atari frames, reference batch, genomes or byte BCs", call, DNE_KIND_CARTPOLE); \
+        if ((h)->pendulum) return (h)->fail("%s is not available on a DNE_KIND_PENDULUM engine (kind %d): the pendulum has no Atari frames, reference batch, genomes or byte BCs", call, DNE_KIND_PENDULUM); \
     } while (0)
 
 // ------------------------------------------------------------------------------- env kernels
@@ -664,7 +666,14 @@ struct dne_handle {
     std::vector<int32_t> mzg_host_slot; std::vector<float> mzg_host_scale;   // what dne_maze_ga_eval uploaded
     bool cartpole = false;           // DNE_KIND_CARTPOLE: whole episodes in k_cartpole_rollout (csrc/cartpole.h); the maze's create path without walls
     double *cp_state = nullptr; int cp_last_n = 0;   // final (x, x_dot, theta, theta_dot) per member of the last evaluation, and how many members that was
-    bool episodic() const { return maze || cartpole; }   // a whole episode per member in one launch: what dne_es_eval and the record calls accept beside the Atari kinds
+    bool pendulum = false;           // DNE_KIND_PENDULUM: MujocoPolicy on the pendulum swing-up, whole episodes in k_pendulum_rollout (csrc/pendulum.h)
+    int pd_hidden = 0, pd_nl = 0;    // hidden width (64 / 128 / 256) and nonlinearity of the engine's policy; pd_opt: outputs, action mode, ob_mean / ob_std, noise std
+    pendulum::Options pd_opt{};
+    bool pd_stat_set = false;        // dne_pendulum_set_ob_stat was called (before it ob_mean / ob_std are NaN and an evaluation is refused)
+    double *pd_state = nullptr, *pd_sum = nullptr, *pd_sumsq = nullptr; int32_t *pd_count = nullptr; int pd_last_n = 0;   // per member of the last evaluation
+    int64_t *pd_acoff = nullptr; uint8_t *pd_flag = nullptr;   // dne_pendulum_set_rollout_options: per member, for the next evaluation only
+    int pd_opt_n = 0; bool pd_has_off = false, pd_has_flag = false; std::vector<int64_t> pd_host_off;   // (the offsets once more on the host: checked again at the launch)
+    bool episodic() const { return maze || cartpole || pendulum; }   // a whole episode per member in one launch: what dne_es_eval and the record calls accept beside the Atari kinds
     bool large = false;              // DNE_KIND_GA_LARGE: y1 [441][32], y2 / y3 [121][64] (conv3 output), y3t = the 512 fc outputs
     float *y1r[2] = {nullptr, nullptr}, *y2r[2] = {nullptr, nullptr}, *y3pr[2] = {nullptr, nullptr};   // reference pass scratch, two ways
     float *fr1[2] = {nullptr, nullptr}, *fr2[2] = {nullptr, nullptr};   // per-frame batch-norm moments of conv1 / conv2 ([rows][2][C])
@@ -830,10 +839,10 @@ static void make_layout(int kind, int nact, Layout *L) {
     memset(L, 0, sizeof(*L));
     L->kind = kind; L->nact = nact;
     auto take = [&](int n) { int r = o; o += n; return r; };
-    if (kind == DNE_KIND_MAZE || kind == DNE_KIND_CARTPOLE) {   // SimpleClassifier (models/simple.py:29-35): csrc/maze.h and csrc/cartpole.h hold its offsets
+    if (kind == DNE_KIND_MAZE || kind == DNE_KIND_CARTPOLE || kind == DNE_KIND_PENDULUM) {   // (DNE_KIND_PENDULUM: P depends on the hidden width, dne_create sets it) SimpleClassifier (models/simple.py:29-35): csrc/maze.h and csrc/cartpole.h hold its offsets
         L->c1w = L->c1b = L->c2w = L->c2b = L->c3w = L->c3b = L->fcw = L->fcb = L->ow = L->ob = -1;
         L->bn1b = L->bn1g = L->bn2b = L->bn2g = L->bn3b = L->bn3g = -1;
-        o = kind == DNE_KIND_MAZE ? maze::NPARAMS : cartpole::NPARAMS;
+        o = kind == DNE_KIND_MAZE ? maze::NPARAMS : kind == DNE_KIND_CARTPOLE ? cartpole::NPARAMS : 0;
     } else if (kind == DNE_KIND_ES) {   // creation order of trainable variables, policies.py:319-330
         L->c1w = take(4096); L->c1b = take(16); L->bn1b = take(16); L->bn1g = take(16);
         L->c2w = take(8192); L->c2b = take(32); L->bn2b = take(32); L->bn2g = take(32);
@@ -939,6 +948,7 @@ struct DevBuf {
 extern "C" int dne_num_params(int kind, int nact) {
     if (kind == DNE_KIND_MAZE && nact != maze::ACT) return -1;   // the maze policy has two raw outputs, nothing else
     if (kind == DNE_KIND_CARTPOLE && nact != cartpole::ACT) return -1;   // CartPole-v1 has two actions
+    if (kind == DNE_KIND_PENDULUM) return -1;   // P depends on the hidden width: dne_pendulum_num_params
     Layout L;
     make_layout(kind, nact, &L);
     return L.P;
@@ -955,6 +965,10 @@ extern "C" int dne_debug_plan(int kind, int n_actions, const dne_plan_facts *fac
     }
     if (kind == DNE_KIND_CARTPOLE) {
         g_create_error = "dne_debug_plan: a DNE_KIND_CARTPOLE engine (kind 5) has no lock-step windows, an evaluation is one k_cartpole_rollout launch";
+        return -1;
+    }
+    if (kind == DNE_KIND_PENDULUM) {
+        g_create_error = "dne_debug_plan: a DNE_KIND_PENDULUM engine (kind 6) has no lock-step windows, an evaluation is one k_pendulum_rollout launch";
         return -1;
     }
     const Knobs k = engine_knobs(kind, n_actions);
@@ -978,6 +992,10 @@ extern "C" int dne_debug_plan_act(int kind, int n_actions, const dne_plan_facts 
     }
     if (kind == DNE_KIND_CARTPOLE) {
         g_create_error = "dne_debug_plan_act: a DNE_KIND_CARTPOLE engine (kind 5) has no dne_act";
+        return -1;
+    }
+    if (kind == DNE_KIND_PENDULUM) {
+        g_create_error = "dne_debug_plan_act: a DNE_KIND_PENDULUM engine (kind 6) has no dne_act";
         return -1;
     }
     if (n < 1) {
@@ -1037,9 +1055,9 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         g_create_error = "dne_create: no HIP device visible (this engine has no CPU fallback)";
         return -1;
     }
-    if (cfg->max_members <= 0 || cfg->n_actions <= 1 ||
+    if (cfg->max_members <= 0 || (cfg->n_actions <= 1 && !(cfg->policy_kind == DNE_KIND_PENDULUM && cfg->n_actions == 1)) ||
         (!es_like(cfg->policy_kind) && cfg->policy_kind != DNE_KIND_GA && cfg->policy_kind != DNE_KIND_GA_LARGE && cfg->policy_kind != DNE_KIND_MAZE &&
-         cfg->policy_kind != DNE_KIND_CARTPOLE)) {
+         cfg->policy_kind != DNE_KIND_CARTPOLE && cfg->policy_kind != DNE_KIND_PENDULUM)) {
         g_create_error = "dne_create: bad config";
         return -1;
     }
@@ -1067,6 +1085,31 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
                          "dne_cartpole_final_state has the final state of every member";
         return -1;
     }
+    if (cfg->policy_kind == DNE_KIND_PENDULUM) {   // the shape: reserved[0] hidden width, [1] action mode, [2] nonlinearity; n_actions = the outputs
+        const int hidden = cfg->reserved[0], mode = cfg->reserved[1], nl = cfg->reserved[2];
+        if (!pendulum::hidden_ok(hidden)) {
+            g_create_error = "dne_create: DNE_KIND_PENDULUM is built for two hidden layers of width 64, 128 or 256; hidden width " + std::to_string(hidden) + " is refused";
+            return -1;
+        }
+        if (mode != pendulum::AC_CONTINUOUS && mode != pendulum::AC_UNIFORM) {
+            g_create_error = "dne_create: DNE_KIND_PENDULUM has action modes 0 (continuous) and 1 (uniform bins); mode " + std::to_string(mode) + " is refused";
+            return -1;
+        }
+        if (nl != pendulum::NL_TANH && nl != pendulum::NL_RELU) {
+            g_create_error = "dne_create: DNE_KIND_PENDULUM has nonlinearities 0 (tanh) and 1 (relu); nonlinearity " + std::to_string(nl) + " is refused";
+            return -1;
+        }
+        if (mode == pendulum::AC_CONTINUOUS ? cfg->n_actions != 1 : (cfg->n_actions < 2 || cfg->n_actions > pendulum::MAX_OUT)) {
+            g_create_error = "dne_create: DNE_KIND_PENDULUM has 1 output under the continuous action and 2..16 under uniform bins, n_actions " +
+                             std::to_string(cfg->n_actions) + " under mode " + std::to_string(mode) + " is refused";
+            return -1;
+        }
+        if (cfg->bc_final_only || cfg->record_bc) {
+            g_create_error = "dne_create: record_bc / bc_final_only are not available on a DNE_KIND_PENDULUM engine (kind 6): it records no behaviour; "
+                             "dne_pendulum_final_state has the final state of every member";
+            return -1;
+        }
+    }
     dne_handle *h = new dne_handle();
     h->cfg = *cfg;
     auto bail = [&](int) { g_create_error = h->err; delete h; return -1; };
@@ -1087,12 +1130,19 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         env_int("DNE_STAGED_COPY", 0, 1, &sc);
         h->staged_copies = sc != 0;
     }
-    if (cfg->policy_kind == DNE_KIND_MAZE || cfg->policy_kind == DNE_KIND_CARTPOLE) {
+    if (cfg->policy_kind == DNE_KIND_MAZE || cfg->policy_kind == DNE_KIND_CARTPOLE || cfg->policy_kind == DNE_KIND_PENDULUM) {
         // theta slots, member descriptors and accumulators, the walls (the cart-pole: seeds and final states), the reduce and optimizer
         // buffers: no frame, activation or ring buffer
         h->maze = cfg->policy_kind == DNE_KIND_MAZE;
-        h->cartpole = !h->maze;
+        h->cartpole = cfg->policy_kind == DNE_KIND_CARTPOLE;
+        h->pendulum = cfg->policy_kind == DNE_KIND_PENDULUM;
         make_layout(cfg->policy_kind, cfg->n_actions, &h->L);
+        if (h->pendulum) {
+            h->pd_hidden = cfg->reserved[0]; h->pd_nl = cfg->reserved[2];
+            h->pd_opt.n_out = cfg->n_actions; h->pd_opt.ac_mode = cfg->reserved[1];
+            for (int i = 0; i < pendulum::OBS; i++) h->pd_opt.mean[i] = h->pd_opt.std[i] = NAN;   // policies.py:138-141
+            h->L.P = pendulum::offsets(h->pd_hidden, cfg->n_actions).P;
+        }
         h->M = cfg->max_members;
         h->base_stride = ((size_t)h->L.P + 63) / 64 * 64;
         const size_t M = h->M;
@@ -1108,9 +1158,16 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         if (h->maze) {
             CH(h->alloc(&h->maze_xy, 2 * M, "maze_xy")); CH(h->alloc(&h->maze_walls, maze::MAX_WALLS * 4, "maze_walls"));
             CH(hipMemset(h->maze_xy, 0, 2 * M * sizeof(float)));
-        } else {
+        } else if (h->cartpole) {
             CH(h->alloc(&h->cp_state, 4 * M, "cartpole_state")); CH(h->alloc(&h->seeds, M, "seeds"));
             CH(hipMemset(h->cp_state, 0, 4 * M * sizeof(double))); CH(hipMemset(h->seeds, 0, M * sizeof(uint32_t)));
+        } else {
+            CH(h->alloc(&h->pd_state, 2 * M, "pendulum_state")); CH(h->alloc(&h->seeds, M, "seeds"));
+            CH(h->alloc(&h->pd_sum, 3 * M, "pendulum_ob_sum")); CH(h->alloc(&h->pd_sumsq, 3 * M, "pendulum_ob_sumsq")); CH(h->alloc(&h->pd_count, M, "pendulum_ob_count"));
+            CH(h->alloc(&h->pd_acoff, M, "pendulum_ac_off")); CH(h->alloc(&h->pd_flag, M, "pendulum_stat_flag"));
+            CH(hipMemset(h->pd_state, 0, 2 * M * sizeof(double))); CH(hipMemset(h->seeds, 0, M * sizeof(uint32_t)));
+            CH(hipMemset(h->pd_sum, 0, 3 * M * sizeof(double))); CH(hipMemset(h->pd_sumsq, 0, 3 * M * sizeof(double))); CH(hipMemset(h->pd_count, 0, M * sizeof(int32_t)));
+            CH(hipMemset(h->pd_acoff, 0xff, M * sizeof(int64_t))); CH(hipMemset(h->pd_flag, 0, M));
         }
         if (h->maze && cfg->record_bc) {   // behaviour: the navigator's (x, y) after every step, [member][bc_max_steps][2] floats
             h->bc_bytes = M * (size_t)std::max(cfg->bc_max_steps, 1) * 2 * sizeof(float);
@@ -1121,7 +1178,7 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         CH(h->alloc(&h->scratch_f, h->scratch_cap, "scratch_f")); CH(h->alloc(&h->scratch_i, h->scratch_cap, "scratch_i"));
         CH(hipEventCreate(&h->ev_a)); CH(hipEventCreate(&h->ev_b));
         CH(hipDeviceSynchronize());
-        h->trace("engine created: kind %d (%s), %d members, %zu device buffers", cfg->policy_kind, h->maze ? "hard maze" : "cart-pole", h->M, h->blocks.size());
+        h->trace("engine created: kind %d (%s), %d members, %zu device buffers", cfg->policy_kind, h->maze ? "hard maze" : h->cartpole ? "cart-pole" : "pendulum", h->M, h->blocks.size());
         *out = h;
         return 0;
     }
@@ -2779,6 +2836,257 @@ extern "C" int dne_cartpole_forward_host(const float *theta, const float *obs, i
     return 0;
 }
 
+// ------------------------------------------------------------------------------- MujocoPolicy on the pendulum (csrc/pendulum.h)
+static int needs_pendulum(dne_handle *h, const char *call) {
+    return h->pendulum ? 0 : h->fail("%s needs a DNE_KIND_PENDULUM engine (this one: kind %d)", call, h->L.kind);
+}
+
+extern "C" int dne_pendulum_num_params(int hidden, int n_out) {
+    if (!pendulum::hidden_ok(hidden) || n_out < 1 || n_out > pendulum::MAX_OUT) return -1;
+    return pendulum::offsets(hidden, n_out).P;
+}
+
+// what k_pendulum_rollout reads for the members [first, first + count) set by dne_set_members; options and outputs are left null
+static pendulum::RolloutArgs pendulum_args(dne_handle *h, int first, int count, int tslimit) {
+    pendulum::RolloutArgs A{};
+    A.noise = h->noise; A.bases = h->bases; A.base_stride = h->base_stride;
+    A.m_slot = h->m_slot; A.m_off = h->m_off; A.m_scale = h->m_scale;
+    A.first = first; A.count = count; A.seed = h->seeds; A.tslimit = tslimit;
+    A.opt = h->pd_opt;
+    return A;
+}
+
+static void pendulum_launch(dne_handle *h, const pendulum::RolloutArgs &A) {
+    const dim3 grid(A.count);
+    const bool th = h->pd_nl == pendulum::NL_TANH;
+    switch (h->pd_hidden) {
+    case 64:
+        if (th) hipLaunchKernelGGL((pendulum::k_pendulum_rollout<64, true>), grid, dim3(64), 0, h->stream, A);
+        else hipLaunchKernelGGL((pendulum::k_pendulum_rollout<64, false>), grid, dim3(64), 0, h->stream, A);
+        break;
+    case 128:
+        if (th) hipLaunchKernelGGL((pendulum::k_pendulum_rollout<128, true>), grid, dim3(128), 0, h->stream, A);
+        else hipLaunchKernelGGL((pendulum::k_pendulum_rollout<128, false>), grid, dim3(128), 0, h->stream, A);
+        break;
+    default:
+        if (th) hipLaunchKernelGGL((pendulum::k_pendulum_rollout<256, true>), grid, dim3(256), 0, h->stream, A);
+        else hipLaunchKernelGGL((pendulum::k_pendulum_rollout<256, false>), grid, dim3(256), 0, h->stream, A);
+    }
+}
+
+extern "C" int dne_pendulum_set_ob_stat(dne_handle *h, const float *mean, const float *std) {
+    DeviceGuard dg(h);
+    if (needs_pendulum(h, "dne_pendulum_set_ob_stat")) return -1;
+    if (!mean || !std) return h->fail("dne_pendulum_set_ob_stat: bad arguments");
+    for (int i = 0; i < pendulum::OBS; i++) { h->pd_opt.mean[i] = mean[i]; h->pd_opt.std[i] = std[i]; }
+    h->pd_stat_set = true;
+    return 0;
+}
+
+// action noise and observation statistics of the NEXT evaluation's first n members (later members: neither); that evaluation clears them
+extern "C" int dne_pendulum_set_rollout_options(dne_handle *h, int n, float ac_noise_std, const int64_t *ac_off, const uint8_t *stat_flag) {
+    DeviceGuard dg(h);
+    if (needs_pendulum(h, "dne_pendulum_set_rollout_options")) return -1;
+    if (check_n(h, n)) return -1;
+    if (!h->noise && ac_off) return h->fail("noise table not uploaded (dne_noise_upload)");
+    if (ac_off)
+        for (int i = 0; i < n; i++)
+            if (ac_off[i] >= 0 && (uint64_t)ac_off[i] + pendulum::EPISODE_STEPS > (uint64_t)h->noise_count)
+                return h->fail("dne_pendulum_set_rollout_options: member %d reads its %d action-noise values from offset %lld, past the noise table's %zu values",
+                               i, pendulum::EPISODE_STEPS, (long long)ac_off[i], (size_t)h->noise_count);
+    h->pd_has_off = ac_off != nullptr; h->pd_has_flag = stat_flag != nullptr;
+    if (ac_off) h->pd_host_off.assign(ac_off, ac_off + n); else h->pd_host_off.clear();
+    if (ac_off) HCHECK(h, hipMemcpyAsync(h->pd_acoff, ac_off, n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    if (stat_flag) HCHECK(h, hipMemcpyAsync(h->pd_flag, stat_flag, n, hipMemcpyHostToDevice, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    h->pd_opt.ac_noise_std = ac_noise_std;
+    h->pd_opt_n = n;
+    return 0;
+}
+
+// members [0, n), one whole episode each under its own reset seed, one launch
+static int pendulum_eval(dne_handle *h, const char *call, int n, int tslimit, const uint32_t *env_seed, float *returns, float *signreturns,
+                         int32_t *lengths, uint8_t *bc_out) {
+    if (bc_out) return h->fail("%s: behaviour characterisations are not available on a DNE_KIND_PENDULUM engine (kind %d): bc must be NULL; "
+                               "dne_pendulum_final_state has the final state of every member", call, DNE_KIND_PENDULUM);
+    if (tslimit <= 0) return h->fail("timestep limit must be positive");
+    if (!env_seed) return h->fail("%s: a DNE_KIND_PENDULUM engine resets every member from its environment seed, env_seed is NULL", call);
+    if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
+    if (!h->pd_stat_set) return h->fail("%s: the observation statistics of a DNE_KIND_PENDULUM engine are NaN until dne_pendulum_set_ob_stat is called", call);
+    const bool has_off = h->pd_has_off, has_flag = h->pd_has_flag;
+    if ((has_off || has_flag) && h->pd_opt_n != n)
+        return h->fail("%s: dne_pendulum_set_rollout_options was given %d members, this evaluation runs %d", call, h->pd_opt_n, n);
+    if (has_off)   // the table may have been replaced since the options were set
+        for (int i = 0; i < n; i++)
+            if (h->pd_host_off[i] >= 0 && (uint64_t)h->pd_host_off[i] + pendulum::EPISODE_STEPS > (uint64_t)h->noise_count)
+                return h->fail("%s: member %d reads its action noise from offset %lld, past the noise table's %zu values", call, i, (long long)h->pd_host_off[i], (size_t)h->noise_count);
+    HCHECK(h, hipMemcpyAsync(h->seeds, env_seed, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    pendulum::RolloutArgs A = pendulum_args(h, 0, n, tslimit);
+    A.ac_off = has_off ? h->pd_acoff : nullptr; A.stat_flag = has_flag ? h->pd_flag : nullptr;
+    A.ret = h->ret; A.sign = h->sign; A.len = h->len; A.state = h->pd_state;
+    A.ob_sum = h->pd_sum; A.ob_sumsq = h->pd_sumsq; A.ob_count = h->pd_count;
+    h->pd_has_off = h->pd_has_flag = false; h->pd_opt_n = 0; h->pd_opt.ac_noise_std = 0.0f;   // the options were for this evaluation only
+    HCHECK(h, hipEventRecord(h->ev_a, h->stream));
+    pendulum_launch(h, A);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipEventRecord(h->ev_b, h->stream));
+    HCHECK(h, hipMemcpyAsync(returns, h->ret, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (signreturns) HCHECK(h, hipMemcpyAsync(signreturns, h->sign, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipMemcpyAsync(lengths, h->len, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    h->pd_last_n = n;
+    float ms = 0;
+    HCHECK(h, hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
+    dne_profile &P = h->prof;
+    P = dne_profile{};
+    P.eval_ms = P.env_ms = ms;
+    P.fc_launches = 1;
+    for (int i = 0; i < n; i++) P.env_steps += lengths[i];
+    return 0;
+}
+
+extern "C" int dne_pendulum_ob_stats(dne_handle *h, int n, double *sum, double *sumsq, int32_t *count) {
+    DeviceGuard dg(h);
+    if (needs_pendulum(h, "dne_pendulum_ob_stats")) return -1;
+    if (n < 1 || n > h->pd_last_n) return h->fail("dne_pendulum_ob_stats: %d members asked for, the last evaluation ran %d", n, h->pd_last_n);
+    if (!sum || !sumsq || !count) return h->fail("dne_pendulum_ob_stats: no output buffer");
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(sum, h->pd_sum, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    HCHECK(h, hipMemcpy(sumsq, h->pd_sumsq, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    HCHECK(h, hipMemcpy(count, h->pd_count, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int dne_pendulum_final_state(dne_handle *h, int n, double *state) {
+    DeviceGuard dg(h);
+    if (needs_pendulum(h, "dne_pendulum_final_state")) return -1;
+    if (n < 1 || n > h->pd_last_n) return h->fail("dne_pendulum_final_state: %d members asked for, the last evaluation ran %d", n, h->pd_last_n);
+    if (!state) return h->fail("dne_pendulum_final_state: no output buffer");
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(state, h->pd_state, (size_t)n * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the kernel once more for ONE of the current members, with every step written out: trace [min(tslimit, 200)][8] as dne_pendulum_rollout_host
+// writes it; no action noise, no statistics.  The accumulators of the last evaluation are left alone.
+extern "C" int dne_pendulum_debug_trace(dne_handle *h, int member, int tslimit, const double *init2, double *trace, int32_t *steps) {
+    DeviceGuard dg(h);
+    if (needs_pendulum(h, "dne_pendulum_debug_trace")) return -1;
+    if (member < 0 || member >= (int)h->host_slot.size()) return h->fail("dne_pendulum_debug_trace: member %d, dne_set_members set %zu", member, h->host_slot.size());
+    if (tslimit <= 0 || !trace || !steps) return h->fail("dne_pendulum_debug_trace: bad arguments");
+    if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
+    if (!h->pd_stat_set) return h->fail("dne_pendulum_debug_trace: the observation statistics of a DNE_KIND_PENDULUM engine are NaN until dne_pendulum_set_ob_stat is called");
+    const int cap = std::min(tslimit, (int)pendulum::EPISODE_STEPS);
+    DevBuf<double> d;
+    DevBuf<int32_t> dn;
+    HCHECK(h, d.alloc((size_t)cap * pendulum::TRACE_W));
+    HCHECK(h, dn.alloc(1));
+    pendulum::RolloutArgs A = pendulum_args(h, member, 1, tslimit);
+    A.opt.ac_noise_std = 0.0f;
+    if (init2) { A.has_init = 1; A.init2[0] = init2[0]; A.init2[1] = init2[1]; }
+    A.trace = d; A.trace_steps = dn;
+    pendulum_launch(h, A);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(steps, dn, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (*steps < 0 || *steps > cap) return h->fail("dne_pendulum_debug_trace: the kernel reports %d steps under a limit of %d", *steps, cap);
+    HCHECK(h, hipMemcpy(trace, d, (size_t)*steps * pendulum::TRACE_W * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// tanh_f, norm_angle and the normalise-and-clip of one component, value by value on the device (fn: pendulum.h's MATH_*; a, b: mean and std of fn 2)
+extern "C" int dne_pendulum_debug_math(dne_handle *h, int fn, const double *x, int n, float a, float b, double *out) {
+    DeviceGuard dg(h);
+    if (needs_pendulum(h, "dne_pendulum_debug_math")) return -1;
+    if (fn < 0 || fn >= pendulum::MATH_FNS || n < 1 || !x || !out) return h->fail("dne_pendulum_debug_math: bad arguments");
+    DevBuf<double> dx, dy;
+    HCHECK(h, dx.alloc(n)); HCHECK(h, dy.alloc(n));
+    HCHECK(h, hipMemcpy(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(pendulum::k_pendulum_math, dim3((n + 255) / 256), dim3(256), 0, h->stream, fn, (const double *)dx, n, a, b, (double *)dy);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(out, dy, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the same header on the CPU: no handle, no GPU
+extern "C" int dne_pendulum_reset_host(uint32_t seed, double *out2) {
+    if (!out2) { g_create_error = "dne_pendulum_reset_host: no output buffer"; return -1; }
+    const pendulum::State s = pendulum::reset_state(seed);
+    out2[0] = s.theta; out2[1] = s.theta_dot;
+    return 0;
+}
+
+static int pendulum_shape_host(const char *call, int hidden, int n_out, int ac_mode, int nonlin) {
+    if (!pendulum::hidden_ok(hidden) || (nonlin != pendulum::NL_TANH && nonlin != pendulum::NL_RELU) ||
+        (ac_mode == pendulum::AC_CONTINUOUS ? n_out != 1 : (ac_mode != pendulum::AC_UNIFORM || n_out < 2 || n_out > pendulum::MAX_OUT))) {
+        g_create_error = std::string(call) + ": hidden width " + std::to_string(hidden) + ", " + std::to_string(n_out) + " outputs, action mode " +
+                         std::to_string(ac_mode) + ", nonlinearity " + std::to_string(nonlin) + " is not a shape csrc/pendulum.h builds";
+        return -1;
+    }
+    return 0;
+}
+
+// one episode for each of n thetas [n][P] under seeds [n] (init2 [n][2] or NULL).  table / ac_off [n] (both or neither; an offset < 0: no noise for
+// that member), stat_flag [n] or NULL: as the device call's options.  Outputs as the kernel writes them; trace [n][tslimit][8] or NULL.
+extern "C" int dne_pendulum_rollout_host(const float *theta, int n, int hidden, int n_out, int ac_mode, int nonlin, const float *mean, const float *std,
+                                         const uint32_t *seeds, const double *init2, int tslimit, float ac_noise_std, const float *table, size_t table_len,
+                                         const int64_t *ac_off, const uint8_t *stat_flag, float *returns, float *signreturns, int32_t *lengths,
+                                         double *state, double *ob_sum, double *ob_sumsq, int32_t *ob_count, double *trace) {
+    if (n < 1 || tslimit <= 0 || !theta || !mean || !std || !seeds || !returns || !signreturns || !lengths || !state || !ob_sum || !ob_sumsq || !ob_count ||
+        (ac_off != nullptr) != (table != nullptr)) { g_create_error = "dne_pendulum_rollout_host: bad arguments"; return -1; }
+    if (pendulum_shape_host("dne_pendulum_rollout_host", hidden, n_out, ac_mode, nonlin)) return -1;
+    pendulum::Options o{};
+    o.n_out = n_out; o.ac_mode = ac_mode; o.ac_noise_std = ac_noise_std;
+    for (int i = 0; i < pendulum::OBS; i++) { o.mean[i] = mean[i]; o.std[i] = std[i]; }
+    const size_t P = pendulum::offsets(hidden, n_out).P;
+    if (ac_off)
+        for (int i = 0; i < n; i++)
+            if (ac_off[i] >= 0 && (uint64_t)ac_off[i] + pendulum::EPISODE_STEPS > (uint64_t)table_len) {
+                g_create_error = "dne_pendulum_rollout_host: member " + std::to_string(i) + " reads its action noise from offset " + std::to_string(ac_off[i]) +
+                                 ", past the noise table's " + std::to_string(table_len) + " values";
+                return -1;
+            }
+    for (int i = 0; i < n; i++) {
+        const bool stat = stat_flag && stat_flag[i];
+        const pendulum::Episode e = pendulum::rollout_host(hidden, nonlin, theta + (size_t)i * P, o, seeds[i], init2 ? init2 + 2 * (size_t)i : nullptr, tslimit,
+                                                           ac_off && ac_off[i] >= 0 ? table + ac_off[i] : nullptr, stat,
+                                                           trace ? trace + (size_t)i * tslimit * pendulum::TRACE_W : nullptr);
+        returns[i] = e.ret; signreturns[i] = e.sign; lengths[i] = e.len;
+        state[2 * (size_t)i] = e.s.theta; state[2 * (size_t)i + 1] = e.s.theta_dot;
+        for (int c = 0; c < pendulum::OBS; c++) { ob_sum[3 * (size_t)i + c] = e.ob_sum[c]; ob_sumsq[3 * (size_t)i + c] = e.ob_sumsq[c]; }
+        ob_count[i] = stat ? e.len : 0;
+    }
+    return 0;
+}
+
+extern "C" int dne_pendulum_actions_host(const float *actions, int n, int T, const double *init2, double *rows) {
+    if (n < 1 || T < 1 || !actions || !init2 || !rows) { g_create_error = "dne_pendulum_actions_host: bad arguments"; return -1; }
+    for (int i = 0; i < n; i++) pendulum::actions_host(actions + (size_t)i * T, T, init2 + 2 * (size_t)i, rows + (size_t)i * T * 3);
+    return 0;
+}
+
+// the policy alone: thetas [n][P] on raw observations [n][3] -> x [n][3] (normalised and clipped), h1 [n][H], h2 [n][H], out [n][n_out], action [n]
+extern "C" int dne_pendulum_forward_host(const float *theta, const float *obs, int n, int hidden, int n_out, int ac_mode, int nonlin, const float *mean,
+                                         const float *std, float *x, float *h1, float *h2, float *out, float *action) {
+    if (n < 1 || !theta || !obs || !mean || !std || !x || !h1 || !h2 || !out || !action) { g_create_error = "dne_pendulum_forward_host: bad arguments"; return -1; }
+    if (pendulum_shape_host("dne_pendulum_forward_host", hidden, n_out, ac_mode, nonlin)) return -1;
+    pendulum::Options o{};
+    o.n_out = n_out; o.ac_mode = ac_mode;
+    for (int i = 0; i < pendulum::OBS; i++) { o.mean[i] = mean[i]; o.std[i] = std[i]; }
+    const size_t P = pendulum::offsets(hidden, n_out).P;
+    for (int i = 0; i < n; i++)
+        action[i] = pendulum::forward_host(hidden, nonlin, theta + (size_t)i * P, o, obs + 3 * (size_t)i, x + 3 * (size_t)i, h1 + (size_t)i * hidden,
+                                           h2 + (size_t)i * hidden, out + (size_t)i * n_out);
+    return 0;
+}
+
+extern "C" int dne_pendulum_math_host(int fn, const double *x, int n, float a, float b, double *out) {
+    if (fn < 0 || fn >= pendulum::MATH_FNS || n < 1 || !x || !out) { g_create_error = "dne_pendulum_math_host: bad arguments"; return -1; }
+    for (int i = 0; i < n; i++) out[i] = pendulum::math_fn(fn, x[i], a, b);
+    return 0;
+}
+
 // ------------------------------------------------------------------------------- evaluations by descriptor: antithetic pairs, members as set
 extern "C" int dne_es_eval(dne_handle *h, const int64_t *idx, int n, float sigma, int tslimit, const uint32_t *env_seed,
                            float *returns_n2, float *signreturns_n2, int32_t *lengths_n2, uint8_t *bc) {
@@ -2805,6 +3113,7 @@ extern "C" int dne_es_eval(dne_handle *h, const int64_t *idx, int n, float sigma
     }
     if (h->maze) return maze_eval(h, 2 * n, tslimit, returns_n2, signreturns_n2, lengths_n2, bc);   // (the episode is deterministic: env_seed is not read)
     if (h->cartpole) return cartpole_eval(h, "dne_es_eval", 2 * n, tslimit, env_seed, returns_n2, signreturns_n2, lengths_n2, bc);
+    if (h->pendulum) return pendulum_eval(h, "dne_es_eval", 2 * n, tslimit, env_seed, returns_n2, signreturns_n2, lengths_n2, bc);
     return eval_core(h, 2 * n, 2, tslimit, env_seed, returns_n2, signreturns_n2, lengths_n2, bc);
 }
 
@@ -2819,6 +3128,10 @@ extern "C" int dne_eval_members(dne_handle *h, int n, int tslimit, const uint32_
     if (h->cartpole) {
         if ((int)h->host_slot.size() < n) return h->fail("dne_eval_members: %d members asked for, dne_set_members set %zu", n, h->host_slot.size());
         return cartpole_eval(h, "dne_eval_members", n, tslimit, env_seed, returns, signreturns, lengths, bc);
+    }
+    if (h->pendulum) {
+        if ((int)h->host_slot.size() < n) return h->fail("dne_eval_members: %d members asked for, dne_set_members set %zu", n, h->host_slot.size());
+        return pendulum_eval(h, "dne_eval_members", n, tslimit, env_seed, returns, signreturns, lengths, bc);
     }
     return eval_core(h, n, 1, tslimit, env_seed, returns, signreturns, lengths, bc);
 }

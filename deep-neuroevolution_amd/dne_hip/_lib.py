@@ -19,6 +19,11 @@ MAZE_OBS, MAZE_STEPS, MAZE_TRACE_W, MAZE_MAX_WALLS = 11, 400, 16, 64   # observa
 MAZE_NOVELTY_KMAX, MAZE_NOVELTY_TILE, MAZE_ARCHIVE_CAP0 = 32, 1024, 64   # csrc/maze_novelty.h: neighbours a lane keeps, archive points per LDS tile; the archive's first allocation (engine.hip)
 KIND_CARTPOLE = 5   # the GPU tree's gym configuration: gym.CartPole-v1 under SimpleClassifier on 4 inputs, whole episodes in one kernel (csrc/cartpole.h)
 CARTPOLE_OBS, CARTPOLE_STEPS, CARTPOLE_TRACE_W, CARTPOLE_P = 4, 500, 8, 386   # observation width, CartPole-v1's max_episode_steps, doubles per trace row, parameters
+KIND_PENDULUM = 6   # es_distributed's MujocoPolicy on the torque-limited pendulum swing-up, whole episodes in one kernel (csrc/pendulum.h)
+PENDULUM_OBS, PENDULUM_STEPS, PENDULUM_TRACE_W, PENDULUM_MAX_OUT = 3, 200, 8, 16   # observation width, Pendulum-v0's max_episode_steps, doubles per trace row, most bins
+PENDULUM_AC_MODES = {'continuous': 0, 'uniform': 1}   # dne_config.reserved[1]
+PENDULUM_NONLINS = {'tanh': 0, 'relu': 1}             # dne_config.reserved[2]
+PENDULUM_MATH = {'tanh': 0, 'norm': 1, 'normalise': 2}   # dne_pendulum_debug_math / _math_host
 ES_KINDS = (KIND_ES, KIND_ES_VBN)   # virtual batch norm over a reference batch, antithetic pairs
 PROC_MODES = {"centered_rank": 0, "sign": 1, "centered_sign_rank": 2}
 OPT_KINDS = {"adam": 0, "sgd": 1}
@@ -76,7 +81,7 @@ class Profile(C.Structure):
 
 def build(force=False):
     """Compile libdne_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h", "cartpole.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h", "cartpole.h", "pendulum.h")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dne_hip.h"))
     if os.environ.get("DNE_LIB_PATH"):
         # another build of the same ABI was asked for by name: `make` only knows the in-tree library, so running it here would
@@ -358,6 +363,108 @@ def cartpole_forward_host(theta, obs):
     return h1, h2, out
 
 
+def pendulum_num_params(hidden, n_out=1):
+    """dne_pendulum_num_params: P = 5 H + H^2 + H O + O (-1: a width or an output count csrc/pendulum.h does not build)"""
+    return load().dne_pendulum_num_params(int(hidden), int(n_out))
+
+
+def pendulum_reset_host(seed):
+    """dne_pendulum_reset_host: the reset state (theta, theta_dot) of one uint32 environment seed, float64 [2]"""
+    out = np.empty(2, np.float64)
+    _ck_host(load().dne_pendulum_reset_host(C.c_uint32(int(seed)), _ptr(out, C.c_double)))
+    return out
+
+
+def _pendulum_shape(hidden, n_out, ac_mode, nonlin):
+    return int(hidden), int(n_out), int(PENDULUM_AC_MODES.get(ac_mode, ac_mode)), int(PENDULUM_NONLINS.get(nonlin, nonlin))
+
+
+def pendulum_rollout_host(theta, seeds, hidden, mean, std, n_out=1, ac_mode='continuous', nonlin='tanh', tslimit=PENDULUM_STEPS, init=None,
+                          ac_noise_std=0.0, table=None, ac_off=None, stat_flag=None, want_trace=False):
+    """dne_pendulum_rollout_host: csrc/pendulum.h on the CPU (no GPU, no handle) for thetas [n][P] under environment seeds [n] (init [n][2]:
+    explicit initial states instead).  table / ac_off [n] (both or neither): the noise table and where each member's 200 action-noise values
+    start (< 0: none); stat_flag [n]: who accumulates its observations.  -> dict(returns, signreturns, lengths, state [n][2], ob_sum [n][3],
+    ob_sumsq [n][3], ob_count [n](, trace float64 [n][tslimit][8]: the three observations acted on, the net's action, the action applied,
+    the reward, theta and theta_dot after the step))"""
+    hidden, n_out, ac_mode, nonlin = _pendulum_shape(hidden, n_out, ac_mode, nonlin)
+    P = pendulum_num_params(hidden, n_out)
+    if P < 0:
+        raise DneError("pendulum_rollout_host: hidden width %d with %d outputs is not a shape csrc/pendulum.h builds" % (hidden, n_out))
+    theta = _arr(theta, np.float32).reshape(-1, P)
+    n = theta.shape[0]
+    seeds = _arr(seeds, np.uint32).reshape(-1)
+    if seeds.size != n:
+        raise DneError("pendulum_rollout_host: %d thetas, %d seeds" % (n, seeds.size))
+    mean = _arr(mean, np.float32).reshape(3); std = _arr(std, np.float32).reshape(3)
+    if init is not None:
+        init = _arr(init, np.float64).reshape(-1, 2)
+        if init.shape[0] != n:
+            raise DneError("pendulum_rollout_host: %d thetas, %d initial states" % (n, init.shape[0]))
+    if table is not None:
+        table = _arr(table, np.float32).reshape(-1)
+    if ac_off is not None:
+        ac_off = _arr(ac_off, np.int64).reshape(-1)
+        if ac_off.size != n:
+            raise DneError("pendulum_rollout_host: %d thetas, %d action-noise offsets" % (n, ac_off.size))
+    if stat_flag is not None:
+        stat_flag = _arr(stat_flag, np.uint8).reshape(-1)
+        if stat_flag.size != n:
+            raise DneError("pendulum_rollout_host: %d thetas, %d statistics flags" % (n, stat_flag.size))
+    r = dict(returns=np.empty(n, np.float32), signreturns=np.empty(n, np.float32), lengths=np.empty(n, np.int32), state=np.empty((n, 2), np.float64),
+             ob_sum=np.empty((n, 3), np.float64), ob_sumsq=np.empty((n, 3), np.float64), ob_count=np.empty(n, np.int32))
+    trace = np.zeros((n, int(tslimit), PENDULUM_TRACE_W), np.float64) if want_trace else None
+    _ck_host(load().dne_pendulum_rollout_host(
+        _ptr(theta, C.c_float), n, hidden, n_out, ac_mode, nonlin, _ptr(mean, C.c_float), _ptr(std, C.c_float), _ptr(seeds, C.c_uint32),
+        _ptr(init, C.c_double), int(tslimit), C.c_float(ac_noise_std), _ptr(table, C.c_float), C.c_size_t(0 if table is None else table.size),
+        _ptr(ac_off, C.c_int64), _ptr(stat_flag, C.c_uint8), _ptr(r['returns'], C.c_float), _ptr(r['signreturns'], C.c_float),
+        _ptr(r['lengths'], C.c_int32), _ptr(r['state'], C.c_double), _ptr(r['ob_sum'], C.c_double), _ptr(r['ob_sumsq'], C.c_double),
+        _ptr(r['ob_count'], C.c_int32), _ptr(trace, C.c_double)))
+    if want_trace:
+        r['trace'] = trace
+    return r
+
+
+def pendulum_actions_host(actions, init):
+    """dne_pendulum_actions_host: the environment alone under open-loop float actions [n][T] from initial states [n][2] -> rows float64
+    [n][T][3] = theta and theta_dot after each step, then the reward"""
+    actions = _arr(actions, np.float32); actions = actions.reshape(-1, actions.shape[-1])
+    n, T = actions.shape
+    init = _arr(init, np.float64).reshape(-1, 2)
+    if init.shape[0] != n:
+        raise DneError("pendulum_actions_host: %d sequences, %d initial states" % (n, init.shape[0]))
+    rows = np.empty((n, T, 3), np.float64)
+    _ck_host(load().dne_pendulum_actions_host(_ptr(actions, C.c_float), n, T, _ptr(init, C.c_double), _ptr(rows, C.c_double)))
+    return rows
+
+
+def pendulum_forward_host(theta, obs, hidden, mean, std, n_out=1, ac_mode='continuous', nonlin='tanh'):
+    """dne_pendulum_forward_host: the policy alone, thetas [n][P] on raw observations [n][3] -> (x [n][3] normalised and clipped, h1 [n][H],
+    h2 [n][H], out [n][O], action [n])"""
+    hidden, n_out, ac_mode, nonlin = _pendulum_shape(hidden, n_out, ac_mode, nonlin)
+    P = pendulum_num_params(hidden, n_out)
+    if P < 0:
+        raise DneError("pendulum_forward_host: hidden width %d with %d outputs is not a shape csrc/pendulum.h builds" % (hidden, n_out))
+    theta = _arr(theta, np.float32).reshape(-1, P); obs = _arr(obs, np.float32).reshape(-1, PENDULUM_OBS)
+    n = theta.shape[0]
+    if obs.shape[0] != n:
+        raise DneError("pendulum_forward_host: %d thetas, %d observations" % (n, obs.shape[0]))
+    mean = _arr(mean, np.float32).reshape(3); std = _arr(std, np.float32).reshape(3)
+    x = np.empty((n, 3), np.float32); h1 = np.empty((n, hidden), np.float32); h2 = np.empty((n, hidden), np.float32)
+    out = np.empty((n, n_out), np.float32); action = np.empty(n, np.float32)
+    _ck_host(load().dne_pendulum_forward_host(_ptr(theta, C.c_float), _ptr(obs, C.c_float), n, hidden, n_out, ac_mode, nonlin, _ptr(mean, C.c_float),
+                                              _ptr(std, C.c_float), _ptr(x, C.c_float), _ptr(h1, C.c_float), _ptr(h2, C.c_float), _ptr(out, C.c_float),
+                                              _ptr(action, C.c_float)))
+    return x, h1, h2, out, action
+
+
+def pendulum_math_host(fn, x, a=0.0, b=1.0):
+    """dne_pendulum_math_host: 'tanh' -> tanh_f(float32(x)), 'norm' -> norm_angle(x), 'normalise' -> clip((float32(x) - a) / b, -5, 5); float64 in and out"""
+    x = _arr(x, np.float64).reshape(-1)
+    out = np.empty(x.size, np.float64)
+    _ck_host(load().dne_pendulum_math_host(int(PENDULUM_MATH.get(fn, fn)), _ptr(x, C.c_double), int(x.size), C.c_float(a), C.c_float(b), _ptr(out, C.c_double)))
+    return out
+
+
 def _ptr(a, t):
     return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
 
@@ -373,7 +480,9 @@ class Engine:
     n_actions of them, and dne_create refuses a wider one (DneError)."""
 
     def __init__(self, kind, n_actions=18, max_members=256, ref_count=128, device_id=0, ref_chunk=0,
-                 record_bc=False, bc_max_steps=0, profile_events=False, bc_final_only=False):
+                 record_bc=False, bc_max_steps=0, profile_events=False, bc_final_only=False, hidden=0, ac_mode=0, nonlin=0):
+        """hidden, ac_mode, nonlin: the shape of a KIND_PENDULUM engine (hidden width 64 / 128 / 256; 'continuous' or 'uniform'; 'tanh' or 'relu'),
+        with n_actions the outputs (1, or the bins)"""
         self.lib = load()
         self.kind, self.n_actions, self.max_members = int(kind), int(n_actions), int(max_members)
         self.ref_count = int(ref_count) if kind in ES_KINDS else 0
@@ -382,12 +491,17 @@ class Engine:
                      ref_count=self.ref_count, ref_chunk=ref_chunk, record_bc=int(bool(record_bc)),
                      bc_max_steps=self.bc_max_steps, profile_events=int(bool(profile_events)),
                      bc_final_only=int(bool(bc_final_only)))
+        self.hidden = int(hidden)
+        if self.kind == KIND_PENDULUM:
+            self.ac_mode, self.nonlin = int(PENDULUM_AC_MODES.get(ac_mode, ac_mode)), int(PENDULUM_NONLINS.get(nonlin, nonlin))
+            cfg.reserved[0], cfg.reserved[1], cfg.reserved[2] = self.hidden, self.ac_mode, self.nonlin
         self.bc_final_only = bool(bc_final_only)
         self.h = C.c_void_p()
         rc = self.lib.dne_create(C.byref(cfg), C.byref(self.h))
         if rc != 0:
             raise DneError(self.lib.dne_last_error(None).decode())
-        self.P = self.lib.dne_num_params(self.kind, self.n_actions)
+        self.P = self.lib.dne_pendulum_num_params(self.hidden, self.n_actions) if self.kind == KIND_PENDULUM else \
+            self.lib.dne_num_params(self.kind, self.n_actions)
         self.record_bc = bool(record_bc)
         self.noise_count = 0
         self._last_eval_n = 0   # members of the last es_eval / eval_members (what the maze's xy=None forms score or append by default)
@@ -609,6 +723,51 @@ class Engine:
         x = _arr(x, np.float64).reshape(-1)
         out = np.empty((x.size, 2), np.float64)
         self._ck(self.lib.dne_maze_debug_math(self.h, int(fn), _ptr(x, C.c_double), int(x.size), _ptr(out, C.c_double)))
+        return out
+
+    # ---- MujocoPolicy on the pendulum (KIND_PENDULUM)
+    def pendulum_set_ob_stat(self, mean, std):
+        mean = _arr(mean, np.float32).reshape(3); std = _arr(std, np.float32).reshape(3)
+        self._ck(self.lib.dne_pendulum_set_ob_stat(self.h, _ptr(mean, C.c_float), _ptr(std, C.c_float)))
+
+    def pendulum_set_rollout_options(self, n, ac_noise_std=0.0, ac_off=None, stat_flag=None):
+        """for the next evaluation only (it must run n members): ac_off int64 [n] -- where each member's 200 action-noise values start in the
+        noise table, < 0 for none -- and stat_flag uint8 [n] -- who accumulates the observations it acts on"""
+        if ac_off is not None:
+            ac_off = _arr(ac_off, np.int64).reshape(-1)
+        if stat_flag is not None:
+            stat_flag = _arr(stat_flag, np.uint8).reshape(-1)
+        for a in (ac_off, stat_flag):
+            if a is not None and a.size != int(n):
+                raise DneError("pendulum_set_rollout_options: %d members, %d values" % (int(n), a.size))
+        self._ck(self.lib.dne_pendulum_set_rollout_options(self.h, int(n), C.c_float(ac_noise_std), _ptr(ac_off, C.c_int64), _ptr(stat_flag, C.c_uint8)))
+
+    def pendulum_ob_stats(self, n):
+        """(sum float64 [n][3], sumsq float64 [n][3], count int32 [n]) of the last evaluation's first n members"""
+        s = np.empty((int(n), 3), np.float64); q = np.empty((int(n), 3), np.float64); c = np.empty(int(n), np.int32)
+        self._ck(self.lib.dne_pendulum_ob_stats(self.h, int(n), _ptr(s, C.c_double), _ptr(q, C.c_double), _ptr(c, C.c_int32)))
+        return s, q, c
+
+    def pendulum_final_state(self, n):
+        """final (theta, theta_dot) of the last evaluation's first n members, float64 [n][2]"""
+        state = np.empty((int(n), 2), np.float64)
+        self._ck(self.lib.dne_pendulum_final_state(self.h, int(n), _ptr(state, C.c_double)))
+        return state
+
+    def pendulum_debug_trace(self, member, tslimit=PENDULUM_STEPS, init=None):
+        """the kernel once more for one current member, every step written out: float64 [steps][8] as pendulum_rollout_host's trace"""
+        out = np.zeros((min(int(tslimit), PENDULUM_STEPS), PENDULUM_TRACE_W), np.float64)
+        steps = C.c_int32(0)
+        init = None if init is None else _arr(init, np.float64).reshape(2)
+        self._ck(self.lib.dne_pendulum_debug_trace(self.h, int(member), int(tslimit), _ptr(init, C.c_double), _ptr(out, C.c_double), C.byref(steps)))
+        return out[:steps.value]
+
+    def pendulum_debug_math(self, fn, x, a=0.0, b=1.0):
+        """pendulum_math_host on the device"""
+        x = _arr(x, np.float64).reshape(-1)
+        out = np.empty(x.size, np.float64)
+        self._ck(self.lib.dne_pendulum_debug_math(self.h, int(PENDULUM_MATH.get(fn, fn)), _ptr(x, C.c_double), int(x.size), C.c_float(a), C.c_float(b),
+                                                  _ptr(out, C.c_double)))
         return out
 
     # ---- gym.CartPole-v1 (KIND_CARTPOLE)

@@ -29,6 +29,33 @@ from .compat import Config, Result, Task   # noqa: E402,F401
 RECORD = _lib.RECORD
 
 
+class RunningStat(object):
+    """es.py:26-48: the master's running observation statistics (float32 sum / sumsq, a float count starting at eps)"""
+
+    def __init__(self, shape, eps):
+        self.sum = np.zeros(shape, dtype=np.float32)
+        self.sumsq = np.full(shape, eps, dtype=np.float32)
+        self.count = eps
+
+    def increment(self, s, ssq, c):
+        self.sum += s
+        self.sumsq += ssq
+        self.count += c
+
+    @property
+    def mean(self):
+        return self.sum / self.count
+
+    @property
+    def std(self):
+        return np.sqrt(np.maximum(self.sumsq / self.count - np.square(self.mean), 1e-2))
+
+    def set_from_init(self, init_mean, init_std, init_count):
+        self.sum[:] = init_mean * init_count
+        self.sumsq[:] = (np.square(init_mean) + np.square(init_std)) * init_count
+        self.count = init_count
+
+
 class SharedNoiseTable(object):
     """es.py:51-67.  Same stream (RandomState(seed).randn, float64 -> float32), same get / sample_index; the
     table additionally lives as one device buffer once attach()ed to an engine."""
@@ -186,6 +213,9 @@ def es_generation(engine, noise_len, config, n_pairs, generation, tslimit, optim
 
 # ---------------------------------------------------------------------------------------------- drivers
 def make_engine(exp, n_pairs, n_actions=18, device_id=0, ref_count=128, **kw):
+    if exp['policy']['type'] == 'MujocoPolicy':           # the pendulum kind, in the shape the policy's arguments ask for
+        from . import pendulum_run
+        return pendulum_run.open_engine(exp, None, max(2 * n_pairs, 2), device_id=device_id)
     kind = {'ESAtariPolicy': _lib.KIND_ES, 'GAAtariPolicy': _lib.KIND_GA}[exp['policy']['type']]
     return _lib.Engine(kind, n_actions, max_members=max(2 * n_pairs, 2), ref_count=ref_count, device_id=device_id, **kw)
 
@@ -196,7 +226,12 @@ def setup(exp, engine=None, n_pairs=None, device_id=0):
     config = Config(**exp['config'])
     if engine is None:
         engine = make_engine(exp, n_pairs or max(config.episodes_per_batch // 2, 1), device_id=device_id)
-    env = policies.HipAtariEnv(engine)
+    if exp['policy']['type'] == 'MujocoPolicy':
+        from . import pendulum_run
+        pendulum_run.open_engine(exp, engine, 0)          # (the caller's engine: env_id and kind are checked)
+        env = policies.PendulumEnv(engine)
+    else:
+        env = policies.HipAtariEnv(engine)
     policy = getattr(policies, exp['policy']['type'])(env.observation_space, env.action_space, engine=engine,
                                                       **exp['policy']['args'])
     return config, env, policy
@@ -287,6 +322,7 @@ def run_master(master_redis_cfg, log_dir, exp, *, engine=None, noise=None, max_i
         policy.set_ref_batch(get_ref_batch(env, batch_size=engine.ref_count, random_stream=np.random.RandomState(seed)))
     tslimit, grow_thresh, grow_ratio, tslimit_max, adaptive = parse_cutoff(config.episode_cutoff_mode)
     episodes_so_far = timesteps_so_far = 0
+    ob_stat = RunningStat(env.observation_space.shape, eps=1e-2) if policy.needs_ob_stat else None   # es.py:157: eps to prevent dividing by zero at the beginning
     tstart = time.time()
     master.declare_experiment(exp)
     it = 0
@@ -295,7 +331,8 @@ def run_master(master_redis_cfg, log_dir, exp, *, engine=None, noise=None, max_i
         t0 = time.time()
         theta = policy.get_trainable_flat()
         assert theta.dtype == np.float32
-        task_id = master.declare_task(Task(params=theta, ob_mean=None, ob_std=None, timestep_limit=tslimit,
+        task_id = master.declare_task(Task(params=theta, ob_mean=ob_stat.mean if policy.needs_ob_stat else None,
+                                           ob_std=ob_stat.std if policy.needs_ob_stat else None, timestep_limit=tslimit,
                                            ref_batch=policy.ref_batch if policy.needs_ref_batch else None))
         tlogger.log('********** Iteration {} **********'.format(task_id))
         batch = collect_batch(master, config, task_id, result_type=result_type)
@@ -309,6 +346,13 @@ def run_master(master_redis_cfg, log_dir, exp, *, engine=None, noise=None, max_i
         # es.py:281-301 on the device: process returns, sum_i w_i * noise[idx_i], g /= 2N, -g + l2*theta, step
         update_ratio = engine.es_update(noise_inds_n, returns_n2, signreturns_n2, config.return_proc_mode, opt['type'],
                                         config.l2coeff, *optimizer_args(opt))
+        ob_count_this_batch = 0
+        if policy.needs_ob_stat:                          # es.py:261-263, 304-305
+            for r in batch.results:
+                if r.ob_count > 0:
+                    ob_stat.increment(r.ob_sum, r.ob_sumsq, r.ob_count)
+                    ob_count_this_batch += r.ob_count
+            policy.set_ob_stat(ob_stat.mean, ob_stat.std)
         if adaptive and (lengths_n2 == tslimit).mean() >= grow_thresh:      # es.py:308-311
             tslimit = min(int(grow_ratio * tslimit), tslimit_max)
         dt = time.time() - t0
@@ -321,7 +365,7 @@ def run_master(master_redis_cfg, log_dir, exp, *, engine=None, noise=None, max_i
             ("TimestepsThisIter", lengths_n2.sum()), ("TimestepsSoFar", timesteps_so_far),
             ("UniqueWorkers", len(set(batch.worker_ids))), ("ResultsSkippedFrac", batch.skipped_frac),
             ("TimeElapsedThisIter", dt), ("TimestepsPerSecondThisIter", lengths_n2.sum() / dt),
-            ("TimeElapsed", time.time() - tstart)])
+            ("TimeElapsed", time.time() - tstart)] + ([("ObCount", ob_count_this_batch)] if policy.needs_ob_stat else []))
         if config.snapshot_freq != 0 and task_id % config.snapshot_freq == 0:    # es.py:345-353
             import os.path as osp
             fn = osp.join(log_dir, ('snapshot_iter{:05d}_rew{}' + snapshot_extension()).format(task_id, int(np.mean(ev)) if ev else np.nan))
@@ -381,7 +425,8 @@ def run_worker(master_redis_cfg, relay_redis_cfg, noise, *, min_task_runtime=.2,
     noise.attach(engine)
     rs = np.random.RandomState(seed)
     worker_id = rs.randint(2 ** 31)
-    assert policy.needs_ob_stat == (config.calc_obstat_prob != 0)
+    # es.py:375 asserts equality; a policy that needs statistics may run with calc_obstat_prob 0 here (none are gathered: mean 0, deviation 1)
+    assert policy.needs_ob_stat or config.calc_obstat_prob == 0
     n_pairs = max(config.episodes_per_batch // 2, 1)
     pacer = TaskPacer(worker, max_tasks, reeval_after)
     while True:
@@ -390,24 +435,44 @@ def run_worker(master_redis_cfg, relay_redis_cfg, noise, *, min_task_runtime=.2,
             break
         task_id, task_data = nxt
         assert isinstance(task_id, int) and isinstance(task_data, Task)
+        if policy.needs_ob_stat:                          # es.py:382-383
+            policy.set_ob_stat(task_data.ob_mean, task_data.ob_std)
         if policy.needs_ref_batch:
             policy.set_ref_batch(task_data.ref_batch)
         policy.set_trainable_flat(task_data.params)
         tslimit = task_data.timestep_limit
-        tslimit = _lib.ENV_MAX_EPISODE_STEPS if tslimit is None else min(tslimit, _lib.ENV_MAX_EPISODE_STEPS)
+        env_steps = getattr(env, 'max_episode_steps', _lib.ENV_MAX_EPISODE_STEPS)   # the environment's own limit: Pendulum-v0's 200 on that kind
+        tslimit = env_steps if tslimit is None else min(tslimit, env_steps)
         if rs.rand() < config.eval_prob:
             # es.py:388-405: noiseless weights, reported separately, never part of the update; "eval rollouts don't obey
             # task_data.timestep_limit" (es.py:391) -- only the environment's own limit applies
             engine.set_members(np.zeros(1, np.int32), np.zeros(1, np.int64), np.zeros(1, np.float32))
-            er, _, el = engine.eval_members(1, _lib.ENV_MAX_EPISODE_STEPS, rs.randint(0, 2 ** 32, size=1, dtype=np.uint64).astype(np.uint32))
+            er, _, el = engine.eval_members(1, env_steps, rs.randint(0, 2 ** 32, size=1, dtype=np.uint64).astype(np.uint32))
             worker.push_result(task_id, Result(worker_id=worker_id, noise_inds_n=None, returns_n2=None,
                                                signreturns_n2=None, lengths_n2=None, eval_return=float(er[0]),
                                                eval_length=int(el[0]), ob_sum=None, ob_sumsq=None, ob_count=None))
         mine = shard_pairs(n_pairs, rank, world)
         noise_inds = np.sort(np.array([noise.sample_index(rs, policy.num_params) for _ in range(len(mine))], dtype=np.int64))   # table order: see generation_inputs
         seeds = rs.randint(0, 2 ** 32, size=2 * len(mine), dtype=np.uint64).astype(np.uint32)
+        ob_sum, ob_sumsq, ob_count = None, None, 0
+        if policy.needs_ob_stat:
+            # es.py:356-363: one coin per episode -- drawn only under needs_ob_stat and a non-zero probability, the reference's short-circuit,
+            # so every other policy's stream is what it was -- then where each episode's action noise starts in the table (the reference
+            # draws it step by step from random_stream.randn; the table is N(0, 1) as well)
+            n_eps = 2 * len(mine)
+            flags = (rs.rand(n_eps) < config.calc_obstat_prob) if config.calc_obstat_prob != 0 else np.zeros(n_eps, bool)
+            noisy = policy.ac_noise_std != 0
+            ac_off = rs.randint(0, len(noise.noise) - env_steps + 1, size=n_eps).astype(np.int64) if noisy else None
+            engine.pendulum_set_rollout_options(n_eps, policy.ac_noise_std if noisy else 0.0, ac_off, flags.astype(np.uint8))
         returns, signreturns, lengths = engine.es_eval(noise_inds, config.noise_stdev, tslimit, seeds)
+        if policy.needs_ob_stat and flags.any():          # es.py:436-438: the flagged episodes' sums, added in member order
+            s, q, c = engine.pendulum_ob_stats(n_eps)
+            acc_s, acc_q = np.zeros(s.shape[1], np.float64), np.zeros(s.shape[1], np.float64)
+            for i in np.flatnonzero(flags):
+                acc_s += s[i]
+                acc_q += q[i]
+            ob_sum, ob_sumsq, ob_count = acc_s.astype(np.float32), acc_q.astype(np.float32), int(c[flags].sum())
         worker.push_result(task_id, Result(
             worker_id=worker_id, noise_inds_n=noise_inds, returns_n2=returns, signreturns_n2=signreturns,
-            lengths_n2=lengths, eval_return=None, eval_length=None, ob_sum=None, ob_sumsq=None, ob_count=0))
+            lengths_n2=lengths, eval_return=None, eval_length=None, ob_sum=ob_sum, ob_sumsq=ob_sumsq, ob_count=ob_count))
         pacer.pushed(task_id)

@@ -25,6 +25,7 @@ from .compat import GATask  # ga.py:4  # noqa: E402
 def setup(exp, engine=None, n_children=None, device_id=0):
     """ga.py:7-20"""
     from . import policies
+    policies.refuse_mujoco(exp, 'ga')
     config = Config(**exp['config'])
     if engine is None:
         engine = _lib.Engine(_lib.KIND_GA, 18, max_members=max(n_children or config.episodes_per_batch, 1), device_id=device_id)

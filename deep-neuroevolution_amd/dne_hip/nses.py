@@ -49,6 +49,7 @@ def run_master(master_redis_cfg, log_dir, exp, *, engine=None, noise=None, max_i
     from . import policies, tabular_logger as tlogger
     logger.info('run_master: {}'.format(locals()))
     tlogger.start(log_dir)
+    policies.refuse_mujoco(exp, 'nses')
     config = Config(**exp['config'])
     algo_type = exp['algo_type']
     tslimit, incr_tslimit_threshold, tslimit_incr_ratio, tslimit_max, adaptive_tslimit = parse_cutoff(config.episode_cutoff_mode)

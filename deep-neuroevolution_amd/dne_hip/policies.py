@@ -243,7 +243,7 @@ class Policy:
         (h5lite.py; this image has the C library but not h5py).  Any other name: the same arrays, names and attributes in
         a numpy container, which tools/npz_to_h5.py turns into the .h5 (snapshot_extension() picks what the drivers use)."""
         arrays = self.variable_arrays()
-        blob = _dumps_spaces(tuple(self.ob_space_shape), self.num_actions, self.kwargs) if filename.endswith('.h5') else \
+        blob = self._spaces_blob() if filename.endswith('.h5') else \
             pickle.dumps((((tuple(self.ob_space_shape), self.num_actions)), self.kwargs), protocol=-1)
         if filename.endswith('.h5'):
             try:
@@ -265,6 +265,9 @@ class Policy:
             return
         np.savez(filename, __name__=type(self).__name__, __args_and_kwargs__=np.void(blob),
                  __variables__=np.array(list(arrays.keys())), **{'var%03d' % i: v for i, v in enumerate(arrays.values())})
+
+    def _spaces_blob(self):
+        return _dumps_spaces(tuple(self.ob_space_shape), self.num_actions, self.kwargs)
 
     @staticmethod
     def _read_snapshot(filename):
@@ -390,6 +393,198 @@ class GAAtariPolicy(Policy):
         return self._flat
 
 
+# ---------------------------------------------------------------------------------------------- MujocoPolicy on the pendulum
+PENDULUM_ENV_ID = 'Pendulum-v0'
+
+
+class PendulumEnv:
+    """The spaces of the torque-limited pendulum swing-up (csrc/pendulum.h) behind the gym-style surface es.setup reads: a Box observation of
+    shape (3,), a Box action of shape (1,) with the finite bounds MujocoPolicy asserts (policies.py:130-132), 200 steps.  Episodes run inside
+    the engine (or its host twin); this object only hands out their reset seeds."""
+    max_episode_steps = _lib.PENDULUM_STEPS
+
+    def __init__(self, engine=None, seed=0):
+        self.engine = engine
+        self.observation_space = _Space(shape=(_lib.PENDULUM_OBS,))
+        self.action_space = _Space(shape=(1,))
+        self.action_space.low, self.action_space.high = np.array([-2.0], np.float32), np.array([2.0], np.float32)
+        self._seed, self._episode = int(seed), 0
+
+    def seed(self, seed):
+        self._seed, self._episode = int(seed), 0
+
+    def next_episode_seed(self):
+        s = (self._seed + self._episode) & 0xFFFFFFFF
+        self._episode += 1
+        return s
+
+    @property
+    def unwrapped(self):
+        return self
+
+
+def mujoco_layout(hidden, n_out):
+    """flat_layout for MujocoPolicy with two hidden layers of one width: TF's creation order, tf_util.dense's shapes (w [in][out], b [out])"""
+    spec, o = OrderedDict(), 0
+    for name, shape in (("l0/w", (_lib.PENDULUM_OBS, hidden)), ("l0/b", (hidden,)), ("l1/w", (hidden, hidden)), ("l1/b", (hidden,)),
+                        ("out/w", (hidden, n_out)), ("out/b", (n_out,))):
+        spec[name] = (o, shape)
+        o += int(np.prod(shape))
+    return spec, o
+
+
+def mujoco_shape(ac_bins, nonlin_type, hidden_dims, connection_type):
+    """(hidden width, outputs, action mode, nonlinearity) of a MujocoPolicy csrc/pendulum.h builds; everything else is refused by name"""
+    if connection_type != 'ff':
+        raise NotImplementedError("MujocoPolicy: connection_type {!r} (the reference itself builds only 'ff', policies.py:157-162)".format(connection_type))
+    hidden_dims = list(hidden_dims)
+    if len(hidden_dims) != 2:
+        raise NotImplementedError("MujocoPolicy: hidden_dims {} -- the HIP engine builds exactly two hidden layers (every shipped configuration has [256, 256])".format(hidden_dims))
+    if hidden_dims[0] != hidden_dims[1]:
+        raise NotImplementedError("MujocoPolicy: hidden_dims {} -- the two hidden layers must have one width".format(hidden_dims))
+    if hidden_dims[0] not in (64, 128, 256):
+        raise NotImplementedError("MujocoPolicy: hidden width {} -- the HIP engine builds 64, 128 and 256".format(hidden_dims[0]))
+    if nonlin_type not in _lib.PENDULUM_NONLINS:
+        raise NotImplementedError("MujocoPolicy: nonlin_type {!r} -- the HIP engine builds 'tanh' and 'relu' ('lrelu' and 'elu' are not built)".format(nonlin_type))
+    if not isinstance(ac_bins, str) or ':' not in ac_bins:
+        raise NotImplementedError("MujocoPolicy: ac_bins {!r} -- 'continuous:' or 'uniform:B' expected".format(ac_bins))
+    mode, arg = ac_bins.split(':')
+    if mode == 'continuous':
+        n_out = 1
+    elif mode == 'uniform':
+        n_out = int(arg)
+        if not 2 <= n_out <= _lib.PENDULUM_MAX_OUT:
+            raise NotImplementedError("MujocoPolicy: ac_bins {!r} -- the HIP engine builds 2..{} uniform bins".format(ac_bins, _lib.PENDULUM_MAX_OUT))
+    else:
+        raise NotImplementedError("MujocoPolicy: ac_bins {!r} -- the HIP engine builds 'continuous:' and 'uniform:B' ('custom:' bins are not built)".format(ac_bins))
+    return int(hidden_dims[0]), n_out, mode, nonlin_type
+
+
+def refuse_mujoco(exp, driver):
+    """nses / ga with MujocoPolicy: the reference's novelty vector is MuJoCo's centre of mass (policies.py:252-256, 292-299), which does not exist here"""
+    if exp['policy']['type'] == 'MujocoPolicy':
+        raise NotImplementedError("{} with MujocoPolicy is not built: its behaviour characterisation is MuJoCo's centre of mass, and no simulator "
+                                  "runs here -- MujocoPolicy runs under es on {}".format(driver, PENDULUM_ENV_ID))
+
+
+def normc_flat(hidden, n_out, seed=0):
+    """Initial MujocoPolicy parameters: U.normc_initializer(1.0) for the hidden layers and (0.01) for `out` -- randn columns scaled to that
+    norm, tf_util.py:108-116 --, zero biases; drawn from RandomState(seed) in creation order (TF's own initialiser is unseeded)"""
+    spec, P = mujoco_layout(hidden, n_out)
+    rs = np.random.RandomState(seed)
+    th = np.zeros(P, np.float32)
+    for name, (off, shape) in spec.items():
+        if name.endswith('/w'):
+            out = rs.randn(*shape).astype(np.float32)
+            out *= (0.01 if name.startswith('out') else 1.0) / np.sqrt(np.square(out).sum(axis=0, keepdims=True))
+            th[off:off + out.size] = out.reshape(-1)
+    return th
+
+
+class MujocoPolicy(Policy):
+    """policies.py:122-217 with connection_type 'ff' and two hidden layers of one width, on the pendulum swing-up (the simulator the reference
+    drives it on is not available): clip((ob - ob_mean) / ob_std, +-5) -> dense H, nonlin -> dense H, nonlin -> out, continuous or uniform bins;
+    Gaussian action noise of ac_noise_std in training rollouts.  The network is csrc/pendulum.h: the engine's kernel for whole populations, the
+    same text compiled for the CPU for act / rollout of the single current theta."""
+    kind = _lib.KIND_PENDULUM
+
+    def __init__(self, ob_space, ac_space, ac_bins, ac_noise_std, nonlin_type, hidden_dims, connection_type, engine=None):
+        self.hidden, self.n_out, self.ac_mode, self.nonlin = mujoco_shape(ac_bins, nonlin_type, hidden_dims, connection_type)
+        assert len(ob_space.shape) == len(ac_space.shape) == 1                                # policies.py:130
+        assert np.all(np.isfinite(ac_space.low)) and np.all(np.isfinite(ac_space.high)), 'Action bounds required'
+        if tuple(ob_space.shape) != (_lib.PENDULUM_OBS,) or tuple(ac_space.shape) != (1,):
+            raise NotImplementedError("MujocoPolicy: observation space {} and action space {} -- the HIP engine runs it on {} only, (3,) and (1,); "
+                                      "no MuJoCo simulator is available".format(tuple(ob_space.shape), tuple(ac_space.shape), PENDULUM_ENV_ID))
+        self.args = (ob_space, ac_space)
+        self.kwargs = dict(ac_bins=ac_bins, ac_noise_std=ac_noise_std, nonlin_type=nonlin_type, hidden_dims=list(hidden_dims), connection_type=connection_type)
+        self.ob_space_shape, self.ac_space, self.num_actions = tuple(ob_space.shape), ac_space, 1   # num_actions: the action's dimension (snapshots)
+        self.ac_bins, self.ac_noise_std, self.hidden_dims, self.connection_type = ac_bins, float(ac_noise_std), list(hidden_dims), connection_type
+        self.spec, self.num_params = mujoco_layout(self.hidden, self.n_out)
+        assert self.num_params == _lib.pendulum_num_params(self.hidden, self.n_out)
+        if engine is not None and (engine.kind != self.kind or engine.P != self.num_params or
+                                   (getattr(engine, 'hidden', self.hidden), getattr(engine, 'n_actions', self.n_out)) != (self.hidden, self.n_out)):
+            raise ValueError("MujocoPolicy: the engine passed in (kind {}, P {}) does not hold this policy (KIND_PENDULUM {}, P {})".format(
+                engine.kind, engine.P, self.kind, self.num_params))
+        self.engine = engine
+        self._flat = np.zeros(self.num_params, np.float32)
+        self.ob_mean = np.full(_lib.PENDULUM_OBS, np.nan, np.float32)                          # policies.py:138-141
+        self.ob_std = np.full(_lib.PENDULUM_OBS, np.nan, np.float32)
+
+    @property
+    def needs_ob_stat(self):
+        return True
+
+    @property
+    def needs_ref_batch(self):
+        return False
+
+    def set_ob_stat(self, ob_mean, ob_std):
+        self.ob_mean, self.ob_std = np.array(ob_mean, np.float32).reshape(-1), np.array(ob_std, np.float32).reshape(-1)
+        if self.engine is not None:
+            self.engine.pendulum_set_ob_stat(self.ob_mean, self.ob_std)
+
+    def initialize(self, seed=0):
+        self.set_trainable_flat(normc_flat(self.hidden, self.n_out, seed))
+
+    def reinitialize(self):
+        raise NotImplementedError("MujocoPolicy.reinitialize is the GA's (ga.py), which is not built for this policy")
+
+    def _shape_kw(self):
+        return dict(hidden=self.hidden, mean=self.ob_mean, std=self.ob_std, n_out=self.n_out, ac_mode=self.ac_mode, nonlin=self.nonlin)
+
+    def act(self, ob, random_stream=None):
+        """policies.py:202-206: actions [n][1] of observations [n][3] under the current theta"""
+        ob = np.asarray(ob, np.float32).reshape(-1, _lib.PENDULUM_OBS)
+        theta = np.broadcast_to(self.get_trainable_flat(), (ob.shape[0], self.num_params))
+        a = _lib.pendulum_forward_host(theta, ob, **self._shape_kw())[4].reshape(-1, 1)
+        if random_stream is not None and self.ac_noise_std != 0:
+            a = a + (random_stream.randn(*a.shape) * self.ac_noise_std).astype(np.float32)
+        return a
+
+    def rollout(self, env, *, render=False, timestep_limit=None, save_obs=False, random_stream=None, policy_seed=None):
+        """policies.py:259-302: one episode of the current theta from env's next reset seed -> (rews float32 [T], T), with save_obs the
+        observations acted on as well.  random_stream: the episode's 200 action-noise values are drawn from it (float32 of randn).  The
+        reference's third value, MuJoCo's centre of mass, does not exist."""
+        limit = _lib.PENDULUM_STEPS if timestep_limit is None else min(int(timestep_limit), _lib.PENDULUM_STEPS)
+        if policy_seed:
+            env.seed(policy_seed)
+            if random_stream:
+                random_stream.seed(policy_seed)
+        noisy = random_stream is not None and self.ac_noise_std != 0
+        table = random_stream.randn(_lib.PENDULUM_STEPS).astype(np.float32) if noisy else None
+        r = _lib.pendulum_rollout_host(self.get_trainable_flat(), [env.next_episode_seed()], tslimit=limit, ac_noise_std=self.ac_noise_std,
+                                       table=table, ac_off=[0] if noisy else None, want_trace=True, **self._shape_kw())
+        tr = r['trace'][0, :limit]
+        rews = tr[:, 5].astype(np.float32)
+        if save_obs:
+            return rews, limit, tr[:, :3].astype(np.float32)
+        return rews, limit
+
+    def extra_variable_arrays(self, scope):
+        """the two non-trainable variables of policies.py:138-141, after the trainable ones as all_variables lists them"""
+        return OrderedDict([('%s/ob_mean:0' % scope, self.ob_mean.copy()), ('%s/ob_std:0' % scope, self.ob_std.copy())])
+
+    def _spaces_blob(self):
+        return _dumps_spaces(self.ob_space_shape, 1, self.kwargs, ac_box=(float(self.ac_space.low[0]), float(self.ac_space.high[0])))
+
+    @classmethod
+    def Load(cls, filename, engine=None, extra_kwargs=None):
+        _, (ob_shape, adim), kwargs, arrays = cls._read_snapshot(filename)
+        if extra_kwargs:
+            kwargs.update(extra_kwargs)
+        if tuple(ob_shape) != (_lib.PENDULUM_OBS,) or adim != 1:
+            raise NotImplementedError("MujocoPolicy.Load: a policy on observations {} and {} action dimensions -- the HIP engine runs it on {} "
+                                      "only; no MuJoCo simulator is available".format(tuple(ob_shape), adim, PENDULUM_ENV_ID))
+        env = PendulumEnv()
+        pol = cls(env.observation_space, env.action_space, engine=engine, **kwargs)
+        pol._set_from_arrays(arrays, exact=True)
+        pol.set_ob_stat(arrays['MujocoPolicy/ob_mean:0'], arrays['MujocoPolicy/ob_std:0'])
+        return pol
+
+    def initialize_from(self, filename, ob_stat=None):
+        raise NotImplementedError("MujocoPolicy.initialize_from is not built (the snapshot the reference ships is 376 observations wide)")
+
+
 class _GymBox(object):
     """stand-in whose pickle is renamed to gym.spaces.box.Box (state: low, high)"""
 
@@ -398,7 +593,7 @@ class _GymDiscrete(object):
     """stand-in whose pickle is renamed to gym.spaces.discrete.Discrete (state: n)"""
 
 
-def _dumps_spaces(ob_shape, nact, kwargs):
+def _dumps_spaces(ob_shape, nact, kwargs, ac_box=None):
     """policies.py:56: `pickle.dumps((self.args, self.kwargs))` where args are the gym spaces the policy was built with.  A stock
     checkout's Policy.Load does `cls(*args, **kwargs)` and reads ob_space.shape / ac_space.n (policies.py:306-309, 434-438), so
     the pickle must name gym's classes -- whether or not gym is installed here, and without touching sys.modules (another thread
@@ -407,11 +602,15 @@ def _dumps_spaces(ob_shape, nact, kwargs):
     `c<module>\n<name>\n`, with no length field in front of it, so the replacement is exact.  The result is the pickle gym 0.9.4
     (requirements.txt:3) produces: Box state {low, high}, Discrete state {n}.
     The two bound arrays are written as `numpy.zeros(shape)` / `numpy.ones(shape)` calls rather than as 2 x 226 KB of buffer:
-    smaller, and free of the numpy-version-specific module path (`numpy._core` vs `numpy.core`) of a pickled ndarray."""
+    smaller, and free of the numpy-version-specific module path (`numpy._core` vs `numpy.core`) of a pickled ndarray.
+    ac_box = (low, high) scalars (MujocoPolicy): the action space is a Box of shape (nact,) with these bounds, written as `numpy.full` calls."""
     import io
-    ob, ac = _GymBox(), _GymDiscrete()
+    ob, ac = _GymBox(), (_GymDiscrete() if ac_box is None else _GymBox())
     ob.low, ob.high = np.zeros(ob_shape), np.ones(ob_shape)      # float64, as box.py builds them from scalar bounds
-    ac.n = int(nact)
+    if ac_box is None:
+        ac.n = int(nact)
+    else:
+        ac.low, ac.high = np.full((int(nact),), float(ac_box[0])), np.full((int(nact),), float(ac_box[1]))
 
     class _Pickler(pickle.Pickler):
         def reducer_override(self, obj):
@@ -419,12 +618,18 @@ def _dumps_spaces(ob_shape, nact, kwargs):
                 return np.zeros, (tuple(ob_shape),)
             if obj is ob.high:
                 return np.ones, (tuple(ob_shape),)
+            if ac_box is not None and obj is ac.low:
+                return np.full, ((int(nact),), float(ac_box[0]))
+            if ac_box is not None and obj is ac.high:
+                return np.full, ((int(nact),), float(ac_box[1]))
             return NotImplemented
     out = io.BytesIO()
     _Pickler(out, protocol=2).dump(((ob, ac), kwargs))
     blob = out.getvalue()
     here = __name__.encode()
     for mine, (mod, name) in ((b'_GymBox', (b'gym.spaces.box', b'Box')), (b'_GymDiscrete', (b'gym.spaces.discrete', b'Discrete'))):
+        if ac_box is not None and mine == b'_GymDiscrete':
+            continue                 # (two Boxes: the class is written once, the second use is a memo reference)
         ref = b'c' + here + b'\n' + mine + b'\n'
         assert blob.count(ref) == 1, 'unexpected pickle layout'
         blob = blob.replace(ref, b'c' + mod + b'\n' + name + b'\n')

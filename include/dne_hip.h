@@ -46,6 +46,16 @@ extern "C" {
                            episode's length (reward 1 per step); a non-NULL bc and bc_final_only = 1 are refused: dne_cartpole_final_state has
                            every member's final state.  The P-generic calls work as on DNE_KIND_MAZE; every Atari-only, maze-only and GA-only
                            call, dne_debug_plan and dne_debug_plan_act refuse the kind. */
+#define DNE_KIND_PENDULUM 6 /* es_distributed's MujocoPolicy (policies.py:122-217) on the torque-limited pendulum swing-up (csrc/pendulum.h, DESIGN.md
+                           section 14): observations normalised by ob_mean / ob_std and clipped to +-5, two hidden layers of one width under tanh or
+                           relu, a continuous or uniformly binned action, optional Gaussian action noise, optional observation statistics.  The
+                           shape comes in through dne_config.reserved: [0] the hidden width (64, 128 or 256), [1] the action mode (0 continuous,
+                           1 uniform bins), [2] the nonlinearity (0 tanh, 1 relu); n_actions carries the outputs (1 continuous, 2..16 bins).
+                           P = dne_pendulum_num_params(hidden, n_actions); dne_num_params answers -1.  A whole episode (200 steps, never done early)
+                           runs inside one kernel, one workgroup per member: dne_set_members + dne_eval_members or dne_es_eval as on
+                           DNE_KIND_CARTPOLE, after dne_pendulum_set_ob_stat.  bc, record_bc and bc_final_only are refused.  The P-generic calls work
+                           as on DNE_KIND_MAZE; every Atari-only, maze-only, cart-pole-only and GA-only call, dne_debug_plan and dne_debug_plan_act
+                           refuse the kind. */
 #define DNE_OB_BYTES (84 * 84 * 4)
 #define DNE_RAM_BYTES 128
 #define DNE_BN_FLOATS 608
@@ -72,7 +82,7 @@ typedef struct {
     int32_t profile_events; /* 1: bracket hot kernels with HIP events (dne_get_profile) */
     int32_t bc_final_only;  /* ES with record_bc: keep only each member's final RAM ([members][128], what es_modified.py's
                                dumps use: bc_vec[-1], es_modified.py:176,197) instead of the whole trajectory */
-    int32_t reserved[6];
+    int32_t reserved[6];    /* DNE_KIND_PENDULUM: [0] hidden width, [1] action mode, [2] nonlinearity (see there); otherwise 0 */
 } dne_config;
 
 typedef struct { /* filled by dne_get_profile; times from HIP events on the engine's stream */
@@ -367,6 +377,44 @@ int dne_cartpole_rollout_host(const float *theta, int n, const uint32_t *seeds, 
                               int32_t *lengths, double *state, double *trace);
 int dne_cartpole_actions_host(const int32_t *actions, int n, int T, const double *init4, double *rows);
 int dne_cartpole_forward_host(const float *theta, const float *obs, int n, float *h1, float *h2, float *out);
+
+/* ---- MujocoPolicy on the pendulum (DNE_KIND_PENDULUM; csrc/pendulum.h) -------------------
+ * dne_pendulum_num_params: P = 5 H + H^2 + H O + O, or -1 for a width or an output count the header does not build.
+ * dne_pendulum_set_ob_stat: ob_mean [3] and ob_std [3] of the normalisation; NaN before the first call, and an evaluation is then refused.
+ * dne_pendulum_set_rollout_options: for the NEXT evaluation only, which must run exactly n members: ac_off [n] (or NULL: no action noise) --
+ *   member i adds fl(ac_noise_std * table[ac_off[i] + t]) to its action at step t, an offset < 0 means none; ac_off[i] + 200 must lie
+ *   inside the noise table -- and stat_flag [n] (or NULL: no statistics) -- a flagged member accumulates the observations it acted on.
+ * dne_pendulum_ob_stats: of the last evaluation's first n members: sum [n][3], sumsq [n][3] (doubles, in step order), count [n] (= the
+ *   length; all zero for an unflagged member).  dne_pendulum_final_state: state [n][2] = (theta, theta_dot).
+ * dne_pendulum_debug_trace: the kernel once more for ONE of the current members, without noise or statistics, every step written out:
+ *   trace [min(tslimit, 200)][8] doubles = the three observations acted on, the net's action, the action applied (before the clip), the
+ *   reward, theta and theta_dot after the step; init2 = an explicit (theta, theta_dot) instead of the reset.
+ * dne_pendulum_debug_math: value by value on the device; fn 0 tanh_f((float)x), 1 norm_angle(x), 2 the normalise-and-clip of (float)x under
+ *   mean a and deviation b.
+ * The CPU twins need no handle and no GPU (errors through dne_last_error(NULL)):
+ *   dne_pendulum_reset_host    (theta, theta_dot) of one seed;
+ *   dne_pendulum_rollout_host  one episode for each of n thetas [n][P]: every input the kernel has (table / ac_off both or neither), every
+ *                              output it writes, trace [n][tslimit][8] or NULL;
+ *   dne_pendulum_actions_host  the environment alone: n sequences of T float actions from init2 [n][2] -> rows [n][T][3] = theta, theta_dot
+ *                              after the step, the reward;
+ *   dne_pendulum_forward_host  the policy alone on raw observations [n][3] -> x [n][3], h1 [n][H], h2 [n][H], out [n][O], action [n];
+ *   dne_pendulum_math_host     dne_pendulum_debug_math on the CPU. */
+int dne_pendulum_num_params(int hidden, int n_out);
+int dne_pendulum_set_ob_stat(dne_handle *h, const float *mean /*[3]*/, const float *std /*[3]*/);
+int dne_pendulum_set_rollout_options(dne_handle *h, int n, float ac_noise_std, const int64_t *ac_off /*[n] or NULL*/, const uint8_t *stat_flag /*[n] or NULL*/);
+int dne_pendulum_ob_stats(dne_handle *h, int n, double *sum /*[n][3]*/, double *sumsq /*[n][3]*/, int32_t *count /*[n]*/);
+int dne_pendulum_final_state(dne_handle *h, int n, double *state /*[n][2]*/);
+int dne_pendulum_debug_trace(dne_handle *h, int member, int tslimit, const double *init2 /*[2] or NULL*/, double *trace, int32_t *steps);
+int dne_pendulum_debug_math(dne_handle *h, int fn, const double *x, int n, float a, float b, double *out);
+int dne_pendulum_reset_host(uint32_t seed, double *out2);
+int dne_pendulum_rollout_host(const float *theta, int n, int hidden, int n_out, int ac_mode, int nonlin, const float *mean, const float *std,
+                              const uint32_t *seeds, const double *init2, int tslimit, float ac_noise_std, const float *table, size_t table_len,
+                              const int64_t *ac_off, const uint8_t *stat_flag, float *returns, float *signreturns, int32_t *lengths,
+                              double *state, double *ob_sum, double *ob_sumsq, int32_t *ob_count, double *trace);
+int dne_pendulum_actions_host(const float *actions, int n, int T, const double *init2, double *rows);
+int dne_pendulum_forward_host(const float *theta, const float *obs, int n, int hidden, int n_out, int ac_mode, int nonlin, const float *mean,
+                              const float *std, float *x, float *h1, float *h2, float *out, float *action);
+int dne_pendulum_math_host(int fn, const double *x, int n, float a, float b, double *out);
 
 /* ---- novelty on the hard maze (csrc/maze_novelty.h) -------------------------------------------
  * A behaviour characterisation is one float32 point (x, y): a navigator's final position.  nses.py:12-32 on such points: for member p and
