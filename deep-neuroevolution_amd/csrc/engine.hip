@@ -1223,7 +1223,7 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
     CH(hipFuncSetAttribute((const void *)k_conv1_ref_shared<16>, hipFuncAttributeMaxDynamicSharedMemorySize, RF_FRAME * (int)sizeof(float)));
     CH(hipFuncSetAttribute((const void *)k_conv1_ref_shared<8>, hipFuncAttributeMaxDynamicSharedMemorySize, RF_FRAME * (int)sizeof(float)));
     CH(hipFuncSetAttribute((const void *)k_conv2_ref_uniq, hipFuncAttributeMaxDynamicSharedMemorySize, C2U_LDS));
-    if (ref_default_route(h->k, h->F)) {   // room for every batch the dedup route takes (ref_dedup_pays)
+    if (h->k.ref_dedup && ref_default_route(h->k, h->F)) {   // room for every batch the dedup route takes (ref_dedup_pays)
         h->ref_cap1 = ref_pad(h->F * RI_N1, REF_U1_PAD);
         h->ref_cap2 = ref_pad(h->F * RI_N2, REF_U2_PAD);
         CH(h->alloc(&h->ref_tab1, (size_t)h->ref_cap1 * 256, "ref_tab1")); CH(h->alloc(&h->ref_idx1, (size_t)h->F * 448, "ref_idx1"));

@@ -43,6 +43,7 @@ struct Knobs {
     int ga_materialize = 0;
     int lfc_cols_max = 96, lfc_pad = 2;
     int fc_rb = 4;
+    int ref_dedup = 1;
 };
 
 struct KnobRow { const char *env; int lo, hi; int Knobs::*field; const char *text; };
@@ -112,6 +113,7 @@ static const KnobRow KNOBS[] = {
     {"DNE_LFC_COLS_MAX", 0, 1 << 20, &Knobs::lfc_cols_max, "LargeModel windows of up to this many members use the column-split fc"},
     {"DNE_LFC_PAD", 0, 2, &Knobs::lfc_pad, "LargeModel's streamed fc with a padded register footprint -- 1: at most two of its workgroups per CU, 2: one (0: as many as fit, five); same-box 282.5 / 285.2 / 291.2 k env-steps/s at 0 / 1 / 2"},
     {"DNE_FC_RB", 2, 8, &Knobs::fc_rb, "rows per batch of the streaming fc kernels (2, 4, 8; the LargeModel's default is 8: measured 8 % faster than 4)"},
+    {"DNE_REF_DEDUP", 0, 1, &Knobs::ref_dedup, "reference pass on the batch's unique conv rows when the batch has few enough (ref_index.h: ref_dedup_pays); 0 = no tables are allocated, every batch takes the dense kernels"},
 };
 
 // ES-like kinds: ESAtariPolicy and the GPU tree's ModelVirtualBN -- the same network, virtual batch norm over a reference batch, antithetic

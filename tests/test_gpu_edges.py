@@ -3,6 +3,8 @@ runtime asserts it does carry: es.py:196,246-248,297; ga.py:148-149)."""
 import numpy as np
 import pytest
 
+import ref_dedup_support as R
+
 pytestmark = pytest.mark.gpu
 NACT, NREF = 18, 16
 
@@ -211,6 +213,7 @@ _ES_STEP_KNOBS = [
     {"DNE_RENDER_BANDS": "2"},                                          # two render workgroups per member
     {"DNE_CONV_FUSED_MIN": "1"},                                        # conv1 + conv2 in one kernel (k_conv12) at every count
     {"DNE_CONV_FUSED": "0", "DNE_CONV_SPLIT_MAX": "0"},                 # never: separate k_conv1 / k_conv2 launches
+    {"DNE_REF_DEDUP": "0"},                                             # reference pass on the dense kernels (k_conv1_ref_shared<16>, k_conv2_ref<16, true>) although the fixture's frames deduplicate; the default plan (last row: the ids of the rows above stay)
 ]
 
 
@@ -362,12 +365,19 @@ def test_emulator_step_from_crafted_states(eng, oracle):
     assert all(v > 0 for v in seen.values()), seen
 
 
-@pytest.mark.parametrize("nref,members", [(8, 3), (24, 9), (40, 5), (32, 17), (64, 2)])
-def test_reference_batch_sizes(nref, members, oracle, small_noise):
+_REF_SIZE_ORACLE = {}   # (nref, member) -> the oracle's reference pass, shared by the routes of a size
+
+
+@pytest.mark.parametrize("nref,members,route", [pytest.param(nref, members, route, id="%d-%d%s" % (nref, members, R.route_id(route)))
+                                                for nref, members in [(8, 3), (24, 9), (40, 5), (32, 17), (64, 2)] for route in R.routes(nref)])
+def test_reference_batch_sizes(nref, members, route, oracle, small_noise, monkeypatch):
     """Virtual batch norm over reference batches other than the reference's 128 frames (es.py:160-162 takes any batch_size): multiples
     of 8 that are / are not multiples of 16 (the shared-image conv1 takes 16 or 8 frames per workgroup), the matrix-core fc path
-    (16, 32, 64, 128 frames) and the generic one, member counts that do not fill the last eight-member workgroup."""
+    (16, 32, 64, 128 frames) and the generic one, member counts that do not fill the last eight-member workgroup.  32 and 64 frames have
+    two routes (csrc/ref_index.h): the engine's pick for these frames (the unique-row kernels, asserted) and, under DNE_REF_DEDUP=0,
+    k_conv1_ref_shared<16> + k_conv2_ref<16, true> in front of k_fc_ref<2> / <4>."""
     from dne_hip import _lib
+    knob = R.route_env(monkeypatch, route)
     e = _lib.Engine(_lib.KIND_ES, NACT, max_members=32, ref_count=nref)
     try:
         e.noise_upload(small_noise)
@@ -376,6 +386,7 @@ def test_reference_batch_sizes(nref, members, oracle, small_noise):
         e.set_theta(th)
         ref = oracle.get_ref_batch(seed=3, batch_size=nref, nact=NACT)
         e.set_ref_batch(ref)
+        print("%d reference frames, %d members, route asked for: %s -> %s kernels" % (nref, members, route, R.expect_route(e, ref, knob, True)))
         rs = np.random.RandomState(nref)
         off = rs.randint(0, small_noise.size - L.P, members).astype(np.int64)
         scale = rs.choice([0.02, -0.02, 0.0, 0.1], members).astype(np.float32)
@@ -383,7 +394,9 @@ def test_reference_batch_sizes(nref, members, oracle, small_noise):
         e.ref_pass(members)
         bn, mom = e.get_bn(members), e.get_bn_moments(members)
         for i in (0, members - 1, members // 2):
-            obn, omom = oracle.es_ref_pass_moments(L, th + np.float32(scale[i]) * small_noise[off[i]:off[i] + L.P], ref)
+            if (nref, i) not in _REF_SIZE_ORACLE:
+                _REF_SIZE_ORACLE[(nref, i)] = oracle.es_ref_pass_moments(L, th + np.float32(scale[i]) * small_noise[off[i]:off[i] + L.P], ref)
+            obn, omom = _REF_SIZE_ORACLE[(nref, i)]
             assert np.array_equal(bn[i], obn) and np.array_equal(mom[i], omom), (nref, i)
     finally:
         e.close()

@@ -14,6 +14,11 @@ repeated-frame batches; 254 / 255 noise under one-tap channels, where rounding e
 128 (matrix-core fc, one and two frame groups) reference frames, on an ES and a ModelVirtualBN engine; 12 members = two chunks of the
 engine's ref_chunk = 8 on two streams, with scales from {0.02, -0.02, 0, 0.5} (the scale-0 members are the case's theta itself).
 
+Routes: at 16 and 128 frames the engine has two sets of convolution kernels for the pass and picks per batch (csrc/ref_index.h); every
+test here runs both -- "default" (the engine's pick: the unique-row kernels for cases a to e, the dense ones for f, asserted) and "dense"
+(DNE_REF_DEDUP=0: k_conv1_ref_shared<16> and k_conv2_ref<16, true> on every batch, the degenerate ones included) -- against the same
+expected side, states the route it ran (ref_dedup_support.expect_route) and prints it.  8 frames have one route.
+
 Chunking: one chunk, a last chunk of one member (seven phantom members in k_fc_ref's eight-member grid), three chunks (a scratch set is
 used twice), three full chunks, and a chunk size that is no multiple of 8.
 
@@ -24,6 +29,7 @@ import multiprocessing as mp
 import numpy as np
 import pytest
 
+import ref_dedup_support as S
 import vbn_stats_support as V
 from vbn_stats_support import CASES, FS, KINDS, NACT
 
@@ -35,7 +41,11 @@ MAX_MEMBERS = 24
 
 _BASE = None
 _REFS = {}       # (kind, case, F, member) -> the oracle / float64 side of one member
-_ENGINES = {}    # (kind, F, ref_chunk) -> Engine
+_ENGINES = {}    # (kind, F, ref_chunk, DNE_REF_DEDUP) -> Engine
+_EVALS = {}      # (kind, batch) -> the oracle's side of test_es_eval_on_degenerate_reference_batches
+# the route dne_set_ref_batch picks for each case's batch on the default knobs, at 16 and at 128 frames alike (the model cost of
+# csrc/ref_index.h against the dense kernels' 29.76: a, b 25.27 / 12.15; c 5.1; d 5.2; e 6.9 / 5.3; f 42.85 -- every row distinct)
+DEDUP_BY_DEFAULT = dict(a=True, b=True, c=True, d=True, e=True, f=False)
 
 
 @pytest.fixture(scope="module")
@@ -49,7 +59,7 @@ def _close_engines(oracle):
     yield
     for e in _ENGINES.values():
         e.close()
-    _ENGINES.clear(); _REFS.clear()
+    _ENGINES.clear(); _REFS.clear(); _EVALS.clear()
 
 
 def _P(kind):
@@ -111,19 +121,24 @@ def _refs(kind, case, F, n, noise):
     return [_REFS[(kind, case, F, i)] for i in range(n)]
 
 
-def _engine(hip, kind, F, ref_chunk, noise):
-    key = (kind, F, ref_chunk)
+def _engine(hip, kind, F, ref_chunk, noise, route, monkeypatch):
+    """(engine, DNE_REF_DEDUP as it was created); the knobs are read once in dne_create, so the environment is set first"""
+    knob = S.route_env(monkeypatch, route)
+    key = (kind, F, ref_chunk, knob)
     if key not in _ENGINES:
         e = hip.Engine(hip.KIND_ES if kind == "es" else hip.KIND_ES_VBN, NACT, max_members=MAX_MEMBERS, ref_count=F, ref_chunk=ref_chunk)
         e.noise_upload(noise)
         _ENGINES[key] = e
-    return _ENGINES[key]
+    return _ENGINES[key], knob
 
 
-def _run_ref_pass(e, kind, case, F, n, noise):
+def _run_ref_pass(e, knob, route, kind, case, F, n, noise):
     off, scale = _members(kind, noise)
     e.set_theta(_base_theta(kind, case, F))
-    e.set_ref_batch(V.case_inputs(case, F)[1])
+    ref = V.case_inputs(case, F)[1]
+    e.set_ref_batch(ref)
+    ran = S.expect_route(e, ref, knob, DEDUP_BY_DEFAULT[case])
+    print("%s case %s F=%d n=%d, route asked for: %s -> %s kernels" % (kind, case, F, n, route, ran))
     e.set_members(np.zeros(n, np.int32), off[:n], scale[:n])
     e.ref_pass(n)
     return e.get_bn(n), e.get_bn_moments(n)
@@ -145,14 +160,13 @@ def _check_members(kind, case, F, n, noise, bn, mom, refs):
     return worst
 
 
-@pytest.mark.parametrize("F", FS)
-@pytest.mark.parametrize("case", CASES)
-@pytest.mark.parametrize("kind", KINDS)
-def test_ref_pass_statistics_every_member(hip, small_noise, kind, case, F):
+@pytest.mark.parametrize("kind, case, F, route", [pytest.param(kind, case, F, route, id="%s-%s-%d%s" % (kind, case, F, S.route_id(route)))
+                                                  for kind in KINDS for case in CASES for F in FS for route in S.routes(F)])
+def test_ref_pass_statistics_every_member(hip, small_noise, monkeypatch, kind, case, F, route):
     n = N_MAIN
     refs = _refs(kind, case, F, n, small_noise)
-    e = _engine(hip, kind, F, 8, small_noise)
-    bn, mom = _run_ref_pass(e, kind, case, F, n, small_noise)
+    e, knob = _engine(hip, kind, F, 8, small_noise, route, monkeypatch)
+    bn, mom = _run_ref_pass(e, knob, route, kind, case, F, n, small_noise)
     _check_members(kind, case, F, n, small_noise, bn, mom, refs)
     if case == "c":       # conv1 of an all-zero batch: every variance exactly 0, the clamped scale gamma / sqrt(1e-3) in every member
         assert not mom[:, 16:32].any()
@@ -177,21 +191,22 @@ def test_ref_pass_statistics_every_member(hip, small_noise, kind, case, F):
 CHUNKING = [(8, 8), (8, 9), (8, 17), (8, 24), (5, 11)]
 
 
-@pytest.mark.parametrize("ref_chunk, n", CHUNKING)
-@pytest.mark.parametrize("F", (128, 8))
-@pytest.mark.parametrize("kind", KINDS)
-def test_ref_pass_chunking_every_member(hip, small_noise, kind, F, ref_chunk, n):
+@pytest.mark.parametrize("kind, F, ref_chunk, n, route", [pytest.param(kind, F, ref_chunk, n, route, id="%s-%d-%d-%d%s" % (kind, F, ref_chunk, n, S.route_id(route)))
+                                                          for kind in KINDS for F in (128, 8) for ref_chunk, n in CHUNKING for route in S.routes(F)])
+def test_ref_pass_chunking_every_member(hip, small_noise, monkeypatch, kind, F, ref_chunk, n, route):
+    """case b: at F = 128 the dedup kernels ("default") and the dense ones ("dense": k_conv1_ref_shared<16>, whose (nc + 7) / 8 workgroups
+    have dead member slots of their own, k_conv2_ref<16, true>), at F = 8 the generic path"""
     case = "b"
     refs = _refs(kind, case, F, n, small_noise)
-    e = _engine(hip, kind, F, ref_chunk, small_noise)
-    bn, mom = _run_ref_pass(e, kind, case, F, n, small_noise)
+    e, knob = _engine(hip, kind, F, ref_chunk, small_noise, route, monkeypatch)
+    bn, mom = _run_ref_pass(e, knob, route, kind, case, F, n, small_noise)
     _check_members(kind, case, F, n, small_noise, bn, mom, refs)
     assert e.check_redzones() == 0
 
 
-@pytest.mark.parametrize("batch", ("zero", "repeated"))
-@pytest.mark.parametrize("kind", KINDS)
-def test_es_eval_on_degenerate_reference_batches(hip, oracle, small_noise, kind, batch):
+@pytest.mark.parametrize("kind, batch, route", [pytest.param(kind, batch, route, id="%s-%s%s" % (kind, batch, S.route_id(route)))
+                                                for kind in KINDS for batch in ("zero", "repeated") for route in S.ROUTES])
+def test_es_eval_on_degenerate_reference_batches(hip, oracle, small_noise, monkeypatch, kind, batch, route):
     """two antithetic pairs, three steps, under batch statistics whose conv1 variances are all exactly zero (all-zero frames) or whose fc
     variances are rounding noise (one frame repeated): the step kernels apply the same clamped scales as the oracle"""
     import vbn_support
@@ -203,15 +218,19 @@ def test_es_eval_on_degenerate_reference_batches(hip, oracle, small_noise, kind,
     idx = np.array([12_345, small_noise.size - P], np.int64)
     seeds = np.array([3, 1_000_003, 77, 2 ** 31 + 5], np.uint32)
     sigma, tslimit = 0.02, 3
-    if kind == "es":
-        oret, osg, oln = O.es_eval(V.layout(), base, small_noise, idx, sigma, tslimit, ref, seeds)
-    else:
-        oret, osg, oln, _ = vbn_support.es_pairs(small_noise, base, ref, idx, seeds, sigma, tslimit, NACT)
+    if (kind, batch) not in _EVALS:
+        if kind == "es":
+            _EVALS[(kind, batch)] = O.es_eval(V.layout(), base, small_noise, idx, sigma, tslimit, ref, seeds)
+        else:
+            _EVALS[(kind, batch)] = vbn_support.es_pairs(small_noise, base, ref, idx, seeds, sigma, tslimit, NACT)[:3]
+    oret, osg, oln = _EVALS[(kind, batch)]
+    knob = S.route_env(monkeypatch, route)
     e = hip.Engine(hip.KIND_ES if kind == "es" else hip.KIND_ES_VBN, NACT, max_members=4, ref_count=F)
     try:
         e.noise_upload(small_noise)
         e.set_theta(base)
         e.set_ref_batch(ref)
+        print("%s %s batch, route asked for: %s -> %s kernels" % (kind, batch, route, S.expect_route(e, ref, knob, True)))
         ret, sg, ln = e.es_eval(idx, sigma, tslimit, seeds)
         assert np.array_equal(ln, oln) and np.array_equal(ret, oret) and np.array_equal(sg, osg), (ret, oret, ln, oln)
         assert (ln == tslimit).all()

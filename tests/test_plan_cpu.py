@@ -217,6 +217,7 @@ _ES_EXPECT = [
     ("k_fc_tail", dict(_TAIL, conv="k_conv12"), [(1, dict(conv="k_conv12", spec=1))]),
     # DNE_CONV_FUSED=0 DNE_CONV_SPLIT_MAX=0 "never: separate k_conv1 / k_conv2 launches": k_conv12 never runs, but up to 64 members k_conv12t does
     ("k_fc_tail", dict(_TAIL, conv="k_conv12t"), [(33, dict(conv="split", s1=4, s2=2)), (400, dict(conv="split", s1=1, s2=2))]),   # (three windows of 266 members: conv2 over 2 up to 512)
+    ("k_fc_tail", dict(_TAIL, conv="k_conv12t", nsub=1), []),                      # DNE_REF_DEDUP=0: the default plan, only the reference pass differs
 ]
 _GA_EXPECT = [      # test_gpu_edges._GA_STEP_KNOBS at the tests' 7 members
     ("k_fc_tail", dict(_TAIL), []),
@@ -267,7 +268,7 @@ def test_es_step_knobs_select_what_their_comments_say(i, monkeypatch):
     kind = _kind_of(KIND_ES, 11, **ES_FACTS)
     assert kind == T._fc_full_kind(knobs), knobs                      # what test_es_step_knob_taps asserts on the GPU
     for name, value in (("DNE_BURST", 5), ("DNE_BURST_TAIL", 40), ("DNE_FC_RB", 2), ("DNE_HEAD_THREADS", 256), ("DNE_SPEC_CONV1", 0), ("DNE_SPEC_BANDS", 2),
-                        ("DNE_CONV1_FPW", None), ("DNE_CONV1_SHARED", 0), ("DNE_TAIL_TABLE", 0), ("DNE_DUO_LAG", 3), ("DNE_BAND_THREADS", 1024)):
+                        ("DNE_CONV1_FPW", None), ("DNE_CONV1_SHARED", 0), ("DNE_REF_DEDUP", 0), ("DNE_TAIL_TABLE", 0), ("DNE_DUO_LAG", 3), ("DNE_BAND_THREADS", 1024)):
         if name in knobs:
             assert _lib.debug_knob(KIND_ES, NACT, name) == (int(knobs[name]) if value is None else value), (knobs, name)
 
@@ -356,7 +357,7 @@ def _table():
 
 def test_knob_table_clamps_and_design_is_current(monkeypatch):
     rows, out = _table()
-    assert len(rows) == 60 and len({r[0] for r in rows}) == 60
+    assert len(rows) == 61 and len({r[0] for r in rows}) == 61
     design = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "DESIGN.md")).read()
     assert out.strip() in design                                     # section 11 is the tool's output
     snapped = {"DNE_HEAD_THREADS", "DNE_RENDER_THREADS", "DNE_BAND_THREADS", "DNE_FC_SUB_SPW"}

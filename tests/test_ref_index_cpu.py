@@ -73,3 +73,36 @@ def test_random_batch_has_nothing_to_share(hip):
 def test_odd_table_sizes(hip):
     U1, U2, dedup = _check(hip, S.odd_frames(16))
     assert U1 % 16 and U2 % 16 and dedup
+
+
+@pytest.mark.parametrize("F", [16, 32])
+def test_route_sweep_from_the_fixture_to_random_bytes(hip, F):
+    """the fixture's frames with k = 0 .. F of them replaced by random bytes: the verdict of dne_debug_ref_index equals the restatement of
+    ref_dedup_pays / ref_dedup_fits (ref_dedup_support.pays) on the U1 / U2 it returns, is True at k = 0 and False at k = F.  At F = 16
+    the k = 3 batch is the longest that takes the dedup route (tests/test_gpu_ref_dedup.py runs it): its slack in the dense route's y1 is
+    below one step of k_conv2_ref_uniq, both its tables end in a segment shorter than steps_per_wg, and one more frame neither pays nor
+    fits.  At F = 32 the verdict flips between k = 14 and k = 16 with room still positive at 14: there the cost decides, not the room."""
+    rows = {}
+    for k in range(F + 1):
+        _, patches, _, windows, dedup = hip.debug_ref_index(S.mixed_frames(F, k))
+        U1, U2 = patches.shape[0], windows.shape[0]
+        rows[k] = (U1, U2, dedup)
+        print("F=%d k=%2d: U1 = %5d, U2 = %4d, cost %.2f (dense %.2f), room %6d floats per member: %s"
+              % (F, k, U1, U2, S.cost(F, U1, U2), S.MS_CONV1_DENSE + S.MS_CONV2_DENSE, S.room(F, U1, U2), "dedup" if dedup else "dense"))
+        assert dedup == S.pays(F, U1, U2), (F, k, U1, U2)
+    assert rows[0][2] and not rows[F][2]
+    assert rows[F][:2] == (F * S.N1, F * S.N2)
+    if F == 16:
+        U1, U2, dedup = rows[3]
+        assert (U1, U2) == (4060, 1416) and dedup
+        assert abs(float(S.cost(F, U1, U2)) - 29.36) < 0.005
+        assert (S.pad(U1, S.U1_PAD), S.pad(U2, S.U2_PAD)) == (4064, 1472)
+        assert 0 <= S.room(F, U1, U2) == 768 < S.C2U_ROWS * 32                      # the slack is below one U2 step
+        assert (4064 // S.C1U_ROWS, 1472 // S.C2U_ROWS) == (127, 23)                # 127 steps over segments of 32, 23 over segments of 16
+        assert 127 % S.SPW1 and 23 % S.SPW2
+        assert rows[4] == (4428, 1498, False)
+        assert S.room(F, 4428, 1498) < 0 and not S.cost(F, 4428, 1498) < S.MS_CONV1_DENSE + S.MS_CONV2_DENSE   # neither fits nor pays
+        assert not any(rows[k][2] for k in range(4, F + 1))
+    else:
+        assert rows[14][2] and S.room(F, *rows[14][:2]) > 0 and not rows[16][2]
+        assert not any(rows[k][2] for k in range(16, F + 1))
