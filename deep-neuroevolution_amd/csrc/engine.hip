@@ -3489,6 +3489,8 @@ extern "C" int dne_optimizer_get_state(dne_handle *h, float *m, float *v, int32_
 extern "C" int dne_optimizer_set_state(dne_handle *h, const float *m, const float *v, int32_t t) {
     DeviceGuard dg(h);
     if (t < 0) return h->fail("optimizer step count must be >= 0");
+    // optimizers.py:11 adds one before the step: the largest int32 would overflow there
+    if (t == INT32_MAX) return h->fail("dne_optimizer_set_state: t = %d leaves no room for the next step (the count is an int32)", t);
     if (m) HCHECK(h, hipMemcpy(h->opt_m, m, (size_t)h->L.P * sizeof(float), hipMemcpyHostToDevice));
     if (v) HCHECK(h, hipMemcpy(h->opt_v, v, (size_t)h->L.P * sizeof(float), hipMemcpyHostToDevice));
     h->opt_t = t;

@@ -13,14 +13,20 @@
 namespace dne {
 
 // es.py:70-85.  rank_i = #{x_j < x_i} + #{j < i : x_j == x_i}  (argsort ties by flat index)
+// The order is numpy's total one: a NaN is greater than everything else, +inf included, and two NaNs are equal (so they fall to the
+// index like any tie).  On input without a NaN both selects below take their second arm and the expression is the one above.
 __global__ __launch_bounds__(256) void k_centered_ranks(const float *__restrict__ x, int n, float *__restrict__ y) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float xi = x[i];
+    const bool ni = xi != xi;
     int rank = 0;
     for (int j = 0; j < n; j++) {
         const float xj = x[j];
-        rank += (xj < xi) || (xj == xi && j < i);
+        const bool nj = xj != xj;
+        const bool lt = ni ? !nj : (xj < xi);
+        const bool eq = ni ? nj : (xj == xi);
+        rank += lt || (eq && j < i);
     }
     float r = (float)rank;
     r = r / (float)(n - 1);
@@ -266,13 +272,22 @@ __global__ void k_zero(float *__restrict__ w, int n) {
     if (i < n) w[i] = 0.0f;
 }
 
-// ga.py:145: position of each candidate in the order (-return, arrival index); the first T are kept.
+// ga.py:145: position of each candidate in the order (-return, arrival index); the first T are kept.  Returns are ordered as in
+// k_centered_ranks (NaN greatest, as numpy's partition has it; two NaNs equal): the positions are a permutation whatever the input,
+// so no two threads store to the same out[pos].
 __global__ __launch_bounds__(256) void k_ga_select(const float *__restrict__ r, int m, int t, int32_t *__restrict__ out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= m) return;
     const float ri = r[i];
+    const bool ni = ri != ri;
     int pos = 0;
-    for (int j = 0; j < m; j++) pos += (r[j] > ri) || (r[j] == ri && j < i);
+    for (int j = 0; j < m; j++) {
+        const float rj = r[j];
+        const bool nj = rj != rj;
+        const bool gt = !ni && (nj || rj > ri);
+        const bool eq = ni ? nj : (rj == ri);
+        pos += gt || (eq && j < i);
+    }
     if (pos < t) out[pos] = i;
 }
 

@@ -250,7 +250,8 @@ int dne_ga_eval_powers(dne_handle *h, const int32_t *chain_offsets /*n+1*/, cons
                        uint8_t *bc);
 
 /* ---- A8-A10: on-device reduce ------------------------------------------------------------------------ */
-int dne_centered_ranks(dne_handle *h, const float *x, int n, float *out);           /* es.py:70-85, stable ties */
+/* es.py:70-85, stable ties; numpy's order: a NaN ranks above everything else (+inf included), NaNs among themselves by index */
+int dne_centered_ranks(dne_handle *h, const float *x, int n, float *out);
 /* es.py:291-296: g = (sum_i w[i] * noise[idx[i]:idx[i]+P]) / denom, kept on device; g_host may be NULL */
 int dne_weighted_sum(dne_handle *h, const int64_t *idx, const float *w, int n, float denom, float *g_host);
 /* es.py:298 + optimizers.py: theta(slot 0) <- theta + step(-g + l2coeff*theta) using the device g */
@@ -260,7 +261,7 @@ int dne_optimizer_reset(dne_handle *h); /* zero m, v, t (a fresh Adam/SGD, optim
 /* nses.py:95-117,283-284 keeps one optimizer per meta-population member: swap its state in and out
  * (Adam: m, v, t ; SGD: v in `v`, m ignored).  Pointers may be NULL to skip a field. */
 int dne_optimizer_get_state(dne_handle *h, float *m, float *v, int32_t *t);
-int dne_optimizer_set_state(dne_handle *h, const float *m, const float *v, int32_t t);
+int dne_optimizer_set_state(dne_handle *h, const float *m, const float *v, int32_t t);   /* 0 <= t <= 2^31 - 2: the next step adds one */
 /* es.py:281-298 in one call: process returns (proc_mode), aggregate, optimizer step */
 int dne_es_update(dne_handle *h, const int64_t *idx, const float *returns_n2, const float *signreturns_n2,
                   int n, int proc_mode, int opt_kind, float l2coeff, double stepsize, double beta1_or_momentum,
@@ -303,7 +304,7 @@ int dne_records_set(dne_handle *h, const void *records /*[n_global], global pair
 int dne_es_update_gathered(dne_handle *h, int proc_mode, int opt_kind, float l2coeff, double stepsize,
                            double beta1_or_momentum, double beta2, double epsilon, double *update_ratio);
 
-/* ga.py:145: indices of the top-T returns, ordered by (-return, arrival index) */
+/* ga.py:145: indices of the top-T returns, ordered by (-return, arrival index); a NaN return is the greatest */
 int dne_ga_select(dne_handle *h, const float *returns, int m, int t, int32_t *out_idx);
 
 /* ---- A13 nses.py:12-32: novelty of one behaviour characterisation against an archive -------------------

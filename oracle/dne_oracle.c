@@ -879,12 +879,17 @@ void orc_es_eval(const orc_layout *L, const float *theta, const float *noise, co
 
 /* ------------------------------------------------------------------ reduce */
 
+/* the order of returns, numpy's (argsort, argpartition): a NaN is greater than everything else and equal to a NaN */
+static int orc_before(float a, float b) { return b != b ? a == a : a < b; }
+static int orc_tied(float a, float b) { return b != b ? a != a : a == b; }
+
 void orc_centered_ranks(const float *x, int n, float *y) {
-    /* es.py:70-85; argsort ties resolved by flat index */
+    /* es.py:70-85; argsort ties resolved by flat index; numpy's order: a NaN after everything else,
+     * +inf included, and two NaNs a tie like any other */
     const float denom = (float)(n - 1);
     for (int i = 0; i < n; i++) {
         int rank = 0;
-        for (int j = 0; j < n; j++) rank += (x[j] < x[i]) || (x[j] == x[i] && j < i);
+        for (int j = 0; j < n; j++) rank += orc_before(x[j], x[i]) || (orc_tied(x[j], x[i]) && j < i);
         float r = (float)rank;
         r = r / denom;
         y[i] = r - 0.5f;
@@ -1002,13 +1007,13 @@ void orc_ga_rebuild(const orc_layout *L, const float *noise, const int64_t *seed
 }
 
 void orc_ga_select(const float *returns, int M, int T, int32_t *out_idx) {
-    /* ga.py:145 top-T by return; order defined as (-return, arrival index) */
+    /* ga.py:145 top-T by return; order defined as (-return, arrival index), a NaN return the greatest */
     uint8_t *used = (uint8_t *)calloc(M, 1);
     for (int t = 0; t < T; t++) {
         int best = -1;
         for (int i = 0; i < M; i++) {
             if (used[i]) continue;
-            if (best < 0 || returns[i] > returns[best]) best = i;
+            if (best < 0 || orc_before(returns[best], returns[i])) best = i;
         }
         used[best] = 1;
         out_idx[t] = best;
