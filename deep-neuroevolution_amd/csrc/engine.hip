@@ -34,6 +34,7 @@
 #include "maze_ga.h"
 #include "cartpole.h"
 #include "pendulum.h"
+#include "step_env.h"
 
 using namespace dne;
 
@@ -673,6 +674,12 @@ struct dne_handle {
     double *pd_state = nullptr, *pd_sum = nullptr, *pd_sumsq = nullptr; int32_t *pd_count = nullptr; int pd_last_n = 0;   // per member of the last evaluation
     int64_t *pd_acoff = nullptr; uint8_t *pd_flag = nullptr;   // dne_pendulum_set_rollout_options: per member, for the next evaluation only
     int pd_opt_n = 0; bool pd_has_off = false, pd_has_flag = false; std::vector<int64_t> pd_host_off;   // (the offsets once more on the host: checked again at the launch)
+    // the step-at-a-time environment batch (csrc/step_env.h, dne_stepenv_*): max_members environments apart from everything an evaluation reads
+    // or writes, allocated by the first dne_stepenv_* call that needs it.  se_io_*: what one call uploads and fetches, [max_members] each
+    stepenv::Batch se{}; bool se_ready = false; std::vector<uint8_t> se_was_reset;   // (the bitmap: on the host, one byte per environment)
+    int32_t *se_io_idx = nullptr, *se_io_steps = nullptr; uint32_t *se_io_seeds = nullptr; float *se_io_act = nullptr, *se_io_rew = nullptr, *se_io_obs = nullptr;
+    uint8_t *se_io_done = nullptr; double *se_io_state = nullptr;
+    hipEvent_t se_ev_a = nullptr, se_ev_b = nullptr; double se_last_ms = -1.0;   // the last step kernel between two device events
     bool episodic() const { return maze || cartpole || pendulum; }   // a whole episode per member in one launch: what dne_es_eval and the record calls accept beside the Atari kinds
     bool large = false;              // DNE_KIND_GA_LARGE: y1 [441][32], y2 / y3 [121][64] (conv3 output), y3t = the 512 fc outputs
     float *y1r[2] = {nullptr, nullptr}, *y2r[2] = {nullptr, nullptr}, *y3pr[2] = {nullptr, nullptr};   // reference pass scratch, two ways
@@ -1335,6 +1342,8 @@ extern "C" void dne_destroy(dne_handle *h) {
     if (h->count_host) hipHostFree(h->count_host);
     for (hipEvent_t e : h->fc_ring) hipEventDestroy(e);
     for (hipEvent_t e : h->ev_ref) if (e) hipEventDestroy(e);
+    if (h->se_ev_a) hipEventDestroy(h->se_ev_a);
+    if (h->se_ev_b) hipEventDestroy(h->se_ev_b);
     if (h->ev_a) hipEventDestroy(h->ev_a);
     if (h->ev_b) hipEventDestroy(h->ev_b);
     for (size_t s = 1; s < h->sub_streams.size(); s++) hipStreamDestroy(h->sub_streams[s]);
@@ -3085,6 +3094,240 @@ extern "C" int dne_pendulum_math_host(int fn, const double *x, int n, float a, f
     if (fn < 0 || fn >= pendulum::MATH_FNS || n < 1 || !x || !out) { g_create_error = "dne_pendulum_math_host: bad arguments"; return -1; }
     for (int i = 0; i < n; i++) out[i] = pendulum::math_fn(fn, x[i], a, b);
     return 0;
+}
+
+// ------------------------------------------------------------------------------- environments stepped by the caller (csrc/step_env.h)
+static_assert(stepenv::KIND_MAZE == DNE_KIND_MAZE && stepenv::KIND_CARTPOLE == DNE_KIND_CARTPOLE && stepenv::KIND_PENDULUM == DNE_KIND_PENDULUM,
+              "step_env.h restates the three kinds");
+
+static const char *se_kind_name(int kind) { return kind == DNE_KIND_MAZE ? "DNE_KIND_MAZE" : kind == DNE_KIND_CARTPOLE ? "DNE_KIND_CARTPOLE" : "DNE_KIND_PENDULUM"; }
+
+extern "C" int dne_stepenv_dims(int kind, int *obs, int *act, int *state, int *act_is_int) {
+    stepenv::Dims d;
+    if (!stepenv::dims(kind, &d)) {
+        g_create_error = "dne_stepenv_dims: kind " + std::to_string(kind) + " has no step-at-a-time environment (DNE_KIND_MAZE, DNE_KIND_CARTPOLE and DNE_KIND_PENDULUM have)";
+        return -1;
+    }
+    if (obs) *obs = d.obs;
+    if (act) *act = d.act;
+    if (state) *state = d.state;
+    if (act_is_int) *act_is_int = d.act_is_int;
+    return 0;
+}
+
+static stepenv::Dims se_dims(const dne_handle *h) {
+    stepenv::Dims d{};
+    stepenv::dims(h->L.kind, &d);
+    return d;
+}
+
+static stepenv::MazeCtx se_maze_ctx(const dne_handle *h) { return {h->maze_hdr, h->maze_walls, h->maze_nw}; }
+
+// the batch, at the first call that needs it: every environment starts as zeros and "never reset"
+static int se_alloc(dne_handle *h) {
+    if (h->se_ready) return 0;
+    const size_t M = h->M;
+    const stepenv::Dims d = se_dims(h);
+    HCHECK(h, h->alloc(&h->se.state, M * d.state, "stepenv_state")); HCHECK(h, h->alloc(&h->se.steps, M, "stepenv_steps"));
+    HCHECK(h, h->alloc(&h->se.limit, M, "stepenv_limit")); HCHECK(h, h->alloc(&h->se.done, M, "stepenv_done"));
+    HCHECK(h, h->alloc(&h->se.obs, M * d.obs, "stepenv_obs"));
+    HCHECK(h, hipMemset(h->se.state, 0, M * d.state * sizeof(double))); HCHECK(h, hipMemset(h->se.steps, 0, M * sizeof(int32_t)));
+    HCHECK(h, hipMemset(h->se.limit, 0, M * sizeof(int32_t))); HCHECK(h, hipMemset(h->se.done, 0, M)); HCHECK(h, hipMemset(h->se.obs, 0, M * d.obs * sizeof(float)));
+    HCHECK(h, h->alloc(&h->se_io_idx, M, "stepenv_io_idx")); HCHECK(h, h->alloc(&h->se_io_steps, M, "stepenv_io_steps"));
+    HCHECK(h, h->alloc(&h->se_io_seeds, M, "stepenv_io_seeds")); HCHECK(h, h->alloc(&h->se_io_act, M * stepenv::MAX_ACT, "stepenv_io_act"));
+    HCHECK(h, h->alloc(&h->se_io_rew, M, "stepenv_io_rew")); HCHECK(h, h->alloc(&h->se_io_obs, M * d.obs, "stepenv_io_obs"));
+    HCHECK(h, h->alloc(&h->se_io_done, M, "stepenv_io_done")); HCHECK(h, h->alloc(&h->se_io_state, M * d.state, "stepenv_io_state"));
+    HCHECK(h, hipEventCreate(&h->se_ev_a)); HCHECK(h, hipEventCreate(&h->se_ev_b));
+    h->se_was_reset.assign(M, 0);
+    h->se_ready = true;
+    return 0;
+}
+
+// What every dne_stepenv_* call on a handle asks first: the kind, the maze's walls, n, the index list (NULL = 0 .. n - 1) in range and without
+// a repeat, and -- for a call that reads environments -- that each was reset.  Fills idx.  A refusal comes before anything on the device moves.
+static int se_check(dne_handle *h, const char *call, int n, const int32_t *indices, bool reads, std::vector<int32_t> &idx) {
+    if (!h->episodic())
+        return h->fail("%s needs a DNE_KIND_MAZE, DNE_KIND_CARTPOLE or DNE_KIND_PENDULUM engine (this one: kind %d)", call, h->L.kind);
+    if (h->maze && h->maze_nw < 1) return h->fail("%s: no maze loaded (dne_maze_set_walls comes before the environments)", call);
+    if (n < 1 || n > h->M) return h->fail("%s: %d environments asked for, the engine holds 1..%d", call, n, h->M);
+    idx.resize(n);
+    std::vector<uint8_t> seen(h->M, 0);
+    for (int i = 0; i < n; i++) {
+        const int e = indices ? indices[i] : i;
+        if (e < 0 || e >= h->M) return h->fail("%s: index %d at position %d is out of range, the engine holds environments 0..%d", call, e, i, h->M - 1);
+        if (seen[e]) return h->fail("%s: environment %d is named twice", call, e);
+        seen[e] = 1;
+        idx[i] = e;
+    }
+    if (reads)
+        for (int i = 0; i < n; i++)
+            if (!h->se_ready || !h->se_was_reset[idx[i]])
+                return h->fail("%s: environment %d was never reset (dne_stepenv_reset or dne_stepenv_set_state comes first)", call, idx[i]);
+    return 0;
+}
+
+// dne_stepenv_reset (state == NULL) and dne_stepenv_set_state: one launch of the kind's reset kernel over the list
+static int se_reset(dne_handle *h, const char *call, int n, const int32_t *indices, const uint32_t *seeds, const double *state, const int32_t *steps,
+                    int max_steps, bool set) {
+    std::vector<int32_t> idx;
+    if (se_check(h, call, n, indices, false, idx)) return -1;
+    const stepenv::Dims d = se_dims(h);
+    const int limit = stepenv::step_limit(max_steps, d.own_limit);
+    if (set) {
+        if (!state || !steps) return h->fail("%s: state or steps missing", call);
+        for (int i = 0; i < n; i++)
+            if (steps[i] < 0 || steps[i] >= limit)
+                return h->fail("%s: %d steps taken at position %d, an environment under a limit of %d has taken 0..%d", call, steps[i], i, limit, limit - 1);
+    } else if (!h->maze && !seeds)
+        return h->fail("%s: a %s engine resets every environment from its seed, seeds is NULL", call, se_kind_name(h->L.kind));
+    if (se_alloc(h)) return -1;
+    HCHECK(h, hipMemcpyAsync(h->se_io_idx, idx.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if (set) {
+        HCHECK(h, hipMemcpyAsync(h->se_io_state, state, (size_t)n * d.state * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HCHECK(h, hipMemcpyAsync(h->se_io_steps, steps, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    } else if (!h->maze)
+        HCHECK(h, hipMemcpyAsync(h->se_io_seeds, seeds, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    const double *init = set ? h->se_io_state : nullptr;
+    if (h->maze)
+        hipLaunchKernelGGL(stepenv::k_stepenv_reset_maze, dim3((n + 3) / 4), dim3(64), 0, h->stream, h->se, se_maze_ctx(h), h->se_io_idx, n, init, h->se_io_steps, limit);
+    else if (h->cartpole)
+        hipLaunchKernelGGL(stepenv::k_stepenv_reset_cartpole, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->se, h->se_io_idx, n, h->se_io_seeds, init, h->se_io_steps, limit);
+    else
+        hipLaunchKernelGGL(stepenv::k_stepenv_reset_pendulum, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->se, h->se_io_idx, n, h->se_io_seeds, init, h->se_io_steps, limit);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < n; i++) h->se_was_reset[idx[i]] = 1;
+    return 0;
+}
+
+extern "C" int dne_stepenv_reset(dne_handle *h, int n, const int32_t *indices, const uint32_t *seeds, int max_steps) {
+    DeviceGuard dg(h);
+    return se_reset(h, "dne_stepenv_reset", n, indices, seeds, nullptr, nullptr, max_steps, false);
+}
+
+extern "C" int dne_stepenv_set_state(dne_handle *h, int n, const int32_t *indices, const double *state, const int32_t *steps, int max_steps) {
+    DeviceGuard dg(h);
+    return se_reset(h, "dne_stepenv_set_state", n, indices, nullptr, state, steps, max_steps, true);
+}
+
+static int se_step(dne_handle *h, const char *call, bool int_actions, int n, const int32_t *indices, const void *actions, float *reward, uint8_t *done) {
+    std::vector<int32_t> idx;
+    if (se_check(h, call, n, indices, true, idx)) return -1;
+    const stepenv::Dims d = se_dims(h);
+    if ((d.act_is_int != 0) != int_actions)
+        return h->fail("%s: a %s engine takes %s actions (dne_stepenv_step_%s)", call, se_kind_name(h->L.kind), d.act_is_int ? "int32" : "float",
+                       d.act_is_int ? "i32" : "f32");
+    if (!actions || !reward || !done) return h->fail("%s: actions, reward or done missing", call);
+    if (h->cartpole)
+        for (int i = 0; i < n; i++) {
+            const int32_t a = ((const int32_t *)actions)[i];
+            if (a != 0 && a != 1) return h->fail("%s: action %d at position %d, CartPole-v1 has actions 0 and 1", call, a, i);
+        }
+    HCHECK(h, hipMemcpyAsync(h->se_io_idx, idx.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HCHECK(h, hipMemcpyAsync(h->se_io_act, actions, (size_t)n * d.act * sizeof(float), hipMemcpyHostToDevice, h->stream));   // (an int32 is a float's size)
+    HCHECK(h, hipEventRecord(h->se_ev_a, h->stream));
+    if (h->maze)
+        hipLaunchKernelGGL(stepenv::k_stepenv_step_maze, dim3((n + 3) / 4), dim3(64), 0, h->stream, h->se, se_maze_ctx(h), h->se_io_idx, n, h->se_io_act, h->se_io_rew, h->se_io_done);
+    else if (h->cartpole)
+        hipLaunchKernelGGL(stepenv::k_stepenv_step_cartpole, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->se, h->se_io_idx, n, (const int32_t *)h->se_io_act, h->se_io_rew, h->se_io_done);
+    else
+        hipLaunchKernelGGL(stepenv::k_stepenv_step_pendulum, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->se, h->se_io_idx, n, h->se_io_act, h->se_io_rew, h->se_io_done);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipEventRecord(h->se_ev_b, h->stream));
+    HCHECK(h, hipMemcpyAsync(reward, h->se_io_rew, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipMemcpyAsync(done, h->se_io_done, n, hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    float ms = 0;
+    HCHECK(h, hipEventElapsedTime(&ms, h->se_ev_a, h->se_ev_b));
+    h->se_last_ms = ms;
+    return 0;
+}
+
+extern "C" int dne_stepenv_step_f32(dne_handle *h, int n, const int32_t *indices, const float *actions, float *reward, uint8_t *done) {
+    DeviceGuard dg(h);
+    return se_step(h, "dne_stepenv_step_f32", false, n, indices, actions, reward, done);
+}
+
+extern "C" int dne_stepenv_step_i32(dne_handle *h, int n, const int32_t *indices, const int32_t *actions, float *reward, uint8_t *done) {
+    DeviceGuard dg(h);
+    return se_step(h, "dne_stepenv_step_i32", true, n, indices, actions, reward, done);
+}
+
+// k_stepenv_gather over the list: whichever of the outputs is not NULL
+static int se_gather(dne_handle *h, const char *call, int n, const int32_t *indices, float *obs, double *state, int32_t *steps, uint8_t *done) {
+    std::vector<int32_t> idx;
+    if (se_check(h, call, n, indices, true, idx)) return -1;
+    const stepenv::Dims d = se_dims(h);
+    HCHECK(h, hipMemcpyAsync(h->se_io_idx, idx.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(stepenv::k_stepenv_gather, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->se, d.state, d.obs, h->se_io_idx, n, obs ? h->se_io_obs : nullptr,
+                       state ? h->se_io_state : nullptr, steps ? h->se_io_steps : nullptr, done ? h->se_io_done : nullptr);
+    HCHECK(h, hipGetLastError());
+    if (obs) HCHECK(h, hipMemcpyAsync(obs, h->se_io_obs, (size_t)n * d.obs * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (state) HCHECK(h, hipMemcpyAsync(state, h->se_io_state, (size_t)n * d.state * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (steps) HCHECK(h, hipMemcpyAsync(steps, h->se_io_steps, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (done) HCHECK(h, hipMemcpyAsync(done, h->se_io_done, n, hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int dne_stepenv_observation(dne_handle *h, int n, const int32_t *indices, float *obs) {
+    DeviceGuard dg(h);
+    if (!obs) return h->fail("dne_stepenv_observation: no output buffer");
+    return se_gather(h, "dne_stepenv_observation", n, indices, obs, nullptr, nullptr, nullptr);
+}
+
+extern "C" int dne_stepenv_get_state(dne_handle *h, int n, const int32_t *indices, double *state, int32_t *steps, uint8_t *done) {
+    DeviceGuard dg(h);
+    if (!state && !steps && !done) return h->fail("dne_stepenv_get_state: no output buffer");
+    return se_gather(h, "dne_stepenv_get_state", n, indices, nullptr, state, steps, done);
+}
+
+extern "C" double dne_stepenv_last_ms(dne_handle *h) { return h->episodic() ? h->se_last_ms : -1.0; }
+
+// the same header on the CPU: no handle, no GPU
+static int se_host_args(const char *call, int kind, int n, const float *header8, const float *lines, int n_walls, stepenv::MazeCtx *mz) {
+    stepenv::Dims d;
+    if (!stepenv::dims(kind, &d)) {
+        g_create_error = std::string(call) + ": kind " + std::to_string(kind) + " has no step-at-a-time environment (DNE_KIND_MAZE, DNE_KIND_CARTPOLE and DNE_KIND_PENDULUM have)";
+        return -1;
+    }
+    if (n < 1) { g_create_error = std::string(call) + ": n = " + std::to_string(n) + ", at least one environment is needed"; return -1; }
+    if (kind == DNE_KIND_MAZE) {
+        if (maze_check(&g_create_error, header8, lines, n_walls)) { g_create_error = std::string(call) + ": " + g_create_error; return -1; }
+        mz->hdr = maze_header(header8); mz->walls = lines; mz->nw = n_walls;
+    }
+    return 0;
+}
+
+extern "C" int dne_stepenv_reset_host(int kind, int n, const uint32_t *seeds, const float *header8, const float *lines, int n_walls, int max_steps,
+                                      double *state, int32_t *steps, int32_t *limit, uint8_t *done, float *obs) {
+    stepenv::MazeCtx mz{};
+    if (se_host_args("dne_stepenv_reset_host", kind, n, header8, lines, n_walls, &mz)) return -1;
+    if (!state || !steps || !limit || !done || !obs) { g_create_error = "dne_stepenv_reset_host: an output buffer is missing"; return -1; }
+    if (kind != DNE_KIND_MAZE && !seeds) { g_create_error = std::string("dne_stepenv_reset_host: ") + se_kind_name(kind) + " resets every environment from its seed, seeds is NULL"; return -1; }
+    return stepenv::reset_host(kind, n, seeds, &mz, max_steps, state, steps, limit, done, obs);
+}
+
+extern "C" int dne_stepenv_step_host(int kind, int n, const void *actions, const float *header8, const float *lines, int n_walls, double *state,
+                                     int32_t *steps, const int32_t *limit, uint8_t *done, float *reward, float *obs) {
+    stepenv::MazeCtx mz{};
+    if (se_host_args("dne_stepenv_step_host", kind, n, header8, lines, n_walls, &mz)) return -1;
+    if (!actions || !state || !steps || !limit || !done || !reward || !obs) { g_create_error = "dne_stepenv_step_host: a buffer is missing"; return -1; }
+    if (stepenv::step_host(kind, n, actions, &mz, state, steps, limit, done, reward, obs) == -2) {
+        for (int i = 0; i < n; i++) {
+            const int32_t a = ((const int32_t *)actions)[i];
+            if (a != 0 && a != 1) { g_create_error = "dne_stepenv_step_host: action " + std::to_string(a) + " at position " + std::to_string(i) + ", CartPole-v1 has actions 0 and 1"; break; }
+        }
+        return -1;
+    }
+    return 0;
+}
+
+extern "C" int dne_stepenv_observe_host(int kind, int n, const double *state, const float *header8, const float *lines, int n_walls, float *obs) {
+    stepenv::MazeCtx mz{};
+    if (se_host_args("dne_stepenv_observe_host", kind, n, header8, lines, n_walls, &mz)) return -1;
+    if (!state || !obs) { g_create_error = "dne_stepenv_observe_host: a buffer is missing"; return -1; }
+    return stepenv::observe_host(kind, n, state, &mz, obs);
 }
 
 // ------------------------------------------------------------------------------- evaluations by descriptor: antithetic pairs, members as set

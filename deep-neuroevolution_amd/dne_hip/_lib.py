@@ -81,7 +81,7 @@ class Profile(C.Structure):
 
 def build(force=False):
     """Compile libdne_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h", "cartpole.h", "pendulum.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h", "cartpole.h", "pendulum.h", "step_env.h")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dne_hip.h"))
     if os.environ.get("DNE_LIB_PATH"):
         # another build of the same ABI was asked for by name: `make` only knows the in-tree library, so running it here would
@@ -465,6 +465,79 @@ def pendulum_math_host(fn, x, a=0.0, b=1.0):
     return out
 
 
+STEPENV_KINDS = (KIND_MAZE, KIND_CARTPOLE, KIND_PENDULUM)   # the kinds with a step-at-a-time environment (csrc/step_env.h)
+
+
+def stepenv_dims(kind):
+    """dne_stepenv_dims: (observation width, action width, state doubles, actions are int32) of a kind; DneError for a kind without such an
+    environment"""
+    v = [C.c_int(0) for _ in range(4)]
+    _ck_host(load().dne_stepenv_dims(int(kind), *[C.byref(x) for x in v]))
+    return v[0].value, v[1].value, v[2].value, bool(v[3].value)
+
+
+def _stepenv_maze(kind, header, lines):
+    """(header pointer, lines pointer, n_walls, the arrays kept alive) for a host twin: the maze's, NULL / NULL / 0 for the other kinds"""
+    if int(kind) != KIND_MAZE:
+        return None, None, 0, ()
+    if header is None or lines is None:
+        raise DneError("stepenv: the maze's host twin needs header and lines (load_maze)")
+    header, lines = _maze_args(header, lines)
+    return _ptr(header, C.c_float), _ptr(lines, C.c_float), int(lines.shape[0]), (header, lines)
+
+
+def stepenv_reset_host(kind, n, seeds=None, max_steps=0, header=None, lines=None):
+    """dne_stepenv_reset_host: n environments of `kind` after reset -> (state float64 [n][S], steps int32 [n], limit int32 [n], done uint8 [n],
+    obs float32 [n][OBS]).  seeds uint32 [n] (the maze reads none); max_steps <= 0: the environment's own limit."""
+    obs_w, _, S, _ = stepenv_dims(kind)
+    n = int(n)
+    if seeds is not None:
+        seeds = _arr(seeds, np.uint32).reshape(-1)
+        if seeds.size != n:
+            raise DneError("stepenv_reset_host: %d environments, %d seeds" % (n, seeds.size))
+    hp, lp, nw, _keep = _stepenv_maze(kind, header, lines)
+    state = np.empty((max(n, 0), S), np.float64); steps = np.empty(max(n, 0), np.int32); limit = np.empty(max(n, 0), np.int32)
+    done = np.empty(max(n, 0), np.uint8); obs = np.empty((max(n, 0), obs_w), np.float32)
+    _ck_host(load().dne_stepenv_reset_host(int(kind), n, _ptr(seeds, C.c_uint32), hp, lp, nw, int(max_steps), _ptr(state, C.c_double),
+                                           _ptr(steps, C.c_int32), _ptr(limit, C.c_int32), _ptr(done, C.c_uint8), _ptr(obs, C.c_float)))
+    return state, steps, limit, done, obs
+
+
+def _stepenv_actions(kind, actions, n):
+    """the actions of one step as the C ABI takes them: float32 [n][2] (maze), int32 [n] (cart-pole), float32 [n] (pendulum)"""
+    _, act_w, _, is_int = stepenv_dims(kind)
+    a = _arr(actions, np.int32 if is_int else np.float32).reshape(-1)
+    if a.size != n * act_w:
+        raise DneError("stepenv: %d environments take %d action values, %d given" % (n, n * act_w, a.size))
+    return a, is_int
+
+
+def stepenv_step_host(kind, actions, state, steps, limit, done, obs, header=None, lines=None):
+    """dne_stepenv_step_host: one step of the n environments held in (state, steps, limit, done, obs) as stepenv_reset_host returned them, IN
+    PLACE -> reward float32 [n].  A done environment keeps every bit and earns 0."""
+    n = steps.shape[0]
+    for a, t in ((state, np.float64), (steps, np.int32), (limit, np.int32), (done, np.uint8), (obs, np.float32)):
+        if a.dtype != t or not a.flags.c_contiguous:
+            raise DneError("stepenv_step_host: the batch arrays are stepenv_reset_host's own (contiguous %s expected)" % np.dtype(t).name)
+    a, is_int = _stepenv_actions(kind, actions, n)
+    hp, lp, nw, _keep = _stepenv_maze(kind, header, lines)
+    reward = np.empty(n, np.float32)
+    _ck_host(load().dne_stepenv_step_host(int(kind), int(n), C.cast(_ptr(a, C.c_int32 if is_int else C.c_float), C.c_void_p), hp, lp, nw,
+                                          _ptr(state, C.c_double), _ptr(steps, C.c_int32), _ptr(limit, C.c_int32), _ptr(done, C.c_uint8),
+                                          _ptr(reward, C.c_float), _ptr(obs, C.c_float)))
+    return reward
+
+
+def stepenv_observe_host(kind, state, header=None, lines=None):
+    """dne_stepenv_observe_host: the observations float32 [n][OBS] of states float64 [n][S]"""
+    obs_w, _, S, _ = stepenv_dims(kind)
+    state = _arr(state, np.float64).reshape(-1, S)
+    hp, lp, nw, _keep = _stepenv_maze(kind, header, lines)
+    obs = np.empty((state.shape[0], obs_w), np.float32)
+    _ck_host(load().dne_stepenv_observe_host(int(kind), int(state.shape[0]), _ptr(state, C.c_double), hp, lp, nw, _ptr(obs, C.c_float)))
+    return obs
+
+
 def _ptr(a, t):
     return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
 
@@ -785,6 +858,72 @@ class Engine:
         steps = C.c_int32(0)
         self._ck(self.lib.dne_cartpole_debug_trace(self.h, int(member), int(tslimit), _ptr(init, C.c_double), _ptr(out, C.c_double), C.byref(steps)))
         return out[:steps.value]
+
+    # ---- the maze, the cart-pole and the pendulum one step at a time (csrc/step_env.h): a batch of max_members environments apart from evaluations
+    def _stepenv_idx(self, indices, n=None):
+        """(pointer or None, count, the array kept alive): indices=None names environments 0 .. n - 1 (the whole batch without n)"""
+        if indices is None:
+            return None, int(self.max_members if n is None else n), None
+        idx = _arr(indices, np.int32).reshape(-1)
+        return _ptr(idx, C.c_int32), int(idx.size), idx
+
+    def stepenv_reset(self, indices=None, seeds=None, max_steps=0, n=None):
+        """dne_stepenv_reset: the named environments restart (the maze from its header; the others from seeds uint32 [n]); steps 0, done 0,
+        limit = min(max_steps, the kind's own), max_steps <= 0 meaning the own limit"""
+        ip, n, _keep = self._stepenv_idx(indices, n)
+        if seeds is not None:
+            seeds = _arr(seeds, np.uint32).reshape(-1)
+            if seeds.size != n:
+                raise DneError("stepenv_reset: %d environments, %d seeds" % (n, seeds.size))
+        self._ck(self.lib.dne_stepenv_reset(self.h, n, ip, _ptr(seeds, C.c_uint32), int(max_steps)))
+
+    def stepenv_step(self, actions, indices=None, as_int=None):
+        """dne_stepenv_step_f32 / _i32 by the dtype the kind takes: one step of the named environments under actions (maze float32 [n][2],
+        cart-pole int32 [n], pendulum float32 [n]) -> (reward float32 [n], done bool [n]).  as_int names the entry point outright (the engine
+        refuses the one its kind does not take)."""
+        is_int = bool(as_int) if as_int is not None else stepenv_dims(self.kind)[3] if self.kind in STEPENV_KINDS else np.asarray(actions).dtype.kind in "iu"
+        a = _arr(actions, np.int32 if is_int else np.float32)
+        ip, n, _keep = self._stepenv_idx(indices, a.shape[0] if a.ndim else 1)
+        if as_int is None and self.kind in STEPENV_KINDS and a.size != n * stepenv_dims(self.kind)[1]:
+            raise DneError("stepenv_step: %d environments take %d action values, %d given" % (n, n * stepenv_dims(self.kind)[1], a.size))
+        rew = np.empty(n, np.float32); done = np.empty(n, np.uint8)
+        if is_int:
+            self._ck(self.lib.dne_stepenv_step_i32(self.h, n, ip, _ptr(a, C.c_int32), _ptr(rew, C.c_float), _ptr(done, C.c_uint8)))
+        else:
+            self._ck(self.lib.dne_stepenv_step_f32(self.h, n, ip, _ptr(a, C.c_float), _ptr(rew, C.c_float), _ptr(done, C.c_uint8)))
+        return rew, done.astype(bool)
+
+    def stepenv_observation(self, indices=None, n=None):
+        """dne_stepenv_observation: what the policy sees next, float32 [n][OBS] in the order of the list"""
+        ip, n, _keep = self._stepenv_idx(indices, n)
+        w = stepenv_dims(self.kind)[0] if self.kind in STEPENV_KINDS else 1
+        out = np.empty((max(n, 0), w), np.float32)
+        self._ck(self.lib.dne_stepenv_observation(self.h, n, ip, _ptr(out, C.c_float)))
+        return out
+
+    def stepenv_state(self, indices=None, n=None):
+        """dne_stepenv_get_state: (state float64 [n][S], steps int32 [n], done bool [n])"""
+        ip, n, _keep = self._stepenv_idx(indices, n)
+        S = stepenv_dims(self.kind)[2] if self.kind in STEPENV_KINDS else 1
+        state = np.empty((max(n, 0), S), np.float64); steps = np.empty(max(n, 0), np.int32); done = np.empty(max(n, 0), np.uint8)
+        self._ck(self.lib.dne_stepenv_get_state(self.h, n, ip, _ptr(state, C.c_double), _ptr(steps, C.c_int32), _ptr(done, C.c_uint8)))
+        return state, steps, done.astype(bool)
+
+    def stepenv_set_state(self, state, steps=None, indices=None, max_steps=0):
+        """dne_stepenv_set_state: the named environments are put into states float64 [n][S] with `steps` already taken (default 0); the
+        observation is recomputed, done cleared, the limit set as by a reset"""
+        S = stepenv_dims(self.kind)[2] if self.kind in STEPENV_KINDS else 1
+        state = _arr(state, np.float64).reshape(-1, S)
+        ip, n, _keep = self._stepenv_idx(indices, state.shape[0])
+        steps = np.zeros(n, np.int32) if steps is None else _arr(steps, np.int32).reshape(-1)
+        if state.shape[0] != n or steps.size != n:
+            raise DneError("stepenv_set_state: %d environments, %d states, %d step counts" % (n, state.shape[0], steps.size))
+        self._ck(self.lib.dne_stepenv_set_state(self.h, n, ip, _ptr(state, C.c_double), _ptr(steps, C.c_int32), int(max_steps)))
+
+    def stepenv_last_ms(self):
+        """the last step kernel between two device events, milliseconds (-1 before the first)"""
+        self.lib.dne_stepenv_last_ms.restype = C.c_double
+        return float(self.lib.dne_stepenv_last_ms(self.h))
 
     # ---- novelty on the hard maze (csrc/maze_novelty.h): BCs are final (x, y) points, the archive lives on the device
     def _maze_points(self, xy, n):

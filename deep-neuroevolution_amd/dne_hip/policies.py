@@ -485,7 +485,8 @@ class MujocoPolicy(Policy):
     """policies.py:122-217 with connection_type 'ff' and two hidden layers of one width, on the pendulum swing-up (the simulator the reference
     drives it on is not available): clip((ob - ob_mean) / ob_std, +-5) -> dense H, nonlin -> dense H, nonlin -> out, continuous or uniform bins;
     Gaussian action noise of ac_noise_std in training rollouts.  The network is csrc/pendulum.h: the engine's kernel for whole populations, the
-    same text compiled for the CPU for act / rollout of the single current theta."""
+    same text compiled for the CPU for act / rollout of the single current theta.  (The environment itself can be stepped on the device under
+    any policy's actions: envs.make('Pendulum-v0', n), csrc/step_env.h.)"""
     kind = _lib.KIND_PENDULUM
 
     def __init__(self, ob_space, ac_space, ac_bins, ac_noise_std, nonlin_type, hidden_dims, connection_type, engine=None):

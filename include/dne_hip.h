@@ -417,6 +417,50 @@ int dne_pendulum_forward_host(const float *theta, const float *obs, int n, int h
                               const float *std, float *x, float *h1, float *h2, float *out, float *action);
 int dne_pendulum_math_host(int fn, const double *x, int n, float a, float b, double *out);
 
+/* ---- the maze, the cart-pole and the pendulum one step at a time (csrc/step_env.h) ------------------------------
+ * The seam of gym_tensorflow/tf_env.py (reset / step / observation / final_state apart from the model) on the three whole-episode kinds: a
+ * batch of max_members environments per handle that persists between calls and moves one step per call under actions the CALLER supplies, so
+ * any policy can drive them.  It is allocated by the first call that needs it and is apart from evaluations: dne_eval_members, dne_es_eval
+ * and dne_maze_ga_eval leave it as it was, and no call here touches members, accumulators or final states.
+ * One environment is a state of S doubles, the steps taken, its step limit, done and its last observation:
+ *   DNE_KIND_MAZE      S 7: x, y, heading, speed, ang_vel, collide, collisions (maze.h's floats and ints, widened exactly); 11 observations;
+ *                      action float[2]; own limit 400
+ *   DNE_KIND_CARTPOLE  S 4: x, x_dot, theta, theta_dot; 4 observations; action int32 in {0, 1}; own limit 500
+ *   DNE_KIND_PENDULUM  S 2: theta, theta_dot; 3 observations (raw: normalising is the policy's business); action float[1]; own limit 200
+ * dne_stepenv_dims: the four widths of a kind, no handle needed (-1 for every other kind; a NULL output is skipped).
+ * indices [n] name the environments of a call, distinct, each in 0 .. max_members - 1; NULL means 0 .. n - 1.  Every per-call array is [n] in
+ * the order of that list, and environments the list does not name keep every bit.
+ * dne_stepenv_reset: the maze restarts from its header (seeds is not read and may be NULL), the other two from reset_state(seeds[i]); steps 0,
+ *   done 0, limit = min(max_steps, own limit), max_steps <= 0 meaning the own limit.
+ * dne_stepenv_step_f32 (maze, pendulum) / _i32 (cart-pole): one step each.  Maze: reward = -(distance to the goal) on the step that makes
+ *   steps == 400 and 0 otherwise, done when steps == limit.  Cart-pole: reward 1 per step taken, done when a threshold is crossed (strictly)
+ *   or steps == limit.  Pendulum: the step's float32 reward, done when steps == limit.  A done environment stepped again: reward 0, done 1,
+ *   state, steps and observation unchanged.
+ * dne_stepenv_observation: what a whole-episode kernel's policy would see next.  dne_stepenv_get_state: state [n][S], steps, done (a NULL
+ *   output is skipped).  dne_stepenv_set_state: the analogue of dne_env_set_ram -- states no reset gives (rounded to the maze's own types),
+ *   steps[i] in 0 .. limit - 1; the observation is recomputed and done cleared.
+ * dne_stepenv_last_ms: the last step kernel between two device events, in milliseconds (-1 before the first, or on another kind).
+ * All calls are ordered on the engine's stream and return when their outputs are on the host.  Refused by name, the batch left as it was: a
+ * handle of another kind; _i32 on the maze or the pendulum, _f32 on the cart-pole; n outside 1 .. max_members; an index out of range or named
+ * twice; stepping, observing or reading an environment that was never reset; the maze before dne_maze_set_walls; a cart-pole action outside
+ * {0, 1} (checked on the host before the launch); NULL seeds on the cart-pole or the pendulum.  dne_env_* keep refusing the three kinds.
+ * The CPU twins need no handle and no GPU (errors through dne_last_error(NULL)); they work on the caller's arrays of n environments (header8 /
+ * lines / n_walls for the maze, else NULL / 0) and run the same header: dne_stepenv_reset_host, dne_stepenv_step_host (actions: float [n][2],
+ * int32 [n] or float [n] by kind), dne_stepenv_observe_host (the observations of given states). */
+int dne_stepenv_dims(int kind, int *obs, int *act, int *state, int *act_is_int);
+int dne_stepenv_reset(dne_handle *h, int n, const int32_t *indices /*[n] or NULL*/, const uint32_t *seeds /*[n]; maze: may be NULL*/, int max_steps);
+int dne_stepenv_step_f32(dne_handle *h, int n, const int32_t *indices, const float *actions /*[n][act]*/, float *reward, uint8_t *done);
+int dne_stepenv_step_i32(dne_handle *h, int n, const int32_t *indices, const int32_t *actions /*[n]*/, float *reward, uint8_t *done);
+int dne_stepenv_observation(dne_handle *h, int n, const int32_t *indices, float *obs /*[n][obs]*/);
+int dne_stepenv_get_state(dne_handle *h, int n, const int32_t *indices, double *state /*[n][S]*/, int32_t *steps, uint8_t *done);
+int dne_stepenv_set_state(dne_handle *h, int n, const int32_t *indices, const double *state, const int32_t *steps, int max_steps);
+double dne_stepenv_last_ms(dne_handle *h);
+int dne_stepenv_reset_host(int kind, int n, const uint32_t *seeds, const float *header8, const float *lines, int n_walls, int max_steps,
+                           double *state, int32_t *steps, int32_t *limit, uint8_t *done, float *obs);
+int dne_stepenv_step_host(int kind, int n, const void *actions, const float *header8, const float *lines, int n_walls, double *state,
+                          int32_t *steps, const int32_t *limit, uint8_t *done, float *reward, float *obs);
+int dne_stepenv_observe_host(int kind, int n, const double *state, const float *header8, const float *lines, int n_walls, float *obs);
+
 /* ---- novelty on the hard maze (csrc/maze_novelty.h) -------------------------------------------
  * A behaviour characterisation is one float32 point (x, y): a navigator's final position.  nses.py:12-32 on such points: for member p and
  * archive point a, d = sqrt(dx*dx + dy*dy) in double with dx = (double)ax - (double)px (unfused, correctly rounded sqrt); novelty = the
