@@ -34,6 +34,7 @@
 #include "maze_ga.h"
 #include "cartpole.h"
 #include "pendulum.h"
+#include "mjmaze.h"
 #include "step_env.h"
 
 using namespace dne;
@@ -52,6 +53,7 @@ static thread_local std::string g_create_error;
         if ((h)->maze) return (h)->fail("%s is not available on a DNE_KIND_MAZE engine (kind %d): the hard maze has no Atari frames, reference batch, genomes or byte BCs", call, DNE_KIND_MAZE); \
         if ((h)->cartpole) return (h)->fail("%s is not available on a DNE_KIND_CARTPOLE engine (kind %d): the cart-pole has no Atari frames, reference batch, genomes or byte BCs", call, DNE_KIND_CARTPOLE); \
         if ((h)->pendulum) return (h)->fail("%s is not available on a DNE_KIND_PENDULUM engine (kind %d): the pendulum has no Atari frames, reference batch, genomes or byte BCs", call, DNE_KIND_PENDULUM); \
+        if ((h)->mjmaze) return (h)->fail("%s is not available on a DNE_KIND_MJMAZE engine (kind %d): MujocoPolicy on the hard maze has no Atari frames, reference batch, genomes or byte BCs", call, DNE_KIND_MJMAZE); \
     } while (0)
 
 // ------------------------------------------------------------------------------- env kernels
@@ -680,7 +682,13 @@ struct dne_handle {
     int32_t *se_io_idx = nullptr, *se_io_steps = nullptr; uint32_t *se_io_seeds = nullptr; float *se_io_act = nullptr, *se_io_rew = nullptr, *se_io_obs = nullptr;
     uint8_t *se_io_done = nullptr; double *se_io_state = nullptr;
     hipEvent_t se_ev_a = nullptr, se_ev_b = nullptr; double se_last_ms = -1.0;   // the last step kernel between two device events
-    bool episodic() const { return maze || cartpole || pendulum; }   // a whole episode per member in one launch: what dne_es_eval and the record calls accept beside the Atari kinds
+    // DNE_KIND_MJMAZE: MujocoPolicy on the hard maze, whole episodes in k_mjmaze_rollout (csrc/mjmaze.h).  It shares the maze's walls, final
+    // positions and archive (maze_*, mzn_*) and the pendulum's shape, per-member options and statistics buffers (pd_hidden, pd_nl, pd_acoff,
+    // pd_flag, pd_sum, pd_sumsq, pd_count, pd_opt_n, pd_has_*, pd_host_off); mj_opt holds its own 11 means and deviations
+    bool mjmaze = false;
+    mjmaze::Options mj_opt{};
+    bool mj_stat_set = false;
+    bool episodic() const { return maze || cartpole || pendulum || mjmaze; }   // a whole episode per member in one launch: what dne_es_eval and the record calls accept beside the Atari kinds
     bool large = false;              // DNE_KIND_GA_LARGE: y1 [441][32], y2 / y3 [121][64] (conv3 output), y3t = the 512 fc outputs
     float *y1r[2] = {nullptr, nullptr}, *y2r[2] = {nullptr, nullptr}, *y3pr[2] = {nullptr, nullptr};   // reference pass scratch, two ways
     float *fr1[2] = {nullptr, nullptr}, *fr2[2] = {nullptr, nullptr};   // per-frame batch-norm moments of conv1 / conv2 ([rows][2][C])
@@ -846,7 +854,7 @@ static void make_layout(int kind, int nact, Layout *L) {
     memset(L, 0, sizeof(*L));
     L->kind = kind; L->nact = nact;
     auto take = [&](int n) { int r = o; o += n; return r; };
-    if (kind == DNE_KIND_MAZE || kind == DNE_KIND_CARTPOLE || kind == DNE_KIND_PENDULUM) {   // (DNE_KIND_PENDULUM: P depends on the hidden width, dne_create sets it) SimpleClassifier (models/simple.py:29-35): csrc/maze.h and csrc/cartpole.h hold its offsets
+    if (kind == DNE_KIND_MAZE || kind == DNE_KIND_CARTPOLE || kind == DNE_KIND_PENDULUM || kind == DNE_KIND_MJMAZE) {   // (DNE_KIND_PENDULUM, DNE_KIND_MJMAZE: P depends on the hidden width, dne_create sets it) SimpleClassifier (models/simple.py:29-35): csrc/maze.h and csrc/cartpole.h hold its offsets
         L->c1w = L->c1b = L->c2w = L->c2b = L->c3w = L->c3b = L->fcw = L->fcb = L->ow = L->ob = -1;
         L->bn1b = L->bn1g = L->bn2b = L->bn2g = L->bn3b = L->bn3g = -1;
         o = kind == DNE_KIND_MAZE ? maze::NPARAMS : kind == DNE_KIND_CARTPOLE ? cartpole::NPARAMS : 0;
@@ -956,6 +964,7 @@ extern "C" int dne_num_params(int kind, int nact) {
     if (kind == DNE_KIND_MAZE && nact != maze::ACT) return -1;   // the maze policy has two raw outputs, nothing else
     if (kind == DNE_KIND_CARTPOLE && nact != cartpole::ACT) return -1;   // CartPole-v1 has two actions
     if (kind == DNE_KIND_PENDULUM) return -1;   // P depends on the hidden width: dne_pendulum_num_params
+    if (kind == DNE_KIND_MJMAZE) return -1;     // likewise: dne_mjmaze_num_params
     Layout L;
     make_layout(kind, nact, &L);
     return L.P;
@@ -976,6 +985,10 @@ extern "C" int dne_debug_plan(int kind, int n_actions, const dne_plan_facts *fac
     }
     if (kind == DNE_KIND_PENDULUM) {
         g_create_error = "dne_debug_plan: a DNE_KIND_PENDULUM engine (kind 6) has no lock-step windows, an evaluation is one k_pendulum_rollout launch";
+        return -1;
+    }
+    if (kind == DNE_KIND_MJMAZE) {
+        g_create_error = "dne_debug_plan: a DNE_KIND_MJMAZE engine (kind 7) has no lock-step windows, an evaluation is one k_mjmaze_rollout launch";
         return -1;
     }
     const Knobs k = engine_knobs(kind, n_actions);
@@ -1003,6 +1016,10 @@ extern "C" int dne_debug_plan_act(int kind, int n_actions, const dne_plan_facts 
     }
     if (kind == DNE_KIND_PENDULUM) {
         g_create_error = "dne_debug_plan_act: a DNE_KIND_PENDULUM engine (kind 6) has no dne_act";
+        return -1;
+    }
+    if (kind == DNE_KIND_MJMAZE) {
+        g_create_error = "dne_debug_plan_act: a DNE_KIND_MJMAZE engine (kind 7) has no dne_act";
         return -1;
     }
     if (n < 1) {
@@ -1064,7 +1081,7 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
     }
     if (cfg->max_members <= 0 || (cfg->n_actions <= 1 && !(cfg->policy_kind == DNE_KIND_PENDULUM && cfg->n_actions == 1)) ||
         (!es_like(cfg->policy_kind) && cfg->policy_kind != DNE_KIND_GA && cfg->policy_kind != DNE_KIND_GA_LARGE && cfg->policy_kind != DNE_KIND_MAZE &&
-         cfg->policy_kind != DNE_KIND_CARTPOLE && cfg->policy_kind != DNE_KIND_PENDULUM)) {
+         cfg->policy_kind != DNE_KIND_CARTPOLE && cfg->policy_kind != DNE_KIND_PENDULUM && cfg->policy_kind != DNE_KIND_MJMAZE)) {
         g_create_error = "dne_create: bad config";
         return -1;
     }
@@ -1117,6 +1134,31 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
             return -1;
         }
     }
+    if (cfg->policy_kind == DNE_KIND_MJMAZE) {   // the shape as on DNE_KIND_PENDULUM; n_actions = the outputs: 2, or 2 B
+        const int hidden = cfg->reserved[0], mode = cfg->reserved[1], nl = cfg->reserved[2];
+        if (!pendulum::hidden_ok(hidden)) {
+            g_create_error = "dne_create: DNE_KIND_MJMAZE is built for two hidden layers of width 64, 128 or 256; hidden width " + std::to_string(hidden) + " is refused";
+            return -1;
+        }
+        if (mode != pendulum::AC_CONTINUOUS && mode != pendulum::AC_UNIFORM) {
+            g_create_error = "dne_create: DNE_KIND_MJMAZE has action modes 0 (continuous) and 1 (uniform bins); mode " + std::to_string(mode) + " is refused";
+            return -1;
+        }
+        if (nl != pendulum::NL_TANH && nl != pendulum::NL_RELU) {
+            g_create_error = "dne_create: DNE_KIND_MJMAZE has nonlinearities 0 (tanh) and 1 (relu); nonlinearity " + std::to_string(nl) + " is refused";
+            return -1;
+        }
+        if (!mjmaze::shape_ok(hidden, cfg->n_actions, mode, nl)) {
+            g_create_error = "dne_create: DNE_KIND_MJMAZE has 2 outputs under the continuous action and 2 B for B = 2..8 uniform bins a dimension, n_actions " +
+                             std::to_string(cfg->n_actions) + " under mode " + std::to_string(mode) + " is refused";
+            return -1;
+        }
+        if (cfg->bc_final_only || cfg->record_bc) {
+            g_create_error = "dne_create: record_bc / bc_final_only are not available on a DNE_KIND_MJMAZE engine (kind 7): its behaviour characterisation is "
+                             "the final (x, y), and dne_maze_final_state has it for every member";
+            return -1;
+        }
+    }
     dne_handle *h = new dne_handle();
     h->cfg = *cfg;
     auto bail = [&](int) { g_create_error = h->err; delete h; return -1; };
@@ -1137,7 +1179,7 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         env_int("DNE_STAGED_COPY", 0, 1, &sc);
         h->staged_copies = sc != 0;
     }
-    if (cfg->policy_kind == DNE_KIND_MAZE || cfg->policy_kind == DNE_KIND_CARTPOLE || cfg->policy_kind == DNE_KIND_PENDULUM) {
+    if (cfg->policy_kind == DNE_KIND_MAZE || cfg->policy_kind == DNE_KIND_CARTPOLE || cfg->policy_kind == DNE_KIND_PENDULUM || cfg->policy_kind == DNE_KIND_MJMAZE) {
         // theta slots, member descriptors and accumulators, the walls (the cart-pole: seeds and final states), the reduce and optimizer
         // buffers: no frame, activation or ring buffer
         h->maze = cfg->policy_kind == DNE_KIND_MAZE;
@@ -1149,6 +1191,13 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
             h->pd_opt.n_out = cfg->n_actions; h->pd_opt.ac_mode = cfg->reserved[1];
             for (int i = 0; i < pendulum::OBS; i++) h->pd_opt.mean[i] = h->pd_opt.std[i] = NAN;   // policies.py:138-141
             h->L.P = pendulum::offsets(h->pd_hidden, cfg->n_actions).P;
+        }
+        h->mjmaze = cfg->policy_kind == DNE_KIND_MJMAZE;
+        if (h->mjmaze) {
+            h->pd_hidden = cfg->reserved[0]; h->pd_nl = cfg->reserved[2];
+            h->mj_opt.n_out = cfg->n_actions; h->mj_opt.ac_mode = cfg->reserved[1];
+            for (int i = 0; i < mjmaze::OBS; i++) h->mj_opt.mean[i] = h->mj_opt.std[i] = NAN;   // policies.py:138-141
+            h->L.P = mjmaze::offsets(h->pd_hidden, cfg->n_actions).P;
         }
         h->M = cfg->max_members;
         h->base_stride = ((size_t)h->L.P + 63) / 64 * 64;
@@ -1168,6 +1217,13 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         } else if (h->cartpole) {
             CH(h->alloc(&h->cp_state, 4 * M, "cartpole_state")); CH(h->alloc(&h->seeds, M, "seeds"));
             CH(hipMemset(h->cp_state, 0, 4 * M * sizeof(double))); CH(hipMemset(h->seeds, 0, M * sizeof(uint32_t)));
+        } else if (h->mjmaze) {
+            CH(h->alloc(&h->maze_xy, 2 * M, "maze_xy")); CH(h->alloc(&h->maze_walls, maze::MAX_WALLS * 4, "maze_walls"));
+            CH(h->alloc(&h->pd_sum, mjmaze::OBS * M, "mjmaze_ob_sum")); CH(h->alloc(&h->pd_sumsq, mjmaze::OBS * M, "mjmaze_ob_sumsq")); CH(h->alloc(&h->pd_count, M, "mjmaze_ob_count"));
+            CH(h->alloc(&h->pd_acoff, M, "mjmaze_ac_off")); CH(h->alloc(&h->pd_flag, M, "mjmaze_stat_flag"));
+            CH(hipMemset(h->maze_xy, 0, 2 * M * sizeof(float)));
+            CH(hipMemset(h->pd_sum, 0, mjmaze::OBS * M * sizeof(double))); CH(hipMemset(h->pd_sumsq, 0, mjmaze::OBS * M * sizeof(double))); CH(hipMemset(h->pd_count, 0, M * sizeof(int32_t)));
+            CH(hipMemset(h->pd_acoff, 0xff, M * sizeof(int64_t))); CH(hipMemset(h->pd_flag, 0, M));
         } else {
             CH(h->alloc(&h->pd_state, 2 * M, "pendulum_state")); CH(h->alloc(&h->seeds, M, "seeds"));
             CH(h->alloc(&h->pd_sum, 3 * M, "pendulum_ob_sum")); CH(h->alloc(&h->pd_sumsq, 3 * M, "pendulum_ob_sumsq")); CH(h->alloc(&h->pd_count, M, "pendulum_ob_count"));
@@ -1185,7 +1241,7 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         CH(h->alloc(&h->scratch_f, h->scratch_cap, "scratch_f")); CH(h->alloc(&h->scratch_i, h->scratch_cap, "scratch_i"));
         CH(hipEventCreate(&h->ev_a)); CH(hipEventCreate(&h->ev_b));
         CH(hipDeviceSynchronize());
-        h->trace("engine created: kind %d (%s), %d members, %zu device buffers", cfg->policy_kind, h->maze ? "hard maze" : h->cartpole ? "cart-pole" : "pendulum", h->M, h->blocks.size());
+        h->trace("engine created: kind %d (%s), %d members, %zu device buffers", cfg->policy_kind, h->maze ? "hard maze" : h->cartpole ? "cart-pole" : h->pendulum ? "pendulum" : "MujocoPolicy on the hard maze", h->M, h->blocks.size());
         *out = h;
         return 0;
     }
@@ -2260,9 +2316,14 @@ static int needs_maze(dne_handle *h, const char *call) {   // (a DNE_KIND_CARTPO
     return h->maze ? 0 : h->fail("%s needs a DNE_KIND_MAZE engine (this one: kind %d)", call, h->L.kind);
 }
 
+// ... and the calls DNE_KIND_MJMAZE shares with it: the walls, the final positions, the archive and dne_maze_novelty
+static int needs_maze_env(dne_handle *h, const char *call) {
+    return h->mjmaze ? 0 : needs_maze(h, call);   // (every other kind: the refusal it always got)
+}
+
 extern "C" int dne_maze_set_walls(dne_handle *h, const float *header8, const float *lines, int n) {
     DeviceGuard dg(h);
-    if (needs_maze(h, "dne_maze_set_walls")) return -1;
+    if (needs_maze_env(h, "dne_maze_set_walls")) return -1;
     if (maze_check(&h->err, header8, lines, n)) return -1;
     HCHECK(h, hipStreamSynchronize(h->stream));
     HCHECK(h, hipMemcpy(h->maze_walls, lines, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice));
@@ -2323,7 +2384,7 @@ static int maze_eval(dne_handle *h, int n, int tslimit, float *returns, float *s
 
 extern "C" int dne_maze_final_state(dne_handle *h, int n, float *xy) {
     DeviceGuard dg(h);
-    if (needs_maze(h, "dne_maze_final_state")) return -1;
+    if (needs_maze_env(h, "dne_maze_final_state")) return -1;
     if (n < 1 || n > h->maze_last_n) return h->fail("dne_maze_final_state: %d members asked for, the last evaluation ran %d", n, h->maze_last_n);
     HCHECK(h, hipStreamSynchronize(h->stream));
     HCHECK(h, hipMemcpy(xy, h->maze_xy, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost));
@@ -2601,7 +2662,7 @@ static int mzn_archive_room(dne_handle *h, const char *call, int more) {
 
 extern "C" int dne_maze_archive_append(dne_handle *h, const float *xy, int n) {
     DeviceGuard dg(h);
-    if (needs_maze(h, "dne_maze_archive_append")) return -1;
+    if (needs_maze_env(h, "dne_maze_archive_append")) return -1;
     if (mzn_check_members(h, "dne_maze_archive_append", xy, n)) return -1;
     if (mzn_archive_room(h, "dne_maze_archive_append", n)) return -1;
     const size_t have = (size_t)h->mzn_arch_n;
@@ -2617,19 +2678,19 @@ extern "C" int dne_maze_archive_append(dne_handle *h, const float *xy, int n) {
 
 extern "C" int dne_maze_archive_clear(dne_handle *h) {
     DeviceGuard dg(h);
-    if (needs_maze(h, "dne_maze_archive_clear")) return -1;
+    if (needs_maze_env(h, "dne_maze_archive_clear")) return -1;
     h->mzn_arch_n = 0;   // (the buffer stays; a later append lands behind every call already on the stream)
     return 0;
 }
 
 extern "C" int dne_maze_archive_size(dne_handle *h) {
-    if (needs_maze(h, "dne_maze_archive_size")) return -1;
+    if (needs_maze_env(h, "dne_maze_archive_size")) return -1;
     return h->mzn_arch_n;
 }
 
 extern "C" int dne_maze_archive_get(dne_handle *h, float *xy, int cap) {
     DeviceGuard dg(h);
-    if (needs_maze(h, "dne_maze_archive_get")) return -1;
+    if (needs_maze_env(h, "dne_maze_archive_get")) return -1;
     if (cap < h->mzn_arch_n) return h->fail("dne_maze_archive_get: room for %d points, the archive holds %d", cap, h->mzn_arch_n);
     if (h->mzn_arch_n > 0) {
         if (!xy) return h->fail("dne_maze_archive_get: no buffer");
@@ -2640,8 +2701,8 @@ extern "C" int dne_maze_archive_get(dne_handle *h, float *xy, int cap) {
 }
 
 // what both scoring calls refuse alike, before the refusals of their own
-static int mzn_score_args(dne_handle *h, const char *call, const float *xy, int n, int k) {
-    if (needs_maze(h, call)) return -1;
+static int mzn_score_args(dne_handle *h, const char *call, bool pool, const float *xy, int n, int k) {
+    if (pool ? needs_maze(h, call) : needs_maze_env(h, call)) return -1;   // (pool novelty is GA-NS's: DNE_KIND_MAZE only)
     if (mzn_check_members(h, call, xy, n)) return -1;
     if (k < 1) return h->fail("%s: k = %d, at least one neighbour is needed", call, k);
     if (k > DNE_MAZE_NOVELTY_KMAX) return h->fail("%s: k = %d, the kernel keeps at most DNE_MAZE_NOVELTY_KMAX = %d neighbours", call, k, DNE_MAZE_NOVELTY_KMAX);
@@ -2674,7 +2735,7 @@ static int mzn_score(dne_handle *h, const char *call, bool pool, const float *xy
 
 extern "C" int dne_maze_novelty(dne_handle *h, const float *xy, int n, int k, double *out) {
     DeviceGuard dg(h);
-    if (mzn_score_args(h, "dne_maze_novelty", xy, n, k)) return -1;
+    if (mzn_score_args(h, "dne_maze_novelty", false, xy, n, k)) return -1;
     if (h->mzn_arch_n < 1) return h->fail("dne_maze_novelty: the archive is empty (dne_maze_archive_append)");
     return mzn_score(h, "dne_maze_novelty", false, xy, n, std::min(k, h->mzn_arch_n), out);
 }
@@ -2682,7 +2743,7 @@ extern "C" int dne_maze_novelty(dne_handle *h, const float *xy, int n, int k, do
 // pool novelty (GA-NS): every member against the archive and the other members
 extern "C" int dne_maze_novelty_pool(dne_handle *h, const float *xy, int n, int k, double *out) {
     DeviceGuard dg(h);
-    if (mzn_score_args(h, "dne_maze_novelty_pool", xy, n, k)) return -1;
+    if (mzn_score_args(h, "dne_maze_novelty_pool", true, xy, n, k)) return -1;
     if (h->mzn_arch_n + (n - 1) < 1) return h->fail("dne_maze_novelty_pool: the pool is empty (one member, no archive point)");
     if ((size_t)h->mzn_arch_n + (size_t)n > (size_t)INT_MAX / 2) return h->fail("dne_maze_novelty_pool: %zu combined slots would not fit an int", (size_t)h->mzn_arch_n + (size_t)n);
     return mzn_score(h, "dne_maze_novelty_pool", true, xy, n, std::min(k, h->mzn_arch_n + n - 1), out);
@@ -3096,6 +3157,216 @@ extern "C" int dne_pendulum_math_host(int fn, const double *x, int n, float a, f
     return 0;
 }
 
+// ------------------------------------------------------------------------------- MujocoPolicy on the hard maze (csrc/mjmaze.h)
+static int needs_mjmaze(dne_handle *h, const char *call) {
+    return h->mjmaze ? 0 : h->fail("%s needs a DNE_KIND_MJMAZE engine (this one: kind %d)", call, h->L.kind);
+}
+
+extern "C" int dne_mjmaze_num_params(int hidden, int n_out) {
+    if (!pendulum::hidden_ok(hidden) || n_out < mjmaze::ADIM || n_out > mjmaze::MAX_OUT || n_out % mjmaze::ADIM != 0) return -1;
+    return mjmaze::offsets(hidden, n_out).P;
+}
+
+// what k_mjmaze_rollout reads for the members [first, first + count) set by dne_set_members; options and outputs are left null
+static mjmaze::RolloutArgs mjmaze_args(dne_handle *h, int first, int count, int tslimit) {
+    mjmaze::RolloutArgs A{};
+    A.noise = h->noise; A.bases = h->bases; A.base_stride = h->base_stride;
+    A.m_slot = h->m_slot; A.m_off = h->m_off; A.m_scale = h->m_scale;
+    A.first = first; A.count = count; A.hdr = h->maze_hdr; A.walls = h->maze_walls; A.nw = h->maze_nw; A.tslimit = tslimit;
+    A.opt = h->mj_opt;
+    return A;
+}
+
+static void mjmaze_launch(dne_handle *h, const mjmaze::RolloutArgs &A) {
+    const dim3 grid(A.count);
+    const bool th = h->pd_nl == pendulum::NL_TANH;
+    switch (h->pd_hidden) {
+    case 64:
+        if (th) hipLaunchKernelGGL((mjmaze::k_mjmaze_rollout<64, true>), grid, dim3(64), 0, h->stream, A);
+        else hipLaunchKernelGGL((mjmaze::k_mjmaze_rollout<64, false>), grid, dim3(64), 0, h->stream, A);
+        break;
+    case 128:
+        if (th) hipLaunchKernelGGL((mjmaze::k_mjmaze_rollout<128, true>), grid, dim3(128), 0, h->stream, A);
+        else hipLaunchKernelGGL((mjmaze::k_mjmaze_rollout<128, false>), grid, dim3(128), 0, h->stream, A);
+        break;
+    default:
+        if (th) hipLaunchKernelGGL((mjmaze::k_mjmaze_rollout<256, true>), grid, dim3(256), 0, h->stream, A);
+        else hipLaunchKernelGGL((mjmaze::k_mjmaze_rollout<256, false>), grid, dim3(256), 0, h->stream, A);
+    }
+}
+
+extern "C" int dne_mjmaze_set_ob_stat(dne_handle *h, const float *mean, const float *std) {
+    DeviceGuard dg(h);
+    if (needs_mjmaze(h, "dne_mjmaze_set_ob_stat")) return -1;
+    if (!mean || !std) return h->fail("dne_mjmaze_set_ob_stat: bad arguments");
+    for (int i = 0; i < mjmaze::OBS; i++) { h->mj_opt.mean[i] = mean[i]; h->mj_opt.std[i] = std[i]; }
+    h->mj_stat_set = true;
+    return 0;
+}
+
+// action noise and observation statistics of the NEXT evaluation's first n members (later members: neither); that evaluation clears them
+extern "C" int dne_mjmaze_set_rollout_options(dne_handle *h, int n, float ac_noise_std, const int64_t *ac_off, const uint8_t *stat_flag) {
+    DeviceGuard dg(h);
+    if (needs_mjmaze(h, "dne_mjmaze_set_rollout_options")) return -1;
+    if (check_n(h, n)) return -1;
+    if (!h->noise && ac_off) return h->fail("noise table not uploaded (dne_noise_upload)");
+    if (ac_off)
+        for (int i = 0; i < n; i++)
+            if (ac_off[i] >= 0 && (uint64_t)ac_off[i] + mjmaze::AC_NOISE > (uint64_t)h->noise_count)
+                return h->fail("dne_mjmaze_set_rollout_options: member %d reads its %d action-noise values from offset %lld, past the noise table's %zu values",
+                               i, mjmaze::AC_NOISE, (long long)ac_off[i], (size_t)h->noise_count);
+    h->pd_has_off = ac_off != nullptr; h->pd_has_flag = stat_flag != nullptr;
+    if (ac_off) h->pd_host_off.assign(ac_off, ac_off + n); else h->pd_host_off.clear();
+    if (ac_off) HCHECK(h, hipMemcpyAsync(h->pd_acoff, ac_off, n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    if (stat_flag) HCHECK(h, hipMemcpyAsync(h->pd_flag, stat_flag, n, hipMemcpyHostToDevice, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    h->mj_opt.ac_noise_std = ac_noise_std;
+    h->pd_opt_n = n;
+    return 0;
+}
+
+// what an evaluation and the trace ask alike before a launch
+static int mjmaze_ready(dne_handle *h, const char *call) {
+    if (h->maze_nw < 1) return h->fail("DNE_KIND_MJMAZE: no maze loaded (dne_maze_set_walls comes before an evaluation)");
+    if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
+    if (!h->mj_stat_set) return h->fail("%s: the observation statistics of a DNE_KIND_MJMAZE engine are NaN until dne_mjmaze_set_ob_stat is called", call);
+    return 0;
+}
+
+// members [0, n), one whole episode each from the header's start point (no reset seed: env_seed is not read), one launch
+static int mjmaze_eval(dne_handle *h, const char *call, int n, int tslimit, float *returns, float *signreturns, int32_t *lengths, uint8_t *bc_out) {
+    if (bc_out) return h->fail("%s: behaviour characterisations are not available on a DNE_KIND_MJMAZE engine (kind %d): bc must be NULL; "
+                               "dne_maze_final_state has the final (x, y) of every member", call, DNE_KIND_MJMAZE);
+    if (tslimit <= 0) return h->fail("timestep limit must be positive");
+    if (mjmaze_ready(h, call)) return -1;
+    const bool has_off = h->pd_has_off, has_flag = h->pd_has_flag;
+    if ((has_off || has_flag) && h->pd_opt_n != n)
+        return h->fail("%s: dne_mjmaze_set_rollout_options was given %d members, this evaluation runs %d", call, h->pd_opt_n, n);
+    if (has_off)   // the table may have been replaced since the options were set
+        for (int i = 0; i < n; i++)
+            if (h->pd_host_off[i] >= 0 && (uint64_t)h->pd_host_off[i] + mjmaze::AC_NOISE > (uint64_t)h->noise_count)
+                return h->fail("%s: member %d reads its action noise from offset %lld, past the noise table's %zu values", call, i, (long long)h->pd_host_off[i], (size_t)h->noise_count);
+    mjmaze::RolloutArgs A = mjmaze_args(h, 0, n, tslimit);
+    A.ac_off = has_off ? h->pd_acoff : nullptr; A.stat_flag = has_flag ? h->pd_flag : nullptr;
+    A.ret = h->ret; A.sign = h->sign; A.len = h->len; A.xy = h->maze_xy;
+    A.ob_sum = h->pd_sum; A.ob_sumsq = h->pd_sumsq; A.ob_count = h->pd_count;
+    h->pd_has_off = h->pd_has_flag = false; h->pd_opt_n = 0; h->mj_opt.ac_noise_std = 0.0f;   // the options were for this evaluation only
+    HCHECK(h, hipEventRecord(h->ev_a, h->stream));
+    mjmaze_launch(h, A);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipEventRecord(h->ev_b, h->stream));
+    HCHECK(h, hipMemcpyAsync(returns, h->ret, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (signreturns) HCHECK(h, hipMemcpyAsync(signreturns, h->sign, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipMemcpyAsync(lengths, h->len, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    h->maze_last_n = h->pd_last_n = n;
+    float ms = 0;
+    HCHECK(h, hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
+    dne_profile &P = h->prof;
+    P = dne_profile{};
+    P.eval_ms = P.env_ms = ms;
+    P.fc_launches = 1;
+    for (int i = 0; i < n; i++) P.env_steps += lengths[i];
+    return 0;
+}
+
+extern "C" int dne_mjmaze_ob_stats(dne_handle *h, int n, double *sum, double *sumsq, int32_t *count) {
+    DeviceGuard dg(h);
+    if (needs_mjmaze(h, "dne_mjmaze_ob_stats")) return -1;
+    if (n < 1 || n > h->pd_last_n) return h->fail("dne_mjmaze_ob_stats: %d members asked for, the last evaluation ran %d", n, h->pd_last_n);
+    if (!sum || !sumsq || !count) return h->fail("dne_mjmaze_ob_stats: no output buffer");
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(sum, h->pd_sum, (size_t)n * mjmaze::OBS * sizeof(double), hipMemcpyDeviceToHost));
+    HCHECK(h, hipMemcpy(sumsq, h->pd_sumsq, (size_t)n * mjmaze::OBS * sizeof(double), hipMemcpyDeviceToHost));
+    HCHECK(h, hipMemcpy(count, h->pd_count, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the kernel once more for ONE of the current members, with every step written out: trace [min(tslimit, 400)][20] as dne_mjmaze_rollout_host
+// writes it; no action noise, no statistics.  The accumulators of the last evaluation are left alone.
+extern "C" int dne_mjmaze_debug_trace(dne_handle *h, int member, int tslimit, float *trace, int32_t *steps) {
+    DeviceGuard dg(h);
+    if (needs_mjmaze(h, "dne_mjmaze_debug_trace")) return -1;
+    if (member < 0 || member >= (int)h->host_slot.size()) return h->fail("dne_mjmaze_debug_trace: member %d, dne_set_members set %zu", member, h->host_slot.size());
+    if (tslimit <= 0 || !trace || !steps) return h->fail("dne_mjmaze_debug_trace: bad arguments");
+    if (mjmaze_ready(h, "dne_mjmaze_debug_trace")) return -1;
+    const int cap = std::min(tslimit, (int)mjmaze::EPISODE_STEPS);
+    DevBuf<float> d;
+    DevBuf<int32_t> dn;
+    HCHECK(h, d.alloc((size_t)cap * mjmaze::TRACE_W));
+    HCHECK(h, dn.alloc(1));
+    mjmaze::RolloutArgs A = mjmaze_args(h, member, 1, tslimit);
+    A.opt.ac_noise_std = 0.0f;
+    A.trace = d; A.trace_steps = dn;
+    mjmaze_launch(h, A);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(steps, dn, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (*steps < 0 || *steps > cap) return h->fail("dne_mjmaze_debug_trace: the kernel reports %d steps under a limit of %d", *steps, cap);
+    HCHECK(h, hipMemcpy(trace, d, (size_t)*steps * mjmaze::TRACE_W * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the same header on the CPU: no handle, no GPU
+static int mjmaze_shape_host(const char *call, int hidden, int n_out, int ac_mode, int nonlin) {
+    if (!mjmaze::shape_ok(hidden, n_out, ac_mode, nonlin)) {
+        g_create_error = std::string(call) + ": hidden width " + std::to_string(hidden) + ", " + std::to_string(n_out) + " outputs, action mode " +
+                         std::to_string(ac_mode) + ", nonlinearity " + std::to_string(nonlin) + " is not a shape csrc/mjmaze.h builds";
+        return -1;
+    }
+    return 0;
+}
+
+// one episode for each of n thetas [n][P] in the maze (header8, lines).  table / ac_off [n] (both or neither; an offset < 0: no noise for that
+// member), stat_flag [n] or NULL: as the device call's options.  Outputs as the kernel writes them; trace [n][tslimit][20] or NULL.
+extern "C" int dne_mjmaze_rollout_host(const float *theta, int n, int hidden, int n_out, int ac_mode, int nonlin, const float *mean, const float *std,
+                                       const float *header8, const float *lines, int n_walls, int tslimit, float ac_noise_std, const float *table,
+                                       size_t table_len, const int64_t *ac_off, const uint8_t *stat_flag, float *returns, float *signreturns,
+                                       int32_t *lengths, float *xy, double *ob_sum, double *ob_sumsq, int32_t *ob_count, float *trace) {
+    if (maze_check(&g_create_error, header8, lines, n_walls)) return -1;
+    if (n < 1 || tslimit <= 0 || !theta || !mean || !std || !returns || !signreturns || !lengths || !xy || !ob_sum || !ob_sumsq || !ob_count ||
+        (ac_off != nullptr) != (table != nullptr)) { g_create_error = "dne_mjmaze_rollout_host: bad arguments"; return -1; }
+    if (mjmaze_shape_host("dne_mjmaze_rollout_host", hidden, n_out, ac_mode, nonlin)) return -1;
+    mjmaze::Options o{};
+    o.n_out = n_out; o.ac_mode = ac_mode; o.ac_noise_std = ac_noise_std;
+    for (int i = 0; i < mjmaze::OBS; i++) { o.mean[i] = mean[i]; o.std[i] = std[i]; }
+    const size_t P = mjmaze::offsets(hidden, n_out).P;
+    if (ac_off)
+        for (int i = 0; i < n; i++)
+            if (ac_off[i] >= 0 && (uint64_t)ac_off[i] + mjmaze::AC_NOISE > (uint64_t)table_len) {
+                g_create_error = "dne_mjmaze_rollout_host: member " + std::to_string(i) + " reads its action noise from offset " + std::to_string(ac_off[i]) +
+                                 ", past the noise table's " + std::to_string(table_len) + " values";
+                return -1;
+            }
+    const maze::Header m = maze_header(header8);
+    for (int i = 0; i < n; i++) {
+        const bool stat = stat_flag && stat_flag[i];
+        const mjmaze::Episode e = mjmaze::rollout_host(hidden, nonlin, theta + (size_t)i * P, o, m, lines, n_walls, tslimit,
+                                                       ac_off && ac_off[i] >= 0 ? table + ac_off[i] : nullptr, stat,
+                                                       trace ? trace + (size_t)i * tslimit * mjmaze::TRACE_W : nullptr);
+        returns[i] = e.ret; signreturns[i] = e.sign; lengths[i] = e.len;
+        xy[2 * (size_t)i] = e.s.x; xy[2 * (size_t)i + 1] = e.s.y;
+        for (int c = 0; c < mjmaze::OBS; c++) { ob_sum[mjmaze::OBS * (size_t)i + c] = e.ob_sum[c]; ob_sumsq[mjmaze::OBS * (size_t)i + c] = e.ob_sumsq[c]; }
+        ob_count[i] = stat ? e.len : 0;
+    }
+    return 0;
+}
+
+// the policy alone: thetas [n][P] on raw observations [n][11] -> x [n][11] (normalised and clipped), h1 [n][H], h2 [n][H], out [n][n_out], action [n][2]
+extern "C" int dne_mjmaze_forward_host(const float *theta, const float *obs, int n, int hidden, int n_out, int ac_mode, int nonlin, const float *mean,
+                                       const float *std, float *x, float *h1, float *h2, float *out, float *action) {
+    if (n < 1 || !theta || !obs || !mean || !std || !x || !h1 || !h2 || !out || !action) { g_create_error = "dne_mjmaze_forward_host: bad arguments"; return -1; }
+    if (mjmaze_shape_host("dne_mjmaze_forward_host", hidden, n_out, ac_mode, nonlin)) return -1;
+    mjmaze::Options o{};
+    o.n_out = n_out; o.ac_mode = ac_mode;
+    for (int i = 0; i < mjmaze::OBS; i++) { o.mean[i] = mean[i]; o.std[i] = std[i]; }
+    const size_t P = mjmaze::offsets(hidden, n_out).P;
+    for (int i = 0; i < n; i++)
+        mjmaze::forward_host(hidden, nonlin, theta + (size_t)i * P, o, obs + mjmaze::OBS * (size_t)i, x + mjmaze::OBS * (size_t)i, h1 + (size_t)i * hidden,
+                             h2 + (size_t)i * hidden, out + (size_t)i * n_out, action + mjmaze::ADIM * (size_t)i);
+    return 0;
+}
+
 // ------------------------------------------------------------------------------- environments stepped by the caller (csrc/step_env.h)
 static_assert(stepenv::KIND_MAZE == DNE_KIND_MAZE && stepenv::KIND_CARTPOLE == DNE_KIND_CARTPOLE && stepenv::KIND_PENDULUM == DNE_KIND_PENDULUM,
               "step_env.h restates the three kinds");
@@ -3146,7 +3417,7 @@ static int se_alloc(dne_handle *h) {
 // What every dne_stepenv_* call on a handle asks first: the kind, the maze's walls, n, the index list (NULL = 0 .. n - 1) in range and without
 // a repeat, and -- for a call that reads environments -- that each was reset.  Fills idx.  A refusal comes before anything on the device moves.
 static int se_check(dne_handle *h, const char *call, int n, const int32_t *indices, bool reads, std::vector<int32_t> &idx) {
-    if (!h->episodic())
+    if (!h->episodic() || h->mjmaze)   // (DNE_KIND_MJMAZE: the maze one step at a time is DNE_KIND_MAZE's)
         return h->fail("%s needs a DNE_KIND_MAZE, DNE_KIND_CARTPOLE or DNE_KIND_PENDULUM engine (this one: kind %d)", call, h->L.kind);
     if (h->maze && h->maze_nw < 1) return h->fail("%s: no maze loaded (dne_maze_set_walls comes before the environments)", call);
     if (n < 1 || n > h->M) return h->fail("%s: %d environments asked for, the engine holds 1..%d", call, n, h->M);
@@ -3357,6 +3628,7 @@ extern "C" int dne_es_eval(dne_handle *h, const int64_t *idx, int n, float sigma
     if (h->maze) return maze_eval(h, 2 * n, tslimit, returns_n2, signreturns_n2, lengths_n2, bc);   // (the episode is deterministic: env_seed is not read)
     if (h->cartpole) return cartpole_eval(h, "dne_es_eval", 2 * n, tslimit, env_seed, returns_n2, signreturns_n2, lengths_n2, bc);
     if (h->pendulum) return pendulum_eval(h, "dne_es_eval", 2 * n, tslimit, env_seed, returns_n2, signreturns_n2, lengths_n2, bc);
+    if (h->mjmaze) return mjmaze_eval(h, "dne_es_eval", 2 * n, tslimit, returns_n2, signreturns_n2, lengths_n2, bc);   // (no reset seed: env_seed is not read)
     return eval_core(h, 2 * n, 2, tslimit, env_seed, returns_n2, signreturns_n2, lengths_n2, bc);
 }
 
@@ -3375,6 +3647,10 @@ extern "C" int dne_eval_members(dne_handle *h, int n, int tslimit, const uint32_
     if (h->pendulum) {
         if ((int)h->host_slot.size() < n) return h->fail("dne_eval_members: %d members asked for, dne_set_members set %zu", n, h->host_slot.size());
         return pendulum_eval(h, "dne_eval_members", n, tslimit, env_seed, returns, signreturns, lengths, bc);
+    }
+    if (h->mjmaze) {
+        if ((int)h->host_slot.size() < n) return h->fail("dne_eval_members: %d members asked for, dne_set_members set %zu", n, h->host_slot.size());
+        return mjmaze_eval(h, "dne_eval_members", n, tslimit, returns, signreturns, lengths, bc);
     }
     return eval_core(h, n, 1, tslimit, env_seed, returns, signreturns, lengths, bc);
 }

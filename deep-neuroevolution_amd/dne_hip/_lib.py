@@ -24,6 +24,11 @@ PENDULUM_OBS, PENDULUM_STEPS, PENDULUM_TRACE_W, PENDULUM_MAX_OUT = 3, 200, 8, 16
 PENDULUM_AC_MODES = {'continuous': 0, 'uniform': 1}   # dne_config.reserved[1]
 PENDULUM_NONLINS = {'tanh': 0, 'relu': 1}             # dne_config.reserved[2]
 PENDULUM_MATH = {'tanh': 0, 'norm': 1, 'normalise': 2}   # dne_pendulum_debug_math / _math_host
+KIND_MJMAZE = 7   # MujocoPolicy on the hard maze (final (x, y) as the behaviour characterisation), whole episodes in one kernel (csrc/mjmaze.h)
+MJMAZE_OBS, MJMAZE_ADIM, MJMAZE_STEPS, MJMAZE_TRACE_W, MJMAZE_MAX_BINS = 11, 2, 400, 20, 8   # observations, action dimensions, steps, floats per trace row, most bins a dimension
+MJMAZE_AC_NOISE = MJMAZE_ADIM * MJMAZE_STEPS            # action-noise values an episode reads from the table
+MJMAZE_AC_LOW, MJMAZE_AC_HIGH = -0.5, 0.5               # the action space: what the maze clamps its raw outputs to
+MUJOCO_KINDS = (KIND_PENDULUM, KIND_MJMAZE)             # the kinds whose shape travels in dne_config.reserved
 ES_KINDS = (KIND_ES, KIND_ES_VBN)   # virtual batch norm over a reference batch, antithetic pairs
 PROC_MODES = {"centered_rank": 0, "sign": 1, "centered_sign_rank": 2}
 OPT_KINDS = {"adam": 0, "sgd": 1}
@@ -81,7 +86,7 @@ class Profile(C.Structure):
 
 def build(force=False):
     """Compile libdne_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h", "cartpole.h", "pendulum.h", "step_env.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h", "cartpole.h", "pendulum.h", "mjmaze.h", "step_env.h")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dne_hip.h"))
     if os.environ.get("DNE_LIB_PATH"):
         # another build of the same ABI was asked for by name: `make` only knows the in-tree library, so running it here would
@@ -457,6 +462,69 @@ def pendulum_forward_host(theta, obs, hidden, mean, std, n_out=1, ac_mode='conti
     return x, h1, h2, out, action
 
 
+def mjmaze_num_params(hidden, n_out=2):
+    """dne_mjmaze_num_params: P = 13 H + H^2 + H O + O (-1: a width or an output count csrc/mjmaze.h does not build)"""
+    return load().dne_mjmaze_num_params(int(hidden), int(n_out))
+
+
+def mjmaze_rollout_host(theta, header, lines, hidden, mean, std, n_out=2, ac_mode='continuous', nonlin='tanh', tslimit=MJMAZE_STEPS,
+                        ac_noise_std=0.0, table=None, ac_off=None, stat_flag=None, want_trace=False):
+    """dne_mjmaze_rollout_host: csrc/mjmaze.h on the CPU (no GPU, no handle) for thetas [n][P] in the maze (header [8], lines [w][4]).
+    table / ac_off [n] (both or neither): the noise table and where each member's 800 action-noise values start (< 0: none); stat_flag [n]: who
+    accumulates its observations.  -> dict(returns, signreturns, lengths, xy [n][2], ob_sum [n][11], ob_sumsq [n][11], ob_count [n](, trace
+    float32 [n][tslimit][20]: the 11 observations acted on, the net's 2 actions, the 2 applied, x, y, heading, speed, ang_vel after the step))"""
+    hidden, n_out, ac_mode, nonlin = _pendulum_shape(hidden, n_out, ac_mode, nonlin)
+    P = mjmaze_num_params(hidden, n_out)
+    if P < 0:
+        raise DneError("mjmaze_rollout_host: hidden width %d with %d outputs is not a shape csrc/mjmaze.h builds" % (hidden, n_out))
+    theta = _arr(theta, np.float32).reshape(-1, P)
+    n = theta.shape[0]
+    header, lines = _maze_args(header, lines)
+    mean = _arr(mean, np.float32).reshape(MJMAZE_OBS); std = _arr(std, np.float32).reshape(MJMAZE_OBS)
+    if table is not None:
+        table = _arr(table, np.float32).reshape(-1)
+    if ac_off is not None:
+        ac_off = _arr(ac_off, np.int64).reshape(-1)
+        if ac_off.size != n:
+            raise DneError("mjmaze_rollout_host: %d thetas, %d action-noise offsets" % (n, ac_off.size))
+    if stat_flag is not None:
+        stat_flag = _arr(stat_flag, np.uint8).reshape(-1)
+        if stat_flag.size != n:
+            raise DneError("mjmaze_rollout_host: %d thetas, %d statistics flags" % (n, stat_flag.size))
+    r = dict(returns=np.empty(n, np.float32), signreturns=np.empty(n, np.float32), lengths=np.empty(n, np.int32), xy=np.empty((n, 2), np.float32),
+             ob_sum=np.empty((n, MJMAZE_OBS), np.float64), ob_sumsq=np.empty((n, MJMAZE_OBS), np.float64), ob_count=np.empty(n, np.int32))
+    trace = np.zeros((n, int(tslimit), MJMAZE_TRACE_W), np.float32) if want_trace else None
+    _ck_host(load().dne_mjmaze_rollout_host(
+        _ptr(theta, C.c_float), n, hidden, n_out, ac_mode, nonlin, _ptr(mean, C.c_float), _ptr(std, C.c_float), _ptr(header, C.c_float),
+        _ptr(lines, C.c_float), int(lines.shape[0]), int(tslimit), C.c_float(ac_noise_std), _ptr(table, C.c_float),
+        C.c_size_t(0 if table is None else table.size), _ptr(ac_off, C.c_int64), _ptr(stat_flag, C.c_uint8), _ptr(r['returns'], C.c_float),
+        _ptr(r['signreturns'], C.c_float), _ptr(r['lengths'], C.c_int32), _ptr(r['xy'], C.c_float), _ptr(r['ob_sum'], C.c_double),
+        _ptr(r['ob_sumsq'], C.c_double), _ptr(r['ob_count'], C.c_int32), _ptr(trace, C.c_float)))
+    if want_trace:
+        r['trace'] = trace
+    return r
+
+
+def mjmaze_forward_host(theta, obs, hidden, mean, std, n_out=2, ac_mode='continuous', nonlin='tanh'):
+    """dne_mjmaze_forward_host: the policy alone, thetas [n][P] on raw observations [n][11] -> (x [n][11] normalised and clipped, h1 [n][H],
+    h2 [n][H], out [n][O], action [n][2])"""
+    hidden, n_out, ac_mode, nonlin = _pendulum_shape(hidden, n_out, ac_mode, nonlin)
+    P = mjmaze_num_params(hidden, n_out)
+    if P < 0:
+        raise DneError("mjmaze_forward_host: hidden width %d with %d outputs is not a shape csrc/mjmaze.h builds" % (hidden, n_out))
+    theta = _arr(theta, np.float32).reshape(-1, P); obs = _arr(obs, np.float32).reshape(-1, MJMAZE_OBS)
+    n = theta.shape[0]
+    if obs.shape[0] != n:
+        raise DneError("mjmaze_forward_host: %d thetas, %d observations" % (n, obs.shape[0]))
+    mean = _arr(mean, np.float32).reshape(MJMAZE_OBS); std = _arr(std, np.float32).reshape(MJMAZE_OBS)
+    x = np.empty((n, MJMAZE_OBS), np.float32); h1 = np.empty((n, hidden), np.float32); h2 = np.empty((n, hidden), np.float32)
+    out = np.empty((n, n_out), np.float32); action = np.empty((n, MJMAZE_ADIM), np.float32)
+    _ck_host(load().dne_mjmaze_forward_host(_ptr(theta, C.c_float), _ptr(obs, C.c_float), n, hidden, n_out, ac_mode, nonlin, _ptr(mean, C.c_float),
+                                            _ptr(std, C.c_float), _ptr(x, C.c_float), _ptr(h1, C.c_float), _ptr(h2, C.c_float), _ptr(out, C.c_float),
+                                            _ptr(action, C.c_float)))
+    return x, h1, h2, out, action
+
+
 def pendulum_math_host(fn, x, a=0.0, b=1.0):
     """dne_pendulum_math_host: 'tanh' -> tanh_f(float32(x)), 'norm' -> norm_angle(x), 'normalise' -> clip((float32(x) - a) / b, -5, 5); float64 in and out"""
     x = _arr(x, np.float64).reshape(-1)
@@ -554,8 +622,8 @@ class Engine:
 
     def __init__(self, kind, n_actions=18, max_members=256, ref_count=128, device_id=0, ref_chunk=0,
                  record_bc=False, bc_max_steps=0, profile_events=False, bc_final_only=False, hidden=0, ac_mode=0, nonlin=0):
-        """hidden, ac_mode, nonlin: the shape of a KIND_PENDULUM engine (hidden width 64 / 128 / 256; 'continuous' or 'uniform'; 'tanh' or 'relu'),
-        with n_actions the outputs (1, or the bins)"""
+        """hidden, ac_mode, nonlin: the shape of a KIND_PENDULUM or KIND_MJMAZE engine (hidden width 64 / 128 / 256; 'continuous' or 'uniform';
+        'tanh' or 'relu'), with n_actions the outputs (the pendulum: 1, or the bins; the maze: 2, or twice the bins)"""
         self.lib = load()
         self.kind, self.n_actions, self.max_members = int(kind), int(n_actions), int(max_members)
         self.ref_count = int(ref_count) if kind in ES_KINDS else 0
@@ -565,7 +633,7 @@ class Engine:
                      bc_max_steps=self.bc_max_steps, profile_events=int(bool(profile_events)),
                      bc_final_only=int(bool(bc_final_only)))
         self.hidden = int(hidden)
-        if self.kind == KIND_PENDULUM:
+        if self.kind in MUJOCO_KINDS:
             self.ac_mode, self.nonlin = int(PENDULUM_AC_MODES.get(ac_mode, ac_mode)), int(PENDULUM_NONLINS.get(nonlin, nonlin))
             cfg.reserved[0], cfg.reserved[1], cfg.reserved[2] = self.hidden, self.ac_mode, self.nonlin
         self.bc_final_only = bool(bc_final_only)
@@ -574,6 +642,7 @@ class Engine:
         if rc != 0:
             raise DneError(self.lib.dne_last_error(None).decode())
         self.P = self.lib.dne_pendulum_num_params(self.hidden, self.n_actions) if self.kind == KIND_PENDULUM else \
+            self.lib.dne_mjmaze_num_params(self.hidden, self.n_actions) if self.kind == KIND_MJMAZE else \
             self.lib.dne_num_params(self.kind, self.n_actions)
         self.record_bc = bool(record_bc)
         self.noise_count = 0
@@ -842,6 +911,36 @@ class Engine:
         self._ck(self.lib.dne_pendulum_debug_math(self.h, int(PENDULUM_MATH.get(fn, fn)), _ptr(x, C.c_double), int(x.size), C.c_float(a), C.c_float(b),
                                                   _ptr(out, C.c_double)))
         return out
+
+    # ---- MujocoPolicy on the hard maze (KIND_MJMAZE); the walls, the final positions and the archive are the maze_* methods
+    def mjmaze_set_ob_stat(self, mean, std):
+        mean = _arr(mean, np.float32).reshape(MJMAZE_OBS); std = _arr(std, np.float32).reshape(MJMAZE_OBS)
+        self._ck(self.lib.dne_mjmaze_set_ob_stat(self.h, _ptr(mean, C.c_float), _ptr(std, C.c_float)))
+
+    def mjmaze_set_rollout_options(self, n, ac_noise_std=0.0, ac_off=None, stat_flag=None):
+        """for the next evaluation only (it must run n members): ac_off int64 [n] -- where each member's 800 action-noise values start in the
+        noise table, < 0 for none -- and stat_flag uint8 [n] -- who accumulates the observations it acts on"""
+        if ac_off is not None:
+            ac_off = _arr(ac_off, np.int64).reshape(-1)
+        if stat_flag is not None:
+            stat_flag = _arr(stat_flag, np.uint8).reshape(-1)
+        for a in (ac_off, stat_flag):
+            if a is not None and a.size != int(n):
+                raise DneError("mjmaze_set_rollout_options: %d members, %d values" % (int(n), a.size))
+        self._ck(self.lib.dne_mjmaze_set_rollout_options(self.h, int(n), C.c_float(ac_noise_std), _ptr(ac_off, C.c_int64), _ptr(stat_flag, C.c_uint8)))
+
+    def mjmaze_ob_stats(self, n):
+        """(sum float64 [n][11], sumsq float64 [n][11], count int32 [n]) of the last evaluation's first n members"""
+        s = np.empty((int(n), MJMAZE_OBS), np.float64); q = np.empty((int(n), MJMAZE_OBS), np.float64); c = np.empty(int(n), np.int32)
+        self._ck(self.lib.dne_mjmaze_ob_stats(self.h, int(n), _ptr(s, C.c_double), _ptr(q, C.c_double), _ptr(c, C.c_int32)))
+        return s, q, c
+
+    def mjmaze_debug_trace(self, member, tslimit=MJMAZE_STEPS):
+        """the kernel once more for one current member, every step written out: float32 [steps][20] as mjmaze_rollout_host's trace"""
+        out = np.zeros((min(int(tslimit), MJMAZE_STEPS), MJMAZE_TRACE_W), np.float32)
+        steps = C.c_int32(0)
+        self._ck(self.lib.dne_mjmaze_debug_trace(self.h, int(member), int(tslimit), _ptr(out, C.c_float), C.byref(steps)))
+        return out[:steps.value]
 
     # ---- gym.CartPole-v1 (KIND_CARTPOLE)
     def cartpole_final_state(self, n):

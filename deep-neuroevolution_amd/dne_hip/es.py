@@ -212,10 +212,21 @@ def es_generation(engine, noise_len, config, n_pairs, generation, tslimit, optim
 
 
 # ---------------------------------------------------------------------------------------------- drivers
+def mujoco_run(exp):
+    """the module that prepares a MujocoPolicy run, by exp['env_id']: mjmaze_run for the hard maze, else pendulum_run (which refuses every id
+    but its own by name)"""
+    from . import mjmaze_run, pendulum_run, policies
+    return mjmaze_run if exp.get('env_id') == policies.MJMAZE_ENV_ID else pendulum_run
+
+
+def open_engine(exp, engine, max_members, device_id=0):
+    """the engine of a MujocoPolicy experiment: the caller's (checked) or a new one of the kind and shape the experiment asks for"""
+    return mujoco_run(exp).open_engine(exp, engine, max_members, device_id=device_id)
+
+
 def make_engine(exp, n_pairs, n_actions=18, device_id=0, ref_count=128, **kw):
-    if exp['policy']['type'] == 'MujocoPolicy':           # the pendulum kind, in the shape the policy's arguments ask for
-        from . import pendulum_run
-        return pendulum_run.open_engine(exp, None, max(2 * n_pairs, 2), device_id=device_id)
+    if exp['policy']['type'] == 'MujocoPolicy':           # the pendulum or the hard-maze kind, in the shape the policy's arguments ask for
+        return open_engine(exp, None, max(2 * n_pairs, 2), device_id=device_id)
     kind = {'ESAtariPolicy': _lib.KIND_ES, 'GAAtariPolicy': _lib.KIND_GA}[exp['policy']['type']]
     return _lib.Engine(kind, n_actions, max_members=max(2 * n_pairs, 2), ref_count=ref_count, device_id=device_id, **kw)
 
@@ -227,9 +238,8 @@ def setup(exp, engine=None, n_pairs=None, device_id=0):
     if engine is None:
         engine = make_engine(exp, n_pairs or max(config.episodes_per_batch // 2, 1), device_id=device_id)
     if exp['policy']['type'] == 'MujocoPolicy':
-        from . import pendulum_run
-        pendulum_run.open_engine(exp, engine, 0)          # (the caller's engine: env_id and kind are checked)
-        env = policies.PendulumEnv(engine)
+        open_engine(exp, engine, 0)                       # (the caller's engine: env_id and kind are checked; the hard maze: the walls are set)
+        env = policies.HardMazeEnv(engine, exp=exp) if exp.get('env_id') == policies.MJMAZE_ENV_ID else policies.PendulumEnv(engine)
     else:
         env = policies.HipAtariEnv(engine)
     policy = getattr(policies, exp['policy']['type'])(env.observation_space, env.action_space, engine=engine,
@@ -406,6 +416,23 @@ class TaskPacer:
         self.last_task, self.pushed_at = task_id, time.time()
 
 
+def mujoco_engine_calls(engine, policy):
+    """(set_rollout_options, ob_stats) of the engine kind a MujocoPolicy runs on"""
+    if policy.kind == _lib.KIND_MJMAZE:
+        return engine.mjmaze_set_rollout_options, engine.mjmaze_ob_stats
+    return engine.pendulum_set_rollout_options, engine.pendulum_ob_stats
+
+
+def flagged_ob_stats(stats, flags):
+    """es.py:436-438: the flagged episodes' sums, added in member order -> (ob_sum float32, ob_sumsq float32, ob_count)"""
+    s, q, c = stats
+    acc_s, acc_q = np.zeros(s.shape[1], np.float64), np.zeros(s.shape[1], np.float64)
+    for i in np.flatnonzero(flags):
+        acc_s += s[i]
+        acc_q += q[i]
+    return acc_s.astype(np.float32), acc_q.astype(np.float32), int(c[flags].sum())
+
+
 def run_worker(master_redis_cfg, relay_redis_cfg, noise, *, min_task_runtime=.2, engine=None, max_tasks=None,
                seed=None, rank=0, world=1, reeval_after=1.0):
     """es.py:366-439 for one GPU: per task, evaluate this worker's whole shard of antithetic pairs in one
@@ -462,16 +489,12 @@ def run_worker(master_redis_cfg, relay_redis_cfg, noise, *, min_task_runtime=.2,
             n_eps = 2 * len(mine)
             flags = (rs.rand(n_eps) < config.calc_obstat_prob) if config.calc_obstat_prob != 0 else np.zeros(n_eps, bool)
             noisy = policy.ac_noise_std != 0
-            ac_off = rs.randint(0, len(noise.noise) - env_steps + 1, size=n_eps).astype(np.int64) if noisy else None
-            engine.pendulum_set_rollout_options(n_eps, policy.ac_noise_std if noisy else 0.0, ac_off, flags.astype(np.uint8))
+            set_options, ob_stats = mujoco_engine_calls(engine, policy)
+            ac_off = rs.randint(0, len(noise.noise) - env_steps * policy.num_actions + 1, size=n_eps).astype(np.int64) if noisy else None   # (one value a step and action dimension)
+            set_options(n_eps, policy.ac_noise_std if noisy else 0.0, ac_off, flags.astype(np.uint8))
         returns, signreturns, lengths = engine.es_eval(noise_inds, config.noise_stdev, tslimit, seeds)
         if policy.needs_ob_stat and flags.any():          # es.py:436-438: the flagged episodes' sums, added in member order
-            s, q, c = engine.pendulum_ob_stats(n_eps)
-            acc_s, acc_q = np.zeros(s.shape[1], np.float64), np.zeros(s.shape[1], np.float64)
-            for i in np.flatnonzero(flags):
-                acc_s += s[i]
-                acc_q += q[i]
-            ob_sum, ob_sumsq, ob_count = acc_s.astype(np.float32), acc_q.astype(np.float32), int(c[flags].sum())
+            ob_sum, ob_sumsq, ob_count = flagged_ob_stats(ob_stats(n_eps), flags)
         worker.push_result(task_id, Result(
             worker_id=worker_id, noise_inds_n=noise_inds, returns_n2=returns, signreturns_n2=signreturns,
             lengths_n2=lengths, eval_return=None, eval_length=None, ob_sum=ob_sum, ob_sumsq=ob_sumsq, ob_count=ob_count))

@@ -423,18 +423,41 @@ class PendulumEnv:
         return self
 
 
-def mujoco_layout(hidden, n_out):
+MJMAZE_ENV_ID = 'HardMaze-v0'
+
+
+class HardMazeEnv(PendulumEnv):
+    """The spaces of the deceptive hard maze (csrc/maze.h under csrc/mjmaze.h) behind the same surface: a Box observation of shape (11,), a Box
+    action of shape (2,) with bounds +-0.5 -- the values the maze clamps its two raw outputs to --, 400 steps.  There is no reset seed: every
+    episode starts from the maze file's start point.  It holds the maze file as maze_run.maze_file resolves it (exp['maze_file'], hard_maze.txt
+    in the working directory, the copy among the test fixtures)."""
+    max_episode_steps = _lib.MJMAZE_STEPS
+
+    def __init__(self, engine=None, seed=0, exp=None):
+        from .maze_run import maze_file
+        PendulumEnv.__init__(self, engine, seed)
+        self.observation_space = _Space(shape=(_lib.MJMAZE_OBS,))
+        self.action_space = _Space(shape=(_lib.MJMAZE_ADIM,))
+        self.action_space.low = np.full(_lib.MJMAZE_ADIM, _lib.MJMAZE_AC_LOW, np.float32)
+        self.action_space.high = np.full(_lib.MJMAZE_ADIM, _lib.MJMAZE_AC_HIGH, np.float32)
+        self.maze_file = maze_file(exp or {})
+        self.header, self.lines = _lib.load_maze(self.maze_file)
+
+
+def mujoco_layout(hidden, n_out, n_obs=_lib.PENDULUM_OBS):
     """flat_layout for MujocoPolicy with two hidden layers of one width: TF's creation order, tf_util.dense's shapes (w [in][out], b [out])"""
     spec, o = OrderedDict(), 0
-    for name, shape in (("l0/w", (_lib.PENDULUM_OBS, hidden)), ("l0/b", (hidden,)), ("l1/w", (hidden, hidden)), ("l1/b", (hidden,)),
+    for name, shape in (("l0/w", (n_obs, hidden)), ("l0/b", (hidden,)), ("l1/w", (hidden, hidden)), ("l1/b", (hidden,)),
                         ("out/w", (hidden, n_out)), ("out/b", (n_out,))):
         spec[name] = (o, shape)
         o += int(np.prod(shape))
     return spec, o
 
 
-def mujoco_shape(ac_bins, nonlin_type, hidden_dims, connection_type):
-    """(hidden width, outputs, action mode, nonlinearity) of a MujocoPolicy csrc/pendulum.h builds; everything else is refused by name"""
+def mujoco_shape(ac_bins, nonlin_type, hidden_dims, connection_type, adim=1):
+    """(hidden width, outputs, action mode, nonlinearity) of a MujocoPolicy csrc/pendulum.h (adim = 1 action dimension) or csrc/mjmaze.h (2)
+    builds; everything else is refused by name.  The outputs are adim under the continuous action and adim * B under B uniform bins a
+    dimension, at most 16 in all: B is bounded by 16 on the pendulum and by 8 on the maze."""
     if connection_type != 'ff':
         raise NotImplementedError("MujocoPolicy: connection_type {!r} (the reference itself builds only 'ff', policies.py:157-162)".format(connection_type))
     hidden_dims = list(hidden_dims)
@@ -450,27 +473,34 @@ def mujoco_shape(ac_bins, nonlin_type, hidden_dims, connection_type):
         raise NotImplementedError("MujocoPolicy: ac_bins {!r} -- 'continuous:' or 'uniform:B' expected".format(ac_bins))
     mode, arg = ac_bins.split(':')
     if mode == 'continuous':
-        n_out = 1
+        n_out = adim
     elif mode == 'uniform':
-        n_out = int(arg)
-        if not 2 <= n_out <= _lib.PENDULUM_MAX_OUT:
-            raise NotImplementedError("MujocoPolicy: ac_bins {!r} -- the HIP engine builds 2..{} uniform bins".format(ac_bins, _lib.PENDULUM_MAX_OUT))
+        n_out = int(arg) * adim
+        if not 2 <= int(arg) <= _lib.PENDULUM_MAX_OUT // adim:
+            raise NotImplementedError("MujocoPolicy: ac_bins {!r} -- the HIP engine builds 2..{} uniform bins".format(ac_bins, _lib.PENDULUM_MAX_OUT // adim))
     else:
         raise NotImplementedError("MujocoPolicy: ac_bins {!r} -- the HIP engine builds 'continuous:' and 'uniform:B' ('custom:' bins are not built)".format(ac_bins))
     return int(hidden_dims[0]), n_out, mode, nonlin_type
 
 
 def refuse_mujoco(exp, driver):
-    """nses / ga with MujocoPolicy: the reference's novelty vector is MuJoCo's centre of mass (policies.py:252-256, 292-299), which does not exist here"""
+    """nses / ga with MujocoPolicy.  The reference's novelty vector for this policy is the final (x_pos, y_pos) of MuJoCo's centre of mass
+    (policies.py:252-256, 292-299).  The pendulum has no position, so there the two drivers are refused.  The hard maze has one -- the
+    navigator's final (x, y) -- so nses lets 'HardMaze-v0' through (NS-ES and NSR-ES; nses.py's MujocoPolicy path); ga with this policy is not built."""
+    if exp['policy']['type'] == 'MujocoPolicy' and exp.get('env_id') == MJMAZE_ENV_ID:
+        if driver == 'nses':
+            return
+        raise NotImplementedError("{} with MujocoPolicy is not built -- MujocoPolicy runs under es and nses (NS-ES, NSR-ES) on {} and under es "
+                                  "on {}".format(driver, MJMAZE_ENV_ID, PENDULUM_ENV_ID))
     if exp['policy']['type'] == 'MujocoPolicy':
         raise NotImplementedError("{} with MujocoPolicy is not built: its behaviour characterisation is MuJoCo's centre of mass, and no simulator "
                                   "runs here -- MujocoPolicy runs under es on {}".format(driver, PENDULUM_ENV_ID))
 
 
-def normc_flat(hidden, n_out, seed=0):
+def normc_flat(hidden, n_out, seed=0, n_obs=_lib.PENDULUM_OBS):
     """Initial MujocoPolicy parameters: U.normc_initializer(1.0) for the hidden layers and (0.01) for `out` -- randn columns scaled to that
     norm, tf_util.py:108-116 --, zero biases; drawn from RandomState(seed) in creation order (TF's own initialiser is unseeded)"""
-    spec, P = mujoco_layout(hidden, n_out)
+    spec, P = mujoco_layout(hidden, n_out, n_obs)
     rs = np.random.RandomState(seed)
     th = np.zeros(P, np.float32)
     for name, (off, shape) in spec.items():
@@ -487,29 +517,36 @@ class MujocoPolicy(Policy):
     Gaussian action noise of ac_noise_std in training rollouts.  The network is csrc/pendulum.h: the engine's kernel for whole populations, the
     same text compiled for the CPU for act / rollout of the single current theta.  (The environment itself can be stepped on the device under
     any policy's actions: envs.make('Pendulum-v0', n), csrc/step_env.h.)"""
-    kind = _lib.KIND_PENDULUM
+    kind = _lib.KIND_PENDULUM          # (an instance on the hard maze's spaces carries KIND_MJMAZE)
 
     def __init__(self, ob_space, ac_space, ac_bins, ac_noise_std, nonlin_type, hidden_dims, connection_type, engine=None):
-        self.hidden, self.n_out, self.ac_mode, self.nonlin = mujoco_shape(ac_bins, nonlin_type, hidden_dims, connection_type)
         assert len(ob_space.shape) == len(ac_space.shape) == 1                                # policies.py:130
+        # the layout comes from the observation width: 3 -> the pendulum (csrc/pendulum.h), 11 -> the hard maze (csrc/mjmaze.h)
+        self.on_maze = (tuple(ob_space.shape), tuple(ac_space.shape)) == ((_lib.MJMAZE_OBS,), (_lib.MJMAZE_ADIM,))
+        self.n_obs, adim = (_lib.MJMAZE_OBS, _lib.MJMAZE_ADIM) if self.on_maze else (_lib.PENDULUM_OBS, 1)
+        self.hidden, self.n_out, self.ac_mode, self.nonlin = mujoco_shape(ac_bins, nonlin_type, hidden_dims, connection_type, adim)
         assert np.all(np.isfinite(ac_space.low)) and np.all(np.isfinite(ac_space.high)), 'Action bounds required'
-        if tuple(ob_space.shape) != (_lib.PENDULUM_OBS,) or tuple(ac_space.shape) != (1,):
+        if not self.on_maze and (tuple(ob_space.shape) != (_lib.PENDULUM_OBS,) or tuple(ac_space.shape) != (1,)):
             raise NotImplementedError("MujocoPolicy: observation space {} and action space {} -- the HIP engine runs it on {} only, (3,) and (1,); "
                                       "no MuJoCo simulator is available".format(tuple(ob_space.shape), tuple(ac_space.shape), PENDULUM_ENV_ID))
         self.args = (ob_space, ac_space)
         self.kwargs = dict(ac_bins=ac_bins, ac_noise_std=ac_noise_std, nonlin_type=nonlin_type, hidden_dims=list(hidden_dims), connection_type=connection_type)
-        self.ob_space_shape, self.ac_space, self.num_actions = tuple(ob_space.shape), ac_space, 1   # num_actions: the action's dimension (snapshots)
+        self.ob_space_shape, self.ac_space, self.num_actions = tuple(ob_space.shape), ac_space, adim   # num_actions: the action's dimension (snapshots)
         self.ac_bins, self.ac_noise_std, self.hidden_dims, self.connection_type = ac_bins, float(ac_noise_std), list(hidden_dims), connection_type
-        self.spec, self.num_params = mujoco_layout(self.hidden, self.n_out)
-        assert self.num_params == _lib.pendulum_num_params(self.hidden, self.n_out)
+        self.spec, self.num_params = mujoco_layout(self.hidden, self.n_out, self.n_obs)
+        if self.on_maze:
+            self.kind = _lib.KIND_MJMAZE
+            assert self.num_params == _lib.mjmaze_num_params(self.hidden, self.n_out)
+        else:
+            assert self.num_params == _lib.pendulum_num_params(self.hidden, self.n_out)
         if engine is not None and (engine.kind != self.kind or engine.P != self.num_params or
                                    (getattr(engine, 'hidden', self.hidden), getattr(engine, 'n_actions', self.n_out)) != (self.hidden, self.n_out)):
-            raise ValueError("MujocoPolicy: the engine passed in (kind {}, P {}) does not hold this policy (KIND_PENDULUM {}, P {})".format(
-                engine.kind, engine.P, self.kind, self.num_params))
+            raise ValueError("MujocoPolicy: the engine passed in (kind {}, P {}) does not hold this policy ({} {}, P {})".format(
+                engine.kind, engine.P, 'KIND_MJMAZE' if self.on_maze else 'KIND_PENDULUM', self.kind, self.num_params))
         self.engine = engine
         self._flat = np.zeros(self.num_params, np.float32)
-        self.ob_mean = np.full(_lib.PENDULUM_OBS, np.nan, np.float32)                          # policies.py:138-141
-        self.ob_std = np.full(_lib.PENDULUM_OBS, np.nan, np.float32)
+        self.ob_mean = np.full(self.n_obs, np.nan, np.float32)                                 # policies.py:138-141
+        self.ob_std = np.full(self.n_obs, np.nan, np.float32)
 
     @property
     def needs_ob_stat(self):
@@ -522,10 +559,10 @@ class MujocoPolicy(Policy):
     def set_ob_stat(self, ob_mean, ob_std):
         self.ob_mean, self.ob_std = np.array(ob_mean, np.float32).reshape(-1), np.array(ob_std, np.float32).reshape(-1)
         if self.engine is not None:
-            self.engine.pendulum_set_ob_stat(self.ob_mean, self.ob_std)
+            (self.engine.mjmaze_set_ob_stat if self.on_maze else self.engine.pendulum_set_ob_stat)(self.ob_mean, self.ob_std)
 
     def initialize(self, seed=0):
-        self.set_trainable_flat(normc_flat(self.hidden, self.n_out, seed))
+        self.set_trainable_flat(normc_flat(self.hidden, self.n_out, seed, self.n_obs))
 
     def reinitialize(self):
         raise NotImplementedError("MujocoPolicy.reinitialize is the GA's (ga.py), which is not built for this policy")
@@ -534,10 +571,11 @@ class MujocoPolicy(Policy):
         return dict(hidden=self.hidden, mean=self.ob_mean, std=self.ob_std, n_out=self.n_out, ac_mode=self.ac_mode, nonlin=self.nonlin)
 
     def act(self, ob, random_stream=None):
-        """policies.py:202-206: actions [n][1] of observations [n][3] under the current theta"""
-        ob = np.asarray(ob, np.float32).reshape(-1, _lib.PENDULUM_OBS)
+        """policies.py:202-206: actions [n][1] of observations [n][3] under the current theta (the hard maze: [n][2] of [n][11])"""
+        ob = np.asarray(ob, np.float32).reshape(-1, self.n_obs)
         theta = np.broadcast_to(self.get_trainable_flat(), (ob.shape[0], self.num_params))
-        a = _lib.pendulum_forward_host(theta, ob, **self._shape_kw())[4].reshape(-1, 1)
+        forward = _lib.mjmaze_forward_host if self.on_maze else _lib.pendulum_forward_host
+        a = forward(theta, ob, **self._shape_kw())[4].reshape(-1, self.num_actions)
         if random_stream is not None and self.ac_noise_std != 0:
             a = a + (random_stream.randn(*a.shape) * self.ac_noise_std).astype(np.float32)
         return a
@@ -545,7 +583,11 @@ class MujocoPolicy(Policy):
     def rollout(self, env, *, render=False, timestep_limit=None, save_obs=False, random_stream=None, policy_seed=None):
         """policies.py:259-302: one episode of the current theta from env's next reset seed -> (rews float32 [T], T), with save_obs the
         observations acted on as well.  random_stream: the episode's 200 action-noise values are drawn from it (float32 of randn).  The
-        reference's third value, MuJoCo's centre of mass, does not exist."""
+        reference's third value, MuJoCo's centre of mass, does not exist.
+        On the hard maze (env: a HardMazeEnv): -> (rews, T, novelty_vector), novelty_vector float32 [2] = the final (x, y) -- the reference's
+        final (x_pos, y_pos), policies.py:292-299; the episode's 800 action-noise values are drawn from random_stream."""
+        if self.on_maze:
+            return self._rollout_maze(env, timestep_limit, save_obs, random_stream, policy_seed)
         limit = _lib.PENDULUM_STEPS if timestep_limit is None else min(int(timestep_limit), _lib.PENDULUM_STEPS)
         if policy_seed:
             env.seed(policy_seed)
@@ -561,22 +603,38 @@ class MujocoPolicy(Policy):
             return rews, limit, tr[:, :3].astype(np.float32)
         return rews, limit
 
+    def _rollout_maze(self, env, timestep_limit, save_obs, random_stream, policy_seed):
+        limit = _lib.MJMAZE_STEPS if timestep_limit is None else min(int(timestep_limit), _lib.MJMAZE_STEPS)
+        if policy_seed and random_stream:
+            random_stream.seed(policy_seed)
+        noisy = random_stream is not None and self.ac_noise_std != 0
+        table = random_stream.randn(_lib.MJMAZE_AC_NOISE).astype(np.float32) if noisy else None
+        r = _lib.mjmaze_rollout_host(self.get_trainable_flat(), env.header, env.lines, tslimit=limit, ac_noise_std=self.ac_noise_std, table=table,
+                                     ac_off=[0] if noisy else None, want_trace=save_obs, **self._shape_kw())
+        rews = np.zeros(limit, np.float32)
+        rews[-1] = r['returns'][0]                    # 0 until step 400, then minus the distance to the goal (a shorter episode: 0 throughout)
+        nov = r['xy'][0].copy()
+        if save_obs:
+            return rews, limit, r['trace'][0, :limit, :_lib.MJMAZE_OBS].copy(), nov
+        return rews, limit, nov
+
     def extra_variable_arrays(self, scope):
         """the two non-trainable variables of policies.py:138-141, after the trainable ones as all_variables lists them"""
         return OrderedDict([('%s/ob_mean:0' % scope, self.ob_mean.copy()), ('%s/ob_std:0' % scope, self.ob_std.copy())])
 
     def _spaces_blob(self):
-        return _dumps_spaces(self.ob_space_shape, 1, self.kwargs, ac_box=(float(self.ac_space.low[0]), float(self.ac_space.high[0])))
+        return _dumps_spaces(self.ob_space_shape, self.num_actions, self.kwargs, ac_box=(float(self.ac_space.low[0]), float(self.ac_space.high[0])))
 
     @classmethod
     def Load(cls, filename, engine=None, extra_kwargs=None):
         _, (ob_shape, adim), kwargs, arrays = cls._read_snapshot(filename)
         if extra_kwargs:
             kwargs.update(extra_kwargs)
-        if tuple(ob_shape) != (_lib.PENDULUM_OBS,) or adim != 1:
+        on_maze = (tuple(ob_shape), adim) == ((_lib.MJMAZE_OBS,), _lib.MJMAZE_ADIM)
+        if not on_maze and (tuple(ob_shape) != (_lib.PENDULUM_OBS,) or adim != 1):
             raise NotImplementedError("MujocoPolicy.Load: a policy on observations {} and {} action dimensions -- the HIP engine runs it on {} "
                                       "only; no MuJoCo simulator is available".format(tuple(ob_shape), adim, PENDULUM_ENV_ID))
-        env = PendulumEnv()
+        env = HardMazeEnv() if on_maze else PendulumEnv()
         pol = cls(env.observation_space, env.action_space, engine=engine, **kwargs)
         pol._set_from_arrays(arrays, exact=True)
         pol.set_ob_stat(arrays['MujocoPolicy/ob_mean:0'], arrays['MujocoPolicy/ob_std:0'])

@@ -56,6 +56,16 @@ extern "C" {
                            DNE_KIND_CARTPOLE, after dne_pendulum_set_ob_stat.  bc, record_bc and bc_final_only are refused.  The P-generic calls work
                            as on DNE_KIND_MAZE; every Atari-only, maze-only, cart-pole-only and GA-only call, dne_debug_plan and dne_debug_plan_act
                            refuse the kind. */
+#define DNE_KIND_MJMAZE 7 /* MujocoPolicy as on DNE_KIND_PENDULUM, on the deceptive hard maze of DNE_KIND_MAZE (csrc/mjmaze.h): 11
+                           observations, the action space Box(-0.5, 0.5, (2,)), 400 steps never done early, the reward 0 until step 400 and minus the
+                           distance to the goal there; the behaviour characterisation is the final (x, y), which is what NS-ES / NSR-ES with this
+                           policy need.  dne_config.reserved as on DNE_KIND_PENDULUM; n_actions carries the outputs: 2 continuous, 2 B for B = 2..8
+                           uniform bins a dimension.  P = dne_mjmaze_num_params(hidden, n_actions); dne_num_params answers -1.  An evaluation
+                           (dne_set_members + dne_eval_members, or dne_es_eval; env_seed may be NULL: there is no reset seed) comes after
+                           dne_maze_set_walls and dne_mjmaze_set_ob_stat.  Accepted beside the dne_mjmaze_* and the P-generic calls:
+                           dne_maze_set_walls, dne_maze_final_state, dne_maze_archive_append / _clear / _size / _get, dne_maze_novelty and
+                           dne_maze_novelty_last_ms.  bc, record_bc and bc_final_only are refused, and so is every other Atari, GA, maze-GA,
+                           pool-novelty, cart-pole, pendulum, plan and dne_stepenv_* call (the maze one step at a time is DNE_KIND_MAZE's). */
 #define DNE_OB_BYTES (84 * 84 * 4)
 #define DNE_RAM_BYTES 128
 #define DNE_BN_FLOATS 608
@@ -82,7 +92,7 @@ typedef struct {
     int32_t profile_events; /* 1: bracket hot kernels with HIP events (dne_get_profile) */
     int32_t bc_final_only;  /* ES with record_bc: keep only each member's final RAM ([members][128], what es_modified.py's
                                dumps use: bc_vec[-1], es_modified.py:176,197) instead of the whole trajectory */
-    int32_t reserved[6];    /* DNE_KIND_PENDULUM: [0] hidden width, [1] action mode, [2] nonlinearity (see there); otherwise 0 */
+    int32_t reserved[6];    /* DNE_KIND_PENDULUM, DNE_KIND_MJMAZE: [0] hidden width, [1] action mode, [2] nonlinearity (see there); otherwise 0 */
 } dne_config;
 
 typedef struct { /* filled by dne_get_profile; times from HIP events on the engine's stream */
@@ -416,6 +426,30 @@ int dne_pendulum_actions_host(const float *actions, int n, int T, const double *
 int dne_pendulum_forward_host(const float *theta, const float *obs, int n, int hidden, int n_out, int ac_mode, int nonlin, const float *mean,
                               const float *std, float *x, float *h1, float *h2, float *out, float *action);
 int dne_pendulum_math_host(int fn, const double *x, int n, float a, float b, double *out);
+
+/* ---- MujocoPolicy on the hard maze (DNE_KIND_MJMAZE; csrc/mjmaze.h) ----------------------
+ * Each call is the sibling of its dne_pendulum_* namesake, on 11 observations and 2 action dimensions.
+ * dne_mjmaze_num_params: P = 13 H + H^2 + H O + O, or -1 for a width or an output count the header does not build (O even, 2..16).
+ * dne_mjmaze_set_ob_stat: ob_mean [11] and ob_std [11]; NaN before the first call, and an evaluation is then refused.
+ * dne_mjmaze_set_rollout_options: for the NEXT evaluation only, which must run exactly n members: ac_off [n] (or NULL) -- where each member's
+ *   800 action-noise values start in the noise table (step t, dimension i reads ac_off + 2 t + i), < 0 for none; ac_off + 800 must lie inside
+ *   the table, checked here and again at the launch -- and stat_flag [n] (or NULL).
+ * dne_mjmaze_ob_stats: sum [n][11], sumsq [n][11] (doubles, in step order), count [n] of the last evaluation's first n members.
+ * dne_mjmaze_debug_trace: the kernel once more for ONE current member, without noise or statistics: trace [min(tslimit, 400)][20] floats = the
+ *   11 observations acted on, the net's 2 actions, the 2 applied, then x, y, heading, speed, ang_vel after the step; *steps = the rows.
+ * No handle, no GPU: dne_mjmaze_rollout_host (every input and output of the kernel; trace [n][tslimit][20] or NULL) and
+ *   dne_mjmaze_forward_host (raw observations [n][11] -> x [n][11], h1 [n][H], h2 [n][H], out [n][O], action [n][2]). */
+int dne_mjmaze_num_params(int hidden, int n_out);
+int dne_mjmaze_set_ob_stat(dne_handle *h, const float *mean /*[11]*/, const float *std /*[11]*/);
+int dne_mjmaze_set_rollout_options(dne_handle *h, int n, float ac_noise_std, const int64_t *ac_off /*[n] or NULL*/, const uint8_t *stat_flag /*[n] or NULL*/);
+int dne_mjmaze_ob_stats(dne_handle *h, int n, double *sum /*[n][11]*/, double *sumsq /*[n][11]*/, int32_t *count /*[n]*/);
+int dne_mjmaze_debug_trace(dne_handle *h, int member, int tslimit, float *trace, int32_t *steps);
+int dne_mjmaze_rollout_host(const float *theta, int n, int hidden, int n_out, int ac_mode, int nonlin, const float *mean, const float *std,
+                            const float *header8, const float *lines, int n_walls, int tslimit, float ac_noise_std, const float *table,
+                            size_t table_len, const int64_t *ac_off, const uint8_t *stat_flag, float *returns, float *signreturns, int32_t *lengths,
+                            float *xy, double *ob_sum, double *ob_sumsq, int32_t *ob_count, float *trace);
+int dne_mjmaze_forward_host(const float *theta, const float *obs, int n, int hidden, int n_out, int ac_mode, int nonlin, const float *mean,
+                            const float *std, float *x, float *h1, float *h2, float *out, float *action);
 
 /* ---- the maze, the cart-pole and the pendulum one step at a time (csrc/step_env.h) ------------------------------
  * The seam of gym_tensorflow/tf_env.py (reset / step / observation / final_state apart from the model) on the three whole-episode kinds: a

@@ -1,0 +1,253 @@
+"""CPU: MujocoPolicy on the hard maze outside the kernel -- csrc/mjmaze.h compiled for the host (dne_mjmaze_rollout_host / _forward_host, no GPU
+and no handle).  The environment is tied to csrc/maze.h (which tests/golden/maze_reference_rollouts.npz pins to the reference's own maze.h) by
+replaying the twin's applied actions through dne_maze_actions_host; the policy is held to the numpy restatement of tests/mjmaze_support.py bit
+for bit; then the action-noise stream, the observation statistics against float64 numpy, the shapes and refusals, nses / nsr / es
+run_master + run_worker on MjMazeHostEngine, and the header under AddressSanitizer + UBSan in a stand-alone program."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import mjmaze_support as S
+import update_support as U
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KW64 = dict(hidden=64, mean=S.MEAN, std=S.STD)
+
+
+@pytest.fixture(scope="module")
+def traced():
+    """one traced episode of the twin in the fixture maze, once: H = 64 tanh, continuous, action noise from offset 1000, statistics on"""
+    from dne_hip import _lib
+    header, lines = S.fixture_maze()
+    theta, table = S.random_theta(64, 2, 11), S.maze_noise()
+    r = _lib.mjmaze_rollout_host(theta[None], header, lines, ac_noise_std=0.05, table=table, ac_off=[1000], stat_flag=[1], want_trace=True, **KW64)
+    return dict(header=header, lines=lines, theta=theta, table=table, r=r, trace=r['trace'][0])
+
+
+# ---- 1. the environment is maze.h's ----------------------------------------------------------------------------------------------------------------
+def test_environment_is_the_maze_headers(traced):
+    from dne_hip import _lib
+    tr, r = traced['trace'], traced['r']
+    assert tr.shape == (S.STEPS, S.TRACE_W) and r['lengths'][0] == S.STEPS
+    rows, obs0 = _lib.maze_actions_host(tr[None, :, 13:15], traced['header'], traced['lines'])
+    rows, obs0 = rows[0], obs0[0]
+    assert np.array_equal(S.bits(tr[0, :11]), S.bits(obs0))                         # the first observation acted on is the reset's
+    assert np.array_equal(S.bits(tr[1:, :11]), S.bits(rows[:-1, :11]))              # every later one is the observation after the step before
+    assert np.array_equal(S.bits(tr[:, 15:20]), S.bits(rows[:, 11:16]))             # x, y, heading, speed, ang_vel after each step
+    assert (tr[:, 0] == 1.0).all() and np.ptp(tr[:, 15]) > 1.0, "the navigator never moved: the episode shows nothing"
+    assert S.bits(r['returns'])[0] == S.bits(rows[-1, 17:18])[0] and r['returns'][0] < 0 and r['signreturns'][0] == -1.0
+    assert np.array_equal(r['xy'][0], tr[-1, 15:17])
+    short = _lib.mjmaze_rollout_host(traced['theta'][None], traced['header'], traced['lines'], tslimit=7, **KW64)
+    assert short['lengths'][0] == 7 and short['returns'][0] == 0.0 and short['signreturns'][0] == 0.0 and S.bits(short['returns'])[0] == 0
+
+
+# ---- 2. the policy ------------------------------------------------------------------------------------------------------------------------------------
+OBS_TYPICAL = np.array([1.0, 0.31, 0.27, 1.0, 0.22, 0.08, 0.55, 0.0, 1.0, 0.0, 0.0], np.float32)
+OBS_CLIP = np.array([1.0, 1.0, 1.0, 0.0, 1.0, 0.01, 1.0, 1.0, 0.0, 1.0, 0.0], np.float32)
+STD_TIGHT = np.array([1.0, 0.1, 0.15, 0.05, 0.1, 0.25, 0.01, 0.3, 0.05, 0.45, 0.4], np.float32)
+
+
+@pytest.mark.parametrize("H", S.HS)
+@pytest.mark.parametrize("nonlin", S.NONLINS)
+@pytest.mark.parametrize("mode, O", S.MODES)
+def test_forward_is_the_numpy_restatement(H, nonlin, mode, O):
+    from dne_hip import _lib
+    theta = S.random_theta(H, O, 100 + H + O)
+    for ob, std in ((OBS_TYPICAL, S.STD), (OBS_CLIP, STD_TIGHT)):
+        got = _lib.mjmaze_forward_host(theta[None], ob[None], H, S.MEAN, std, n_out=O, ac_mode=mode, nonlin=nonlin)
+        want = S.forward_np(theta, ob, H, O, mode, nonlin, S.MEAN, std)
+        for g, w, name in zip(got, want, ("x", "h1", "h2", "out", "action")):
+            assert np.array_equal(S.bits(g[0]), S.bits(w)), (name, H, nonlin, mode, O)
+        assert got[0][0, 0] == np.float32(np.float32(1.0) - np.float32(0.9))         # the constant bias input is normalised like the rest
+    assert (got[0][0] == 5.0).any() and (got[0][0] == -5.0).any()                    # the second observation clips both ways
+    if mode == 'uniform':
+        assert (got[4] >= -0.5).all() and (got[4] <= 0.5).all()                      # a bin's centre lies inside the action space
+
+
+def _bias_theta(H, biases):
+    """every weight 0: the outputs are the output biases"""
+    th = np.zeros(S.offsets(H, len(biases))[6], np.float32)
+    th[-len(biases):] = biases
+    return th
+
+
+def test_bin_edge_cases():
+    from dne_hip import _lib
+    nan = np.nan
+    for biases, want in (([1, 2, 2, 0, 3, 3, 3, 3], (-0.5 + 1 / 3, -0.5)),           # a tie picks the lower bin
+                         ([nan] * 8, (-0.5, -0.5)),                                  # all NaN gives bin 0
+                         ([nan, nan, nan, nan, 0, 0, 1, 0], (-0.5, -0.5 + 2 / 3)),   # NaN in one dimension only
+                         ([nan, 5, nan, 7, -np.inf, -np.inf, -np.inf, -np.inf], (0.5, -0.5))):   # a NaN never wins; all -inf gives bin 0
+        th = _bias_theta(64, np.array(biases, np.float32))
+        out, act = _lib.mjmaze_forward_host(th[None], OBS_TYPICAL[None], 64, S.MEAN, S.STD, n_out=8, ac_mode='uniform')[3:]
+        assert S.bits(act[0]).tolist() == S.bits(np.array([S.pick_dim_np(out[0], i, 'uniform') for i in (0, 1)], np.float32)).tolist()
+        assert np.allclose(act[0], want, atol=1e-6)
+
+
+# ---- 3. action noise, statistics ---------------------------------------------------------------------------------------------------------------------
+def test_action_noise_reads_the_table_at_2t_plus_i(traced):
+    tr, table = traced['trace'], traced['table']
+    eps = table[1000:1000 + S.AC_NOISE].reshape(S.STEPS, 2)
+    want = (tr[:, 11:13] + (np.float32(0.05) * eps).astype(np.float32)).astype(np.float32)
+    assert np.array_equal(S.bits(tr[:, 13:15]), S.bits(want)) and not np.array_equal(tr[:, 13:15], tr[:, 11:13])
+
+
+def test_statistics_are_float64_sums_in_step_order(traced):
+    from dne_hip import _lib
+    tr, r = traced['trace'], traced['r']
+    s, q = np.zeros(11), np.zeros(11)
+    for t in range(S.STEPS):
+        d = tr[t, :11].astype(np.float64)
+        s += d
+        q += d * d
+    assert np.array_equal(r['ob_sum'][0], s) and np.array_equal(r['ob_sumsq'][0], q) and r['ob_count'][0] == S.STEPS
+    plain = _lib.mjmaze_rollout_host(np.stack([traced['theta']] * 2), traced['header'], traced['lines'], tslimit=9, stat_flag=[0, 1], **KW64)
+    assert not plain['ob_sum'][0].any() and not plain['ob_sumsq'][0].any() and plain['ob_count'].tolist() == [0, 9]
+    assert plain['ob_sum'][1][0] == 9.0
+
+
+# ---- 4. shapes and refusals ----------------------------------------------------------------------------------------------------------------------------
+def test_shapes_and_refusals(oracle, tmp_path):
+    from dne_hip import _lib, es, ga, nses, policies
+    for H in S.HS:
+        for O in (2, 4, 16):
+            assert _lib.mjmaze_num_params(H, O) == 13 * H + H * H + H * O + O == S.offsets(H, O)[6]
+    assert _lib.mjmaze_num_params(256, 2) == 69378 and _lib.mjmaze_num_params(64, 2) == 5058
+    assert _lib.mjmaze_num_params(96, 2) == -1 and _lib.mjmaze_num_params(64, 18) == -1 and _lib.mjmaze_num_params(64, 3) == -1
+    assert _lib.num_params(_lib.KIND_MJMAZE, 2) == -1
+    header, lines = S.fixture_maze()
+    th, table = S.random_theta(64, 2, 1)[None], S.maze_noise()
+    ok = _lib.mjmaze_rollout_host(th, header, lines, tslimit=3, ac_noise_std=0.01, table=table, ac_off=[table.size - S.AC_NOISE], **KW64)
+    assert ok['lengths'][0] == 3                                                        # ac_off + 800 at the table's end is accepted
+    with pytest.raises(_lib.DneError, match="past the noise table"):                    # one further is refused
+        _lib.mjmaze_rollout_host(th, header, lines, tslimit=3, ac_noise_std=0.01, table=table, ac_off=[table.size - S.AC_NOISE + 1], **KW64)
+    e = S.MjMazeHostEngine()
+    e.noise_upload(table)
+    e.mjmaze_set_rollout_options(2, 0.01, np.array([0, table.size - S.AC_NOISE], np.int64), None)
+    with pytest.raises(_lib.DneError, match="past the noise table"):
+        e.mjmaze_set_rollout_options(2, 0.01, np.array([0, table.size - S.AC_NOISE + 1], np.int64), None)
+    with pytest.raises(_lib.DneError, match="not a shape"):
+        _lib.mjmaze_rollout_host(np.zeros((1, _lib.mjmaze_num_params(64, 4)), np.float32), header, lines, n_out=4, ac_mode='continuous', **KW64)
+    env = policies.HardMazeEnv()
+    assert env.observation_space.shape == (11,) and env.action_space.shape == (2,) and env.max_episode_steps == 400
+    assert env.action_space.low.tolist() == [-0.5, -0.5] and env.action_space.high.tolist() == [0.5, 0.5] and os.path.exists(env.maze_file)
+    base = S.humanoid_exp()["policy"]["args"]
+    for over, word in ((dict(ac_bins="uniform:9"), "uniform:9"), (dict(ac_bins="custom:-1,0,1"), "custom"), (dict(hidden_dims=[96, 96]), "96"),
+                       (dict(nonlin_type="elu"), "elu"), (dict(ac_bins="uniform:1"), "uniform:1")):
+        with pytest.raises(NotImplementedError, match=word):
+            policies.MujocoPolicy(env.observation_space, env.action_space, **dict(base, **over))
+    assert policies.MujocoPolicy(env.observation_space, env.action_space, **dict(base, ac_bins="uniform:8")).n_out == 16
+    pend = policies.PendulumEnv()
+    assert policies.MujocoPolicy(pend.observation_space, pend.action_space, **dict(base, ac_bins="uniform:16")).n_out == 16   # the pendulum keeps its 16
+    for kind_call in (_lib.debug_plan, _lib.debug_plan_act):
+        with pytest.raises(_lib.DneError, match="DNE_KIND_MJMAZE"):
+            kind_call(_lib.KIND_MJMAZE, 2, 8, 2) if kind_call is _lib.debug_plan else kind_call(_lib.KIND_MJMAZE, 2, 8)
+    with pytest.raises(_lib.DneError, match="kind 7 has no step-at-a-time environment"):
+        _lib.stepenv_dims(_lib.KIND_MJMAZE)
+    # the drivers: an env_id that is neither keeps its message, the pendulum under nses / ga keeps its refusal, ga stays refused on the maze
+    import pendulum_support as PS
+    with pytest.raises(NotImplementedError, match="MuJoCo"):
+        es.setup(S.humanoid_exp(env_id="Humanoid-v1"), engine=S.MjMazeHostEngine())
+    with pytest.raises(ValueError, match="KIND_MJMAZE"):
+        es.setup(S.humanoid_exp(), engine=PS.PendulumHostEngine())
+    with pytest.raises(NotImplementedError, match="nses with MujocoPolicy is not built: its behaviour characterisation is MuJoCo's centre of mass"):
+        nses.run_master({}, str(tmp_path), dict(PS.humanoid_exp(), algo_type="nses", novelty_search={}), engine=PS.PendulumHostEngine())
+    with pytest.raises(NotImplementedError, match="ga with MujocoPolicy"):
+        ga.setup(S.humanoid_exp(), engine=S.MjMazeHostEngine())
+    # an evaluation before a maze is loaded, and before the statistics are set
+    with pytest.raises(_lib.DneError, match="no maze loaded"):
+        e.es_eval(np.array([5], np.int64), 0.02, 400, np.zeros(2, np.uint32))
+    e.maze_set_walls(header, lines)
+    e.mjmaze_set_rollout_options(2, 0.0, None, None)
+    with pytest.raises(_lib.DneError, match="set_ob_stat"):
+        e.es_eval(np.array([5], np.int64), 0.02, 400, np.zeros(2, np.uint32))
+
+
+def test_policy_surface_and_snapshot_round_trip(tmp_path):
+    from dne_hip import _lib, policies
+    env = policies.HardMazeEnv()
+    args = S.humanoid_exp(ac_bins="uniform:5", nonlin="relu")["policy"]["args"]
+    pol = policies.MujocoPolicy(env.observation_space, env.action_space, **args)
+    assert pol.kind == _lib.KIND_MJMAZE and pol.num_params == _lib.mjmaze_num_params(64, 10) and pol.needs_ob_stat and pol.num_actions == 2
+    pol.initialize(2)
+    pol.set_ob_stat(S.MEAN, S.STD)
+    th = pol.get_trainable_flat()
+    a = pol.act(OBS_TYPICAL[None])
+    assert a.shape == (1, 2) and np.array_equal(a[0], S.forward_np(th, OBS_TYPICAL, 64, 10, 'uniform', 'relu', S.MEAN, S.STD)[4])
+    rews, t, nov = pol.rollout(env)
+    want = _lib.mjmaze_rollout_host(th[None], env.header, env.lines, 64, S.MEAN, S.STD, n_out=10, ac_mode='uniform', nonlin='relu')
+    assert t == 400 and rews.shape == (400,) and not rews[:-1].any() and rews[-1] == want['returns'][0]
+    assert nov.dtype == np.float32 and nov.shape == (2,) and np.array_equal(nov, want['xy'][0])
+    rews, t, nov = pol.rollout(env, timestep_limit=13, random_stream=np.random.RandomState(2))
+    assert t == 13 and not rews.any()
+    arrays = pol.variable_arrays()
+    assert [x.shape for x in arrays.values()] == [(11, 64), (64,), (64, 64), (64,), (64, 10), (10,), (11,), (11,)]
+    for ext in (".npz", policies.snapshot_extension()):
+        fn = str(tmp_path / ("snap" + ext))
+        pol.save(fn)
+        back = policies.MujocoPolicy.Load(fn)
+        assert np.array_equal(back.get_trainable_flat(), th) and np.array_equal(back.ob_mean, S.MEAN) and np.array_equal(back.ob_std, S.STD)
+        assert back.kwargs == pol.kwargs and (back.kind, back.hidden, back.n_out, back.ac_mode, back.nonlin) == (_lib.KIND_MJMAZE, 64, 10, 'uniform', 'relu')
+        assert back.ac_space.low.tolist() == [-0.5, -0.5]
+
+
+# ---- 5. the drivers on the host twin ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("algo", ["ns", "nsr"])
+def test_nses_and_nsr_on_the_host_twin(oracle, tmp_path, algo):
+    from dne_hip import es
+    noise = es.SharedNoiseTable(count=400_000)
+    exp = S.humanoid_nses_exp(algo_type=algo)
+    me, we = S.MjMazeHostEngine(), S.MjMazeHostEngine()
+    seen = S.spy_novelty(we)
+    run = S.run_nses(exp, me, we, noise, tmp_path)
+    S.check_nses_run(run, exp, noise, seen)
+    assert we.appends_seen == [5, 1]                                    # the worker's mirror of the archive takes only what is new
+    n, std, off, flag = we.options_seen[0]
+    assert n == 8 and std == np.float32(0.01) and off is not None and (off + S.AC_NOISE <= noise.noise.size).all() and flag.shape == (8,)
+
+
+def test_es_on_the_host_twin(oracle, tmp_path):
+    import es_driver_support as D
+    from dne_hip import es, policies
+    noise = es.SharedNoiseTable(count=400_000)
+    exp = S.humanoid_exp(pop=8, eval_prob=1.0)
+    me, we = S.MjMazeHostEngine(), S.MjMazeHostEngine()
+    run = D.run_driver(es, exp, me, we, noise, tmp_path, 1, worker_seed=1234)
+    wid = np.random.RandomState(1234).randint(2 ** 31)
+    mine = [(t, r) for t, r in run.pushed if r.worker_id == wid]
+    shards = [r for _, r in mine if r.eval_length is None]
+    evals = [r for _, r in mine if r.eval_length is not None]
+    assert len(shards) == 1 and len(evals) == 1 and evals[0].eval_length == S.STEPS and evals[0].eval_return < 0
+    r0 = shards[0]
+    n, std, off, flag = we.options_seen[0]
+    assert n == 8 and r0.ob_count == S.STEPS * int(flag.sum()) > 0 and r0.ob_sum.shape == (11,) and r0.ob_sum.dtype == np.float32
+    theta0 = policies.normc_flat(64, 2, 0, 11)
+    assert np.array_equal(run.tasks[0].params, theta0) and np.array_equal(run.tasks[0].ob_mean, np.zeros(11, np.float32))
+    g = U.weighted_sum_np(noise.noise, r0.noise_inds_n, U.pair_weights_np(U.ranks_np(r0.returns_n2)), theta0.size, float(r0.returns_n2.size))
+    new, _, _, ratio = U.adam_np(theta0, np.zeros_like(theta0), np.zeros_like(theta0), g, 1, 0.005, 0.01)
+    assert U.same_bits(run.theta, new) and abs(run.ratios[0] - ratio) <= 1e-9 * ratio
+    st = es.RunningStat((11,), eps=1e-2)
+    st.increment(r0.ob_sum, r0.ob_sumsq, r0.ob_count)
+    assert np.array_equal(run.policy.ob_mean, st.mean) and np.array_equal(run.policy.ob_std, st.std)
+
+
+# ---- 6. the header under AddressSanitizer and UBSan, in a program of its own ---------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def sanitizer_program(tmp_path_factory):
+    """tests/mjmaze_asan_main.cpp, built once: address, undefined and float-cast-overflow (a NaN or an infinity reaching a cast to int)"""
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
+    src = os.path.join(ROOT, "tests", "mjmaze_asan_main.cpp")
+    exe = str(tmp_path_factory.mktemp("mjmaze_asan") / "mjmaze_asan")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined,float-cast-overflow",
+                           "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "deep-neuroevolution_amd", "csrc"), src, "-o", exe, "-lm"])
+    return exe
+
+
+def test_header_under_sanitizers_in_a_stand_alone_program(sanitizer_program):
+    out = subprocess.run([sanitizer_program], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    # 3 widths x 4 output counts x 2 nonlinearities (2 of 400 steps, 22 of 23); 5 facts each + 4; outside the contract 6 fills x 3 deviations x 2
+    assert out.stdout.split() == ["ok", "24", "1306", "facts", "124", "wild", "36", "900"], out.stdout
