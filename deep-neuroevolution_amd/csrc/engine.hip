@@ -670,12 +670,17 @@ struct dne_handle {
     bool cartpole = false;           // DNE_KIND_CARTPOLE: whole episodes in k_cartpole_rollout (csrc/cartpole.h); the maze's create path without walls
     double *cp_state = nullptr; int cp_last_n = 0;   // final (x, x_dot, theta, theta_dot) per member of the last evaluation, and how many members that was
     bool pendulum = false;           // DNE_KIND_PENDULUM: MujocoPolicy on the pendulum swing-up, whole episodes in k_pendulum_rollout (csrc/pendulum.h)
-    int pd_hidden = 0, pd_nl = 0;    // hidden width (64 / 128 / 256) and nonlinearity of the engine's policy; pd_opt: outputs, action mode, ob_mean / ob_std, noise std
-    pendulum::Options pd_opt{};
-    bool pd_stat_set = false;        // dne_pendulum_set_ob_stat was called (before it ob_mean / ob_std are NaN and an evaluation is refused)
-    double *pd_state = nullptr, *pd_sum = nullptr, *pd_sumsq = nullptr; int32_t *pd_count = nullptr; int pd_last_n = 0;   // per member of the last evaluation
-    int64_t *pd_acoff = nullptr; uint8_t *pd_flag = nullptr;   // dne_pendulum_set_rollout_options: per member, for the next evaluation only
-    int pd_opt_n = 0; bool pd_has_off = false, pd_has_flag = false; std::vector<int64_t> pd_host_off;   // (the offsets once more on the host: checked again at the launch)
+    pendulum::Options pd_opt{};      // outputs, action mode, ob_mean / ob_std, noise std
+    double *pd_state = nullptr;      // final (theta, theta_dot) per member of the last evaluation
+    // what the two MujocoPolicy kinds (DNE_KIND_PENDULUM, DNE_KIND_MJMAZE: a handle is one of them) keep alike; their Options differ in width
+    int pd_hidden = 0, pd_nl = 0;    // hidden width (64 / 128 / 256) and nonlinearity of the engine's policy
+    int pd_last_n = 0;               // members of the last evaluation
+    struct MujocoOptions {
+        bool stat_set = false;       // dne_*_set_ob_stat was called (before it ob_mean / ob_std are NaN and an evaluation is refused)
+        double *sum = nullptr, *sumsq = nullptr; int32_t *count = nullptr;   // observation statistics per member of the last evaluation
+        int64_t *off = nullptr; uint8_t *flag = nullptr;   // dne_*_set_rollout_options: per member, for the next evaluation only
+        int n = 0; bool has_off = false, has_flag = false; std::vector<int64_t> host_off;   // (the offsets once more on the host: checked again at the launch)
+    } mo;
     // the step-at-a-time environment batch (csrc/step_env.h, dne_stepenv_*): max_members environments apart from everything an evaluation reads
     // or writes, allocated by the first dne_stepenv_* call that needs it.  se_io_*: what one call uploads and fetches, [max_members] each
     stepenv::Batch se{}; bool se_ready = false; std::vector<uint8_t> se_was_reset;   // (the bitmap: on the host, one byte per environment)
@@ -683,11 +688,9 @@ struct dne_handle {
     uint8_t *se_io_done = nullptr; double *se_io_state = nullptr;
     hipEvent_t se_ev_a = nullptr, se_ev_b = nullptr; double se_last_ms = -1.0;   // the last step kernel between two device events
     // DNE_KIND_MJMAZE: MujocoPolicy on the hard maze, whole episodes in k_mjmaze_rollout (csrc/mjmaze.h).  It shares the maze's walls, final
-    // positions and archive (maze_*, mzn_*) and the pendulum's shape, per-member options and statistics buffers (pd_hidden, pd_nl, pd_acoff,
-    // pd_flag, pd_sum, pd_sumsq, pd_count, pd_opt_n, pd_has_*, pd_host_off); mj_opt holds its own 11 means and deviations
+    // positions and archive (maze_*, mzn_*); mj_opt holds its own 11 means and deviations
     bool mjmaze = false;
     mjmaze::Options mj_opt{};
-    bool mj_stat_set = false;
     bool episodic() const { return maze || cartpole || pendulum || mjmaze; }   // a whole episode per member in one launch: what dne_es_eval and the record calls accept beside the Atari kinds
     bool large = false;              // DNE_KIND_GA_LARGE: y1 [441][32], y2 / y3 [121][64] (conv3 output), y3t = the 512 fc outputs
     float *y1r[2] = {nullptr, nullptr}, *y2r[2] = {nullptr, nullptr}, *y3pr[2] = {nullptr, nullptr};   // reference pass scratch, two ways
@@ -848,6 +851,26 @@ struct DeviceGuard {
     }
     ~DeviceGuard() { if (prev >= 0) hipSetDevice(prev); }
 };
+
+// the four whole-episode kinds by name, and the one spelling of "this call is another kind's"
+static_assert(DNE_KIND_CARTPOLE == DNE_KIND_MAZE + 1 && DNE_KIND_PENDULUM == DNE_KIND_MAZE + 2 && DNE_KIND_MJMAZE == DNE_KIND_MAZE + 3, "the table below");
+static const char *episodic_kind_name(int kind) {
+    static const char *const names[] = {"DNE_KIND_MAZE", "DNE_KIND_CARTPOLE", "DNE_KIND_PENDULUM", "DNE_KIND_MJMAZE"};
+    return names[kind - DNE_KIND_MAZE];
+}
+static int needs_kind(dne_handle *h, const char *call, int kind) {
+    return h->L.kind == kind ? 0 : h->fail("%s needs a %s engine (this one: kind %d)", call, episodic_kind_name(kind), h->L.kind);
+}
+
+// f(the Options of the MujocoPolicy kind this handle is): the two types differ in the width of mean / std alone
+template <class F> static void with_mujoco_options(dne_handle *h, F &&f) { if (h->mjmaze) f(h->mj_opt); else f(h->pd_opt); }
+
+// an Options (pendulum: 3 observations, mjmaze: 11) from its parts; mean / std null: NaN, the policy before set_ob_stat (policies.py:138-141)
+template <class Options>
+static void fill_options(Options &o, int n_out, int ac_mode, float ac_noise_std, const float *mean, const float *std) {
+    o.n_out = n_out; o.ac_mode = ac_mode; o.ac_noise_std = ac_noise_std;
+    for (size_t i = 0; i < sizeof(o.mean) / sizeof(float); i++) { o.mean[i] = mean ? mean[i] : NAN; o.std[i] = std ? std[i] : NAN; }
+}
 
 static void make_layout(int kind, int nact, Layout *L) {
     int o = 0;
@@ -1185,19 +1208,13 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         h->maze = cfg->policy_kind == DNE_KIND_MAZE;
         h->cartpole = cfg->policy_kind == DNE_KIND_CARTPOLE;
         h->pendulum = cfg->policy_kind == DNE_KIND_PENDULUM;
-        make_layout(cfg->policy_kind, cfg->n_actions, &h->L);
-        if (h->pendulum) {
-            h->pd_hidden = cfg->reserved[0]; h->pd_nl = cfg->reserved[2];
-            h->pd_opt.n_out = cfg->n_actions; h->pd_opt.ac_mode = cfg->reserved[1];
-            for (int i = 0; i < pendulum::OBS; i++) h->pd_opt.mean[i] = h->pd_opt.std[i] = NAN;   // policies.py:138-141
-            h->L.P = pendulum::offsets(h->pd_hidden, cfg->n_actions).P;
-        }
         h->mjmaze = cfg->policy_kind == DNE_KIND_MJMAZE;
-        if (h->mjmaze) {
+        const bool mujoco = h->pendulum || h->mjmaze;
+        make_layout(cfg->policy_kind, cfg->n_actions, &h->L);
+        if (mujoco) {
             h->pd_hidden = cfg->reserved[0]; h->pd_nl = cfg->reserved[2];
-            h->mj_opt.n_out = cfg->n_actions; h->mj_opt.ac_mode = cfg->reserved[1];
-            for (int i = 0; i < mjmaze::OBS; i++) h->mj_opt.mean[i] = h->mj_opt.std[i] = NAN;   // policies.py:138-141
-            h->L.P = mjmaze::offsets(h->pd_hidden, cfg->n_actions).P;
+            with_mujoco_options(h, [&](auto &o) { fill_options(o, cfg->n_actions, cfg->reserved[1], 0.0f, nullptr, nullptr); });
+            h->L.P = h->mjmaze ? mjmaze::offsets(h->pd_hidden, cfg->n_actions).P : pendulum::offsets(h->pd_hidden, cfg->n_actions).P;
         }
         h->M = cfg->max_members;
         h->base_stride = ((size_t)h->L.P + 63) / 64 * 64;
@@ -1211,26 +1228,23 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         CH(hipMemset(h->m_slot, 0, M * sizeof(int32_t))); CH(hipMemset(h->m_off, 0, M * sizeof(int64_t))); CH(hipMemset(h->m_scale, 0, M * sizeof(float)));
         CH(h->alloc(&h->ret, M, "ret")); CH(h->alloc(&h->sign, M, "sign")); CH(h->alloc(&h->len, M, "len"));
         CH(hipMemset(h->ret, 0, M * sizeof(float))); CH(hipMemset(h->sign, 0, M * sizeof(float))); CH(hipMemset(h->len, 0, M * sizeof(int32_t)));
-        if (h->maze) {
+        if (h->maze || h->mjmaze) {
             CH(h->alloc(&h->maze_xy, 2 * M, "maze_xy")); CH(h->alloc(&h->maze_walls, maze::MAX_WALLS * 4, "maze_walls"));
             CH(hipMemset(h->maze_xy, 0, 2 * M * sizeof(float)));
-        } else if (h->cartpole) {
-            CH(h->alloc(&h->cp_state, 4 * M, "cartpole_state")); CH(h->alloc(&h->seeds, M, "seeds"));
-            CH(hipMemset(h->cp_state, 0, 4 * M * sizeof(double))); CH(hipMemset(h->seeds, 0, M * sizeof(uint32_t)));
-        } else if (h->mjmaze) {
-            CH(h->alloc(&h->maze_xy, 2 * M, "maze_xy")); CH(h->alloc(&h->maze_walls, maze::MAX_WALLS * 4, "maze_walls"));
-            CH(h->alloc(&h->pd_sum, mjmaze::OBS * M, "mjmaze_ob_sum")); CH(h->alloc(&h->pd_sumsq, mjmaze::OBS * M, "mjmaze_ob_sumsq")); CH(h->alloc(&h->pd_count, M, "mjmaze_ob_count"));
-            CH(h->alloc(&h->pd_acoff, M, "mjmaze_ac_off")); CH(h->alloc(&h->pd_flag, M, "mjmaze_stat_flag"));
-            CH(hipMemset(h->maze_xy, 0, 2 * M * sizeof(float)));
-            CH(hipMemset(h->pd_sum, 0, mjmaze::OBS * M * sizeof(double))); CH(hipMemset(h->pd_sumsq, 0, mjmaze::OBS * M * sizeof(double))); CH(hipMemset(h->pd_count, 0, M * sizeof(int32_t)));
-            CH(hipMemset(h->pd_acoff, 0xff, M * sizeof(int64_t))); CH(hipMemset(h->pd_flag, 0, M));
-        } else {
-            CH(h->alloc(&h->pd_state, 2 * M, "pendulum_state")); CH(h->alloc(&h->seeds, M, "seeds"));
-            CH(h->alloc(&h->pd_sum, 3 * M, "pendulum_ob_sum")); CH(h->alloc(&h->pd_sumsq, 3 * M, "pendulum_ob_sumsq")); CH(h->alloc(&h->pd_count, M, "pendulum_ob_count"));
-            CH(h->alloc(&h->pd_acoff, M, "pendulum_ac_off")); CH(h->alloc(&h->pd_flag, M, "pendulum_stat_flag"));
-            CH(hipMemset(h->pd_state, 0, 2 * M * sizeof(double))); CH(hipMemset(h->seeds, 0, M * sizeof(uint32_t)));
-            CH(hipMemset(h->pd_sum, 0, 3 * M * sizeof(double))); CH(hipMemset(h->pd_sumsq, 0, 3 * M * sizeof(double))); CH(hipMemset(h->pd_count, 0, M * sizeof(int32_t)));
-            CH(hipMemset(h->pd_acoff, 0xff, M * sizeof(int64_t))); CH(hipMemset(h->pd_flag, 0, M));
+        } else {   // the kinds that reset from a seed: the final state's doubles (the cart-pole: 4, the pendulum: 2) and the seeds
+            double *&state = h->cartpole ? h->cp_state : h->pd_state;
+            const size_t S = h->cartpole ? 4 : 2;
+            CH(h->alloc(&state, S * M, h->cartpole ? "cartpole_state" : "pendulum_state")); CH(h->alloc(&h->seeds, M, "seeds"));
+            CH(hipMemset(state, 0, S * M * sizeof(double))); CH(hipMemset(h->seeds, 0, M * sizeof(uint32_t)));
+        }
+        if (mujoco) {   // the statistics and the per-member options, under the kind's own block names
+            dne_handle::MujocoOptions &O = h->mo;
+            const size_t W = h->mjmaze ? mjmaze::OBS : pendulum::OBS;
+            const std::string kind = h->mjmaze ? "mjmaze" : "pendulum";
+            CH(h->alloc(&O.sum, W * M, (kind + "_ob_sum").c_str())); CH(h->alloc(&O.sumsq, W * M, (kind + "_ob_sumsq").c_str())); CH(h->alloc(&O.count, M, (kind + "_ob_count").c_str()));
+            CH(h->alloc(&O.off, M, (kind + "_ac_off").c_str())); CH(h->alloc(&O.flag, M, (kind + "_stat_flag").c_str()));
+            CH(hipMemset(O.sum, 0, W * M * sizeof(double))); CH(hipMemset(O.sumsq, 0, W * M * sizeof(double))); CH(hipMemset(O.count, 0, M * sizeof(int32_t)));
+            CH(hipMemset(O.off, 0xff, M * sizeof(int64_t))); CH(hipMemset(O.flag, 0, M));
         }
         if (h->maze && cfg->record_bc) {   // behaviour: the navigator's (x, y) after every step, [member][bc_max_steps][2] floats
             h->bc_bytes = M * (size_t)std::max(cfg->bc_max_steps, 1) * 2 * sizeof(float);
@@ -2311,14 +2325,81 @@ static maze::Header maze_header(const float *h8) {
     return m;
 }
 
-// what every entry point of the three maze sections asks first
-static int needs_maze(dne_handle *h, const char *call) {   // (a DNE_KIND_CARTPOLE engine is refused here like every other kind)
-    return h->maze ? 0 : h->fail("%s needs a DNE_KIND_MAZE engine (this one: kind %d)", call, h->L.kind);
+// ---- what the four whole-episode kinds share on the host: the evaluation, the arguments, the trace, the final state ----
+// where a rollout's members come from: descriptors (slot, off, scale) over the rows of `bases`
+struct MazeMembers { const float *bases; const int32_t *slot; const int64_t *off; const float *scale; };
+
+// the members set by dne_set_members
+static MazeMembers maze_set_members(dne_handle *h) { return {h->bases, h->m_slot, h->m_off, h->m_scale}; }
+
+// what every k_*_rollout reads for members [first, first + count) of M; the kind's own inputs and every output are left null
+template <class Args>
+static Args member_args(dne_handle *h, const MazeMembers &M, int first, int count, int tslimit) {
+    Args A{};
+    A.noise = h->noise; A.bases = M.bases; A.base_stride = h->base_stride;
+    A.m_slot = M.slot; A.m_off = M.off; A.m_scale = M.scale;
+    A.first = first; A.count = count; A.tslimit = tslimit;
+    return A;
 }
 
-// ... and the calls DNE_KIND_MJMAZE shares with it: the walls, the final positions, the archive and dne_maze_novelty
+// One evaluation of members [0, n), a whole episode each: launch() between ev_a and ev_b, the returns, sign-returns and lengths copied back, the
+// profile written.  What a kind refuses, uploads or clears comes before this call; what it counts (its *_last_n) after a 0 from here.
+template <class Launch>
+static int run_episodes(dne_handle *h, int n, float *returns, float *signreturns, int32_t *lengths, Launch &&launch) {
+    HCHECK(h, hipEventRecord(h->ev_a, h->stream));
+    launch();
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipEventRecord(h->ev_b, h->stream));
+    HCHECK(h, hipMemcpyAsync(returns, h->ret, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (signreturns) HCHECK(h, hipMemcpyAsync(signreturns, h->sign, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipMemcpyAsync(lengths, h->len, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    float ms = 0;
+    HCHECK(h, hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
+    dne_profile &P = h->prof;
+    P = dne_profile{};
+    P.eval_ms = P.env_ms = ms;
+    P.fc_launches = 1;
+    for (int i = 0; i < n; i++) P.env_steps += lengths[i];
+    return 0;
+}
+
+// what dne_{cartpole,pendulum,mjmaze}_debug_trace ask first ...
+static int trace_args(dne_handle *h, const char *call, int kind, int member, bool args_ok) {
+    if (needs_kind(h, call, kind)) return -1;
+    if (member < 0 || member >= (int)h->host_slot.size()) return h->fail("%s: member %d, dne_set_members set %zu", call, member, h->host_slot.size());
+    return args_ok ? 0 : h->fail("%s: bad arguments", call);
+}
+
+// ... and do last: launch(trace rows, step count) for one block, then the rows the kernel says it wrote, cap at the most
+template <class T, class Launch>
+static int run_trace(dne_handle *h, const char *call, int cap, int width, T *trace, int32_t *steps, Launch &&launch) {
+    DevBuf<T> d;
+    DevBuf<int32_t> dn;
+    HCHECK(h, d.alloc((size_t)cap * width));
+    HCHECK(h, dn.alloc(1));
+    launch((T *)d, (int32_t *)dn);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(steps, dn, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (*steps < 0 || *steps > cap) return h->fail("%s: the kernel reports %d steps under a limit of %d", call, *steps, cap);
+    HCHECK(h, hipMemcpy(trace, d, (size_t)*steps * width * sizeof(T), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// rows [0, n) of a per-member buffer of the last evaluation (its final states: `width` values a member)
+template <class T>
+static int last_eval_rows(dne_handle *h, const char *call, int n, int last_n, bool out_ok, T *out, const T *dev, int width) {
+    if (n < 1 || n > last_n) return h->fail("%s: %d members asked for, the last evaluation ran %d", call, n, last_n);
+    if (!out_ok) return h->fail("%s: no output buffer", call);
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(out, dev, (size_t)n * width * sizeof(T), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the calls DNE_KIND_MJMAZE shares with DNE_KIND_MAZE: the walls, the final positions, the archive and dne_maze_novelty
 static int needs_maze_env(dne_handle *h, const char *call) {
-    return h->mjmaze ? 0 : needs_maze(h, call);   // (every other kind: the refusal it always got)
+    return h->mjmaze ? 0 : needs_kind(h, call, DNE_KIND_MAZE);   // (every other kind: the refusal it always got)
 }
 
 extern "C" int dne_maze_set_walls(dne_handle *h, const float *header8, const float *lines, int n) {
@@ -2332,22 +2413,14 @@ extern "C" int dne_maze_set_walls(dne_handle *h, const float *header8, const flo
     return 0;
 }
 
-// where a rollout's members come from: descriptors (slot, off, scale) over the rows of `bases`
-struct MazeMembers { const float *bases; const int32_t *slot; const int64_t *off; const float *scale; };
-
-// the members set by dne_set_members
-static MazeMembers maze_set_members(dne_handle *h) { return {h->bases, h->m_slot, h->m_off, h->m_scale}; }
-
 // what k_maze_rollout reads for members [first, first + count) of M; its outputs are left null (maze_eval_members and the trace set theirs)
 static maze::RolloutArgs maze_args(dne_handle *h, const MazeMembers &M, int first, int count, int tslimit) {
-    maze::RolloutArgs A{};
-    A.noise = h->noise; A.bases = M.bases; A.base_stride = h->base_stride;
-    A.m_slot = M.slot; A.m_off = M.off; A.m_scale = M.scale;
-    A.first = first; A.count = count; A.hdr = h->maze_hdr; A.walls = h->maze_walls; A.nw = h->maze_nw; A.tslimit = tslimit;
+    maze::RolloutArgs A = member_args<maze::RolloutArgs>(h, M, first, count, tslimit);
+    A.hdr = h->maze_hdr; A.walls = h->maze_walls; A.nw = h->maze_nw;
     return A;
 }
 
-// members [0, n) of M, one whole episode each, one launch
+// members [0, n) of M (dne_set_members', or the GA bank's), one whole episode each, one launch
 static int maze_eval_members(dne_handle *h, const MazeMembers &M, int n, int tslimit, float *returns, float *signreturns, int32_t *lengths, uint8_t *bc_out) {
     if (h->maze_nw < 1) return h->fail("DNE_KIND_MAZE: no maze loaded (dne_maze_set_walls comes before an evaluation)");
     if (tslimit <= 0) return h->fail("timestep limit must be positive");
@@ -2358,44 +2431,23 @@ static int maze_eval_members(dne_handle *h, const MazeMembers &M, int n, int tsl
     maze::RolloutArgs A = maze_args(h, M, 0, n, tslimit);
     A.ret = h->ret; A.sign = h->sign; A.len = h->len; A.xy = h->maze_xy;
     A.bc = (float *)h->bc; A.bc_max_steps = h->bc ? std::max(h->cfg.bc_max_steps, 1) : 0;
-    HCHECK(h, hipEventRecord(h->ev_a, h->stream));
-    hipLaunchKernelGGL(maze::k_maze_rollout, dim3((n + 3) / 4), dim3(64), 0, h->stream, A);
-    HCHECK(h, hipGetLastError());
-    HCHECK(h, hipEventRecord(h->ev_b, h->stream));
-    HCHECK(h, hipMemcpyAsync(returns, h->ret, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    if (signreturns) HCHECK(h, hipMemcpyAsync(signreturns, h->sign, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HCHECK(h, hipMemcpyAsync(lengths, h->len, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HCHECK(h, hipStreamSynchronize(h->stream));
+    if (run_episodes(h, n, returns, signreturns, lengths, [&] { hipLaunchKernelGGL(maze::k_maze_rollout, dim3((n + 3) / 4), dim3(64), 0, h->stream, A); })) return -1;
     if (bc_out) HCHECK(h, hipMemcpy(bc_out, h->bc, bc_floats * sizeof(float), hipMemcpyDeviceToHost));
     h->maze_last_n = n;
-    float ms = 0;
-    HCHECK(h, hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
-    dne_profile &P = h->prof;
-    P = dne_profile{};
-    P.eval_ms = P.env_ms = ms;
-    P.fc_launches = 1;
-    for (int i = 0; i < n; i++) P.env_steps += lengths[i];
     return 0;
-}
-
-static int maze_eval(dne_handle *h, int n, int tslimit, float *returns, float *signreturns, int32_t *lengths, uint8_t *bc_out) {
-    return maze_eval_members(h, maze_set_members(h), n, tslimit, returns, signreturns, lengths, bc_out);
 }
 
 extern "C" int dne_maze_final_state(dne_handle *h, int n, float *xy) {
     DeviceGuard dg(h);
     if (needs_maze_env(h, "dne_maze_final_state")) return -1;
-    if (n < 1 || n > h->maze_last_n) return h->fail("dne_maze_final_state: %d members asked for, the last evaluation ran %d", n, h->maze_last_n);
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    HCHECK(h, hipMemcpy(xy, h->maze_xy, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    return last_eval_rows(h, "dne_maze_final_state", n, h->maze_last_n, true /* (xy is not looked at) */, xy, (const float *)h->maze_xy, 2);
 }
 
 // the kernel once more for ONE of the current members, with every step written out: trace [min(tslimit, 400)][16] as dne_maze_rollout_host
 // writes it.  The accumulators of the last evaluation are left alone.
 extern "C" int dne_maze_debug_trace(dne_handle *h, int member, int tslimit, float *trace) {
     DeviceGuard dg(h);
-    if (needs_maze(h, "dne_maze_debug_trace")) return -1;
+    if (needs_kind(h, "dne_maze_debug_trace", DNE_KIND_MAZE)) return -1;
     if (h->maze_nw < 1) return h->fail("DNE_KIND_MAZE: no maze loaded (dne_maze_set_walls comes before an evaluation)");
     if (member < 0 || member >= (int)h->host_slot.size()) return h->fail("dne_maze_debug_trace: member %d, dne_set_members set %zu", member, h->host_slot.size());
     if (tslimit <= 0 || !trace) return h->fail("dne_maze_debug_trace: bad arguments");
@@ -2453,7 +2505,7 @@ extern "C" int dne_maze_math_host(int fn, const double *x, int n, double *out) {
 
 extern "C" int dne_maze_debug_math(dne_handle *h, int fn, const double *x, int n, double *out) {
     DeviceGuard dg(h);
-    if (needs_maze(h, "dne_maze_debug_math")) return -1;
+    if (needs_kind(h, "dne_maze_debug_math", DNE_KIND_MAZE)) return -1;
     if (fn < 0 || fn >= maze::MATH_FNS || n < 1 || !x || !out) return h->fail("dne_maze_debug_math: bad arguments (fn 0..3, n >= 1)");
     DevBuf<double> dx, dout;
     HCHECK(h, dx.alloc((size_t)n)); HCHECK(h, dout.alloc(2 * (size_t)n));
@@ -2470,7 +2522,7 @@ static float *mzg_bank(dne_handle *h, int half) { return h->mzg_mem + (size_t)ha
 
 extern "C" int dne_maze_ga_set_init_scale(dne_handle *h, const float *scale_by, size_t n) {
     DeviceGuard dg(h);
-    if (needs_maze(h, "dne_maze_ga_set_init_scale")) return -1;
+    if (needs_kind(h, "dne_maze_ga_set_init_scale", DNE_KIND_MAZE)) return -1;
     if (n != (size_t)maze_ga::P || !scale_by) return h->fail("dne_maze_ga_set_init_scale: expected %d values, got %zu", maze_ga::P, n);
     if (!h->mzg_mem) {
         const size_t M = h->M;
@@ -2503,7 +2555,7 @@ static int mzg_upload_members(dne_handle *h, int n, const int32_t *a, const int6
 
 extern "C" int dne_maze_ga_build(dne_handle *h, int T, const int32_t *chain_offsets, const int64_t *seeds, const float *powers) {
     DeviceGuard dg(h);
-    if (needs_maze(h, "dne_maze_ga_build")) return -1;
+    if (needs_kind(h, "dne_maze_ga_build", DNE_KIND_MAZE)) return -1;
     if (mzg_ready(h, "dne_maze_ga_build", false)) return -1;
     if (T < 1 || T > h->M) return h->fail("dne_maze_ga_build: T = %d outside [1, max_members = %d]", T, h->M);
     if (!chain_offsets || !seeds || !powers) return h->fail("dne_maze_ga_build: a buffer is missing");
@@ -2532,7 +2584,7 @@ extern "C" int dne_maze_ga_build(dne_handle *h, int T, const int32_t *chain_offs
 
 extern "C" int dne_maze_ga_promote(dne_handle *h, int T_new, const int32_t *parent, const int64_t *idx, const float *power) {
     DeviceGuard dg(h);
-    if (needs_maze(h, "dne_maze_ga_promote")) return -1;
+    if (needs_kind(h, "dne_maze_ga_promote", DNE_KIND_MAZE)) return -1;
     if (mzg_ready(h, "dne_maze_ga_promote", false)) return -1;
     if (T_new < 1 || T_new > h->M) return h->fail("dne_maze_ga_promote: T = %d outside [1, max_members = %d]", T_new, h->M);
     if (!parent || !idx || !power) return h->fail("dne_maze_ga_promote: a buffer is missing");
@@ -2554,7 +2606,7 @@ extern "C" int dne_maze_ga_promote(dne_handle *h, int T_new, const int32_t *pare
 extern "C" int dne_maze_ga_eval(dne_handle *h, int n, const int32_t *parent, const int64_t *idx, const float *power, int tslimit,
                                 float *returns, float *signreturns, int32_t *lengths) {
     DeviceGuard dg(h);
-    if (needs_maze(h, "dne_maze_ga_eval")) return -1;
+    if (needs_kind(h, "dne_maze_ga_eval", DNE_KIND_MAZE)) return -1;
     if (mzg_ready(h, "dne_maze_ga_eval", true)) return -1;
     if (n < 1 || n > h->M) return h->fail("dne_maze_ga_eval: n = %d outside [1, max_members = %d]", n, h->M);
     if (!parent || !idx || !power || !returns || !lengths) return h->fail("dne_maze_ga_eval: a buffer is missing");
@@ -2583,13 +2635,13 @@ extern "C" int dne_maze_ga_eval(dne_handle *h, int n, const int32_t *parent, con
 }
 
 extern "C" int dne_maze_ga_parents(dne_handle *h) {
-    if (needs_maze(h, "dne_maze_ga_parents")) return -1;
+    if (needs_kind(h, "dne_maze_ga_parents", DNE_KIND_MAZE)) return -1;
     return h->mzg_T;
 }
 
 extern "C" int dne_maze_ga_get_parent(dne_handle *h, int j, float *out) {
     DeviceGuard dg(h);
-    if (needs_maze(h, "dne_maze_ga_get_parent")) return -1;
+    if (needs_kind(h, "dne_maze_ga_get_parent", DNE_KIND_MAZE)) return -1;
     if (j < 0 || j >= h->mzg_T) return h->fail("dne_maze_ga_get_parent: parent %d, the bank holds %d", j, h->mzg_T);
     if (!out) return h->fail("dne_maze_ga_get_parent: no output buffer");
     HCHECK(h, hipStreamSynchronize(h->stream));
@@ -2702,7 +2754,7 @@ extern "C" int dne_maze_archive_get(dne_handle *h, float *xy, int cap) {
 
 // what both scoring calls refuse alike, before the refusals of their own
 static int mzn_score_args(dne_handle *h, const char *call, bool pool, const float *xy, int n, int k) {
-    if (pool ? needs_maze(h, call) : needs_maze_env(h, call)) return -1;   // (pool novelty is GA-NS's: DNE_KIND_MAZE only)
+    if (pool ? needs_kind(h, call, DNE_KIND_MAZE) : needs_maze_env(h, call)) return -1;   // (pool novelty is GA-NS's: DNE_KIND_MAZE only)
     if (mzn_check_members(h, call, xy, n)) return -1;
     if (k < 1) return h->fail("%s: k = %d, at least one neighbour is needed", call, k);
     if (k > DNE_MAZE_NOVELTY_KMAX) return h->fail("%s: k = %d, the kernel keeps at most DNE_MAZE_NOVELTY_KMAX = %d neighbours", call, k, DNE_MAZE_NOVELTY_KMAX);
@@ -2752,7 +2804,7 @@ extern "C" int dne_maze_novelty_pool(dne_handle *h, const float *xy, int n, int 
 // archive slot A + i = the final position of the last evaluation's member members[i], device to device (k_maze_archive_gather)
 extern "C" int dne_maze_archive_append_members(dne_handle *h, const int32_t *members, int count) {
     DeviceGuard dg(h);
-    if (needs_maze(h, "dne_maze_archive_append_members")) return -1;
+    if (needs_kind(h, "dne_maze_archive_append_members", DNE_KIND_MAZE)) return -1;
     if (count < 1) return h->fail("dne_maze_archive_append_members: count = %d, at least one member is needed", count);
     if (!members) return h->fail("dne_maze_archive_append_members: no member indices");
     for (int i = 0; i < count; i++)
@@ -2793,16 +2845,10 @@ extern "C" int dne_maze_novelty_pool_host(const float *xy, int n, const float *a
 }
 
 // ------------------------------------------------------------------------------- gym.CartPole-v1 (csrc/cartpole.h)
-static int needs_cartpole(dne_handle *h, const char *call) {
-    return h->cartpole ? 0 : h->fail("%s needs a DNE_KIND_CARTPOLE engine (this one: kind %d)", call, h->L.kind);
-}
-
 // what k_cartpole_rollout reads for the members [first, first + count) set by dne_set_members; its outputs are left null
 static cartpole::RolloutArgs cartpole_args(dne_handle *h, int first, int count, int tslimit) {
-    cartpole::RolloutArgs A{};
-    A.noise = h->noise; A.bases = h->bases; A.base_stride = h->base_stride;
-    A.m_slot = h->m_slot; A.m_off = h->m_off; A.m_scale = h->m_scale;
-    A.first = first; A.count = count; A.seed = h->seeds; A.tslimit = tslimit;
+    cartpole::RolloutArgs A = member_args<cartpole::RolloutArgs>(h, maze_set_members(h), first, count, tslimit);
+    A.seed = h->seeds;
     return A;
 }
 
@@ -2817,58 +2863,29 @@ static int cartpole_eval(dne_handle *h, const char *call, int n, int tslimit, co
     HCHECK(h, hipMemcpyAsync(h->seeds, env_seed, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     cartpole::RolloutArgs A = cartpole_args(h, 0, n, tslimit);
     A.ret = h->ret; A.sign = h->sign; A.len = h->len; A.state = h->cp_state;
-    HCHECK(h, hipEventRecord(h->ev_a, h->stream));
-    hipLaunchKernelGGL(cartpole::k_cartpole_rollout, dim3((n + 3) / 4), dim3(64), 0, h->stream, A);
-    HCHECK(h, hipGetLastError());
-    HCHECK(h, hipEventRecord(h->ev_b, h->stream));
-    HCHECK(h, hipMemcpyAsync(returns, h->ret, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    if (signreturns) HCHECK(h, hipMemcpyAsync(signreturns, h->sign, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HCHECK(h, hipMemcpyAsync(lengths, h->len, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HCHECK(h, hipStreamSynchronize(h->stream));
+    if (run_episodes(h, n, returns, signreturns, lengths, [&] { hipLaunchKernelGGL(cartpole::k_cartpole_rollout, dim3((n + 3) / 4), dim3(64), 0, h->stream, A); })) return -1;
     h->cp_last_n = n;
-    float ms = 0;
-    HCHECK(h, hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
-    dne_profile &P = h->prof;
-    P = dne_profile{};
-    P.eval_ms = P.env_ms = ms;
-    P.fc_launches = 1;
-    for (int i = 0; i < n; i++) P.env_steps += lengths[i];
     return 0;
 }
 
 extern "C" int dne_cartpole_final_state(dne_handle *h, int n, double *state) {
     DeviceGuard dg(h);
-    if (needs_cartpole(h, "dne_cartpole_final_state")) return -1;
-    if (n < 1 || n > h->cp_last_n) return h->fail("dne_cartpole_final_state: %d members asked for, the last evaluation ran %d", n, h->cp_last_n);
-    if (!state) return h->fail("dne_cartpole_final_state: no output buffer");
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    HCHECK(h, hipMemcpy(state, h->cp_state, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    if (needs_kind(h, "dne_cartpole_final_state", DNE_KIND_CARTPOLE)) return -1;
+    return last_eval_rows(h, "dne_cartpole_final_state", n, h->cp_last_n, state != nullptr, state, (const double *)h->cp_state, 4);
 }
 
 // the kernel once more for ONE of the current members, with every step written out: trace [min(tslimit, 500)][8] as
 // dne_cartpole_rollout_host writes it.  The accumulators of the last evaluation are left alone.
 extern "C" int dne_cartpole_debug_trace(dne_handle *h, int member, int tslimit, const double *init4, double *trace, int32_t *steps) {
     DeviceGuard dg(h);
-    if (needs_cartpole(h, "dne_cartpole_debug_trace")) return -1;
-    if (member < 0 || member >= (int)h->host_slot.size()) return h->fail("dne_cartpole_debug_trace: member %d, dne_set_members set %zu", member, h->host_slot.size());
-    if (tslimit <= 0 || !trace || !steps) return h->fail("dne_cartpole_debug_trace: bad arguments");
+    if (trace_args(h, "dne_cartpole_debug_trace", DNE_KIND_CARTPOLE, member, tslimit > 0 && trace && steps)) return -1;
     if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
-    const int cap = std::min(tslimit, (int)cartpole::EPISODE_STEPS);
-    DevBuf<double> d;
-    DevBuf<int32_t> dn;
-    HCHECK(h, d.alloc((size_t)cap * cartpole::TRACE_W));
-    HCHECK(h, dn.alloc(1));
     cartpole::RolloutArgs A = cartpole_args(h, member, 1, tslimit);
     if (init4) { A.has_init = 1; for (int i = 0; i < 4; i++) A.init4[i] = init4[i]; }
-    A.trace = d; A.trace_steps = dn;
-    hipLaunchKernelGGL(cartpole::k_cartpole_rollout, dim3(1), dim3(64), 0, h->stream, A);
-    HCHECK(h, hipGetLastError());
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    HCHECK(h, hipMemcpy(steps, dn, sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (*steps < 0 || *steps > cap) return h->fail("dne_cartpole_debug_trace: the kernel reports %d steps under a limit of %d", *steps, cap);
-    HCHECK(h, hipMemcpy(trace, d, (size_t)*steps * cartpole::TRACE_W * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    return run_trace(h, "dne_cartpole_debug_trace", std::min(tslimit, (int)cartpole::EPISODE_STEPS), cartpole::TRACE_W, trace, steps, [&](double *rows, int32_t *count) {
+        A.trace = rows; A.trace_steps = count;
+        hipLaunchKernelGGL(cartpole::k_cartpole_rollout, dim3(1), dim3(64), 0, h->stream, A);
+    });
 }
 
 // the same header on the CPU: no handle, no GPU (like dne_maze_rollout_host)
@@ -2907,71 +2924,134 @@ extern "C" int dne_cartpole_forward_host(const float *theta, const float *obs, i
 }
 
 // ------------------------------------------------------------------------------- MujocoPolicy on the pendulum (csrc/pendulum.h)
-static int needs_pendulum(dne_handle *h, const char *call) {
-    return h->pendulum ? 0 : h->fail("%s needs a DNE_KIND_PENDULUM engine (this one: kind %d)", call, h->L.kind);
+// ---- what DNE_KIND_PENDULUM and DNE_KIND_MJMAZE share on the host; a call is told which of the two it belongs to by one of these
+struct MujocoKind { int kind; const char *name; int obs, ac_values; };   // (name: dne_<name>_*; the observation width; the action-noise values a member reads)
+static const MujocoKind MJ_PENDULUM = {DNE_KIND_PENDULUM, "pendulum", pendulum::OBS, pendulum::EPISODE_STEPS};
+static const MujocoKind MJ_MAZE = {DNE_KIND_MJMAZE, "mjmaze", mjmaze::OBS, mjmaze::AC_NOISE};
+
+// f(int_c<H>, std::bool_constant<TANH>) for the engine's hidden width and nonlinearity: the six instantiations of a MujocoPolicy kernel
+template <class F>
+static void with_mujoco_shape(const dne_handle *h, F &&f) {
+    const bool th = h->pd_nl == pendulum::NL_TANH;
+    switch (h->pd_hidden) {
+    case 64: with_bool(th, [&](auto TANH) { f(int_c<64>{}, TANH); }); break;
+    case 128: with_bool(th, [&](auto TANH) { f(int_c<128>{}, TANH); }); break;
+    default: with_bool(th, [&](auto TANH) { f(int_c<256>{}, TANH); });
+    }
 }
 
+// "" when every member's action-noise values [off, off + values) lie inside a table of `count` values (an offset < 0: the member reads none), else
+// the refusal; say_values: in the setter's words, which name how many values a member reads
+static std::string ac_off_refusal(const char *call, const int64_t *off, int n, int values, size_t count, bool say_values) {
+    for (int i = 0; i < n; i++)
+        if (off[i] >= 0 && (uint64_t)off[i] + values > (uint64_t)count)
+            return std::string(call) + ": member " + std::to_string(i) + " reads its " + (say_values ? std::to_string(values) + " action-noise values" : "action noise") +
+                   " from offset " + std::to_string(off[i]) + ", past the noise table's " + std::to_string(count) + " values";
+    return "";
+}
+static int ac_off_check(dne_handle *h, const char *call, const int64_t *off, int n, int values, bool say_values) {   // ... of a device call
+    const std::string bad = ac_off_refusal(call, off, n, values, h->noise_count, say_values);
+    return bad.empty() ? 0 : h->fail("%s", bad.c_str());
+}
+static int ac_off_check_host(const char *call, const int64_t *off, int n, int values, size_t count) {               // ... of a host call
+    const std::string bad = ac_off_refusal(call, off, n, values, count, false);
+    if (!bad.empty()) g_create_error = bad;
+    return bad.empty() ? 0 : -1;
+}
+
+static int mujoco_shape_host(const char *call, bool ok, int hidden, int n_out, int ac_mode, int nonlin, const char *header) {
+    if (!ok)
+        g_create_error = std::string(call) + ": hidden width " + std::to_string(hidden) + ", " + std::to_string(n_out) + " outputs, action mode " +
+                         std::to_string(ac_mode) + ", nonlinearity " + std::to_string(nonlin) + " is not a shape csrc/" + header + " builds";
+    return ok ? 0 : -1;
+}
+
+static int mujoco_set_ob_stat(dne_handle *h, const MujocoKind &K, const char *call, const float *mean, const float *std) {
+    DeviceGuard dg(h);
+    if (needs_kind(h, call, K.kind)) return -1;
+    if (!mean || !std) return h->fail("%s: bad arguments", call);
+    with_mujoco_options(h, [&](auto &o) { fill_options(o, o.n_out, o.ac_mode, o.ac_noise_std, mean, std); });
+    h->mo.stat_set = true;
+    return 0;
+}
+
+// action noise and observation statistics of the NEXT evaluation's first n members (later members: neither); that evaluation clears them
+static int mujoco_set_rollout_options(dne_handle *h, const MujocoKind &K, const char *call, int n, float ac_noise_std, const int64_t *ac_off, const uint8_t *stat_flag) {
+    DeviceGuard dg(h);
+    dne_handle::MujocoOptions &O = h->mo;
+    if (needs_kind(h, call, K.kind)) return -1;
+    if (check_n(h, n)) return -1;
+    if (!h->noise && ac_off) return h->fail("noise table not uploaded (dne_noise_upload)");
+    if (ac_off && ac_off_check(h, call, ac_off, n, K.ac_values, true)) return -1;
+    O.has_off = ac_off != nullptr; O.has_flag = stat_flag != nullptr;
+    if (ac_off) O.host_off.assign(ac_off, ac_off + n); else O.host_off.clear();
+    if (ac_off) HCHECK(h, hipMemcpyAsync(O.off, ac_off, n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    if (stat_flag) HCHECK(h, hipMemcpyAsync(O.flag, stat_flag, n, hipMemcpyHostToDevice, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    with_mujoco_options(h, [&](auto &o) { o.ac_noise_std = ac_noise_std; });
+    O.n = n;
+    return 0;
+}
+
+// what an evaluation and the trace ask alike of the statistics ...
+static int mujoco_stat_ready(dne_handle *h, const MujocoKind &K, const char *call) {
+    return h->mo.stat_set ? 0 : h->fail("%s: the observation statistics of a %s engine are NaN until dne_%s_set_ob_stat is called", call, episodic_kind_name(K.kind), K.name);
+}
+
+// ... and what an evaluation of n members asks of the options last: they were given for n members, and the table (it may have been replaced
+// since) still holds every member's action noise
+static int mujoco_options_ready(dne_handle *h, const MujocoKind &K, const char *call, int n) {
+    const dne_handle::MujocoOptions &O = h->mo;
+    if ((O.has_off || O.has_flag) && O.n != n)
+        return h->fail("%s: dne_%s_set_rollout_options was given %d members, this evaluation runs %d", call, K.name, O.n, n);
+    return O.has_off ? ac_off_check(h, call, O.host_off.data(), n, K.ac_values, false) : 0;
+}
+
+// the options and the statistics buffers into an evaluation's arguments (A.opt is the handle's already); the options were for this evaluation only
+template <class Args>
+static void mujoco_take_options(dne_handle *h, Args &A) {
+    dne_handle::MujocoOptions &O = h->mo;
+    A.ac_off = O.has_off ? O.off : nullptr; A.stat_flag = O.has_flag ? O.flag : nullptr;
+    A.ob_sum = O.sum; A.ob_sumsq = O.sumsq; A.ob_count = O.count;
+    O.has_off = O.has_flag = false; O.n = 0;
+    with_mujoco_options(h, [](auto &o) { o.ac_noise_std = 0.0f; });
+}
+
+static int mujoco_ob_stats(dne_handle *h, const MujocoKind &K, const char *call, int n, double *sum, double *sumsq, int32_t *count) {
+    DeviceGuard dg(h);
+    if (needs_kind(h, call, K.kind)) return -1;
+    if (n < 1 || n > h->pd_last_n) return h->fail("%s: %d members asked for, the last evaluation ran %d", call, n, h->pd_last_n);
+    if (!sum || !sumsq || !count) return h->fail("%s: no output buffer", call);
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(sum, h->mo.sum, (size_t)n * K.obs * sizeof(double), hipMemcpyDeviceToHost));
+    HCHECK(h, hipMemcpy(sumsq, h->mo.sumsq, (size_t)n * K.obs * sizeof(double), hipMemcpyDeviceToHost));
+    HCHECK(h, hipMemcpy(count, h->mo.count, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- the pendulum's own
 extern "C" int dne_pendulum_num_params(int hidden, int n_out) {
     if (!pendulum::hidden_ok(hidden) || n_out < 1 || n_out > pendulum::MAX_OUT) return -1;
     return pendulum::offsets(hidden, n_out).P;
 }
 
-// what k_pendulum_rollout reads for the members [first, first + count) set by dne_set_members; options and outputs are left null
+// what k_pendulum_rollout reads for the members [first, first + count) set by dne_set_members; the per-member options and the outputs are left null
 static pendulum::RolloutArgs pendulum_args(dne_handle *h, int first, int count, int tslimit) {
-    pendulum::RolloutArgs A{};
-    A.noise = h->noise; A.bases = h->bases; A.base_stride = h->base_stride;
-    A.m_slot = h->m_slot; A.m_off = h->m_off; A.m_scale = h->m_scale;
-    A.first = first; A.count = count; A.seed = h->seeds; A.tslimit = tslimit;
-    A.opt = h->pd_opt;
+    pendulum::RolloutArgs A = member_args<pendulum::RolloutArgs>(h, maze_set_members(h), first, count, tslimit);
+    A.seed = h->seeds; A.opt = h->pd_opt;
     return A;
 }
 
 static void pendulum_launch(dne_handle *h, const pendulum::RolloutArgs &A) {
-    const dim3 grid(A.count);
-    const bool th = h->pd_nl == pendulum::NL_TANH;
-    switch (h->pd_hidden) {
-    case 64:
-        if (th) hipLaunchKernelGGL((pendulum::k_pendulum_rollout<64, true>), grid, dim3(64), 0, h->stream, A);
-        else hipLaunchKernelGGL((pendulum::k_pendulum_rollout<64, false>), grid, dim3(64), 0, h->stream, A);
-        break;
-    case 128:
-        if (th) hipLaunchKernelGGL((pendulum::k_pendulum_rollout<128, true>), grid, dim3(128), 0, h->stream, A);
-        else hipLaunchKernelGGL((pendulum::k_pendulum_rollout<128, false>), grid, dim3(128), 0, h->stream, A);
-        break;
-    default:
-        if (th) hipLaunchKernelGGL((pendulum::k_pendulum_rollout<256, true>), grid, dim3(256), 0, h->stream, A);
-        else hipLaunchKernelGGL((pendulum::k_pendulum_rollout<256, false>), grid, dim3(256), 0, h->stream, A);
-    }
+    with_mujoco_shape(h, [&](auto H, auto TANH) { hipLaunchKernelGGL((pendulum::k_pendulum_rollout<H(), TANH()>), dim3(A.count), dim3(H()), 0, h->stream, A); });
 }
 
 extern "C" int dne_pendulum_set_ob_stat(dne_handle *h, const float *mean, const float *std) {
-    DeviceGuard dg(h);
-    if (needs_pendulum(h, "dne_pendulum_set_ob_stat")) return -1;
-    if (!mean || !std) return h->fail("dne_pendulum_set_ob_stat: bad arguments");
-    for (int i = 0; i < pendulum::OBS; i++) { h->pd_opt.mean[i] = mean[i]; h->pd_opt.std[i] = std[i]; }
-    h->pd_stat_set = true;
-    return 0;
+    return mujoco_set_ob_stat(h, MJ_PENDULUM, "dne_pendulum_set_ob_stat", mean, std);
 }
 
-// action noise and observation statistics of the NEXT evaluation's first n members (later members: neither); that evaluation clears them
 extern "C" int dne_pendulum_set_rollout_options(dne_handle *h, int n, float ac_noise_std, const int64_t *ac_off, const uint8_t *stat_flag) {
-    DeviceGuard dg(h);
-    if (needs_pendulum(h, "dne_pendulum_set_rollout_options")) return -1;
-    if (check_n(h, n)) return -1;
-    if (!h->noise && ac_off) return h->fail("noise table not uploaded (dne_noise_upload)");
-    if (ac_off)
-        for (int i = 0; i < n; i++)
-            if (ac_off[i] >= 0 && (uint64_t)ac_off[i] + pendulum::EPISODE_STEPS > (uint64_t)h->noise_count)
-                return h->fail("dne_pendulum_set_rollout_options: member %d reads its %d action-noise values from offset %lld, past the noise table's %zu values",
-                               i, pendulum::EPISODE_STEPS, (long long)ac_off[i], (size_t)h->noise_count);
-    h->pd_has_off = ac_off != nullptr; h->pd_has_flag = stat_flag != nullptr;
-    if (ac_off) h->pd_host_off.assign(ac_off, ac_off + n); else h->pd_host_off.clear();
-    if (ac_off) HCHECK(h, hipMemcpyAsync(h->pd_acoff, ac_off, n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    if (stat_flag) HCHECK(h, hipMemcpyAsync(h->pd_flag, stat_flag, n, hipMemcpyHostToDevice, h->stream));
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    h->pd_opt.ac_noise_std = ac_noise_std;
-    h->pd_opt_n = n;
-    return 0;
+    return mujoco_set_rollout_options(h, MJ_PENDULUM, "dne_pendulum_set_rollout_options", n, ac_noise_std, ac_off, stat_flag);
 }
 
 // members [0, n), one whole episode each under its own reset seed, one launch
@@ -2982,92 +3062,46 @@ static int pendulum_eval(dne_handle *h, const char *call, int n, int tslimit, co
     if (tslimit <= 0) return h->fail("timestep limit must be positive");
     if (!env_seed) return h->fail("%s: a DNE_KIND_PENDULUM engine resets every member from its environment seed, env_seed is NULL", call);
     if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
-    if (!h->pd_stat_set) return h->fail("%s: the observation statistics of a DNE_KIND_PENDULUM engine are NaN until dne_pendulum_set_ob_stat is called", call);
-    const bool has_off = h->pd_has_off, has_flag = h->pd_has_flag;
-    if ((has_off || has_flag) && h->pd_opt_n != n)
-        return h->fail("%s: dne_pendulum_set_rollout_options was given %d members, this evaluation runs %d", call, h->pd_opt_n, n);
-    if (has_off)   // the table may have been replaced since the options were set
-        for (int i = 0; i < n; i++)
-            if (h->pd_host_off[i] >= 0 && (uint64_t)h->pd_host_off[i] + pendulum::EPISODE_STEPS > (uint64_t)h->noise_count)
-                return h->fail("%s: member %d reads its action noise from offset %lld, past the noise table's %zu values", call, i, (long long)h->pd_host_off[i], (size_t)h->noise_count);
+    if (mujoco_stat_ready(h, MJ_PENDULUM, call) || mujoco_options_ready(h, MJ_PENDULUM, call, n)) return -1;
     HCHECK(h, hipMemcpyAsync(h->seeds, env_seed, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     pendulum::RolloutArgs A = pendulum_args(h, 0, n, tslimit);
-    A.ac_off = has_off ? h->pd_acoff : nullptr; A.stat_flag = has_flag ? h->pd_flag : nullptr;
     A.ret = h->ret; A.sign = h->sign; A.len = h->len; A.state = h->pd_state;
-    A.ob_sum = h->pd_sum; A.ob_sumsq = h->pd_sumsq; A.ob_count = h->pd_count;
-    h->pd_has_off = h->pd_has_flag = false; h->pd_opt_n = 0; h->pd_opt.ac_noise_std = 0.0f;   // the options were for this evaluation only
-    HCHECK(h, hipEventRecord(h->ev_a, h->stream));
-    pendulum_launch(h, A);
-    HCHECK(h, hipGetLastError());
-    HCHECK(h, hipEventRecord(h->ev_b, h->stream));
-    HCHECK(h, hipMemcpyAsync(returns, h->ret, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    if (signreturns) HCHECK(h, hipMemcpyAsync(signreturns, h->sign, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HCHECK(h, hipMemcpyAsync(lengths, h->len, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HCHECK(h, hipStreamSynchronize(h->stream));
+    mujoco_take_options(h, A);
+    if (run_episodes(h, n, returns, signreturns, lengths, [&] { pendulum_launch(h, A); })) return -1;
     h->pd_last_n = n;
-    float ms = 0;
-    HCHECK(h, hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
-    dne_profile &P = h->prof;
-    P = dne_profile{};
-    P.eval_ms = P.env_ms = ms;
-    P.fc_launches = 1;
-    for (int i = 0; i < n; i++) P.env_steps += lengths[i];
     return 0;
 }
 
 extern "C" int dne_pendulum_ob_stats(dne_handle *h, int n, double *sum, double *sumsq, int32_t *count) {
-    DeviceGuard dg(h);
-    if (needs_pendulum(h, "dne_pendulum_ob_stats")) return -1;
-    if (n < 1 || n > h->pd_last_n) return h->fail("dne_pendulum_ob_stats: %d members asked for, the last evaluation ran %d", n, h->pd_last_n);
-    if (!sum || !sumsq || !count) return h->fail("dne_pendulum_ob_stats: no output buffer");
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    HCHECK(h, hipMemcpy(sum, h->pd_sum, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    HCHECK(h, hipMemcpy(sumsq, h->pd_sumsq, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    HCHECK(h, hipMemcpy(count, h->pd_count, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return 0;
+    return mujoco_ob_stats(h, MJ_PENDULUM, "dne_pendulum_ob_stats", n, sum, sumsq, count);
 }
 
 extern "C" int dne_pendulum_final_state(dne_handle *h, int n, double *state) {
     DeviceGuard dg(h);
-    if (needs_pendulum(h, "dne_pendulum_final_state")) return -1;
-    if (n < 1 || n > h->pd_last_n) return h->fail("dne_pendulum_final_state: %d members asked for, the last evaluation ran %d", n, h->pd_last_n);
-    if (!state) return h->fail("dne_pendulum_final_state: no output buffer");
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    HCHECK(h, hipMemcpy(state, h->pd_state, (size_t)n * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    if (needs_kind(h, "dne_pendulum_final_state", DNE_KIND_PENDULUM)) return -1;
+    return last_eval_rows(h, "dne_pendulum_final_state", n, h->pd_last_n, state != nullptr, state, (const double *)h->pd_state, 2);
 }
 
 // the kernel once more for ONE of the current members, with every step written out: trace [min(tslimit, 200)][8] as dne_pendulum_rollout_host
 // writes it; no action noise, no statistics.  The accumulators of the last evaluation are left alone.
 extern "C" int dne_pendulum_debug_trace(dne_handle *h, int member, int tslimit, const double *init2, double *trace, int32_t *steps) {
     DeviceGuard dg(h);
-    if (needs_pendulum(h, "dne_pendulum_debug_trace")) return -1;
-    if (member < 0 || member >= (int)h->host_slot.size()) return h->fail("dne_pendulum_debug_trace: member %d, dne_set_members set %zu", member, h->host_slot.size());
-    if (tslimit <= 0 || !trace || !steps) return h->fail("dne_pendulum_debug_trace: bad arguments");
+    if (trace_args(h, "dne_pendulum_debug_trace", DNE_KIND_PENDULUM, member, tslimit > 0 && trace && steps)) return -1;
     if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
-    if (!h->pd_stat_set) return h->fail("dne_pendulum_debug_trace: the observation statistics of a DNE_KIND_PENDULUM engine are NaN until dne_pendulum_set_ob_stat is called");
-    const int cap = std::min(tslimit, (int)pendulum::EPISODE_STEPS);
-    DevBuf<double> d;
-    DevBuf<int32_t> dn;
-    HCHECK(h, d.alloc((size_t)cap * pendulum::TRACE_W));
-    HCHECK(h, dn.alloc(1));
+    if (mujoco_stat_ready(h, MJ_PENDULUM, "dne_pendulum_debug_trace")) return -1;
     pendulum::RolloutArgs A = pendulum_args(h, member, 1, tslimit);
     A.opt.ac_noise_std = 0.0f;
     if (init2) { A.has_init = 1; A.init2[0] = init2[0]; A.init2[1] = init2[1]; }
-    A.trace = d; A.trace_steps = dn;
-    pendulum_launch(h, A);
-    HCHECK(h, hipGetLastError());
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    HCHECK(h, hipMemcpy(steps, dn, sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (*steps < 0 || *steps > cap) return h->fail("dne_pendulum_debug_trace: the kernel reports %d steps under a limit of %d", *steps, cap);
-    HCHECK(h, hipMemcpy(trace, d, (size_t)*steps * pendulum::TRACE_W * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    return run_trace(h, "dne_pendulum_debug_trace", std::min(tslimit, (int)pendulum::EPISODE_STEPS), pendulum::TRACE_W, trace, steps, [&](double *rows, int32_t *count) {
+        A.trace = rows; A.trace_steps = count;
+        pendulum_launch(h, A);
+    });
 }
 
 // tanh_f, norm_angle and the normalise-and-clip of one component, value by value on the device (fn: pendulum.h's MATH_*; a, b: mean and std of fn 2)
 extern "C" int dne_pendulum_debug_math(dne_handle *h, int fn, const double *x, int n, float a, float b, double *out) {
     DeviceGuard dg(h);
-    if (needs_pendulum(h, "dne_pendulum_debug_math")) return -1;
+    if (needs_kind(h, "dne_pendulum_debug_math", DNE_KIND_PENDULUM)) return -1;
     if (fn < 0 || fn >= pendulum::MATH_FNS || n < 1 || !x || !out) return h->fail("dne_pendulum_debug_math: bad arguments");
     DevBuf<double> dx, dy;
     HCHECK(h, dx.alloc(n)); HCHECK(h, dy.alloc(n));
@@ -3088,13 +3122,9 @@ extern "C" int dne_pendulum_reset_host(uint32_t seed, double *out2) {
 }
 
 static int pendulum_shape_host(const char *call, int hidden, int n_out, int ac_mode, int nonlin) {
-    if (!pendulum::hidden_ok(hidden) || (nonlin != pendulum::NL_TANH && nonlin != pendulum::NL_RELU) ||
-        (ac_mode == pendulum::AC_CONTINUOUS ? n_out != 1 : (ac_mode != pendulum::AC_UNIFORM || n_out < 2 || n_out > pendulum::MAX_OUT))) {
-        g_create_error = std::string(call) + ": hidden width " + std::to_string(hidden) + ", " + std::to_string(n_out) + " outputs, action mode " +
-                         std::to_string(ac_mode) + ", nonlinearity " + std::to_string(nonlin) + " is not a shape csrc/pendulum.h builds";
-        return -1;
-    }
-    return 0;
+    const bool ok = pendulum::hidden_ok(hidden) && (nonlin == pendulum::NL_TANH || nonlin == pendulum::NL_RELU) &&
+                    (ac_mode == pendulum::AC_CONTINUOUS ? n_out == 1 : (ac_mode == pendulum::AC_UNIFORM && n_out >= 2 && n_out <= pendulum::MAX_OUT));
+    return mujoco_shape_host(call, ok, hidden, n_out, ac_mode, nonlin, "pendulum.h");
 }
 
 // one episode for each of n thetas [n][P] under seeds [n] (init2 [n][2] or NULL).  table / ac_off [n] (both or neither; an offset < 0: no noise for
@@ -3107,16 +3137,9 @@ extern "C" int dne_pendulum_rollout_host(const float *theta, int n, int hidden, 
         (ac_off != nullptr) != (table != nullptr)) { g_create_error = "dne_pendulum_rollout_host: bad arguments"; return -1; }
     if (pendulum_shape_host("dne_pendulum_rollout_host", hidden, n_out, ac_mode, nonlin)) return -1;
     pendulum::Options o{};
-    o.n_out = n_out; o.ac_mode = ac_mode; o.ac_noise_std = ac_noise_std;
-    for (int i = 0; i < pendulum::OBS; i++) { o.mean[i] = mean[i]; o.std[i] = std[i]; }
+    fill_options(o, n_out, ac_mode, ac_noise_std, mean, std);
     const size_t P = pendulum::offsets(hidden, n_out).P;
-    if (ac_off)
-        for (int i = 0; i < n; i++)
-            if (ac_off[i] >= 0 && (uint64_t)ac_off[i] + pendulum::EPISODE_STEPS > (uint64_t)table_len) {
-                g_create_error = "dne_pendulum_rollout_host: member " + std::to_string(i) + " reads its action noise from offset " + std::to_string(ac_off[i]) +
-                                 ", past the noise table's " + std::to_string(table_len) + " values";
-                return -1;
-            }
+    if (ac_off && ac_off_check_host("dne_pendulum_rollout_host", ac_off, n, MJ_PENDULUM.ac_values, table_len)) return -1;
     for (int i = 0; i < n; i++) {
         const bool stat = stat_flag && stat_flag[i];
         const pendulum::Episode e = pendulum::rollout_host(hidden, nonlin, theta + (size_t)i * P, o, seeds[i], init2 ? init2 + 2 * (size_t)i : nullptr, tslimit,
@@ -3142,8 +3165,7 @@ extern "C" int dne_pendulum_forward_host(const float *theta, const float *obs, i
     if (n < 1 || !theta || !obs || !mean || !std || !x || !h1 || !h2 || !out || !action) { g_create_error = "dne_pendulum_forward_host: bad arguments"; return -1; }
     if (pendulum_shape_host("dne_pendulum_forward_host", hidden, n_out, ac_mode, nonlin)) return -1;
     pendulum::Options o{};
-    o.n_out = n_out; o.ac_mode = ac_mode;
-    for (int i = 0; i < pendulum::OBS; i++) { o.mean[i] = mean[i]; o.std[i] = std[i]; }
+    fill_options(o, n_out, ac_mode, 0.0f, mean, std);
     const size_t P = pendulum::offsets(hidden, n_out).P;
     for (int i = 0; i < n; i++)
         action[i] = pendulum::forward_host(hidden, nonlin, theta + (size_t)i * P, o, obs + 3 * (size_t)i, x + 3 * (size_t)i, h1 + (size_t)i * hidden,
@@ -3158,79 +3180,35 @@ extern "C" int dne_pendulum_math_host(int fn, const double *x, int n, float a, f
 }
 
 // ------------------------------------------------------------------------------- MujocoPolicy on the hard maze (csrc/mjmaze.h)
-static int needs_mjmaze(dne_handle *h, const char *call) {
-    return h->mjmaze ? 0 : h->fail("%s needs a DNE_KIND_MJMAZE engine (this one: kind %d)", call, h->L.kind);
-}
-
 extern "C" int dne_mjmaze_num_params(int hidden, int n_out) {
     if (!pendulum::hidden_ok(hidden) || n_out < mjmaze::ADIM || n_out > mjmaze::MAX_OUT || n_out % mjmaze::ADIM != 0) return -1;
     return mjmaze::offsets(hidden, n_out).P;
 }
 
-// what k_mjmaze_rollout reads for the members [first, first + count) set by dne_set_members; options and outputs are left null
+// what k_mjmaze_rollout reads for the members [first, first + count) set by dne_set_members; the per-member options and the outputs are left null
 static mjmaze::RolloutArgs mjmaze_args(dne_handle *h, int first, int count, int tslimit) {
-    mjmaze::RolloutArgs A{};
-    A.noise = h->noise; A.bases = h->bases; A.base_stride = h->base_stride;
-    A.m_slot = h->m_slot; A.m_off = h->m_off; A.m_scale = h->m_scale;
-    A.first = first; A.count = count; A.hdr = h->maze_hdr; A.walls = h->maze_walls; A.nw = h->maze_nw; A.tslimit = tslimit;
-    A.opt = h->mj_opt;
+    mjmaze::RolloutArgs A = member_args<mjmaze::RolloutArgs>(h, maze_set_members(h), first, count, tslimit);
+    A.hdr = h->maze_hdr; A.walls = h->maze_walls; A.nw = h->maze_nw; A.opt = h->mj_opt;
     return A;
 }
 
 static void mjmaze_launch(dne_handle *h, const mjmaze::RolloutArgs &A) {
-    const dim3 grid(A.count);
-    const bool th = h->pd_nl == pendulum::NL_TANH;
-    switch (h->pd_hidden) {
-    case 64:
-        if (th) hipLaunchKernelGGL((mjmaze::k_mjmaze_rollout<64, true>), grid, dim3(64), 0, h->stream, A);
-        else hipLaunchKernelGGL((mjmaze::k_mjmaze_rollout<64, false>), grid, dim3(64), 0, h->stream, A);
-        break;
-    case 128:
-        if (th) hipLaunchKernelGGL((mjmaze::k_mjmaze_rollout<128, true>), grid, dim3(128), 0, h->stream, A);
-        else hipLaunchKernelGGL((mjmaze::k_mjmaze_rollout<128, false>), grid, dim3(128), 0, h->stream, A);
-        break;
-    default:
-        if (th) hipLaunchKernelGGL((mjmaze::k_mjmaze_rollout<256, true>), grid, dim3(256), 0, h->stream, A);
-        else hipLaunchKernelGGL((mjmaze::k_mjmaze_rollout<256, false>), grid, dim3(256), 0, h->stream, A);
-    }
+    with_mujoco_shape(h, [&](auto H, auto TANH) { hipLaunchKernelGGL((mjmaze::k_mjmaze_rollout<H(), TANH()>), dim3(A.count), dim3(H()), 0, h->stream, A); });
 }
 
 extern "C" int dne_mjmaze_set_ob_stat(dne_handle *h, const float *mean, const float *std) {
-    DeviceGuard dg(h);
-    if (needs_mjmaze(h, "dne_mjmaze_set_ob_stat")) return -1;
-    if (!mean || !std) return h->fail("dne_mjmaze_set_ob_stat: bad arguments");
-    for (int i = 0; i < mjmaze::OBS; i++) { h->mj_opt.mean[i] = mean[i]; h->mj_opt.std[i] = std[i]; }
-    h->mj_stat_set = true;
-    return 0;
+    return mujoco_set_ob_stat(h, MJ_MAZE, "dne_mjmaze_set_ob_stat", mean, std);
 }
 
-// action noise and observation statistics of the NEXT evaluation's first n members (later members: neither); that evaluation clears them
 extern "C" int dne_mjmaze_set_rollout_options(dne_handle *h, int n, float ac_noise_std, const int64_t *ac_off, const uint8_t *stat_flag) {
-    DeviceGuard dg(h);
-    if (needs_mjmaze(h, "dne_mjmaze_set_rollout_options")) return -1;
-    if (check_n(h, n)) return -1;
-    if (!h->noise && ac_off) return h->fail("noise table not uploaded (dne_noise_upload)");
-    if (ac_off)
-        for (int i = 0; i < n; i++)
-            if (ac_off[i] >= 0 && (uint64_t)ac_off[i] + mjmaze::AC_NOISE > (uint64_t)h->noise_count)
-                return h->fail("dne_mjmaze_set_rollout_options: member %d reads its %d action-noise values from offset %lld, past the noise table's %zu values",
-                               i, mjmaze::AC_NOISE, (long long)ac_off[i], (size_t)h->noise_count);
-    h->pd_has_off = ac_off != nullptr; h->pd_has_flag = stat_flag != nullptr;
-    if (ac_off) h->pd_host_off.assign(ac_off, ac_off + n); else h->pd_host_off.clear();
-    if (ac_off) HCHECK(h, hipMemcpyAsync(h->pd_acoff, ac_off, n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    if (stat_flag) HCHECK(h, hipMemcpyAsync(h->pd_flag, stat_flag, n, hipMemcpyHostToDevice, h->stream));
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    h->mj_opt.ac_noise_std = ac_noise_std;
-    h->pd_opt_n = n;
-    return 0;
+    return mujoco_set_rollout_options(h, MJ_MAZE, "dne_mjmaze_set_rollout_options", n, ac_noise_std, ac_off, stat_flag);
 }
 
 // what an evaluation and the trace ask alike before a launch
 static int mjmaze_ready(dne_handle *h, const char *call) {
     if (h->maze_nw < 1) return h->fail("DNE_KIND_MJMAZE: no maze loaded (dne_maze_set_walls comes before an evaluation)");
     if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
-    if (!h->mj_stat_set) return h->fail("%s: the observation statistics of a DNE_KIND_MJMAZE engine are NaN until dne_mjmaze_set_ob_stat is called", call);
-    return 0;
+    return mujoco_stat_ready(h, MJ_MAZE, call);
 }
 
 // members [0, n), one whole episode each from the header's start point (no reset seed: env_seed is not read), one launch
@@ -3238,83 +3216,36 @@ static int mjmaze_eval(dne_handle *h, const char *call, int n, int tslimit, floa
     if (bc_out) return h->fail("%s: behaviour characterisations are not available on a DNE_KIND_MJMAZE engine (kind %d): bc must be NULL; "
                                "dne_maze_final_state has the final (x, y) of every member", call, DNE_KIND_MJMAZE);
     if (tslimit <= 0) return h->fail("timestep limit must be positive");
-    if (mjmaze_ready(h, call)) return -1;
-    const bool has_off = h->pd_has_off, has_flag = h->pd_has_flag;
-    if ((has_off || has_flag) && h->pd_opt_n != n)
-        return h->fail("%s: dne_mjmaze_set_rollout_options was given %d members, this evaluation runs %d", call, h->pd_opt_n, n);
-    if (has_off)   // the table may have been replaced since the options were set
-        for (int i = 0; i < n; i++)
-            if (h->pd_host_off[i] >= 0 && (uint64_t)h->pd_host_off[i] + mjmaze::AC_NOISE > (uint64_t)h->noise_count)
-                return h->fail("%s: member %d reads its action noise from offset %lld, past the noise table's %zu values", call, i, (long long)h->pd_host_off[i], (size_t)h->noise_count);
+    if (mjmaze_ready(h, call) || mujoco_options_ready(h, MJ_MAZE, call, n)) return -1;
     mjmaze::RolloutArgs A = mjmaze_args(h, 0, n, tslimit);
-    A.ac_off = has_off ? h->pd_acoff : nullptr; A.stat_flag = has_flag ? h->pd_flag : nullptr;
     A.ret = h->ret; A.sign = h->sign; A.len = h->len; A.xy = h->maze_xy;
-    A.ob_sum = h->pd_sum; A.ob_sumsq = h->pd_sumsq; A.ob_count = h->pd_count;
-    h->pd_has_off = h->pd_has_flag = false; h->pd_opt_n = 0; h->mj_opt.ac_noise_std = 0.0f;   // the options were for this evaluation only
-    HCHECK(h, hipEventRecord(h->ev_a, h->stream));
-    mjmaze_launch(h, A);
-    HCHECK(h, hipGetLastError());
-    HCHECK(h, hipEventRecord(h->ev_b, h->stream));
-    HCHECK(h, hipMemcpyAsync(returns, h->ret, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    if (signreturns) HCHECK(h, hipMemcpyAsync(signreturns, h->sign, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HCHECK(h, hipMemcpyAsync(lengths, h->len, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HCHECK(h, hipStreamSynchronize(h->stream));
+    mujoco_take_options(h, A);
+    if (run_episodes(h, n, returns, signreturns, lengths, [&] { mjmaze_launch(h, A); })) return -1;
     h->maze_last_n = h->pd_last_n = n;
-    float ms = 0;
-    HCHECK(h, hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
-    dne_profile &P = h->prof;
-    P = dne_profile{};
-    P.eval_ms = P.env_ms = ms;
-    P.fc_launches = 1;
-    for (int i = 0; i < n; i++) P.env_steps += lengths[i];
     return 0;
 }
 
 extern "C" int dne_mjmaze_ob_stats(dne_handle *h, int n, double *sum, double *sumsq, int32_t *count) {
-    DeviceGuard dg(h);
-    if (needs_mjmaze(h, "dne_mjmaze_ob_stats")) return -1;
-    if (n < 1 || n > h->pd_last_n) return h->fail("dne_mjmaze_ob_stats: %d members asked for, the last evaluation ran %d", n, h->pd_last_n);
-    if (!sum || !sumsq || !count) return h->fail("dne_mjmaze_ob_stats: no output buffer");
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    HCHECK(h, hipMemcpy(sum, h->pd_sum, (size_t)n * mjmaze::OBS * sizeof(double), hipMemcpyDeviceToHost));
-    HCHECK(h, hipMemcpy(sumsq, h->pd_sumsq, (size_t)n * mjmaze::OBS * sizeof(double), hipMemcpyDeviceToHost));
-    HCHECK(h, hipMemcpy(count, h->pd_count, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return 0;
+    return mujoco_ob_stats(h, MJ_MAZE, "dne_mjmaze_ob_stats", n, sum, sumsq, count);
 }
 
 // the kernel once more for ONE of the current members, with every step written out: trace [min(tslimit, 400)][20] as dne_mjmaze_rollout_host
 // writes it; no action noise, no statistics.  The accumulators of the last evaluation are left alone.
 extern "C" int dne_mjmaze_debug_trace(dne_handle *h, int member, int tslimit, float *trace, int32_t *steps) {
     DeviceGuard dg(h);
-    if (needs_mjmaze(h, "dne_mjmaze_debug_trace")) return -1;
-    if (member < 0 || member >= (int)h->host_slot.size()) return h->fail("dne_mjmaze_debug_trace: member %d, dne_set_members set %zu", member, h->host_slot.size());
-    if (tslimit <= 0 || !trace || !steps) return h->fail("dne_mjmaze_debug_trace: bad arguments");
+    if (trace_args(h, "dne_mjmaze_debug_trace", DNE_KIND_MJMAZE, member, tslimit > 0 && trace && steps)) return -1;
     if (mjmaze_ready(h, "dne_mjmaze_debug_trace")) return -1;
-    const int cap = std::min(tslimit, (int)mjmaze::EPISODE_STEPS);
-    DevBuf<float> d;
-    DevBuf<int32_t> dn;
-    HCHECK(h, d.alloc((size_t)cap * mjmaze::TRACE_W));
-    HCHECK(h, dn.alloc(1));
     mjmaze::RolloutArgs A = mjmaze_args(h, member, 1, tslimit);
     A.opt.ac_noise_std = 0.0f;
-    A.trace = d; A.trace_steps = dn;
-    mjmaze_launch(h, A);
-    HCHECK(h, hipGetLastError());
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    HCHECK(h, hipMemcpy(steps, dn, sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (*steps < 0 || *steps > cap) return h->fail("dne_mjmaze_debug_trace: the kernel reports %d steps under a limit of %d", *steps, cap);
-    HCHECK(h, hipMemcpy(trace, d, (size_t)*steps * mjmaze::TRACE_W * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    return run_trace(h, "dne_mjmaze_debug_trace", std::min(tslimit, (int)mjmaze::EPISODE_STEPS), mjmaze::TRACE_W, trace, steps, [&](float *rows, int32_t *count) {
+        A.trace = rows; A.trace_steps = count;
+        mjmaze_launch(h, A);
+    });
 }
 
 // the same header on the CPU: no handle, no GPU
 static int mjmaze_shape_host(const char *call, int hidden, int n_out, int ac_mode, int nonlin) {
-    if (!mjmaze::shape_ok(hidden, n_out, ac_mode, nonlin)) {
-        g_create_error = std::string(call) + ": hidden width " + std::to_string(hidden) + ", " + std::to_string(n_out) + " outputs, action mode " +
-                         std::to_string(ac_mode) + ", nonlinearity " + std::to_string(nonlin) + " is not a shape csrc/mjmaze.h builds";
-        return -1;
-    }
-    return 0;
+    return mujoco_shape_host(call, mjmaze::shape_ok(hidden, n_out, ac_mode, nonlin), hidden, n_out, ac_mode, nonlin, "mjmaze.h");
 }
 
 // one episode for each of n thetas [n][P] in the maze (header8, lines).  table / ac_off [n] (both or neither; an offset < 0: no noise for that
@@ -3328,16 +3259,9 @@ extern "C" int dne_mjmaze_rollout_host(const float *theta, int n, int hidden, in
         (ac_off != nullptr) != (table != nullptr)) { g_create_error = "dne_mjmaze_rollout_host: bad arguments"; return -1; }
     if (mjmaze_shape_host("dne_mjmaze_rollout_host", hidden, n_out, ac_mode, nonlin)) return -1;
     mjmaze::Options o{};
-    o.n_out = n_out; o.ac_mode = ac_mode; o.ac_noise_std = ac_noise_std;
-    for (int i = 0; i < mjmaze::OBS; i++) { o.mean[i] = mean[i]; o.std[i] = std[i]; }
+    fill_options(o, n_out, ac_mode, ac_noise_std, mean, std);
     const size_t P = mjmaze::offsets(hidden, n_out).P;
-    if (ac_off)
-        for (int i = 0; i < n; i++)
-            if (ac_off[i] >= 0 && (uint64_t)ac_off[i] + mjmaze::AC_NOISE > (uint64_t)table_len) {
-                g_create_error = "dne_mjmaze_rollout_host: member " + std::to_string(i) + " reads its action noise from offset " + std::to_string(ac_off[i]) +
-                                 ", past the noise table's " + std::to_string(table_len) + " values";
-                return -1;
-            }
+    if (ac_off && ac_off_check_host("dne_mjmaze_rollout_host", ac_off, n, MJ_MAZE.ac_values, table_len)) return -1;
     const maze::Header m = maze_header(header8);
     for (int i = 0; i < n; i++) {
         const bool stat = stat_flag && stat_flag[i];
@@ -3358,8 +3282,7 @@ extern "C" int dne_mjmaze_forward_host(const float *theta, const float *obs, int
     if (n < 1 || !theta || !obs || !mean || !std || !x || !h1 || !h2 || !out || !action) { g_create_error = "dne_mjmaze_forward_host: bad arguments"; return -1; }
     if (mjmaze_shape_host("dne_mjmaze_forward_host", hidden, n_out, ac_mode, nonlin)) return -1;
     mjmaze::Options o{};
-    o.n_out = n_out; o.ac_mode = ac_mode;
-    for (int i = 0; i < mjmaze::OBS; i++) { o.mean[i] = mean[i]; o.std[i] = std[i]; }
+    fill_options(o, n_out, ac_mode, 0.0f, mean, std);
     const size_t P = mjmaze::offsets(hidden, n_out).P;
     for (int i = 0; i < n; i++)
         mjmaze::forward_host(hidden, nonlin, theta + (size_t)i * P, o, obs + mjmaze::OBS * (size_t)i, x + mjmaze::OBS * (size_t)i, h1 + (size_t)i * hidden,
@@ -3370,8 +3293,6 @@ extern "C" int dne_mjmaze_forward_host(const float *theta, const float *obs, int
 // ------------------------------------------------------------------------------- environments stepped by the caller (csrc/step_env.h)
 static_assert(stepenv::KIND_MAZE == DNE_KIND_MAZE && stepenv::KIND_CARTPOLE == DNE_KIND_CARTPOLE && stepenv::KIND_PENDULUM == DNE_KIND_PENDULUM,
               "step_env.h restates the three kinds");
-
-static const char *se_kind_name(int kind) { return kind == DNE_KIND_MAZE ? "DNE_KIND_MAZE" : kind == DNE_KIND_CARTPOLE ? "DNE_KIND_CARTPOLE" : "DNE_KIND_PENDULUM"; }
 
 extern "C" int dne_stepenv_dims(int kind, int *obs, int *act, int *state, int *act_is_int) {
     stepenv::Dims d;
@@ -3450,7 +3371,7 @@ static int se_reset(dne_handle *h, const char *call, int n, const int32_t *indic
             if (steps[i] < 0 || steps[i] >= limit)
                 return h->fail("%s: %d steps taken at position %d, an environment under a limit of %d has taken 0..%d", call, steps[i], i, limit, limit - 1);
     } else if (!h->maze && !seeds)
-        return h->fail("%s: a %s engine resets every environment from its seed, seeds is NULL", call, se_kind_name(h->L.kind));
+        return h->fail("%s: a %s engine resets every environment from its seed, seeds is NULL", call, episodic_kind_name(h->L.kind));
     if (se_alloc(h)) return -1;
     HCHECK(h, hipMemcpyAsync(h->se_io_idx, idx.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     if (set) {
@@ -3486,7 +3407,7 @@ static int se_step(dne_handle *h, const char *call, bool int_actions, int n, con
     if (se_check(h, call, n, indices, true, idx)) return -1;
     const stepenv::Dims d = se_dims(h);
     if ((d.act_is_int != 0) != int_actions)
-        return h->fail("%s: a %s engine takes %s actions (dne_stepenv_step_%s)", call, se_kind_name(h->L.kind), d.act_is_int ? "int32" : "float",
+        return h->fail("%s: a %s engine takes %s actions (dne_stepenv_step_%s)", call, episodic_kind_name(h->L.kind), d.act_is_int ? "int32" : "float",
                        d.act_is_int ? "i32" : "f32");
     if (!actions || !reward || !done) return h->fail("%s: actions, reward or done missing", call);
     if (h->cartpole)
@@ -3575,7 +3496,7 @@ extern "C" int dne_stepenv_reset_host(int kind, int n, const uint32_t *seeds, co
     stepenv::MazeCtx mz{};
     if (se_host_args("dne_stepenv_reset_host", kind, n, header8, lines, n_walls, &mz)) return -1;
     if (!state || !steps || !limit || !done || !obs) { g_create_error = "dne_stepenv_reset_host: an output buffer is missing"; return -1; }
-    if (kind != DNE_KIND_MAZE && !seeds) { g_create_error = std::string("dne_stepenv_reset_host: ") + se_kind_name(kind) + " resets every environment from its seed, seeds is NULL"; return -1; }
+    if (kind != DNE_KIND_MAZE && !seeds) { g_create_error = std::string("dne_stepenv_reset_host: ") + episodic_kind_name(kind) + " resets every environment from its seed, seeds is NULL"; return -1; }
     return stepenv::reset_host(kind, n, seeds, &mz, max_steps, state, steps, limit, done, obs);
 }
 
@@ -3602,6 +3523,16 @@ extern "C" int dne_stepenv_observe_host(int kind, int n, const double *state, co
 }
 
 // ------------------------------------------------------------------------------- evaluations by descriptor: antithetic pairs, members as set
+// the members set by dne_set_members through the whole-episode kernel of the engine's kind (the maze's episode is deterministic and mjmaze's has no
+// reset seed: neither reads env_seed)
+static int episodic_eval(dne_handle *h, const char *call, int n, int tslimit, const uint32_t *env_seed, float *returns, float *signreturns,
+                         int32_t *lengths, uint8_t *bc) {
+    if (h->maze) return maze_eval_members(h, maze_set_members(h), n, tslimit, returns, signreturns, lengths, bc);
+    if (h->cartpole) return cartpole_eval(h, call, n, tslimit, env_seed, returns, signreturns, lengths, bc);
+    if (h->pendulum) return pendulum_eval(h, call, n, tslimit, env_seed, returns, signreturns, lengths, bc);
+    return mjmaze_eval(h, call, n, tslimit, returns, signreturns, lengths, bc);
+}
+
 extern "C" int dne_es_eval(dne_handle *h, const int64_t *idx, int n, float sigma, int tslimit, const uint32_t *env_seed,
                            float *returns_n2, float *signreturns_n2, int32_t *lengths_n2, uint8_t *bc) {
     DeviceGuard dg(h);
@@ -3625,10 +3556,7 @@ extern "C" int dne_es_eval(dne_handle *h, const int64_t *idx, int n, float sigma
         const double span = (double)(hi - lo) + (double)h->L.P;
         h->dense_scale = std::min(16.0, std::max(1.0, (double)h->noise_count / std::max(span, 1.0)));
     }
-    if (h->maze) return maze_eval(h, 2 * n, tslimit, returns_n2, signreturns_n2, lengths_n2, bc);   // (the episode is deterministic: env_seed is not read)
-    if (h->cartpole) return cartpole_eval(h, "dne_es_eval", 2 * n, tslimit, env_seed, returns_n2, signreturns_n2, lengths_n2, bc);
-    if (h->pendulum) return pendulum_eval(h, "dne_es_eval", 2 * n, tslimit, env_seed, returns_n2, signreturns_n2, lengths_n2, bc);
-    if (h->mjmaze) return mjmaze_eval(h, "dne_es_eval", 2 * n, tslimit, returns_n2, signreturns_n2, lengths_n2, bc);   // (no reset seed: env_seed is not read)
+    if (h->episodic()) return episodic_eval(h, "dne_es_eval", 2 * n, tslimit, env_seed, returns_n2, signreturns_n2, lengths_n2, bc);
     return eval_core(h, 2 * n, 2, tslimit, env_seed, returns_n2, signreturns_n2, lengths_n2, bc);
 }
 
@@ -3636,21 +3564,9 @@ extern "C" int dne_eval_members(dne_handle *h, int n, int tslimit, const uint32_
                                 float *signreturns, int32_t *lengths, uint8_t *bc) {
     DeviceGuard dg(h);
     if (check_n(h, n)) return -1;
-    if (h->maze) {
+    if (h->episodic()) {
         if ((int)h->host_slot.size() < n) return h->fail("dne_eval_members: %d members asked for, dne_set_members set %zu", n, h->host_slot.size());
-        return maze_eval(h, n, tslimit, returns, signreturns, lengths, bc);
-    }
-    if (h->cartpole) {
-        if ((int)h->host_slot.size() < n) return h->fail("dne_eval_members: %d members asked for, dne_set_members set %zu", n, h->host_slot.size());
-        return cartpole_eval(h, "dne_eval_members", n, tslimit, env_seed, returns, signreturns, lengths, bc);
-    }
-    if (h->pendulum) {
-        if ((int)h->host_slot.size() < n) return h->fail("dne_eval_members: %d members asked for, dne_set_members set %zu", n, h->host_slot.size());
-        return pendulum_eval(h, "dne_eval_members", n, tslimit, env_seed, returns, signreturns, lengths, bc);
-    }
-    if (h->mjmaze) {
-        if ((int)h->host_slot.size() < n) return h->fail("dne_eval_members: %d members asked for, dne_set_members set %zu", n, h->host_slot.size());
-        return mjmaze_eval(h, "dne_eval_members", n, tslimit, returns, signreturns, lengths, bc);
+        return episodic_eval(h, "dne_eval_members", n, tslimit, env_seed, returns, signreturns, lengths, bc);
     }
     return eval_core(h, n, 1, tslimit, env_seed, returns, signreturns, lengths, bc);
 }

@@ -867,28 +867,44 @@ class Engine:
         self._ck(self.lib.dne_maze_debug_math(self.h, int(fn), _ptr(x, C.c_double), int(x.size), _ptr(out, C.c_double)))
         return out
 
-    # ---- MujocoPolicy on the pendulum (KIND_PENDULUM)
+    # ---- MujocoPolicy on the pendulum (KIND_PENDULUM) and on the hard maze (KIND_MJMAZE): dne_<name>_* with observations `obs` wide
+    def _mujoco_set_ob_stat(self, name, obs, mean, std):
+        mean = _arr(mean, np.float32).reshape(obs); std = _arr(std, np.float32).reshape(obs)
+        self._ck(getattr(self.lib, "dne_%s_set_ob_stat" % name)(self.h, _ptr(mean, C.c_float), _ptr(std, C.c_float)))
+
+    def _mujoco_set_rollout_options(self, name, n, ac_noise_std, ac_off, stat_flag):
+        ac_off = None if ac_off is None else _arr(ac_off, np.int64).reshape(-1)
+        stat_flag = None if stat_flag is None else _arr(stat_flag, np.uint8).reshape(-1)
+        for a in (ac_off, stat_flag):
+            if a is not None and a.size != int(n):
+                raise DneError("%s_set_rollout_options: %d members, %d values" % (name, int(n), a.size))
+        self._ck(getattr(self.lib, "dne_%s_set_rollout_options" % name)(self.h, int(n), C.c_float(ac_noise_std), _ptr(ac_off, C.c_int64),
+                                                                        _ptr(stat_flag, C.c_uint8)))
+
+    def _mujoco_ob_stats(self, name, obs, n):
+        s = np.empty((int(n), obs), np.float64); q = np.empty((int(n), obs), np.float64); c = np.empty(int(n), np.int32)
+        self._ck(getattr(self.lib, "dne_%s_ob_stats" % name)(self.h, int(n), _ptr(s, C.c_double), _ptr(q, C.c_double), _ptr(c, C.c_int32)))
+        return s, q, c
+
+    def _debug_trace(self, name, member, tslimit, cap, width, dtype, init=()):
+        """dne_<name>_debug_trace: [steps][width] rows of `dtype`; init: the kind's leading arguments (an initial state or None), if it has any"""
+        out = np.zeros((min(int(tslimit), cap), width), dtype)
+        steps = C.c_int32(0)
+        ct = C.c_double if dtype == np.float64 else C.c_float
+        self._ck(getattr(self.lib, "dne_%s_debug_trace" % name)(self.h, int(member), int(tslimit), *init, _ptr(out, ct), C.byref(steps)))
+        return out[:steps.value]
+
     def pendulum_set_ob_stat(self, mean, std):
-        mean = _arr(mean, np.float32).reshape(3); std = _arr(std, np.float32).reshape(3)
-        self._ck(self.lib.dne_pendulum_set_ob_stat(self.h, _ptr(mean, C.c_float), _ptr(std, C.c_float)))
+        self._mujoco_set_ob_stat("pendulum", PENDULUM_OBS, mean, std)
 
     def pendulum_set_rollout_options(self, n, ac_noise_std=0.0, ac_off=None, stat_flag=None):
         """for the next evaluation only (it must run n members): ac_off int64 [n] -- where each member's 200 action-noise values start in the
         noise table, < 0 for none -- and stat_flag uint8 [n] -- who accumulates the observations it acts on"""
-        if ac_off is not None:
-            ac_off = _arr(ac_off, np.int64).reshape(-1)
-        if stat_flag is not None:
-            stat_flag = _arr(stat_flag, np.uint8).reshape(-1)
-        for a in (ac_off, stat_flag):
-            if a is not None and a.size != int(n):
-                raise DneError("pendulum_set_rollout_options: %d members, %d values" % (int(n), a.size))
-        self._ck(self.lib.dne_pendulum_set_rollout_options(self.h, int(n), C.c_float(ac_noise_std), _ptr(ac_off, C.c_int64), _ptr(stat_flag, C.c_uint8)))
+        self._mujoco_set_rollout_options("pendulum", n, ac_noise_std, ac_off, stat_flag)
 
     def pendulum_ob_stats(self, n):
         """(sum float64 [n][3], sumsq float64 [n][3], count int32 [n]) of the last evaluation's first n members"""
-        s = np.empty((int(n), 3), np.float64); q = np.empty((int(n), 3), np.float64); c = np.empty(int(n), np.int32)
-        self._ck(self.lib.dne_pendulum_ob_stats(self.h, int(n), _ptr(s, C.c_double), _ptr(q, C.c_double), _ptr(c, C.c_int32)))
-        return s, q, c
+        return self._mujoco_ob_stats("pendulum", PENDULUM_OBS, n)
 
     def pendulum_final_state(self, n):
         """final (theta, theta_dot) of the last evaluation's first n members, float64 [n][2]"""
@@ -898,11 +914,8 @@ class Engine:
 
     def pendulum_debug_trace(self, member, tslimit=PENDULUM_STEPS, init=None):
         """the kernel once more for one current member, every step written out: float64 [steps][8] as pendulum_rollout_host's trace"""
-        out = np.zeros((min(int(tslimit), PENDULUM_STEPS), PENDULUM_TRACE_W), np.float64)
-        steps = C.c_int32(0)
         init = None if init is None else _arr(init, np.float64).reshape(2)
-        self._ck(self.lib.dne_pendulum_debug_trace(self.h, int(member), int(tslimit), _ptr(init, C.c_double), _ptr(out, C.c_double), C.byref(steps)))
-        return out[:steps.value]
+        return self._debug_trace("pendulum", member, tslimit, PENDULUM_STEPS, PENDULUM_TRACE_W, np.float64, (_ptr(init, C.c_double),))
 
     def pendulum_debug_math(self, fn, x, a=0.0, b=1.0):
         """pendulum_math_host on the device"""
@@ -912,35 +925,22 @@ class Engine:
                                                   _ptr(out, C.c_double)))
         return out
 
-    # ---- MujocoPolicy on the hard maze (KIND_MJMAZE); the walls, the final positions and the archive are the maze_* methods
+    # (KIND_MJMAZE: the walls, the final positions and the archive are the maze_* methods)
     def mjmaze_set_ob_stat(self, mean, std):
-        mean = _arr(mean, np.float32).reshape(MJMAZE_OBS); std = _arr(std, np.float32).reshape(MJMAZE_OBS)
-        self._ck(self.lib.dne_mjmaze_set_ob_stat(self.h, _ptr(mean, C.c_float), _ptr(std, C.c_float)))
+        self._mujoco_set_ob_stat("mjmaze", MJMAZE_OBS, mean, std)
 
     def mjmaze_set_rollout_options(self, n, ac_noise_std=0.0, ac_off=None, stat_flag=None):
         """for the next evaluation only (it must run n members): ac_off int64 [n] -- where each member's 800 action-noise values start in the
         noise table, < 0 for none -- and stat_flag uint8 [n] -- who accumulates the observations it acts on"""
-        if ac_off is not None:
-            ac_off = _arr(ac_off, np.int64).reshape(-1)
-        if stat_flag is not None:
-            stat_flag = _arr(stat_flag, np.uint8).reshape(-1)
-        for a in (ac_off, stat_flag):
-            if a is not None and a.size != int(n):
-                raise DneError("mjmaze_set_rollout_options: %d members, %d values" % (int(n), a.size))
-        self._ck(self.lib.dne_mjmaze_set_rollout_options(self.h, int(n), C.c_float(ac_noise_std), _ptr(ac_off, C.c_int64), _ptr(stat_flag, C.c_uint8)))
+        self._mujoco_set_rollout_options("mjmaze", n, ac_noise_std, ac_off, stat_flag)
 
     def mjmaze_ob_stats(self, n):
         """(sum float64 [n][11], sumsq float64 [n][11], count int32 [n]) of the last evaluation's first n members"""
-        s = np.empty((int(n), MJMAZE_OBS), np.float64); q = np.empty((int(n), MJMAZE_OBS), np.float64); c = np.empty(int(n), np.int32)
-        self._ck(self.lib.dne_mjmaze_ob_stats(self.h, int(n), _ptr(s, C.c_double), _ptr(q, C.c_double), _ptr(c, C.c_int32)))
-        return s, q, c
+        return self._mujoco_ob_stats("mjmaze", MJMAZE_OBS, n)
 
     def mjmaze_debug_trace(self, member, tslimit=MJMAZE_STEPS):
         """the kernel once more for one current member, every step written out: float32 [steps][20] as mjmaze_rollout_host's trace"""
-        out = np.zeros((min(int(tslimit), MJMAZE_STEPS), MJMAZE_TRACE_W), np.float32)
-        steps = C.c_int32(0)
-        self._ck(self.lib.dne_mjmaze_debug_trace(self.h, int(member), int(tslimit), _ptr(out, C.c_float), C.byref(steps)))
-        return out[:steps.value]
+        return self._debug_trace("mjmaze", member, tslimit, MJMAZE_STEPS, MJMAZE_TRACE_W, np.float32)
 
     # ---- gym.CartPole-v1 (KIND_CARTPOLE)
     def cartpole_final_state(self, n):
@@ -952,11 +952,8 @@ class Engine:
     def cartpole_debug_trace(self, member, tslimit=CARTPOLE_STEPS, init=None):
         """the kernel once more for one current member, every step written out: float64 [steps][8] as cartpole_rollout_host's trace, cut at the
         episode's length.  init [4]: the initial state; None: the reset of the seed that member had in the last evaluation."""
-        out = np.zeros((min(int(tslimit), CARTPOLE_STEPS), CARTPOLE_TRACE_W), np.float64)
         init = None if init is None else _arr(init, np.float64).reshape(4)
-        steps = C.c_int32(0)
-        self._ck(self.lib.dne_cartpole_debug_trace(self.h, int(member), int(tslimit), _ptr(init, C.c_double), _ptr(out, C.c_double), C.byref(steps)))
-        return out[:steps.value]
+        return self._debug_trace("cartpole", member, tslimit, CARTPOLE_STEPS, CARTPOLE_TRACE_W, np.float64, (_ptr(init, C.c_double),))
 
     # ---- the maze, the cart-pole and the pendulum one step at a time (csrc/step_env.h): a batch of max_members environments apart from evaluations
     def _stepenv_idx(self, indices, n=None):

@@ -527,3 +527,14 @@ def test_math_probe_pins_and_refusals():
             _lib.maze_math_host(fn, [0.0])
     with pytest.raises(_lib.DneError, match="n >= 1"):
         _lib.maze_math_host(0, [])
+
+
+def test_wall_count_refusals_word_for_word():
+    """the whole text of what every maze entry point says of a wall count outside 1..64 (dne_maze_set_walls says the same on the device)"""
+    from dne_hip import _lib
+    header, _ = M.fixture_maze()
+    theta = np.zeros((1, 498), np.float32)
+    for n in (0, 65):
+        with pytest.raises(_lib.DneError) as ei:
+            _lib.maze_rollout_host(theta, header, np.zeros((n, 4), np.float32), tslimit=3)
+        assert str(ei.value) == "maze: %d walls, the kernel and the host function take 1..64" % n

@@ -251,3 +251,27 @@ def test_header_under_sanitizers_in_a_stand_alone_program(sanitizer_program):
     assert out.returncode == 0, out.stderr[-2000:]
     # 3 widths x 4 output counts x 2 nonlinearities (2 of 400 steps, 22 of 23); 5 facts each + 4; outside the contract 6 fills x 3 deviations x 2
     assert out.stdout.split() == ["ok", "24", "1306", "facts", "124", "wild", "36", "900"], out.stdout
+
+
+def test_host_refusals_word_for_word():
+    """the whole text of what dne_mjmaze_rollout_host / dne_mjmaze_forward_host refuse: a shape the header does not build, an action-noise offset
+    whose 800 values end past the table; a maze without walls wins over both"""
+    from dne_hip import _lib
+    header, lines = S.fixture_maze()
+    th = np.zeros((2, _lib.mjmaze_num_params(64, 4)), np.float32)
+    shape = "dne_mjmaze_%s_host: hidden width 64, 4 outputs, action mode 0, nonlinearity 0 is not a shape csrc/mjmaze.h builds"
+    with pytest.raises(_lib.DneError) as ei:
+        _lib.mjmaze_rollout_host(th, header, lines, n_out=4, ac_mode='continuous', **KW64)
+    assert str(ei.value) == shape % "rollout"
+    with pytest.raises(_lib.DneError) as ei:
+        _lib.mjmaze_forward_host(th, np.zeros((2, 11), np.float32), n_out=4, ac_mode='continuous', **KW64)
+    assert str(ei.value) == shape % "forward"
+    with pytest.raises(_lib.DneError) as ei:
+        _lib.mjmaze_rollout_host(th, header, lines, n_out=4, ac_mode='uniform', table=np.zeros(1000, np.float32), ac_off=[-1, 201], **KW64)
+    assert str(ei.value) == "dne_mjmaze_rollout_host: member 1 reads its action noise from offset 201, past the noise table's 1000 values"
+    with pytest.raises(_lib.DneError) as ei:
+        _lib.mjmaze_rollout_host(th, header, lines, n_out=4, ac_mode='uniform', tslimit=0, **KW64)
+    assert str(ei.value) == "dne_mjmaze_rollout_host: bad arguments"
+    with pytest.raises(_lib.DneError) as ei:
+        _lib.mjmaze_rollout_host(th, header, lines[:0], n_out=4, ac_mode='continuous', table=np.zeros(1000, np.float32), ac_off=[-1, 201], **KW64)
+    assert str(ei.value) == "maze: 0 walls, the kernel and the host function take 1..64"

@@ -430,3 +430,23 @@ def test_header_under_sanitizers_in_a_stand_alone_program(sanitizer_program):
     assert out.returncode == 0, out.stderr[-2000:]
     # 3 widths x 4 output counts x 2 nonlinearities (8 of 200 steps, 16 of 37); 3 facts each + 4; outside the contract 6 fills x 3 deviations x 2
     assert out.stdout.split() == ["ok", "24", "2192", "facts", "76", "wild", "36", "900"], out.stdout
+
+
+def test_host_refusals_word_for_word():
+    """the whole text of what dne_pendulum_rollout_host / dne_pendulum_forward_host refuse: a shape the header does not build, an action-noise
+    offset whose 200 values end past the table"""
+    from dne_hip import _lib
+    th = np.zeros((2, _lib.pendulum_num_params(64, 4)), np.float32)
+    shape = "dne_pendulum_%s_host: hidden width 64, 4 outputs, action mode 0, nonlinearity 0 is not a shape csrc/pendulum.h builds"
+    with pytest.raises(_lib.DneError) as ei:
+        _lib.pendulum_rollout_host(th, [1, 2], 64, MEAN, STD, n_out=4, ac_mode='continuous')
+    assert str(ei.value) == shape % "rollout"
+    with pytest.raises(_lib.DneError) as ei:
+        _lib.pendulum_forward_host(th, np.zeros((2, 3), np.float32), 64, MEAN, STD, n_out=4, ac_mode='continuous')
+    assert str(ei.value) == shape % "forward"
+    with pytest.raises(_lib.DneError) as ei:
+        _lib.pendulum_rollout_host(th, [1, 2], 64, MEAN, STD, n_out=4, ac_mode='uniform', table=np.zeros(1000, np.float32), ac_off=[-1, 801])
+    assert str(ei.value) == "dne_pendulum_rollout_host: member 1 reads its action noise from offset 801, past the noise table's 1000 values"
+    with pytest.raises(_lib.DneError) as ei:
+        _lib.pendulum_rollout_host(th, [1, 2], 64, MEAN, STD, n_out=4, ac_mode='uniform', tslimit=0)
+    assert str(ei.value) == "dne_pendulum_rollout_host: bad arguments"
