@@ -36,6 +36,7 @@
 #include "pendulum.h"
 #include "mjmaze.h"
 #include "step_env.h"
+#include "dense.h"
 
 using namespace dne;
 
@@ -54,6 +55,7 @@ static thread_local std::string g_create_error;
         if ((h)->cartpole) return (h)->fail("%s is not available on a DNE_KIND_CARTPOLE engine (kind %d): the cart-pole has no Atari frames, reference batch, genomes or byte BCs", call, DNE_KIND_CARTPOLE); \
         if ((h)->pendulum) return (h)->fail("%s is not available on a DNE_KIND_PENDULUM engine (kind %d): the pendulum has no Atari frames, reference batch, genomes or byte BCs", call, DNE_KIND_PENDULUM); \
         if ((h)->mjmaze) return (h)->fail("%s is not available on a DNE_KIND_MJMAZE engine (kind %d): MujocoPolicy on the hard maze has no Atari frames, reference batch, genomes or byte BCs", call, DNE_KIND_MJMAZE); \
+        if ((h)->dense) return (h)->fail("%s is not available on a DNE_KIND_DENSE engine (kind %d): a dense policy on a step environment has no Atari frames, reference batch, genomes or byte BCs", call, DNE_KIND_DENSE); \
     } while (0)
 
 // ------------------------------------------------------------------------------- env kernels
@@ -691,7 +693,12 @@ struct dne_handle {
     // positions and archive (maze_*, mzn_*); mj_opt holds its own 11 means and deviations
     bool mjmaze = false;
     mjmaze::Options mj_opt{};
-    bool episodic() const { return maze || cartpole || pendulum || mjmaze; }   // a whole episode per member in one launch: what dne_es_eval and the record calls accept beside the Atari kinds
+    // DNE_KIND_DENSE: a dense policy of the shape dn_shape on the step environment dn_shape.env, k_dense_run (csrc/dense.h)
+    bool dense = false;
+    dense::Shape dn_shape{};
+    double *dn_state = nullptr; int dn_last_n = 0;   // final state records [member][S] of the last evaluation, and how many members that was
+    int32_t *se_io_mem = nullptr; float *se_io_out = nullptr;   // dne_stepenv_act / _run: the member of each listed environment; the raw outputs
+    bool episodic() const { return maze || cartpole || pendulum || mjmaze || dense; }   // a whole episode per member in one launch: what dne_es_eval and the record calls accept beside the Atari kinds
     bool large = false;              // DNE_KIND_GA_LARGE: y1 [441][32], y2 / y3 [121][64] (conv3 output), y3t = the 512 fc outputs
     float *y1r[2] = {nullptr, nullptr}, *y2r[2] = {nullptr, nullptr}, *y3pr[2] = {nullptr, nullptr};   // reference pass scratch, two ways
     float *fr1[2] = {nullptr, nullptr}, *fr2[2] = {nullptr, nullptr};   // per-frame batch-norm moments of conv1 / conv2 ([rows][2][C])
@@ -877,7 +884,7 @@ static void make_layout(int kind, int nact, Layout *L) {
     memset(L, 0, sizeof(*L));
     L->kind = kind; L->nact = nact;
     auto take = [&](int n) { int r = o; o += n; return r; };
-    if (kind == DNE_KIND_MAZE || kind == DNE_KIND_CARTPOLE || kind == DNE_KIND_PENDULUM || kind == DNE_KIND_MJMAZE) {   // (DNE_KIND_PENDULUM, DNE_KIND_MJMAZE: P depends on the hidden width, dne_create sets it) SimpleClassifier (models/simple.py:29-35): csrc/maze.h and csrc/cartpole.h hold its offsets
+    if (kind == DNE_KIND_MAZE || kind == DNE_KIND_CARTPOLE || kind == DNE_KIND_PENDULUM || kind == DNE_KIND_MJMAZE || kind == DNE_KIND_DENSE) {   // (DNE_KIND_PENDULUM, DNE_KIND_MJMAZE, DNE_KIND_DENSE: P depends on the hidden width, dne_create sets it) SimpleClassifier (models/simple.py:29-35): csrc/maze.h and csrc/cartpole.h hold its offsets
         L->c1w = L->c1b = L->c2w = L->c2b = L->c3w = L->c3b = L->fcw = L->fcb = L->ow = L->ob = -1;
         L->bn1b = L->bn1g = L->bn2b = L->bn2g = L->bn3b = L->bn3g = -1;
         o = kind == DNE_KIND_MAZE ? maze::NPARAMS : kind == DNE_KIND_CARTPOLE ? cartpole::NPARAMS : 0;
@@ -983,11 +990,41 @@ struct DevBuf {
     operator T *() const { return p; }
 };
 
+// a refused shape of DNE_KIND_DENSE by name (code: dense::make_shape's answer); 0 for a shape that is built
+static int dense_shape_error(const char *who, int code, int env, int n_hidden, const int32_t *widths, int n_widths, int nonlin, int n_out) {
+    const std::string w(who);
+    if (code == dense::SHAPE_OK) return 0;
+    if (code == dense::SHAPE_ENV)
+        g_create_error = w + " runs on the environments DNE_KIND_MAZE (4), DNE_KIND_CARTPOLE (5) and DNE_KIND_PENDULUM (6); environment " + std::to_string(env) + " is refused";
+    else if (code == dense::SHAPE_LAYERS)
+        g_create_error = w + " is built for 0.." + std::to_string(dense::MAX_HIDDEN) + " hidden layers; " + std::to_string(n_hidden) + " hidden layers are refused";
+    else if (code == dense::SHAPE_WIDTH) {
+        int i = 0;
+        while (i < n_hidden - 1 && widths[i] >= 1 && widths[i] <= dense::MAX_WIDTH) i++;
+        g_create_error = w + " is built for hidden widths 1.." + std::to_string(dense::MAX_WIDTH) + "; width " + std::to_string(widths[i]) + " of hidden layer " + std::to_string(i) + " is refused";
+    } else if (code == dense::SHAPE_TAIL) {
+        int i = n_hidden;
+        while (i < n_widths - 1 && widths[i] == 0) i++;
+        g_create_error = w + ": " + std::to_string(n_hidden) + " hidden layers, and a width of " + std::to_string(widths[i]) + " behind them (entry " + std::to_string(i) + "); unused widths are 0";
+    } else if (code == dense::SHAPE_OUT)
+        g_create_error = w + " has " + std::to_string(dense::env_outputs(env)) + " outputs on environment " + std::to_string(env) + " (the maze and the cart-pole 2, the pendulum 1), n_actions " + std::to_string(n_out) + " is refused";
+    else
+        g_create_error = w + " has nonlinearities 0 (tanh) and 1 (relu); nonlinearity " + std::to_string(nonlin) + " is refused";
+    return -1;
+}
+
+extern "C" int dne_dense_num_params(int env_kind, int n_hidden, const int32_t *widths, int n_out) {
+    dense::Shape sh;
+    if (n_hidden > 0 && !widths) return -1;
+    return dense::make_shape(env_kind, n_hidden, widths, n_hidden < 0 ? 0 : n_hidden, dense::NL_RELU, n_out, &sh) == dense::SHAPE_OK ? sh.P : -1;
+}
+
 extern "C" int dne_num_params(int kind, int nact) {
     if (kind == DNE_KIND_MAZE && nact != maze::ACT) return -1;   // the maze policy has two raw outputs, nothing else
     if (kind == DNE_KIND_CARTPOLE && nact != cartpole::ACT) return -1;   // CartPole-v1 has two actions
     if (kind == DNE_KIND_PENDULUM) return -1;   // P depends on the hidden width: dne_pendulum_num_params
     if (kind == DNE_KIND_MJMAZE) return -1;     // likewise: dne_mjmaze_num_params
+    if (kind == DNE_KIND_DENSE) return -1;      // P depends on the whole shape: dne_dense_num_params
     Layout L;
     make_layout(kind, nact, &L);
     return L.P;
@@ -1012,6 +1049,10 @@ extern "C" int dne_debug_plan(int kind, int n_actions, const dne_plan_facts *fac
     }
     if (kind == DNE_KIND_MJMAZE) {
         g_create_error = "dne_debug_plan: a DNE_KIND_MJMAZE engine (kind 7) has no lock-step windows, an evaluation is one k_mjmaze_rollout launch";
+        return -1;
+    }
+    if (kind == DNE_KIND_DENSE) {
+        g_create_error = "dne_debug_plan: a DNE_KIND_DENSE engine (kind 8) has no lock-step windows, an evaluation is one k_dense_run launch";
         return -1;
     }
     const Knobs k = engine_knobs(kind, n_actions);
@@ -1043,6 +1084,10 @@ extern "C" int dne_debug_plan_act(int kind, int n_actions, const dne_plan_facts 
     }
     if (kind == DNE_KIND_MJMAZE) {
         g_create_error = "dne_debug_plan_act: a DNE_KIND_MJMAZE engine (kind 7) has no dne_act";
+        return -1;
+    }
+    if (kind == DNE_KIND_DENSE) {
+        g_create_error = "dne_debug_plan_act: a DNE_KIND_DENSE engine (kind 8) has no dne_act (dne_stepenv_act is its forward pass)";
         return -1;
     }
     if (n < 1) {
@@ -1102,9 +1147,9 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         g_create_error = "dne_create: no HIP device visible (this engine has no CPU fallback)";
         return -1;
     }
-    if (cfg->max_members <= 0 || (cfg->n_actions <= 1 && !(cfg->policy_kind == DNE_KIND_PENDULUM && cfg->n_actions == 1)) ||
+    if (cfg->max_members <= 0 || (cfg->n_actions <= 1 && !(cfg->policy_kind == DNE_KIND_PENDULUM && cfg->n_actions == 1) && cfg->policy_kind != DNE_KIND_DENSE) ||
         (!es_like(cfg->policy_kind) && cfg->policy_kind != DNE_KIND_GA && cfg->policy_kind != DNE_KIND_GA_LARGE && cfg->policy_kind != DNE_KIND_MAZE &&
-         cfg->policy_kind != DNE_KIND_CARTPOLE && cfg->policy_kind != DNE_KIND_PENDULUM && cfg->policy_kind != DNE_KIND_MJMAZE)) {
+         cfg->policy_kind != DNE_KIND_CARTPOLE && cfg->policy_kind != DNE_KIND_PENDULUM && cfg->policy_kind != DNE_KIND_MJMAZE && cfg->policy_kind != DNE_KIND_DENSE)) {
         g_create_error = "dne_create: bad config";
         return -1;
     }
@@ -1182,6 +1227,16 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
             return -1;
         }
     }
+    dense::Shape dn_shape{};
+    if (cfg->policy_kind == DNE_KIND_DENSE) {   // the shape: reserved[0] the environment, [1] hidden layers, [2] nonlinearity, [3..5] the widths; n_actions = the outputs
+        if (dense_shape_error("dne_create: DNE_KIND_DENSE", dense::make_shape(cfg->reserved[0], cfg->reserved[1], cfg->reserved + 3, 3, cfg->reserved[2], cfg->n_actions, &dn_shape),
+                              cfg->reserved[0], cfg->reserved[1], cfg->reserved + 3, 3, cfg->reserved[2], cfg->n_actions)) return -1;
+        if (cfg->bc_final_only || cfg->record_bc) {
+            g_create_error = "dne_create: record_bc / bc_final_only are not available on a DNE_KIND_DENSE engine (kind 8): it records no behaviour; "
+                             "dne_dense_final_state has the final state of every member";
+            return -1;
+        }
+    }
     dne_handle *h = new dne_handle();
     h->cfg = *cfg;
     auto bail = [&](int) { g_create_error = h->err; delete h; return -1; };
@@ -1202,13 +1257,15 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         env_int("DNE_STAGED_COPY", 0, 1, &sc);
         h->staged_copies = sc != 0;
     }
-    if (cfg->policy_kind == DNE_KIND_MAZE || cfg->policy_kind == DNE_KIND_CARTPOLE || cfg->policy_kind == DNE_KIND_PENDULUM || cfg->policy_kind == DNE_KIND_MJMAZE) {
+    if (cfg->policy_kind == DNE_KIND_MAZE || cfg->policy_kind == DNE_KIND_CARTPOLE || cfg->policy_kind == DNE_KIND_PENDULUM || cfg->policy_kind == DNE_KIND_MJMAZE ||
+        cfg->policy_kind == DNE_KIND_DENSE) {
         // theta slots, member descriptors and accumulators, the walls (the cart-pole: seeds and final states), the reduce and optimizer
         // buffers: no frame, activation or ring buffer
         h->maze = cfg->policy_kind == DNE_KIND_MAZE;
         h->cartpole = cfg->policy_kind == DNE_KIND_CARTPOLE;
         h->pendulum = cfg->policy_kind == DNE_KIND_PENDULUM;
         h->mjmaze = cfg->policy_kind == DNE_KIND_MJMAZE;
+        h->dense = cfg->policy_kind == DNE_KIND_DENSE;
         const bool mujoco = h->pendulum || h->mjmaze;
         make_layout(cfg->policy_kind, cfg->n_actions, &h->L);
         if (mujoco) {
@@ -1216,6 +1273,7 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
             with_mujoco_options(h, [&](auto &o) { fill_options(o, cfg->n_actions, cfg->reserved[1], 0.0f, nullptr, nullptr); });
             h->L.P = h->mjmaze ? mjmaze::offsets(h->pd_hidden, cfg->n_actions).P : pendulum::offsets(h->pd_hidden, cfg->n_actions).P;
         }
+        if (h->dense) { h->dn_shape = dn_shape; h->L.P = dn_shape.P; }
         h->M = cfg->max_members;
         h->base_stride = ((size_t)h->L.P + 63) / 64 * 64;
         const size_t M = h->M;
@@ -1228,7 +1286,13 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         CH(hipMemset(h->m_slot, 0, M * sizeof(int32_t))); CH(hipMemset(h->m_off, 0, M * sizeof(int64_t))); CH(hipMemset(h->m_scale, 0, M * sizeof(float)));
         CH(h->alloc(&h->ret, M, "ret")); CH(h->alloc(&h->sign, M, "sign")); CH(h->alloc(&h->len, M, "len"));
         CH(hipMemset(h->ret, 0, M * sizeof(float))); CH(hipMemset(h->sign, 0, M * sizeof(float))); CH(hipMemset(h->len, 0, M * sizeof(int32_t)));
-        if (h->maze || h->mjmaze) {
+        if (h->dense) {   // the final state records, the seeds, and the walls when the environment is the maze
+            stepenv::Dims d{};
+            stepenv::dims(dn_shape.env, &d);
+            CH(h->alloc(&h->dn_state, (size_t)d.state * M, "dense_state")); CH(h->alloc(&h->seeds, M, "seeds"));
+            CH(hipMemset(h->dn_state, 0, (size_t)d.state * M * sizeof(double))); CH(hipMemset(h->seeds, 0, M * sizeof(uint32_t)));
+            if (dn_shape.env == DNE_KIND_MAZE) CH(h->alloc(&h->maze_walls, maze::MAX_WALLS * 4, "maze_walls"));
+        } else if (h->maze || h->mjmaze) {
             CH(h->alloc(&h->maze_xy, 2 * M, "maze_xy")); CH(h->alloc(&h->maze_walls, maze::MAX_WALLS * 4, "maze_walls"));
             CH(hipMemset(h->maze_xy, 0, 2 * M * sizeof(float)));
         } else {   // the kinds that reset from a seed: the final state's doubles (the cart-pole: 4, the pendulum: 2) and the seeds
@@ -1255,7 +1319,7 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
         CH(h->alloc(&h->scratch_f, h->scratch_cap, "scratch_f")); CH(h->alloc(&h->scratch_i, h->scratch_cap, "scratch_i"));
         CH(hipEventCreate(&h->ev_a)); CH(hipEventCreate(&h->ev_b));
         CH(hipDeviceSynchronize());
-        h->trace("engine created: kind %d (%s), %d members, %zu device buffers", cfg->policy_kind, h->maze ? "hard maze" : h->cartpole ? "cart-pole" : h->pendulum ? "pendulum" : "MujocoPolicy on the hard maze", h->M, h->blocks.size());
+        h->trace("engine created: kind %d (%s), %d members, %zu device buffers", cfg->policy_kind, h->maze ? "hard maze" : h->cartpole ? "cart-pole" : h->pendulum ? "pendulum" : h->dense ? "dense policy on a step environment" : "MujocoPolicy on the hard maze", h->M, h->blocks.size());
         *out = h;
         return 0;
     }
@@ -2404,7 +2468,7 @@ static int needs_maze_env(dne_handle *h, const char *call) {
 
 extern "C" int dne_maze_set_walls(dne_handle *h, const float *header8, const float *lines, int n) {
     DeviceGuard dg(h);
-    if (needs_maze_env(h, "dne_maze_set_walls")) return -1;
+    if (!(h->dense && h->dn_shape.env == DNE_KIND_MAZE) && needs_maze_env(h, "dne_maze_set_walls")) return -1;   // (a dense policy on the maze shares the walls)
     if (maze_check(&h->err, header8, lines, n)) return -1;
     HCHECK(h, hipStreamSynchronize(h->stream));
     HCHECK(h, hipMemcpy(h->maze_walls, lines, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice));
@@ -3307,9 +3371,11 @@ extern "C" int dne_stepenv_dims(int kind, int *obs, int *act, int *state, int *a
     return 0;
 }
 
+// the environment a handle steps: its kind, or what a DNE_KIND_DENSE engine was created on
+static int se_env(const dne_handle *h) { return h->dense ? h->dn_shape.env : h->L.kind; }
 static stepenv::Dims se_dims(const dne_handle *h) {
     stepenv::Dims d{};
-    stepenv::dims(h->L.kind, &d);
+    stepenv::dims(se_env(h), &d);
     return d;
 }
 
@@ -3329,6 +3395,7 @@ static int se_alloc(dne_handle *h) {
     HCHECK(h, h->alloc(&h->se_io_seeds, M, "stepenv_io_seeds")); HCHECK(h, h->alloc(&h->se_io_act, M * stepenv::MAX_ACT, "stepenv_io_act"));
     HCHECK(h, h->alloc(&h->se_io_rew, M, "stepenv_io_rew")); HCHECK(h, h->alloc(&h->se_io_obs, M * d.obs, "stepenv_io_obs"));
     HCHECK(h, h->alloc(&h->se_io_done, M, "stepenv_io_done")); HCHECK(h, h->alloc(&h->se_io_state, M * d.state, "stepenv_io_state"));
+    if (h->dense) { HCHECK(h, h->alloc(&h->se_io_mem, M, "stepenv_io_mem")); HCHECK(h, h->alloc(&h->se_io_out, M * dense::MAX_OUT, "stepenv_io_out")); }
     HCHECK(h, hipEventCreate(&h->se_ev_a)); HCHECK(h, hipEventCreate(&h->se_ev_b));
     h->se_was_reset.assign(M, 0);
     h->se_ready = true;
@@ -3340,7 +3407,7 @@ static int se_alloc(dne_handle *h) {
 static int se_check(dne_handle *h, const char *call, int n, const int32_t *indices, bool reads, std::vector<int32_t> &idx) {
     if (!h->episodic() || h->mjmaze)   // (DNE_KIND_MJMAZE: the maze one step at a time is DNE_KIND_MAZE's)
         return h->fail("%s needs a DNE_KIND_MAZE, DNE_KIND_CARTPOLE or DNE_KIND_PENDULUM engine (this one: kind %d)", call, h->L.kind);
-    if (h->maze && h->maze_nw < 1) return h->fail("%s: no maze loaded (dne_maze_set_walls comes before the environments)", call);
+    if (se_env(h) == DNE_KIND_MAZE && h->maze_nw < 1) return h->fail("%s: no maze loaded (dne_maze_set_walls comes before the environments)", call);
     if (n < 1 || n > h->M) return h->fail("%s: %d environments asked for, the engine holds 1..%d", call, n, h->M);
     idx.resize(n);
     std::vector<uint8_t> seen(h->M, 0);
@@ -3364,25 +3431,26 @@ static int se_reset(dne_handle *h, const char *call, int n, const int32_t *indic
     std::vector<int32_t> idx;
     if (se_check(h, call, n, indices, false, idx)) return -1;
     const stepenv::Dims d = se_dims(h);
+    const bool is_maze = se_env(h) == DNE_KIND_MAZE, is_cartpole = se_env(h) == DNE_KIND_CARTPOLE;
     const int limit = stepenv::step_limit(max_steps, d.own_limit);
     if (set) {
         if (!state || !steps) return h->fail("%s: state or steps missing", call);
         for (int i = 0; i < n; i++)
             if (steps[i] < 0 || steps[i] >= limit)
                 return h->fail("%s: %d steps taken at position %d, an environment under a limit of %d has taken 0..%d", call, steps[i], i, limit, limit - 1);
-    } else if (!h->maze && !seeds)
-        return h->fail("%s: a %s engine resets every environment from its seed, seeds is NULL", call, episodic_kind_name(h->L.kind));
+    } else if (!is_maze && !seeds)
+        return h->fail("%s: a %s engine resets every environment from its seed, seeds is NULL", call, episodic_kind_name(se_env(h)));
     if (se_alloc(h)) return -1;
     HCHECK(h, hipMemcpyAsync(h->se_io_idx, idx.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     if (set) {
         HCHECK(h, hipMemcpyAsync(h->se_io_state, state, (size_t)n * d.state * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HCHECK(h, hipMemcpyAsync(h->se_io_steps, steps, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    } else if (!h->maze)
+    } else if (!is_maze)
         HCHECK(h, hipMemcpyAsync(h->se_io_seeds, seeds, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     const double *init = set ? h->se_io_state : nullptr;
-    if (h->maze)
+    if (is_maze)
         hipLaunchKernelGGL(stepenv::k_stepenv_reset_maze, dim3((n + 3) / 4), dim3(64), 0, h->stream, h->se, se_maze_ctx(h), h->se_io_idx, n, init, h->se_io_steps, limit);
-    else if (h->cartpole)
+    else if (is_cartpole)
         hipLaunchKernelGGL(stepenv::k_stepenv_reset_cartpole, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->se, h->se_io_idx, n, h->se_io_seeds, init, h->se_io_steps, limit);
     else
         hipLaunchKernelGGL(stepenv::k_stepenv_reset_pendulum, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->se, h->se_io_idx, n, h->se_io_seeds, init, h->se_io_steps, limit);
@@ -3406,11 +3474,12 @@ static int se_step(dne_handle *h, const char *call, bool int_actions, int n, con
     std::vector<int32_t> idx;
     if (se_check(h, call, n, indices, true, idx)) return -1;
     const stepenv::Dims d = se_dims(h);
+    const bool is_maze = se_env(h) == DNE_KIND_MAZE, is_cartpole = se_env(h) == DNE_KIND_CARTPOLE;
     if ((d.act_is_int != 0) != int_actions)
-        return h->fail("%s: a %s engine takes %s actions (dne_stepenv_step_%s)", call, episodic_kind_name(h->L.kind), d.act_is_int ? "int32" : "float",
+        return h->fail("%s: a %s engine takes %s actions (dne_stepenv_step_%s)", call, episodic_kind_name(se_env(h)), d.act_is_int ? "int32" : "float",
                        d.act_is_int ? "i32" : "f32");
     if (!actions || !reward || !done) return h->fail("%s: actions, reward or done missing", call);
-    if (h->cartpole)
+    if (is_cartpole)
         for (int i = 0; i < n; i++) {
             const int32_t a = ((const int32_t *)actions)[i];
             if (a != 0 && a != 1) return h->fail("%s: action %d at position %d, CartPole-v1 has actions 0 and 1", call, a, i);
@@ -3418,9 +3487,9 @@ static int se_step(dne_handle *h, const char *call, bool int_actions, int n, con
     HCHECK(h, hipMemcpyAsync(h->se_io_idx, idx.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HCHECK(h, hipMemcpyAsync(h->se_io_act, actions, (size_t)n * d.act * sizeof(float), hipMemcpyHostToDevice, h->stream));   // (an int32 is a float's size)
     HCHECK(h, hipEventRecord(h->se_ev_a, h->stream));
-    if (h->maze)
+    if (is_maze)
         hipLaunchKernelGGL(stepenv::k_stepenv_step_maze, dim3((n + 3) / 4), dim3(64), 0, h->stream, h->se, se_maze_ctx(h), h->se_io_idx, n, h->se_io_act, h->se_io_rew, h->se_io_done);
-    else if (h->cartpole)
+    else if (is_cartpole)
         hipLaunchKernelGGL(stepenv::k_stepenv_step_cartpole, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->se, h->se_io_idx, n, (const int32_t *)h->se_io_act, h->se_io_rew, h->se_io_done);
     else
         hipLaunchKernelGGL(stepenv::k_stepenv_step_pendulum, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->se, h->se_io_idx, n, h->se_io_act, h->se_io_rew, h->se_io_done);
@@ -3522,12 +3591,147 @@ extern "C" int dne_stepenv_observe_host(int kind, int n, const double *state, co
     return stepenv::observe_host(kind, n, state, &mz, obs);
 }
 
+
+// ------------------------------------------------------------------------------- dense policies on the step environments (csrc/dense.h)
+static void dense_launch(dne_handle *h, int items, const dense::RunArgs &A) {
+    const size_t lds = (size_t)A.shape.P * sizeof(float);
+    if (A.shape.env == DNE_KIND_MAZE) hipLaunchKernelGGL(dense::k_dense_run<DNE_KIND_MAZE>, dim3(items), dim3(64), lds, h->stream, A);
+    else if (A.shape.env == DNE_KIND_CARTPOLE) hipLaunchKernelGGL(dense::k_dense_run<DNE_KIND_CARTPOLE>, dim3(items), dim3(64), lds, h->stream, A);
+    else hipLaunchKernelGGL(dense::k_dense_run<DNE_KIND_PENDULUM>, dim3(items), dim3(64), lds, h->stream, A);
+}
+
+// what k_dense_run reads whatever it is used for: the members set by dne_set_members, the shape, the maze
+static dense::RunArgs dense_args(dne_handle *h) {
+    dense::RunArgs A{};
+    A.noise = h->noise; A.bases = h->bases; A.base_stride = h->base_stride;
+    A.m_slot = h->m_slot; A.m_off = h->m_off; A.m_scale = h->m_scale;
+    A.shape = h->dn_shape;
+    A.C = se_maze_ctx(h);
+    return A;
+}
+
+// members [0, n), one whole episode each from its own reset, one launch; the step-at-a-time batch is not touched
+static int dense_eval(dne_handle *h, const char *call, int n, int tslimit, const uint32_t *env_seed, float *returns, float *signreturns,
+                      int32_t *lengths, uint8_t *bc_out) {
+    const bool is_maze = h->dn_shape.env == DNE_KIND_MAZE;
+    if (bc_out) return h->fail("%s: behaviour characterisations are not available on a DNE_KIND_DENSE engine (kind %d): bc must be NULL; "
+                               "dne_dense_final_state has the final state of every member", call, DNE_KIND_DENSE);
+    if (tslimit <= 0) return h->fail("timestep limit must be positive");
+    if (is_maze && h->maze_nw < 1) return h->fail("DNE_KIND_DENSE: no maze loaded (dne_maze_set_walls comes before an evaluation)");
+    if (!is_maze && !env_seed) return h->fail("%s: a DNE_KIND_DENSE engine on the %s resets every member from its environment seed, env_seed is NULL", call,
+                                              h->dn_shape.env == DNE_KIND_CARTPOLE ? "cart-pole" : "pendulum");
+    if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
+    if (!is_maze) HCHECK(h, hipMemcpyAsync(h->seeds, env_seed, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    dense::RunArgs A = dense_args(h);
+    A.seed = h->seeds; A.episode = 1; A.max_steps = tslimit;
+    A.ret = h->ret; A.sign = h->sign; A.steps_out = h->len; A.state_out = h->dn_state;
+    if (run_episodes(h, n, returns, signreturns, lengths, [&] { dense_launch(h, n, A); })) return -1;
+    h->dn_last_n = n;
+    return 0;
+}
+
+extern "C" int dne_dense_env_kind(dne_handle *h) { return se_env(h); }
+
+extern "C" int dne_dense_final_state(dne_handle *h, int n, double *state) {
+    DeviceGuard dg(h);
+    if (!h->dense) return h->fail("dne_dense_final_state needs a DNE_KIND_DENSE engine (this one: kind %d)", h->L.kind);
+    return last_eval_rows(h, "dne_dense_final_state", n, h->dn_last_n, state != nullptr, state, (const double *)h->dn_state, se_dims(h).state);
+}
+
+// dne_stepenv_act (max_steps == 0) and dne_stepenv_run: the policy of members[i] behind environment indices[i], one k_dense_run launch
+static int se_dense(dne_handle *h, const char *call, bool run, int n, const int32_t *indices, const int32_t *members, int max_steps, float *out, void *actions,
+                    float *reward_sum, int32_t *steps_taken, uint8_t *done) {
+    if (!h->dense) return h->fail("%s needs a DNE_KIND_DENSE engine (this one: kind %d)", call, h->L.kind);
+    if (run && max_steps < 1) return h->fail("%s: max_steps = %d, at least one act -> step round is needed", call, max_steps);
+    std::vector<int32_t> idx;
+    if (se_check(h, call, n, indices, true, idx)) return -1;
+    const int set = (int)h->host_slot.size();
+    if (set < 1) return h->fail("%s: no members set (dne_set_members comes before the policy)", call);
+    std::vector<int32_t> mem(n);
+    for (int i = 0; i < n; i++) {
+        mem[i] = members ? members[i] : idx[i];
+        if (mem[i] < 0 || mem[i] >= set) return h->fail("%s: member %d at position %d is out of range, dne_set_members set members 0..%d", call, mem[i], i, set - 1);
+    }
+    if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
+    const stepenv::Dims d = se_dims(h);
+    HCHECK(h, hipMemcpyAsync(h->se_io_idx, idx.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HCHECK(h, hipMemcpyAsync(h->se_io_mem, mem.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    dense::RunArgs A = dense_args(h);
+    A.idx = h->se_io_idx; A.mem = h->se_io_mem; A.B = h->se; A.max_steps = run ? max_steps : 0;
+    if (run) { A.ret = h->se_io_rew; A.steps_out = h->se_io_steps; A.done_out = h->se_io_done; }
+    else { A.out = h->se_io_out; A.act = h->se_io_act; }
+    HCHECK(h, hipEventRecord(h->se_ev_a, h->stream));
+    dense_launch(h, n, A);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipEventRecord(h->se_ev_b, h->stream));
+    if (run) {
+        if (reward_sum) HCHECK(h, hipMemcpyAsync(reward_sum, h->se_io_rew, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        if (steps_taken) HCHECK(h, hipMemcpyAsync(steps_taken, h->se_io_steps, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        if (done) HCHECK(h, hipMemcpyAsync(done, h->se_io_done, n, hipMemcpyDeviceToHost, h->stream));
+    } else {
+        if (out) HCHECK(h, hipMemcpyAsync(out, h->se_io_out, (size_t)n * h->dn_shape.dim[h->dn_shape.n_hidden + 1] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        if (actions) HCHECK(h, hipMemcpyAsync(actions, h->se_io_act, (size_t)n * d.act * sizeof(float), hipMemcpyDeviceToHost, h->stream));   // (an int32 is a float's size)
+    }
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    float ms = 0;
+    HCHECK(h, hipEventElapsedTime(&ms, h->se_ev_a, h->se_ev_b));
+    h->se_last_ms = ms;
+    return 0;
+}
+
+extern "C" int dne_stepenv_act(dne_handle *h, int n, const int32_t *indices, const int32_t *members, float *out, void *actions) {
+    DeviceGuard dg(h);
+    return se_dense(h, "dne_stepenv_act", false, n, indices, members, 0, out, actions, nullptr, nullptr, nullptr);
+}
+
+extern "C" int dne_stepenv_run(dne_handle *h, int n, const int32_t *indices, const int32_t *members, int max_steps, float *reward_sum, int32_t *steps_taken,
+                               uint8_t *done) {
+    DeviceGuard dg(h);
+    return se_dense(h, "dne_stepenv_run", true, n, indices, members, max_steps, nullptr, nullptr, reward_sum, steps_taken, done);
+}
+
+// the same header on the CPU: no handle, no GPU
+static int dense_host_shape(const char *call, int env_kind, int n_hidden, const int32_t *widths, int nonlin, int n_out, dense::Shape *sh) {
+    if (n_hidden > 0 && !widths) { g_create_error = std::string(call) + ": widths is NULL"; return -1; }
+    const int nw = n_hidden < 0 ? 0 : n_hidden;   // (widths holds the n_hidden widths and nothing behind them)
+    return dense_shape_error(call, dense::make_shape(env_kind, n_hidden, widths, nw, nonlin, n_out, sh), env_kind, n_hidden, widths, nw, nonlin, n_out);
+}
+
+extern "C" int dne_dense_forward_host(const float *theta, const float *obs, int n, int env_kind, int n_hidden, const int32_t *widths, int nonlin, int n_out,
+                                      float *layers, float *out, void *action) {
+    dense::Shape sh;
+    if (dense_host_shape("dne_dense_forward_host", env_kind, n_hidden, widths, nonlin, n_out, &sh)) return -1;
+    if (n < 1 || !theta || !obs || !out) { g_create_error = "dne_dense_forward_host: bad arguments"; return -1; }
+    int hid = 0;
+    for (int l = 1; l <= sh.n_hidden; l++) hid += sh.dim[l];
+    const int act_w = env_kind == DNE_KIND_MAZE ? 2 : 1;
+    for (int i = 0; i < n; i++) {
+        dense::forward_host(sh, theta + (size_t)i * sh.P, obs + (size_t)i * sh.dim[0], layers ? layers + (size_t)i * hid : nullptr, out + (size_t)i * n_out);
+        if (action) dense::write_action(env_kind, out + (size_t)i * n_out, (char *)action + (size_t)i * act_w * sizeof(float));
+    }
+    return 0;
+}
+
+extern "C" int dne_dense_rollout_host(const float *theta, int n, int env_kind, int n_hidden, const int32_t *widths, int nonlin, int n_out, const uint32_t *seeds,
+                                      const double *init_state, const float *header8, const float *lines, int n_walls, int tslimit, float *returns,
+                                      float *signreturns, int32_t *lengths, double *state) {
+    dense::Shape sh;
+    if (dense_host_shape("dne_dense_rollout_host", env_kind, n_hidden, widths, nonlin, n_out, &sh)) return -1;
+    stepenv::MazeCtx mz{};
+    if (se_host_args("dne_dense_rollout_host", env_kind, n, header8, lines, n_walls, &mz)) return -1;
+    if (tslimit <= 0 || !theta || !returns || !lengths || !state) { g_create_error = "dne_dense_rollout_host: bad arguments"; return -1; }
+    if (env_kind != DNE_KIND_MAZE && !seeds && !init_state) { g_create_error = std::string("dne_dense_rollout_host: ") + episodic_kind_name(env_kind) + " resets every environment from its seed, seeds is NULL"; return -1; }
+    dense::rollout_host(sh, theta, n, seeds, init_state, mz, tslimit, returns, signreturns, lengths, state);
+    return 0;
+}
+
 // ------------------------------------------------------------------------------- evaluations by descriptor: antithetic pairs, members as set
 // the members set by dne_set_members through the whole-episode kernel of the engine's kind (the maze's episode is deterministic and mjmaze's has no
 // reset seed: neither reads env_seed)
 static int episodic_eval(dne_handle *h, const char *call, int n, int tslimit, const uint32_t *env_seed, float *returns, float *signreturns,
                          int32_t *lengths, uint8_t *bc) {
     if (h->maze) return maze_eval_members(h, maze_set_members(h), n, tslimit, returns, signreturns, lengths, bc);
+    if (h->dense) return dense_eval(h, call, n, tslimit, env_seed, returns, signreturns, lengths, bc);
     if (h->cartpole) return cartpole_eval(h, call, n, tslimit, env_seed, returns, signreturns, lengths, bc);
     if (h->pendulum) return pendulum_eval(h, call, n, tslimit, env_seed, returns, signreturns, lengths, bc);
     return mjmaze_eval(h, call, n, tslimit, returns, signreturns, lengths, bc);

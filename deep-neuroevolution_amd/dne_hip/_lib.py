@@ -28,6 +28,8 @@ KIND_MJMAZE = 7   # MujocoPolicy on the hard maze (final (x, y) as the behaviour
 MJMAZE_OBS, MJMAZE_ADIM, MJMAZE_STEPS, MJMAZE_TRACE_W, MJMAZE_MAX_BINS = 11, 2, 400, 20, 8   # observations, action dimensions, steps, floats per trace row, most bins a dimension
 MJMAZE_AC_NOISE = MJMAZE_ADIM * MJMAZE_STEPS            # action-noise values an episode reads from the table
 MJMAZE_AC_LOW, MJMAZE_AC_HIGH = -0.5, 0.5               # the action space: what the maze clamps its raw outputs to
+KIND_DENSE = 8    # a dense policy of any small shape (0..3 hidden layers of width 1..64) on the maze, the cart-pole or the pendulum (csrc/dense.h)
+DENSE_NONLINS = {'tanh': 0, 'relu': 1}                # dne_config.reserved[2] of a KIND_DENSE engine
 MUJOCO_KINDS = (KIND_PENDULUM, KIND_MJMAZE)             # the kinds whose shape travels in dne_config.reserved
 ES_KINDS = (KIND_ES, KIND_ES_VBN)   # virtual batch norm over a reference batch, antithetic pairs
 PROC_MODES = {"centered_rank": 0, "sign": 1, "centered_sign_rank": 2}
@@ -86,7 +88,7 @@ class Profile(C.Structure):
 
 def build(force=False):
     """Compile libdne_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h", "cartpole.h", "pendulum.h", "mjmaze.h", "step_env.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h", "cartpole.h", "pendulum.h", "mjmaze.h", "step_env.h", "dense.h")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dne_hip.h"))
     if os.environ.get("DNE_LIB_PATH"):
         # another build of the same ABI was asked for by name: `make` only knows the in-tree library, so running it here would
@@ -606,6 +608,66 @@ def stepenv_observe_host(kind, state, header=None, lines=None):
     return obs
 
 
+# ---- dense policies of any small shape on the step environments (csrc/dense.h) ------------------------------------------------------------------
+def _dense_shape(hidden, nonlin):
+    """(n_hidden, the widths as int32 array or None, the nonlinearity's number)"""
+    hidden = tuple(int(w) for w in hidden)
+    return len(hidden), (np.array(hidden, np.int32) if hidden else None), int(DENSE_NONLINS.get(nonlin, nonlin))
+
+
+def dense_num_params(env_kind, hidden, n_out):
+    """dne_dense_num_params: P of the shape (env_kind's inputs, the hidden widths, n_out outputs), -1 for a shape that is not built"""
+    L, w, _ = _dense_shape(hidden, 1)
+    return load().dne_dense_num_params(int(env_kind), L, _ptr(w, C.c_int32), int(n_out))
+
+
+def dense_forward_host(theta, obs, env_kind, hidden, nonlin, n_out):
+    """dne_dense_forward_host: theta [n][P], obs [n][OBS] -> (layers float32 [n][sum(hidden)]: every hidden layer behind its nonlinearity, out
+    float32 [n][n_out], actions as stepenv_step takes them)"""
+    env_kind, n_out = int(env_kind), int(n_out)
+    L, w, nl = _dense_shape(hidden, nonlin)
+    obs_w, act_w, _, is_int = stepenv_dims(env_kind) if env_kind in STEPENV_KINDS else (1, 1, 1, False)
+    P = load().dne_dense_num_params(env_kind, L, _ptr(w, C.c_int32), n_out)
+    if P < 0:   # (one row of whatever was given: the call below names what is wrong with the shape)
+        theta, obs = _arr(theta, np.float32).reshape(1, -1), _arr(obs, np.float32).reshape(1, -1)
+    theta = _arr(theta, np.float32).reshape(-1, P if P > 0 else theta.size)
+    obs = _arr(obs, np.float32).reshape(-1, obs_w if P > 0 else obs.size)
+    n = theta.shape[0]
+    if obs.shape[0] != n:
+        raise DneError("dense_forward_host: %d thetas, %d observations" % (n, obs.shape[0]))
+    layers = np.empty((n, int(sum(hidden))), np.float32); out = np.empty((n, max(n_out, 1)), np.float32)
+    act = np.empty((n, act_w) if act_w > 1 else n, np.int32 if is_int else np.float32)
+    _ck_host(load().dne_dense_forward_host(_ptr(theta, C.c_float), _ptr(obs, C.c_float), n, env_kind, L, _ptr(w, C.c_int32), nl, n_out,
+                                           _ptr(layers, C.c_float), _ptr(out, C.c_float), C.cast(_ptr(act, C.c_int32 if is_int else C.c_float), C.c_void_p)))
+    return layers, out, act
+
+
+def dense_rollout_host(theta, env_kind, hidden, nonlin, n_out, seeds=None, tslimit=0, init=None, header=None, lines=None):
+    """dne_dense_rollout_host: one whole episode per theta [n][P] from its reset (seeds uint32 [n]; the maze reads none) or from init [n][S], to
+    the environment's own limit or tslimit (<= 0: the own limit) -> dict(returns, signreturns, lengths, state float64 [n][S])"""
+    env_kind, n_out = int(env_kind), int(n_out)
+    L, w, nl = _dense_shape(hidden, nonlin)
+    S = stepenv_dims(env_kind)[2] if env_kind in STEPENV_KINDS else 1   # (another kind: the call below refuses it by name)
+    P = load().dne_dense_num_params(env_kind, L, _ptr(w, C.c_int32), n_out)
+    theta = _arr(theta, np.float32)
+    theta = theta.reshape(-1, P) if P > 0 else theta.reshape(1, -1)   # (a shape that is not built: one row, the call below names what is wrong)
+    n = theta.shape[0]
+    if seeds is not None:
+        seeds = _arr(seeds, np.uint32).reshape(-1)
+        if seeds.size != n:
+            raise DneError("dense_rollout_host: %d thetas, %d seeds" % (n, seeds.size))
+    if init is not None:
+        init = _arr(init, np.float64).reshape(n, S)
+    if int(tslimit) <= 0:
+        tslimit = {KIND_MAZE: MAZE_STEPS, KIND_CARTPOLE: CARTPOLE_STEPS, KIND_PENDULUM: PENDULUM_STEPS}.get(env_kind, 1)
+    hp, lp, nw, _keep = _stepenv_maze(env_kind, header, lines)
+    ret = np.empty(n, np.float32); sign = np.empty(n, np.float32); ln = np.empty(n, np.int32); state = np.empty((n, S), np.float64)
+    _ck_host(load().dne_dense_rollout_host(_ptr(theta, C.c_float), n, env_kind, L, _ptr(w, C.c_int32), nl, n_out, _ptr(seeds, C.c_uint32),
+                                           _ptr(init, C.c_double), hp, lp, nw, int(tslimit), _ptr(ret, C.c_float), _ptr(sign, C.c_float),
+                                           _ptr(ln, C.c_int32), _ptr(state, C.c_double)))
+    return dict(returns=ret, signreturns=sign, lengths=ln, state=state)
+
+
 def _ptr(a, t):
     return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
 
@@ -621,9 +683,11 @@ class Engine:
     n_actions of them, and dne_create refuses a wider one (DneError)."""
 
     def __init__(self, kind, n_actions=18, max_members=256, ref_count=128, device_id=0, ref_chunk=0,
-                 record_bc=False, bc_max_steps=0, profile_events=False, bc_final_only=False, hidden=0, ac_mode=0, nonlin=0):
+                 record_bc=False, bc_max_steps=0, profile_events=False, bc_final_only=False, hidden=0, ac_mode=0, nonlin=0, env=None):
         """hidden, ac_mode, nonlin: the shape of a KIND_PENDULUM or KIND_MJMAZE engine (hidden width 64 / 128 / 256; 'continuous' or 'uniform';
-        'tanh' or 'relu'), with n_actions the outputs (the pendulum: 1, or the bins; the maze: 2, or twice the bins)"""
+        'tanh' or 'relu'), with n_actions the outputs (the pendulum: 1, or the bins; the maze: 2, or twice the bins).
+        A KIND_DENSE engine: env the environment's kind (KIND_MAZE, KIND_CARTPOLE or KIND_PENDULUM), hidden the tuple of hidden widths (() is
+        LinearClassifier), nonlin 'tanh' or 'relu', n_actions the outputs (2, 2, 1)"""
         self.lib = load()
         self.kind, self.n_actions, self.max_members = int(kind), int(n_actions), int(max_members)
         self.ref_count = int(ref_count) if kind in ES_KINDS else 0
@@ -632,7 +696,18 @@ class Engine:
                      ref_count=self.ref_count, ref_chunk=ref_chunk, record_bc=int(bool(record_bc)),
                      bc_max_steps=self.bc_max_steps, profile_events=int(bool(profile_events)),
                      bc_final_only=int(bool(bc_final_only)))
-        self.hidden = int(hidden)
+        self.env_kind = self.kind   # the environment the stepenv_* methods step: a KIND_DENSE engine's is the one it was created on
+        if self.kind == KIND_DENSE:
+            self.hidden = tuple(int(w) for w in (hidden if hasattr(hidden, '__len__') else ((hidden,) if hidden else ())))
+            self.nonlin = int(DENSE_NONLINS.get(nonlin, nonlin))
+            self.env_kind = int(KIND_MAZE if env is None else env)
+            cfg.reserved[0], cfg.reserved[1], cfg.reserved[2] = self.env_kind, len(self.hidden), self.nonlin
+            for i, w in enumerate(self.hidden[:3]):
+                cfg.reserved[3 + i] = w
+            if len(self.hidden) > 3:
+                cfg.reserved[1] = len(self.hidden)   # (dne_create refuses it by name)
+        else:
+            self.hidden = int(hidden)
         if self.kind in MUJOCO_KINDS:
             self.ac_mode, self.nonlin = int(PENDULUM_AC_MODES.get(ac_mode, ac_mode)), int(PENDULUM_NONLINS.get(nonlin, nonlin))
             cfg.reserved[0], cfg.reserved[1], cfg.reserved[2] = self.hidden, self.ac_mode, self.nonlin
@@ -643,6 +718,7 @@ class Engine:
             raise DneError(self.lib.dne_last_error(None).decode())
         self.P = self.lib.dne_pendulum_num_params(self.hidden, self.n_actions) if self.kind == KIND_PENDULUM else \
             self.lib.dne_mjmaze_num_params(self.hidden, self.n_actions) if self.kind == KIND_MJMAZE else \
+            dense_num_params(self.env_kind, self.hidden, self.n_actions) if self.kind == KIND_DENSE else \
             self.lib.dne_num_params(self.kind, self.n_actions)
         self.record_bc = bool(record_bc)
         self.noise_count = 0
@@ -977,11 +1053,11 @@ class Engine:
         """dne_stepenv_step_f32 / _i32 by the dtype the kind takes: one step of the named environments under actions (maze float32 [n][2],
         cart-pole int32 [n], pendulum float32 [n]) -> (reward float32 [n], done bool [n]).  as_int names the entry point outright (the engine
         refuses the one its kind does not take)."""
-        is_int = bool(as_int) if as_int is not None else stepenv_dims(self.kind)[3] if self.kind in STEPENV_KINDS else np.asarray(actions).dtype.kind in "iu"
+        is_int = bool(as_int) if as_int is not None else stepenv_dims(self.env_kind)[3] if self.env_kind in STEPENV_KINDS else np.asarray(actions).dtype.kind in "iu"
         a = _arr(actions, np.int32 if is_int else np.float32)
         ip, n, _keep = self._stepenv_idx(indices, a.shape[0] if a.ndim else 1)
-        if as_int is None and self.kind in STEPENV_KINDS and a.size != n * stepenv_dims(self.kind)[1]:
-            raise DneError("stepenv_step: %d environments take %d action values, %d given" % (n, n * stepenv_dims(self.kind)[1], a.size))
+        if as_int is None and self.env_kind in STEPENV_KINDS and a.size != n * stepenv_dims(self.env_kind)[1]:
+            raise DneError("stepenv_step: %d environments take %d action values, %d given" % (n, n * stepenv_dims(self.env_kind)[1], a.size))
         rew = np.empty(n, np.float32); done = np.empty(n, np.uint8)
         if is_int:
             self._ck(self.lib.dne_stepenv_step_i32(self.h, n, ip, _ptr(a, C.c_int32), _ptr(rew, C.c_float), _ptr(done, C.c_uint8)))
@@ -992,7 +1068,7 @@ class Engine:
     def stepenv_observation(self, indices=None, n=None):
         """dne_stepenv_observation: what the policy sees next, float32 [n][OBS] in the order of the list"""
         ip, n, _keep = self._stepenv_idx(indices, n)
-        w = stepenv_dims(self.kind)[0] if self.kind in STEPENV_KINDS else 1
+        w = stepenv_dims(self.env_kind)[0] if self.env_kind in STEPENV_KINDS else 1
         out = np.empty((max(n, 0), w), np.float32)
         self._ck(self.lib.dne_stepenv_observation(self.h, n, ip, _ptr(out, C.c_float)))
         return out
@@ -1000,7 +1076,7 @@ class Engine:
     def stepenv_state(self, indices=None, n=None):
         """dne_stepenv_get_state: (state float64 [n][S], steps int32 [n], done bool [n])"""
         ip, n, _keep = self._stepenv_idx(indices, n)
-        S = stepenv_dims(self.kind)[2] if self.kind in STEPENV_KINDS else 1
+        S = stepenv_dims(self.env_kind)[2] if self.env_kind in STEPENV_KINDS else 1
         state = np.empty((max(n, 0), S), np.float64); steps = np.empty(max(n, 0), np.int32); done = np.empty(max(n, 0), np.uint8)
         self._ck(self.lib.dne_stepenv_get_state(self.h, n, ip, _ptr(state, C.c_double), _ptr(steps, C.c_int32), _ptr(done, C.c_uint8)))
         return state, steps, done.astype(bool)
@@ -1008,7 +1084,7 @@ class Engine:
     def stepenv_set_state(self, state, steps=None, indices=None, max_steps=0):
         """dne_stepenv_set_state: the named environments are put into states float64 [n][S] with `steps` already taken (default 0); the
         observation is recomputed, done cleared, the limit set as by a reset"""
-        S = stepenv_dims(self.kind)[2] if self.kind in STEPENV_KINDS else 1
+        S = stepenv_dims(self.env_kind)[2] if self.env_kind in STEPENV_KINDS else 1
         state = _arr(state, np.float64).reshape(-1, S)
         ip, n, _keep = self._stepenv_idx(indices, state.shape[0])
         steps = np.zeros(n, np.int32) if steps is None else _arr(steps, np.int32).reshape(-1)
@@ -1020,6 +1096,42 @@ class Engine:
         """the last step kernel between two device events, milliseconds (-1 before the first)"""
         self.lib.dne_stepenv_last_ms.restype = C.c_double
         return float(self.lib.dne_stepenv_last_ms(self.h))
+
+    # ---- a dense policy behind the environments (KIND_DENSE; csrc/dense.h)
+    def _stepenv_members(self, members, n):
+        if members is None:
+            return None, None
+        m = _arr(members, np.int32).reshape(-1)
+        if m.size != n:
+            raise DneError("stepenv: %d environments, %d members" % (n, m.size))
+        return _ptr(m, C.c_int32), m
+
+    def stepenv_act(self, indices=None, members=None, n=None):
+        """dne_stepenv_act: the forward pass of member members[i] (None: members[i] = indices[i]) on the current observation of environment
+        indices[i] -> (out float32 [n][outputs], actions as stepenv_step takes them)"""
+        ip, n, _keep = self._stepenv_idx(indices, n)
+        mp, _keep2 = self._stepenv_members(members, n)
+        obs_w, act_w, _, is_int = stepenv_dims(self.env_kind) if self.env_kind in STEPENV_KINDS else (1, 1, 1, False)
+        out = np.empty((max(n, 0), self.n_actions), np.float32)
+        act = np.empty((max(n, 0), act_w) if act_w > 1 else max(n, 0), np.int32 if is_int else np.float32)
+        self._ck(self.lib.dne_stepenv_act(self.h, n, ip, mp, _ptr(out, C.c_float), C.cast(_ptr(act, C.c_int32 if is_int else C.c_float), C.c_void_p)))
+        return out, act
+
+    def stepenv_run(self, max_steps, indices=None, members=None, n=None):
+        """dne_stepenv_run: max_steps >= 1 rounds of act -> step in one launch from the batch's current state -> (reward_sum float32 [n]: the
+        float64 sum of this call's rewards cast once, steps_taken int32 [n], done bool [n])"""
+        ip, n, _keep = self._stepenv_idx(indices, n)
+        mp, _keep2 = self._stepenv_members(members, n)
+        rew = np.empty(max(n, 0), np.float32); steps = np.empty(max(n, 0), np.int32); done = np.empty(max(n, 0), np.uint8)
+        self._ck(self.lib.dne_stepenv_run(self.h, n, ip, mp, int(max_steps), _ptr(rew, C.c_float), _ptr(steps, C.c_int32), _ptr(done, C.c_uint8)))
+        return rew, steps, done.astype(bool)
+
+    def dense_final_state(self, n):
+        """dne_dense_final_state: the final states float64 [n][S] of the last evaluation"""
+        S = stepenv_dims(self.env_kind)[2] if self.env_kind in STEPENV_KINDS else 1
+        out = np.empty((max(int(n), 0), S), np.float64)
+        self._ck(self.lib.dne_dense_final_state(self.h, int(n), _ptr(out, C.c_double)))
+        return out
 
     # ---- novelty on the hard maze (csrc/maze_novelty.h): BCs are final (x, y) points, the archive lives on the device
     def _maze_points(self, xy, n):

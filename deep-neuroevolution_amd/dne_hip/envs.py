@@ -22,22 +22,26 @@ class HipStepEnv:
     game = None
     env_default_timestep_cutoff = None
 
-    def __init__(self, batch_size, engine=None, seed=0):
+    def __init__(self, batch_size, engine=None, seed=0, hidden=None, nonlin='relu'):
         batch_size = int(batch_size)
         if batch_size < 1:
             raise ValueError("{}: a batch of {} environments".format(self.game, batch_size))
-        if engine is not None and engine.kind != self.kind:
+        if engine is not None and getattr(engine, 'env_kind', engine.kind) != self.kind:   # (a KIND_DENSE engine steps the environment it was created on)
             raise ValueError("game {!r} asked for, the engine passed in is of kind {} (kind {} runs it)".format(self.game, engine.kind, self.kind))
         if engine is not None and engine.max_members < batch_size:
             raise ValueError("game {!r}: a batch of {} environments, the engine passed in holds {}".format(self.game, batch_size, engine.max_members))
         self._own = engine is None
-        self.engine = self._open(batch_size) if engine is None else engine
+        self.engine = (self._open(batch_size) if hidden is None else self._open_dense(batch_size, hidden, nonlin)) if engine is None else engine
         self.batch_size = batch_size
         self._obs_w, self._act_w, self._state_w, self._int_act = _lib.stepenv_dims(self.kind)
         self.np_random = np.random.RandomState(seed)
 
     def _open(self, batch_size):
         return _lib.Engine(self.kind, 2, max_members=batch_size)
+
+    def _open_dense(self, batch_size, hidden, nonlin):
+        """an engine whose policy is a dense stack of the caller's shape (hidden: the tuple of widths, () a LinearClassifier) on this environment"""
+        return _lib.Engine(_lib.KIND_DENSE, 1 if self.kind == _lib.KIND_PENDULUM else 2, max_members=batch_size, env=self.kind, hidden=tuple(hidden), nonlin=nonlin)
 
     # ---- tf_env.py's properties
     @property
@@ -98,9 +102,9 @@ class HipMazeEnv(HipStepEnv):
     """the hard maze (gym_tensorflow/maze/): 11 observations, two raw outputs as the action, 400 steps, the reward on the last of them"""
     kind, game, env_default_timestep_cutoff = _lib.KIND_MAZE, MAZE_GAME, _lib.MAZE_STEPS
 
-    def __init__(self, batch_size, engine=None, seed=0, maze_file=None):
+    def __init__(self, batch_size, engine=None, seed=0, maze_file=None, hidden=None, nonlin='relu'):
         self._maze_file = maze_file
-        super().__init__(batch_size, engine, seed)
+        super().__init__(batch_size, engine, seed, hidden, nonlin)
         if self._own or maze_file is not None:
             self.engine.maze_set_walls(*_lib.load_maze(self._path()))
 
@@ -130,7 +134,9 @@ _GAMES = {MAZE_GAME: HipMazeEnv, CARTPOLE_GAME: HipCartPoleEnv, PENDULUM_GAME: H
 
 def make(game, batch_size, engine=None, **kw):
     """gym_tensorflow.make for the three games: 'maze' (maze_file=... as the maze drivers take it), 'gym.CartPole-v1', 'Pendulum-v0'.  engine:
-    an Engine of the game's kind with max_members >= batch_size (None: one is made and closed with the environment); seed=... starts np_random"""
+    an Engine of the game's kind with max_members >= batch_size (None: one is made and closed with the environment); seed=... starts np_random.
+    hidden=(...) (and nonlin='relu' or 'tanh'): the engine made is a KIND_DENSE one whose policy is a dense stack of those hidden widths on the
+    game's environment (() is a LinearClassifier), so that run() below keeps whole episodes on the device; an engine of that kind may be passed in too"""
     if game not in _GAMES:
         raise NotImplementedError("game {!r}: the step-at-a-time environments are {}".format(game, ", ".join(repr(g) for g in _GAMES)))
     return _GAMES[game](batch_size, engine=engine, **kw)
@@ -148,4 +154,22 @@ def rollout(env, act, seeds=None, max_frames=None):
         reward, done = env.step(act(env.observation()))
         total += reward.astype(np.float64)
         lengths += live
+    return total.astype(np.float32), lengths
+
+
+def run(env, members=None, max_steps=None, seeds=None, max_frames=None):
+    """rollout's device counterpart on a KIND_DENSE engine: reset, then the policy of the engine's members behind the environments
+    (members[i] under environment i; None: member i) in stepenv_run launches of max_steps rounds each (None: one launch to the end) until every
+    environment is done.  Returns (returns float32 [n], lengths int32 [n]) with rollout's contract when the episodes finish in one launch; over
+    several launches each launch's float64 sum is cast once and the casts are added in float64."""
+    env.reset(max_frames=max_frames, seeds=seeds)
+    n = env.batch_size
+    if members is not None:
+        members = np.ascontiguousarray(members, np.int32).reshape(-1)
+    rounds = env.env_default_timestep_cutoff if max_steps is None else int(max_steps)
+    total, lengths, done = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, bool)
+    while not done.all():
+        reward, steps, done = env.engine.stepenv_run(rounds, env._indices(None), members)
+        total += reward.astype(np.float64)
+        lengths += steps
     return total.astype(np.float32), lengths

@@ -39,6 +39,13 @@ episodes included, as on Atari); theta starts as noise.get(idx, 386) * policies.
 'env_default' means 500 steps, and a larger cutoff (the shipped 5000) leaves gym's own 500 in force (GymEnv.reset ignores max_frames, tf_env.py:47-52).
 A step is a frame.  The game is recorded in snapshot.pkl like the maze's.  Every other 'gym.*' name is refused by name: no other gym environment is built.
 
+exp['model'] == 'LinearClassifier' (models/simple.py:23-27: one dense layer from the observation to the outputs) on game 'maze' or
+'gym.CartPole-v1' runs on a DNE_KIND_DENSE engine with no hidden layer (csrc/dense.h: a dense stack of any small shape on the step environments,
+whole episodes in k_dense_run) through the same episodic loop; theta starts as noise.get(idx, P) * policies.dense_scale_by(...) with idx the
+stream's first draw.  A caller's engine of kind KIND_DENSE, of any shape, is accepted on its environment's game (its model is recorded as
+'LinearClassifier' without hidden layers, else as dense_model_name writes the shape); one whose environment is not the game's is refused, naming
+both.  SimpleClassifier keeps its own kinds and kernels.
+
 Where the arithmetic lives: ranks, sum_i w_i * noise[idx_i] / 2N, -g + l2coeff * theta and the optimizer step are dne_es_update on the device
 (the same formulas as es_distributed: es.py:227-246 here = es_distributed/es.py:281-301).  The GPU tree's SGD keeps v = momentum * v + g
 (neuroevolution/optimizers.py:49-51) where es_distributed keeps (1 - momentum) * g: with u = (1 - momentum) * v that is the engine's SGD at
@@ -56,11 +63,20 @@ from .es import SharedNoiseTable, get_ref_batch, optimizer_args, parse_cutoff
 from .ga_gpu import Offspring, Schedule, model_scale_by
 from . import cartpole_run
 from .cartpole_run import CARTPOLE_GAME
-from .maze_run import MAZE_FILE, MAZE_MODEL, check_engine, maze_file, open_engine   # noqa: F401 (MAZE_FILE, maze_file: read as es_gpu's by callers)
+from .maze_run import MAZE_FILE, MAZE_MODEL, attach_table, check_engine, maze_file, open_engine   # noqa: F401 (MAZE_FILE, maze_file: read as es_gpu's by callers)
 
 # exp['model'] (es.py:144): neuroevolution/models/batchnorm.py:52 (in either flat layout, FLAT_LAYOUTS) and models/dqn.py:39
 MODEL_KINDS = {'ModelVirtualBN': _lib.KIND_ES, 'LargeModel': _lib.KIND_GA_LARGE}
 FLAT_LAYOUTS = {'es_distributed': _lib.KIND_ES, 'native': _lib.KIND_ES_VBN}   # exp['flat_layout'] -> the engine kind that runs it
+LINEAR_MODEL = 'LinearClassifier'        # neuroevolution/models/simple.py:23-27, on a KIND_DENSE engine without hidden layers
+DENSE_GAMES = {_lib.KIND_MAZE: 'maze', _lib.KIND_CARTPOLE: CARTPOLE_GAME, _lib.KIND_PENDULUM: 'Pendulum-v0'}   # a KIND_DENSE engine's environment -> its game
+
+
+def dense_model_name(engine):
+    """the model a KIND_DENSE engine runs, as snapshot.pkl records it"""
+    if not engine.hidden:
+        return LINEAR_MODEL
+    return 'Dense({}; {})'.format(', '.join(str(w) for w in engine.hidden), 'relu' if engine.nonlin == _lib.DENSE_NONLINS['relu'] else 'tanh')
 
 
 class TrainingState(object):
@@ -112,9 +128,10 @@ def engine_optimizer(opt):
 
 def _env_limit(engine):
     """the environment's own episode bound: env_default_timestep_cutoff of the maze (tf_maze.py:32-33), CartPole-v1's 500, gym's TimeLimit for Atari"""
-    if engine.kind == _lib.KIND_CARTPOLE:
+    kind = getattr(engine, 'env_kind', engine.kind)   # (a KIND_DENSE engine: the environment it was created on)
+    if kind == _lib.KIND_CARTPOLE:
         return _lib.CARTPOLE_STEPS
-    return _lib.MAZE_STEPS if engine.kind == _lib.KIND_MAZE else _lib.ENV_MAX_EPISODE_STEPS
+    return _lib.MAZE_STEPS if kind == _lib.KIND_MAZE else _lib.ENV_MAX_EPISODE_STEPS
 
 
 def _episodes_of_theta(engine, n, tslimit, rs):
@@ -143,9 +160,21 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
     game = exp.get('game')
     if isinstance(game, str) and game.startswith('gym.') and game != CARTPOLE_GAME:
         raise NotImplementedError("game {!r}: of gym_tensorflow's 'gym.*' environments this loop runs {!r} only".format(game, CARTPOLE_GAME))
+    dense = engine.kind == _lib.KIND_DENSE if engine is not None else asked == LINEAR_MODEL   # a dense stack on a step environment (csrc/dense.h)
     cart = game == CARTPOLE_GAME or (engine is not None and engine.kind == _lib.KIND_CARTPOLE)
     maze = not cart and (game == 'maze' or (engine is not None and engine.kind == _lib.KIND_MAZE))
-    if cart:                                                        # gym_tensorflow.make(game='gym.CartPole-v1'): GymEnv's cart-pole under SimpleClassifier
+    if dense:
+        if engine is None and not (cart or maze):
+            raise NotImplementedError("model {!r} on game {!r}: this loop runs it on 'maze' and {!r}".format(asked, game, CARTPOLE_GAME))
+        if engine is not None:
+            if DENSE_GAMES.get(engine.env_kind) != game:
+                raise ValueError("game {!r} asked for, the engine passed in (kind {} on environment kind {}) runs {!r}".format(
+                    game, engine.kind, engine.env_kind, DENSE_GAMES.get(engine.env_kind)))
+            if engine.env_kind == _lib.KIND_PENDULUM:
+                raise NotImplementedError("game {!r}: this loop runs a KIND_DENSE engine on 'maze' and {!r}".format(game, CARTPOLE_GAME))
+        if asked is not None and engine is not None and asked != dense_model_name(engine):
+            raise ValueError("model {!r} asked for, the engine passed in (kind {}) runs {!r}".format(asked, engine.kind, dense_model_name(engine)))
+    elif cart:                                                        # gym_tensorflow.make(game='gym.CartPole-v1'): GymEnv's cart-pole under SimpleClassifier
         if game != CARTPOLE_GAME:
             raise ValueError("game {!r} asked for, the engine passed in (kind {}) runs {!r}".format(game, engine.kind, CARTPOLE_GAME))
         cartpole_run.check_engine(engine)
@@ -163,18 +192,26 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
     if not episodic and asked is not None and asked not in MODEL_KINDS:
         raise NotImplementedError("model {!r}: this loop runs {}".format(asked, sorted(MODEL_KINDS)))
     large = not episodic and (engine.kind if engine is not None else MODEL_KINDS[asked]) == _lib.KIND_GA_LARGE
-    model = MAZE_MODEL if episodic else 'LargeModel' if large else 'ModelVirtualBN'
+    model = (LINEAR_MODEL if engine is None else dense_model_name(engine)) if dense else MAZE_MODEL if episodic else 'LargeModel' if large else 'ModelVirtualBN'
     if asked is not None and asked != model:
         raise ValueError("model {!r} asked for, the engine passed in (kind {}) runs {!r}".format(asked, engine.kind, model))
     if episodic:                                                    # one flat layout, no reference batch; the maze: the walls instead
         layout = 'native'
         if exp.get('flat_layout', layout) != layout:
-            raise ValueError("flat_layout {!r}: SimpleClassifier has one layout, 'native'".format(exp['flat_layout']))
-        if maze:
+            raise ValueError("flat_layout {!r}: {} has one layout, 'native'".format(exp['flat_layout'], model))
+        if dense:
+            if engine is None:
+                engine = _lib.Engine(_lib.KIND_DENSE, 2, max_members=2 * n_pairs, env=_lib.KIND_MAZE if maze else _lib.KIND_CARTPOLE, hidden=(), nonlin='relu')
+            if maze:
+                engine.maze_set_walls(*_lib.load_maze(maze_file(exp)))
+            noise = attach_table(engine, noise)
+            scale_by = policies.dense_scale_by(engine.env_kind, engine.hidden, engine.n_actions)
+        elif maze:
             engine, noise = open_engine(exp, engine, noise, 2 * n_pairs)
         else:
             engine, noise = cartpole_run.open_engine(engine, noise, 2 * n_pairs)
-        scale_by = policies.simple_scale_by(engine.kind)
+        if not dense:
+            scale_by = policies.simple_scale_by(engine.kind)
     elif large:                                                       # one flat layout, the model's own; no reference batch
         layout = 'native'
         if exp.get('flat_layout', layout) != layout:

@@ -87,6 +87,21 @@ def simple_scale_by(kind=_lib.KIND_MAZE):
     return sb
 
 
+def dense_scale_by(env_kind, hidden, n_out):
+    """scale_by of a dense stack on a step environment (a KIND_DENSE engine's flat order: per layer w [in][out], then b [out]):
+    Model.create_weight_variable's std / sqrt(prod(shape[:-1])) for each w, 0 for each b.  std is 1.0, and 0.1 on the last layer of a stack
+    with hidden layers (models/simple.py:34); LinearClassifier's single layer (hidden = ()) keeps 1.0 (simple.py:26).  For (16, 16) on the
+    maze or the cart-pole it is simple_scale_by."""
+    hidden = tuple(int(w) for w in hidden)
+    dims = (_lib.stepenv_dims(env_kind)[0],) + hidden + (int(n_out),)
+    parts = []
+    for l in range(len(dims) - 1):
+        std = 0.1 if hidden and l == len(dims) - 2 else 1.0
+        parts.append(np.full(dims[l] * dims[l + 1], np.float32(std / np.sqrt(dims[l])), np.float32))
+        parts.append(np.zeros(dims[l + 1], np.float32))
+    return np.concatenate(parts)
+
+
 def xavier_flat(nact, seed=0):
     """Initial ESAtariPolicy parameters: tf.contrib.layers defaults (xavier-uniform weights, zero biases,
     BN beta 0 / gamma 1) drawn from RandomState(seed) -- TF's own initialiser is unseeded."""

@@ -66,6 +66,20 @@ extern "C" {
                            dne_maze_set_walls, dne_maze_final_state, dne_maze_archive_append / _clear / _size / _get, dne_maze_novelty and
                            dne_maze_novelty_last_ms.  bc, record_bc and bc_final_only are refused, and so is every other Atari, GA, maze-GA,
                            pool-novelty, cart-pole, pendulum, plan and dne_stepenv_* call (the maze one step at a time is DNE_KIND_MAZE's). */
+#define DNE_KIND_DENSE 8 /* a dense policy of any small shape on one of the three step environments (csrc/dense.h): the
+                           model half of concurrent_worker.py:56-67 beside the dne_stepenv_* environments.  dne_config.reserved: [0] the
+                           environment (DNE_KIND_MAZE, DNE_KIND_CARTPOLE or DNE_KIND_PENDULUM: 11 / 4 / 3 inputs and the action convention),
+                           [1] hidden layers L = 0..3 (0: models/simple.py:23-27 LinearClassifier), [2] nonlinearity (0 tanh, 1 relu),
+                           [3..5] the L hidden widths, each 1..64, unused entries 0.  n_actions carries the outputs: maze 2 (the raw outputs
+                           are the action), cart-pole 2 (the first maximum; a tie or a NaN gives 0), pendulum 1 (the raw output is the torque,
+                           observations are raw).  The flat vector is in creation order: per layer w [in][out] row-major, then b [out].
+                           P = dne_dense_num_params(...); dne_num_params answers -1.  dne_set_members + dne_eval_members, or dne_es_eval, run
+                           whole episodes (reset from env_seed, which the maze does not read; to the environment's own limit or tslimit) and
+                           leave the step-at-a-time batch as it was; dne_dense_final_state has the final states.  dne_stepenv_* work on the
+                           environment of reserved[0], and dne_stepenv_act / dne_stepenv_run put the policy behind them.  dne_maze_set_walls
+                           is accepted when the environment is the maze.  The P-generic calls work as on DNE_KIND_MAZE.  bc, record_bc and
+                           bc_final_only are refused, and so is every Atari, GA, maze-GA, novelty, plan, cart-pole-only, pendulum-only and
+                           mjmaze call. */
 #define DNE_OB_BYTES (84 * 84 * 4)
 #define DNE_RAM_BYTES 128
 #define DNE_BN_FLOATS 608
@@ -92,7 +106,8 @@ typedef struct {
     int32_t profile_events; /* 1: bracket hot kernels with HIP events (dne_get_profile) */
     int32_t bc_final_only;  /* ES with record_bc: keep only each member's final RAM ([members][128], what es_modified.py's
                                dumps use: bc_vec[-1], es_modified.py:176,197) instead of the whole trajectory */
-    int32_t reserved[6];    /* DNE_KIND_PENDULUM, DNE_KIND_MJMAZE: [0] hidden width, [1] action mode, [2] nonlinearity (see there); otherwise 0 */
+    int32_t reserved[6];    /* DNE_KIND_PENDULUM, DNE_KIND_MJMAZE: [0] hidden width, [1] action mode, [2] nonlinearity; DNE_KIND_DENSE: the
+                               environment, the layers, the nonlinearity and the widths (see there); otherwise 0 */
 } dne_config;
 
 typedef struct { /* filled by dne_get_profile; times from HIP events on the engine's stream */
@@ -494,6 +509,36 @@ int dne_stepenv_reset_host(int kind, int n, const uint32_t *seeds, const float *
 int dne_stepenv_step_host(int kind, int n, const void *actions, const float *header8, const float *lines, int n_walls, double *state,
                           int32_t *steps, const int32_t *limit, uint8_t *done, float *reward, float *obs);
 int dne_stepenv_observe_host(int kind, int n, const double *state, const float *header8, const float *lines, int n_walls, float *obs);
+
+/* ---- dense policies of any small shape on the step environments (DNE_KIND_DENSE; csrc/dense.h) ----
+ * dne_dense_num_params: P of a shape (widths: n_hidden entries), or -1 for a shape that is not built.
+ * dne_dense_env_kind: the environment of a DNE_KIND_DENSE engine (its reserved[0]); the kind itself on every other engine.
+ * dne_dense_final_state: the final states [n][S] of the last evaluation, in the record format of the dne_stepenv_* calls.
+ * dne_stepenv_act: the forward pass of member members[i] (0 .. members set - 1, repeats allowed; members == NULL: members[i] = indices[i])
+ * on the current observation of environment indices[i]: out [n][outputs] and the actions as dne_stepenv_step_* take them (maze float [n][2],
+ * cart-pole int32 [n], pendulum float [n]), each unless NULL.  Nothing on the device changes.
+ * dne_stepenv_run: max_steps >= 1 rounds of act -> step in ONE launch, from the batch's current state, which is written back; an
+ * environment stops when it is done (and one that was done keeps every bit).  reward_sum [n]: the float64 sum of the rewards of this call
+ * in step order, cast once; steps_taken [n]: the steps this call took; done [n]; each unless NULL.
+ * Both are refused by name, with nothing changed: on another kind, when no members are set or a member index is out of range, for
+ * max_steps < 1 (dne_stepenv_run), and for everything dne_stepenv_step_* refuses.  dne_stepenv_last_ms covers the run kernel too.
+ * dne_dense_forward_host / dne_dense_rollout_host: the same header on the CPU, no handle, no GPU, errors through dne_last_error(NULL).
+ * theta [n][P].  layers (may be NULL): per row the hidden layers' activations behind their nonlinearity, concatenated; out [n][outputs];
+ * action (may be NULL) as dne_stepenv_act's.  The rollout resets from seeds (the maze reads none) or starts from init_state [n][S], runs to the
+ * environment's own limit or tslimit and leaves returns, signreturns (may be NULL), lengths and the final state [n][S]. */
+#define DNE_DENSE_TANH 0
+#define DNE_DENSE_RELU 1
+int dne_dense_num_params(int env_kind, int n_hidden, const int32_t *widths, int n_out);
+int dne_dense_env_kind(dne_handle *h);
+int dne_dense_final_state(dne_handle *h, int n, double *state /*[n][S]*/);
+int dne_stepenv_act(dne_handle *h, int n, const int32_t *indices, const int32_t *members, float *out /*[n][O] or NULL*/, void *actions /*[n][act] or NULL*/);
+int dne_stepenv_run(dne_handle *h, int n, const int32_t *indices, const int32_t *members, int max_steps, float *reward_sum, int32_t *steps_taken,
+                    uint8_t *done);
+int dne_dense_forward_host(const float *theta, const float *obs, int n, int env_kind, int n_hidden, const int32_t *widths, int nonlin, int n_out,
+                           float *layers, float *out, void *action);
+int dne_dense_rollout_host(const float *theta, int n, int env_kind, int n_hidden, const int32_t *widths, int nonlin, int n_out, const uint32_t *seeds,
+                           const double *init_state, const float *header8, const float *lines, int n_walls, int tslimit, float *returns,
+                           float *signreturns, int32_t *lengths, double *state);
 
 /* ---- novelty on the hard maze (csrc/maze_novelty.h) -------------------------------------------
  * A behaviour characterisation is one float32 point (x, y): a navigator's final position.  nses.py:12-32 on such points: for member p and
