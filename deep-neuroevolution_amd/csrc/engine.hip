@@ -37,6 +37,7 @@
 #include "mjmaze.h"
 #include "step_env.h"
 #include "dense.h"
+#include "dense_ga.h"
 
 using namespace dne;
 
@@ -664,7 +665,8 @@ struct dne_handle {
     double mzn_last_ms = -1.0;
     // Deep-GA on the maze (csrc/maze_ga.h): 3 M slots of base_stride floats apart from `bases` -- the parents' bank as a double buffer
     // (halves of M slots, mzg_half the live one, mzg_T parents in it), then one scratch slot per member for an evaluation's roots -- and
-    // the member descriptors of dne_maze_ga_eval / dne_maze_ga_promote, apart from dne_set_members' own
+    // the member descriptors of dne_maze_ga_eval / dne_maze_ga_promote, apart from dne_set_members' own.  A DNE_KIND_DENSE handle keeps the
+    // same fields for dne_dense_ga_* (csrc/dense_ga.h: the bank with P at run time; a handle is of one kind)
     float *mzg_mem = nullptr; int mzg_half = 0, mzg_T = 0;
     int32_t *mzg_slot = nullptr; int64_t *mzg_off = nullptr; float *mzg_scale = nullptr;
     int32_t *mzg_chain_offs = nullptr; int64_t *mzg_seeds = nullptr; float *mzg_powers = nullptr; size_t mzg_chain_cap = 0;
@@ -3600,18 +3602,18 @@ static void dense_launch(dne_handle *h, int items, const dense::RunArgs &A) {
     else hipLaunchKernelGGL(dense::k_dense_run<DNE_KIND_PENDULUM>, dim3(items), dim3(64), lds, h->stream, A);
 }
 
-// what k_dense_run reads whatever it is used for: the members set by dne_set_members, the shape, the maze
-static dense::RunArgs dense_args(dne_handle *h) {
+// what k_dense_run reads whatever it is used for: the members M (dne_set_members', or the GA bank's), the shape, the maze
+static dense::RunArgs dense_args(dne_handle *h, const MazeMembers &M) {
     dense::RunArgs A{};
-    A.noise = h->noise; A.bases = h->bases; A.base_stride = h->base_stride;
-    A.m_slot = h->m_slot; A.m_off = h->m_off; A.m_scale = h->m_scale;
+    A.noise = h->noise; A.bases = M.bases; A.base_stride = h->base_stride;
+    A.m_slot = M.slot; A.m_off = M.off; A.m_scale = M.scale;
     A.shape = h->dn_shape;
     A.C = se_maze_ctx(h);
     return A;
 }
 
-// members [0, n), one whole episode each from its own reset, one launch; the step-at-a-time batch is not touched
-static int dense_eval(dne_handle *h, const char *call, int n, int tslimit, const uint32_t *env_seed, float *returns, float *signreturns,
+// members [0, n) of M, one whole episode each from its own reset, one launch; the step-at-a-time batch is not touched
+static int dense_eval(dne_handle *h, const MazeMembers &M, const char *call, int n, int tslimit, const uint32_t *env_seed, float *returns, float *signreturns,
                       int32_t *lengths, uint8_t *bc_out) {
     const bool is_maze = h->dn_shape.env == DNE_KIND_MAZE;
     if (bc_out) return h->fail("%s: behaviour characterisations are not available on a DNE_KIND_DENSE engine (kind %d): bc must be NULL; "
@@ -3622,7 +3624,7 @@ static int dense_eval(dne_handle *h, const char *call, int n, int tslimit, const
                                               h->dn_shape.env == DNE_KIND_CARTPOLE ? "cart-pole" : "pendulum");
     if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
     if (!is_maze) HCHECK(h, hipMemcpyAsync(h->seeds, env_seed, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    dense::RunArgs A = dense_args(h);
+    dense::RunArgs A = dense_args(h, M);
     A.seed = h->seeds; A.episode = 1; A.max_steps = tslimit;
     A.ret = h->ret; A.sign = h->sign; A.steps_out = h->len; A.state_out = h->dn_state;
     if (run_episodes(h, n, returns, signreturns, lengths, [&] { dense_launch(h, n, A); })) return -1;
@@ -3656,7 +3658,7 @@ static int se_dense(dne_handle *h, const char *call, bool run, int n, const int3
     const stepenv::Dims d = se_dims(h);
     HCHECK(h, hipMemcpyAsync(h->se_io_idx, idx.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HCHECK(h, hipMemcpyAsync(h->se_io_mem, mem.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    dense::RunArgs A = dense_args(h);
+    dense::RunArgs A = dense_args(h, maze_set_members(h));
     A.idx = h->se_io_idx; A.mem = h->se_io_mem; A.B = h->se; A.max_steps = run ? max_steps : 0;
     if (run) { A.ret = h->se_io_rew; A.steps_out = h->se_io_steps; A.done_out = h->se_io_done; }
     else { A.out = h->se_io_out; A.act = h->se_io_act; }
@@ -3725,13 +3727,182 @@ extern "C" int dne_dense_rollout_host(const float *theta, int n, int env_kind, i
     return 0;
 }
 
+// ------------------------------------------------------------------------------- Deep-GA on a dense policy (csrc/dense_ga.h)
+// maze_ga's bank (mzg_*: two halves of M slots and M scratch slots, the GA's own descriptors) with P = dn_shape.P at run time
+static int needs_dense(dne_handle *h, const char *call) {
+    return h->dense ? 0 : h->fail("%s needs a DNE_KIND_DENSE engine (this one: kind %d)", call, h->L.kind);
+}
+
+static dim3 dga_grid(dne_handle *h, int count) { return dim3(count, (h->dn_shape.P + 255) / 256); }
+
+extern "C" int dne_dense_ga_set_init_scale(dne_handle *h, const float *scale_by, size_t n) {
+    DeviceGuard dg(h);
+    if (needs_dense(h, "dne_dense_ga_set_init_scale")) return -1;
+    if (n != (size_t)h->dn_shape.P || !scale_by) return h->fail("dne_dense_ga_set_init_scale: expected P = %d values, got %zu", h->dn_shape.P, n);
+    if (!h->mzg_mem) {
+        const size_t M = h->M;
+        HCHECK(h, h->alloc(&h->init_scale, n, "dense_ga_init_scale"));
+        HCHECK(h, h->alloc(&h->mzg_slot, M, "dense_ga_slot")); HCHECK(h, h->alloc(&h->mzg_off, M, "dense_ga_off")); HCHECK(h, h->alloc(&h->mzg_scale, M, "dense_ga_scale"));
+        float *mem = nullptr;
+        HCHECK(h, h->alloc(&mem, 3 * M * h->base_stride, "dense_ga_bank"));
+        HCHECK(h, hipMemset(mem, 0, 3 * M * h->base_stride * sizeof(float)));
+        h->mzg_mem = mem;
+    }
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(h->init_scale, scale_by, n * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// what every call that reads the table or the bank needs first
+static int dga_ready(dne_handle *h, const char *call, bool eval) {
+    if (!h->mzg_mem) return h->fail("%s: no init scale (dne_dense_ga_set_init_scale comes first)", call);
+    if (!h->noise) return h->fail("%s: noise table not uploaded (dne_noise_upload)", call);
+    if (eval && h->dn_shape.env == DNE_KIND_MAZE && h->maze_nw < 1) return h->fail("%s: no maze loaded (dne_maze_set_walls comes before an evaluation)", call);
+    return 0;
+}
+
+extern "C" int dne_dense_ga_build(dne_handle *h, int T, const int32_t *chain_offsets, const int64_t *seeds, const float *powers) {
+    DeviceGuard dg(h);
+    if (needs_dense(h, "dne_dense_ga_build")) return -1;
+    if (dga_ready(h, "dne_dense_ga_build", false)) return -1;
+    if (T < 1 || T > h->M) return h->fail("dne_dense_ga_build: T = %d outside [1, max_members = %d]", T, h->M);
+    if (!chain_offsets || !seeds || !powers) return h->fail("dne_dense_ga_build: a buffer is missing");
+    if (chain_offsets[0] != 0) return h->fail("dne_dense_ga_build: chain_offsets starts at %d, not 0", chain_offsets[0]);
+    const int P = h->dn_shape.P;
+    const std::string bad = dense_ga::check_genomes(T, P, chain_offsets, seeds, h->noise_count);
+    if (!bad.empty()) return h->fail("dne_dense_ga_build: %s", bad.c_str());
+    const size_t total = (size_t)chain_offsets[T];
+    if (total > h->mzg_chain_cap || !h->mzg_chain_offs) {
+        HCHECK(h, hipStreamSynchronize(h->stream));
+        HCHECK(h, h->release(h->mzg_chain_offs)); HCHECK(h, h->release(h->mzg_seeds)); HCHECK(h, h->release(h->mzg_powers));
+        h->mzg_chain_cap = std::max<size_t>(2 * total, 4096);
+        HCHECK(h, h->alloc(&h->mzg_chain_offs, (size_t)h->M + 1, "dense_ga_chain_offs"));
+        HCHECK(h, h->alloc(&h->mzg_seeds, h->mzg_chain_cap, "dense_ga_seeds")); HCHECK(h, h->alloc(&h->mzg_powers, h->mzg_chain_cap, "dense_ga_powers"));
+    }
+    HCHECK(h, hipMemcpyAsync(h->mzg_chain_offs, chain_offsets, ((size_t)T + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HCHECK(h, hipMemcpyAsync(h->mzg_seeds, seeds, total * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    HCHECK(h, hipMemcpyAsync(h->mzg_powers, powers, total * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    const int other = 1 - h->mzg_half;
+    hipLaunchKernelGGL(dense_ga::k_dense_ga_build, dga_grid(h, T), dim3(256), 0, h->stream, (const float *)h->noise, (const float *)h->init_scale, P,
+                       (const int32_t *)h->mzg_chain_offs, (const int64_t *)h->mzg_seeds, (const float *)h->mzg_powers, mzg_bank(h, other), h->base_stride);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipStreamSynchronize(h->stream));   // the caller's arrays may go away
+    h->mzg_half = other; h->mzg_T = T;
+    return 0;
+}
+
+extern "C" int dne_dense_ga_promote(dne_handle *h, int T_new, const int32_t *parent, const int64_t *idx, const float *power) {
+    DeviceGuard dg(h);
+    if (needs_dense(h, "dne_dense_ga_promote")) return -1;
+    if (dga_ready(h, "dne_dense_ga_promote", false)) return -1;
+    if (T_new < 1 || T_new > h->M) return h->fail("dne_dense_ga_promote: T = %d outside [1, max_members = %d]", T_new, h->M);
+    if (!parent || !idx || !power) return h->fail("dne_dense_ga_promote: a buffer is missing");
+    const int P = h->dn_shape.P;
+    for (int j = 0; j < T_new; j++) {
+        const std::string bad = dense_ga::check_member(j, h->mzg_T, P, h->noise_count, parent[j], idx[j], true);
+        if (!bad.empty()) return h->fail("dne_dense_ga_promote: %s", bad.c_str());
+    }
+    if (mzg_upload_members(h, T_new, parent, idx, power)) return -1;
+    const int other = 1 - h->mzg_half;
+    hipLaunchKernelGGL(dense_ga::k_dense_ga_promote, dga_grid(h, T_new), dim3(256), 0, h->stream, (const float *)h->noise, (const float *)h->init_scale, P,
+                       (const float *)mzg_bank(h, h->mzg_half), mzg_bank(h, other), h->base_stride, (const int32_t *)h->mzg_slot,
+                       (const int64_t *)h->mzg_off, (const float *)h->mzg_scale);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    h->mzg_half = other; h->mzg_T = T_new;
+    return 0;
+}
+
+extern "C" int dne_dense_ga_eval(dne_handle *h, int n, const int32_t *parent, const int64_t *idx, const float *power, const uint32_t *env_seed, int tslimit,
+                                 float *returns, float *signreturns, int32_t *lengths) {
+    DeviceGuard dg(h);
+    if (needs_dense(h, "dne_dense_ga_eval")) return -1;
+    if (dga_ready(h, "dne_dense_ga_eval", true)) return -1;
+    if (n < 1 || n > h->M) return h->fail("dne_dense_ga_eval: n = %d outside [1, max_members = %d]", n, h->M);
+    if (!parent || !idx || !power || !returns || !lengths) return h->fail("dne_dense_ga_eval: a buffer is missing");
+    if (tslimit <= 0) return h->fail("dne_dense_ga_eval: timestep limit must be positive");
+    if (h->dn_shape.env != DNE_KIND_MAZE && !env_seed)
+        return h->fail("dne_dense_ga_eval: a DNE_KIND_DENSE engine on the %s resets every member from its environment seed, env_seed is NULL",
+                       h->dn_shape.env == DNE_KIND_CARTPOLE ? "cart-pole" : "pendulum");
+    // a child is k_dense_run's own member: (its parent's bank slot, idx, power); a root runs from scratch slot 2 M + i at scale 0
+    const int P = h->dn_shape.P, bank0 = h->mzg_half * h->M, root0 = 2 * h->M;
+    std::vector<int32_t> &slot = h->mzg_host_slot;
+    std::vector<float> &scale = h->mzg_host_scale;
+    slot.resize(n); scale.resize(n);
+    bool roots = false;
+    for (int i = 0; i < n; i++) {
+        const std::string bad = dense_ga::check_member(i, h->mzg_T, P, h->noise_count, parent[i], idx[i], false);
+        if (!bad.empty()) return h->fail("dne_dense_ga_eval: %s", bad.c_str());
+        const bool root = parent[i] < 0;
+        slot[i] = root ? root0 + i : bank0 + parent[i];
+        scale[i] = root ? 0.0f : power[i];
+        roots = roots || root;
+    }
+    if (mzg_upload_members(h, n, slot.data(), idx, scale.data())) return -1;
+    if (roots) {
+        hipLaunchKernelGGL(dense_ga::k_dense_ga_roots, dga_grid(h, n), dim3(256), 0, h->stream, (const float *)h->noise, (const float *)h->init_scale, P,
+                           (const int32_t *)h->mzg_slot, (const int64_t *)h->mzg_off, root0, h->mzg_mem, h->base_stride);
+        HCHECK(h, hipGetLastError());
+    }
+    return dense_eval(h, MazeMembers{h->mzg_mem, h->mzg_slot, h->mzg_off, h->mzg_scale}, "dne_dense_ga_eval", n, tslimit, env_seed, returns, signreturns,
+                      lengths, nullptr);
+}
+
+extern "C" int dne_dense_ga_parents(dne_handle *h) {
+    if (needs_dense(h, "dne_dense_ga_parents")) return -1;
+    return h->mzg_T;
+}
+
+extern "C" int dne_dense_ga_get_parent(dne_handle *h, int j, float *out) {
+    DeviceGuard dg(h);
+    if (needs_dense(h, "dne_dense_ga_get_parent")) return -1;
+    if (j < 0 || j >= h->mzg_T) return h->fail("dne_dense_ga_get_parent: parent %d, the bank holds %d", j, h->mzg_T);
+    if (!out) return h->fail("dne_dense_ga_get_parent: no output buffer");
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(out, mzg_bank(h, h->mzg_half) + (size_t)j * h->base_stride, (size_t)h->dn_shape.P * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the same header on the CPU: no handle, no GPU
+static int dga_host_table(const char *call, const float *noise, size_t count, const float *scale_by, int P) {
+    if (P < 1 || P > dense::MAX_P) { g_create_error = std::string(call) + ": P = " + std::to_string(P) + " outside [1, " + std::to_string(dense::MAX_P) + "]"; return -1; }
+    if (!noise || !scale_by) { g_create_error = std::string(call) + ": a buffer is missing"; return -1; }
+    if (count < (size_t)P) { g_create_error = std::string(call) + ": a table of " + std::to_string(count) + " floats holds no P = " + std::to_string(P) + " parameters"; return -1; }
+    return 0;
+}
+
+extern "C" int dne_dense_ga_theta_host(const float *noise, size_t count, const float *scale_by, int P, const int64_t *seeds, const float *powers, int nseeds,
+                                       float *out) {
+    if (dga_host_table("dne_dense_ga_theta_host", noise, count, scale_by, P)) return -1;
+    if (!seeds || !powers || !out) { g_create_error = "dne_dense_ga_theta_host: a buffer is missing"; return -1; }
+    const int32_t co[2] = {0, nseeds};
+    const std::string bad = dense_ga::check_genomes(1, P, co, seeds, count);
+    if (!bad.empty()) { g_create_error = "dne_dense_ga_theta_host: " + bad; return -1; }
+    dense_ga::genome_host(noise, scale_by, P, seeds, powers, nseeds, out);
+    return 0;
+}
+
+extern "C" int dne_dense_ga_members_host(const float *noise, size_t count, const float *scale_by, int P, const float *bank, int T, const int32_t *parent,
+                                         const int64_t *idx, const float *power, int n, float *out) {
+    if (dga_host_table("dne_dense_ga_members_host", noise, count, scale_by, P)) return -1;
+    if (n < 1) { g_create_error = "dne_dense_ga_members_host: n = " + std::to_string(n) + ", at least one member is needed"; return -1; }
+    if (T < 0 || (T > 0 && !bank)) { g_create_error = "dne_dense_ga_members_host: T = " + std::to_string(T) + " parents without a bank"; return -1; }
+    if (!parent || !idx || !power || !out) { g_create_error = "dne_dense_ga_members_host: a buffer is missing"; return -1; }
+    for (int i = 0; i < n; i++) {
+        const std::string bad = dense_ga::check_member(i, T, P, count, parent[i], idx[i], true);
+        if (!bad.empty()) { g_create_error = "dne_dense_ga_members_host: " + bad; return -1; }
+    }
+    dense_ga::members_host(noise, scale_by, P, bank, parent, idx, power, n, out);
+    return 0;
+}
+
 // ------------------------------------------------------------------------------- evaluations by descriptor: antithetic pairs, members as set
 // the members set by dne_set_members through the whole-episode kernel of the engine's kind (the maze's episode is deterministic and mjmaze's has no
 // reset seed: neither reads env_seed)
 static int episodic_eval(dne_handle *h, const char *call, int n, int tslimit, const uint32_t *env_seed, float *returns, float *signreturns,
                          int32_t *lengths, uint8_t *bc) {
     if (h->maze) return maze_eval_members(h, maze_set_members(h), n, tslimit, returns, signreturns, lengths, bc);
-    if (h->dense) return dense_eval(h, call, n, tslimit, env_seed, returns, signreturns, lengths, bc);
+    if (h->dense) return dense_eval(h, maze_set_members(h), call, n, tslimit, env_seed, returns, signreturns, lengths, bc);
     if (h->cartpole) return cartpole_eval(h, call, n, tslimit, env_seed, returns, signreturns, lengths, bc);
     if (h->pendulum) return pendulum_eval(h, call, n, tslimit, env_seed, returns, signreturns, lengths, bc);
     return mjmaze_eval(h, call, n, tslimit, returns, signreturns, lengths, bc);

@@ -88,7 +88,7 @@ class Profile(C.Structure):
 
 def build(force=False):
     """Compile libdne_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h", "cartpole.h", "pendulum.h", "mjmaze.h", "step_env.h", "dense.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h", "cartpole.h", "pendulum.h", "mjmaze.h", "step_env.h", "dense.h", "dense_ga.h")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dne_hip.h"))
     if os.environ.get("DNE_LIB_PATH"):
         # another build of the same ABI was asked for by name: `make` only knows the in-tree library, so running it here would
@@ -668,6 +668,32 @@ def dense_rollout_host(theta, env_kind, hidden, nonlin, n_out, seeds=None, tslim
     return dict(returns=ret, signreturns=sign, lengths=ln, state=state)
 
 
+# ---- Deep-GA on a dense policy (csrc/dense_ga.h): maze_ga's twins with P a parameter ---------------------------------------------------------------
+def dense_ga_theta_host(noise, scale_by, genome):
+    """dne_dense_ga_theta_host: csrc/dense_ga.h on the CPU (no GPU, no handle): theta [P] of one genome (idx0, (idx1, power1), ...); P is
+    scale_by's length"""
+    noise = _arr(noise, np.float32).reshape(-1); scale_by = _arr(scale_by, np.float32).reshape(-1)
+    idx, pw = split_genome(genome)
+    out = np.empty(scale_by.size, np.float32)
+    _ck_host(load().dne_dense_ga_theta_host(_ptr(noise, C.c_float), C.c_size_t(noise.size), _ptr(scale_by, C.c_float), int(scale_by.size),
+                                            _ptr(idx, C.c_int64), _ptr(pw, C.c_float), int(idx.size), _ptr(out, C.c_float)))
+    return out
+
+
+def dense_ga_members_host(noise, scale_by, bank, parent, idx, power):
+    """dne_dense_ga_members_host: the theta [n][P] of n member descriptors (parent, idx, power) against a host bank [T][P] (None: empty):
+    parent -1 a root, idx < 0 the parent itself, otherwise bank[parent] + fl(power * noise[idx:idx + P]); P is scale_by's length"""
+    noise = _arr(noise, np.float32).reshape(-1); scale_by = _arr(scale_by, np.float32).reshape(-1)
+    P = int(scale_by.size)
+    bank = np.zeros((0, max(P, 1)), np.float32) if bank is None else _arr(bank, np.float32).reshape(-1, max(P, 1))
+    parent, idx, power = _maze_ga_members(parent, idx, power)
+    out = np.empty((parent.size, P), np.float32)
+    _ck_host(load().dne_dense_ga_members_host(_ptr(noise, C.c_float), C.c_size_t(noise.size), _ptr(scale_by, C.c_float), P,
+                                              _ptr(bank, C.c_float) if bank.shape[0] else None, int(bank.shape[0]), _ptr(parent, C.c_int32),
+                                              _ptr(idx, C.c_int64), _ptr(power, C.c_float), int(parent.size), _ptr(out, C.c_float)))
+    return out
+
+
 def _ptr(a, t):
     return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
 
@@ -1198,14 +1224,20 @@ class Engine:
         sb = _arr(scale_by, np.float32)
         self._ck(self.lib.dne_maze_ga_set_init_scale(self.h, _ptr(sb, C.c_float), C.c_size_t(sb.size)))
 
-    def maze_ga_build(self, genomes):
-        """the bank = these genomes' thetas, parent j from genomes[j] = (idx0, (idx1, power1), ...)"""
+    @staticmethod
+    def _pack_genomes(genomes):
+        """(T, chain_offsets int32 [T + 1], indices int64, powers float32) of genomes (idx0, (idx1, power1), ...)"""
         T = len(genomes)
         co = np.zeros(T + 1, np.int32)
         parts = [split_genome(g) for g in genomes]
         co[1:] = np.cumsum([p[0].size for p in parts])
         flat = _arr(np.concatenate([p[0] for p in parts]) if parts else np.zeros(0), np.int64)
         pw = _arr(np.concatenate([p[1] for p in parts]) if parts else np.zeros(0), np.float32)
+        return T, co, flat, pw
+
+    def maze_ga_build(self, genomes):
+        """the bank = these genomes' thetas, parent j from genomes[j] = (idx0, (idx1, power1), ...)"""
+        T, co, flat, pw = self._pack_genomes(genomes)
         self._ck(self.lib.dne_maze_ga_build(self.h, T, _ptr(co, C.c_int32), _ptr(flat, C.c_int64), _ptr(pw, C.c_float)))
 
     def maze_ga_eval(self, parent, idx, power, tslimit=MAZE_STEPS):
@@ -1232,6 +1264,46 @@ class Engine:
     def maze_ga_get_parent(self, j):
         out = np.empty(self.P, np.float32)
         self._ck(self.lib.dne_maze_ga_get_parent(self.h, int(j), _ptr(out, C.c_float)))
+        return out
+
+    # ---- Deep-GA on a dense policy (csrc/dense_ga.h): the same surface on a KIND_DENSE engine of any shape, P the engine's
+    def dense_ga_set_init_scale(self, scale_by):
+        sb = _arr(scale_by, np.float32)
+        self._ck(self.lib.dne_dense_ga_set_init_scale(self.h, _ptr(sb, C.c_float), C.c_size_t(sb.size)))
+
+    def dense_ga_build(self, genomes):
+        """the bank = these genomes' thetas, parent j from genomes[j] = (idx0, (idx1, power1), ...)"""
+        T, co, flat, pw = self._pack_genomes(genomes)
+        self._ck(self.lib.dne_dense_ga_build(self.h, T, _ptr(co, C.c_int32), _ptr(flat, C.c_int64), _ptr(pw, C.c_float)))
+
+    def dense_ga_eval(self, parent, idx, power, tslimit, env_seed=None):
+        """one episode per member (parent -1: a root at idx; otherwise bank[parent] + fl(power * noise[idx])), member i reset from env_seed[i]
+        (the cart-pole and the pendulum need it; the maze reads none) -> (returns, signs, lengths)"""
+        parent, idx, power = _maze_ga_members(parent, idx, power)
+        n = parent.size
+        seeds = None if env_seed is None else _arr(env_seed, np.uint32).reshape(-1)
+        if seeds is not None and seeds.size != n:
+            raise DneError("dense_ga_eval: %d members, %d environment seeds" % (n, seeds.size))
+        ret = np.empty(n, np.float32); sg = np.empty(n, np.float32); ln = np.empty(n, np.int32)
+        self._ck(self.lib.dne_dense_ga_eval(self.h, n, _ptr(parent, C.c_int32), _ptr(idx, C.c_int64), _ptr(power, C.c_float), _ptr(seeds, C.c_uint32),
+                                            int(tslimit), _ptr(ret, C.c_float), _ptr(sg, C.c_float), _ptr(ln, C.c_int32)))
+        self._last_eval_n = n
+        return ret, sg, ln
+
+    def dense_ga_promote(self, parent, idx, power):
+        """new parent j = the theta of descriptor j over the bank as it is (idx < 0: parent[j] itself), all at once"""
+        parent, idx, power = _maze_ga_members(parent, idx, power)
+        self._ck(self.lib.dne_dense_ga_promote(self.h, int(parent.size), _ptr(parent, C.c_int32), _ptr(idx, C.c_int64), _ptr(power, C.c_float)))
+
+    def dense_ga_parents(self):
+        n = self.lib.dne_dense_ga_parents(self.h)
+        if n < 0:
+            self._ck(n)
+        return n
+
+    def dense_ga_get_parent(self, j):
+        out = np.empty(self.P, np.float32)
+        self._ck(self.lib.dne_dense_ga_get_parent(self.h, int(j), _ptr(out, C.c_float)))
         return out
 
     # ---- gpu-tree genomes: ((idx0,), (idx1, power1), ...)

@@ -16,8 +16,14 @@ evaluates as it stands, selected children become parents device to device (dne_m
 few individuals that survive a generation.  SimpleClassifier on an Atari game and the Atari models on the maze are refused.
 With exp['novelty_search'] = {'k': ..., 'archive_prob': ...} the maze loop is GA-NS (maze_ns_main): the same GA selecting on novelty against the
 archive and the current population, scored on the device (k_maze_novelty_pool).  The key on an Atari game is refused.
-The three loops share what is the same in them as plain functions (_validate_and_test, _record_rows, _end_generation; the two maze loops also
-_open_maze_run, _resume_maze, _draw_generation, _member, _promote); the engine, walls and noise table come from maze_run.open_engine.
+A dense policy of any small shape on the maze or the cart-pole runs dense_main on a DNE_KIND_DENSE engine (csrc/dense_ga.h, DESIGN.md section
+17a): exp['model'] == 'LinearClassifier' on 'maze' or 'gym.CartPole-v1', 'SimpleClassifier' on 'gym.CartPole-v1' (hidden (16, 16): the GPU tree's
+gym configuration), or a caller's engine of kind KIND_DENSE of any shape on its environment's game.  It is maze_main's loop -- _bank_loop, one text
+for both -- on dense_ga_build / dense_ga_eval / dense_ga_promote; selection_threshold 0 is random search.  Every other kind of engine with these
+models or games is refused as before.
+The loops share what is the same in them as plain functions (_validate_and_test, _record_rows, _end_generation; the bank loops also
+_resume_maze, _draw_generation, _member, _promote, _bank_evaluate; maze_main and dense_main the whole _bank_loop); the maze's engine, walls and
+noise table come from maze_run.open_engine.
 """
 import math
 import numbers
@@ -267,6 +273,8 @@ def _end_generation(state, log_dir, lens, rs=None):
 def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
     """gpu_implementation/ga.py:114-275.  Returns (curr_solution_test, {'val': curr_solution_val}, state)."""
     maze, asked = exp.get('game') == 'maze', exp.get('model', 'Model')
+    if _is_dense_run(engine, exp):                                  # a dense policy on a step environment: the bank of csrc/dense_ga.h
+        return dense_main(log_dir, engine=engine, noise=noise, seed=seed, max_iters=max_iters, **exp)
     if maze != (asked == MAZE_MODEL):                               # ga.py:110-114 takes any pair; the engine has these
         raise NotImplementedError("model {!r} on game {!r}: {!r} runs on game 'maze' only, and 'maze' runs nothing else".format(
             asked, exp.get('game'), MAZE_MODEL))
@@ -337,13 +345,42 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
 KEPT = -1          # a descriptor's noise index that means "the parent itself" (dne_maze_ga_promote)
 
 
-def _maze_evaluate(engine, members, tslimit):
+class _MazeBank(object):
+    """the device bank of a KIND_MAZE engine as the loops below call it: build(genomes), promote(parent, idx, power) and
+    eval(parent, idx, power, tslimit) -> (returns, lengths), tslimit None meaning the environment's own limit"""
+
+    def __init__(self, engine):
+        self.engine, self.max_members = engine, engine.max_members
+        self.build, self.promote = engine.maze_ga_build, engine.maze_ga_promote
+
+    def eval(self, parent, idx, power, tslimit):
+        ret, _, ln = self.engine.maze_ga_eval(parent, idx, power, step_limit(tslimit))
+        return ret, ln
+
+
+class _DenseBank(object):
+    """the same three calls on a KIND_DENSE engine (dense_ga_*).  On the cart-pole every eval draws its members' environment seeds from rs,
+    after whatever its caller drew; on the maze nothing is drawn"""
+
+    def __init__(self, engine, rs):
+        self.engine, self.max_members, self.rs = engine, engine.max_members, rs
+        self.build, self.promote = engine.dense_ga_build, engine.dense_ga_promote
+        self.own = _lib.MAZE_STEPS if engine.env_kind == _lib.KIND_MAZE else _lib.CARTPOLE_STEPS
+
+    def eval(self, parent, idx, power, tslimit):
+        seeds = None
+        if self.engine.env_kind != _lib.KIND_MAZE:
+            seeds = self.rs.randint(0, 2 ** 32, size=len(parent), dtype=np.uint64).astype(np.uint32)
+        ret, _, ln = self.engine.dense_ga_eval(parent, idx, power, self.own if tslimit is None else min(int(tslimit), self.own), seeds)
+        return ret, ln
+
+
+def _bank_evaluate(bank, members, tslimit):
     """(returns, lengths) of one episode per (parent, idx, power) member, in calls of at most max_members"""
-    limit = step_limit(tslimit)
     out_r, out_l = [], []
-    for s in range(0, len(members), engine.max_members):
-        parent, idx, power = zip(*members[s:s + engine.max_members])
-        ret, _, ln = engine.maze_ga_eval(np.array(parent, np.int32), np.array(idx, np.int64), np.array(power, np.float32), limit)
+    for s in range(0, len(members), bank.max_members):
+        parent, idx, power = zip(*members[s:s + bank.max_members])
+        ret, ln = bank.eval(np.array(parent, np.int32), np.array(idx, np.int64), np.array(power, np.float32), tslimit)
         out_r.append(ret); out_l.append(ln)
     return np.concatenate(out_r), np.concatenate(out_l)
 
@@ -356,9 +393,10 @@ def _open_maze_run(log_dir, engine, noise, seed, exp):
     return engine, noise, np.random.RandomState(seed)
 
 
-def _resume_maze(log_dir, algo, rs):
-    """ga.py:135-143 for a maze GA run of `algo`: the state in log_dir's snapshot.pkl with the position of its stream restored into rs, or
-    None if there is no such file.  A snapshot of another driver, game or model is refused, naming both."""
+def _resume_maze(log_dir, algo, rs, game='maze', model=MAZE_MODEL, P=None):
+    """ga.py:135-143 for a bank GA run of `algo` (the maze loops; dense_main with its game, model and P): the state in log_dir's snapshot.pkl
+    with the position of its stream restored into rs, or None if there is no such file.  A snapshot of another driver, game, model or P is
+    refused, naming both."""
     try:
         with open(os.path.join(log_dir, 'snapshot.pkl'), 'rb') as file:
             state = pickle.load(file)
@@ -369,9 +407,12 @@ def _resume_maze(log_dir, algo, rs):
     if was_algo != algo:
         raise ValueError("snapshot.pkl in {} was written by {!r}; this run is {!r}".format(log_dir, was_algo, algo))
     was = (getattr(state, 'game', None) or 'an Atari game', getattr(state, 'model', 'Model'))
-    if was != ('maze', MAZE_MODEL):
-        raise ValueError("snapshot.pkl in {} holds game {!r} under model {!r}; this run is game 'maze' under model {!r}".format(
-            log_dir, was[0], was[1], MAZE_MODEL))
+    if was != (game, model):
+        raise ValueError("snapshot.pkl in {} holds game {!r} under model {!r}; this run is game {!r} under model {!r}".format(
+            log_dir, was[0], was[1], game, model))
+    if P is not None and getattr(state, 'num_params', None) != P:
+        raise ValueError("snapshot.pkl in {} holds model {!r} with P = {}; this run is model {!r} with P = {}".format(
+            log_dir, was[1], getattr(state, 'num_params', None), model, P))
     if getattr(state, 'stream', None) is not None:
         rs.set_state(state.stream)
     return state
@@ -391,46 +432,22 @@ def _member(i, of, idx, power, parents):
     return (int(of[i]), int(idx[i]), float(power)), tuple(parents[of[i]]) + ((int(idx[i]), power), )
 
 
-def _promote(engine, descriptors):
-    """the next bank from descriptors over this one, device to device"""
-    engine.maze_ga_promote(*(np.array(c, t) for c, t in zip(zip(*descriptors), (np.int32, np.int64, np.float32))))
+def _promote(promote, descriptors):
+    """the next bank from descriptors over this one, device to device; promote is the engine's call (maze_ga_promote, dense_ga_promote)"""
+    promote(*(np.array(c, t) for c, t in zip(zip(*descriptors), (np.int32, np.int64, np.float32))))
 
 
-def maze_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
-    """gpu_implementation/ga.py:114-275 with game 'maze' and model 'SimpleClassifier'.  Returns (curr_solution_test, {'val': ...}, state).
-
-    A generation's member i is the triple (parent p_i, noise index idx_i, power) over the device's bank of T parents -- a root (-1, idx_i)
-    while there are none -- so a generation is ONE maze_ga_eval of three small arrays.  Its genome, parents[p_i] + ((idx_i, power),), is only
-    written out for the top max(selection_threshold, validation_threshold) and the elite: state.population holds just those (the reference
-    reads no more of it, ga.py:150-154, 188).  The next parents are made on the device from this generation's descriptors by one
-    maze_ga_promote (a retained elite as the kept form); maze_ga_build from whole genomes runs once per call of main: for the first
-    bank after generation 0, or before the loop when load_population or a snapshot brought a population.
-    Decisions of ours: the reference's stream is unseeded (ga.py:117) and drawn from one offspring at a time; here a generation takes
-    rs.randint(T, size=n) for the parents (if there are any), then rs.randint(0, len(noise) - P + 1, size=n) for the indices, as two
-    whole-array draws from RandomState(seed), and no environment seeds (the episode is deterministic).  The stream's position is kept in
-    snapshot.pkl with game, model and algo = 'ga', so a resumed run continues bit for bit; a resume under another game or model, or from
-    a snapshot of es_gpu.main / nses_gpu.main, raises and names both.  A previous elite is evaluated again as (its bank index, idx 0,
-    power 0): the child formula, bank + fl(0 * noise).  The elite's test episodes are num_test_episodes identical deterministic episodes
-    at the 400-step default, as the reference runs them.  num_frames counts steps (the maze has no frame skip).
-    maze_ns_main below is the same scaffold (the _helpers above) around another selection."""
-    if NS_KEY in exp:
-        return maze_ns_main(log_dir, engine=engine, noise=noise, seed=seed, max_iters=max_iters, **exp)
+def _bank_loop(log_dir, exp, state, bank, engine, rs, indices, max_iters, all_tstart):
+    """maze_main's and dense_main's generations over a device bank (their docstrings say what one is): state is the run's TrainingState, bank
+    a _MazeBank or _DenseBank, indices the number of admissible noise indices.  Returns what main returns."""
     n, T, V = exp['population_size'], exp['selection_threshold'], exp['validation_threshold']
-    engine, noise, rs = _open_maze_run(log_dir, engine, noise, seed, exp)
-    all_tstart = time.time()
-    state = _resume_maze(log_dir, ALGO, rs)
-    if state is None:
-        state = TrainingState(exp)
-    state.game, state.model, state.algo = 'maze', MAZE_MODEL, ALGO
-    if 'load_population' in exp:
-        state.copy_population(exp['load_population'])
     parents = parents_of(state, T)                                  # the genomes of the bank's parents, kept beside it
     if parents:
-        engine.maze_ga_build(parents)
+        bank.build(parents)
     descriptor = {}                                                 # id(Offspring) -> its descriptor over the bank as it is now
 
     def evaluate(individuals, tslimit):
-        return _maze_evaluate(engine, [descriptor[id(o)] for o in individuals], tslimit)
+        return _bank_evaluate(bank, [descriptor[id(o)] for o in individuals], tslimit)
 
     iters = 0
     while max_iters is None or iters < max_iters:
@@ -440,8 +457,8 @@ def maze_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
             break
         assert (len(parents) == 0 and state.it == 0) or len(parents) == T
         power = state.sample(state.mutation_power)
-        of, idx = _draw_generation(rs, n, len(parents), len(noise.noise) - engine.P + 1)
-        rets, _, lens = engine.maze_ga_eval(of, idx, np.full(n, power, np.float32), step_limit(state.tslimit))
+        of, idx = _draw_generation(rs, n, len(parents), indices)
+        rets, lens = bank.eval(of, idx, np.full(n, power, np.float32), state.tslimit)
         state.num_frames += int(lens.sum())
         state.it += 1
         rewards = np.asarray(rets, np.float64)
@@ -472,17 +489,122 @@ def maze_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
         # ga.py:261-274 on the device: the next parents from this generation's descriptors, the retained elite as it stands
         new_parents = parents_of(state, T)
         if new_parents and not parents:                             # the start: generation 0's roots become the first bank
-            engine.maze_ga_build(new_parents)
+            bank.build(new_parents)
         elif new_parents:
             by_genome = {o.seeds: descriptor[id(o)] for o in state.population}
             if old_elite is not None and state.elite is old_elite and state.elite.seeds in parents:
                 by_genome[state.elite.seeds] = (parents.index(state.elite.seeds), KEPT, 0.0)
-            _promote(engine, [by_genome[g] for g in new_parents])
+            _promote(bank.promote, [by_genome[g] for g in new_parents])
         parents = new_parents
         _end_generation(state, log_dir, lens, rs)
         if state.timesteps_so_far >= exp['timesteps']:
             break
     return float(state.curr_solution_test), {'val': float(state.curr_solution_val)}, state
+
+
+def maze_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
+    """gpu_implementation/ga.py:114-275 with game 'maze' and model 'SimpleClassifier'.  Returns (curr_solution_test, {'val': ...}, state).
+
+    A generation's member i is the triple (parent p_i, noise index idx_i, power) over the device's bank of T parents -- a root (-1, idx_i)
+    while there are none -- so a generation is ONE maze_ga_eval of three small arrays.  Its genome, parents[p_i] + ((idx_i, power),), is only
+    written out for the top max(selection_threshold, validation_threshold) and the elite: state.population holds just those (the reference
+    reads no more of it, ga.py:150-154, 188).  The next parents are made on the device from this generation's descriptors by one
+    maze_ga_promote (a retained elite as the kept form); maze_ga_build from whole genomes runs once per call of main: for the first
+    bank after generation 0, or before the loop when load_population or a snapshot brought a population.
+    Decisions of ours: the reference's stream is unseeded (ga.py:117) and drawn from one offspring at a time; here a generation takes
+    rs.randint(T, size=n) for the parents (if there are any), then rs.randint(0, len(noise) - P + 1, size=n) for the indices, as two
+    whole-array draws from RandomState(seed), and no environment seeds (the episode is deterministic).  The stream's position is kept in
+    snapshot.pkl with game, model and algo = 'ga', so a resumed run continues bit for bit; a resume under another game or model, or from
+    a snapshot of es_gpu.main / nses_gpu.main, raises and names both.  A previous elite is evaluated again as (its bank index, idx 0,
+    power 0): the child formula, bank + fl(0 * noise).  The elite's test episodes are num_test_episodes identical deterministic episodes
+    at the 400-step default, as the reference runs them.  num_frames counts steps (the maze has no frame skip).
+    maze_ns_main below is the same scaffold (the _helpers above) around another selection."""
+    if NS_KEY in exp:
+        return maze_ns_main(log_dir, engine=engine, noise=noise, seed=seed, max_iters=max_iters, **exp)
+    engine, noise, rs = _open_maze_run(log_dir, engine, noise, seed, exp)
+    all_tstart = time.time()
+    state = _resume_maze(log_dir, ALGO, rs)
+    if state is None:
+        state = TrainingState(exp)
+    state.game, state.model, state.algo = 'maze', MAZE_MODEL, ALGO
+    if 'load_population' in exp:
+        state.copy_population(exp['load_population'])
+    return _bank_loop(log_dir, exp, state, _MazeBank(engine), engine, rs, len(noise.noise) - engine.P + 1, max_iters, all_tstart)
+
+
+# ---------------------------------------------------------------------------------------------- a dense policy on a step environment
+DENSE_SIMPLE_HIDDEN = (16, 16)           # SimpleClassifier as a dense shape (models/simple.py:29-35): on the cart-pole csrc/cartpole.h's layout, P = 386
+
+
+def _is_dense_run(engine, exp):
+    """main's routing: a caller's KIND_DENSE engine always; without an engine LinearClassifier on the maze or the cart-pole and
+    SimpleClassifier on the cart-pole.  An engine of another kind is never a dense run (main refuses it as it always did)."""
+    from .es_gpu import CARTPOLE_GAME, LINEAR_MODEL
+    if engine is not None:
+        return engine.kind == _lib.KIND_DENSE
+    game, asked = exp.get('game'), exp.get('model')
+    return (asked == LINEAR_MODEL and game in ('maze', CARTPOLE_GAME)) or (asked == MAZE_MODEL and game == CARTPOLE_GAME)
+
+
+def dense_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
+    """gpu_implementation/ga.py:114-275 over a dense policy of any small shape on the maze or the cart-pole (a DNE_KIND_DENSE engine,
+    csrc/dense_ga.h): maze_main's loop (_bank_loop) on dense_ga_build / dense_ga_eval / dense_ga_promote.  Returns what main returns.
+
+    The engine: a caller's KIND_DENSE engine of any shape, on its environment's game (es_gpu.DENSE_GAMES; another game, or a model name that
+    is not es_gpu.dense_model_name(engine), is a ValueError naming both; the pendulum is not built); without one, exp['model'] ==
+    'LinearClassifier' opens an engine with no hidden layer on 'maze' or 'gym.CartPole-v1', and 'SimpleClassifier' on 'gym.CartPole-v1' one of
+    hidden (16, 16), relu -- the GPU tree's gym configuration under GA.  The init scale is policies.dense_scale_by of the shape.
+    Lazy genomes, one build per call, promotion with the kept form and selection_threshold == 0 (roots every generation, an empty bank:
+    random search) are maze_main's, word for word.  Decisions of ours:
+      draws        parents and indices are maze_main's two whole-array draws.  On the maze no environment seed is drawn: the stream is
+                   maze_main's, so a (16, 16) relu engine on the maze writes the rows maze_main writes.  On the cart-pole EVERY evaluation
+                   call -- a generation, each call of the validation episodes, the test episodes -- draws
+                   rs.randint(0, 2**32, size=n, dtype=np.uint64).astype(np.uint32) for its n members after the two draws, so each
+                   validation and test episode is a different episode.
+      limits       a generation and the validation episodes run under state.tslimit, at most the environment's own limit; the elite's
+                   test episodes at the environment's own limit (maze 400, cart-pole 500).
+      counters     num_frames counts steps (no frame skip).
+      snapshot     game, model (es_gpu.dense_model_name(engine), or 'SimpleClassifier' for the (16, 16) cart-pole route), algo = 'ga',
+                   num_params = P and the stream's position; a resume continues bit for bit.  A resume under another game, model, P or
+                   driver raises and names both.
+    exp['novelty_search'] is not built for a dense run (the archive calls are DNE_KIND_MAZE's)."""
+    from .es_gpu import CARTPOLE_GAME, DENSE_GAMES, LINEAR_MODEL, dense_model_name
+    from .maze_run import attach_table, maze_file
+    if NS_KEY in exp:
+        raise NotImplementedError("exp[{!r}] with a dense policy: GA-NS runs on game 'maze' under model {!r} only".format(NS_KEY, MAZE_MODEL))
+    game, asked = exp.get('game'), exp.get('model')
+    if engine is None:
+        if not _is_dense_run(None, exp):
+            raise NotImplementedError("model {!r} on game {!r}: without an engine dense_main runs {!r} on 'maze' and {!r}, and {!r} on {!r}".format(
+                asked, game, LINEAR_MODEL, CARTPOLE_GAME, MAZE_MODEL, CARTPOLE_GAME))
+        model = asked
+        engine = _lib.Engine(_lib.KIND_DENSE, 2, max_members=exp['population_size'], env=_lib.KIND_MAZE if game == 'maze' else _lib.KIND_CARTPOLE,
+                             hidden=DENSE_SIMPLE_HIDDEN if asked == MAZE_MODEL else (), nonlin='relu')
+    else:
+        if engine.kind != _lib.KIND_DENSE:
+            raise ValueError("dense_main needs an engine of kind KIND_DENSE ({}), the engine passed in is of kind {}".format(_lib.KIND_DENSE, engine.kind))
+        if DENSE_GAMES.get(engine.env_kind) != game:
+            raise ValueError("game {!r} asked for, the engine passed in (kind {} on environment kind {}) runs {!r}".format(
+                game, engine.kind, engine.env_kind, DENSE_GAMES.get(engine.env_kind)))
+        if engine.env_kind == _lib.KIND_PENDULUM:
+            raise NotImplementedError("game {!r}: this loop runs a KIND_DENSE engine on 'maze' and {!r}".format(game, CARTPOLE_GAME))
+        model = dense_model_name(engine)
+        if asked is not None and asked != model:
+            raise ValueError("model {!r} asked for, the engine passed in (kind {}) runs {!r}".format(asked, engine.kind, model))
+    tlogger.start(log_dir)
+    if engine.env_kind == _lib.KIND_MAZE:
+        engine.maze_set_walls(*_lib.load_maze(maze_file(exp)))
+    noise = attach_table(engine, noise)
+    engine.dense_ga_set_init_scale(policies.dense_scale_by(engine.env_kind, engine.hidden, engine.n_actions))
+    rs = np.random.RandomState(seed)
+    all_tstart = time.time()
+    state = _resume_maze(log_dir, ALGO, rs, game, model, engine.P)
+    if state is None:
+        state = TrainingState(exp)
+    state.game, state.model, state.algo, state.num_params = game, model, ALGO, engine.P
+    if 'load_population' in exp:
+        state.copy_population(exp['load_population'])
+    return _bank_loop(log_dir, exp, state, _DenseBank(engine, rs), engine, rs, len(noise.noise) - engine.P + 1, max_iters, all_tstart)
 
 
 # ---------------------------------------------------------------------------------------------- GA-NS on the hard maze
@@ -537,9 +659,10 @@ def maze_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp
     if parents:
         engine.maze_ga_build(parents)
     descriptor = {}                                                 # id(Offspring) -> its descriptor over the bank as it is now
+    bank = _MazeBank(engine)
 
     def evaluate(individuals, tslimit):
-        return _maze_evaluate(engine, [descriptor[id(o)] for o in individuals], tslimit)
+        return _bank_evaluate(bank, [descriptor[id(o)] for o in individuals], tslimit)
 
     iters = 0
     while max_iters is None or iters < max_iters:
@@ -579,7 +702,7 @@ def maze_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp
         if new_parents and not parents:
             engine.maze_ga_build(new_parents)
         elif new_parents:
-            _promote(engine, [descriptor[id(o)] for o in selected])
+            _promote(engine.maze_ga_promote, [descriptor[id(o)] for o in selected])
         parents = new_parents
         state.archive = engine.maze_archive()
         dt = time.time() - tstart_iteration

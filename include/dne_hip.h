@@ -540,6 +540,38 @@ int dne_dense_rollout_host(const float *theta, int n, int env_kind, int n_hidden
                            const double *init_state, const float *header8, const float *lines, int n_walls, int tslimit, float *returns,
                            float *signreturns, int32_t *lengths, double *state);
 
+/* ---- Deep-GA on a dense policy (DNE_KIND_DENSE; csrc/dense_ga.h) -----------------------------
+ * The Deep-GA surface of the hard maze (dne_maze_ga_*, below) for a dense policy of any shape: P is the handle's, the arithmetic is
+ * csrc/maze_ga.h's.  A bank of T <= max_members parents lives on the device, apart from the base slots; a member is (parent, idx, power):
+ *   root   parent == -1, idx >= 0      theta_p = fl(noise[idx + p] * scale_by[p])                (power is not read)
+ *   child  0 <= parent < T, idx >= 0   theta_p = bank[parent][p] + fl(power * noise[idx + p])     (never fused)
+ *   kept   0 <= parent < T, idx < 0    bank[parent] bit for bit: dne_dense_ga_promote only
+ * dne_dense_ga_set_init_scale takes scale_by [P] (policies.dense_scale_by of the shape) and allocates the bank: 3 * max_members slots (two
+ * halves of a double buffer and one scratch slot per member) and the GA's own descriptor arrays.  dne_dense_ga_build fills the bank with T
+ * parents from their genomes (chain_offsets [T + 1] into seeds / powers, from 0).  dne_dense_ga_eval runs one episode per root / child member
+ * in one k_dense_run launch; member i is reset from env_seed[i] on the cart-pole and the pendulum (required there; the maze reads none, NULL
+ * is fine).  dne_dense_final_state, dne_get_profile and dne_stepenv_last_ms follow it as they follow dne_eval_members.  dne_dense_ga_promote
+ * makes the theta of descriptor j the new parent j, for all T_new at once and from the bank as it was: a kept parent may move to another
+ * index and two descriptors may name one source.  dne_dense_ga_parents returns T (-1 on another kind), dne_dense_ga_get_parent copies one
+ * parent [P] out.  All are ordered on the engine's stream.
+ * Refused by name, with the bank left bit for bit as it was: another kind, no init scale, no noise table, (evaluation) no maze loaded on
+ * the maze and a NULL env_seed elsewhere, n or T outside 1 .. max_members, a parent >= T or any parent on an empty bank, the kept form in
+ * an evaluation, idx + P past the table, an empty chain or chain_offsets[0] != 0, a missing buffer, tslimit <= 0.
+ * None of these reads or writes the base slots, the members of dne_set_members or the step-at-a-time batch.
+ * dne_dense_ga_theta_host / dne_dense_ga_members_host are the same header on the CPU (no handle, no GPU; P in 1 .. 9218): the theta of one
+ * genome, and of n descriptors -- the kept form included -- against a host bank [T][P] (NULL when T == 0); errors through dne_last_error(NULL). */
+int dne_dense_ga_set_init_scale(dne_handle *h, const float *scale_by, size_t n /*P*/);
+int dne_dense_ga_build(dne_handle *h, int T, const int32_t *chain_offsets /*T+1*/, const int64_t *seeds, const float *powers);
+int dne_dense_ga_eval(dne_handle *h, int n, const int32_t *parent, const int64_t *idx, const float *power, const uint32_t *env_seed /*n or NULL*/,
+                      int tslimit, float *returns, float *signreturns /*or NULL*/, int32_t *lengths);
+int dne_dense_ga_promote(dne_handle *h, int T_new, const int32_t *parent, const int64_t *idx, const float *power);
+int dne_dense_ga_parents(dne_handle *h);
+int dne_dense_ga_get_parent(dne_handle *h, int j, float *out /*P*/);
+int dne_dense_ga_theta_host(const float *noise, size_t count, const float *scale_by, int P, const int64_t *seeds, const float *powers, int nseeds,
+                            float *out /*P*/);
+int dne_dense_ga_members_host(const float *noise, size_t count, const float *scale_by, int P, const float *bank /*[T][P]*/, int T,
+                              const int32_t *parent, const int64_t *idx, const float *power, int n, float *out /*[n][P]*/);
+
 /* ---- novelty on the hard maze (csrc/maze_novelty.h) -------------------------------------------
  * A behaviour characterisation is one float32 point (x, y): a navigator's final position.  nses.py:12-32 on such points: for member p and
  * archive point a, d = sqrt(dx*dx + dy*dy) in double with dx = (double)ax - (double)px (unfused, correctly rounded sqrt); novelty = the
