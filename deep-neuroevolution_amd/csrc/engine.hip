@@ -38,6 +38,7 @@
 #include "step_env.h"
 #include "dense.h"
 #include "dense_ga.h"
+#include "dense_novelty.h"
 
 using namespace dne;
 
@@ -699,6 +700,7 @@ struct dne_handle {
     bool dense = false;
     dense::Shape dn_shape{};
     double *dn_state = nullptr; int dn_last_n = 0;   // final state records [member][S] of the last evaluation, and how many members that was
+    float *dn_bc = nullptr; bool dn_bc_valid = false;   // the BCs [member][D] of the last evaluation (csrc/dense_novelty.h), formed by the first call that needs them
     int32_t *se_io_mem = nullptr; float *se_io_out = nullptr;   // dne_stepenv_act / _run: the member of each listed environment; the raw outputs
     bool episodic() const { return maze || cartpole || pendulum || mjmaze || dense; }   // a whole episode per member in one launch: what dne_es_eval and the record calls accept beside the Atari kinds
     bool large = false;              // DNE_KIND_GA_LARGE: y1 [441][32], y2 / y3 [121][64] (conv3 output), y3t = the 512 fc outputs
@@ -3627,6 +3629,7 @@ static int dense_eval(dne_handle *h, const MazeMembers &M, const char *call, int
     dense::RunArgs A = dense_args(h, M);
     A.seed = h->seeds; A.episode = 1; A.max_steps = tslimit;
     A.ret = h->ret; A.sign = h->sign; A.steps_out = h->len; A.state_out = h->dn_state;
+    h->dn_bc_valid = false;   // (whatever the launch leaves in dn_state, the BCs formed from the evaluation before are not its)
     if (run_episodes(h, n, returns, signreturns, lengths, [&] { dense_launch(h, n, A); })) return -1;
     h->dn_last_n = n;
     return 0;
@@ -3893,6 +3896,143 @@ extern "C" int dne_dense_ga_members_host(const float *noise, size_t count, const
         if (!bad.empty()) { g_create_error = "dne_dense_ga_members_host: " + bad; return -1; }
     }
     dense_ga::members_host(noise, scale_by, P, bank, parent, idx, power, n, out);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------- novelty over final states on a dense policy (csrc/dense_novelty.h)
+// A handle is of one kind, so the archive, the host members' points and the results are the maze's fields (mzn_*) with D floats a point.
+static int dnv_dim(dne_handle *h) { return dense_novelty::bc_dim(h->dn_shape.env); }
+
+// the BCs of the last evaluation's members, formed once per evaluation (dense_eval withdraws them) on the engine's stream
+static int dnv_last_bc(dne_handle *h) {
+    if (h->dn_bc_valid || h->dn_last_n < 1) return 0;
+    if (!h->dn_bc) HCHECK(h, h->alloc(&h->dn_bc, (size_t)h->M * dense_novelty::MAX_D, "dense_bc"));
+    const int n = h->dn_last_n, env = h->dn_shape.env;
+    const dim3 grid((n + 255) / 256), block(256);
+    if (env == DNE_KIND_MAZE) hipLaunchKernelGGL(dense_novelty::k_dense_bc<DNE_KIND_MAZE>, grid, block, 0, h->stream, (const double *)h->dn_state, n, h->dn_bc);
+    else if (env == DNE_KIND_CARTPOLE) hipLaunchKernelGGL(dense_novelty::k_dense_bc<DNE_KIND_CARTPOLE>, grid, block, 0, h->stream, (const double *)h->dn_state, n, h->dn_bc);
+    else hipLaunchKernelGGL(dense_novelty::k_dense_bc<DNE_KIND_PENDULUM>, grid, block, 0, h->stream, (const double *)h->dn_state, n, h->dn_bc);
+    HCHECK(h, hipGetLastError());
+    h->dn_bc_valid = true;
+    return 0;
+}
+
+// bc == NULL: the last evaluation's members
+static int dnv_check_members(dne_handle *h, const char *call, const float *bc, int n) {
+    if (n < 1) return h->fail("%s: n = %d, at least one point is needed", call, n);
+    if (!bc && n > h->dn_last_n) return h->fail("%s: %d members asked for, the last evaluation ran %d", call, n, h->dn_last_n);
+    return 0;
+}
+
+extern "C" int dne_dense_bc_dim(dne_handle *h) {
+    if (needs_dense(h, "dne_dense_bc_dim")) return -1;
+    return dnv_dim(h);
+}
+
+extern "C" int dne_dense_bc(dne_handle *h, int n, float *bc) {
+    DeviceGuard dg(h);
+    if (needs_dense(h, "dne_dense_bc")) return -1;
+    if (n >= 1 && n <= h->dn_last_n && bc && dnv_last_bc(h)) return -1;
+    return last_eval_rows(h, "dne_dense_bc", n, h->dn_last_n, bc != nullptr, bc, (const float *)h->dn_bc, dnv_dim(h));
+}
+
+extern "C" int dne_dense_archive_append(dne_handle *h, const float *bc, int n) {
+    DeviceGuard dg(h);
+    if (needs_dense(h, "dne_dense_archive_append")) return -1;
+    if (dnv_check_members(h, "dne_dense_archive_append", bc, n)) return -1;
+    const size_t have = (size_t)h->mzn_arch_n, D = (size_t)dnv_dim(h);
+    if (have + (size_t)n > (size_t)INT_MAX / 4) return h->fail("dne_dense_archive_append: %zu points would not fit an int", have + (size_t)n);
+    if (mzn_reserve(h, h->mzn_arch, h->mzn_arch_cap, D * (have + n), D * have, D * MZN_ARCH_CAP0, "dense_archive")) return -1;
+    if (bc) {
+        HCHECK(h, hipMemcpyAsync(h->mzn_arch + D * have, bc, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HCHECK(h, hipStreamSynchronize(h->stream));   // the caller's buffer is free again
+    } else {
+        if (dnv_last_bc(h)) return -1;
+        HCHECK(h, hipMemcpyAsync(h->mzn_arch + D * have, h->dn_bc, (size_t)n * D * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    }
+    h->mzn_arch_n += n;
+    return 0;
+}
+
+extern "C" int dne_dense_archive_clear(dne_handle *h) {
+    DeviceGuard dg(h);
+    if (needs_dense(h, "dne_dense_archive_clear")) return -1;
+    h->mzn_arch_n = 0;   // (the buffer stays; a later append lands behind every call already on the stream)
+    return 0;
+}
+
+extern "C" int dne_dense_archive_size(dne_handle *h) {
+    if (needs_dense(h, "dne_dense_archive_size")) return -1;
+    return h->mzn_arch_n;
+}
+
+extern "C" int dne_dense_archive_get(dne_handle *h, float *bc, int cap) {
+    DeviceGuard dg(h);
+    if (needs_dense(h, "dne_dense_archive_get")) return -1;
+    if (cap < h->mzn_arch_n) return h->fail("dne_dense_archive_get: room for %d points, the archive holds %d", cap, h->mzn_arch_n);
+    if (h->mzn_arch_n > 0) {
+        if (!bc) return h->fail("dne_dense_archive_get: no buffer");
+        HCHECK(h, hipMemcpyAsync(bc, h->mzn_arch, (size_t)h->mzn_arch_n * dnv_dim(h) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HCHECK(h, hipStreamSynchronize(h->stream));
+    }
+    return 0;
+}
+
+// bc staged (or the last evaluation's BCs), k_dense_novelty<D> over the kk = min(k, archive) nearest between two events, the n novelties back
+extern "C" int dne_dense_novelty(dne_handle *h, const float *bc, int n, int k, double *out) {
+    DeviceGuard dg(h);
+    const char *call = "dne_dense_novelty";
+    if (needs_dense(h, call)) return -1;
+    if (dnv_check_members(h, call, bc, n)) return -1;
+    if (k < 1) return h->fail("%s: k = %d, at least one neighbour is needed", call, k);
+    if (k > DNE_DENSE_NOVELTY_KMAX) return h->fail("%s: k = %d, the kernel keeps at most DNE_DENSE_NOVELTY_KMAX = %d neighbours", call, k, DNE_DENSE_NOVELTY_KMAX);
+    if (h->mzn_arch_n < 1) return h->fail("%s: the archive is empty (dne_dense_archive_append)", call);
+    if (!out) return h->fail("%s: no output buffer", call);
+    const int D = dnv_dim(h), kk = std::min(k, h->mzn_arch_n);
+    const float *pts = nullptr;
+    if (bc) {
+        if (mzn_reserve(h, h->mzn_xy, h->mzn_xy_cap, (size_t)D * n, 0, 4096, "dense_novelty_bc")) return -1;
+        HCHECK(h, hipMemcpyAsync(h->mzn_xy, bc, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        pts = h->mzn_xy;
+    } else {
+        if (dnv_last_bc(h)) return -1;
+        pts = h->dn_bc;
+    }
+    if (mzn_reserve(h, h->mzn_out, h->mzn_out_cap, (size_t)n, 0, 4096, "dense_novelty_out")) return -1;
+    HCHECK(h, hipEventRecord(h->ev_a, h->stream));
+    if (D == 2) hipLaunchKernelGGL(dense_novelty::k_dense_novelty<2>, dim3((n + 3) / 4), dim3(256), 0, h->stream, pts, n, (const float *)h->mzn_arch, h->mzn_arch_n, kk, h->mzn_out);
+    else hipLaunchKernelGGL(dense_novelty::k_dense_novelty<4>, dim3((n + 3) / 4), dim3(256), 0, h->stream, pts, n, (const float *)h->mzn_arch, h->mzn_arch_n, kk, h->mzn_out);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipEventRecord(h->ev_b, h->stream));
+    HCHECK(h, hipMemcpyAsync(out, h->mzn_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    float ms = 0;
+    HCHECK(h, hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
+    h->mzn_last_ms = ms;
+    return 0;
+}
+
+extern "C" double dne_dense_novelty_last_ms(dne_handle *h) { return h->dense ? h->mzn_last_ms : -1.0; }
+
+// the same header on the CPU: no handle, no GPU
+extern "C" int dne_dense_novelty_host(const float *bc, int n, const float *archive, int narch, int D, int k, double *out) {
+    if (!bc || !archive || !out) { g_create_error = "dne_dense_novelty_host: a buffer is missing"; return -1; }
+    if (D != 2 && D != 4) { g_create_error = "dne_dense_novelty_host: D = " + std::to_string(D) + ", a behaviour characterisation has 2 or 4 values"; return -1; }
+    if (n < 1) { g_create_error = "dne_dense_novelty_host: n = " + std::to_string(n) + ", at least one point is needed"; return -1; }
+    if (narch < 1) { g_create_error = "dne_dense_novelty_host: the archive is empty"; return -1; }
+    if (k < 1) { g_create_error = "dne_dense_novelty_host: k = " + std::to_string(k) + ", at least one neighbour is needed"; return -1; }
+    dense_novelty::novelty_host(bc, n, archive, narch, D, k, out);
+    return 0;
+}
+
+extern "C" int dne_dense_bc_host(int env_kind, const double *rec, int n, float *bc) {
+    if (env_kind != DNE_KIND_MAZE && env_kind != DNE_KIND_CARTPOLE && env_kind != DNE_KIND_PENDULUM) {
+        g_create_error = "dne_dense_bc_host: environment " + std::to_string(env_kind) + " is none of DNE_KIND_MAZE, DNE_KIND_CARTPOLE, DNE_KIND_PENDULUM";
+        return -1;
+    }
+    if (!rec || !bc) { g_create_error = "dne_dense_bc_host: a buffer is missing"; return -1; }
+    if (n < 1) { g_create_error = "dne_dense_bc_host: n = " + std::to_string(n) + ", at least one record is needed"; return -1; }
+    dense_novelty::bc_host(env_kind, rec, n, bc);
     return 0;
 }
 

@@ -16,6 +16,7 @@ KIND_ES, KIND_GA, KIND_GA_LARGE = 0, 1, 2   # DNE_KIND_* (include/dne_hip.h); 2 
 KIND_ES_VBN = 3   # the GPU tree's ModelVirtualBN in its own flat layout (models/batchnorm.py:52-123): the ES kind's network and entry points
 KIND_MAZE = 4     # the GPU tree's hard maze under SimpleClassifier (gym_tensorflow/maze/, models/simple.py:29-35): whole episodes in one kernel (csrc/maze.h)
 MAZE_OBS, MAZE_STEPS, MAZE_TRACE_W, MAZE_MAX_WALLS = 11, 400, 16, 64   # observation width, tf_maze.cpp's episode length, floats per trace row, walls the kernel takes
+DENSE_NOVELTY_KMAX = 32   # DNE_DENSE_NOVELTY_KMAX = DNE_MAZE_NOVELTY_KMAX (csrc/dense_novelty.h uses maze_novelty.h's list)
 MAZE_NOVELTY_KMAX, MAZE_NOVELTY_TILE, MAZE_ARCHIVE_CAP0 = 32, 1024, 64   # csrc/maze_novelty.h: neighbours a lane keeps, archive points per LDS tile; the archive's first allocation (engine.hip)
 KIND_CARTPOLE = 5   # the GPU tree's gym configuration: gym.CartPole-v1 under SimpleClassifier on 4 inputs, whole episodes in one kernel (csrc/cartpole.h)
 CARTPOLE_OBS, CARTPOLE_STEPS, CARTPOLE_TRACE_W, CARTPOLE_P = 4, 500, 8, 386   # observation width, CartPole-v1's max_episode_steps, doubles per trace row, parameters
@@ -88,7 +89,7 @@ class Profile(C.Structure):
 
 def build(force=False):
     """Compile libdne_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h", "cartpole.h", "pendulum.h", "mjmaze.h", "step_env.h", "dense.h", "dense_ga.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h", "cartpole.h", "pendulum.h", "mjmaze.h", "step_env.h", "dense.h", "dense_ga.h", "dense_novelty.h")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dne_hip.h"))
     if os.environ.get("DNE_LIB_PATH"):
         # another build of the same ABI was asked for by name: `make` only knows the in-tree library, so running it here would
@@ -694,6 +695,34 @@ def dense_ga_members_host(noise, scale_by, bank, parent, idx, power):
     return out
 
 
+# ---- novelty over final states on a dense policy (csrc/dense_novelty.h) ---------------------------------------------------------------------------
+def dense_bc_dim(env_kind):
+    """D of an environment's behaviour characterisation: the cart-pole 4 (x, x_dot, theta, theta_dot), the maze (x, y) and the pendulum (theta, theta_dot) 2"""
+    return 4 if int(env_kind) == KIND_CARTPOLE else 2
+
+
+def dense_bc_host(env_kind, rec):
+    """dne_dense_bc_host: the BCs float32 [n][D] of final state records float64 [n][S] (dense_final_state's, dense_rollout_host's 'state')"""
+    env_kind = int(env_kind)
+    S = stepenv_dims(env_kind)[2] if env_kind in STEPENV_KINDS else 1   # (another kind: the call below refuses it by name)
+    rec = None if rec is None else _arr(rec, np.float64).reshape(-1, S)
+    n = 0 if rec is None else int(rec.shape[0])
+    out = np.empty((n, dense_bc_dim(env_kind)), np.float32)
+    _ck_host(load().dne_dense_bc_host(env_kind, _ptr(rec, C.c_double), n, _ptr(out, C.c_float)))
+    return out
+
+
+def dense_novelty_host(bc, archive, k, D=None):
+    """dne_dense_novelty_host: csrc/dense_novelty.h on the CPU (no GPU, no handle) for BCs [n][D] against archive [narch][D] -> float64 [n];
+    D is bc's second dimension unless given"""
+    D = int(np.shape(bc)[-1] if D is None else D)
+    bc = _arr(bc, np.float32).reshape(-1, max(D, 1)); archive = _arr(archive, np.float32).reshape(-1, max(D, 1))
+    out = np.empty(bc.shape[0], np.float64)
+    _ck_host(load().dne_dense_novelty_host(_ptr(bc, C.c_float), int(bc.shape[0]), _ptr(archive, C.c_float), int(archive.shape[0]), D, int(k),
+                                           _ptr(out, C.c_double)))
+    return out
+
+
 def _ptr(a, t):
     return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
 
@@ -1158,6 +1187,63 @@ class Engine:
         out = np.empty((max(int(n), 0), S), np.float64)
         self._ck(self.lib.dne_dense_final_state(self.h, int(n), _ptr(out, C.c_double)))
         return out
+
+    # ---- novelty over final states on a dense policy (csrc/dense_novelty.h): BCs are D floats of the final state, the archive lives on the device
+    def dense_bc_dim(self):
+        D = self.lib.dne_dense_bc_dim(self.h)
+        if D < 0:
+            self._ck(D)
+        return D
+
+    def dense_bc(self, n):
+        """dne_dense_bc: the BCs float32 [n][D] of the last evaluation's first n members"""
+        out = np.empty((max(int(n), 0), self.dense_bc_dim()), np.float32)
+        self._ck(self.lib.dne_dense_bc(self.h, int(n), _ptr(out, C.c_float)))
+        return out
+
+    def _dense_points(self, bc, n):
+        """(host BCs or None, count): bc=None means the first n members of the last evaluation (all of them without n), read on the device"""
+        if bc is None:
+            return None, int(self._last_eval_n if n is None else n)
+        D = self.dense_bc_dim()
+        bc = _arr(bc, np.float32).reshape(-1, D)
+        if n is not None and int(n) != bc.shape[0]:
+            raise DneError("%d points given, n = %d" % (bc.shape[0], int(n)))
+        return bc, int(bc.shape[0])
+
+    def dense_archive_append(self, bc=None, n=None):
+        """append BCs [n][D] to the device-resident archive, in order; bc=None: those of the last evaluation's first n members, device to device"""
+        bc, n = self._dense_points(bc, n)
+        self._ck(self.lib.dne_dense_archive_append(self.h, _ptr(bc, C.c_float), n))
+
+    def dense_archive_clear(self):
+        self._ck(self.lib.dne_dense_archive_clear(self.h))
+
+    def dense_archive_size(self):
+        n = self.lib.dne_dense_archive_size(self.h)
+        if n < 0:
+            self._ck(n)
+        return n
+
+    def dense_archive(self):
+        """the archive's BCs in insertion order, [size][D] float32"""
+        n = self.dense_archive_size()
+        out = np.empty((n, self.dense_bc_dim()), np.float32)
+        self._ck(self.lib.dne_dense_archive_get(self.h, _ptr(out, C.c_float), n))
+        return out
+
+    def dense_novelty(self, k, bc=None, n=None):
+        """nses.py:22-32 on BCs of D floats: the mean distance of each to its min(k, archive size) nearest archive points, float64 [n]
+        (k_dense_novelty; 1 <= k <= DENSE_NOVELTY_KMAX).  bc=None scores the last evaluation's first n members on the device."""
+        bc, n = self._dense_points(bc, n)
+        out = np.empty(max(n, 0), np.float64)
+        self._ck(self.lib.dne_dense_novelty(self.h, _ptr(bc, C.c_float), n, int(k), _ptr(out, C.c_double)))
+        return out
+
+    def dense_novelty_last_ms(self):
+        """the scoring kernel of the last dense_novelty call between two device events, milliseconds (-1 before the first)"""
+        self.lib.dne_dense_novelty_last_ms.restype = C.c_double
+        return float(self.lib.dne_dense_novelty_last_ms(self.h))
 
     # ---- novelty on the hard maze (csrc/maze_novelty.h): BCs are final (x, y) points, the archive lives on the device
     def _maze_points(self, xy, n):

@@ -607,6 +607,32 @@ int dne_maze_novelty_pool(dne_handle *h, const float *xy /*[n][2], or NULL*/, in
 int dne_maze_novelty_pool_host(const float *xy, int n, const float *archive /*[narch][2]*/, int narch, int k, double *out);
 int dne_maze_archive_append_members(dne_handle *h, const int32_t *members /*[count]*/, int count);
 
+/* ---- novelty over final states on a dense policy (DNE_KIND_DENSE; csrc/dense_novelty.h) ------
+ * The behaviour characterisation (BC) of a member is D float32 values of its final state record (dne_dense_final_state's doubles), one
+ * round-to-nearest cast each, NaN and +-inf passing through: the maze D = 2 (x, y) -- MazeFinalState; the cart-pole D = 4 (x, x_dot, theta,
+ * theta_dot); the pendulum D = 2 (theta, theta_dot).  dne_dense_bc_dim returns D, dne_dense_bc copies out the BCs of the last evaluation's
+ * first n members (dne_dense_final_state's rule for n).  Novelty is the contract above with D coordinates: d = sqrt(s), s = d_0 * d_0, then
+ * s = s + d_i * d_i for i ascending with d_i = (double)a_i - (double)p_i, unfused; the order (isnan, value, archive slot); the kk = min(k,
+ * archive size) first distances added one by one into a double from 0.0, divided by kk.  For D = 2 it is dne_maze_novelty's bit for bit.
+ * The archive is a device buffer of D floats a point in insertion order; appends, clears and scoring are ordered on the engine's stream.
+ * bc == NULL means the first n members of the last evaluation (dne_eval_members, dne_es_eval or dne_dense_ga_eval), device to device.
+ * Refused by name, the archive left as it was: an engine of another kind, n < 1, the NULL form beyond the last evaluation's members, an empty
+ * archive for a novelty call, k < 1, k > DNE_DENSE_NOVELTY_KMAX, a missing output buffer, cap below the archive's size.  The dne_maze_*
+ * calls above keep refusing this kind.  dne_dense_novelty_last_ms: k_dense_novelty of the last dne_dense_novelty between two device events,
+ * in milliseconds (-1 before the first).  dne_dense_novelty_host (D 2 or 4, any k >= 1) and dne_dense_bc_host (rec [n][S] of env_kind) are
+ * the same header on the CPU: no handle, no GPU, errors through dne_last_error(NULL). */
+#define DNE_DENSE_NOVELTY_KMAX DNE_MAZE_NOVELTY_KMAX
+int dne_dense_bc_dim(dne_handle *h);
+int dne_dense_bc(dne_handle *h, int n, float *bc /*[n][D]*/);
+int dne_dense_archive_append(dne_handle *h, const float *bc /*[n][D], or NULL*/, int n);
+int dne_dense_archive_clear(dne_handle *h);
+int dne_dense_archive_size(dne_handle *h);
+int dne_dense_archive_get(dne_handle *h, float *bc /*[cap][D]*/, int cap);
+int dne_dense_novelty(dne_handle *h, const float *bc /*[n][D], or NULL*/, int n, int k, double *out /*[n]*/);
+double dne_dense_novelty_last_ms(dne_handle *h);
+int dne_dense_novelty_host(const float *bc, int n, const float *archive /*[narch][D]*/, int narch, int D, int k, double *out);
+int dne_dense_bc_host(int env_kind, const double *rec /*[n][S]*/, int n, float *bc /*[n][D]*/);
+
 /* ---- Deep-GA on the hard maze (csrc/maze_ga.h) -----------------------------------------------
  * gpu_implementation/ga.py on SimpleClassifier.  A genome is (idx0, (idx1, power1), ...) as seeds[] / powers[] (powers[0] is not read):
  * theta_p = fl(noise[idx0 + p] * scale_by[p]), then per mutation, in order, theta_p = theta_p + fl(power_j * noise[idx_j + p]), never fused.
