@@ -618,6 +618,7 @@ struct dne_handle {
     float *theta_perm = nullptr;     // [3872 + 16][256]: base slot 0's fc matrix, every row stored as columns l, l+64, l+128, l+192 per lane (k_theta_perm, once per evaluation)
     float *y3s = nullptr;            // [member][32][256]: the chain sums k_fc_sub leaves for k_out<.., SUB>
     int *unit_order = nullptr;       // [4 * groups]: per window, its (group, k-slice) units in noise-table order
+    float *zero_rows = nullptr;      // [ZERO_ROWS_FLOATS] zeros: what k_fc_sub fetches in place of a dead weight row (FwdArgs::zero_rows)
     uint8_t *spec_prev = nullptr, *spec_cur = nullptr, *spec_stacks = nullptr;   // candidate outcomes of the speculative tail (DNE_SPEC_MAX)
     int32_t *spec_rw = nullptr;
     float *spec_y1 = nullptr;
@@ -804,6 +805,7 @@ struct dne_handle {
         A.noise = noise; A.bases = bases; A.base_stride = base_stride;
         A.m_slot = m_slot; A.m_off = m_off; A.m_scale = m_scale; A.bn = bn; A.bn_mom = bn_mom;
         A.done = use_done ? done : nullptr; A.L = L;
+        A.zero_rows = zero_rows;
         A.sub_sums = p.sub ? 1 : 0;
         if (tt) A.tt = *tt; else A.tt.n = 0;
         return A;
@@ -1113,6 +1115,7 @@ extern "C" int dne_debug_knob(int kind, int n_actions, const char *name) {
 
 extern "C" const char *dne_last_error(dne_handle *h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
+constexpr size_t ZERO_ROWS_FLOATS = 8 * 256;            // a row block of zeros (8 KB): k_fc_sub's dead rows (forward.h)
 constexpr size_t OVERFETCH_FLOATS = 2 * 8 * 256 + 64;   // one row block of the streaming fc + the 64 floats of slack the table always had
 static int grow_bases(dne_handle *h, int cap) {
     if (cap <= h->base_cap) return 0;
@@ -1394,6 +1397,10 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
     if (h->large) { CH(h->alloc(&h->y1, M * 14112, "y1")); CH(h->alloc(&h->y2, M * 7744, "y2")); CH(h->alloc(&h->y3, M * 7744, "y3")); CH(h->alloc(&h->y3t, M * 512, "y3t")); }
     else { CH(h->alloc(&h->y1, M * 7056, "y1")); CH(h->alloc(&h->y2, M * 3872 + 64, "y2"));   /* (+ 64: k_fc_ring fetches the eight activations behind a slice's end and never uses them) */ CH(h->alloc(&h->y3, M * 256, "y3")); CH(h->alloc(&h->y3t, M * 4 * 256, "y3t")); }
     CH(h->alloc(&h->unit_order, M * 4, "unit_order"));
+    if (!h->large) {   // a dead row's load: uniform base + lane * 16 + an immediate of up to 3 KB, whichever of the two 4 KB halves of a block it stands for
+        CH(h->alloc(&h->zero_rows, ZERO_ROWS_FLOATS, "zero_rows"));
+        CH(hipMemset(h->zero_rows, 0, ZERO_ROWS_FLOATS * sizeof(float)));
+    }
     if (!h->large && h->k.fc_sub) CH(h->alloc(&h->y3s, M * 32 * 256, "y3s"));
     if (!h->large && h->k.ring_on && es_like(cfg->policy_kind)) CH(h->alloc(&h->theta_perm, (size_t)(3872 + 16) * 256, "theta_perm"));
     if (h->k.spec_max > 0) {   // candidate outcomes of the speculative tail: [list position][action]

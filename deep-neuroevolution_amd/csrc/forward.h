@@ -60,6 +60,7 @@ struct FwdArgs {
     float *bn;               // [members][608]: s1[16] h1[16] s2[32] h2[32] s3[256] h3[256]
     float *bn_mom;           // [members][608]: the batch moments behind them, mean / variance in the same layout (snapshots)
     const int32_t *done;     // per member, step mode only
+    const float *zero_rows;  // 8 KB of zeros: what k_fc_sub fetches in place of a weight row that meets only relu zeros (dead rows)
     int sub_sums;            // the fc left 32 chain sums per column (k_fc_sub: y3s[member][32][256]) instead of 4 quarter sums: the head folds them
     Layout L;
     TailTable tt;
@@ -1728,6 +1729,11 @@ __device__ __forceinline__ long long uni64(long long v) {
 #ifndef DNE_THETA_MOD
 #define DNE_THETA_MOD ""
 #endif
+// dead rows (k_fc_sub): 1 = the activations of a finished member of a pair keep no row alive (its sums are read by nobody),
+// 0 = every member of the launch counts (same-box A/B through DNE_LIB_PATH; the product library is built with 1)
+#ifndef DNE_SKIP_FINISHED
+#define DNE_SKIP_FINISHED 1
+#endif
 template <int OFF>
 __device__ __forceinline__ void gload4(f32x4 &dst, unsigned voff, const float *sbase) {
     // "+v": the registers of the row just consumed are the destination (its readers come first; nothing is kept alive or copied)
@@ -3225,9 +3231,8 @@ __global__ __launch_bounds__(256) void k_fc_cols(FwdArgs A, const int *__restric
 // here: a wave walks the rows of ONE sub-slice (or of `spw` consecutive ones) with whole 1 KB rows per load instruction (lane = 4
 // columns) through k_fc_duo's rolling window -- W rows per stream always in flight, each row's registers refilled the moment it is
 // consumed, no LDS, no barrier -- and stores the chain's 256 sums to y3s[member][32][256]; the head (FwdArgs::sub_sums) folds them in
-// the oracle's order.  250 members = 8000 waves: the whole machine streams.  The block behind a chain's last one is fetched and never
-// used: the next sub-slice, or what follows the fc matrix (fc bias / bn3 / output layer, and for small action counts the floats behind the
-// member's slice: the bases and noise allocations carry a block of padding for that, engine.hip OVERFETCH_FLOATS).
+// the oracle's order.  250 members = 8000 waves: the whole machine streams.  The block behind a chain's last one is requested and never
+// used: like every dead row (below) it reads FwdArgs::zero_rows.
 template <int NV, bool HAS_BN, bool NOISE>
 __global__ __launch_bounds__(256) void k_fc_sub(FwdArgs A, const int *__restrict__ list, int n_groups, int spw /* sub-slices per wave: 1, 2, 4, 8 */,
                                                 int prio, const float *__restrict__ y2, float *__restrict__ y3s /*[member][32][256]*/) {
@@ -3244,10 +3249,17 @@ __global__ __launch_bounds__(256) void k_fc_sub(FwdArgs A, const int *__restrict
     for (int w = uni(blockIdx.x * 4 + wv); w < n_groups * upg; w += gridDim.x * 4) {
     const int gi = w / upg, j = w - gi * upg;
     const int g = uni(list ? list[gi] : gi);
+    bool runs[NV];   // the member is not finished (wave-uniform): only such members keep a row alive (dead rows, below)
+#pragma unroll
+    for (int v = 0; v < NV; v++) runs[v] = true;
     if (A.done) {   // finished group still in the list: nobody reads its sums
         int all_done = 1;
 #pragma unroll
-        for (int v = 0; v < NV; v++) all_done &= uni(A.done[g * NV + v]) != 0;
+        for (int v = 0; v < NV; v++) {
+            const int d = uni(A.done[g * NV + v]);
+            all_done &= d != 0;
+            if (DNE_SKIP_FINISHED) runs[v] = d == 0;   // ... nor the sums of a pair's finished member
+        }
         if (all_done) continue;
     }
     const int m0 = g * NV;
@@ -3280,6 +3292,22 @@ __global__ __launch_bounds__(256) void k_fc_sub(FwdArgs A, const int *__restrict
                 asm volatile("" : "+v"(xa[v]), "+v"(xb[v]));
             }
         }
+        // dead rows: a row whose activation is +0 in every member that still runs changes no accumulator (fma(+0, w, acc) == acc for
+        // finite w), so its two loads are pointed at FwdArgs::zero_rows instead -- the same instructions into the same registers at
+        // the same place of the window, a cache hit in place of 1 KB of the noise table and 1 KB of the base vector.  One bit per
+        // row of the chain, wave-uniform (SGPRs); rows behind the chain's end (the over-fetched block) are dead by construction.
+        unsigned long long live_a, live_b;
+        {
+            bool la = false, lb = false;
+#pragma unroll
+            for (int v = 0; v < NV; v++) {
+                la = la || (runs[v] && xa[v] > 0.0f);
+                lb = lb || (runs[v] && xb[v] > 0.0f);
+            }
+            live_a = __builtin_amdgcn_ballot_w64(la);
+            live_b = __builtin_amdgcn_ballot_w64(lb && 64 + lane < nrows);
+        }
+        unsigned lm = (unsigned)live_a & 0xffu;         // the rows of the block being requested, bit I = row I (wave-uniform)
         const float *tnext = base + (size_t)R0 * 256;   // wave-uniform: the chain's next row block
         const float *enext = eps + (size_t)R0 * 256;
         f32x2 acc[NV][2];
@@ -3293,13 +3321,16 @@ __global__ __launch_bounds__(256) void k_fc_sub(FwdArgs A, const int *__restrict
         constexpr int PENDING = (W - 1) * (NOISE ? 2 : 1);
         auto refill = [&](auto ii) {
             constexpr int I = decltype(ii)::value;
+            const bool live = (lm >> I & 1u) != 0;   // a scalar select of the base address, nothing else
+            const float *tp = live ? tnext + (I / 4) * 1024 : A.zero_rows;
             if constexpr (NOISE) {
-                if constexpr (NV == 2) gload4_after<(I % 4) * 1024>(e[I], voff, enext + (I / 4) * 1024, acc[0][0], acc[0][1], acc[1][0], acc[1][1]);
-                else gload4_after<(I % 4) * 1024>(e[I], voff, enext + (I / 4) * 1024, acc[0][0], acc[0][1]);
-                gload4<(I % 4) * 1024>(t[I], voff, tnext + (I / 4) * 1024);
+                const float *ep = live ? enext + (I / 4) * 1024 : A.zero_rows;
+                if constexpr (NV == 2) gload4_after<(I % 4) * 1024>(e[I], voff, ep, acc[0][0], acc[0][1], acc[1][0], acc[1][1]);
+                else gload4_after<(I % 4) * 1024>(e[I], voff, ep, acc[0][0], acc[0][1]);
+                gload4<(I % 4) * 1024>(t[I], voff, tp);
             } else {
-                if constexpr (NV == 2) gload4_after<(I % 4) * 1024>(t[I], voff, tnext + (I / 4) * 1024, acc[0][0], acc[0][1], acc[1][0], acc[1][1]);
-                else gload4_after<(I % 4) * 1024>(t[I], voff, tnext + (I / 4) * 1024, acc[0][0], acc[0][1]);
+                if constexpr (NV == 2) gload4_after<(I % 4) * 1024>(t[I], voff, tp, acc[0][0], acc[0][1], acc[1][0], acc[1][1]);
+                else gload4_after<(I % 4) * 1024>(t[I], voff, tp, acc[0][0], acc[0][1]);
             }
         };
         static_for<W>(refill);
@@ -3307,6 +3338,7 @@ __global__ __launch_bounds__(256) void k_fc_sub(FwdArgs A, const int *__restrict
         const int nb = nrows / W;   // 16 or 15 row blocks
         for (int b = 0; b < nb; b++) {
             const int li = (b & 7) * W;
+            lm = b + 1 < nb ? (unsigned)((b + 1 < 8 ? live_a : live_b) >> (((b + 1) & 7) * W)) & 0xffu : 0u;   // this block's refills request block b + 1
             float xs[NV];   // rows 0 .. 63 of the chain come from xa, the rest from xb
 #pragma unroll
             for (int v = 0; v < NV; v++) xs[v] = b < 8 ? xa[v] : xb[v];
@@ -3377,7 +3409,9 @@ __global__ __launch_bounds__(256) void k_out(FwdArgs A, const int *__restrict__ 
         float pvb = sc[v] * fb_e;
         const float fb = fb_t + pvb;
         t = t + fb;
-        y3[(size_t)m * 256 + tid] = t;
+        // a pair's finished member: its row keeps its last lock-step's values (the streaming fc skipped rows on the other member's
+        // zeros alone -- dead rows -- so this sum is not the member's; nobody reads its action either)
+        if (!DNE_SKIP_FINISHED || !A.done || A.done[m] == 0) y3[(size_t)m * 256 + tid] = t;
         if (HAS_BN) {
             t = t * A.bn[(size_t)m * 608 + 96 + tid];
             t = t + A.bn[(size_t)m * 608 + 352 + tid];
