@@ -109,13 +109,17 @@ def oracle_last_step(L, theta_i, ref, env_seed, T, large=False):
 
 
 def activated_y2(y2, bn):
-    """what the ring regime leaves in the y2 row: relu(bn2(y2)) as k_conv12 (act2) / k_y2_activate compute it -- multiply, then add, then max,
-    two float32 roundings (bn: the member's 608 floats, scale2 at 32, shift2 at 64; channel = i % 32)"""
+    """what the ring regime leaves in the y2 row: relu(bn2(y2)) as k_conv12 (act2) / k_y2_activate compute it -- multiply, then add, then the
+    oracle's select t > 0 ? t : 0, two float32 roundings (bn: the member's 608 floats, scale2 at 32, shift2 at 64; channel = i % 32).
+    The select sends NaN and -0 to +0 as bn_relu of oracle/dne_oracle.c does; np.maximum, which stood here before, hands NaN on.  On every
+    t that is not a NaN the two are equal under np.array_equal, which is how the tests of finite values compare, so nothing they assert has
+    moved (tests/test_value_edges_cpu.py holds this function to the oracle's bn_relu on NaN, +-inf, +-0, a subnormal and a NaN scale)."""
     y2 = np.asarray(y2, np.float32)
     c = np.arange(y2.size) & 31
-    t = (y2 * bn[32 + c]).astype(np.float32)
-    t = (t + bn[64 + c]).astype(np.float32)
-    return np.maximum(t, np.float32(0.0))
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = (y2 * bn[32 + c]).astype(np.float32)
+        t = (t + bn[64 + c]).astype(np.float32)
+        return np.where(t > 0, t, np.float32(0.0)).astype(np.float32)
 
 
 # ---- base vectors and member vectors per engine kind ------------------------------------------------------------------------------------
