@@ -11,7 +11,11 @@
 //     (-ffp-contract=off on both passes); sqrt the correctly rounded one.  For D = 2 this is maze_novelty::distance bit for bit;
 //   * the order is (isnan, value, archive slot) through sort_key;
 //   * novelty = (the kk = min(k, narch) first distances of that order, added one by one in that order into a double that starts at 0.0) / kk.
-// The archive form only: the pool form (GA-NS) has no driver on a dense run.  No [n][narch] matrix exists on either side.
+// Two forms, as in maze_novelty.h.  The archive form (NS-ES / NSR-ES, section 17b) is the one above.  The pool form (GA-NS, section 17c,
+// ga_gpu.dense_ns_main) scores member p of n members against the archive AND the population it belongs to: the slots are the combined ones, the
+// archive's points at 0 .. narch - 1, then the population's at narch .. narch + n - 1 (on equal distances an archive point comes first); p's own
+// combined slot narch + p is left out by index, not by value; kk = min(k, narch + n - 1); a NaN member gets a NaN novelty; narch may be 0, and a
+// pool with nothing in it (n = 1, narch = 0) has no novelty: the callers refuse it.  No [n][narch] or [n][narch + n] matrix exists on either side.
 // A plain C++ compiler can include this file (the kernels are behind __HIPCC__): tests/dense_novelty_asan_main.cpp does.
 #pragma once
 #include "dense.h"
@@ -58,6 +62,24 @@ inline void novelty_host(const float *bc, int n, const float *archive, int narch
     std::vector<std::pair<uint64_t, int32_t>> e((size_t)narch);
     for (int p = 0; p < n; p++) {
         for (int c = 0; c < narch; c++) e[c] = std::make_pair(sort_key(distance(bc + (size_t)D * p, archive + (size_t)D * c, D)), (int32_t)c);
+        std::partial_sort(e.begin(), e.begin() + kk, e.end());
+        double s = 0.0;
+        for (int t = 0; t < kk; t++) s += key_value(e[t].first);
+        out[p] = s / (double)kk;
+    }
+}
+
+// the pool form: the entries are the combined slots 0 .. narch + n - 1 without narch + p (narch may be 0, archive is not read then; narch + n - 1 >= 1)
+inline void novelty_pool_host(const float *bc, int n, const float *archive, int narch, int D, int k, double *out) {
+    const int total = narch + n, pool = total - 1, kk = k < pool ? k : pool;
+    std::vector<std::pair<uint64_t, int32_t>> e((size_t)pool);
+    for (int p = 0; p < n; p++) {
+        size_t at = 0;
+        for (int c = 0; c < total; c++) {
+            if (c == narch + p) continue;
+            const float *q = c < narch ? archive + (size_t)D * c : bc + (size_t)D * (c - narch);
+            e[at++] = std::make_pair(sort_key(distance(bc + (size_t)D * p, q, D)), (int32_t)c);
+        }
         std::partial_sort(e.begin(), e.begin() + kk, e.end());
         double s = 0.0;
         for (int t = 0; t < kk; t++) s += key_value(e[t].first);
@@ -147,6 +169,83 @@ __global__ __launch_bounds__(256) void k_dense_novelty(const float *__restrict__
         sum += key_value(bk);
     }
     if (lane == 0 && live) out[m] = sum / (double)kk;
+}
+
+// k_dense_novelty's scheme over the pool, as k_maze_novelty_pool is to k_maze_novelty: the tiles run over the COMBINED slots 0 .. narch + n - 1,
+// the archive first and the population behind it (the staging loop picks the source per point, so a tile may hold the end of one and the start
+// of the other); a lane still sees its points in ascending combined slot and a candidate still comes after everything already in its list.  The
+// member's own combined slot narch + m is passed over, by index.  kk <= narch + n - 1, so the kk rounds never reach an empty place.  archive is
+// not read when narch == 0 (it may be null).  Same list, same compile-time indices.
+template <int D>
+__global__ __launch_bounds__(256) void k_dense_novelty_pool(const float *__restrict__ bc, int n, const float *__restrict__ archive, int narch, int kk,
+                                                            double *__restrict__ out) {
+    typedef typename PointOf<D>::T Pt;
+    __shared__ Pt s_pts[TILE];
+    const int lane = threadIdx.x & 63;
+    int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const bool live = m < n;
+    if (!live) m = n - 1;
+    float p[D], a[D];
+    spread(((const Pt *)bc)[(size_t)m], p);
+    const int total = narch + n, self = narch + m;
+    uint64_t key[KMAX];
+    int slot[KMAX];
+#pragma unroll
+    for (int i = 0; i < KMAX; i++) { key[i] = KEY_NONE; slot[i] = INT_MAX; }
+    uint64_t worst = KEY_NONE;
+    for (int t0 = 0; t0 < total; t0 += TILE) {
+        const int cnt = total - t0 < TILE ? total - t0 : TILE;
+        __syncthreads();                            // the tile before this one has been read by every wave
+        for (int i = threadIdx.x; i < cnt; i += 256) {
+            const int c = t0 + i;
+            s_pts[i] = c < narch ? ((const Pt *)archive)[(size_t)c] : ((const Pt *)bc)[(size_t)(c - narch)];
+        }
+        __syncthreads();
+        for (int j = lane; j < cnt; j += 64) {
+            spread(s_pts[j], a);
+            const uint64_t ck = sort_key(distance(p, a, D));
+            const int cs = t0 + j;
+            if (ck < worst && cs != self) {         // (the candidate's combined slot is above every slot of the list: on equal keys it comes after)
+#pragma unroll
+                for (int i = KMAX - 1; i >= 1; i--) {
+                    const bool shift = key[i - 1] > ck, here = key[i] > ck;
+                    key[i] = shift ? key[i - 1] : here ? ck : key[i];
+                    slot[i] = shift ? slot[i - 1] : here ? cs : slot[i];
+                }
+                if (key[0] > ck) { key[0] = ck; slot[0] = cs; }
+#pragma unroll
+                for (int i = 0; i < KMAX; i++) worst = i == kk - 1 ? key[i] : worst;
+            }
+        }
+    }
+    double sum = 0.0;
+    for (int t = 0; t < kk; t++) {
+        uint64_t bk = key[0];
+        int bs = slot[0];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint64_t ok = (uint64_t)__shfl_xor((long long)bk, o);
+            const int os = __shfl_xor(bs, o);
+            if (ok < bk || (ok == bk && os < bs)) { bk = ok; bs = os; }
+        }
+        if (slot[0] == bs) {                        // a combined slot lives in one lane
+#pragma unroll
+            for (int i = 0; i < KMAX - 1; i++) { key[i] = key[i + 1]; slot[i] = slot[i + 1]; }
+            key[KMAX - 1] = KEY_NONE; slot[KMAX - 1] = INT_MAX;
+        }
+        sum += key_value(bk);
+    }
+    if (lane == 0 && live) out[m] = sum / (double)kk;
+}
+
+// archive slot have + i = the BC of the last evaluation's member members[i], in the order given (indices may repeat); one thread per point,
+// one load and one store of 4 D bytes
+template <int D>
+__global__ __launch_bounds__(256) void k_dense_archive_gather(const float *__restrict__ bc, const int32_t *__restrict__ members, int count,
+                                                              float *__restrict__ dst) {
+    typedef typename PointOf<D>::T Pt;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < count) ((Pt *)dst)[i] = ((const Pt *)bc)[members[i]];
 }
 #endif
 

@@ -4019,6 +4019,68 @@ extern "C" int dne_dense_novelty(dne_handle *h, const float *bc, int n, int k, d
     return 0;
 }
 
+// pool novelty (GA-NS): every member against the archive and the other members, k_dense_novelty_pool<D> between two events
+extern "C" int dne_dense_novelty_pool(dne_handle *h, const float *bc, int n, int k, double *out) {
+    DeviceGuard dg(h);
+    const char *call = "dne_dense_novelty_pool";
+    if (needs_dense(h, call)) return -1;
+    if (dnv_check_members(h, call, bc, n)) return -1;
+    if (k < 1) return h->fail("%s: k = %d, at least one neighbour is needed", call, k);
+    if (k > DNE_DENSE_NOVELTY_KMAX) return h->fail("%s: k = %d, the kernel keeps at most DNE_DENSE_NOVELTY_KMAX = %d neighbours", call, k, DNE_DENSE_NOVELTY_KMAX);
+    if (h->mzn_arch_n + (n - 1) < 1) return h->fail("%s: the pool is empty (one member, no archive point)", call);
+    if ((size_t)h->mzn_arch_n + (size_t)n > (size_t)INT_MAX / 4) return h->fail("%s: %zu combined slots would not fit an int", call, (size_t)h->mzn_arch_n + (size_t)n);
+    if (!out) return h->fail("%s: no output buffer", call);
+    const int D = dnv_dim(h), kk = std::min(k, h->mzn_arch_n + n - 1);
+    const float *pts = nullptr;
+    if (bc) {
+        if (mzn_reserve(h, h->mzn_xy, h->mzn_xy_cap, (size_t)D * n, 0, 4096, "dense_novelty_bc")) return -1;
+        HCHECK(h, hipMemcpyAsync(h->mzn_xy, bc, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        pts = h->mzn_xy;
+    } else {
+        if (dnv_last_bc(h)) return -1;
+        pts = h->dn_bc;
+    }
+    if (mzn_reserve(h, h->mzn_out, h->mzn_out_cap, (size_t)n, 0, 4096, "dense_novelty_out")) return -1;
+    HCHECK(h, hipEventRecord(h->ev_a, h->stream));
+    if (D == 2) hipLaunchKernelGGL(dense_novelty::k_dense_novelty_pool<2>, dim3((n + 3) / 4), dim3(256), 0, h->stream, pts, n, (const float *)h->mzn_arch, h->mzn_arch_n, kk, h->mzn_out);
+    else hipLaunchKernelGGL(dense_novelty::k_dense_novelty_pool<4>, dim3((n + 3) / 4), dim3(256), 0, h->stream, pts, n, (const float *)h->mzn_arch, h->mzn_arch_n, kk, h->mzn_out);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipEventRecord(h->ev_b, h->stream));
+    HCHECK(h, hipMemcpyAsync(out, h->mzn_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    float ms = 0;
+    HCHECK(h, hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
+    h->mzn_last_ms = ms;
+    return 0;
+}
+
+// archive slot A + i = the BC of the last evaluation's member members[i], device to device (k_dense_archive_gather<D>); the indices are checked
+// before anything is launched, and the gather follows mzn_reserve's reallocation on the engine's stream
+extern "C" int dne_dense_archive_append_members(dne_handle *h, const int32_t *members, int count) {
+    DeviceGuard dg(h);
+    const char *call = "dne_dense_archive_append_members";
+    if (needs_dense(h, call)) return -1;
+    if (count < 1) return h->fail("%s: count = %d, at least one member is needed", call, count);
+    if (!members) return h->fail("%s: no member indices", call);
+    for (int i = 0; i < count; i++)
+        if (members[i] < 0 || members[i] >= h->dn_last_n)
+            return h->fail("%s: index %d is member %d, the last evaluation ran %d", call, i, members[i], h->dn_last_n);
+    const size_t have = (size_t)h->mzn_arch_n, D = (size_t)dnv_dim(h);
+    if (have + (size_t)count > (size_t)INT_MAX / 4) return h->fail("%s: %zu points would not fit an int", call, have + (size_t)count);
+    if (mzn_reserve(h, h->mzn_arch, h->mzn_arch_cap, D * (have + count), D * have, D * MZN_ARCH_CAP0, "dense_archive")) return -1;
+    if (mzn_reserve(h, h->mzn_idx, h->mzn_idx_cap, (size_t)count, 0, 4096, "dense_archive_members")) return -1;
+    if (dnv_last_bc(h)) return -1;
+    HCHECK(h, hipMemcpyAsync(h->mzn_idx, members, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    const dim3 grid((count + 255) / 256), block(256);
+    if (D == 2) hipLaunchKernelGGL(dense_novelty::k_dense_archive_gather<2>, grid, block, 0, h->stream, (const float *)h->dn_bc, (const int32_t *)h->mzn_idx, count, h->mzn_arch + D * have);
+    else hipLaunchKernelGGL(dense_novelty::k_dense_archive_gather<4>, grid, block, 0, h->stream, (const float *)h->dn_bc, (const int32_t *)h->mzn_idx, count, h->mzn_arch + D * have);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipStreamSynchronize(h->stream));   // the caller's buffer is free again
+    h->mzn_arch_n += count;
+    return 0;
+}
+
+// the scoring kernel of the last scoring call of either form
 extern "C" double dne_dense_novelty_last_ms(dne_handle *h) { return h->dense ? h->mzn_last_ms : -1.0; }
 
 // the same header on the CPU: no handle, no GPU
@@ -4029,6 +4091,17 @@ extern "C" int dne_dense_novelty_host(const float *bc, int n, const float *archi
     if (narch < 1) { g_create_error = "dne_dense_novelty_host: the archive is empty"; return -1; }
     if (k < 1) { g_create_error = "dne_dense_novelty_host: k = " + std::to_string(k) + ", at least one neighbour is needed"; return -1; }
     dense_novelty::novelty_host(bc, n, archive, narch, D, k, out);
+    return 0;
+}
+
+extern "C" int dne_dense_novelty_pool_host(const float *bc, int n, const float *archive, int narch, int D, int k, double *out) {
+    if (!bc || !out || (narch > 0 && !archive)) { g_create_error = "dne_dense_novelty_pool_host: a buffer is missing"; return -1; }
+    if (D != 2 && D != 4) { g_create_error = "dne_dense_novelty_pool_host: D = " + std::to_string(D) + ", a behaviour characterisation has 2 or 4 values"; return -1; }
+    if (n < 1) { g_create_error = "dne_dense_novelty_pool_host: n = " + std::to_string(n) + ", at least one point is needed"; return -1; }
+    if (narch < 0) { g_create_error = "dne_dense_novelty_pool_host: narch = " + std::to_string(narch); return -1; }
+    if (k < 1) { g_create_error = "dne_dense_novelty_pool_host: k = " + std::to_string(k) + ", at least one neighbour is needed"; return -1; }
+    if ((long long)narch + n - 1 < 1) { g_create_error = "dne_dense_novelty_pool_host: the pool is empty (one member, no archive point)"; return -1; }
+    dense_novelty::novelty_pool_host(bc, n, archive, narch, D, k, out);
     return 0;
 }
 

@@ -723,6 +723,18 @@ def dense_novelty_host(bc, archive, k, D=None):
     return out
 
 
+def dense_novelty_pool_host(bc, archive, k, D=None):
+    """dne_dense_novelty_pool_host: csrc/dense_novelty.h's pool form on the CPU (no GPU, no handle): each of the BCs [n][D] against the archive
+    [narch][D] (None or empty: no archive) and the other n - 1 BCs -> float64 [n]; D is bc's second dimension unless given"""
+    D = int(np.shape(bc)[-1] if D is None else D)
+    bc = _arr(bc, np.float32).reshape(-1, max(D, 1))
+    archive = _arr(np.zeros((0, max(D, 1))) if archive is None else archive, np.float32).reshape(-1, max(D, 1))
+    out = np.empty(bc.shape[0], np.float64)
+    _ck_host(load().dne_dense_novelty_pool_host(_ptr(bc, C.c_float), int(bc.shape[0]), _ptr(archive, C.c_float) if archive.size else None,
+                                                int(archive.shape[0]), D, int(k), _ptr(out, C.c_double)))
+    return out
+
+
 def _ptr(a, t):
     return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
 
@@ -1240,8 +1252,22 @@ class Engine:
         self._ck(self.lib.dne_dense_novelty(self.h, _ptr(bc, C.c_float), n, int(k), _ptr(out, C.c_double)))
         return out
 
+    def dense_novelty_pool(self, k, bc=None, n=None):
+        """GA-NS's novelty on BCs of D floats: the mean distance of each to its min(k, archive size + n - 1) nearest among the archive's points
+        and the OTHER n - 1 BCs, float64 [n] (k_dense_novelty_pool; 1 <= k <= DENSE_NOVELTY_KMAX).  bc=None scores the last evaluation's first
+        n members on the device."""
+        bc, n = self._dense_points(bc, n)
+        out = np.empty(max(n, 0), np.float64)
+        self._ck(self.lib.dne_dense_novelty_pool(self.h, _ptr(bc, C.c_float), n, int(k), _ptr(out, C.c_double)))
+        return out
+
+    def dense_archive_append_members(self, members):
+        """append the BCs of the last evaluation's members `members` (indices, in this order, repeats allowed) to the archive, device to device"""
+        members = _arr(members, np.int32).reshape(-1)
+        self._ck(self.lib.dne_dense_archive_append_members(self.h, _ptr(members, C.c_int32), int(members.size)))
+
     def dense_novelty_last_ms(self):
-        """the scoring kernel of the last dense_novelty call between two device events, milliseconds (-1 before the first)"""
+        """the scoring kernel of the last dense_novelty / dense_novelty_pool call between two device events, milliseconds (-1 before the first)"""
         self.lib.dne_dense_novelty_last_ms.restype = C.c_double
         return float(self.lib.dne_dense_novelty_last_ms(self.h))
 

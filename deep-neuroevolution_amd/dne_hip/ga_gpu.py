@@ -21,8 +21,11 @@ A dense policy of any small shape on the maze or the cart-pole runs dense_main o
 gym configuration), or a caller's engine of kind KIND_DENSE of any shape on its environment's game.  It is maze_main's loop -- _bank_loop, one text
 for both -- on dense_ga_build / dense_ga_eval / dense_ga_promote; selection_threshold 0 is random search.  Every other kind of engine with these
 models or games is refused as before.
+GA-NS on a dense policy is dense_ns_main, called directly (main and dense_main refuse exp['novelty_search'] on a dense run): maze_ns_main's loop on the
+dense bank, novelty over final states scored on the device (k_dense_novelty_pool).
 The loops share what is the same in them as plain functions (_validate_and_test, _record_rows, _end_generation; the bank loops also
-_resume_maze, _draw_generation, _member, _promote, _bank_evaluate; maze_main and dense_main the whole _bank_loop); the maze's engine, walls and
+_resume_maze, _draw_generation, _member, _promote, _bank_evaluate; maze_main and dense_main the whole _bank_loop; dense_main and dense_ns_main
+the engine's opening, _open_dense_run); the maze's engine, walls and
 noise table come from maze_run.open_engine.
 """
 import math
@@ -271,7 +274,10 @@ def _end_generation(state, log_dir, lens, rs=None):
 
 
 def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
-    """gpu_implementation/ga.py:114-275.  Returns (curr_solution_test, {'val': curr_solution_val}, state)."""
+    """gpu_implementation/ga.py:114-275.  Returns (curr_solution_test, {'val': curr_solution_val}, state).
+
+    exp['novelty_search'] runs GA-NS on game 'maze' under 'SimpleClassifier' (maze_ns_main).  On a dense run it raises NotImplementedError:
+    GA-NS on a dense policy is dense_ns_main, called directly."""
     maze, asked = exp.get('game') == 'maze', exp.get('model', 'Model')
     if _is_dense_run(engine, exp):                                  # a dense policy on a step environment: the bank of csrc/dense_ga.h
         return dense_main(log_dir, engine=engine, noise=noise, seed=seed, max_iters=max_iters, **exp)
@@ -546,6 +552,38 @@ def _is_dense_run(engine, exp):
     return (asked == LINEAR_MODEL and game in ('maze', CARTPOLE_GAME)) or (asked == MAZE_MODEL and game == CARTPOLE_GAME)
 
 
+def _open_dense_run(who, log_dir, engine, noise, exp):
+    """what dense_main and dense_ns_main (`who`) do before they look for a snapshot: the routing and its refusals, the log, the engine with
+    walls (on the maze), table and init scale.  Returns (engine, noise, game, model)."""
+    from .es_gpu import CARTPOLE_GAME, DENSE_GAMES, LINEAR_MODEL, dense_model_name
+    from .maze_run import attach_table, maze_file
+    game, asked = exp.get('game'), exp.get('model')
+    if engine is None:
+        if not _is_dense_run(None, exp):
+            raise NotImplementedError("model {!r} on game {!r}: without an engine {} runs {!r} on 'maze' and {!r}, and {!r} on {!r}".format(
+                asked, game, who, LINEAR_MODEL, CARTPOLE_GAME, MAZE_MODEL, CARTPOLE_GAME))
+        model = asked
+        engine = _lib.Engine(_lib.KIND_DENSE, 2, max_members=exp['population_size'], env=_lib.KIND_MAZE if game == 'maze' else _lib.KIND_CARTPOLE,
+                             hidden=DENSE_SIMPLE_HIDDEN if asked == MAZE_MODEL else (), nonlin='relu')
+    else:
+        if engine.kind != _lib.KIND_DENSE:
+            raise ValueError("{} needs an engine of kind KIND_DENSE ({}), the engine passed in is of kind {}".format(who, _lib.KIND_DENSE, engine.kind))
+        if DENSE_GAMES.get(engine.env_kind) != game:
+            raise ValueError("game {!r} asked for, the engine passed in (kind {} on environment kind {}) runs {!r}".format(
+                game, engine.kind, engine.env_kind, DENSE_GAMES.get(engine.env_kind)))
+        if engine.env_kind == _lib.KIND_PENDULUM:
+            raise NotImplementedError("game {!r}: this loop runs a KIND_DENSE engine on 'maze' and {!r}".format(game, CARTPOLE_GAME))
+        model = dense_model_name(engine)
+        if asked is not None and asked != model:
+            raise ValueError("model {!r} asked for, the engine passed in (kind {}) runs {!r}".format(asked, engine.kind, model))
+    tlogger.start(log_dir)
+    if engine.env_kind == _lib.KIND_MAZE:
+        engine.maze_set_walls(*_lib.load_maze(maze_file(exp)))
+    noise = attach_table(engine, noise)
+    engine.dense_ga_set_init_scale(policies.dense_scale_by(engine.env_kind, engine.hidden, engine.n_actions))
+    return engine, noise, game, model
+
+
 def dense_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
     """gpu_implementation/ga.py:114-275 over a dense policy of any small shape on the maze or the cart-pole (a DNE_KIND_DENSE engine,
     csrc/dense_ga.h): maze_main's loop (_bank_loop) on dense_ga_build / dense_ga_eval / dense_ga_promote.  Returns what main returns.
@@ -567,35 +605,11 @@ def dense_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
       snapshot     game, model (es_gpu.dense_model_name(engine), or 'SimpleClassifier' for the (16, 16) cart-pole route), algo = 'ga',
                    num_params = P and the stream's position; a resume continues bit for bit.  A resume under another game, model, P or
                    driver raises and names both.
-    exp['novelty_search'] is not built for a dense run (the archive calls are DNE_KIND_MAZE's)."""
-    from .es_gpu import CARTPOLE_GAME, DENSE_GAMES, LINEAR_MODEL, dense_model_name
-    from .maze_run import attach_table, maze_file
+    exp['novelty_search'] raises NotImplementedError here, as it does from main on a dense run: GA-NS on a dense policy is dense_ns_main below,
+    called directly."""
     if NS_KEY in exp:
         raise NotImplementedError("exp[{!r}] with a dense policy: GA-NS runs on game 'maze' under model {!r} only".format(NS_KEY, MAZE_MODEL))
-    game, asked = exp.get('game'), exp.get('model')
-    if engine is None:
-        if not _is_dense_run(None, exp):
-            raise NotImplementedError("model {!r} on game {!r}: without an engine dense_main runs {!r} on 'maze' and {!r}, and {!r} on {!r}".format(
-                asked, game, LINEAR_MODEL, CARTPOLE_GAME, MAZE_MODEL, CARTPOLE_GAME))
-        model = asked
-        engine = _lib.Engine(_lib.KIND_DENSE, 2, max_members=exp['population_size'], env=_lib.KIND_MAZE if game == 'maze' else _lib.KIND_CARTPOLE,
-                             hidden=DENSE_SIMPLE_HIDDEN if asked == MAZE_MODEL else (), nonlin='relu')
-    else:
-        if engine.kind != _lib.KIND_DENSE:
-            raise ValueError("dense_main needs an engine of kind KIND_DENSE ({}), the engine passed in is of kind {}".format(_lib.KIND_DENSE, engine.kind))
-        if DENSE_GAMES.get(engine.env_kind) != game:
-            raise ValueError("game {!r} asked for, the engine passed in (kind {} on environment kind {}) runs {!r}".format(
-                game, engine.kind, engine.env_kind, DENSE_GAMES.get(engine.env_kind)))
-        if engine.env_kind == _lib.KIND_PENDULUM:
-            raise NotImplementedError("game {!r}: this loop runs a KIND_DENSE engine on 'maze' and {!r}".format(game, CARTPOLE_GAME))
-        model = dense_model_name(engine)
-        if asked is not None and asked != model:
-            raise ValueError("model {!r} asked for, the engine passed in (kind {}) runs {!r}".format(asked, engine.kind, model))
-    tlogger.start(log_dir)
-    if engine.env_kind == _lib.KIND_MAZE:
-        engine.maze_set_walls(*_lib.load_maze(maze_file(exp)))
-    noise = attach_table(engine, noise)
-    engine.dense_ga_set_init_scale(policies.dense_scale_by(engine.env_kind, engine.hidden, engine.n_actions))
+    engine, noise, game, model = _open_dense_run('dense_main', log_dir, engine, noise, exp)
     rs = np.random.RandomState(seed)
     all_tstart = time.time()
     state = _resume_maze(log_dir, ALGO, rs, game, model, engine.P)
@@ -705,6 +719,113 @@ def maze_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp
             _promote(engine.maze_ga_promote, [descriptor[id(o)] for o in selected])
         parents = new_parents
         state.archive = engine.maze_archive()
+        dt = time.time() - tstart_iteration
+        state.time_elapsed += dt
+        _record_rows(state, power, rewards, T, v, dt, all_tstart)
+        for key, val in (('NoveltyMean', float(np.mean(novelty))), ('NoveltyMax', float(np.max(novelty))),
+                         ('ArchiveSize', int(state.archive.shape[0])), ('BestDistanceToGoal', -float(np.max(rewards)))):
+            tlogger.record_tabular(key, val)
+        tlogger.dump_tabular()
+        _end_generation(state, log_dir, lens, rs)
+        if state.timesteps_so_far >= exp['timesteps']:
+            break
+    return float(state.curr_solution_test), {'val': float(state.curr_solution_val)}, state
+
+
+# ---------------------------------------------------------------------------------------------- GA-NS on a dense policy
+def dense_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
+    """GA-NS over a dense policy of any small shape on the maze or the cart-pole (a DNE_KIND_DENSE engine): maze_ns_main's loop, its decisions
+    and its tabular keys, on the dense bank (dense_ga_*) with novelty over final states (csrc/dense_novelty.h, the pool form).
+    exp['novelty_search'] = {'k': 1 .. DENSE_NOVELTY_KMAX, 'archive_prob': 0 .. 1}.  Returns what main returns.  DESIGN.md section 17c.
+
+    Called directly: main and dense_main raise NotImplementedError for exp['novelty_search'] on a dense run.  The engine is opened and checked
+    as dense_main does it (same routing, same refusals), the init scale is policies.dense_scale_by of the shape.  What differs from maze_ns_main:
+      draws        the two whole-array draws, then rs.random_sample(n) < archive_prob; on the cart-pole the generation's environment seeds
+                   follow (drawn by the evaluation, as every evaluation call of dense_main draws them), and each validation and test call draws
+                   its own.  On the maze nothing more is drawn: a (16, 16) relu engine on the maze consumes maze_ns_main's stream draw for draw.
+      BC           section 17b's: one episode's final state record cast to D floats (maze (x, y), cart-pole (x, x_dot, theta, theta_dot)).  On
+                   the cart-pole it is the ONE episode the generation ran under its drawn seed; no mean BC over several episodes.
+      scoring      one dense_ga_eval, then dense_novelty_pool(k) on the BCs of that evaluation, on the device; the masked members are appended
+                   afterwards by one dense_archive_append_members.
+      limits       dense_main's: a generation and the validation episodes under state.tslimit, at most the environment's own limit; the test
+                   episodes at the environment's own limit.  num_frames counts steps.
+      snapshot     algo = 'ga_ns', game, model, num_params = P, k, archive_prob, the archive [A][D] and the stream; a resume pushes the archive
+                   back with dense_archive_append and continues bit for bit.  A resume under another algo, game, model, P, k or archive_prob
+                   raises and names both sides."""
+    ns = exp[NS_KEY]
+    k, prob = int(ns['k']), float(ns['archive_prob'])
+    if not 1 <= k <= _lib.DENSE_NOVELTY_KMAX:
+        raise ValueError("novelty_search k = {}: expected 1 .. DENSE_NOVELTY_KMAX = {}".format(k, _lib.DENSE_NOVELTY_KMAX))
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError("novelty_search archive_prob = {!r}: expected a probability".format(ns['archive_prob']))
+    n, T, V = exp['population_size'], exp['selection_threshold'], exp['validation_threshold']
+    engine, noise, game, model = _open_dense_run('dense_ns_main', log_dir, engine, noise, exp)
+    rs = np.random.RandomState(seed)
+    all_tstart = time.time()
+    engine.dense_archive_clear()
+    state = _resume_maze(log_dir, ALGO_NS, rs, game, model, engine.P)
+    if state is None:
+        state = TrainingState(exp)
+        state.archive, state.stream = np.zeros((0, engine.dense_bc_dim()), np.float32), None
+    else:
+        if (state.k, state.archive_prob) != (k, prob):
+            raise ValueError("snapshot.pkl in {} holds k {}, archive_prob {!r}; this run is k {}, archive_prob {!r}".format(
+                log_dir, state.k, state.archive_prob, k, prob))
+        if len(state.archive):
+            engine.dense_archive_append(state.archive)
+    state.game, state.model, state.algo, state.num_params, state.k, state.archive_prob = game, model, ALGO_NS, engine.P, k, prob
+    if 'load_population' in exp:
+        state.copy_population(exp['load_population'])
+    parents = [o.seeds for o in state.population[:T]]               # the genomes of the bank's parents: the top T by novelty, no elite carried
+    bank = _DenseBank(engine, rs)
+    if parents:
+        bank.build(parents)
+    descriptor = {}                                                 # id(Offspring) -> its descriptor over the bank as it is now
+
+    def evaluate(individuals, tslimit):
+        return _bank_evaluate(bank, [descriptor[id(o)] for o in individuals], tslimit)
+
+    iters = 0
+    while max_iters is None or iters < max_iters:
+        iters += 1
+        tstart_iteration = time.time()
+        if state.timesteps_so_far >= exp['timesteps']:
+            break
+        assert (len(parents) == 0 and (state.it == 0 or T == 0)) or len(parents) == T
+        power = state.sample(state.mutation_power)
+        of, idx = _draw_generation(rs, n, len(parents), len(noise.noise) - engine.P + 1)
+        archived = np.flatnonzero(rs.random_sample(n) < prob).astype(np.int32)
+        rets, lens = bank.eval(of, idx, np.full(n, power, np.float32), state.tslimit)
+        raw = np.asarray(engine.dense_novelty_pool(k), np.float64)  # against the archive as it was before this generation, and the generation
+        novelty = np.where(np.isfinite(raw), raw, 0.0)
+        if archived.size:
+            engine.dense_archive_append_members(archived)
+        state.num_frames += int(lens.sum())
+        state.it += 1
+        rewards = np.asarray(rets, np.float64)
+        by_novelty = np.argsort(-novelty, kind='stable')            # (-novelty, arrival index)
+        by_reward = engine.ga_select(np.asarray(rets, np.float32), n)
+        offspring = {}                                              # member index -> its Offspring
+        descriptor.clear()
+        for i in list(by_novelty[:T]) + list(by_reward[:V]):
+            i = int(i)
+            if i not in offspring:
+                d, genome = _member(i, of, idx, power, parents)
+                offspring[i] = Offspring(genome, [float(rets[i])], [int(lens[i])])
+                offspring[i].novelty = float(novelty[i])
+                descriptor[id(offspring[i])] = d
+        selected = [offspring[int(i)] for i in by_novelty[:T]]
+        validation_population = [offspring[int(i)] for i in by_reward[:V]]
+        state.population = selected + [o for o in validation_population if not any(o is s for s in selected)]
+        v = _validate_and_test(state, exp, validation_population, evaluate, int(lens.sum()))
+        # the next parents on the device: the top T by novelty, every one a root (generation 0) or a child of the bank as it is
+        new_parents = [o.seeds for o in selected]
+        if new_parents and not parents:
+            bank.build(new_parents)
+        elif new_parents:
+            _promote(bank.promote, [descriptor[id(o)] for o in selected])
+        parents = new_parents
+        state.archive = engine.dense_archive()
         dt = time.time() - tstart_iteration
         state.time_elapsed += dt
         _record_rows(state, power, rewards, T, v, dt, all_tstart)

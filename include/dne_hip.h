@@ -632,6 +632,22 @@ int dne_dense_novelty(dne_handle *h, const float *bc /*[n][D], or NULL*/, int n,
 double dne_dense_novelty_last_ms(dne_handle *h);
 int dne_dense_novelty_host(const float *bc, int n, const float *archive /*[narch][D]*/, int narch, int D, int k, double *out);
 int dne_dense_bc_host(int env_kind, const double *rec /*[n][S]*/, int n, float *bc /*[n][D]*/);
+/* Pool novelty on a dense policy (GA-NS): section 12c's contract with the point above.  Member p of the n members is
+ * scored against the archive's A points at combined slots 0 .. A - 1 followed by the n members at combined slots A .. A + n - 1, the combined
+ * slot A + p left out -- by index, not by value.  Distances, keys and the sequential sum are dne_dense_novelty's; the order is (key, combined
+ * slot), so an archive point comes before a population point at the same distance; kk = min(k, A + n - 1).  A NaN member gets a NaN novelty.
+ * bc == NULL reads the BCs of the last evaluation's first n members on the device (dne_dense_final_state's rule for n), and those n are the
+ * population; a host bc takes any n >= 1.  dne_dense_novelty_pool_host is the same header on the CPU (narch may be 0 and archive NULL then,
+ * any k >= 1, D 2 or 4).  dne_dense_archive_append_members appends the BCs of the last evaluation's members members[0 .. count - 1], in that
+ * order, device to device (k_dense_archive_gather); indices may repeat and are checked before anything is launched.
+ * Refused by name, the archive left as it was: an engine of another kind, n < 1, the NULL form beyond the last evaluation's members (or before
+ * any), k < 1, k > DNE_DENSE_NOVELTY_KMAX, an empty pool (n = 1 and A = 0), a missing output buffer; for the gather count < 1 and an index
+ * outside the last evaluation's members; for the host twin a missing buffer and D outside {2, 4}.  dne_maze_novelty_pool and
+ * dne_maze_archive_append_members keep refusing this kind.  dne_dense_novelty_last_ms reports the scoring kernel of the last
+ * dne_dense_novelty or dne_dense_novelty_pool. */
+int dne_dense_novelty_pool(dne_handle *h, const float *bc /*[n][D], or NULL*/, int n, int k, double *out /*[n]*/);
+int dne_dense_novelty_pool_host(const float *bc, int n, const float *archive /*[narch][D], or NULL with narch 0*/, int narch, int D, int k, double *out);
+int dne_dense_archive_append_members(dne_handle *h, const int32_t *members /*[count]*/, int count);
 
 /* ---- Deep-GA on the hard maze (csrc/maze_ga.h) -----------------------------------------------
  * gpu_implementation/ga.py on SimpleClassifier.  A genome is (idx0, (idx1, power1), ...) as seeds[] / powers[] (powers[0] is not read):
