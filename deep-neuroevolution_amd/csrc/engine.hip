@@ -39,6 +39,7 @@
 #include "dense.h"
 #include "dense_ga.h"
 #include "dense_novelty.h"
+#include "ram_novelty.h"
 
 using namespace dne;
 
@@ -749,6 +750,14 @@ struct dne_handle {
     uint8_t *nov_idx = nullptr; size_t nov_idx_cap = 0;
     uint8_t *nov_rows = nullptr; size_t nov_rows_cap = 0;
     unsigned long long *nov_acc = nullptr; size_t nov_acc_cap = 0;   // [n][narch][2] sums of a row-split distance launch
+    // pool novelty over final RAM states (csrc/ram_novelty.h): how many members the last evaluation left one 128-byte row each in bc (0: none
+    // yet, or bc holds full trajectories), the caller's index of each row (dne_ga_eval* reorders its members), and the calls' device scratch
+    int ram_last_n = 0; std::vector<int32_t> ram_last_caller;
+    uint8_t *ram_pts = nullptr; size_t ram_pts_cap = 0;      // a host bc's rows, or the recorded rows in the caller's order
+    double *ram_out = nullptr; size_t ram_out_cap = 0;
+    int32_t *ram_nb = nullptr; size_t ram_nb_cap = 0;        // [n][kk] neighbours
+    int32_t *ram_idx = nullptr; size_t ram_idx_cap = 0;      // bc rows to gather
+    double ram_last_ms = -1.0;
     // RCCL communicator (dne_comm_init); the library is opened on demand
     void *rccl_lib = nullptr; void *comm = nullptr; int comm_rank = 0, comm_size = 1;
     bool comm_borrowed = false;      // dne_comm_share: the communicator belongs to another handle of this process
@@ -2271,6 +2280,7 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
     // when the whole buffer is about to be downloaded
     if (bc_mode == 1 && bc_out) HCHECK(h, hipMemsetAsync(h->bc, 0, (size_t)n * h->cfg.bc_max_steps * 128, h->stream));
     if (bc_mode == 2) HCHECK(h, hipMemsetAsync(h->bc, 0, (size_t)n * 128, h->stream));
+    h->ram_last_n = 0;   // (set again at the end: an evaluation that fails half way leaves no points to score)
     HCHECK(h, hipEventRecord(h->ev_a, h->stream));
     HCHECK(h, hipMemcpyAsync(h->seeds, env_seed, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     launch_env_reset(h, n);
@@ -2383,6 +2393,11 @@ static int eval_core(dne_handle *h, int n, int gsize, int tslimit, const uint32_
     P.fc_full_kind = fc_full_kind(ev);
     P.fc_full_union_ms = 0;
     if (prof && reduce_profile(h, evs)) return -1;
+    if (bc_mode == 2) {   // dne_ram_novelty_pool(bc = NULL) / dne_archive_append_members: row j of bc is the caller's member ram_last_caller[j] --
+        h->ram_last_n = n;   // j itself for a caller of this function's own entry points; ga_eval_impl, which reorders its members, says otherwise
+        h->ram_last_caller.resize(n);
+        for (int j = 0; j < n; j++) h->ram_last_caller[j] = j;
+    }
     return 0;
 }
 
@@ -4434,6 +4449,7 @@ static int ga_eval_impl(dne_handle *h, const int32_t *co, const int64_t *seeds, 
     h->host_caller.assign(order.begin(), order.end());
     std::vector<float> pret(n), psg(n); std::vector<int32_t> plen(n); std::vector<uint8_t> pbc(bc ? (size_t)n * 128 : 0);
     if (eval_core(h, n, 1, tslimit, pseed.data(), pret.data(), psg.data(), plen.data(), bc ? pbc.data() : nullptr)) return -1;
+    if (h->ram_last_n == n) h->ram_last_caller.assign(order.begin(), order.end());
     for (int j = 0; j < n; j++) {
         const int i = order[j];
         returns[i] = pret[j]; lengths[i] = plen[j];
@@ -5065,4 +5081,149 @@ extern "C" int dne_novelty_batch(dne_handle *h, const uint8_t *archive, const in
     for (int i = 0; i < n; i++)
         if (lengths[i] < 1 || lengths[i] > h->cfg.bc_max_steps) return h->fail("member %d: trajectory length %d outside the recorded capacity %d", i, lengths[i], h->cfg.bc_max_steps);
     return novelty_run(h, nullptr, lengths, n, k, out);
+}
+
+// ---- pool novelty over final RAM states (GA-NS on Atari; csrc/ram_novelty.h) ----------------------------------------
+// what every call below needs of the resident archive: empty, or 128 bytes wide with every entry of length 1 (entry e is then row e)
+static int ram_check_archive(dne_handle *h, const char *call) {
+    const size_t A = h->arch_len_host.size();
+    if (A && h->arch_dim != ram_novelty::ROW) return h->fail("%s: the archive holds entries of width %d, a RAM point has %d bytes", call, h->arch_dim, ram_novelty::ROW);
+    for (size_t e = 0; e < A; e++)
+        if (h->arch_len_host[e] != 1) return h->fail("%s: archive entry %zu has length %d, a RAM point is an entry of length 1", call, e, h->arch_len_host[e]);
+    return 0;
+}
+
+// the engine keeps one final RAM row per member of its last evaluation in bc
+static int ram_check_recorded(dne_handle *h, const char *call) {
+    if (!h->bc) return h->fail("%s: the engine was created with record_bc = 0, it keeps no final RAM states", call);
+    if (es_like(h->L.kind) && !h->cfg.bc_final_only)
+        return h->fail("%s: the engine records full trajectories (an ES kind without bc_final_only), not one final RAM state per member", call);
+    if (h->ram_last_n < 1) return h->fail("%s: no evaluation has left final RAM states yet", call);
+    return 0;
+}
+
+// rows[i] = the bc row of the caller's member members[i] of the last evaluation (members == NULL: members 0 .. count - 1); identity reports
+// whether that is rows[i] = i
+static void ram_rows_of(dne_handle *h, const int32_t *members, int count, std::vector<int32_t> &rows, bool &identity) {
+    std::vector<int32_t> inv(h->ram_last_n);
+    for (int j = 0; j < h->ram_last_n; j++) inv[h->ram_last_caller[j]] = j;
+    rows.resize(count);
+    identity = true;
+    for (int i = 0; i < count; i++) { rows[i] = inv[members ? members[i] : i]; identity = identity && rows[i] == i; }
+}
+
+extern "C" int dne_ram_novelty_pool(dne_handle *h, const uint8_t *bc, int n, int k, double *out, int32_t *neighbours) {
+    DeviceGuard dg(h);
+    const char *call = "dne_ram_novelty_pool";
+    MAZE_REFUSE(h, call);
+    if (n < 1) return h->fail("%s: n = %d, at least one member is needed", call, n);
+    if (k < 1) return h->fail("%s: k = %d, at least one neighbour is needed", call, k);
+    if (k > DNE_RAM_NOVELTY_KMAX) return h->fail("%s: k = %d, the kernel keeps at most DNE_RAM_NOVELTY_KMAX = %d neighbours", call, k, DNE_RAM_NOVELTY_KMAX);
+    if (!out) return h->fail("%s: no output buffer", call);
+    if (!bc) {
+        if (ram_check_recorded(h, call)) return -1;
+        if (n > h->ram_last_n) return h->fail("%s: %d members asked for, the last evaluation ran %d", call, n, h->ram_last_n);
+    }
+    if (ram_check_archive(h, call)) return -1;
+    const size_t A = h->arch_len_host.size();
+    if (A + (size_t)n - 1 < 1) return h->fail("%s: the pool is empty (one member, no archive point)", call);
+    if (A + (size_t)n > (size_t)INT_MAX) return h->fail("%s: %zu combined slots would not fit the kernel's 31-bit slot field", call, A + (size_t)n);
+    const int narch = (int)A, kk = (int)std::min<size_t>((size_t)k, A + (size_t)n - 1);
+    const uint8_t *pts = nullptr;
+    if (bc) {
+        if (novelty_grow(h, h->ram_pts, h->ram_pts_cap, (size_t)n * ram_novelty::ROW, "ram_novelty_points")) return -1;
+        if (copy_h2d(h, h->ram_pts, bc, (size_t)n * ram_novelty::ROW)) return -1;
+        pts = h->ram_pts;
+    } else {
+        std::vector<int32_t> rows; bool identity;
+        ram_rows_of(h, nullptr, n, rows, identity);
+        pts = h->bc;
+        if (!identity) {   // the evaluation reordered its members: the population in the caller's order, device to device
+            if (novelty_grow(h, h->ram_pts, h->ram_pts_cap, (size_t)n * ram_novelty::ROW, "ram_novelty_points")) return -1;
+            if (novelty_grow(h, h->ram_idx, h->ram_idx_cap, (size_t)n, "ram_novelty_rows")) return -1;
+            HCHECK(h, hipMemcpyAsync(h->ram_idx, rows.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+            hipLaunchKernelGGL(ram_novelty::k_ram_archive_gather, dim3((unsigned)(((size_t)n * 8 + 255) / 256)), dim3(256), 0, h->stream,
+                               (const uint32_t *)h->bc, (const int32_t *)h->ram_idx, n, (uint32_t *)h->ram_pts);
+            HCHECK(h, hipGetLastError());
+            HCHECK(h, hipStreamSynchronize(h->stream));   // rows goes away
+            pts = h->ram_pts;
+        }
+    }
+    if (novelty_grow(h, h->ram_out, h->ram_out_cap, (size_t)n, "ram_novelty_out")) return -1;
+    if (neighbours && novelty_grow(h, h->ram_nb, h->ram_nb_cap, (size_t)n * kk, "ram_novelty_neighbours")) return -1;
+    HCHECK(h, hipEventRecord(h->ev_a, h->stream));
+    hipLaunchKernelGGL(ram_novelty::k_ram_novelty_pool, dim3((n + ram_novelty::MEMBERS - 1) / ram_novelty::MEMBERS), dim3(ram_novelty::THREADS), 0, h->stream,
+                       (const uint32_t *)pts, n, (const uint32_t *)(narch ? h->arch : nullptr), narch, kk, h->ram_out, neighbours ? h->ram_nb : (int32_t *)nullptr);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipEventRecord(h->ev_b, h->stream));
+    HCHECK(h, hipMemcpyAsync(out, h->ram_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (neighbours) HCHECK(h, hipMemcpyAsync(neighbours, h->ram_nb, (size_t)n * kk * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    float ms = 0;
+    HCHECK(h, hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
+    h->ram_last_ms = ms;
+    return 0;
+}
+
+// archive entry A + i = the final RAM of the last evaluation's member members[i] (the caller's indices), device to device; the indices are
+// checked before anything is launched, and the gather follows archive_reserve's reallocation on the engine's stream
+extern "C" int dne_archive_append_members(dne_handle *h, const int32_t *members, int count) {
+    DeviceGuard dg(h);
+    const char *call = "dne_archive_append_members";
+    MAZE_REFUSE(h, call);
+    if (count < 1) return h->fail("%s: count = %d, at least one member is needed", call, count);
+    if (!members) return h->fail("%s: no member indices", call);
+    if (ram_check_recorded(h, call)) return -1;
+    for (int i = 0; i < count; i++)
+        if (members[i] < 0 || members[i] >= h->ram_last_n)
+            return h->fail("%s: index %d is member %d, the last evaluation ran %d", call, i, members[i], h->ram_last_n);
+    if (h->arch_dim && h->arch_dim != ram_novelty::ROW) return h->fail("dne_archive_append: entry width %d, archive holds %d", ram_novelty::ROW, h->arch_dim);
+    const size_t A = h->arch_len_host.size();
+    if (A + (size_t)count > (size_t)INT_MAX) return h->fail("%s: %zu entries would not fit an int", call, A + (size_t)count);
+    std::vector<int32_t> rows; bool identity;
+    ram_rows_of(h, members, count, rows, identity);
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    if (archive_reserve(h, h->arch_rows + count, A + count, ram_novelty::ROW)) return -1;
+    if (novelty_grow(h, h->ram_idx, h->ram_idx_cap, (size_t)count, "ram_novelty_rows")) return -1;
+    h->arch_dim = ram_novelty::ROW; h->arch_pitch = row_pitch(ram_novelty::ROW);
+    HCHECK(h, hipMemcpyAsync(h->ram_idx, rows.data(), (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(ram_novelty::k_ram_archive_gather, dim3((unsigned)(((size_t)count * 8 + 255) / 256)), dim3(256), 0, h->stream,
+                       (const uint32_t *)h->bc, (const int32_t *)h->ram_idx, count, (uint32_t *)(h->arch + h->arch_rows * h->arch_pitch));
+    HCHECK(h, hipGetLastError());
+    for (int i = 0; i < count; i++) { h->arch_row0_host.push_back((int64_t)h->arch_rows + i); h->arch_len_host.push_back(1); }
+    HCHECK(h, hipMemcpyAsync(h->arch_row0 + A, h->arch_row0_host.data() + A, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    HCHECK(h, hipMemcpyAsync(h->arch_len + A, h->arch_len_host.data() + A, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));   // rows and the caller's buffer are free again
+    h->arch_rows += count;
+    return 0;
+}
+
+extern "C" int dne_archive_get_points(dne_handle *h, int first, int count, uint8_t *out) {
+    DeviceGuard dg(h);
+    const char *call = "dne_archive_get_points";
+    MAZE_REFUSE(h, call);
+    const size_t A = h->arch_len_host.size();
+    if (count < 1) return h->fail("%s: count = %d, at least one entry is needed", call, count);
+    if (first < 0 || (size_t)first + (size_t)count > A) return h->fail("%s: entries %d .. %lld asked for, the archive holds %zu", call, first, (long long)first + count - 1, A);
+    if (!out) return h->fail("%s: no buffer", call);
+    if (h->arch_dim != ram_novelty::ROW) return h->fail("%s: the archive holds entries of width %d, a RAM point has %d bytes", call, h->arch_dim, ram_novelty::ROW);
+    for (int e = first; e < first + count; e++)
+        if (h->arch_len_host[e] != 1) return h->fail("%s: archive entry %d has length %d, a RAM point is an entry of length 1", call, e, h->arch_len_host[e]);
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    return copy_d2h(h, out, h->arch + (size_t)h->arch_row0_host[first] * h->arch_pitch, (size_t)count * ram_novelty::ROW);
+}
+
+extern "C" double dne_ram_novelty_last_ms(dne_handle *h) { return h->episodic() ? -1.0 : h->ram_last_ms; }
+
+// the same header on the CPU: no handle, no GPU
+extern "C" int dne_ram_novelty_pool_host(const uint8_t *bc, int n, const uint8_t *archive, int narch, int k, double *out, int32_t *neighbours) {
+    const char *call = "dne_ram_novelty_pool_host";
+    if (!bc || !out || (narch > 0 && !archive)) { g_create_error = std::string(call) + ": a buffer is missing"; return -1; }
+    if (n < 1) { g_create_error = std::string(call) + ": n = " + std::to_string(n) + ", at least one member is needed"; return -1; }
+    if (narch < 0) { g_create_error = std::string(call) + ": narch = " + std::to_string(narch); return -1; }
+    if (k < 1) { g_create_error = std::string(call) + ": k = " + std::to_string(k) + ", at least one neighbour is needed"; return -1; }
+    if ((long long)narch + n - 1 < 1) { g_create_error = std::string(call) + ": the pool is empty (one member, no archive point)"; return -1; }
+    if ((long long)narch + n > (long long)INT_MAX) { g_create_error = std::string(call) + ": " + std::to_string((long long)narch + n) + " combined slots would not fit the 31-bit slot field"; return -1; }
+    ram_novelty::novelty_pool_host(bc, n, archive, narch, k, out, neighbours);
+    return 0;
 }

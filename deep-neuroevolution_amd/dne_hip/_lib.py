@@ -16,6 +16,7 @@ KIND_ES, KIND_GA, KIND_GA_LARGE = 0, 1, 2   # DNE_KIND_* (include/dne_hip.h); 2 
 KIND_ES_VBN = 3   # the GPU tree's ModelVirtualBN in its own flat layout (models/batchnorm.py:52-123): the ES kind's network and entry points
 KIND_MAZE = 4     # the GPU tree's hard maze under SimpleClassifier (gym_tensorflow/maze/, models/simple.py:29-35): whole episodes in one kernel (csrc/maze.h)
 MAZE_OBS, MAZE_STEPS, MAZE_TRACE_W, MAZE_MAX_WALLS = 11, 400, 16, 64   # observation width, tf_maze.cpp's episode length, floats per trace row, walls the kernel takes
+RAM_NOVELTY_KMAX, RAM_NOVELTY_TILE, RAM_NOVELTY_MEMBERS = 32, 256, 4   # DNE_RAM_NOVELTY_* (csrc/ram_novelty.h): neighbours a lane keeps, combined slots per LDS tile, members per workgroup
 DENSE_NOVELTY_KMAX = 32   # DNE_DENSE_NOVELTY_KMAX = DNE_MAZE_NOVELTY_KMAX (csrc/dense_novelty.h uses maze_novelty.h's list)
 MAZE_NOVELTY_KMAX, MAZE_NOVELTY_TILE, MAZE_ARCHIVE_CAP0 = 32, 1024, 64   # csrc/maze_novelty.h: neighbours a lane keeps, archive points per LDS tile; the archive's first allocation (engine.hip)
 KIND_CARTPOLE = 5   # the GPU tree's gym configuration: gym.CartPole-v1 under SimpleClassifier on 4 inputs, whole episodes in one kernel (csrc/cartpole.h)
@@ -89,7 +90,7 @@ class Profile(C.Structure):
 
 def build(force=False):
     """Compile libdne_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h", "cartpole.h", "pendulum.h", "mjmaze.h", "step_env.h", "dense.h", "dense_ga.h", "dense_novelty.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h", "cartpole.h", "pendulum.h", "mjmaze.h", "step_env.h", "dense.h", "dense_ga.h", "dense_novelty.h", "ram_novelty.h")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dne_hip.h"))
     if os.environ.get("DNE_LIB_PATH"):
         # another build of the same ABI was asked for by name: `make` only knows the in-tree library, so running it here would
@@ -735,6 +736,20 @@ def dense_novelty_pool_host(bc, archive, k, D=None):
     return out
 
 
+def ram_novelty_pool_host(bc, archive, k, neighbours=False):
+    """dne_ram_novelty_pool_host: csrc/ram_novelty.h on the CPU (no GPU, no handle): each of the RAM points uint8 [n][128] against the archive
+    [narch][128] (None or empty: no archive) and the other n - 1 points -> float64 [n]; with neighbours also int32 [n][min(k, narch + n - 1)],
+    each member's nearest combined slots in the contract's order"""
+    bc = _arr(bc, np.uint8).reshape(-1, RAM_BYTES)
+    archive = _arr(np.zeros((0, RAM_BYTES), np.uint8) if archive is None else archive, np.uint8).reshape(-1, RAM_BYTES)
+    n, A = int(bc.shape[0]), int(archive.shape[0])
+    out = np.empty(n, np.float64)
+    nb = np.empty((n, max(min(int(k), A + n - 1), 0)), np.int32) if neighbours else None
+    _ck_host(load().dne_ram_novelty_pool_host(_ptr(bc, C.c_uint8), n, _ptr(archive, C.c_uint8) if A else None, A, int(k), _ptr(out, C.c_double),
+                                              _ptr(nb, C.c_int32)))
+    return (out, nb) if neighbours else out
+
+
 def _ptr(a, t):
     return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
 
@@ -983,6 +998,7 @@ class Engine:
         self._ck(self.lib.dne_ga_eval(self.h, _ptr(co, C.c_int32), _ptr(flat, C.c_int64), n, C.c_float(sigma), int(tslimit),
                                       _ptr(seeds, C.c_uint32), _ptr(ret, C.c_float), _ptr(sg, C.c_float), _ptr(ln, C.c_int32),
                                       _ptr(bc, C.c_uint8)))
+        self._last_eval_n = n
         return (ret, sg, ln, bc) if want_bc else (ret, sg, ln)
 
     # ---- the hard maze (KIND_MAZE)
@@ -1449,6 +1465,7 @@ class Engine:
         self._ck(self.lib.dne_ga_eval_powers(self.h, _ptr(co, C.c_int32), _ptr(flat, C.c_int64), _ptr(pw, C.c_float), n, int(tslimit),
                                              _ptr(seeds, C.c_uint32), _ptr(ret, C.c_float), _ptr(sg, C.c_float), _ptr(ln, C.c_int32),
                                              _ptr(bc, C.c_uint8)))
+        self._last_eval_n = n
         return (ret, sg, ln, bc) if want_bc else (ret, sg, ln)
 
     def ga_rebuild(self, slot, seeds, sigma, copy_out=True):
@@ -1577,6 +1594,8 @@ class Engine:
         """Bring the device-resident archive up to `archive`.  The master's archive only grows (dist.py:93-98) and the
         transport hands back the same entry objects on every call, so entries are recognised by identity and only new ones
         are uploaded; any other list (fresh arrays, a shorter archive) is uploaded from scratch."""
+        if archive is None:                  # the resident archive as it stands (what archive_append_members / archive_append_points built)
+            return
         have = getattr(self, "_arch_objs", [])
         if len(have) > len(archive) or any(a is not b for a, b in zip(have, archive)):
             self._ck(self.lib.dne_archive_clear(self.h))
@@ -1586,6 +1605,56 @@ class Engine:
             u = u.reshape(-1, u.shape[-1])
             self._ck(self.lib.dne_archive_append(self.h, _ptr(u, C.c_uint8), int(u.shape[0]), int(u.shape[1])))
         self._arch_objs = list(archive)      # references keep the identities from being recycled
+
+    # ---- pool novelty over final RAM states (GA-NS on Atari; csrc/ram_novelty.h)
+    def ram_novelty_pool(self, k, bc=None, n=None, neighbours=False):
+        """dne_ram_novelty_pool: the mean distance of each of n RAM points to its kk = min(k, A + n - 1) nearest among the resident archive's A
+        points and the OTHER n - 1 points, float64 [n] (k_ram_novelty_pool; 1 <= k <= RAM_NOVELTY_KMAX).  bc=None scores the last evaluation's
+        first n members (all of them by default) where the evaluation left their final RAM, in the caller's member order; bc uint8 [n][128]
+        scores host points.  With neighbours also int32 [n][kk]: each member's nearest combined slots, in order."""
+        if bc is not None:
+            bc = _arr(bc, np.uint8).reshape(-1, RAM_BYTES)
+            n = int(bc.shape[0])
+        elif n is None:
+            n = self._last_eval_n
+        n = int(n)
+        out = np.empty(max(n, 0), np.float64)
+        kk = max(min(int(k), self.archive_size() + n - 1), 0)
+        nb = np.empty((max(n, 0), kk), np.int32) if neighbours else None
+        self._ck(self.lib.dne_ram_novelty_pool(self.h, _ptr(bc, C.c_uint8), n, int(k), _ptr(out, C.c_double), _ptr(nb, C.c_int32)))
+        return (out, nb) if neighbours else out
+
+    def archive_append_members(self, members):
+        """dne_archive_append_members: the final RAM of the last evaluation's members `members` (the caller's indices, in that order, repeats
+        allowed) become archive entries of length 1, device to device"""
+        members = _arr(np.asarray(members).reshape(-1), np.int32)
+        self._ck(self.lib.dne_archive_append_members(self.h, _ptr(members, C.c_int32), int(members.size)))
+        self._arch_objs = list(getattr(self, "_arch_objs", [])) + [object() for _ in range(members.size)]   # entries no host list holds
+
+    def archive_get_points(self, first, count):
+        """dne_archive_get_points: entries first .. first + count - 1 of the resident archive, each of length 1, as uint8 [count][128]"""
+        out = np.empty((max(int(count), 0), RAM_BYTES), np.uint8)
+        self._ck(self.lib.dne_archive_get_points(self.h, int(first), int(count), _ptr(out, C.c_uint8)))
+        return out
+
+    def archive_size(self):
+        return int(self.lib.dne_archive_size(self.h))
+
+    def archive_clear(self):
+        self._ck(self.lib.dne_archive_clear(self.h))
+        self._arch_objs = []
+
+    def archive_append_points(self, points):
+        """each row of points uint8 [m][128] becomes an archive entry of length 1 (dne_archive_append, one call per row)"""
+        points = _arr(points, np.uint8).reshape(-1, RAM_BYTES)
+        for row in points:
+            self._ck(self.lib.dne_archive_append(self.h, _ptr(row, C.c_uint8), 1, RAM_BYTES))
+        self._arch_objs = list(getattr(self, "_arch_objs", [])) + [object() for _ in range(len(points))]
+
+    def ram_novelty_last_ms(self):
+        """the scoring kernel of the last ram_novelty_pool call between two device events, milliseconds (-1 before the first)"""
+        self.lib.dne_ram_novelty_last_ms.restype = C.c_double
+        return float(self.lib.dne_ram_novelty_last_ms(self.h))
 
     def novelty(self, archive, bc, k):
         bc = _arr(bc, np.uint8).reshape(-1, np.asarray(bc).shape[-1])

@@ -23,6 +23,8 @@ for both -- on dense_ga_build / dense_ga_eval / dense_ga_promote; selection_thre
 models or games is refused as before.
 GA-NS on a dense policy is dense_ns_main, called directly (main and dense_main refuse exp['novelty_search'] on a dense run): maze_ns_main's loop on the
 dense bank, novelty over final states scored on the device (k_dense_novelty_pool).
+GA-NS on an Atari game is atari_ns_main, called directly as well (main keeps refusing exp['novelty_search'] there): main's Atari loop with
+maze_ns_main's decisions, novelty over final RAM states scored on the device (k_ram_novelty_pool).
 The loops share what is the same in them as plain functions (_validate_and_test, _record_rows, _end_generation; the bank loops also
 _resume_maze, _draw_generation, _member, _promote, _bank_evaluate; maze_main and dense_main the whole _bank_loop; dense_main and dense_ns_main
 the engine's opening, _open_dense_run); the maze's engine, walls and
@@ -831,6 +833,119 @@ def dense_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **ex
         _record_rows(state, power, rewards, T, v, dt, all_tstart)
         for key, val in (('NoveltyMean', float(np.mean(novelty))), ('NoveltyMax', float(np.max(novelty))),
                          ('ArchiveSize', int(state.archive.shape[0])), ('BestDistanceToGoal', -float(np.max(rewards)))):
+            tlogger.record_tabular(key, val)
+        tlogger.dump_tabular()
+        _end_generation(state, log_dir, lens, rs)
+        if state.timesteps_so_far >= exp['timesteps']:
+            break
+    return float(state.curr_solution_test), {'val': float(state.curr_solution_val)}, state
+
+
+# ---------------------------------------------------------------------------------------------- GA-NS on an Atari game
+def atari_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
+    """GA-NS on an Atari game under `Model` / `LargeModel`: main's Atari loop (the genome store behind ga_eval_powers, HipModel) with
+    maze_ns_main's decisions and tabular keys (without BestDistanceToGoal), novelty over the members' final 128-byte RAM states
+    (GAAtariPolicy.rollout's behaviour characterisation, policies.py:510) scored on the device (csrc/ram_novelty.h).
+    exp['novelty_search'] = {'k': 1 .. RAM_NOVELTY_KMAX, 'archive_prob': 0 .. 1}.  Returns what main returns.
+
+    Called directly: main raises NotImplementedError for exp['novelty_search'] under an Atari game.  What differs from maze_ns_main:
+      engine       a caller's engine must be of the model's kind (KIND_GA for 'Model', KIND_GA_LARGE for 'LargeModel') and created with
+                   record_bc (ValueError otherwise); without one, an engine with record_bc and max_members = population_size is opened.  The
+                   population must fit engine.max_members (ValueError): the whole generation is ONE ga_eval_powers, because the last
+                   evaluation is the pool.
+      draws        the two whole-array draws, then rs.random_sample(n) < archive_prob, then the generation's n environment seeds (drawn by
+                   the evaluation, as every evaluation call of main draws them); each validation and test call draws its own.
+      genomes      every member's genome is written out (ga_eval_powers takes genomes; the store keeps the parents' vectors cached).
+      scoring      one ga_eval_powers, then ram_novelty_pool(k) on the final RAM states where the evaluation left them; the masked members
+                   are appended afterwards by one archive_append_members, before the validation episodes overwrite the recorded states.
+      limits       main's: a generation and the validation episodes under state.tslimit, the test episodes under the environment's own
+                   limit.  num_frames counts 4 frames a step.
+      snapshot     algo = 'ga_ns', game, model, num_params = P, k, archive_prob, the archive uint8 [A][128] (read back through
+                   archive_get_points) and the stream; a resume pushes the archive back and continues bit for bit.  A resume under another
+                   algo, game, model, P, k or archive_prob raises and names both sides."""
+    ns = exp[NS_KEY]
+    k, prob = int(ns['k']), float(ns['archive_prob'])
+    if not 1 <= k <= _lib.RAM_NOVELTY_KMAX:
+        raise ValueError("novelty_search k = {}: expected 1 .. RAM_NOVELTY_KMAX = {}".format(k, _lib.RAM_NOVELTY_KMAX))
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError("novelty_search archive_prob = {!r}: expected a probability".format(ns['archive_prob']))
+    n, T, V = exp['population_size'], exp['selection_threshold'], exp['validation_threshold']
+    asked, game = exp.get('model', 'Model'), exp.get('game') or 'an Atari game'
+    if asked not in MODEL_KINDS or game == 'maze' or _is_dense_run(None, exp):
+        raise NotImplementedError("model {!r} on game {!r}: atari_ns_main runs {} on an Atari game".format(
+            asked, exp.get('game'), ' and '.join(repr(m) for m in sorted(MODEL_KINDS))))
+    if engine is None:
+        engine = _lib.Engine(MODEL_KINDS[asked], 18, max_members=n, record_bc=True)
+    elif engine.kind != MODEL_KINDS[asked]:
+        raise ValueError("model {!r} asked for (engine kind {}), the engine passed in is of kind {}".format(asked, MODEL_KINDS[asked], engine.kind))
+    if not getattr(engine, 'record_bc', False):
+        raise ValueError("atari_ns_main needs an engine created with record_bc: the final RAM states are the behaviour characterisations")
+    if n > engine.max_members:
+        raise ValueError("population_size {} exceeds the engine's max_members {}: a GA-NS generation is one evaluation, its members are the pool".format(
+            n, engine.max_members))
+    tlogger.start(log_dir)
+    noise = noise if noise is not None else SharedNoiseTable()
+    noise.attach(engine)
+    model = HipModel(engine)
+    rs = np.random.RandomState(seed)
+    all_tstart = time.time()
+    engine.archive_clear()
+    state = _resume_maze(log_dir, ALGO_NS, rs, game, asked, engine.P)
+    if state is None:
+        state = TrainingState(exp)
+        state.archive, state.stream = np.zeros((0, _lib.RAM_BYTES), np.uint8), None
+    else:
+        if (state.k, state.archive_prob) != (k, prob):
+            raise ValueError("snapshot.pkl in {} holds k {}, archive_prob {!r}; this run is k {}, archive_prob {!r}".format(
+                log_dir, state.k, state.archive_prob, k, prob))
+        if len(state.archive):
+            engine.archive_append_points(state.archive)
+    state.game, state.model, state.algo, state.num_params, state.k, state.archive_prob = exp.get('game'), asked, ALGO_NS, engine.P, k, prob
+    if 'load_population' in exp:
+        state.copy_population(exp['load_population'])
+    parents = [o.seeds for o in state.population[:T]]               # the top T by novelty, no elite carried
+
+    def evaluate(individuals, tslimit):
+        return _evaluate(engine, [o.seeds for o in individuals], tslimit, rs)
+
+    iters = 0
+    while max_iters is None or iters < max_iters:
+        iters += 1
+        tstart_iteration = time.time()
+        if state.timesteps_so_far >= exp['timesteps']:
+            break
+        assert (len(parents) == 0 and (state.it == 0 or T == 0)) or len(parents) == T
+        power = state.sample(state.mutation_power)
+        of, idx = _draw_generation(rs, n, len(parents), len(noise.noise) - model.num_params + 1)
+        archived = np.flatnonzero(rs.random_sample(n) < prob).astype(np.int32)
+        tasks = [_member(i, of, idx, power, parents)[1] for i in range(n)]
+        rets, lens = _evaluate(engine, tasks, state.tslimit, rs)   # one call: n <= max_members
+        raw = np.asarray(engine.ram_novelty_pool(k), np.float64)   # against the archive as it was before this generation, and the generation
+        novelty = np.where(np.isfinite(raw), raw, 0.0)
+        if archived.size:
+            engine.archive_append_members(archived)
+            state.archive = np.concatenate([state.archive, engine.archive_get_points(len(state.archive), archived.size)])
+        state.num_frames += int(lens.sum()) * 4
+        state.it += 1
+        rewards = np.asarray(rets, np.float64)
+        by_novelty = np.argsort(-novelty, kind='stable')            # (-novelty, arrival index)
+        by_reward = engine.ga_select(np.asarray(rets, np.float32), n)
+        offspring = {}                                              # member index -> its Offspring
+        for i in list(by_novelty[:T]) + list(by_reward[:V]):
+            i = int(i)
+            if i not in offspring:
+                offspring[i] = Offspring(tasks[i], [float(rets[i])], [int(lens[i])])
+                offspring[i].novelty = float(novelty[i])
+        selected = [offspring[int(i)] for i in by_novelty[:T]]
+        validation_population = [offspring[int(i)] for i in by_reward[:V]]
+        state.population = selected + [o for o in validation_population if not any(o is s for s in selected)]
+        v = _validate_and_test(state, exp, validation_population, evaluate, int(lens.sum()))
+        parents = [o.seeds for o in selected]
+        dt = time.time() - tstart_iteration
+        state.time_elapsed += dt
+        _record_rows(state, power, rewards, T, v, dt, all_tstart)
+        for key, val in (('NoveltyMean', float(np.mean(novelty))), ('NoveltyMax', float(np.max(novelty))),
+                         ('ArchiveSize', int(state.archive.shape[0]))):
             tlogger.record_tabular(key, val)
         tlogger.dump_tabular()
         _end_generation(state, log_dir, lens, rs)

@@ -355,6 +355,38 @@ int dne_novelty_batch(dne_handle *h, const uint8_t *archive, const int32_t *arch
  * dne_novelty (n = 1, host rows) and dne_novelty_batch (the recorded trajectories) are this call behind their own checks. */
 int dne_novelty_knn(dne_handle *h, const uint8_t *bcs, const int32_t *lengths, int n, int dim, int k, double *out);
 
+/* ---- pool novelty over final RAM states (GA-NS on Atari; csrc/ram_novelty.h) ------------------
+ * A point is 128 bytes: the final RAM a record_bc GA engine (or a record_bc + bc_final_only ES engine) keeps per member.  Member m of the n
+ * members is scored against the resident archive's A points (dne_archive_append: every entry of length 1 and width 128) at combined slots
+ * 0 .. A - 1 followed by the n members at combined slots A .. A + n - 1, the combined slot A + m left out -- by index, not by value.
+ * S = the exact integer sum of squared byte differences, d = orc_bc_distance of two one-row trajectories (sqrt((double)S), then
+ * sqrt(a * a + 0.0)); the order is (S, combined slot); novelty = the first kk = min(k, A + n - 1) distances of that order added one by one
+ * into a double, divided by kk; neighbours (or NULL) receives those kk combined slots per member, in that order.
+ * bc == NULL reads the first n members of the last dne_ga_eval / dne_ga_eval_powers / dne_eval_members / dne_es_eval, in the caller's member
+ * order, where the evaluation left them, and those n are the population; a host bc [n][128] takes any n >= 1 on any Atari engine.
+ * k_ram_novelty_pool fuses distances and selection: no n x (A + n) buffer exists.  dne_ram_novelty_pool_host is the same header on the CPU
+ * (no handle, no GPU; narch may be 0 and archive NULL then, any k >= 1).
+ * dne_archive_append_members appends the points of the last evaluation's members members[0 .. count - 1], in that order, as entries of
+ * length 1 and width 128, device to device (k_ram_archive_gather); indices may repeat and are checked before anything is launched.
+ * dne_archive_get_points reads count entries of length 1 back, from entry `first`.  dne_ram_novelty_last_ms: the scoring kernel of the last
+ * dne_ram_novelty_pool between two device events, in milliseconds (-1 before the first).
+ * Refused by name, the archive, the recorded points and every other state left as they were: a whole-episode, step or dense engine kind; for
+ * the NULL form and the gather an engine whose bc buffer is absent or holds full trajectories, a call before any evaluation, n (an index)
+ * beyond the last evaluation's members; k < 1, k > DNE_RAM_NOVELTY_KMAX; n < 1; an empty pool (n = 1 and A = 0); an archive whose width is
+ * not 128 or that holds an entry of length != 1 (the first such entry is named); A + n above INT_MAX, the kernel's slot field; a missing
+ * buffer; for the gather and the read-back count < 1 or an index out of range; a gather into an archive of another width (in
+ * dne_archive_append's words). */
+#define DNE_RAM_NOVELTY_KMAX 32
+#define DNE_RAM_NOVELTY_TILE 256      /* combined slots k_ram_novelty_pool stages at a time */
+#define DNE_RAM_NOVELTY_MEMBERS 4     /* members of one workgroup's tile */
+int dne_ram_novelty_pool(dne_handle *h, const uint8_t *bc /*[n][128], or NULL*/, int n, int k, double *out /*[n]*/,
+                         int32_t *neighbours /*[n][min(k, A + n - 1)], or NULL*/);
+int dne_ram_novelty_pool_host(const uint8_t *bc /*[n][128]*/, int n, const uint8_t *archive /*[narch][128], or NULL with narch 0*/, int narch,
+                              int k, double *out /*[n]*/, int32_t *neighbours /*or NULL*/);
+int dne_archive_append_members(dne_handle *h, const int32_t *members /*[count]*/, int count);
+int dne_archive_get_points(dne_handle *h, int first, int count, uint8_t *out /*[count][128]*/);
+double dne_ram_novelty_last_ms(dne_handle *h);
+
 /* ---- the hard maze (DNE_KIND_MAZE; csrc/maze.h) ---------------------------------------------------------------
  * header8 = disable, steps, start x, start y, heading, goal x, goal y, 0 as the maze file gives them (`steps` and `heading` travel with the file
  * and are not read: tf_maze.cpp ends an episode after 400 steps and reset() starts at heading 0); lines [n][4] = wall segments ax, ay, bx, by.
