@@ -1350,10 +1350,13 @@ extern "C" int dne_create(const dne_config *cfg, dne_handle **out) {
     CH(hipFuncSetAttribute((const void *)k_lconv_mfma<64, 64, 3, 1, 11, 11, 1, 68, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lconv_mfma_lds_bytes<64, 3, 1, 11, 68>()));
     CH(hipFuncSetAttribute((const void *)k_lconv_mfma<32, 64, 4, 2, 21, 11, 1, 34, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lconv_mfma_lds_bytes<32, 4, 2, 11, 34>()));
     CH(hipFuncSetAttribute((const void *)k_lconv_mfma<64, 64, 3, 1, 11, 11, 1, 68, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lconv_mfma_lds_bytes<64, 3, 1, 11, 68>()));
-    CH(hipFuncSetAttribute((const void *)k_out<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));   // the DNE_OUT_LDS_KB reservation
-    CH(hipFuncSetAttribute((const void *)k_out<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    CH(hipFuncSetAttribute((const void *)k_out<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    CH(hipFuncSetAttribute((const void *)k_out<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    {   // k_out: the staged output weights (66 KB for a pair at 32 actions) or the DNE_OUT_LDS_KB reservation, whichever is larger
+        constexpr int out_lds_max = (int)std::max(out_stage_bytes(2, OUT_NA), (size_t)64 * 1024);
+        const void *outs[] = {(const void *)k_out<1, false, OUT_NA_ATARI>, (const void *)k_out<1, true, OUT_NA_ATARI>, (const void *)k_out<2, false, OUT_NA_ATARI>,
+                              (const void *)k_out<2, true, OUT_NA_ATARI>,  (const void *)k_out<1, false, OUT_NA>,      (const void *)k_out<1, true, OUT_NA>,
+                              (const void *)k_out<2, false, OUT_NA>,       (const void *)k_out<2, true, OUT_NA>};
+        for (const void *f : outs) CH(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, out_lds_max));
+    }
 #ifdef DNE_PHASE_CLOCK
     {
         int burn = 0;
@@ -2033,6 +2036,64 @@ static void launch_forward(dne_handle *h, const StepPlan &p, const WindowPlan &w
     if (w.act2) hipLaunchKernelGGL(k_y2_activate, dim3(items), dim3(256), 0, st, A, list, gsize, h->y2);
 }
 
+// k_out behind a streaming fc: the action loops unrolled over 18 where the policy has no more actions, dynamic LDS = the staged output
+// weights or the caller's reservation (DNE_OUT_LDS_KB: bounds the kernel's workgroups per CU), whichever is larger
+template <int NV, bool BN>
+static void launch_out(hipStream_t st, int count, size_t reserve, const FwdArgs &A, const int *list, const float *sums, float *y3, int32_t *action, float *logits) {
+    const size_t lds = std::max(out_stage_bytes(NV, A.L.nact), reserve);
+    if (A.L.nact <= OUT_NA_ATARI) hipLaunchKernelGGL((k_out<NV, BN, OUT_NA_ATARI>), dim3(count), dim3(256), lds, st, A, list, sums, y3, action, logits);
+    else hipLaunchKernelGGL((k_out<NV, BN, OUT_NA>), dim3(count), dim3(256), lds, st, A, list, sums, y3, action, logits);
+}
+
+// Test hook: k_out on inputs the caller lays out, at every width the kernel is built for (1 .. 32: dne_create admits 2 .. 18, the
+// fixture's emulator has 18 actions) and under any LDS reservation.  kind: DNE_KIND_ES (batch norm, `bn` rows) or DNE_KIND_GA; gsize 2
+// runs k_out<2, ..> on pairs (members 2g, 2g + 1 share off[2g]), gsize 1 k_out<1, ..>.  list NULL: groups 0 .. n_groups - 1.  y3 /
+// actions / logits go in and come back, so the caller sees what the kernel left alone.  Returns 0, -1 on a refused argument or a HIP error.
+extern "C" int dne_debug_out_head(int kind, int gsize, int n_actions, int n_members, const int32_t *list, int n_groups, const float *noise,
+                                  size_t noise_count, const float *base, const int64_t *off, const float *scale, const int32_t *done,
+                                  const float *bn, const float *sums, int sub_sums, int reserve_lds_kb, float *y3, int32_t *actions, float *logits) {
+    if ((kind != DNE_KIND_ES && kind != DNE_KIND_GA) || (gsize != 1 && gsize != 2) || n_actions < 1 || n_actions > OUT_NA || n_members < gsize ||
+        n_members % gsize || n_groups < 1 || reserve_lds_kb < 0 || reserve_lds_kb > 64 || !noise || !base || !off || !scale || !sums || !y3 || !actions ||
+        (kind == DNE_KIND_ES && !bn))
+        return -1;
+    Layout L;
+    make_layout(kind, n_actions, &L);
+    for (int m = 0; m < n_members; m++)
+        if (off[m] < 0 || (size_t)off[m] + (size_t)L.P > noise_count || off[m] != off[m - m % gsize]) return -1;
+    for (int g = 0; list && g < n_groups; g++)
+        if (list[g] < 0 || list[g] >= n_members / gsize) return -1;
+    if (!list && n_groups > n_members / gsize) return -1;
+    const size_t nsum = (size_t)n_members * (sub_sums ? 32 : 4) * 256, nlog = logits ? (size_t)n_members * n_actions : 0;
+    DevBuf<float> d_noise, d_base, d_scale, d_bn, d_sums, d_y3, d_logits;
+    DevBuf<int32_t> d_list, d_slot, d_done, d_act;
+    DevBuf<int64_t> d_off;
+#define UP(buf, src, n) do { if (buf.alloc(n) != hipSuccess || hipMemcpy(buf.p, src, (n) * sizeof(*buf.p), hipMemcpyHostToDevice) != hipSuccess) return -1; } while (0)
+    UP(d_noise, noise, noise_count); UP(d_base, base, (size_t)L.P); UP(d_scale, scale, (size_t)n_members); UP(d_off, off, (size_t)n_members);
+    UP(d_sums, sums, nsum); UP(d_y3, y3, (size_t)n_members * 256); UP(d_act, actions, (size_t)n_members);
+    if (bn) UP(d_bn, bn, (size_t)n_members * 608);
+    if (done) UP(d_done, done, (size_t)n_members);
+    if (list) UP(d_list, list, (size_t)n_groups);
+    if (logits) UP(d_logits, logits, nlog);
+#undef UP
+    if (d_slot.alloc(n_members) != hipSuccess || hipMemset(d_slot.p, 0, (size_t)n_members * sizeof(int32_t)) != hipSuccess) return -1;
+    const void *outs[] = {(const void *)k_out<1, false, OUT_NA_ATARI>, (const void *)k_out<1, true, OUT_NA_ATARI>, (const void *)k_out<2, false, OUT_NA_ATARI>,
+                          (const void *)k_out<2, true, OUT_NA_ATARI>,  (const void *)k_out<1, false, OUT_NA>,      (const void *)k_out<1, true, OUT_NA>,
+                          (const void *)k_out<2, false, OUT_NA>,       (const void *)k_out<2, true, OUT_NA>};
+    for (const void *f : outs)
+        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(out_stage_bytes(2, OUT_NA), (size_t)64 * 1024)) != hipSuccess) return -1;
+    FwdArgs A = {};
+    A.noise = d_noise; A.bases = d_base; A.base_stride = (size_t)L.P; A.m_slot = d_slot; A.m_off = d_off; A.m_scale = d_scale; A.bn = d_bn;
+    A.done = done ? d_done.p : nullptr; A.sub_sums = sub_sums ? 1 : 0; A.L = L;
+    with_bool(gsize == 2, [&](auto PAIRS) { with_bool(kind == DNE_KIND_ES, [&](auto BN) {
+        launch_out<PAIRS() ? 2 : 1, BN()>(nullptr, n_groups, (size_t)reserve_lds_kb * 1024, A, list ? d_list.p : nullptr, d_sums, d_y3, d_act, logits ? d_logits.p : nullptr);
+    }); });
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpy(y3, d_y3, (size_t)n_members * 256 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (hipMemcpy(actions, d_act, (size_t)n_members * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (logits && hipMemcpy(logits, d_logits, nlog * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return 0;
+}
+
 // the window's fc (w.fc) and, unless the caller runs k_tail_step behind it (w.head_fused), the output layer
 static void launch_fc(dne_handle *h, const StepPlan &p, const WindowPlan &w, const TailTable *tt, const int *list, int gsize, float *logits,
                       hipStream_t st = nullptr,
@@ -2068,7 +2129,7 @@ static void launch_fc(dne_handle *h, const StepPlan &p, const WindowPlan &w, con
             constexpr int NV = ES() ? 2 : 1;
             hipLaunchKernelGGL((k_fc_sub<NV, ES(), ES()>), dim3(w.sub_blocks), dim3(256), 0, st, A, list, count, w.sub_spw, k.fc_sub_prio, (const float *)h->y2, h->y3s);
             if (out_fused) return;   // the caller runs k_tail_step (FwdArgs::sub_sums tells it to fold the chain sums)
-            hipLaunchKernelGGL((k_out<NV, ES()>), dim3(count), dim3(256), 0, st, A, list, (const float *)h->y3s, h->y3, h->action, (float *)nullptr);
+            launch_out<NV, ES()>(st, count, 0, A, list, (const float *)h->y3s, h->y3, h->action, nullptr);
         });
         return;
     case DNE_FC_QUAD: case DNE_FC_TAIL: case DNE_FC_COLS:   // latency-bound regime: 64 / 16 / 4 workgroups per group + a separate output-layer kernel
@@ -2081,14 +2142,14 @@ static void launch_fc(dne_handle *h, const StepPlan &p, const WindowPlan &w, con
             } else if (w.fc == DNE_FC_QUAD) hipLaunchKernelGGL((k_fc_quad<NV, BN>), dim3(count * 64), dim3(256), 0, st, A, list, (const float *)h->y2, h->y3t);
             else if (w.fc == DNE_FC_TAIL) hipLaunchKernelGGL((k_fc_tail<NV, BN>), dim3(count * 16), dim3(512), 0, st, A, list, (const float *)h->y2, h->y3t);
             else hipLaunchKernelGGL((k_fc_cols<NV, BN>), dim3(count * 4), dim3(256), 0, st, A, list, (const float *)h->y2, h->y3t);
-            if (!out_fused) hipLaunchKernelGGL((k_out<NV, BN>), dim3(count), dim3(256), 0, st, A, list, (const float *)h->y3t, h->y3, h->action, logits);
+            if (!out_fused) launch_out<NV, BN>(st, count, 0, A, list, (const float *)h->y3t, h->y3, h->action, logits);
         }); });
         return;
     case DNE_FC_RING: case DNE_FC_DUO: {   // table-ordered units: adjacent (pair, k-slice) units share their noise rows (ES pairs only: plan_step)
         const bool solo = w.solo;
         const int duo_grid = k.duo_grid ? k.duo_grid : k.fc_grid;
         const int n_units = 4 * count, items = ((solo ? n_units : (n_units + 1) / 2) + 3) / 4, blocks = std::min(items, duo_grid);
-        const size_t out_lds = (size_t)k.out_lds_kb * 1024;   // an LDS reservation nobody uses: it only bounds k_out's workgroups per CU next to the streaming fc
+        const size_t out_lds = (size_t)k.out_lds_kb * 1024;   // an LDS reservation beyond k_out's own need: it only bounds the kernel's workgroups per CU next to the streaming fc
         const int flags = k.duo_lag | (solo ? 256 : 0) | (k.fc_prio << 9) | ((k.duo_sync - 1) << 11);
         if (w.fc == DNE_FC_RING) {   // one unit per wave, eight units per workgroup whatever the regime
             const int ring_blocks = std::min((n_units + 7) / 8, duo_grid);
@@ -2100,7 +2161,7 @@ static void launch_fc(dne_handle *h, const StepPlan &p, const WindowPlan &w, con
         else hipLaunchKernelGGL((k_fc_duo<2, true>), dim3(blocks), dim3(256), 0, st, A, order, n_units, (const float *)h->y2, h->y3t, flags);
         if (after_stream_kernel) hipEventRecord(after_stream_kernel, st);
         if (out_fused) return;   // the caller runs k_tail_step: policy head + emulator step in one launch
-        hipLaunchKernelGGL((k_out<2, true>), dim3(count), dim3(256), out_lds, st, A, list, (const float *)h->y3t, h->y3, h->action, (float *)nullptr);
+        launch_out<2, true>(st, count, out_lds, A, list, (const float *)h->y3t, h->y3, h->action, nullptr);
         return;
     }
     case DNE_FC_FC2: {   // two pairs per work item share the base rows (ES pairs over one base slot only: plan_step)

@@ -1398,8 +1398,12 @@ __device__ __forceinline__ float lane_bcast(float v, int lane) {
 // logit[a] = tree over k of p[k] = a3[k] * w[k][a]:  every group of 64 consecutive k is one wavefront, lane = k, and the 64
 // products are summed by a lane butterfly with strides 1, 2, 4, 8, 16, 32 -- a balanced binary tree, neighbours first, both lanes
 // of a pair holding the same sum at every level (fp addition is commutative); the groups' sums meet in LDS and are combined
-// ((S0+S1)+(S2+S3)) (+ ((S4+S5)+(S6+S7)) for the LargeModel's 512 inputs) + bias.  No serial chain, no staging of the weights:
-// a thread loads the nact consecutive weights of its own k (base and noise) and that is the layer's whole memory traffic.
+// ((S0+S1)+(S2+S3)) (+ ((S4+S5)+(S6+S7)) for the LargeModel's 512 inputs) + bias.  No serial chain.  Where the weights come from
+// is the caller's business: the kernels that finish a forward pass inside a latency-bound launch (k_fc, k_fc2, k_tail_step, the
+// speculative tail, k_lout) let a thread load the nact consecutive weights of its own k (out_products: a lane stride of 4 * nact
+// bytes, about one cache line per lane and load instruction -- cheap on an idle chip, staging measured slower there); k_out, the
+// head of the throughput-bound lock-steps, reads the same 256 x nact block with whole-line loads and turns it through LDS
+// (out_stage_weights / out_products_staged).  Same products into the same tree either way.
 template <int CTRL>
 __device__ __forceinline__ float dpp_get(float v) {
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xf, 0xf, true));
@@ -1418,21 +1422,22 @@ __device__ __forceinline__ float wave_tree_sum(float v) {
 }
 constexpr int WAVE_TREE_LANE = 63;
 
-constexpr int OUT_NA = 32;         // the action loops are unrolled over the largest action set the engine accepts
+constexpr int OUT_NA = 32;         // the action loops are unrolled over the largest action set the engine accepts ...
+constexpr int OUT_NA_ATARI = 18;   // ... or, in k_out, over the full Atari action set when the policy has no more actions than that
 
 // p[s][a] = x[s] * fl(theta[a] + fl(sc[s] * eps[a])) for this thread's k; wb / we point at w[k][0] in the base vector / noise slice.
-// The NS members share one base vector and one noise slice (an antithetic pair: scales +sigma / -sigma).
-template <int NS>
-__device__ __forceinline__ void out_products(float (&p)[NS][OUT_NA], const float (&x)[NS], const float *__restrict__ wb,
+// The NS members share one base vector and one noise slice (an antithetic pair: scales +sigma / -sigma).  NA >= nact: the unrolled width.
+template <int NS, int NA>
+__device__ __forceinline__ void out_products(float (&p)[NS][NA], const float (&x)[NS], const float *__restrict__ wb,
                                              const float *__restrict__ we, const float (&sc)[NS], int nact) {
-    float th[OUT_NA], ep[OUT_NA];
+    float th[NA], ep[NA];
 #pragma unroll
-    for (int a = 0; a < OUT_NA; a++) {
+    for (int a = 0; a < NA; a++) {
         th[a] = a < nact ? wb[a] : 0.0f;
         ep[a] = a < nact ? we[a] : 0.0f;
     }
 #pragma unroll
-    for (int a = 0; a < OUT_NA; a++)
+    for (int a = 0; a < NA; a++)
 #pragma unroll
         for (int s2 = 0; s2 < NS; s2++) {
             float pv = sc[s2] * ep[a];
@@ -1441,18 +1446,76 @@ __device__ __forceinline__ void out_products(float (&p)[NS][OUT_NA], const float
         }
 }
 
-// the wavefront's tree sums of p -> red[s][a] (this wave's slot in LDS)
-template <int NS>
-__device__ __forceinline__ void out_wave_sums(float (&p)[NS][OUT_NA], int nact, float (*red)[OUT_NA], int lane) {
+// The staged form of the same products (k_out).  The 256 x nact block is contiguous in the base vector and in the noise slice, so
+// the workgroup reads it as nact pieces of 1 KB: thread t takes dword t of every piece -- a wave-level load covers 256 consecutive
+// bytes (four or five cache lines) where out_products' covers 64 lines for the same 256 bytes.  The noise block starts at any
+// float, so these are 4-byte loads.  The thread that loaded element i = k * nact + a forms the members' weights
+// fl(theta + fl(sc * eps)) -- out_products' two roundings -- and writes them to LDS at word i + k = k * (nact + 1) + a: rows of
+// nact + 1.  An odd row length puts the 32 lanes of a half-wave on 32 different banks when thread k reads its row back (nact odd:
+// the row length is even and lanes 16 apart can meet -- two-way at worst, and only there); the members' weights sit side by side
+// (one 4 * NS-byte word per element, 8 * (nact + 1) bytes per row: for a pair an odd number of bank PAIRS).
+template <int NS> struct alignas(4 * NS) OutW { float w[NS]; };
+__host__ __device__ constexpr size_t out_stage_bytes(int ns, int nact) { return (size_t)ns * 256 * (nact + 1) * sizeof(float); }
+
+// the loads of the block, issued before anything else the kernel waits for: piece j -> th[j], ep[j]
+template <int NA>
+__device__ __forceinline__ void out_stage_load(float (&th)[NA], float (&ep)[NA], const float *__restrict__ wb, const float *__restrict__ we,
+                                               int nact, int tid) {
 #pragma unroll
-    for (int a = 0; a < OUT_NA; a++)
+    for (int j = 0; j < NA; j++) {
+        th[j] = j < nact ? wb[j * 256 + tid] : 0.0f;
+        ep[j] = j < nact ? we[j * 256 + tid] : 0.0f;
+    }
+}
+// weights of the loaded elements -> LDS rows (the caller puts a barrier between this and out_products_staged)
+template <int NS, int NA>
+__device__ __forceinline__ void out_stage_weights(OutW<NS> *__restrict__ stage, const float (&th)[NA], const float (&ep)[NA],
+                                                  const float (&sc)[NS], int nact, int tid) {
+    // element i = j * 256 + tid = k * nact + a: k and a advance by 256 / nact and 256 % nact per piece, no division in the loop
+    const int dk = 256 / nact, da = 256 - dk * nact;
+    int k = tid / nact, a = tid - k * nact;
+#pragma unroll
+    for (int j = 0; j < NA; j++) {
+        if (j < nact) {
+            OutW<NS> o;
+#pragma unroll
+            for (int s2 = 0; s2 < NS; s2++) {
+                float pv = sc[s2] * ep[j];
+                o.w[s2] = th[j] + pv;
+            }
+            stage[j * 256 + tid + k] = o;
+            k += dk; a += da;
+            if (a >= nact) { a -= nact; k++; }
+        }
+    }
+}
+// p[s][a] = x[s] * w[s][k][a] from the staged rows, k = this thread
+template <int NS, int NA>
+__device__ __forceinline__ void out_products_staged(float (&p)[NS][NA], const float (&x)[NS], const OutW<NS> *__restrict__ stage, int nact, int k) {
+    const OutW<NS> *row = stage + k * (nact + 1);
+#pragma unroll
+    for (int a = 0; a < NA; a++) {
+        OutW<NS> o;
+#pragma unroll
+        for (int s2 = 0; s2 < NS; s2++) o.w[s2] = 0.0f;
+        if (a < nact) o = row[a];
+#pragma unroll
+        for (int s2 = 0; s2 < NS; s2++) p[s2][a] = x[s2] * o.w[s2];
+    }
+}
+
+// the wavefront's tree sums of p -> red[s][a] (this wave's slot in LDS)
+template <int NS, int NA>
+__device__ __forceinline__ void out_wave_sums(float (&p)[NS][NA], int nact, float (*red)[NA], int lane) {
+#pragma unroll
+    for (int a = 0; a < NA; a++)
         if (a < nact) {
 #pragma unroll
             for (int s2 = 0; s2 < NS; s2++) p[s2][a] = wave_tree_sum(p[s2][a]);
         }
     if (lane == WAVE_TREE_LANE) {
 #pragma unroll
-        for (int a = 0; a < OUT_NA; a++)
+        for (int a = 0; a < NA; a++)
             if (a < nact) {
 #pragma unroll
                 for (int s2 = 0; s2 < NS; s2++) red[s2][a] = p[s2][a];
@@ -3377,11 +3440,15 @@ __global__ __launch_bounds__(256) void k_fc_sub(FwdArgs A, const int *__restrict
     }   // persistent loop over the launch's waves' worth of work
 }
 
-template <int NV, bool HAS_BN>
+// NA: the unrolled width of the action loops (OUT_NA_ATARI when nact <= 18, else OUT_NA: launch_out).  Dynamic LDS: out_stage_bytes(NV, nact),
+// or more where the caller reserves LDS to bound the kernel's workgroups per CU (DNE_OUT_LDS_KB).
+template <int NV, bool HAS_BN, int NA>
 __global__ __launch_bounds__(256) void k_out(FwdArgs A, const int *__restrict__ list, const float *__restrict__ y3t,
                                             float *__restrict__ y3, int32_t *__restrict__ actions,
                                             float *__restrict__ logits_out) {
-    __shared__ float red[4][NV][OUT_NA];
+    extern __shared__ __attribute__((aligned(16))) unsigned char out_stage_lds[];
+    OutW<NV> *stage = reinterpret_cast<OutW<NV> *>(out_stage_lds);
+    __shared__ float red[4][NV][NA];
     __shared__ float lg[NV][32];
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
     const Layout &L = A.L;
@@ -3401,6 +3468,9 @@ __global__ __launch_bounds__(256) void k_out(FwdArgs A, const int *__restrict__ 
     float sc[NV], x3[NV];
 #pragma unroll
     for (int v = 0; v < NV; v++) sc[v] = A.m_scale[m0 + v];
+    // the output layer's weights do not depend on the fc sums: their loads go out first
+    float th[NA], ep[NA];
+    out_stage_load<NA>(th, ep, base + L.ow, eps + L.ow, nact, tid);
     const float fb_t = opt_bias(L.fcb, base[opt_off(L.fcb) + tid]), fb_e = opt_bias(L.fcb, eps[opt_off(L.fcb) + tid]);
 #pragma unroll
     for (int v = 0; v < NV; v++) {
@@ -3418,10 +3488,12 @@ __global__ __launch_bounds__(256) void k_out(FwdArgs A, const int *__restrict__ 
         }
         x3[v] = t > 0.0f ? t : 0.0f;
     }
+    out_stage_weights<NV, NA>(stage, th, ep, sc, nact, tid);
+    __syncthreads();
     {
-        float p[NV][OUT_NA];
-        out_products<NV>(p, x3, base + L.ow + tid * nact, eps + L.ow + tid * nact, sc, nact);
-        out_wave_sums<NV>(p, nact, red[wv], lane);
+        float p[NV][NA];
+        out_products_staged<NV, NA>(p, x3, stage, nact, tid);
+        out_wave_sums<NV, NA>(p, nact, red[wv], lane);
     }
     __syncthreads();
     if (tid < NV * nact) {

@@ -102,7 +102,7 @@ static const KnobRow KNOBS[] = {
     {"DNE_CONV2_REF_FPW", 1, 8, &Knobs::conv2_ref_fpw, "reference frames per conv2 workgroup (8, 4, or 1 = the lock-step kernel)"},
     {"DNE_DUO_SOLO_BELOW", 0, 1 << 30, &Knobs::duo_solo_below, "with fewer active groups (all windows) every wave takes one unit instead of two (sparse table: little to share, and twice the waves)"},
     {"DNE_DUO_HEAD_FUSED", 0, 1, &Knobs::duo_head_fused, "behind k_fc_duo the policy head and the emulator step share a launch (k_tail_step) instead of k_out + k_env_logic; same-box A/B: 402.7 ms fused, 403.3 separate, 399.8 separate with k_out at two workgroups per CU -> off"},
-    {"DNE_OUT_LDS_KB", 0, 64, &Knobs::out_lds_kb, "an unused LDS reservation that bounds k_out's workgroups per CU (round 2's k_out staged 37 KB of output weights and ran best at two workgroups per CU = 64 KB; round 3's stages nothing)"},
+    {"DNE_OUT_LDS_KB", 0, 64, &Knobs::out_lds_kb, "an LDS reservation that bounds k_out's workgroups per CU behind k_fc_ring / k_fc_duo: the launch asks for this much when it is more than the staged output weights need (39 KB for a pair at 18 actions: four workgroups per CU; 64 KB: two)"},
     {"DNE_FC_DUO_MIN", 2, 1 << 30, &Knobs::fc_duo_min, "table-ordered fc from this many active groups (round 4: 451, right above the sub-slice fc's range; 800 before -- with one k_fc_duo workgroup per CU a 625-pair share takes 84.5 instead of 88.4 ms per generation)"},
     {"DNE_RENDER_BANDS", 1, 84, &Knobs::render_bands, "tail: workgroups per frame (1 = render inside k_tail_step)"},
     {"DNE_RENDER_WG_MAX", 1, 1 << 20, &Knobs::render_wg_max, "... halved until members x bands fits this many workgroups"},

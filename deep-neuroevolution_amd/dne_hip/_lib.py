@@ -170,6 +170,33 @@ def debug_knob(kind, nact, name):
     return load().dne_debug_knob(int(kind), int(nact), name.encode())
 
 
+def debug_out_head(kind, gsize, nact, noise, base, off, scale, sums, y3, actions, logits=None, bn=None, done=None, list=None, sub_sums=False,
+                   reserve_lds_kb=0):
+    """dne_debug_out_head: k_out (the policy head behind the streaming fc kernels) on arrays the caller lays out, 1 .. 32 actions.  y3 [n][256]
+    float32, actions [n] int32 and logits [n][nact] float32 (or None) are read and overwritten in place, so what the kernel did not write keeps
+    the caller's values.  sums: [n][4][256], or [n][32][256] with sub_sums.  list: group indices (None: every group in order)."""
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    noise, base, scale, sums, bn = f32(noise), f32(base), f32(scale), f32(sums), f32(bn)
+    off = np.ascontiguousarray(off, np.int64)
+    done = None if done is None else np.ascontiguousarray(done, np.int32)
+    list = None if list is None else np.ascontiguousarray(list, np.int32)
+    n = off.size
+    assert y3.dtype == np.float32 and y3.shape == (n, 256) and y3.flags.c_contiguous and actions.dtype == np.int32 and actions.shape == (n,)
+    assert logits is None or (logits.dtype == np.float32 and logits.shape == (n, nact) and logits.flags.c_contiguous)
+    assert sums.shape == (n, 32 if sub_sums else 4, 256) and scale.shape == (n,) and (bn is None or bn.shape == (n, 608))
+    p = lambda a, t: None if a is None else a.ctypes.data_as(C.POINTER(t))
+    fn = load().dne_debug_out_head
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_int64),
+                   C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_float),
+                   C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+    rc = fn(int(kind), int(gsize), int(nact), n, p(list, C.c_int32), n // gsize if list is None else list.size, p(noise, C.c_float), noise.size,
+            p(base, C.c_float), p(off, C.c_int64), p(scale, C.c_float), p(done, C.c_int32), p(bn, C.c_float), p(sums, C.c_float), int(bool(sub_sums)),
+            int(reserve_lds_kb), p(y3, C.c_float), p(actions, C.c_int32), p(logits, C.c_float))
+    if rc != 0:
+        raise DneError("dne_debug_out_head refused its arguments or a HIP call failed (rc %d)" % rc)
+
+
 def load_maze(path):
     """A maze file of the reference (maze.h:468-495: disable, steps, number of lines, start x y, heading, goal x y, poi x y, then the lines)
     -> (header8 float32 [8] = disable, steps, start x, start y, heading, goal x, goal y, 0; lines float32 [n][4]).  The point of interest

@@ -244,6 +244,14 @@ int dne_debug_ref_index(const uint8_t *ref, int count, int32_t *idx1, uint8_t *p
 int dne_ref_dedup_active(dne_handle *h, int *U1, int *U2);
 /* the value of one knob (by its DNE_* name) after defaults, environment and clamping, as dne_create would see it; -1: no such knob */
 int dne_debug_knob(int kind, int n_actions, const char *name);
+/* k_out -- the policy head behind the streaming fc kernels -- on inputs the caller lays out: kind DNE_KIND_ES (bn rows [n_members][608]) or
+ * DNE_KIND_GA, groups of gsize 1 or 2 members over one noise slice each, 1 .. 32 actions, the fc sums as the fc kernels leave them
+ * ([member][4][256], or [member][32][256] with sub_sums), an LDS reservation of 0 .. 64 KB as DNE_OUT_LDS_KB makes it.  y3, actions and
+ * logits (may be NULL) are read and written back.  A test hook: no handle, every buffer is uploaded for the call. */
+int dne_debug_out_head(int kind, int gsize, int n_actions, int n_members, const int32_t *list /*[n_groups] or NULL*/, int n_groups,
+                       const float *noise, size_t noise_count, const float *base /*[P]*/, const int64_t *off /*[n_members]*/,
+                       const float *scale /*[n_members]*/, const int32_t *done /*[n_members] or NULL*/, const float *bn, const float *sums,
+                       int sub_sums, int reserve_lds_kb, float *y3 /*[n_members][256]*/, int32_t *actions /*[n_members]*/, float *logits);
 
 /* ---- A1-A7: whole-batch evaluation ------------------------------------------------------------------ */
 /* es.py:411-426 for n pairs at once: returns_n2/signreturns_n2/lengths_n2 are [n][2] like Result (es.py:18-23).
