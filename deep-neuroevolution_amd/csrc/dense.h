@@ -1,18 +1,18 @@
-// dense.h -- a dense policy of any small shape on the three step environments (the model half of concurrent_worker.py:56-67: env.observation,
+// dense.h -- a dense policy of any small shape on the four step environments (the model half of concurrent_worker.py:56-67: env.observation,
 // model.make_net over IndexedBatchMatMul, env.step), as ONE __host__ __device__ text in the manner of its siblings.  The environment is
 // step_env.h's (advance, observe, the reset_state of each kind), the arithmetic is maze.h's and pendulum.h's (perturbed, relu, tanh_f,
 // pick_action): used, not copied, so a value this header produces is bit for bit the one the whole-episode kernels of the baked shapes and the
 // step-at-a-time batch produce.  A plain C++ compiler can include this file (the kernel is behind __HIPCC__): tests/dense_asan_main.cpp does.
 // DESIGN.md section 17.
 //
-// The shape: `n_hidden` (0..3) hidden layers of width 1..64 between the environment's inputs (maze 11, cart-pole 4, pendulum 3) and its
-// outputs (2, 2, 1); one nonlinearity (tanh_f or relu) behind every hidden layer, none behind the last.  n_hidden = 0 is models/simple.py:23-27
+// The shape: `n_hidden` (0..3) hidden layers of width 1..64 between the environment's inputs (maze 11, cart-pole 4, pendulum 3, acrobot 6) and its
+// outputs (2, 2, 1, 3); one nonlinearity (tanh_f or relu) behind every hidden layer, none behind the last.  n_hidden = 0 is models/simple.py:23-27
 // LinearClassifier.  The flat vector is in creation order (models/base.py:166-178): per layer w [in][out] row-major, then b [out] -- so (16, 16)
 // on the maze is maze.h's own layout and on the cart-pole cartpole.h's.
 // The numerics: one output unit is one fmaf chain over k ascending from +0.0f, then + b, then the nonlinearity (maze.h's dense_unit with the
 // widths at run time); -ffp-contract=off on both passes; theta_p = perturbed(base[slot][p], scale, noise[off + p]).
 // The action: the maze takes the two raw outputs, the cart-pole cartpole::pick_action of them, the pendulum the raw output as its torque (the
-// step clips it; observations are raw, nothing is normalised here).
+// step clips it; observations are raw, nothing is normalised here), the acrobot acrobot::pick_action of its three.
 // An episode's return is the float64 sum of its rewards in step order, cast once; its sign-return the sum of np.sign of each reward, likewise.
 #pragma once
 #include "step_env.h"
@@ -23,17 +23,23 @@ namespace dense {
 using stepenv::KIND_MAZE;
 using stepenv::KIND_CARTPOLE;
 using stepenv::KIND_PENDULUM;
+using stepenv::ENV_ACROBOT;
 using stepenv::MazeCtx;
 
-constexpr int MAX_HIDDEN = 3, MAX_WIDTH = 64, MAX_LAYERS = MAX_HIDDEN + 1, MAX_OUT = 2;
-constexpr int MAX_P = (maze::OBS + 1) * MAX_WIDTH + 2 * (MAX_WIDTH + 1) * MAX_WIDTH + (MAX_WIDTH + 1) * MAX_OUT;   // 11 -> 64 -> 64 -> 64 -> 2: 9218
+constexpr int MAX_HIDDEN = 3, MAX_WIDTH = 64, MAX_LAYERS = MAX_HIDDEN + 1, MAX_OUT = 3;
+// the widest shape an environment takes: obs -> 64 -> 64 -> 64 -> out
+constexpr int widest_p(int obs, int out) { return (obs + 1) * MAX_WIDTH + 2 * (MAX_WIDTH + 1) * MAX_WIDTH + (MAX_WIDTH + 1) * out; }
+constexpr int max_i(int a, int b) { return a > b ? a : b; }
+constexpr int MAX_P = max_i(max_i(widest_p(maze::OBS, 2), widest_p(cartpole::OBS, 2)),
+                            max_i(widest_p(pendulum::OBS, 1), widest_p(acrobot::OBS, acrobot::ACT)));   // the maze's: 9218 (the acrobot's: 8963)
+static_assert(MAX_P == 9218, "the maze's 11 -> 64 -> 64 -> 64 -> 2");
 enum { NL_TANH = 0, NL_RELU = 1 };
 enum { SHAPE_OK = 0, SHAPE_ENV, SHAPE_LAYERS, SHAPE_WIDTH, SHAPE_TAIL, SHAPE_OUT, SHAPE_NONLIN };
 
 // dim: inputs, the hidden widths, outputs; off[l]: where layer l's w starts (its b follows at off[l] + dim[l] * dim[l + 1])
 struct Shape { int env, n_hidden, nonlin, dim[MAX_LAYERS + 1], off[MAX_LAYERS], P; };
 
-MZ_HD int env_outputs(int env) { return env == KIND_PENDULUM ? 1 : 2; }
+MZ_HD int env_outputs(int env) { return env == KIND_PENDULUM ? 1 : env == ENV_ACROBOT ? acrobot::ACT : 2; }
 
 // the shape from its parts, or which part is refused (SHAPE_*).  widths holds n_widths entries: the n_hidden widths, then zeros
 MZ_HD int make_shape(int env, int n_hidden, const int32_t *widths, int n_widths, int nonlin, int n_out, Shape *sh) {
@@ -76,26 +82,30 @@ MZ_HD float layer_unit(const Shape &sh, const float *theta, int l, const float *
     return l < sh.n_hidden ? activate(sh.nonlin, v) : v;
 }
 
-// the action as the environment's step takes it: maze float [2], cart-pole int32 [1], pendulum float [1]
+// the action as the environment's step takes it: maze float [2], cart-pole int32 [1], pendulum float [1], acrobot int32 [1]
 MZ_HD void write_action(int env, const float *out, void *action) {
     if (env == KIND_MAZE) { ((float *)action)[0] = out[0]; ((float *)action)[1] = out[1]; }
     else if (env == KIND_CARTPOLE) ((int32_t *)action)[0] = cartpole::pick_action(out[0], out[1]);
+    else if (env == ENV_ACROBOT) ((int32_t *)action)[0] = acrobot::pick_action(out);
     else ((float *)action)[0] = out[0];
 }
 
-// ---- the three environments under one spelling ------------------------------------------------------------------------------------------------
+// ---- the four environments under one spelling - ------------------------------------------------------------------------------------------------
 template <int ENV> struct EnvOf;
 template <> struct EnvOf<KIND_MAZE> { typedef maze::State State; static constexpr int OBS = maze::OBS, S = 7, OUT = 2, OWN = maze::EPISODE_STEPS; };
 template <> struct EnvOf<KIND_CARTPOLE> { typedef cartpole::State State; static constexpr int OBS = cartpole::OBS, S = 4, OUT = 2, OWN = cartpole::EPISODE_STEPS; };
 template <> struct EnvOf<KIND_PENDULUM> { typedef pendulum::State State; static constexpr int OBS = pendulum::OBS, S = 2, OUT = 1, OWN = pendulum::EPISODE_STEPS; };
+template <> struct EnvOf<ENV_ACROBOT> { typedef acrobot::State State; static constexpr int OBS = acrobot::OBS, S = 4, OUT = acrobot::ACT, OWN = acrobot::EPISODE_STEPS; };
 
 MZ_HD void reset(maze::State &s, uint32_t, const MazeCtx &c) { s = maze::reset_state(c.hdr); }
 MZ_HD void reset(cartpole::State &s, uint32_t seed, const MazeCtx &) { s = cartpole::reset_state(seed); }
 MZ_HD void reset(pendulum::State &s, uint32_t seed, const MazeCtx &) { s = pendulum::reset_state(seed); }
+MZ_HD void reset(acrobot::State &s, uint32_t seed, const MazeCtx &) { s = acrobot::reset_state(seed); }
 
 template <class R> MZ_HD void look(const maze::State &s, const MazeCtx &c, const maze::SinCosF *dir, const R &r, float *obs) { stepenv::observe(s, c, dir, r, obs); }
 template <class R> MZ_HD void look(const cartpole::State &s, const MazeCtx &, const maze::SinCosF *, const R &, float *obs) { stepenv::observe(s, obs); }
 template <class R> MZ_HD void look(const pendulum::State &s, const MazeCtx &, const maze::SinCosF *, const R &, float *obs) { stepenv::observe(s, obs); }
+template <class R> MZ_HD void look(const acrobot::State &s, const MazeCtx &, const maze::SinCosF *, const R &, float *obs) { stepenv::observe(s, obs); }
 
 // outputs -> action -> stepenv::advance
 template <class R>
@@ -112,6 +122,11 @@ template <class R>
 MZ_HD bool act_advance(pendulum::State &s, int &steps, int limit, int &done, const float *out, const MazeCtx &, const maze::SinCosF *, const R &,
                        float &reward, float *obs) {
     return stepenv::advance(s, steps, limit, done, out[0], reward, obs);
+}
+template <class R>
+MZ_HD bool act_advance(acrobot::State &s, int &steps, int limit, int &done, const float *out, const MazeCtx &, const maze::SinCosF *, const R &,
+                       float &reward, float *obs) {
+    return stepenv::advance(s, steps, limit, done, acrobot::pick_action(out), reward, obs);
 }
 
 // ---- the CPU twins ----------------------------------------------------------------------------------------------------------------------------
@@ -137,7 +152,7 @@ inline void rollout_one(const Shape &sh, const float *theta, uint32_t seed, cons
     if (init) stepenv::unpack(init, s);
     maze::SinCosF dir[6] = {};
     if (ENV == KIND_MAZE) maze::rangefinder_dirs(dir);
-    float obs[E::OBS], out[MAX_OUT] = {0.0f, 0.0f};
+    float obs[E::OBS], out[MAX_OUT] = {};
     look(s, c, dir, stepenv::Solo(), obs);
     int steps = 0, done = 0;
     const int limit = stepenv::step_limit(tslimit, E::OWN);
@@ -163,7 +178,8 @@ inline void rollout_host(const Shape &sh, const float *theta, int n, const uint3
         float *sg = sign ? sign + i : nullptr;
         if (sh.env == KIND_MAZE) rollout_one<KIND_MAZE>(sh, th, seed, init ? init + (size_t)i * 7 : nullptr, c, tslimit, ret + i, sg, len + i, state + (size_t)i * 7);
         else if (sh.env == KIND_CARTPOLE) rollout_one<KIND_CARTPOLE>(sh, th, seed, init ? init + (size_t)i * 4 : nullptr, c, tslimit, ret + i, sg, len + i, state + (size_t)i * 4);
-        else rollout_one<KIND_PENDULUM>(sh, th, seed, init ? init + (size_t)i * 2 : nullptr, c, tslimit, ret + i, sg, len + i, state + (size_t)i * 2);
+        else if (sh.env == KIND_PENDULUM) rollout_one<KIND_PENDULUM>(sh, th, seed, init ? init + (size_t)i * 2 : nullptr, c, tslimit, ret + i, sg, len + i, state + (size_t)i * 2);
+        else rollout_one<ENV_ACROBOT>(sh, th, seed, init ? init + (size_t)i * 4 : nullptr, c, tslimit, ret + i, sg, len + i, state + (size_t)i * 4);
     }
 }
 
@@ -234,7 +250,7 @@ __global__ __launch_bounds__(64) void k_dense_run(const RunArgs A) {
     }
 
     // the forward pass on obs: the outputs end in s_act[(n_hidden + 1) & 1][0 .. OUT); every lane leaves with them in o[]
-    float o[MAX_OUT] = {0.0f, 0.0f};
+    float o[MAX_OUT] = {};
     auto forward = [&]() {
         if (lane == 0) {
 #pragma unroll
@@ -253,7 +269,7 @@ __global__ __launch_bounds__(64) void k_dense_run(const RunArgs A) {
 
     if (!A.episode && A.max_steps == 0) {
         forward();
-        if (A.out && lane < E::OUT) A.out[(size_t)item * E::OUT + lane] = o[lane & (MAX_OUT - 1)];
+        if (A.out && lane < E::OUT) A.out[(size_t)item * E::OUT + lane] = o[lane < MAX_OUT ? lane : 0];
         if (A.act && lane == 0) write_action(ENV, o, (char *)A.act + (size_t)item * (ENV == KIND_MAZE ? 2 : 1) * sizeof(float));
         return;
     }

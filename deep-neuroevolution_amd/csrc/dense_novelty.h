@@ -7,6 +7,7 @@
 //       maze       D = 2: (float)rec[0], (float)rec[1] -- the record holds widened floats, so this is MazeFinalState, the (x, y) k_maze_rollout leaves
 //       cart-pole  D = 4: (float) of x, x_dot, theta, theta_dot
 //       pendulum   D = 2: (float) of theta, theta_dot
+//       acrobot    D = 4: (float) of theta1, theta2, omega1, omega2
 //   * d(p, a) = sqrt(s): per coordinate d_i = (double)a_i - (double)p_i; s = d_0 * d_0, then s = s + d_i * d_i for i ascending, never fused
 //     (-ffp-contract=off on both passes); sqrt the correctly rounded one.  For D = 2 this is maze_novelty::distance bit for bit;
 //   * the order is (isnan, value, archive slot) through sort_key;
@@ -34,7 +35,7 @@ using maze_novelty::sort_key;
 constexpr int MAX_D = 4;
 
 // ---- the behaviour characterisation ---------------------------------------------------------------------------------------------------------
-MZ_HD int bc_dim(int env) { return env == dense::KIND_CARTPOLE ? 4 : 2; }
+MZ_HD int bc_dim(int env) { return env == dense::KIND_CARTPOLE || env == dense::ENV_ACROBOT ? 4 : 2; }
 
 MZ_HD void bc_of_record(int env, const double *rec, float *bc) {
     const int D = bc_dim(env);
@@ -53,7 +54,7 @@ MZN_HD double distance(const float *p, const float *a, int D) {
 
 // ---- the CPU side: a plain partial sort on (key, slot), then the sum in that order, as maze_novelty::novelty_host_body ------------------------
 inline void bc_host(int env, const double *rec, int n, float *bc) {
-    const int S = env == dense::KIND_MAZE ? 7 : env == dense::KIND_CARTPOLE ? 4 : 2, D = bc_dim(env);
+    const int S = env == dense::KIND_MAZE ? 7 : env == dense::KIND_CARTPOLE || env == dense::ENV_ACROBOT ? 4 : 2, D = bc_dim(env);
     for (int i = 0; i < n; i++) bc_of_record(env, rec + (size_t)i * S, bc + (size_t)i * D);
 }
 

@@ -878,6 +878,7 @@ struct DeviceGuard {
 static_assert(DNE_KIND_CARTPOLE == DNE_KIND_MAZE + 1 && DNE_KIND_PENDULUM == DNE_KIND_MAZE + 2 && DNE_KIND_MJMAZE == DNE_KIND_MAZE + 3, "the table below");
 static const char *episodic_kind_name(int kind) {
     static const char *const names[] = {"DNE_KIND_MAZE", "DNE_KIND_CARTPOLE", "DNE_KIND_PENDULUM", "DNE_KIND_MJMAZE"};
+    if (kind == DNE_ENV_ACROBOT) return "DNE_ENV_ACROBOT";   // (an environment id: what a DNE_KIND_DENSE engine or a host twin steps)
     return names[kind - DNE_KIND_MAZE];
 }
 static int needs_kind(dne_handle *h, const char *call, int kind) {
@@ -1010,7 +1011,7 @@ static int dense_shape_error(const char *who, int code, int env, int n_hidden, c
     const std::string w(who);
     if (code == dense::SHAPE_OK) return 0;
     if (code == dense::SHAPE_ENV)
-        g_create_error = w + " runs on the environments DNE_KIND_MAZE (4), DNE_KIND_CARTPOLE (5) and DNE_KIND_PENDULUM (6); environment " + std::to_string(env) + " is refused";
+        g_create_error = w + " runs on the environments DNE_KIND_MAZE (4), DNE_KIND_CARTPOLE (5) and DNE_KIND_PENDULUM (6); environment " + std::to_string(env) + " is refused (DNE_ENV_ACROBOT (9) is the fourth)";
     else if (code == dense::SHAPE_LAYERS)
         g_create_error = w + " is built for 0.." + std::to_string(dense::MAX_HIDDEN) + " hidden layers; " + std::to_string(n_hidden) + " hidden layers are refused";
     else if (code == dense::SHAPE_WIDTH) {
@@ -1022,7 +1023,7 @@ static int dense_shape_error(const char *who, int code, int env, int n_hidden, c
         while (i < n_widths - 1 && widths[i] == 0) i++;
         g_create_error = w + ": " + std::to_string(n_hidden) + " hidden layers, and a width of " + std::to_string(widths[i]) + " behind them (entry " + std::to_string(i) + "); unused widths are 0";
     } else if (code == dense::SHAPE_OUT)
-        g_create_error = w + " has " + std::to_string(dense::env_outputs(env)) + " outputs on environment " + std::to_string(env) + " (the maze and the cart-pole 2, the pendulum 1), n_actions " + std::to_string(n_out) + " is refused";
+        g_create_error = w + " has " + std::to_string(dense::env_outputs(env)) + " outputs on environment " + std::to_string(env) + " (the maze and the cart-pole 2, the pendulum 1, the acrobot 3), n_actions " + std::to_string(n_out) + " is refused";
     else
         g_create_error = w + " has nonlinearities 0 (tanh) and 1 (relu); nonlinearity " + std::to_string(nonlin) + " is refused";
     return -1;
@@ -1040,6 +1041,7 @@ extern "C" int dne_num_params(int kind, int nact) {
     if (kind == DNE_KIND_PENDULUM) return -1;   // P depends on the hidden width: dne_pendulum_num_params
     if (kind == DNE_KIND_MJMAZE) return -1;     // likewise: dne_mjmaze_num_params
     if (kind == DNE_KIND_DENSE) return -1;      // P depends on the whole shape: dne_dense_num_params
+    if (kind == DNE_ENV_ACROBOT) return -1;     // an environment id, not a kind: dne_dense_num_params(DNE_ENV_ACROBOT, ...)
     Layout L;
     make_layout(kind, nact, &L);
     return L.P;
@@ -3444,11 +3446,12 @@ extern "C" int dne_mjmaze_forward_host(const float *theta, const float *obs, int
 // ------------------------------------------------------------------------------- environments stepped by the caller (csrc/step_env.h)
 static_assert(stepenv::KIND_MAZE == DNE_KIND_MAZE && stepenv::KIND_CARTPOLE == DNE_KIND_CARTPOLE && stepenv::KIND_PENDULUM == DNE_KIND_PENDULUM,
               "step_env.h restates the three kinds");
+static_assert(stepenv::ENV_ACROBOT == DNE_ENV_ACROBOT, "step_env.h restates the environment id");
 
 extern "C" int dne_stepenv_dims(int kind, int *obs, int *act, int *state, int *act_is_int) {
     stepenv::Dims d;
     if (!stepenv::dims(kind, &d)) {
-        g_create_error = "dne_stepenv_dims: kind " + std::to_string(kind) + " has no step-at-a-time environment (DNE_KIND_MAZE, DNE_KIND_CARTPOLE and DNE_KIND_PENDULUM have)";
+        g_create_error = "dne_stepenv_dims: kind " + std::to_string(kind) + " has no step-at-a-time environment (DNE_KIND_MAZE, DNE_KIND_CARTPOLE and DNE_KIND_PENDULUM have, and the id DNE_ENV_ACROBOT)";
         return -1;
     }
     if (obs) *obs = d.obs;
@@ -3518,7 +3521,7 @@ static int se_reset(dne_handle *h, const char *call, int n, const int32_t *indic
     std::vector<int32_t> idx;
     if (se_check(h, call, n, indices, false, idx)) return -1;
     const stepenv::Dims d = se_dims(h);
-    const bool is_maze = se_env(h) == DNE_KIND_MAZE, is_cartpole = se_env(h) == DNE_KIND_CARTPOLE;
+    const bool is_maze = se_env(h) == DNE_KIND_MAZE, is_cartpole = se_env(h) == DNE_KIND_CARTPOLE, is_acrobot = se_env(h) == DNE_ENV_ACROBOT;
     const int limit = stepenv::step_limit(max_steps, d.own_limit);
     if (set) {
         if (!state || !steps) return h->fail("%s: state or steps missing", call);
@@ -3539,6 +3542,8 @@ static int se_reset(dne_handle *h, const char *call, int n, const int32_t *indic
         hipLaunchKernelGGL(stepenv::k_stepenv_reset_maze, dim3((n + 3) / 4), dim3(64), 0, h->stream, h->se, se_maze_ctx(h), h->se_io_idx, n, init, h->se_io_steps, limit);
     else if (is_cartpole)
         hipLaunchKernelGGL(stepenv::k_stepenv_reset_cartpole, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->se, h->se_io_idx, n, h->se_io_seeds, init, h->se_io_steps, limit);
+    else if (is_acrobot)
+        hipLaunchKernelGGL(stepenv::k_stepenv_reset_acrobot, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->se, h->se_io_idx, n, h->se_io_seeds, init, h->se_io_steps, limit);
     else
         hipLaunchKernelGGL(stepenv::k_stepenv_reset_pendulum, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->se, h->se_io_idx, n, h->se_io_seeds, init, h->se_io_steps, limit);
     HCHECK(h, hipGetLastError());
@@ -3561,7 +3566,7 @@ static int se_step(dne_handle *h, const char *call, bool int_actions, int n, con
     std::vector<int32_t> idx;
     if (se_check(h, call, n, indices, true, idx)) return -1;
     const stepenv::Dims d = se_dims(h);
-    const bool is_maze = se_env(h) == DNE_KIND_MAZE, is_cartpole = se_env(h) == DNE_KIND_CARTPOLE;
+    const bool is_maze = se_env(h) == DNE_KIND_MAZE, is_cartpole = se_env(h) == DNE_KIND_CARTPOLE, is_acrobot = se_env(h) == DNE_ENV_ACROBOT;
     if ((d.act_is_int != 0) != int_actions)
         return h->fail("%s: a %s engine takes %s actions (dne_stepenv_step_%s)", call, episodic_kind_name(se_env(h)), d.act_is_int ? "int32" : "float",
                        d.act_is_int ? "i32" : "f32");
@@ -3571,6 +3576,11 @@ static int se_step(dne_handle *h, const char *call, bool int_actions, int n, con
             const int32_t a = ((const int32_t *)actions)[i];
             if (a != 0 && a != 1) return h->fail("%s: action %d at position %d, CartPole-v1 has actions 0 and 1", call, a, i);
         }
+    if (is_acrobot)
+        for (int i = 0; i < n; i++) {
+            const int32_t a = ((const int32_t *)actions)[i];
+            if (a < 0 || a > 2) return h->fail("%s: action %d at position %d, Acrobot-v1 has actions 0, 1 and 2", call, a, i);
+        }
     HCHECK(h, hipMemcpyAsync(h->se_io_idx, idx.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HCHECK(h, hipMemcpyAsync(h->se_io_act, actions, (size_t)n * d.act * sizeof(float), hipMemcpyHostToDevice, h->stream));   // (an int32 is a float's size)
     HCHECK(h, hipEventRecord(h->se_ev_a, h->stream));
@@ -3578,6 +3588,8 @@ static int se_step(dne_handle *h, const char *call, bool int_actions, int n, con
         hipLaunchKernelGGL(stepenv::k_stepenv_step_maze, dim3((n + 3) / 4), dim3(64), 0, h->stream, h->se, se_maze_ctx(h), h->se_io_idx, n, h->se_io_act, h->se_io_rew, h->se_io_done);
     else if (is_cartpole)
         hipLaunchKernelGGL(stepenv::k_stepenv_step_cartpole, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->se, h->se_io_idx, n, (const int32_t *)h->se_io_act, h->se_io_rew, h->se_io_done);
+    else if (is_acrobot)
+        hipLaunchKernelGGL(stepenv::k_stepenv_step_acrobot, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->se, h->se_io_idx, n, (const int32_t *)h->se_io_act, h->se_io_rew, h->se_io_done);
     else
         hipLaunchKernelGGL(stepenv::k_stepenv_step_pendulum, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->se, h->se_io_idx, n, h->se_io_act, h->se_io_rew, h->se_io_done);
     HCHECK(h, hipGetLastError());
@@ -3636,7 +3648,7 @@ extern "C" double dne_stepenv_last_ms(dne_handle *h) { return h->episodic() ? h-
 static int se_host_args(const char *call, int kind, int n, const float *header8, const float *lines, int n_walls, stepenv::MazeCtx *mz) {
     stepenv::Dims d;
     if (!stepenv::dims(kind, &d)) {
-        g_create_error = std::string(call) + ": kind " + std::to_string(kind) + " has no step-at-a-time environment (DNE_KIND_MAZE, DNE_KIND_CARTPOLE and DNE_KIND_PENDULUM have)";
+        g_create_error = std::string(call) + ": kind " + std::to_string(kind) + " has no step-at-a-time environment (DNE_KIND_MAZE, DNE_KIND_CARTPOLE and DNE_KIND_PENDULUM have, and the id DNE_ENV_ACROBOT)";
         return -1;
     }
     if (n < 1) { g_create_error = std::string(call) + ": n = " + std::to_string(n) + ", at least one environment is needed"; return -1; }
@@ -3664,10 +3676,20 @@ extern "C" int dne_stepenv_step_host(int kind, int n, const void *actions, const
     if (stepenv::step_host(kind, n, actions, &mz, state, steps, limit, done, reward, obs) == -2) {
         for (int i = 0; i < n; i++) {
             const int32_t a = ((const int32_t *)actions)[i];
-            if (a != 0 && a != 1) { g_create_error = "dne_stepenv_step_host: action " + std::to_string(a) + " at position " + std::to_string(i) + ", CartPole-v1 has actions 0 and 1"; break; }
+            if (kind == DNE_ENV_ACROBOT) {
+                if (a < 0 || a > 2) { g_create_error = "dne_stepenv_step_host: action " + std::to_string(a) + " at position " + std::to_string(i) + ", Acrobot-v1 has actions 0, 1 and 2"; break; }
+            } else if (a != 0 && a != 1) { g_create_error = "dne_stepenv_step_host: action " + std::to_string(a) + " at position " + std::to_string(i) + ", CartPole-v1 has actions 0 and 1"; break; }
         }
         return -1;
     }
+    return 0;
+}
+
+extern "C" int dne_acrobot_actions_host(const int32_t *actions, int n, int T, const double *init4, double *rows) {
+    if (n < 1 || T < 1 || !actions || !init4 || !rows) { g_create_error = "dne_acrobot_actions_host: bad arguments"; return -1; }
+    for (size_t i = 0; i < (size_t)n * T; i++)
+        if (actions[i] < 0 || actions[i] > 2) { g_create_error = "dne_acrobot_actions_host: action " + std::to_string(actions[i]) + ", Acrobot-v1 has actions 0, 1 and 2"; return -1; }
+    for (int i = 0; i < n; i++) acrobot::actions_host(actions + (size_t)i * T, T, init4 + 4 * (size_t)i, rows + (size_t)i * T * 5);
     return 0;
 }
 
@@ -3684,7 +3706,8 @@ static void dense_launch(dne_handle *h, int items, const dense::RunArgs &A) {
     const size_t lds = (size_t)A.shape.P * sizeof(float);
     if (A.shape.env == DNE_KIND_MAZE) hipLaunchKernelGGL(dense::k_dense_run<DNE_KIND_MAZE>, dim3(items), dim3(64), lds, h->stream, A);
     else if (A.shape.env == DNE_KIND_CARTPOLE) hipLaunchKernelGGL(dense::k_dense_run<DNE_KIND_CARTPOLE>, dim3(items), dim3(64), lds, h->stream, A);
-    else hipLaunchKernelGGL(dense::k_dense_run<DNE_KIND_PENDULUM>, dim3(items), dim3(64), lds, h->stream, A);
+    else if (A.shape.env == DNE_KIND_PENDULUM) hipLaunchKernelGGL(dense::k_dense_run<DNE_KIND_PENDULUM>, dim3(items), dim3(64), lds, h->stream, A);
+    else hipLaunchKernelGGL(dense::k_dense_run<DNE_ENV_ACROBOT>, dim3(items), dim3(64), lds, h->stream, A);
 }
 
 // what k_dense_run reads whatever it is used for: the members M (dne_set_members', or the GA bank's), the shape, the maze
@@ -3697,6 +3720,8 @@ static dense::RunArgs dense_args(dne_handle *h, const MazeMembers &M) {
     return A;
 }
 
+static const char *dense_env_name(int env) { return env == DNE_KIND_CARTPOLE ? "cart-pole" : env == DNE_ENV_ACROBOT ? "acrobot" : "pendulum"; }
+
 // members [0, n) of M, one whole episode each from its own reset, one launch; the step-at-a-time batch is not touched
 static int dense_eval(dne_handle *h, const MazeMembers &M, const char *call, int n, int tslimit, const uint32_t *env_seed, float *returns, float *signreturns,
                       int32_t *lengths, uint8_t *bc_out) {
@@ -3706,7 +3731,7 @@ static int dense_eval(dne_handle *h, const MazeMembers &M, const char *call, int
     if (tslimit <= 0) return h->fail("timestep limit must be positive");
     if (is_maze && h->maze_nw < 1) return h->fail("DNE_KIND_DENSE: no maze loaded (dne_maze_set_walls comes before an evaluation)");
     if (!is_maze && !env_seed) return h->fail("%s: a DNE_KIND_DENSE engine on the %s resets every member from its environment seed, env_seed is NULL", call,
-                                              h->dn_shape.env == DNE_KIND_CARTPOLE ? "cart-pole" : "pendulum");
+                                              dense_env_name(h->dn_shape.env));
     if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
     if (!is_maze) HCHECK(h, hipMemcpyAsync(h->seeds, env_seed, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     dense::RunArgs A = dense_args(h, M);
@@ -3909,7 +3934,7 @@ extern "C" int dne_dense_ga_eval(dne_handle *h, int n, const int32_t *parent, co
     if (tslimit <= 0) return h->fail("dne_dense_ga_eval: timestep limit must be positive");
     if (h->dn_shape.env != DNE_KIND_MAZE && !env_seed)
         return h->fail("dne_dense_ga_eval: a DNE_KIND_DENSE engine on the %s resets every member from its environment seed, env_seed is NULL",
-                       h->dn_shape.env == DNE_KIND_CARTPOLE ? "cart-pole" : "pendulum");
+                       dense_env_name(h->dn_shape.env));
     // a child is k_dense_run's own member: (its parent's bank slot, idx, power); a root runs from scratch slot 2 M + i at scale 0
     const int P = h->dn_shape.P, bank0 = h->mzg_half * h->M, root0 = 2 * h->M;
     std::vector<int32_t> &slot = h->mzg_host_slot;
@@ -3994,7 +4019,8 @@ static int dnv_last_bc(dne_handle *h) {
     const dim3 grid((n + 255) / 256), block(256);
     if (env == DNE_KIND_MAZE) hipLaunchKernelGGL(dense_novelty::k_dense_bc<DNE_KIND_MAZE>, grid, block, 0, h->stream, (const double *)h->dn_state, n, h->dn_bc);
     else if (env == DNE_KIND_CARTPOLE) hipLaunchKernelGGL(dense_novelty::k_dense_bc<DNE_KIND_CARTPOLE>, grid, block, 0, h->stream, (const double *)h->dn_state, n, h->dn_bc);
-    else hipLaunchKernelGGL(dense_novelty::k_dense_bc<DNE_KIND_PENDULUM>, grid, block, 0, h->stream, (const double *)h->dn_state, n, h->dn_bc);
+    else if (env == DNE_KIND_PENDULUM) hipLaunchKernelGGL(dense_novelty::k_dense_bc<DNE_KIND_PENDULUM>, grid, block, 0, h->stream, (const double *)h->dn_state, n, h->dn_bc);
+    else hipLaunchKernelGGL(dense_novelty::k_dense_bc<DNE_ENV_ACROBOT>, grid, block, 0, h->stream, (const double *)h->dn_state, n, h->dn_bc);
     HCHECK(h, hipGetLastError());
     h->dn_bc_valid = true;
     return 0;
@@ -4182,8 +4208,8 @@ extern "C" int dne_dense_novelty_pool_host(const float *bc, int n, const float *
 }
 
 extern "C" int dne_dense_bc_host(int env_kind, const double *rec, int n, float *bc) {
-    if (env_kind != DNE_KIND_MAZE && env_kind != DNE_KIND_CARTPOLE && env_kind != DNE_KIND_PENDULUM) {
-        g_create_error = "dne_dense_bc_host: environment " + std::to_string(env_kind) + " is none of DNE_KIND_MAZE, DNE_KIND_CARTPOLE, DNE_KIND_PENDULUM";
+    if (env_kind != DNE_KIND_MAZE && env_kind != DNE_KIND_CARTPOLE && env_kind != DNE_KIND_PENDULUM && env_kind != DNE_ENV_ACROBOT) {
+        g_create_error = "dne_dense_bc_host: environment " + std::to_string(env_kind) + " is none of DNE_KIND_MAZE, DNE_KIND_CARTPOLE, DNE_KIND_PENDULUM, DNE_ENV_ACROBOT";
         return -1;
     }
     if (!rec || !bc) { g_create_error = "dne_dense_bc_host: a buffer is missing"; return -1; }

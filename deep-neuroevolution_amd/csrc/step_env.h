@@ -1,4 +1,4 @@
-// step_env.h -- the hard maze, the cart-pole and the pendulum as environments of their own: a batch that persists between calls and moves ONE
+// step_env.h -- the hard maze, the cart-pole, the pendulum and the acrobot as environments of their own: a batch that persists between calls and moves ONE
 // step per call under actions the caller supplies (the seam of gym_tensorflow/tf_env.py:27-124: reset, step, observation, final_state apart
 // from the model).  Nothing is derived here: every operation is a function of maze.h, cartpole.h or pendulum.h, used, not copied, so a value
 // this header produces is bit for bit the one the whole-episode kernels and their host twins produce.  As those headers it is ONE
@@ -10,6 +10,8 @@
 //              state given from outside is rounded to those types, a value no int holds becomes 0); OBS 11; action float[2]; own limit 400
 //   cart-pole  S 4: x, x_dot, theta, theta_dot; OBS 4; action int32 in {0, 1}; own limit 500
 //   pendulum   S 2: theta, theta_dot; OBS 3; action float[1]; own limit 200
+//   acrobot    S 4: theta1, theta2, omega1, omega2; OBS 6; action int32 in {0, 1, 2}; own limit 500.  An environment id (ENV_ACROBOT,
+//              DNE_ENV_ACROBOT), not an engine kind: a DNE_KIND_DENSE engine created on it steps it, and every host twin takes the id
 // reset    maze: reset_state(header), the seed is not read; cart-pole and pendulum: reset_state(seed).  steps = 0, done = 0,
 //          limit = min(max_steps, own limit), max_steps <= 0 meaning the own limit (max_frames=None).
 // observe  what the whole-episode kernel's policy would see next: the maze's 11 floats of observe_host; the cart-pole's four state values cast
@@ -18,17 +20,20 @@
 //          and 0 on every other one (a smaller limit ends the episode at reward 0, as maze::rollout_host); done when steps == limit.
 //          cart-pole: reward 1 on every step taken, the terminating one included; done when cartpole::step's strict thresholds fire or
 //          steps == limit.  pendulum: pendulum::step (the torque clip is inside it), its float reward; done when steps == limit, never earlier.
+//          acrobot: acrobot::step; reward -1 on every step but the terminal one, which earns 0; done when terminal or steps == limit.
 // a done environment stepped again: reward 0, done stays 1, state, steps and observation keep every bit (advance returns false and its
 //          caller writes nothing back), so a caller may go on stepping a whole batch until its last member ends.
 #pragma once
 #include "maze.h"
 #include "cartpole.h"
 #include "pendulum.h"
+#include "acrobot.h"
 
 namespace dne {
 namespace stepenv {
 
 enum { KIND_MAZE = 4, KIND_CARTPOLE = 5, KIND_PENDULUM = 6 };   // DNE_KIND_* of include/dne_hip.h (engine.hip asserts the three)
+enum { ENV_ACROBOT = 9 };                                        // DNE_ENV_ACROBOT: an environment without an engine kind of its own
 constexpr int MAX_S = 7, MAX_OBS = 11, MAX_ACT = 2;
 
 struct Dims { int obs, act, state, act_is_int, own_limit; };
@@ -36,6 +41,7 @@ MZ_HD bool dims(int kind, Dims *d) {
     if (kind == KIND_MAZE) { d->obs = maze::OBS; d->act = 2; d->state = 7; d->act_is_int = 0; d->own_limit = maze::EPISODE_STEPS; return true; }
     if (kind == KIND_CARTPOLE) { d->obs = cartpole::OBS; d->act = 1; d->state = 4; d->act_is_int = 1; d->own_limit = cartpole::EPISODE_STEPS; return true; }
     if (kind == KIND_PENDULUM) { d->obs = pendulum::OBS; d->act = 1; d->state = 2; d->act_is_int = 0; d->own_limit = pendulum::EPISODE_STEPS; return true; }
+    if (kind == ENV_ACROBOT) { d->obs = acrobot::OBS; d->act = 1; d->state = 4; d->act_is_int = 1; d->own_limit = acrobot::EPISODE_STEPS; return true; }
     return false;
 }
 MZ_HD int step_limit(int max_steps, int own) { return max_steps <= 0 || max_steps > own ? own : max_steps; }
@@ -55,6 +61,8 @@ MZ_HD void unpack(const double *p, cartpole::State &s) { s.x = p[0]; s.x_dot = p
 MZ_HD void pack(const cartpole::State &s, double *p) { p[0] = s.x; p[1] = s.x_dot; p[2] = s.theta; p[3] = s.theta_dot; }
 MZ_HD void unpack(const double *p, pendulum::State &s) { s.theta = p[0]; s.theta_dot = p[1]; }
 MZ_HD void pack(const pendulum::State &s, double *p) { p[0] = s.theta; p[1] = s.theta_dot; }
+MZ_HD void unpack(const double *p, acrobot::State &s) { s.th1 = p[0]; s.th2 = p[1]; s.w1 = p[2]; s.w2 = p[3]; }
+MZ_HD void pack(const acrobot::State &s, double *p) { p[0] = s.th1; p[1] = s.th2; p[2] = s.w1; p[3] = s.w2; }
 
 // ---- the maze: who looks at which walls -------------------------------------------------------------------------------------------------------
 // sense_partial and collide_partial take (w0, stride).  Solo is one caller over every wall (the CPU twin: observe_host's own call); Row16 is
@@ -92,6 +100,7 @@ MZ_HD void observe(const pendulum::State &s, float *obs) {
     const pendulum::Seen v = pendulum::look(s);
     for (int i = 0; i < pendulum::OBS; i++) obs[i] = v.ob[i];
 }
+MZ_HD void observe(const acrobot::State &s, float *obs) { acrobot::make_obs(s, obs); }
 
 // ---- advance: one step of one environment -----------------------------------------------------------------------------------------------------
 // (state, steps, limit, done, action) -> (state, steps, done, reward, observation).  Returns false for an environment that was done already:
@@ -130,10 +139,20 @@ MZ_HD bool advance(pendulum::State &s, int &steps, int limit, int &done, float a
     observe(s, obs);
     return true;
 }
+MZ_HD bool advance(acrobot::State &s, int &steps, int limit, int &done, int a, float &reward, float *obs) {
+    reward = 0.0f;
+    if (done) return false;
+    const bool over = acrobot::step(s, a);
+    steps++;
+    reward = over ? 0.0f : -1.0f;
+    done = over || steps >= limit;
+    observe(s, obs);
+    return true;
+}
 
 // ---- the CPU twins: n environments in arrays of exactly their size -------------------------------------------------------------------------------
 // state [n][S], steps [n], limit [n], done [n], obs [n][OBS]; mz for the maze only.  Return 0, -1 for a kind that has no environment here,
-// -2 for a cart-pole action outside {0, 1} (checked for all n before anything moves).
+// -2 for a cart-pole action outside {0, 1} or an acrobot action outside {0, 1, 2} (checked for all n before anything moves).
 inline int observe_host(int kind, int n, const double *state, const MazeCtx *mz, float *obs) {
     if (kind == KIND_MAZE) {
         maze::SinCosF dir[6];
@@ -143,6 +162,8 @@ inline int observe_host(int kind, int n, const double *state, const MazeCtx *mz,
         for (int i = 0; i < n; i++) { cartpole::State s; unpack(state + (size_t)i * 4, s); observe(s, obs + (size_t)i * cartpole::OBS); }
     } else if (kind == KIND_PENDULUM) {
         for (int i = 0; i < n; i++) { pendulum::State s; unpack(state + (size_t)i * 2, s); observe(s, obs + (size_t)i * pendulum::OBS); }
+    } else if (kind == ENV_ACROBOT) {
+        for (int i = 0; i < n; i++) { acrobot::State s; unpack(state + (size_t)i * 4, s); observe(s, obs + (size_t)i * acrobot::OBS); }
     } else return -1;
     return 0;
 }
@@ -154,7 +175,8 @@ inline int reset_host(int kind, int n, const uint32_t *seeds, const MazeCtx *mz,
     for (int i = 0; i < n; i++) {
         if (kind == KIND_MAZE) pack(maze::reset_state(mz->hdr), state + (size_t)i * 7);
         else if (kind == KIND_CARTPOLE) pack(cartpole::reset_state(seeds[i]), state + (size_t)i * 4);
-        else pack(pendulum::reset_state(seeds[i]), state + (size_t)i * 2);
+        else if (kind == KIND_PENDULUM) pack(pendulum::reset_state(seeds[i]), state + (size_t)i * 2);
+        else pack(acrobot::reset_state(seeds[i]), state + (size_t)i * 4);
         steps[i] = 0; done[i] = 0; limit[i] = step_limit(max_steps, d.own_limit);
     }
     return observe_host(kind, n, state, mz, obs);
@@ -196,6 +218,18 @@ inline int step_host(int kind, int n, const void *actions, const MazeCtx *mz, do
             if (advance(s, t, limit[i], dn, a[i], reward[i], o)) {
                 pack(s, state + (size_t)i * 2); steps[i] = t; done[i] = (uint8_t)dn;
                 for (int k = 0; k < pendulum::OBS; k++) obs[(size_t)i * pendulum::OBS + k] = o[k];
+            }
+        }
+    } else if (kind == ENV_ACROBOT) {
+        const int32_t *a = (const int32_t *)actions;
+        for (int i = 0; i < n; i++) if (a[i] < 0 || a[i] > 2) return -2;
+        for (int i = 0; i < n; i++) {
+            acrobot::State s; unpack(state + (size_t)i * 4, s);
+            int t = steps[i], dn = done[i];
+            float o[acrobot::OBS];
+            if (advance(s, t, limit[i], dn, (int)a[i], reward[i], o)) {
+                pack(s, state + (size_t)i * 4); steps[i] = t; done[i] = (uint8_t)dn;
+                for (int k = 0; k < acrobot::OBS; k++) obs[(size_t)i * acrobot::OBS + k] = o[k];
             }
         }
     } else return -1;
@@ -273,7 +307,7 @@ __global__ __launch_bounds__(64) void k_stepenv_step_maze(const Batch B, const M
     }
 }
 
-// The cart-pole and the pendulum: one lane per environment, 64-thread workgroups.
+// The cart-pole, the pendulum and the acrobot: one lane per environment, 64-thread workgroups.
 __global__ __launch_bounds__(64) void k_stepenv_reset_cartpole(const Batch B, const int32_t *idx, int n, const uint32_t *seeds, const double *init,
                                                                const int32_t *init_steps, int limit) {
     const int k = blockIdx.x * 64 + threadIdx.x;
@@ -330,6 +364,36 @@ __global__ __launch_bounds__(64) void k_stepenv_step_pendulum(const Batch B, con
         B.steps[e] = steps; B.done[e] = (uint8_t)done;
 #pragma unroll
         for (int i = 0; i < pendulum::OBS; i++) B.obs[(size_t)e * pendulum::OBS + i] = obs[i];
+    }
+    reward[k] = r; done_out[k] = (uint8_t)done;
+}
+
+__global__ __launch_bounds__(64) void k_stepenv_reset_acrobot(const Batch B, const int32_t *idx, int n, const uint32_t *seeds, const double *init,
+                                                              const int32_t *init_steps, int limit) {
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= n) return;
+    const int e = idx[k];
+    acrobot::State s;
+    if (init) unpack(init + (size_t)k * 4, s); else s = acrobot::reset_state(seeds[k]);
+    pack(s, B.state + (size_t)e * 4);
+    B.steps[e] = init ? init_steps[k] : 0; B.limit[e] = limit; B.done[e] = 0;
+    observe(s, B.obs + (size_t)e * acrobot::OBS);
+}
+
+__global__ __launch_bounds__(64) void k_stepenv_step_acrobot(const Batch B, const int32_t *idx, int n, const int32_t *act, float *reward,
+                                                             uint8_t *done_out) {
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= n) return;
+    const int e = idx[k];
+    acrobot::State s;
+    unpack(B.state + (size_t)e * 4, s);
+    int steps = B.steps[e], done = B.done[e];
+    float obs[acrobot::OBS], r;
+    if (advance(s, steps, B.limit[e], done, (int)act[k], r, obs)) {
+        pack(s, B.state + (size_t)e * 4);
+        B.steps[e] = steps; B.done[e] = (uint8_t)done;
+#pragma unroll
+        for (int i = 0; i < acrobot::OBS; i++) B.obs[(size_t)e * acrobot::OBS + i] = obs[i];
     }
     reward[k] = r; done_out[k] = (uint8_t)done;
 }

@@ -30,7 +30,9 @@ KIND_MJMAZE = 7   # MujocoPolicy on the hard maze (final (x, y) as the behaviour
 MJMAZE_OBS, MJMAZE_ADIM, MJMAZE_STEPS, MJMAZE_TRACE_W, MJMAZE_MAX_BINS = 11, 2, 400, 20, 8   # observations, action dimensions, steps, floats per trace row, most bins a dimension
 MJMAZE_AC_NOISE = MJMAZE_ADIM * MJMAZE_STEPS            # action-noise values an episode reads from the table
 MJMAZE_AC_LOW, MJMAZE_AC_HIGH = -0.5, 0.5               # the action space: what the maze clamps its raw outputs to
-KIND_DENSE = 8    # a dense policy of any small shape (0..3 hidden layers of width 1..64) on the maze, the cart-pole or the pendulum (csrc/dense.h)
+KIND_DENSE = 8    # a dense policy of any small shape (0..3 hidden layers of width 1..64) on the maze, the cart-pole, the pendulum or the acrobot (csrc/dense.h)
+ENV_ACROBOT = 9   # DNE_ENV_ACROBOT: gym.Acrobot-v1 (csrc/acrobot.h), an environment id -- no engine kind: a KIND_DENSE engine is created on it (env=ENV_ACROBOT, 3 outputs)
+ACROBOT_OBS, ACROBOT_STEPS, ACROBOT_ACTIONS = 6, 500, 3   # observation width, Acrobot-v1's max_episode_steps, actions (torque -1 / 0 / +1)
 DENSE_NONLINS = {'tanh': 0, 'relu': 1}                # dne_config.reserved[2] of a KIND_DENSE engine
 MUJOCO_KINDS = (KIND_PENDULUM, KIND_MJMAZE)             # the kinds whose shape travels in dne_config.reserved
 ES_KINDS = (KIND_ES, KIND_ES_VBN)   # virtual batch norm over a reference batch, antithetic pairs
@@ -564,7 +566,8 @@ def pendulum_math_host(fn, x, a=0.0, b=1.0):
     return out
 
 
-STEPENV_KINDS = (KIND_MAZE, KIND_CARTPOLE, KIND_PENDULUM)   # the kinds with a step-at-a-time environment (csrc/step_env.h)
+STEPENV_KINDS = (KIND_MAZE, KIND_CARTPOLE, KIND_PENDULUM)   # the engine kinds that step their own environment (csrc/step_env.h)
+STEP_ENVS = STEPENV_KINDS + (ENV_ACROBOT,)                  # every id that has a step environment: those kinds, and the environments a KIND_DENSE engine alone steps
 
 
 def stepenv_dims(kind):
@@ -573,6 +576,19 @@ def stepenv_dims(kind):
     v = [C.c_int(0) for _ in range(4)]
     _ck_host(load().dne_stepenv_dims(int(kind), *[C.byref(x) for x in v]))
     return v[0].value, v[1].value, v[2].value, bool(v[3].value)
+
+
+def acrobot_actions_host(actions, init):
+    """dne_acrobot_actions_host: the acrobot alone under open-loop actions [n][T] (0 / 1 / 2) from initial states [n][4] -> rows float64
+    [n][T][5] = the state after each step, then terminal (1 / 0); the stepping goes on past it"""
+    actions = _arr(actions, np.int32); actions = actions.reshape(-1, actions.shape[-1])
+    n, T = actions.shape
+    init = _arr(init, np.float64).reshape(-1, 4)
+    if init.shape[0] != n:
+        raise DneError("acrobot_actions_host: %d sequences, %d initial states" % (n, init.shape[0]))
+    rows = np.empty((n, T, 5), np.float64)
+    _ck_host(load().dne_acrobot_actions_host(_ptr(actions, C.c_int32), n, T, _ptr(init, C.c_double), _ptr(rows, C.c_double)))
+    return rows
 
 
 def _stepenv_maze(kind, header, lines):
@@ -603,7 +619,7 @@ def stepenv_reset_host(kind, n, seeds=None, max_steps=0, header=None, lines=None
 
 
 def _stepenv_actions(kind, actions, n):
-    """the actions of one step as the C ABI takes them: float32 [n][2] (maze), int32 [n] (cart-pole), float32 [n] (pendulum)"""
+    """the actions of one step as the C ABI takes them: float32 [n][2] (maze), int32 [n] (cart-pole, acrobot), float32 [n] (pendulum)"""
     _, act_w, _, is_int = stepenv_dims(kind)
     a = _arr(actions, np.int32 if is_int else np.float32).reshape(-1)
     if a.size != n * act_w:
@@ -655,7 +671,7 @@ def dense_forward_host(theta, obs, env_kind, hidden, nonlin, n_out):
     float32 [n][n_out], actions as stepenv_step takes them)"""
     env_kind, n_out = int(env_kind), int(n_out)
     L, w, nl = _dense_shape(hidden, nonlin)
-    obs_w, act_w, _, is_int = stepenv_dims(env_kind) if env_kind in STEPENV_KINDS else (1, 1, 1, False)
+    obs_w, act_w, _, is_int = stepenv_dims(env_kind) if env_kind in STEP_ENVS else (1, 1, 1, False)
     P = load().dne_dense_num_params(env_kind, L, _ptr(w, C.c_int32), n_out)
     if P < 0:   # (one row of whatever was given: the call below names what is wrong with the shape)
         theta, obs = _arr(theta, np.float32).reshape(1, -1), _arr(obs, np.float32).reshape(1, -1)
@@ -676,7 +692,7 @@ def dense_rollout_host(theta, env_kind, hidden, nonlin, n_out, seeds=None, tslim
     the environment's own limit or tslimit (<= 0: the own limit) -> dict(returns, signreturns, lengths, state float64 [n][S])"""
     env_kind, n_out = int(env_kind), int(n_out)
     L, w, nl = _dense_shape(hidden, nonlin)
-    S = stepenv_dims(env_kind)[2] if env_kind in STEPENV_KINDS else 1   # (another kind: the call below refuses it by name)
+    S = stepenv_dims(env_kind)[2] if env_kind in STEP_ENVS else 1   # (another kind: the call below refuses it by name)
     P = load().dne_dense_num_params(env_kind, L, _ptr(w, C.c_int32), n_out)
     theta = _arr(theta, np.float32)
     theta = theta.reshape(-1, P) if P > 0 else theta.reshape(1, -1)   # (a shape that is not built: one row, the call below names what is wrong)
@@ -688,7 +704,7 @@ def dense_rollout_host(theta, env_kind, hidden, nonlin, n_out, seeds=None, tslim
     if init is not None:
         init = _arr(init, np.float64).reshape(n, S)
     if int(tslimit) <= 0:
-        tslimit = {KIND_MAZE: MAZE_STEPS, KIND_CARTPOLE: CARTPOLE_STEPS, KIND_PENDULUM: PENDULUM_STEPS}.get(env_kind, 1)
+        tslimit = {KIND_MAZE: MAZE_STEPS, KIND_CARTPOLE: CARTPOLE_STEPS, KIND_PENDULUM: PENDULUM_STEPS, ENV_ACROBOT: ACROBOT_STEPS}.get(env_kind, 1)
     hp, lp, nw, _keep = _stepenv_maze(env_kind, header, lines)
     ret = np.empty(n, np.float32); sign = np.empty(n, np.float32); ln = np.empty(n, np.int32); state = np.empty((n, S), np.float64)
     _ck_host(load().dne_dense_rollout_host(_ptr(theta, C.c_float), n, env_kind, L, _ptr(w, C.c_int32), nl, n_out, _ptr(seeds, C.c_uint32),
@@ -725,14 +741,15 @@ def dense_ga_members_host(noise, scale_by, bank, parent, idx, power):
 
 # ---- novelty over final states on a dense policy (csrc/dense_novelty.h) ---------------------------------------------------------------------------
 def dense_bc_dim(env_kind):
-    """D of an environment's behaviour characterisation: the cart-pole 4 (x, x_dot, theta, theta_dot), the maze (x, y) and the pendulum (theta, theta_dot) 2"""
-    return 4 if int(env_kind) == KIND_CARTPOLE else 2
+    """D of an environment's behaviour characterisation: the cart-pole 4 (x, x_dot, theta, theta_dot), the acrobot 4 (theta1, theta2, omega1,
+    omega2), the maze (x, y) and the pendulum (theta, theta_dot) 2"""
+    return 4 if int(env_kind) in (KIND_CARTPOLE, ENV_ACROBOT) else 2
 
 
 def dense_bc_host(env_kind, rec):
     """dne_dense_bc_host: the BCs float32 [n][D] of final state records float64 [n][S] (dense_final_state's, dense_rollout_host's 'state')"""
     env_kind = int(env_kind)
-    S = stepenv_dims(env_kind)[2] if env_kind in STEPENV_KINDS else 1   # (another kind: the call below refuses it by name)
+    S = stepenv_dims(env_kind)[2] if env_kind in STEP_ENVS else 1   # (another kind: the call below refuses it by name)
     rec = None if rec is None else _arr(rec, np.float64).reshape(-1, S)
     n = 0 if rec is None else int(rec.shape[0])
     out = np.empty((n, dense_bc_dim(env_kind)), np.float32)
@@ -795,8 +812,8 @@ class Engine:
                  record_bc=False, bc_max_steps=0, profile_events=False, bc_final_only=False, hidden=0, ac_mode=0, nonlin=0, env=None):
         """hidden, ac_mode, nonlin: the shape of a KIND_PENDULUM or KIND_MJMAZE engine (hidden width 64 / 128 / 256; 'continuous' or 'uniform';
         'tanh' or 'relu'), with n_actions the outputs (the pendulum: 1, or the bins; the maze: 2, or twice the bins).
-        A KIND_DENSE engine: env the environment's kind (KIND_MAZE, KIND_CARTPOLE or KIND_PENDULUM), hidden the tuple of hidden widths (() is
-        LinearClassifier), nonlin 'tanh' or 'relu', n_actions the outputs (2, 2, 1)"""
+        A KIND_DENSE engine: env the environment (KIND_MAZE, KIND_CARTPOLE, KIND_PENDULUM or ENV_ACROBOT), hidden the tuple of hidden widths
+        (() is LinearClassifier), nonlin 'tanh' or 'relu', n_actions the outputs (2, 2, 1, 3)"""
         self.lib = load()
         self.kind, self.n_actions, self.max_members = int(kind), int(n_actions), int(max_members)
         self.ref_count = int(ref_count) if kind in ES_KINDS else 0
@@ -1163,10 +1180,10 @@ class Engine:
         """dne_stepenv_step_f32 / _i32 by the dtype the kind takes: one step of the named environments under actions (maze float32 [n][2],
         cart-pole int32 [n], pendulum float32 [n]) -> (reward float32 [n], done bool [n]).  as_int names the entry point outright (the engine
         refuses the one its kind does not take)."""
-        is_int = bool(as_int) if as_int is not None else stepenv_dims(self.env_kind)[3] if self.env_kind in STEPENV_KINDS else np.asarray(actions).dtype.kind in "iu"
+        is_int = bool(as_int) if as_int is not None else stepenv_dims(self.env_kind)[3] if self.env_kind in STEP_ENVS else np.asarray(actions).dtype.kind in "iu"
         a = _arr(actions, np.int32 if is_int else np.float32)
         ip, n, _keep = self._stepenv_idx(indices, a.shape[0] if a.ndim else 1)
-        if as_int is None and self.env_kind in STEPENV_KINDS and a.size != n * stepenv_dims(self.env_kind)[1]:
+        if as_int is None and self.env_kind in STEP_ENVS and a.size != n * stepenv_dims(self.env_kind)[1]:
             raise DneError("stepenv_step: %d environments take %d action values, %d given" % (n, n * stepenv_dims(self.env_kind)[1], a.size))
         rew = np.empty(n, np.float32); done = np.empty(n, np.uint8)
         if is_int:
@@ -1178,7 +1195,7 @@ class Engine:
     def stepenv_observation(self, indices=None, n=None):
         """dne_stepenv_observation: what the policy sees next, float32 [n][OBS] in the order of the list"""
         ip, n, _keep = self._stepenv_idx(indices, n)
-        w = stepenv_dims(self.env_kind)[0] if self.env_kind in STEPENV_KINDS else 1
+        w = stepenv_dims(self.env_kind)[0] if self.env_kind in STEP_ENVS else 1
         out = np.empty((max(n, 0), w), np.float32)
         self._ck(self.lib.dne_stepenv_observation(self.h, n, ip, _ptr(out, C.c_float)))
         return out
@@ -1186,7 +1203,7 @@ class Engine:
     def stepenv_state(self, indices=None, n=None):
         """dne_stepenv_get_state: (state float64 [n][S], steps int32 [n], done bool [n])"""
         ip, n, _keep = self._stepenv_idx(indices, n)
-        S = stepenv_dims(self.env_kind)[2] if self.env_kind in STEPENV_KINDS else 1
+        S = stepenv_dims(self.env_kind)[2] if self.env_kind in STEP_ENVS else 1
         state = np.empty((max(n, 0), S), np.float64); steps = np.empty(max(n, 0), np.int32); done = np.empty(max(n, 0), np.uint8)
         self._ck(self.lib.dne_stepenv_get_state(self.h, n, ip, _ptr(state, C.c_double), _ptr(steps, C.c_int32), _ptr(done, C.c_uint8)))
         return state, steps, done.astype(bool)
@@ -1194,7 +1211,7 @@ class Engine:
     def stepenv_set_state(self, state, steps=None, indices=None, max_steps=0):
         """dne_stepenv_set_state: the named environments are put into states float64 [n][S] with `steps` already taken (default 0); the
         observation is recomputed, done cleared, the limit set as by a reset"""
-        S = stepenv_dims(self.env_kind)[2] if self.env_kind in STEPENV_KINDS else 1
+        S = stepenv_dims(self.env_kind)[2] if self.env_kind in STEP_ENVS else 1
         state = _arr(state, np.float64).reshape(-1, S)
         ip, n, _keep = self._stepenv_idx(indices, state.shape[0])
         steps = np.zeros(n, np.int32) if steps is None else _arr(steps, np.int32).reshape(-1)
@@ -1221,7 +1238,7 @@ class Engine:
         indices[i] -> (out float32 [n][outputs], actions as stepenv_step takes them)"""
         ip, n, _keep = self._stepenv_idx(indices, n)
         mp, _keep2 = self._stepenv_members(members, n)
-        obs_w, act_w, _, is_int = stepenv_dims(self.env_kind) if self.env_kind in STEPENV_KINDS else (1, 1, 1, False)
+        obs_w, act_w, _, is_int = stepenv_dims(self.env_kind) if self.env_kind in STEP_ENVS else (1, 1, 1, False)
         out = np.empty((max(n, 0), self.n_actions), np.float32)
         act = np.empty((max(n, 0), act_w) if act_w > 1 else max(n, 0), np.int32 if is_int else np.float32)
         self._ck(self.lib.dne_stepenv_act(self.h, n, ip, mp, _ptr(out, C.c_float), C.cast(_ptr(act, C.c_int32 if is_int else C.c_float), C.c_void_p)))
@@ -1238,7 +1255,7 @@ class Engine:
 
     def dense_final_state(self, n):
         """dne_dense_final_state: the final states float64 [n][S] of the last evaluation"""
-        S = stepenv_dims(self.env_kind)[2] if self.env_kind in STEPENV_KINDS else 1
+        S = stepenv_dims(self.env_kind)[2] if self.env_kind in STEP_ENVS else 1
         out = np.empty((max(int(n), 0), S), np.float64)
         self._ck(self.lib.dne_dense_final_state(self.h, int(n), _ptr(out, C.c_double)))
         return out

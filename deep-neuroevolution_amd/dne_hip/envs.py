@@ -1,4 +1,4 @@
-"""The hard maze, the cart-pole and the pendulum as batched environments of their own: the surface of the GPU tree's
+"""The hard maze, the cart-pole, the pendulum and the acrobot as batched environments of their own: the surface of the GPU tree's
 gym_tensorflow/tf_env.py:27-124 (reset / step / observation / final_state apart from the model) without TensorFlow, over the engine's
 step-at-a-time batch (csrc/step_env.h, dne_stepenv_*).  One object = the first batch_size environments of one engine; every value it returns
 is the one the whole-episode kernels compute, bit for bit, so a policy the kernels do not contain -- a LinearClassifier, a wider net, a
@@ -13,12 +13,13 @@ import numpy as np
 from . import _lib
 from .maze_run import maze_file
 
-MAZE_GAME, CARTPOLE_GAME, PENDULUM_GAME = 'maze', 'gym.CartPole-v1', 'Pendulum-v0'
+MAZE_GAME, CARTPOLE_GAME, PENDULUM_GAME, ACROBOT_GAME = 'maze', 'gym.CartPole-v1', 'Pendulum-v0', 'gym.Acrobot-v1'
 
 
 class HipStepEnv:
-    """what the three classes share; a subclass names its kind, game and env_default_timestep_cutoff"""
+    """what the four classes share; a subclass names its kind, game and env_default_timestep_cutoff (n_actions: of a discrete action space)"""
     kind = None
+    n_actions = 2
     game = None
     env_default_timestep_cutoff = None
 
@@ -41,7 +42,7 @@ class HipStepEnv:
 
     def _open_dense(self, batch_size, hidden, nonlin):
         """an engine whose policy is a dense stack of the caller's shape (hidden: the tuple of widths, () a LinearClassifier) on this environment"""
-        return _lib.Engine(_lib.KIND_DENSE, 1 if self.kind == _lib.KIND_PENDULUM else 2, max_members=batch_size, env=self.kind, hidden=tuple(hidden), nonlin=nonlin)
+        return _lib.Engine(_lib.KIND_DENSE, 1 if self.kind == _lib.KIND_PENDULUM else self.n_actions, max_members=batch_size, env=self.kind, hidden=tuple(hidden), nonlin=nonlin)
 
     # ---- tf_env.py's properties
     @property
@@ -51,7 +52,7 @@ class HipStepEnv:
     @property
     def action_space(self):
         """the number of actions (discrete) or the action's width (continuous)"""
-        return 2 if self._int_act else self._act_w
+        return self.n_actions if self._int_act else self._act_w
 
     @property
     def discrete_action(self):
@@ -129,11 +130,22 @@ class HipPendulumEnv(HipStepEnv):
         return _lib.Engine(self.kind, 1, max_members=batch_size, hidden=64)
 
 
-_GAMES = {MAZE_GAME: HipMazeEnv, CARTPOLE_GAME: HipCartPoleEnv, PENDULUM_GAME: HipPendulumEnv}
+class HipAcrobotEnv(HipStepEnv):
+    """gym.Acrobot-v1 (csrc/acrobot.h): six observations (cos, sin of both angles, both velocities), actions 0 / 1 / 2 (torque -1 / 0 / +1), reward
+    -1 a step and 0 on the step that swings the free end above the line, at most 500 steps.  There is no native engine kind: the engine is a
+    KIND_DENSE one created on the environment (hidden=() unless given), whose policy envs.run puts behind the batch"""
+    kind, game, env_default_timestep_cutoff, n_actions = _lib.ENV_ACROBOT, ACROBOT_GAME, _lib.ACROBOT_STEPS, _lib.ACROBOT_ACTIONS
+
+    def _open(self, batch_size):
+        return self._open_dense(batch_size, (), 'relu')
+
+
+_GAMES = {MAZE_GAME: HipMazeEnv, CARTPOLE_GAME: HipCartPoleEnv, PENDULUM_GAME: HipPendulumEnv, ACROBOT_GAME: HipAcrobotEnv}
 
 
 def make(game, batch_size, engine=None, **kw):
-    """gym_tensorflow.make for the three games: 'maze' (maze_file=... as the maze drivers take it), 'gym.CartPole-v1', 'Pendulum-v0'.  engine:
+    """gym_tensorflow.make for the four games: 'maze' (maze_file=... as the maze drivers take it), 'gym.CartPole-v1', 'Pendulum-v0',
+    'gym.Acrobot-v1' (always on a KIND_DENSE engine: the environment has no kind of its own).  engine:
     an Engine of the game's kind with max_members >= batch_size (None: one is made and closed with the environment); seed=... starts np_random.
     hidden=(...) (and nonlin='relu' or 'tanh'): the engine made is a KIND_DENSE one whose policy is a dense stack of those hidden widths on the
     game's environment (() is a LinearClassifier), so that run() below keeps whole episodes on the device; an engine of that kind may be passed in too"""

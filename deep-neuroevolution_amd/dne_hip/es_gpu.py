@@ -46,6 +46,12 @@ stream's first draw.  A caller's engine of kind KIND_DENSE, of any shape, is acc
 'LinearClassifier' without hidden layers, else as dense_model_name writes the shape); one whose environment is not the game's is refused, naming
 both.  SimpleClassifier keeps its own kinds and kernels.
 
+exp['game'] == 'gym.Acrobot-v1' (csrc/acrobot.h) has no engine kind of its own: every run is a DNE_KIND_DENSE engine created on
+the environment id ENV_ACROBOT, through the same episodic loop.  Without an engine exp['model'] == 'LinearClassifier' opens one with no hidden
+layer (P = 21) and 'SimpleClassifier' one of hidden (16, 16), relu (P = 435); a caller's KIND_DENSE engine of any shape on that environment is
+accepted (acrobot_run).  'env_default' means 500 steps and a larger cutoff leaves 500 in force, as on the cart-pole; the game is recorded in
+snapshot.pkl.  'gym.MountainCar-v0', 'gym.CartPole-v0', 'gym.Acrobot-v0' and every other 'gym.*' name stay refused by name.
+
 Where the arithmetic lives: ranks, sum_i w_i * noise[idx_i] / 2N, -g + l2coeff * theta and the optimizer step are dne_es_update on the device
 (the same formulas as es_distributed: es.py:227-246 here = es_distributed/es.py:281-301).  The GPU tree's SGD keeps v = momentum * v + g
 (neuroevolution/optimizers.py:49-51) where es_distributed keeps (1 - momentum) * g: with u = (1 - momentum) * v that is the engine's SGD at
@@ -61,7 +67,8 @@ import numpy as np
 from . import _lib
 from .es import SharedNoiseTable, get_ref_batch, optimizer_args, parse_cutoff
 from .ga_gpu import Offspring, Schedule, model_scale_by
-from . import cartpole_run
+from . import acrobot_run, cartpole_run
+from .acrobot_run import ACROBOT_GAME
 from .cartpole_run import CARTPOLE_GAME
 from .maze_run import MAZE_FILE, MAZE_MODEL, attach_table, check_engine, maze_file, open_engine   # noqa: F401 (MAZE_FILE, maze_file: read as es_gpu's by callers)
 
@@ -69,7 +76,8 @@ from .maze_run import MAZE_FILE, MAZE_MODEL, attach_table, check_engine, maze_fi
 MODEL_KINDS = {'ModelVirtualBN': _lib.KIND_ES, 'LargeModel': _lib.KIND_GA_LARGE}
 FLAT_LAYOUTS = {'es_distributed': _lib.KIND_ES, 'native': _lib.KIND_ES_VBN}   # exp['flat_layout'] -> the engine kind that runs it
 LINEAR_MODEL = 'LinearClassifier'        # neuroevolution/models/simple.py:23-27, on a KIND_DENSE engine without hidden layers
-DENSE_GAMES = {_lib.KIND_MAZE: 'maze', _lib.KIND_CARTPOLE: CARTPOLE_GAME, _lib.KIND_PENDULUM: 'Pendulum-v0'}   # a KIND_DENSE engine's environment -> its game
+DENSE_GAMES = {_lib.KIND_MAZE: 'maze', _lib.KIND_CARTPOLE: CARTPOLE_GAME, _lib.KIND_PENDULUM: 'Pendulum-v0',
+               _lib.ENV_ACROBOT: ACROBOT_GAME}   # a KIND_DENSE engine's environment -> its game
 
 
 def dense_model_name(engine):
@@ -131,6 +139,8 @@ def _env_limit(engine):
     kind = getattr(engine, 'env_kind', engine.kind)   # (a KIND_DENSE engine: the environment it was created on)
     if kind == _lib.KIND_CARTPOLE:
         return _lib.CARTPOLE_STEPS
+    if kind == _lib.ENV_ACROBOT:
+        return _lib.ACROBOT_STEPS
     return _lib.MAZE_STEPS if kind == _lib.KIND_MAZE else _lib.ENV_MAX_EPISODE_STEPS
 
 
@@ -158,21 +168,28 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
     n_pairs = exp['population_size'] // 2
     asked = exp['model'] if engine is None else exp.get('model')   # the caller's engine decides; a name given with it must agree
     game = exp.get('game')
-    if isinstance(game, str) and game.startswith('gym.') and game != CARTPOLE_GAME:
-        raise NotImplementedError("game {!r}: of gym_tensorflow's 'gym.*' environments this loop runs {!r} only".format(game, CARTPOLE_GAME))
-    dense = engine.kind == _lib.KIND_DENSE if engine is not None else asked == LINEAR_MODEL   # a dense stack on a step environment (csrc/dense.h)
+    if isinstance(game, str) and game.startswith('gym.') and game not in (CARTPOLE_GAME, ACROBOT_GAME):
+        raise NotImplementedError("game {!r}: of gym_tensorflow's 'gym.*' environments this loop runs {!r} only, and {!r} on a dense policy".format(
+            game, CARTPOLE_GAME, ACROBOT_GAME))
+    if game == ACROBOT_GAME:                                          # no kind of its own: a KIND_DENSE engine on ENV_ACROBOT, the caller's or one of the two named shapes
+        acrobot_run.check_engine(engine)
+        if engine is None and asked not in acrobot_run.MODEL_HIDDEN:
+            raise NotImplementedError("model {!r} on game {!r}: without an engine this loop runs {!r} and {!r} there".format(
+                asked, game, LINEAR_MODEL, MAZE_MODEL))
+    acro = game == ACROBOT_GAME
+    dense = engine.kind == _lib.KIND_DENSE if engine is not None else (asked == LINEAR_MODEL or acro)   # a dense stack on a step environment (csrc/dense.h)
     cart = game == CARTPOLE_GAME or (engine is not None and engine.kind == _lib.KIND_CARTPOLE)
     maze = not cart and (game == 'maze' or (engine is not None and engine.kind == _lib.KIND_MAZE))
     if dense:
-        if engine is None and not (cart or maze):
-            raise NotImplementedError("model {!r} on game {!r}: this loop runs it on 'maze' and {!r}".format(asked, game, CARTPOLE_GAME))
+        if engine is None and not (cart or maze or acro):
+            raise NotImplementedError("model {!r} on game {!r}: this loop runs it on 'maze' and {!r}, and on {!r}".format(asked, game, CARTPOLE_GAME, ACROBOT_GAME))
         if engine is not None:
             if DENSE_GAMES.get(engine.env_kind) != game:
                 raise ValueError("game {!r} asked for, the engine passed in (kind {} on environment kind {}) runs {!r}".format(
                     game, engine.kind, engine.env_kind, DENSE_GAMES.get(engine.env_kind)))
             if engine.env_kind == _lib.KIND_PENDULUM:
                 raise NotImplementedError("game {!r}: this loop runs a KIND_DENSE engine on 'maze' and {!r}".format(game, CARTPOLE_GAME))
-        if asked is not None and engine is not None and asked != dense_model_name(engine):
+        if asked is not None and engine is not None and asked != (acrobot_run.simple_name(engine, asked) or dense_model_name(engine)):
             raise ValueError("model {!r} asked for, the engine passed in (kind {}) runs {!r}".format(asked, engine.kind, dense_model_name(engine)))
     elif cart:                                                        # gym_tensorflow.make(game='gym.CartPole-v1'): GymEnv's cart-pole under SimpleClassifier
         if game != CARTPOLE_GAME:
@@ -188,11 +205,11 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
             raise NotImplementedError("model {!r} on game 'maze': this loop runs {!r} there".format(asked, MAZE_MODEL))
     elif asked == MAZE_MODEL:
         raise NotImplementedError("model {!r} on game {!r}: it runs on game 'maze' only".format(asked, exp.get('game')))
-    episodic = maze or cart                                         # a whole episode per member in one kernel: one layout, no reference batch, no frame skip
+    episodic = maze or cart or acro                                 # a whole episode per member in one kernel: one layout, no reference batch, no frame skip
     if not episodic and asked is not None and asked not in MODEL_KINDS:
         raise NotImplementedError("model {!r}: this loop runs {}".format(asked, sorted(MODEL_KINDS)))
     large = not episodic and (engine.kind if engine is not None else MODEL_KINDS[asked]) == _lib.KIND_GA_LARGE
-    model = (LINEAR_MODEL if engine is None else dense_model_name(engine)) if dense else MAZE_MODEL if episodic else 'LargeModel' if large else 'ModelVirtualBN'
+    model = (asked if engine is None else acrobot_run.simple_name(engine, asked) or dense_model_name(engine)) if dense else MAZE_MODEL if episodic else 'LargeModel' if large else 'ModelVirtualBN'
     if asked is not None and asked != model:
         raise ValueError("model {!r} asked for, the engine passed in (kind {}) runs {!r}".format(asked, engine.kind, model))
     if episodic:                                                    # one flat layout, no reference batch; the maze: the walls instead
@@ -200,11 +217,14 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
         if exp.get('flat_layout', layout) != layout:
             raise ValueError("flat_layout {!r}: {} has one layout, 'native'".format(exp['flat_layout'], model))
         if dense:
-            if engine is None:
-                engine = _lib.Engine(_lib.KIND_DENSE, 2, max_members=2 * n_pairs, env=_lib.KIND_MAZE if maze else _lib.KIND_CARTPOLE, hidden=(), nonlin='relu')
-            if maze:
-                engine.maze_set_walls(*_lib.load_maze(maze_file(exp)))
-            noise = attach_table(engine, noise)
+            if acro:
+                engine, noise = acrobot_run.open_engine(engine, noise, 2 * n_pairs, asked)
+            else:
+                if engine is None:
+                    engine = _lib.Engine(_lib.KIND_DENSE, 2, max_members=2 * n_pairs, env=_lib.KIND_MAZE if maze else _lib.KIND_CARTPOLE, hidden=(), nonlin='relu')
+                if maze:
+                    engine.maze_set_walls(*_lib.load_maze(maze_file(exp)))
+                noise = attach_table(engine, noise)
             scale_by = policies.dense_scale_by(engine.env_kind, engine.hidden, engine.n_actions)
         elif maze:
             engine, noise = open_engine(exp, engine, noise, 2 * n_pairs)
@@ -240,7 +260,7 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
             state = pickle.load(file)
         tlogger.log("Loaded iteration {} from {}".format(state.it, log_dir))
         was_game = getattr(state, 'game', None)
-        if was_game != ('maze' if maze else CARTPOLE_GAME if cart else None):
+        if was_game != ('maze' if maze else CARTPOLE_GAME if cart else ACROBOT_GAME if acro else None):
             raise ValueError("snapshot.pkl in {} holds game {!r}; this run is game {!r}".format(
                 log_dir, was_game if was_game is not None else 'an Atari game', exp.get('game')))
         was_model = getattr(state, 'model', 'ModelVirtualBN')
@@ -259,7 +279,7 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, ref_count=128
         else:
             state.theta = policies.xavier_flat(engine.n_actions, seed)   # es.py:173: state.initialize(rs, noise, worker.model)
     state.flat_layout, state.num_params, state.model = layout, engine.P, model
-    state.game = 'maze' if maze else CARTPOLE_GAME if cart else None
+    state.game = 'maze' if maze else CARTPOLE_GAME if cart else ACROBOT_GAME if acro else None
     state.push(engine)
     if not large and not episodic:                                               # ModelVirtualBN.requires_ref_batch (batchnorm.py:60-62); LargeModel has none
         env = policies.HipAtariEnv(engine, seed=seed)

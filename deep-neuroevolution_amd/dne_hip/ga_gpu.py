@@ -367,13 +367,13 @@ class _MazeBank(object):
 
 
 class _DenseBank(object):
-    """the same three calls on a KIND_DENSE engine (dense_ga_*).  On the cart-pole every eval draws its members' environment seeds from rs,
+    """the same three calls on a KIND_DENSE engine (dense_ga_*).  On the cart-pole and the acrobot every eval draws its members' environment seeds from rs,
     after whatever its caller drew; on the maze nothing is drawn"""
 
     def __init__(self, engine, rs):
         self.engine, self.max_members, self.rs = engine, engine.max_members, rs
         self.build, self.promote = engine.dense_ga_build, engine.dense_ga_promote
-        self.own = _lib.MAZE_STEPS if engine.env_kind == _lib.KIND_MAZE else _lib.CARTPOLE_STEPS
+        self.own = {_lib.KIND_MAZE: _lib.MAZE_STEPS, _lib.ENV_ACROBOT: _lib.ACROBOT_STEPS}.get(engine.env_kind, _lib.CARTPOLE_STEPS)
 
     def eval(self, parent, idx, power, tslimit):
         seeds = None
@@ -546,27 +546,31 @@ DENSE_SIMPLE_HIDDEN = (16, 16)           # SimpleClassifier as a dense shape (mo
 
 def _is_dense_run(engine, exp):
     """main's routing: a caller's KIND_DENSE engine always; without an engine LinearClassifier on the maze or the cart-pole and
-    SimpleClassifier on the cart-pole.  An engine of another kind is never a dense run (main refuses it as it always did)."""
-    from .es_gpu import CARTPOLE_GAME, LINEAR_MODEL
+    SimpleClassifier on the cart-pole, and both on the acrobot.  An engine of another kind is never a dense run (main refuses it as it always did)."""
+    from .es_gpu import ACROBOT_GAME, CARTPOLE_GAME, LINEAR_MODEL
     if engine is not None:
         return engine.kind == _lib.KIND_DENSE
     game, asked = exp.get('game'), exp.get('model')
-    return (asked == LINEAR_MODEL and game in ('maze', CARTPOLE_GAME)) or (asked == MAZE_MODEL and game == CARTPOLE_GAME)
+    return (asked == LINEAR_MODEL and game in ('maze', CARTPOLE_GAME, ACROBOT_GAME)) or (asked == MAZE_MODEL and game in (CARTPOLE_GAME, ACROBOT_GAME))
 
 
 def _open_dense_run(who, log_dir, engine, noise, exp):
     """what dense_main and dense_ns_main (`who`) do before they look for a snapshot: the routing and its refusals, the log, the engine with
     walls (on the maze), table and init scale.  Returns (engine, noise, game, model)."""
-    from .es_gpu import CARTPOLE_GAME, DENSE_GAMES, LINEAR_MODEL, dense_model_name
+    from . import acrobot_run
+    from .es_gpu import ACROBOT_GAME, CARTPOLE_GAME, DENSE_GAMES, LINEAR_MODEL, dense_model_name
     from .maze_run import attach_table, maze_file
     game, asked = exp.get('game'), exp.get('model')
     if engine is None:
         if not _is_dense_run(None, exp):
-            raise NotImplementedError("model {!r} on game {!r}: without an engine {} runs {!r} on 'maze' and {!r}, and {!r} on {!r}".format(
-                asked, game, who, LINEAR_MODEL, CARTPOLE_GAME, MAZE_MODEL, CARTPOLE_GAME))
+            raise NotImplementedError("model {!r} on game {!r}: without an engine {} runs {!r} on 'maze' and {!r}, and {!r} on {!r}; both on {!r}".format(
+                asked, game, who, LINEAR_MODEL, CARTPOLE_GAME, MAZE_MODEL, CARTPOLE_GAME, ACROBOT_GAME))
         model = asked
-        engine = _lib.Engine(_lib.KIND_DENSE, 2, max_members=exp['population_size'], env=_lib.KIND_MAZE if game == 'maze' else _lib.KIND_CARTPOLE,
-                             hidden=DENSE_SIMPLE_HIDDEN if asked == MAZE_MODEL else (), nonlin='relu')
+        if game == ACROBOT_GAME:
+            engine = acrobot_run.make_engine(exp['population_size'], asked)
+        else:
+            engine = _lib.Engine(_lib.KIND_DENSE, 2, max_members=exp['population_size'], env=_lib.KIND_MAZE if game == 'maze' else _lib.KIND_CARTPOLE,
+                                 hidden=DENSE_SIMPLE_HIDDEN if asked == MAZE_MODEL else (), nonlin='relu')
     else:
         if engine.kind != _lib.KIND_DENSE:
             raise ValueError("{} needs an engine of kind KIND_DENSE ({}), the engine passed in is of kind {}".format(who, _lib.KIND_DENSE, engine.kind))
@@ -575,7 +579,7 @@ def _open_dense_run(who, log_dir, engine, noise, exp):
                 game, engine.kind, engine.env_kind, DENSE_GAMES.get(engine.env_kind)))
         if engine.env_kind == _lib.KIND_PENDULUM:
             raise NotImplementedError("game {!r}: this loop runs a KIND_DENSE engine on 'maze' and {!r}".format(game, CARTPOLE_GAME))
-        model = dense_model_name(engine)
+        model = (acrobot_run.simple_name(engine, asked) if acrobot_run.is_engine(engine) else None) or dense_model_name(engine)
         if asked is not None and asked != model:
             raise ValueError("model {!r} asked for, the engine passed in (kind {}) runs {!r}".format(asked, engine.kind, model))
     tlogger.start(log_dir)
@@ -587,13 +591,15 @@ def _open_dense_run(who, log_dir, engine, noise, exp):
 
 
 def dense_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
-    """gpu_implementation/ga.py:114-275 over a dense policy of any small shape on the maze or the cart-pole (a DNE_KIND_DENSE engine,
+    """gpu_implementation/ga.py:114-275 over a dense policy of any small shape on the maze, the cart-pole or the acrobot (a DNE_KIND_DENSE engine,
     csrc/dense_ga.h): maze_main's loop (_bank_loop) on dense_ga_build / dense_ga_eval / dense_ga_promote.  Returns what main returns.
 
     The engine: a caller's KIND_DENSE engine of any shape, on its environment's game (es_gpu.DENSE_GAMES; another game, or a model name that
     is not es_gpu.dense_model_name(engine), is a ValueError naming both; the pendulum is not built); without one, exp['model'] ==
     'LinearClassifier' opens an engine with no hidden layer on 'maze' or 'gym.CartPole-v1', and 'SimpleClassifier' on 'gym.CartPole-v1' one of
-    hidden (16, 16), relu -- the GPU tree's gym configuration under GA.  The init scale is policies.dense_scale_by of the shape.
+    hidden (16, 16), relu -- the GPU tree's gym configuration under GA; on 'gym.Acrobot-v1' (acrobot_run; draws, limits and seeds as on the
+    cart-pole, own limit 500) both names open their shape, and a (16, 16) relu engine of the caller's is 'SimpleClassifier' when the run asks
+    for that name.  The init scale is policies.dense_scale_by of the shape.
     Lazy genomes, one build per call, promotion with the kept form and selection_threshold == 0 (roots every generation, an empty bank:
     random search) are maze_main's, word for word.  Decisions of ours:
       draws        parents and indices are maze_main's two whole-array draws.  On the maze no environment seed is drawn: the stream is
@@ -736,7 +742,7 @@ def maze_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp
 
 # ---------------------------------------------------------------------------------------------- GA-NS on a dense policy
 def dense_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
-    """GA-NS over a dense policy of any small shape on the maze or the cart-pole (a DNE_KIND_DENSE engine): maze_ns_main's loop, its decisions
+    """GA-NS over a dense policy of any small shape on the maze, the cart-pole or the acrobot (a DNE_KIND_DENSE engine): maze_ns_main's loop, its decisions
     and its tabular keys, on the dense bank (dense_ga_*) with novelty over final states (csrc/dense_novelty.h, the pool form).
     exp['novelty_search'] = {'k': 1 .. DENSE_NOVELTY_KMAX, 'archive_prob': 0 .. 1}.  Returns what main returns.  DESIGN.md section 17c.
 
@@ -745,7 +751,7 @@ def dense_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **ex
       draws        the two whole-array draws, then rs.random_sample(n) < archive_prob; on the cart-pole the generation's environment seeds
                    follow (drawn by the evaluation, as every evaluation call of dense_main draws them), and each validation and test call draws
                    its own.  On the maze nothing more is drawn: a (16, 16) relu engine on the maze consumes maze_ns_main's stream draw for draw.
-      BC           section 17b's: one episode's final state record cast to D floats (maze (x, y), cart-pole (x, x_dot, theta, theta_dot)).  On
+      BC           section 17b's: one episode's final state record cast to D floats (maze (x, y), cart-pole (x, x_dot, theta, theta_dot), acrobot (theta1, theta2, omega1, omega2)).  On
                    the cart-pole it is the ONE episode the generation ran under its drawn seed; no mean BC over several episodes.
       scoring      one dense_ga_eval, then dense_novelty_pool(k) on the BCs of that evaluation, on the device; the masked members are appended
                    afterwards by one dense_archive_append_members.

@@ -44,6 +44,9 @@ nses.py:34-39's get_mean_bc: R episodes of theta at power 0 under R fresh seeds,
 float32, appended from the host (R = 1: device to device); the logged test return is the first episode's.  snapshot.pkl records game, model,
 num_params and, on a dense run, num_rollouts (the maze path runs 1 and its snapshot keeps the attributes it had); a resume under another of
 them raises and names both sides.
+'gym.Acrobot-v1' (csrc/acrobot.h) runs here as the cart-pole does -- seeds, num_rollouts >= 1, own limit 500 -- with the BC
+(theta1, theta2, omega1, omega2) of the final state, D = 4: a caller's KIND_DENSE engine created on ENV_ACROBOT, or no engine and exp['model'] ==
+'LinearClassifier' or 'SimpleClassifier' (hidden (16, 16), relu), opened by acrobot_run.
 """
 import os
 import pickle
@@ -53,7 +56,8 @@ import numpy as np
 
 from . import _lib, nses
 from .es import pack_records, parse_cutoff
-from .es_gpu import CARTPOLE_GAME, DENSE_GAMES, LINEAR_MODEL, _env_limit, _episodes_of_theta, dense_model_name
+from . import acrobot_run
+from .es_gpu import ACROBOT_GAME, CARTPOLE_GAME, DENSE_GAMES, LINEAR_MODEL, _env_limit, _episodes_of_theta, dense_model_name
 from .ga_gpu import Schedule
 from .maze_run import MAZE_MODEL, attach_table, check_engine, maze_file, open_engine, step_limit
 
@@ -133,15 +137,18 @@ class _MazeSide(object):
 
 
 class _DenseSide(object):
-    """the same of a DNE_KIND_DENSE engine on the maze or the cart-pole: P and the scale of its shape, BCs of D floats, k_dense_novelty"""
+    """the same of a DNE_KIND_DENSE engine on the maze, the cart-pole or the acrobot: P and the scale of its shape, BCs of D floats, k_dense_novelty"""
 
     def __init__(self, exp, engine, noise, max_members):
         from . import policies
         self.game = exp.get('game')
-        if engine is None:
+        made = engine is None
+        if made and self.game == ACROBOT_GAME:
+            engine = acrobot_run.make_engine(max_members, exp.get('model'))
+        elif made:
             engine = _lib.Engine(_lib.KIND_DENSE, 2, max_members=max_members, env=_lib.KIND_MAZE if self.game == 'maze' else _lib.KIND_CARTPOLE,
                                  hidden=(), nonlin='relu')
-        self.model = dense_model_name(engine)
+        self.model = (acrobot_run.simple_name(engine, exp.get('model')) if acrobot_run.is_engine(engine) else None) or dense_model_name(engine)
         if engine.env_kind == _lib.KIND_MAZE:
             engine.maze_set_walls(*_lib.load_maze(maze_file(exp)))
         self.engine, self.noise = engine, attach_table(engine, noise)
@@ -171,11 +178,13 @@ class _DenseSide(object):
 
 
 def _is_dense_run(engine, exp):
-    """main's routing: a caller's KIND_DENSE engine; without an engine LinearClassifier on the maze or the cart-pole.  Everything else is the
+    """main's routing: a caller's KIND_DENSE engine; without an engine LinearClassifier on the maze, the cart-pole or the acrobot, and
+    SimpleClassifier on the acrobot (which has no kind of its own).  Everything else is the
     maze path's, which refuses what it always refused."""
     if engine is not None:
         return engine.kind == _lib.KIND_DENSE
-    return exp.get('model') == LINEAR_MODEL and exp.get('game') in ('maze', CARTPOLE_GAME)
+    return (exp.get('model') == LINEAR_MODEL and exp.get('game') in ('maze', CARTPOLE_GAME, ACROBOT_GAME)) or \
+        (exp.get('model') == acrobot_run.SIMPLE_MODEL and exp.get('game') == ACROBOT_GAME)
 
 
 def _check_dense(engine, exp):
@@ -188,7 +197,7 @@ def _check_dense(engine, exp):
             game, engine.kind, engine.env_kind, DENSE_GAMES.get(engine.env_kind)))
     if engine.env_kind == _lib.KIND_PENDULUM:
         raise NotImplementedError("game {!r}: this loop runs a KIND_DENSE engine on 'maze' and {!r}".format(game, CARTPOLE_GAME))
-    if asked is not None and asked != dense_model_name(engine):
+    if asked is not None and asked != ((acrobot_run.simple_name(engine, asked) if acrobot_run.is_engine(engine) else None) or dense_model_name(engine)):
         raise ValueError("model {!r} asked for, the engine passed in (kind {}) runs {!r}".format(asked, engine.kind, dense_model_name(engine)))
 
 
@@ -209,7 +218,7 @@ def main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
     ns = exp['novelty_search']
     M, k, method = int(ns['population_size']), int(ns['k']), ns['selection_method']
     R = int(ns['num_rollouts'])
-    if dense and exp.get('game') == CARTPOLE_GAME:
+    if dense and exp.get('game') in (CARTPOLE_GAME, ACROBOT_GAME):
         if R < 1:
             raise ValueError("num_rollouts {!r}: at least one episode forms a behaviour characterisation".format(ns['num_rollouts']))
     elif R != 1:

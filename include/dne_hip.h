@@ -66,13 +66,14 @@ extern "C" {
                            dne_maze_set_walls, dne_maze_final_state, dne_maze_archive_append / _clear / _size / _get, dne_maze_novelty and
                            dne_maze_novelty_last_ms.  bc, record_bc and bc_final_only are refused, and so is every other Atari, GA, maze-GA,
                            pool-novelty, cart-pole, pendulum, plan and dne_stepenv_* call (the maze one step at a time is DNE_KIND_MAZE's). */
-#define DNE_KIND_DENSE 8 /* a dense policy of any small shape on one of the three step environments (csrc/dense.h): the
+#define DNE_KIND_DENSE 8 /* a dense policy of any small shape on one of the four step environments (csrc/dense.h): the
                            model half of concurrent_worker.py:56-67 beside the dne_stepenv_* environments.  dne_config.reserved: [0] the
-                           environment (DNE_KIND_MAZE, DNE_KIND_CARTPOLE or DNE_KIND_PENDULUM: 11 / 4 / 3 inputs and the action convention),
+                           environment (DNE_KIND_MAZE, DNE_KIND_CARTPOLE, DNE_KIND_PENDULUM or DNE_ENV_ACROBOT: 11 / 4 / 3 / 6 inputs and the
+                           action convention),
                            [1] hidden layers L = 0..3 (0: models/simple.py:23-27 LinearClassifier), [2] nonlinearity (0 tanh, 1 relu),
                            [3..5] the L hidden widths, each 1..64, unused entries 0.  n_actions carries the outputs: maze 2 (the raw outputs
                            are the action), cart-pole 2 (the first maximum; a tie or a NaN gives 0), pendulum 1 (the raw output is the torque,
-                           observations are raw).  The flat vector is in creation order: per layer w [in][out] row-major, then b [out].
+                           observations are raw), acrobot 3 (the first maximum; a NaN never wins).  The flat vector is in creation order: per layer w [in][out] row-major, then b [out].
                            P = dne_dense_num_params(...); dne_num_params answers -1.  dne_set_members + dne_eval_members, or dne_es_eval, run
                            whole episodes (reset from env_seed, which the maze does not read; to the environment's own limit or tslimit) and
                            leave the step-at-a-time batch as it was; dne_dense_final_state has the final states.  dne_stepenv_* work on the
@@ -80,6 +81,11 @@ extern "C" {
                            is accepted when the environment is the maze.  The P-generic calls work as on DNE_KIND_MAZE.  bc, record_bc and
                            bc_final_only are refused, and so is every Atari, GA, maze-GA, novelty, plan, cart-pole-only, pendulum-only and
                            mjmaze call. */
+#define DNE_ENV_ACROBOT 9 /* gym.Acrobot-v1 (csrc/acrobot.h): an ENVIRONMENT id, not an engine kind -- dne_create refuses it as
+                           policy_kind.  It is valid as reserved[0] of DNE_KIND_DENSE with n_actions = 3, as the kind argument of
+                           dne_stepenv_dims (6 observations, 1 action value, 4 state doubles, int32 actions) and of the dne_stepenv_*_host,
+                           dne_dense_*_host and dne_dense_bc_host twins.  State theta1, theta2, omega1, omega2; actions 0 / 1 / 2 (torque -1 / 0 /
+                           +1); reward -1 a step and 0 on the terminal one; at most 500 steps. */
 #define DNE_OB_BYTES (84 * 84 * 4)
 #define DNE_RAM_BYTES 128
 #define DNE_BN_FLOATS 608
@@ -516,14 +522,17 @@ int dne_mjmaze_forward_host(const float *theta, const float *obs, int n, int hid
  *                      action float[2]; own limit 400
  *   DNE_KIND_CARTPOLE  S 4: x, x_dot, theta, theta_dot; 4 observations; action int32 in {0, 1}; own limit 500
  *   DNE_KIND_PENDULUM  S 2: theta, theta_dot; 3 observations (raw: normalising is the policy's business); action float[1]; own limit 200
+ *   DNE_ENV_ACROBOT    S 4: theta1, theta2, omega1, omega2; 6 observations (cos, sin of each angle, the velocities); action int32 in {0, 1, 2};
+ *                      own limit 500.  No engine kind of its own: a DNE_KIND_DENSE engine created on it steps it
  * dne_stepenv_dims: the four widths of a kind, no handle needed (-1 for every other kind; a NULL output is skipped).
  * indices [n] name the environments of a call, distinct, each in 0 .. max_members - 1; NULL means 0 .. n - 1.  Every per-call array is [n] in
  * the order of that list, and environments the list does not name keep every bit.
  * dne_stepenv_reset: the maze restarts from its header (seeds is not read and may be NULL), the other two from reset_state(seeds[i]); steps 0,
  *   done 0, limit = min(max_steps, own limit), max_steps <= 0 meaning the own limit.
- * dne_stepenv_step_f32 (maze, pendulum) / _i32 (cart-pole): one step each.  Maze: reward = -(distance to the goal) on the step that makes
+ * dne_stepenv_step_f32 (maze, pendulum) / _i32 (cart-pole, acrobot): one step each.  Maze: reward = -(distance to the goal) on the step that makes
  *   steps == 400 and 0 otherwise, done when steps == limit.  Cart-pole: reward 1 per step taken, done when a threshold is crossed (strictly)
- *   or steps == limit.  Pendulum: the step's float32 reward, done when steps == limit.  A done environment stepped again: reward 0, done 1,
+ *   or steps == limit.  Pendulum: the step's float32 reward, done when steps == limit.  Acrobot: reward -1 per step and 0 on the terminal one, done when the
+ *   free end rises above the line (strictly) or steps == limit.  A done environment stepped again: reward 0, done 1,
  *   state, steps and observation unchanged.
  * dne_stepenv_observation: what a whole-episode kernel's policy would see next.  dne_stepenv_get_state: state [n][S], steps, done (a NULL
  *   output is skipped).  dne_stepenv_set_state: the analogue of dne_env_set_ram -- states no reset gives (rounded to the maze's own types),
@@ -532,7 +541,7 @@ int dne_mjmaze_forward_host(const float *theta, const float *obs, int n, int hid
  * All calls are ordered on the engine's stream and return when their outputs are on the host.  Refused by name, the batch left as it was: a
  * handle of another kind; _i32 on the maze or the pendulum, _f32 on the cart-pole; n outside 1 .. max_members; an index out of range or named
  * twice; stepping, observing or reading an environment that was never reset; the maze before dne_maze_set_walls; a cart-pole action outside
- * {0, 1} (checked on the host before the launch); NULL seeds on the cart-pole or the pendulum.  dne_env_* keep refusing the three kinds.
+ * {0, 1} or an acrobot action outside {0, 1, 2} (checked on the host before the launch); NULL seeds on the cart-pole or the pendulum.  dne_env_* keep refusing the three kinds.
  * The CPU twins need no handle and no GPU (errors through dne_last_error(NULL)); they work on the caller's arrays of n environments (header8 /
  * lines / n_walls for the maze, else NULL / 0) and run the same header: dne_stepenv_reset_host, dne_stepenv_step_host (actions: float [n][2],
  * int32 [n] or float [n] by kind), dne_stepenv_observe_host (the observations of given states). */
@@ -549,6 +558,9 @@ int dne_stepenv_reset_host(int kind, int n, const uint32_t *seeds, const float *
 int dne_stepenv_step_host(int kind, int n, const void *actions, const float *header8, const float *lines, int n_walls, double *state,
                           int32_t *steps, const int32_t *limit, uint8_t *done, float *reward, float *obs);
 int dne_stepenv_observe_host(int kind, int n, const double *state, const float *header8, const float *lines, int n_walls, float *obs);
+/* the acrobot alone (csrc/acrobot.h): n sequences of T actions (0 / 1 / 2) from init4 [n][4] -> rows [n][T][5] = the state after the step, then
+ * terminal (1 / 0); stepping goes on past it.  No handle, no GPU. */
+int dne_acrobot_actions_host(const int32_t *actions, int n, int T, const double *init4, double *rows);
 
 /* ---- dense policies of any small shape on the step environments (DNE_KIND_DENSE; csrc/dense.h) ----
  * dne_dense_num_params: P of a shape (widths: n_hidden entries), or -1 for a shape that is not built.

@@ -2,7 +2,7 @@
 """What a dense policy of the caller's own shape costs on the device (DNE_KIND_DENSE, k_dense_run of csrc/dense.h), beside
 the kernels of the baked shape and beside the route a policy outside the kernels had before: a host `act` callback around the step-at-a-time batch.
 
-Prints ONE JSON line.  Per environment ('maze', 'cartpole') and --members members (antithetic pairs around theta_0 = noise * scale_by at sigma 0.02,
+Prints ONE JSON line.  Per environment of --games ('maze', 'cartpole' and, when asked for, 'acrobot') and --members members (antithetic pairs around theta_0 = noise * scale_by at sigma 0.02,
 every episode under its own seed, run to the environment's own limit):
 
   dense["<shape>"]     k_dense_run whole episodes for the shapes linear (LinearClassifier), 16x16 and 64x64x64 (relu):
@@ -19,9 +19,13 @@ every episode under its own seed, run to the environment's own limit):
                        tool with --route host under DNE_LIB_PATH=<that commit's library> to time it there.
   device_beats_host    wall_ms of dense["linear"] at its slowest repetition is below host_act's wall_ms at its fastest
 
+'acrobot' (gym.Acrobot-v1, csrc/acrobot.h) has no baked kernel and no engine kind of its own: its entry holds dense[...] alone (three outputs, own
+limit 500).  --shapes picks among linear, 16x16 and 64x64x64 for the games that have no baked kernel to be compared with.
+
 A machine without a GPU fails at Engine(): there is no fall-back.
 
-Usage: python tools/dense_timing.py [--members 1000] [--reps 10] [--warmup 3] [--host-reps 3] [--route all|host] [--out FILE]
+Usage: python tools/dense_timing.py [--members 1000] [--reps 10] [--warmup 3] [--host-reps 3] [--route all|host] [--games maze,cartpole]
+                                    [--shapes linear,16x16,64x64x64] [--out FILE]
 """
 import argparse
 import json
@@ -35,8 +39,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "deep-neuroevolution_amd"))
 
 SHAPES = {"linear": (), "16x16": (16, 16), "64x64x64": (64, 64, 64)}
-GAMES = {"maze": "maze", "cartpole": "gym.CartPole-v1"}
-N_IN = {"maze": 11, "cartpole": 4}
+GAMES = {"maze": "maze", "cartpole": "gym.CartPole-v1", "acrobot": "gym.Acrobot-v1"}
+N_IN = {"maze": 11, "cartpole": 4, "acrobot": 6}
 SIGMA = 0.02
 
 
@@ -85,6 +89,26 @@ def host_act_route(_lib, envs, env, noise, theta0, idx, seeds, reps):
     return {"wall_ms": stats(wall), "steps_per_episode": int(lens.max()), "env_steps": int(lens.sum())}
 
 
+def acrobot_entry(_lib, noise, pairs, shapes, reps, warmup):
+    """dense[<shape>] on gym.Acrobot-v1: the members, seeds and indices drawn as for the other games, whole episodes to the own limit of 500"""
+    from dne_hip import policies
+    rs = np.random.RandomState(0)
+    seeds = rs.randint(0, 2 ** 32, size=2 * pairs, dtype=np.uint64).astype(np.uint32)
+    idx = rs.randint(0, noise.size - 9218 + 1, size=pairs).astype(np.int64)
+    r = {"dense": {}}
+    for name in shapes:
+        eng = _lib.Engine(_lib.KIND_DENSE, _lib.ACROBOT_ACTIONS, max_members=2 * pairs, env=_lib.ENV_ACROBOT, hidden=SHAPES[name], nonlin="relu")
+        try:
+            eng.noise_upload(noise)
+            eng.set_theta(noise[4321:4321 + eng.P] * policies.dense_scale_by(_lib.ENV_ACROBOT, SHAPES[name], _lib.ACROBOT_ACTIONS))
+            r["dense"][name], out = timed_evals(eng, idx, seeds, _lib.ACROBOT_STEPS, reps, warmup)
+            r["dense"][name]["episodes_ended_early"] = int(np.sum(out[2] < _lib.ACROBOT_STEPS))
+            assert eng.check_redzones() == 0
+        finally:
+            eng.close()
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--members", type=int, default=1000)
@@ -92,15 +116,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--host-reps", type=int, default=3)
     ap.add_argument("--route", choices=("all", "host"), default="all")
+    ap.add_argument("--games", default="maze,cartpole", help="comma-separated: maze, cartpole, acrobot")
+    ap.add_argument("--shapes", default=",".join(SHAPES), help="comma-separated shapes of the acrobot's entry: " + ", ".join(SHAPES))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.reps < 3 or a.host_reps < 3:
         ap.error("at least three repetitions")
+    games, shapes = a.games.split(","), a.shapes.split(",")
+    if not games or any(g not in GAMES for g in games) or not shapes or any(s not in SHAPES for s in shapes):
+        ap.error("--games takes %s, --shapes %s" % (", ".join(GAMES), ", ".join(SHAPES)))
     from dne_hip import _lib, envs
     pairs = a.members // 2
     noise = np.random.RandomState(123).randn(2_000_000).astype(np.float32)
-    res = {"tool": "dense_timing", "members": 2 * pairs, "reps": a.reps, "warmup": a.warmup, "host_reps": a.host_reps, "route": a.route, "lib": "DNE_LIB_PATH" if os.environ.get("DNE_LIB_PATH") else "in-tree"}
-    for env in ("maze", "cartpole"):
+    res = {"tool": "dense_timing", "members": 2 * pairs, "reps": a.reps, "warmup": a.warmup, "host_reps": a.host_reps, "route": a.route, "games": games, "lib": "DNE_LIB_PATH" if os.environ.get("DNE_LIB_PATH") else "in-tree"}
+    for env in games:
+        if env == "acrobot":
+            res[env] = acrobot_entry(_lib, noise, pairs, [s for s in SHAPES if s in shapes], a.reps, a.warmup)
+            continue
         kind = _lib.KIND_MAZE if env == "maze" else _lib.KIND_CARTPOLE
         limit = _lib.MAZE_STEPS if env == "maze" else _lib.CARTPOLE_STEPS
         rs = np.random.RandomState(0)
