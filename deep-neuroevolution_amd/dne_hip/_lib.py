@@ -1273,123 +1273,120 @@ class Engine:
         self._ck(self.lib.dne_dense_bc(self.h, int(n), _ptr(out, C.c_float)))
         return out
 
-    def _dense_points(self, bc, n):
-        """(host BCs or None, count): bc=None means the first n members of the last evaluation (all of them without n), read on the device"""
-        if bc is None:
+    # ---- the device-resident archive and its novelty, once for the maze_* and dense_* methods below: `family` is the C prefix ('maze': points of
+    # width 2, csrc/maze_novelty.h; 'dense': BCs of width dense_bc_dim(), csrc/dense_novelty.h), and the entry point is dne_<family>_<name>
+    def _width(self, family):
+        return 2 if family == 'maze' else self.dense_bc_dim()
+
+    def _points(self, family, points, n):
+        """(host points or None, count): points=None means the first n members of the last evaluation (all of them without n), read on the device"""
+        if points is None:
             return None, int(self._last_eval_n if n is None else n)
-        D = self.dense_bc_dim()
-        bc = _arr(bc, np.float32).reshape(-1, D)
-        if n is not None and int(n) != bc.shape[0]:
-            raise DneError("%d points given, n = %d" % (bc.shape[0], int(n)))
-        return bc, int(bc.shape[0])
+        points = _arr(points, np.float32).reshape(-1, self._width(family))
+        if n is not None and int(n) != points.shape[0]:
+            raise DneError("%d points given, n = %d" % (points.shape[0], int(n)))
+        return points, int(points.shape[0])
+
+    def _archive_append(self, family, points, n):
+        points, n = self._points(family, points, n)
+        self._ck(getattr(self.lib, 'dne_%s_archive_append' % family)(self.h, _ptr(points, C.c_float), n))
+
+    def _archive_size(self, family):
+        n = getattr(self.lib, 'dne_%s_archive_size' % family)(self.h)
+        if n < 0:
+            self._ck(n)
+        return n
+
+    def _archive(self, family):
+        n = self._archive_size(family)
+        out = np.empty((n, self._width(family)), np.float32)
+        self._ck(getattr(self.lib, 'dne_%s_archive_get' % family)(self.h, _ptr(out, C.c_float), n))
+        return out
+
+    def _novelty(self, family, name, k, points, n):
+        """name 'novelty' or 'novelty_pool' -> float64 [n]"""
+        points, n = self._points(family, points, n)
+        out = np.empty(max(n, 0), np.float64)
+        self._ck(getattr(self.lib, 'dne_%s_%s' % (family, name))(self.h, _ptr(points, C.c_float), n, int(k), _ptr(out, C.c_double)))
+        return out
+
+    def _archive_append_members(self, family, members):
+        members = _arr(members, np.int32).reshape(-1)
+        self._ck(getattr(self.lib, 'dne_%s_archive_append_members' % family)(self.h, _ptr(members, C.c_int32), int(members.size)))
+
+    def _novelty_last_ms(self, family):
+        fn = getattr(self.lib, 'dne_%s_novelty_last_ms' % family)
+        fn.restype = C.c_double
+        return float(fn(self.h))
 
     def dense_archive_append(self, bc=None, n=None):
         """append BCs [n][D] to the device-resident archive, in order; bc=None: those of the last evaluation's first n members, device to device"""
-        bc, n = self._dense_points(bc, n)
-        self._ck(self.lib.dne_dense_archive_append(self.h, _ptr(bc, C.c_float), n))
+        self._archive_append('dense', bc, n)
 
     def dense_archive_clear(self):
         self._ck(self.lib.dne_dense_archive_clear(self.h))
 
     def dense_archive_size(self):
-        n = self.lib.dne_dense_archive_size(self.h)
-        if n < 0:
-            self._ck(n)
-        return n
+        return self._archive_size('dense')
 
     def dense_archive(self):
         """the archive's BCs in insertion order, [size][D] float32"""
-        n = self.dense_archive_size()
-        out = np.empty((n, self.dense_bc_dim()), np.float32)
-        self._ck(self.lib.dne_dense_archive_get(self.h, _ptr(out, C.c_float), n))
-        return out
+        return self._archive('dense')
 
     def dense_novelty(self, k, bc=None, n=None):
         """nses.py:22-32 on BCs of D floats: the mean distance of each to its min(k, archive size) nearest archive points, float64 [n]
         (k_dense_novelty; 1 <= k <= DENSE_NOVELTY_KMAX).  bc=None scores the last evaluation's first n members on the device."""
-        bc, n = self._dense_points(bc, n)
-        out = np.empty(max(n, 0), np.float64)
-        self._ck(self.lib.dne_dense_novelty(self.h, _ptr(bc, C.c_float), n, int(k), _ptr(out, C.c_double)))
-        return out
+        return self._novelty('dense', 'novelty', k, bc, n)
 
     def dense_novelty_pool(self, k, bc=None, n=None):
         """GA-NS's novelty on BCs of D floats: the mean distance of each to its min(k, archive size + n - 1) nearest among the archive's points
         and the OTHER n - 1 BCs, float64 [n] (k_dense_novelty_pool; 1 <= k <= DENSE_NOVELTY_KMAX).  bc=None scores the last evaluation's first
         n members on the device."""
-        bc, n = self._dense_points(bc, n)
-        out = np.empty(max(n, 0), np.float64)
-        self._ck(self.lib.dne_dense_novelty_pool(self.h, _ptr(bc, C.c_float), n, int(k), _ptr(out, C.c_double)))
-        return out
+        return self._novelty('dense', 'novelty_pool', k, bc, n)
 
     def dense_archive_append_members(self, members):
         """append the BCs of the last evaluation's members `members` (indices, in this order, repeats allowed) to the archive, device to device"""
-        members = _arr(members, np.int32).reshape(-1)
-        self._ck(self.lib.dne_dense_archive_append_members(self.h, _ptr(members, C.c_int32), int(members.size)))
+        self._archive_append_members('dense', members)
 
     def dense_novelty_last_ms(self):
         """the scoring kernel of the last dense_novelty / dense_novelty_pool call between two device events, milliseconds (-1 before the first)"""
-        self.lib.dne_dense_novelty_last_ms.restype = C.c_double
-        return float(self.lib.dne_dense_novelty_last_ms(self.h))
+        return self._novelty_last_ms('dense')
 
     # ---- novelty on the hard maze (csrc/maze_novelty.h): BCs are final (x, y) points, the archive lives on the device
-    def _maze_points(self, xy, n):
-        """(host points or None, count): xy=None means the first n members of the last evaluation (all of them without n), read on the device"""
-        if xy is None:
-            return None, int(self._last_eval_n if n is None else n)
-        xy = _arr(xy, np.float32).reshape(-1, 2)
-        if n is not None and int(n) != xy.shape[0]:
-            raise DneError("%d points given, n = %d" % (xy.shape[0], int(n)))
-        return xy, int(xy.shape[0])
-
     def maze_archive_append(self, xy=None, n=None):
         """append points [n][2] to the device-resident archive, in order; xy=None: the final positions of the last evaluation's first n
         members, device to device"""
-        xy, n = self._maze_points(xy, n)
-        self._ck(self.lib.dne_maze_archive_append(self.h, _ptr(xy, C.c_float), n))
+        self._archive_append('maze', xy, n)
 
     def maze_archive_clear(self):
         self._ck(self.lib.dne_maze_archive_clear(self.h))
 
     def maze_archive_size(self):
-        n = self.lib.dne_maze_archive_size(self.h)
-        if n < 0:
-            self._ck(n)
-        return n
+        return self._archive_size('maze')
 
     def maze_archive(self):
         """the archive's points in insertion order, [size][2] float32"""
-        n = self.maze_archive_size()
-        out = np.empty((n, 2), np.float32)
-        self._ck(self.lib.dne_maze_archive_get(self.h, _ptr(out, C.c_float), n))
-        return out
+        return self._archive('maze')
 
     def maze_novelty(self, k, xy=None, n=None):
         """nses.py:22-32 on (x, y) points: the mean distance of each point to its min(k, archive size) nearest archive points, float64 [n]
         (k_maze_novelty; 1 <= k <= MAZE_NOVELTY_KMAX).  xy=None scores the last evaluation's first n members where the rollout left them."""
-        xy, n = self._maze_points(xy, n)
-        out = np.empty(max(n, 0), np.float64)
-        self._ck(self.lib.dne_maze_novelty(self.h, _ptr(xy, C.c_float), n, int(k), _ptr(out, C.c_double)))
-        return out
+        return self._novelty('maze', 'novelty', k, xy, n)
 
     def maze_novelty_pool(self, k, xy=None, n=None):
         """GA-NS's novelty: the mean distance of each point to its min(k, archive size + n - 1) nearest among the archive's points and the
         OTHER n - 1 points, float64 [n] (k_maze_novelty_pool; 1 <= k <= MAZE_NOVELTY_KMAX).  xy=None scores the last evaluation's first n
         members where the rollout left them."""
-        xy, n = self._maze_points(xy, n)
-        out = np.empty(max(n, 0), np.float64)
-        self._ck(self.lib.dne_maze_novelty_pool(self.h, _ptr(xy, C.c_float), n, int(k), _ptr(out, C.c_double)))
-        return out
+        return self._novelty('maze', 'novelty_pool', k, xy, n)
 
     def maze_archive_append_members(self, members):
         """append the final positions of the last evaluation's members `members` (indices, in this order, repeats allowed) to the archive,
         device to device"""
-        members = _arr(members, np.int32).reshape(-1)
-        self._ck(self.lib.dne_maze_archive_append_members(self.h, _ptr(members, C.c_int32), int(members.size)))
+        self._archive_append_members('maze', members)
 
     def maze_novelty_last_ms(self):
         """the scoring kernel of the last maze_novelty / maze_novelty_pool call between two device events, milliseconds"""
-        self.lib.dne_maze_novelty_last_ms.restype = C.c_double
-        return float(self.lib.dne_maze_novelty_last_ms(self.h))
+        return self._novelty_last_ms('maze')
 
     # ---- Deep-GA on the hard maze (csrc/maze_ga.h): the parents live in a bank on the device, a member is (parent, idx, power)
     def maze_ga_set_init_scale(self, scale_by):

@@ -23,12 +23,13 @@ for both -- on dense_ga_build / dense_ga_eval / dense_ga_promote; selection_thre
 models or games is refused as before.
 GA-NS on a dense policy is dense_ns_main, called directly (main and dense_main refuse exp['novelty_search'] on a dense run): maze_ns_main's loop on the
 dense bank, novelty over final states scored on the device (k_dense_novelty_pool).
-GA-NS on an Atari game is atari_ns_main, called directly as well (main keeps refusing exp['novelty_search'] there): main's Atari loop with
-maze_ns_main's decisions, novelty over final RAM states scored on the device (k_ram_novelty_pool).
-The loops share what is the same in them as plain functions (_validate_and_test, _record_rows, _end_generation; the bank loops also
-_resume_maze, _draw_generation, _member, _promote, _bank_evaluate; maze_main and dense_main the whole _bank_loop; dense_main and dense_ns_main
-the engine's opening, _open_dense_run); the maze's engine, walls and
-noise table come from maze_run.open_engine.
+GA-NS on an Atari game is atari_ns_main, called directly as well (main keeps refusing exp['novelty_search'] there): main's Atari evaluation under
+the same loop, novelty over final RAM states scored on the device (k_ram_novelty_pool).
+There are three generation loops: main's Atari loop, _bank_loop (maze_main and dense_main, over a _MazeBank or a _DenseBank) and _ns_loop (maze_ns_main,
+dense_ns_main and atari_ns_main, over a _BankNs around one of the two banks or an _AtariNs; its docstring holds GA-NS's decisions).  They share what is
+the same in them as plain functions: all three _validate_and_test, _record_rows and _end_generation; _bank_loop and _ns_loop also _resume and
+_draw_generation, and _member, _promote and _bank_evaluate where there is a bank; the GA-NS drivers _check_ns; dense_main and dense_ns_main the
+engine's opening, _open_dense_run, maze_main and maze_ns_main _open_maze_run.  The maze's engine, walls and noise table come from maze_run.open_engine.
 """
 import math
 import numbers
@@ -355,7 +356,8 @@ KEPT = -1          # a descriptor's noise index that means "the parent itself" (
 
 class _MazeBank(object):
     """the device bank of a KIND_MAZE engine as the loops below call it: build(genomes), promote(parent, idx, power) and
-    eval(parent, idx, power, tslimit) -> (returns, lengths), tslimit None meaning the environment's own limit"""
+    eval(parent, idx, power, tslimit) -> (returns, lengths), tslimit None meaning the environment's own limit.  For GA-NS, archive() names
+    the engine's archive calls as _BankNs takes them: clear, append, novelty_pool, append_members, the whole read-back, and the empty archive"""
 
     def __init__(self, engine):
         self.engine, self.max_members = engine, engine.max_members
@@ -364,6 +366,11 @@ class _MazeBank(object):
     def eval(self, parent, idx, power, tslimit):
         ret, _, ln = self.engine.maze_ga_eval(parent, idx, power, step_limit(tslimit))
         return ret, ln
+
+    def archive(self):
+        e = self.engine
+        return (e.maze_archive_clear, e.maze_archive_append, e.maze_novelty_pool, e.maze_archive_append_members, e.maze_archive,
+                np.zeros((0, 2), np.float32))
 
 
 class _DenseBank(object):
@@ -381,6 +388,11 @@ class _DenseBank(object):
             seeds = self.rs.randint(0, 2 ** 32, size=len(parent), dtype=np.uint64).astype(np.uint32)
         ret, _, ln = self.engine.dense_ga_eval(parent, idx, power, self.own if tslimit is None else min(int(tslimit), self.own), seeds)
         return ret, ln
+
+    def archive(self):
+        e = self.engine
+        return (e.dense_archive_clear, e.dense_archive_append, e.dense_novelty_pool, e.dense_archive_append_members, e.dense_archive,
+                np.zeros((0, e.dense_bc_dim()), np.float32))
 
 
 def _bank_evaluate(bank, members, tslimit):
@@ -401,8 +413,8 @@ def _open_maze_run(log_dir, engine, noise, seed, exp):
     return engine, noise, np.random.RandomState(seed)
 
 
-def _resume_maze(log_dir, algo, rs, game='maze', model=MAZE_MODEL, P=None):
-    """ga.py:135-143 for a bank GA run of `algo` (the maze loops; dense_main with its game, model and P): the state in log_dir's snapshot.pkl
+def _resume(log_dir, algo, rs, game='maze', model=MAZE_MODEL, P=None):
+    """ga.py:135-143 for a run of `algo` in _bank_loop or _ns_loop (the maze drivers; the others with their game, model and P): the state in log_dir's snapshot.pkl
     with the position of its stream restored into rs, or None if there is no such file.  A snapshot of another driver, game, model or P is
     refused, naming both."""
     try:
@@ -526,12 +538,12 @@ def maze_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
     a snapshot of es_gpu.main / nses_gpu.main, raises and names both.  A previous elite is evaluated again as (its bank index, idx 0,
     power 0): the child formula, bank + fl(0 * noise).  The elite's test episodes are num_test_episodes identical deterministic episodes
     at the 400-step default, as the reference runs them.  num_frames counts steps (the maze has no frame skip).
-    maze_ns_main below is the same scaffold (the _helpers above) around another selection."""
+    maze_ns_main below (_ns_loop) is the same scaffold (the _helpers above) around another selection."""
     if NS_KEY in exp:
         return maze_ns_main(log_dir, engine=engine, noise=noise, seed=seed, max_iters=max_iters, **exp)
     engine, noise, rs = _open_maze_run(log_dir, engine, noise, seed, exp)
     all_tstart = time.time()
-    state = _resume_maze(log_dir, ALGO, rs)
+    state = _resume(log_dir, ALGO, rs)
     if state is None:
         state = TrainingState(exp)
     state.game, state.model, state.algo = 'maze', MAZE_MODEL, ALGO
@@ -620,7 +632,7 @@ def dense_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
     engine, noise, game, model = _open_dense_run('dense_main', log_dir, engine, noise, exp)
     rs = np.random.RandomState(seed)
     all_tstart = time.time()
-    state = _resume_maze(log_dir, ALGO, rs, game, model, engine.P)
+    state = _resume(log_dir, ALGO, rs, game, model, engine.P)
     if state is None:
         state = TrainingState(exp)
     state.game, state.model, state.algo, state.num_params = game, model, ALGO, engine.P
@@ -629,63 +641,141 @@ def dense_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
     return _bank_loop(log_dir, exp, state, _DenseBank(engine, rs), engine, rs, len(noise.noise) - engine.P + 1, max_iters, all_tstart)
 
 
-# ---------------------------------------------------------------------------------------------- GA-NS on the hard maze
-def maze_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
-    """GA-NS (the Deep-GA paper's novelty-search GA, Lehman and Stanley's novelty) on game 'maze' under 'SimpleClassifier': maze_main's loop with
-    novelty as the fitness.  exp['novelty_search'] = {'k': 1 .. MAZE_NOVELTY_KMAX, 'archive_prob': 0 .. 1}.  Returns what maze_main returns.
+# ---------------------------------------------------------------------------------------------- GA-NS: one loop, one side object per family
+def _check_ns(exp, kmax_name):
+    """(k, archive_prob) of exp['novelty_search'], k within 1 .. _lib.<kmax_name> (the family's limit: the message names it)"""
+    ns = exp[NS_KEY]
+    k, prob, kmax = int(ns['k']), float(ns['archive_prob']), getattr(_lib, kmax_name)
+    if not 1 <= k <= kmax:
+        raise ValueError("novelty_search k = {}: expected 1 .. {} = {}".format(k, kmax_name, kmax))
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError("novelty_search archive_prob = {!r}: expected a probability".format(ns['archive_prob']))
+    return k, prob
 
-    The reference has no GA-NS code (gpu_implementation/README.md leaves it for later), so every decision here is ours:
-      draws        maze_main's two whole-array draws first, then rs.random_sample(n) < archive_prob: this generation's archive mask.
-      scoring      one maze_ga_eval, then maze_novelty_pool(k) where k_maze_rollout left the final positions: each member against the
-                   archive and the other members of its generation (csrc/maze_novelty.h, the pool form).  The n doubles are all that comes back.
-      non-finite   a novelty that is not finite counts as 0.0 (nses_gpu's rule): the lowest there is, so a NaN policy is never selected
-                   ahead of a finite one.
+
+class _BankNs(object):
+    """what _ns_loop asks of a family, for the two whose parents live in a device bank (a _MazeBank or a _DenseBank, which also names its engine's
+    archive calls): a member is a descriptor over the bank, its genome is written out only for an Offspring, and the whole archive is read back"""
+    frames, goal_row = 1, True                                      # num_frames counts steps; BestDistanceToGoal is written (on every game)
+
+    def __init__(self, bank):
+        self.bank, self.build = bank, bank.build
+        self.clear, self.append, self.novelty_pool, self._append_members, self._read, self.empty = bank.archive()
+        self.descriptor = {}                                        # id(Offspring) -> its descriptor over the bank as it is now
+
+    def generation(self, of, idx, power, parents, tslimit):
+        self.descriptor.clear()
+        self.drawn = (of, idx, power, parents)
+        return self.bank.eval(of, idx, np.full(len(of), power, np.float32), tslimit)
+
+    def append_members(self, members, archive):
+        if members.size:
+            self._append_members(members)
+        return self._read()
+
+    def offspring(self, i, ret, length):
+        d, genome = _member(i, *self.drawn)
+        o = Offspring(genome, [ret], [length])
+        self.descriptor[id(o)] = d
+        return o
+
+    def evaluate(self, individuals, tslimit):
+        return _bank_evaluate(self.bank, [self.descriptor[id(o)] for o in individuals], tslimit)
+
+    def next_parents(self, selected, had_parents):
+        """the top T by novelty on the device: every one a root (generation 0, built once) or a child of the bank as it is"""
+        if selected and not had_parents:
+            self.build([o.seeds for o in selected])
+        elif selected:
+            _promote(self.bank.promote, [self.descriptor[id(o)] for o in selected])
+
+
+class _AtariNs(object):
+    """the same of an Atari engine created with record_bc: a member is its written-out genome (ga_eval_powers takes genomes, the store keeps the
+    parents' vectors cached, so there is no bank to build or promote), and only the appended points are read back"""
+    frames, goal_row = 4, False                                     # num_frames counts 4 frames a step; no BestDistanceToGoal
+
+    def __init__(self, engine, rs):
+        self.engine, self.rs = engine, rs
+        self.clear, self.append, self.novelty_pool = engine.archive_clear, engine.archive_append_points, engine.ram_novelty_pool
+        self.empty = np.zeros((0, _lib.RAM_BYTES), np.uint8)
+
+    def build(self, parents):
+        pass
+
+    def generation(self, of, idx, power, parents, tslimit):
+        self.tasks = [_member(i, of, idx, power, parents)[1] for i in range(len(of))]
+        return _evaluate(self.engine, self.tasks, tslimit, self.rs)     # one call: n <= max_members
+
+    def append_members(self, members, archive):
+        if not members.size:
+            return archive
+        self.engine.archive_append_members(members)
+        return np.concatenate([archive, self.engine.archive_get_points(len(archive), members.size)])
+
+    def offspring(self, i, ret, length):
+        return Offspring(self.tasks[i], [ret], [length])
+
+    def evaluate(self, individuals, tslimit):
+        return _evaluate(self.engine, [o.seeds for o in individuals], tslimit, self.rs)
+
+    def next_parents(self, selected, had_parents):
+        pass
+
+
+def _ns_loop(log_dir, exp, k, prob, side, engine, rs, game, model, P, indices, max_iters):
+    """GA-NS (the Deep-GA paper's novelty-search GA, Lehman and Stanley's novelty) behind maze_ns_main, dense_ns_main and atari_ns_main: the resume,
+    the generations and the Novelty* rows, once.  side is a _BankNs or an _AtariNs, (k, prob) what _check_ns returned, (game, model, P) what the
+    snapshot is held to (P None on the maze: its state carries no num_params), indices the number of admissible noise indices.  Returns what
+    main returns.
+
+    The reference has no GA-NS code (gpu_implementation/README.md leaves it for later), so every decision here is ours; the three drivers'
+    docstrings say what each family adds:
+      draws        maze_main's two whole-array draws first, then rs.random_sample(n) < archive_prob: this generation's archive mask; then
+                   whatever the family's evaluation calls draw.
+      scoring      ONE evaluation of the generation, then the family's pool novelty (k) where the evaluation left the behaviour
+                   characterisations: each member against the archive and the other members of its generation.  The n doubles are all that
+                   comes back.
+      non-finite   a novelty that is not finite counts as 0.0 (nses_gpu's rule, nses_gpu.sanitized): the lowest there is, so a NaN policy is
+                   never selected ahead of a finite one.
       order        descending novelty, then arrival index, by a stable host sort of the doubles (ga_select is float32 and would make
                    ties the doubles do not have).
       parents      the top T by novelty.  No reward elite enters the bank: every parent of the next generation is a child descriptor of
-                   this one (maze_ga_promote never takes the kept form); generation 0's roots are built once by maze_ga_build.
-      archive      after scoring, the masked members are appended in arrival order by one maze_archive_append_members, device to device:
+                   this one (the promote call never takes the kept form); generation 0's roots are built once.
+      archive      after scoring, the masked members are appended in arrival order by one append_members call, device to device:
                    a generation is never scored against its own entries.
       reporting    the validation set is this generation's top V by reward (ga_select), without the [elite] + carry; elite, test episodes
                    and curr_solution_* follow ga.py's rules on that set.  The reward is never used for selection.
       genomes      Offspring objects exist for the union of the top T by novelty and the top V by reward: state.population holds the
                    former in novelty order, then the rest of the latter in reward order.
-      snapshot     algo = 'ga_ns', the archive, k, archive_prob and the stream; a resume pushes the archive back and continues bit for
-                   bit.  A resume from a 'ga', es_gpu or nses_gpu snapshot, or under another k or archive_prob, raises and names both.
+      snapshot     algo = 'ga_ns', game, model, the archive, k, archive_prob and the stream; a resume pushes the archive back and continues
+                   bit for bit.  A resume from a 'ga', es_gpu or nses_gpu snapshot, or under another game, model, P, k or archive_prob,
+                   raises and names both.
       T == 0       allowed: random search, with an archive that still fills.
-    Tabular keys: maze_main's, plus NoveltyMean, NoveltyMax (after the non-finite rule), ArchiveSize, BestDistanceToGoal = -max reward."""
-    ns = exp[NS_KEY]
-    k, prob = int(ns['k']), float(ns['archive_prob'])
-    if not 1 <= k <= _lib.MAZE_NOVELTY_KMAX:
-        raise ValueError("novelty_search k = {}: expected 1 .. MAZE_NOVELTY_KMAX = {}".format(k, _lib.MAZE_NOVELTY_KMAX))
-    if not 0.0 <= prob <= 1.0:
-        raise ValueError("novelty_search archive_prob = {!r}: expected a probability".format(ns['archive_prob']))
+    Tabular keys: maze_main's, plus NoveltyMean, NoveltyMax (after the non-finite rule), ArchiveSize and, for the bank families,
+    BestDistanceToGoal = -max reward."""
+    from .nses_gpu import sanitized                                 # nses_gpu imports this module's Schedule
     n, T, V = exp['population_size'], exp['selection_threshold'], exp['validation_threshold']
-    engine, noise, rs = _open_maze_run(log_dir, engine, noise, seed, exp)
     all_tstart = time.time()
-    engine.maze_archive_clear()
-    state = _resume_maze(log_dir, ALGO_NS, rs)
+    side.clear()
+    state = _resume(log_dir, ALGO_NS, rs, game or 'an Atari game', model, P)
     if state is None:
         state = TrainingState(exp)
-        state.archive, state.stream = np.zeros((0, 2), np.float32), None
+        state.archive, state.stream = side.empty, None
     else:
         if (state.k, state.archive_prob) != (k, prob):
             raise ValueError("snapshot.pkl in {} holds k {}, archive_prob {!r}; this run is k {}, archive_prob {!r}".format(
                 log_dir, state.k, state.archive_prob, k, prob))
         if len(state.archive):
-            engine.maze_archive_append(state.archive)
-    state.game, state.model, state.algo, state.k, state.archive_prob = 'maze', MAZE_MODEL, ALGO_NS, k, prob
+            side.append(state.archive)
+    state.game, state.model, state.algo, state.k, state.archive_prob = game, model, ALGO_NS, k, prob
+    if P is not None:
+        state.num_params = P
     if 'load_population' in exp:
         state.copy_population(exp['load_population'])
-    parents = [o.seeds for o in state.population[:T]]               # the genomes of the bank's parents: the top T by novelty, no elite carried
+    parents = [o.seeds for o in state.population[:T]]               # the genomes of the parents: the top T by novelty, no elite carried
     if parents:
-        engine.maze_ga_build(parents)
-    descriptor = {}                                                 # id(Offspring) -> its descriptor over the bank as it is now
-    bank = _MazeBank(engine)
-
-    def evaluate(individuals, tslimit):
-        return _bank_evaluate(bank, [descriptor[id(o)] for o in individuals], tslimit)
-
+        side.build(parents)
     iters = 0
     while max_iters is None or iters < max_iters:
         iters += 1
@@ -694,44 +784,35 @@ def maze_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp
             break
         assert (len(parents) == 0 and (state.it == 0 or T == 0)) or len(parents) == T
         power = state.sample(state.mutation_power)
-        of, idx = _draw_generation(rs, n, len(parents), len(noise.noise) - engine.P + 1)
+        of, idx = _draw_generation(rs, n, len(parents), indices)
         archived = np.flatnonzero(rs.random_sample(n) < prob).astype(np.int32)
-        rets, _, lens = engine.maze_ga_eval(of, idx, np.full(n, power, np.float32), step_limit(state.tslimit))
-        raw = np.asarray(engine.maze_novelty_pool(k), np.float64)   # against the archive as it was before this generation, and the generation
-        novelty = np.where(np.isfinite(raw), raw, 0.0)
-        if archived.size:
-            engine.maze_archive_append_members(archived)
-        state.num_frames += int(lens.sum())
+        rets, lens = side.generation(of, idx, power, parents, state.tslimit)
+        novelty = sanitized(side.novelty_pool(k))                   # against the archive as it was before this generation, and the generation
+        state.archive = side.append_members(archived, state.archive)   # ahead of the validation episodes: on Atari they overwrite the recorded states
+        state.num_frames += int(lens.sum()) * side.frames
         state.it += 1
         rewards = np.asarray(rets, np.float64)
         by_novelty = np.argsort(-novelty, kind='stable')            # (-novelty, arrival index)
         by_reward = engine.ga_select(np.asarray(rets, np.float32), n)
         offspring = {}                                              # member index -> its Offspring
-        descriptor.clear()
         for i in list(by_novelty[:T]) + list(by_reward[:V]):
             i = int(i)
             if i not in offspring:
-                d, genome = _member(i, of, idx, power, parents)
-                offspring[i] = Offspring(genome, [float(rets[i])], [int(lens[i])])
+                offspring[i] = side.offspring(i, float(rets[i]), int(lens[i]))
                 offspring[i].novelty = float(novelty[i])
-                descriptor[id(offspring[i])] = d
         selected = [offspring[int(i)] for i in by_novelty[:T]]
         validation_population = [offspring[int(i)] for i in by_reward[:V]]
         state.population = selected + [o for o in validation_population if not any(o is s for s in selected)]
-        v = _validate_and_test(state, exp, validation_population, evaluate, int(lens.sum()))
-        # the next parents on the device: the top T by novelty, every one a root (generation 0) or a child of the bank as it is
-        new_parents = [o.seeds for o in selected]
-        if new_parents and not parents:
-            engine.maze_ga_build(new_parents)
-        elif new_parents:
-            _promote(engine.maze_ga_promote, [descriptor[id(o)] for o in selected])
-        parents = new_parents
-        state.archive = engine.maze_archive()
+        v = _validate_and_test(state, exp, validation_population, side.evaluate, int(lens.sum()))
+        side.next_parents(selected, bool(parents))
+        parents = [o.seeds for o in selected]
         dt = time.time() - tstart_iteration
         state.time_elapsed += dt
         _record_rows(state, power, rewards, T, v, dt, all_tstart)
-        for key, val in (('NoveltyMean', float(np.mean(novelty))), ('NoveltyMax', float(np.max(novelty))),
-                         ('ArchiveSize', int(state.archive.shape[0])), ('BestDistanceToGoal', -float(np.max(rewards)))):
+        rows = [('NoveltyMean', float(np.mean(novelty))), ('NoveltyMax', float(np.max(novelty))), ('ArchiveSize', int(state.archive.shape[0]))]
+        if side.goal_row:
+            rows.append(('BestDistanceToGoal', -float(np.max(rewards))))
+        for key, val in rows:
             tlogger.record_tabular(key, val)
         tlogger.dump_tabular()
         _end_generation(state, log_dir, lens, rs)
@@ -740,9 +821,24 @@ def maze_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp
     return float(state.curr_solution_test), {'val': float(state.curr_solution_val)}, state
 
 
-# ---------------------------------------------------------------------------------------------- GA-NS on a dense policy
+def maze_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
+    """GA-NS on game 'maze' under 'SimpleClassifier': maze_main's loop with novelty as the fitness (_ns_loop, whose docstring holds the decisions).
+    exp['novelty_search'] = {'k': 1 .. MAZE_NOVELTY_KMAX, 'archive_prob': 0 .. 1}.  Returns what maze_main returns.
+
+    On the maze:
+      draws        nothing beyond the loop's three: the episode is deterministic, no environment seed is drawn.
+      scoring      one maze_ga_eval, then maze_novelty_pool(k) where k_maze_rollout left the final positions (csrc/maze_novelty.h, the pool
+                   form); the masked members are appended by one maze_archive_append_members.
+      parents      maze_ga_build for generation 0's roots, one maze_ga_promote of child descriptors after that.
+      snapshot     game 'maze', model 'SimpleClassifier', no num_params; the archive is float32 [A][2], read back whole.
+    num_frames counts steps, as in maze_main."""
+    k, prob = _check_ns(exp, 'MAZE_NOVELTY_KMAX')
+    engine, noise, rs = _open_maze_run(log_dir, engine, noise, seed, exp)
+    return _ns_loop(log_dir, exp, k, prob, _BankNs(_MazeBank(engine)), engine, rs, 'maze', MAZE_MODEL, None, len(noise.noise) - engine.P + 1, max_iters)
+
+
 def dense_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
-    """GA-NS over a dense policy of any small shape on the maze, the cart-pole or the acrobot (a DNE_KIND_DENSE engine): maze_ns_main's loop, its decisions
+    """GA-NS over a dense policy of any small shape on the maze, the cart-pole or the acrobot (a DNE_KIND_DENSE engine): _ns_loop, its decisions
     and its tabular keys, on the dense bank (dense_ga_*) with novelty over final states (csrc/dense_novelty.h, the pool form).
     exp['novelty_search'] = {'k': 1 .. DENSE_NOVELTY_KMAX, 'archive_prob': 0 .. 1}.  Returns what main returns.  DESIGN.md section 17c.
 
@@ -757,100 +853,16 @@ def dense_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **ex
                    afterwards by one dense_archive_append_members.
       limits       dense_main's: a generation and the validation episodes under state.tslimit, at most the environment's own limit; the test
                    episodes at the environment's own limit.  num_frames counts steps.
-      snapshot     algo = 'ga_ns', game, model, num_params = P, k, archive_prob, the archive [A][D] and the stream; a resume pushes the archive
-                   back with dense_archive_append and continues bit for bit.  A resume under another algo, game, model, P, k or archive_prob
-                   raises and names both sides."""
-    ns = exp[NS_KEY]
-    k, prob = int(ns['k']), float(ns['archive_prob'])
-    if not 1 <= k <= _lib.DENSE_NOVELTY_KMAX:
-        raise ValueError("novelty_search k = {}: expected 1 .. DENSE_NOVELTY_KMAX = {}".format(k, _lib.DENSE_NOVELTY_KMAX))
-    if not 0.0 <= prob <= 1.0:
-        raise ValueError("novelty_search archive_prob = {!r}: expected a probability".format(ns['archive_prob']))
-    n, T, V = exp['population_size'], exp['selection_threshold'], exp['validation_threshold']
+      snapshot     num_params = P as well, the archive [A][D]; a resume pushes it back with dense_archive_append."""
+    k, prob = _check_ns(exp, 'DENSE_NOVELTY_KMAX')
     engine, noise, game, model = _open_dense_run('dense_ns_main', log_dir, engine, noise, exp)
     rs = np.random.RandomState(seed)
-    all_tstart = time.time()
-    engine.dense_archive_clear()
-    state = _resume_maze(log_dir, ALGO_NS, rs, game, model, engine.P)
-    if state is None:
-        state = TrainingState(exp)
-        state.archive, state.stream = np.zeros((0, engine.dense_bc_dim()), np.float32), None
-    else:
-        if (state.k, state.archive_prob) != (k, prob):
-            raise ValueError("snapshot.pkl in {} holds k {}, archive_prob {!r}; this run is k {}, archive_prob {!r}".format(
-                log_dir, state.k, state.archive_prob, k, prob))
-        if len(state.archive):
-            engine.dense_archive_append(state.archive)
-    state.game, state.model, state.algo, state.num_params, state.k, state.archive_prob = game, model, ALGO_NS, engine.P, k, prob
-    if 'load_population' in exp:
-        state.copy_population(exp['load_population'])
-    parents = [o.seeds for o in state.population[:T]]               # the genomes of the bank's parents: the top T by novelty, no elite carried
-    bank = _DenseBank(engine, rs)
-    if parents:
-        bank.build(parents)
-    descriptor = {}                                                 # id(Offspring) -> its descriptor over the bank as it is now
-
-    def evaluate(individuals, tslimit):
-        return _bank_evaluate(bank, [descriptor[id(o)] for o in individuals], tslimit)
-
-    iters = 0
-    while max_iters is None or iters < max_iters:
-        iters += 1
-        tstart_iteration = time.time()
-        if state.timesteps_so_far >= exp['timesteps']:
-            break
-        assert (len(parents) == 0 and (state.it == 0 or T == 0)) or len(parents) == T
-        power = state.sample(state.mutation_power)
-        of, idx = _draw_generation(rs, n, len(parents), len(noise.noise) - engine.P + 1)
-        archived = np.flatnonzero(rs.random_sample(n) < prob).astype(np.int32)
-        rets, lens = bank.eval(of, idx, np.full(n, power, np.float32), state.tslimit)
-        raw = np.asarray(engine.dense_novelty_pool(k), np.float64)  # against the archive as it was before this generation, and the generation
-        novelty = np.where(np.isfinite(raw), raw, 0.0)
-        if archived.size:
-            engine.dense_archive_append_members(archived)
-        state.num_frames += int(lens.sum())
-        state.it += 1
-        rewards = np.asarray(rets, np.float64)
-        by_novelty = np.argsort(-novelty, kind='stable')            # (-novelty, arrival index)
-        by_reward = engine.ga_select(np.asarray(rets, np.float32), n)
-        offspring = {}                                              # member index -> its Offspring
-        descriptor.clear()
-        for i in list(by_novelty[:T]) + list(by_reward[:V]):
-            i = int(i)
-            if i not in offspring:
-                d, genome = _member(i, of, idx, power, parents)
-                offspring[i] = Offspring(genome, [float(rets[i])], [int(lens[i])])
-                offspring[i].novelty = float(novelty[i])
-                descriptor[id(offspring[i])] = d
-        selected = [offspring[int(i)] for i in by_novelty[:T]]
-        validation_population = [offspring[int(i)] for i in by_reward[:V]]
-        state.population = selected + [o for o in validation_population if not any(o is s for s in selected)]
-        v = _validate_and_test(state, exp, validation_population, evaluate, int(lens.sum()))
-        # the next parents on the device: the top T by novelty, every one a root (generation 0) or a child of the bank as it is
-        new_parents = [o.seeds for o in selected]
-        if new_parents and not parents:
-            bank.build(new_parents)
-        elif new_parents:
-            _promote(bank.promote, [descriptor[id(o)] for o in selected])
-        parents = new_parents
-        state.archive = engine.dense_archive()
-        dt = time.time() - tstart_iteration
-        state.time_elapsed += dt
-        _record_rows(state, power, rewards, T, v, dt, all_tstart)
-        for key, val in (('NoveltyMean', float(np.mean(novelty))), ('NoveltyMax', float(np.max(novelty))),
-                         ('ArchiveSize', int(state.archive.shape[0])), ('BestDistanceToGoal', -float(np.max(rewards)))):
-            tlogger.record_tabular(key, val)
-        tlogger.dump_tabular()
-        _end_generation(state, log_dir, lens, rs)
-        if state.timesteps_so_far >= exp['timesteps']:
-            break
-    return float(state.curr_solution_test), {'val': float(state.curr_solution_val)}, state
+    return _ns_loop(log_dir, exp, k, prob, _BankNs(_DenseBank(engine, rs)), engine, rs, game, model, engine.P, len(noise.noise) - engine.P + 1, max_iters)
 
 
-# ---------------------------------------------------------------------------------------------- GA-NS on an Atari game
 def atari_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **exp):
-    """GA-NS on an Atari game under `Model` / `LargeModel`: main's Atari loop (the genome store behind ga_eval_powers, HipModel) with
-    maze_ns_main's decisions and tabular keys (without BestDistanceToGoal), novelty over the members' final 128-byte RAM states
+    """GA-NS on an Atari game under `Model` / `LargeModel`: main's Atari evaluation (the genome store behind ga_eval_powers, HipModel) in
+    _ns_loop, with its decisions and tabular keys (without BestDistanceToGoal), novelty over the members' final 128-byte RAM states
     (GAAtariPolicy.rollout's behaviour characterisation, policies.py:510) scored on the device (csrc/ram_novelty.h).
     exp['novelty_search'] = {'k': 1 .. RAM_NOVELTY_KMAX, 'archive_prob': 0 .. 1}.  Returns what main returns.
 
@@ -866,18 +878,11 @@ def atari_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **ex
                    are appended afterwards by one archive_append_members, before the validation episodes overwrite the recorded states.
       limits       main's: a generation and the validation episodes under state.tslimit, the test episodes under the environment's own
                    limit.  num_frames counts 4 frames a step.
-      snapshot     algo = 'ga_ns', game, model, num_params = P, k, archive_prob, the archive uint8 [A][128] (read back through
-                   archive_get_points) and the stream; a resume pushes the archive back and continues bit for bit.  A resume under another
-                   algo, game, model, P, k or archive_prob raises and names both sides."""
-    ns = exp[NS_KEY]
-    k, prob = int(ns['k']), float(ns['archive_prob'])
-    if not 1 <= k <= _lib.RAM_NOVELTY_KMAX:
-        raise ValueError("novelty_search k = {}: expected 1 .. RAM_NOVELTY_KMAX = {}".format(k, _lib.RAM_NOVELTY_KMAX))
-    if not 0.0 <= prob <= 1.0:
-        raise ValueError("novelty_search archive_prob = {!r}: expected a probability".format(ns['archive_prob']))
-    n, T, V = exp['population_size'], exp['selection_threshold'], exp['validation_threshold']
-    asked, game = exp.get('model', 'Model'), exp.get('game') or 'an Atari game'
-    if asked not in MODEL_KINDS or game == 'maze' or _is_dense_run(None, exp):
+      snapshot     num_params = P as well, the archive uint8 [A][128] (read back through archive_get_points, the appended entries only);
+                   a resume pushes it back with archive_append_points."""
+    k, prob = _check_ns(exp, 'RAM_NOVELTY_KMAX')
+    n, asked = exp['population_size'], exp.get('model', 'Model')
+    if asked not in MODEL_KINDS or exp.get('game') == 'maze' or _is_dense_run(None, exp):
         raise NotImplementedError("model {!r} on game {!r}: atari_ns_main runs {} on an Atari game".format(
             asked, exp.get('game'), ' and '.join(repr(m) for m in sorted(MODEL_KINDS))))
     if engine is None:
@@ -892,69 +897,7 @@ def atari_ns_main(log_dir, engine=None, noise=None, seed=0, max_iters=None, **ex
     tlogger.start(log_dir)
     noise = noise if noise is not None else SharedNoiseTable()
     noise.attach(engine)
-    model = HipModel(engine)
+    engine.ga_set_init_scale(model_scale_by(engine.n_actions, engine.kind))     # as HipModel sets it for main
     rs = np.random.RandomState(seed)
-    all_tstart = time.time()
-    engine.archive_clear()
-    state = _resume_maze(log_dir, ALGO_NS, rs, game, asked, engine.P)
-    if state is None:
-        state = TrainingState(exp)
-        state.archive, state.stream = np.zeros((0, _lib.RAM_BYTES), np.uint8), None
-    else:
-        if (state.k, state.archive_prob) != (k, prob):
-            raise ValueError("snapshot.pkl in {} holds k {}, archive_prob {!r}; this run is k {}, archive_prob {!r}".format(
-                log_dir, state.k, state.archive_prob, k, prob))
-        if len(state.archive):
-            engine.archive_append_points(state.archive)
-    state.game, state.model, state.algo, state.num_params, state.k, state.archive_prob = exp.get('game'), asked, ALGO_NS, engine.P, k, prob
-    if 'load_population' in exp:
-        state.copy_population(exp['load_population'])
-    parents = [o.seeds for o in state.population[:T]]               # the top T by novelty, no elite carried
+    return _ns_loop(log_dir, exp, k, prob, _AtariNs(engine, rs), engine, rs, exp.get('game'), asked, engine.P, len(noise.noise) - engine.P + 1, max_iters)
 
-    def evaluate(individuals, tslimit):
-        return _evaluate(engine, [o.seeds for o in individuals], tslimit, rs)
-
-    iters = 0
-    while max_iters is None or iters < max_iters:
-        iters += 1
-        tstart_iteration = time.time()
-        if state.timesteps_so_far >= exp['timesteps']:
-            break
-        assert (len(parents) == 0 and (state.it == 0 or T == 0)) or len(parents) == T
-        power = state.sample(state.mutation_power)
-        of, idx = _draw_generation(rs, n, len(parents), len(noise.noise) - model.num_params + 1)
-        archived = np.flatnonzero(rs.random_sample(n) < prob).astype(np.int32)
-        tasks = [_member(i, of, idx, power, parents)[1] for i in range(n)]
-        rets, lens = _evaluate(engine, tasks, state.tslimit, rs)   # one call: n <= max_members
-        raw = np.asarray(engine.ram_novelty_pool(k), np.float64)   # against the archive as it was before this generation, and the generation
-        novelty = np.where(np.isfinite(raw), raw, 0.0)
-        if archived.size:
-            engine.archive_append_members(archived)
-            state.archive = np.concatenate([state.archive, engine.archive_get_points(len(state.archive), archived.size)])
-        state.num_frames += int(lens.sum()) * 4
-        state.it += 1
-        rewards = np.asarray(rets, np.float64)
-        by_novelty = np.argsort(-novelty, kind='stable')            # (-novelty, arrival index)
-        by_reward = engine.ga_select(np.asarray(rets, np.float32), n)
-        offspring = {}                                              # member index -> its Offspring
-        for i in list(by_novelty[:T]) + list(by_reward[:V]):
-            i = int(i)
-            if i not in offspring:
-                offspring[i] = Offspring(tasks[i], [float(rets[i])], [int(lens[i])])
-                offspring[i].novelty = float(novelty[i])
-        selected = [offspring[int(i)] for i in by_novelty[:T]]
-        validation_population = [offspring[int(i)] for i in by_reward[:V]]
-        state.population = selected + [o for o in validation_population if not any(o is s for s in selected)]
-        v = _validate_and_test(state, exp, validation_population, evaluate, int(lens.sum()))
-        parents = [o.seeds for o in selected]
-        dt = time.time() - tstart_iteration
-        state.time_elapsed += dt
-        _record_rows(state, power, rewards, T, v, dt, all_tstart)
-        for key, val in (('NoveltyMean', float(np.mean(novelty))), ('NoveltyMax', float(np.max(novelty))),
-                         ('ArchiveSize', int(state.archive.shape[0]))):
-            tlogger.record_tabular(key, val)
-        tlogger.dump_tabular()
-        _end_generation(state, log_dir, lens, rs)
-        if state.timesteps_so_far >= exp['timesteps']:
-            break
-    return float(state.curr_solution_test), {'val': float(state.curr_solution_val)}, state

@@ -73,7 +73,25 @@ def _ga_atari(log_dir):
     ga_gpu.main(log_dir, engine=OracleEngine(1), noise=es.SharedNoiseTable(count=2_500_000), seed=5, max_iters=ITERS, **exp)
 
 
-RUNS = {"es_maze": _es, "nses_ns": _nses("ns"), "nses_nsr": _nses("nsr"), "ga_maze": _ga(False), "ga_ns_maze": _ga(True), "ga_atari": _ga_atari}
+def _ga_ns_dense(env, game):
+    def run(log_dir):
+        import dense_gans_support as S
+        from dne_hip import ga_gpu
+        exp = S.exp(game)                      # LinearClassifier, population 10, T = 3, V = 2, k = 3, archive_prob = 0.3
+        ga_gpu.dense_ns_main(log_dir, engine=S.host_engine((env, (), "relu"), 10), noise=S.shared_noise(), seed=4, max_iters=ITERS, **exp)
+    return run
+
+
+def _ga_ns_atari(log_dir):
+    import atari_gans_support as S
+    from dne_hip import ga_gpu
+    exp = S.exp()                              # Model on frostbite, population 6, T = 2, V = 2, k = 3, archive_prob = 0.3
+    ga_gpu.atari_ns_main(log_dir, engine=S.AtariGaNsHostEngine(max_members=6), noise=S.shared_noise(), seed=5, max_iters=ITERS, **exp)
+
+
+RUNS = {"es_maze": _es, "nses_ns": _nses("ns"), "nses_nsr": _nses("nsr"), "ga_maze": _ga(False), "ga_ns_maze": _ga(True), "ga_atari": _ga_atari,
+        "ga_ns_dense_maze": _ga_ns_dense("maze", "maze"), "ga_ns_dense_cartpole": _ga_ns_dense("cartpole", "gym.CartPole-v1"),
+        "ga_ns_atari": _ga_ns_atari}
 
 
 def table_keys(log_path):
