@@ -38,6 +38,7 @@
 #include "step_env.h"
 #include "dense.h"
 #include "dense_ga.h"
+#include "mujoco_ga.h"
 #include "dense_novelty.h"
 #include "ram_novelty.h"
 
@@ -698,6 +699,12 @@ struct dne_handle {
     // positions and archive (maze_*, mzn_*); mj_opt holds its own 11 means and deviations
     bool mjmaze = false;
     mjmaze::Options mj_opt{};
+    // Deep-GA on the two MujocoPolicy kinds (csrc/mujoco_ga.h, dne_mujoco_ga_*): the bank is mzg_mem as two halves of mjg_Tmax slots, then
+    // mjg_root_cap scratch slots for an evaluation's roots (none until an evaluation has a root); mzg_slot / mzg_off / mzg_scale hold the
+    // descriptors; mjg_sc [entry][mjg_sc_stride] the column scales of every entry with a root, mjg_root_idx [entry] its noise index (< 0: none)
+    int mjg_Tmax = 0, mjg_sc_stride = 0; size_t mjg_root_cap = 0, mjg_entries = 0;
+    float *mjg_sc = nullptr; int64_t *mjg_root_idx = nullptr; std::vector<int64_t> mjg_host_root;
+    mujoco_ga::Layout mjg_L{};
     // DNE_KIND_DENSE: a dense policy of the shape dn_shape on the step environment dn_shape.env, k_dense_run (csrc/dense.h)
     bool dense = false;
     dense::Shape dn_shape{};
@@ -3188,9 +3195,10 @@ extern "C" int dne_pendulum_num_params(int hidden, int n_out) {
     return pendulum::offsets(hidden, n_out).P;
 }
 
-// what k_pendulum_rollout reads for the members [first, first + count) set by dne_set_members; the per-member options and the outputs are left null
-static pendulum::RolloutArgs pendulum_args(dne_handle *h, int first, int count, int tslimit) {
-    pendulum::RolloutArgs A = member_args<pendulum::RolloutArgs>(h, maze_set_members(h), first, count, tslimit);
+// what k_pendulum_rollout reads for the members [first, first + count) of M (dne_set_members', or the GA bank's); the per-member options and the
+// outputs are left null
+static pendulum::RolloutArgs pendulum_args(dne_handle *h, const MazeMembers &M, int first, int count, int tslimit) {
+    pendulum::RolloutArgs A = member_args<pendulum::RolloutArgs>(h, M, first, count, tslimit);
     A.seed = h->seeds; A.opt = h->pd_opt;
     return A;
 }
@@ -3207,8 +3215,8 @@ extern "C" int dne_pendulum_set_rollout_options(dne_handle *h, int n, float ac_n
     return mujoco_set_rollout_options(h, MJ_PENDULUM, "dne_pendulum_set_rollout_options", n, ac_noise_std, ac_off, stat_flag);
 }
 
-// members [0, n), one whole episode each under its own reset seed, one launch
-static int pendulum_eval(dne_handle *h, const char *call, int n, int tslimit, const uint32_t *env_seed, float *returns, float *signreturns,
+// members [0, n) of M, one whole episode each under its own reset seed, one launch
+static int pendulum_eval(dne_handle *h, const MazeMembers &M, const char *call, int n, int tslimit, const uint32_t *env_seed, float *returns, float *signreturns,
                          int32_t *lengths, uint8_t *bc_out) {
     if (bc_out) return h->fail("%s: behaviour characterisations are not available on a DNE_KIND_PENDULUM engine (kind %d): bc must be NULL; "
                                "dne_pendulum_final_state has the final state of every member", call, DNE_KIND_PENDULUM);
@@ -3217,7 +3225,7 @@ static int pendulum_eval(dne_handle *h, const char *call, int n, int tslimit, co
     if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
     if (mujoco_stat_ready(h, MJ_PENDULUM, call) || mujoco_options_ready(h, MJ_PENDULUM, call, n)) return -1;
     HCHECK(h, hipMemcpyAsync(h->seeds, env_seed, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    pendulum::RolloutArgs A = pendulum_args(h, 0, n, tslimit);
+    pendulum::RolloutArgs A = pendulum_args(h, M, 0, n, tslimit);
     A.ret = h->ret; A.sign = h->sign; A.len = h->len; A.state = h->pd_state;
     mujoco_take_options(h, A);
     if (run_episodes(h, n, returns, signreturns, lengths, [&] { pendulum_launch(h, A); })) return -1;
@@ -3242,7 +3250,7 @@ extern "C" int dne_pendulum_debug_trace(dne_handle *h, int member, int tslimit, 
     if (trace_args(h, "dne_pendulum_debug_trace", DNE_KIND_PENDULUM, member, tslimit > 0 && trace && steps)) return -1;
     if (!h->noise) return h->fail("noise table not uploaded (dne_noise_upload)");
     if (mujoco_stat_ready(h, MJ_PENDULUM, "dne_pendulum_debug_trace")) return -1;
-    pendulum::RolloutArgs A = pendulum_args(h, member, 1, tslimit);
+    pendulum::RolloutArgs A = pendulum_args(h, maze_set_members(h), member, 1, tslimit);
     A.opt.ac_noise_std = 0.0f;
     if (init2) { A.has_init = 1; A.init2[0] = init2[0]; A.init2[1] = init2[1]; }
     return run_trace(h, "dne_pendulum_debug_trace", std::min(tslimit, (int)pendulum::EPISODE_STEPS), pendulum::TRACE_W, trace, steps, [&](double *rows, int32_t *count) {
@@ -3338,9 +3346,10 @@ extern "C" int dne_mjmaze_num_params(int hidden, int n_out) {
     return mjmaze::offsets(hidden, n_out).P;
 }
 
-// what k_mjmaze_rollout reads for the members [first, first + count) set by dne_set_members; the per-member options and the outputs are left null
-static mjmaze::RolloutArgs mjmaze_args(dne_handle *h, int first, int count, int tslimit) {
-    mjmaze::RolloutArgs A = member_args<mjmaze::RolloutArgs>(h, maze_set_members(h), first, count, tslimit);
+// what k_mjmaze_rollout reads for the members [first, first + count) of M (dne_set_members', or the GA bank's); the per-member options and the
+// outputs are left null
+static mjmaze::RolloutArgs mjmaze_args(dne_handle *h, const MazeMembers &M, int first, int count, int tslimit) {
+    mjmaze::RolloutArgs A = member_args<mjmaze::RolloutArgs>(h, M, first, count, tslimit);
     A.hdr = h->maze_hdr; A.walls = h->maze_walls; A.nw = h->maze_nw; A.opt = h->mj_opt;
     return A;
 }
@@ -3364,13 +3373,13 @@ static int mjmaze_ready(dne_handle *h, const char *call) {
     return mujoco_stat_ready(h, MJ_MAZE, call);
 }
 
-// members [0, n), one whole episode each from the header's start point (no reset seed: env_seed is not read), one launch
-static int mjmaze_eval(dne_handle *h, const char *call, int n, int tslimit, float *returns, float *signreturns, int32_t *lengths, uint8_t *bc_out) {
+// members [0, n) of M, one whole episode each from the header's start point (no reset seed: env_seed is not read), one launch
+static int mjmaze_eval(dne_handle *h, const MazeMembers &M, const char *call, int n, int tslimit, float *returns, float *signreturns, int32_t *lengths, uint8_t *bc_out) {
     if (bc_out) return h->fail("%s: behaviour characterisations are not available on a DNE_KIND_MJMAZE engine (kind %d): bc must be NULL; "
                                "dne_maze_final_state has the final (x, y) of every member", call, DNE_KIND_MJMAZE);
     if (tslimit <= 0) return h->fail("timestep limit must be positive");
     if (mjmaze_ready(h, call) || mujoco_options_ready(h, MJ_MAZE, call, n)) return -1;
-    mjmaze::RolloutArgs A = mjmaze_args(h, 0, n, tslimit);
+    mjmaze::RolloutArgs A = mjmaze_args(h, M, 0, n, tslimit);
     A.ret = h->ret; A.sign = h->sign; A.len = h->len; A.xy = h->maze_xy;
     mujoco_take_options(h, A);
     if (run_episodes(h, n, returns, signreturns, lengths, [&] { mjmaze_launch(h, A); })) return -1;
@@ -3388,7 +3397,7 @@ extern "C" int dne_mjmaze_debug_trace(dne_handle *h, int member, int tslimit, fl
     DeviceGuard dg(h);
     if (trace_args(h, "dne_mjmaze_debug_trace", DNE_KIND_MJMAZE, member, tslimit > 0 && trace && steps)) return -1;
     if (mjmaze_ready(h, "dne_mjmaze_debug_trace")) return -1;
-    mjmaze::RolloutArgs A = mjmaze_args(h, member, 1, tslimit);
+    mjmaze::RolloutArgs A = mjmaze_args(h, maze_set_members(h), member, 1, tslimit);
     A.opt.ac_noise_std = 0.0f;
     return run_trace(h, "dne_mjmaze_debug_trace", std::min(tslimit, (int)mjmaze::EPISODE_STEPS), mjmaze::TRACE_W, trace, steps, [&](float *rows, int32_t *count) {
         A.trace = rows; A.trace_steps = count;
@@ -3440,6 +3449,247 @@ extern "C" int dne_mjmaze_forward_host(const float *theta, const float *obs, int
     for (int i = 0; i < n; i++)
         mjmaze::forward_host(hidden, nonlin, theta + (size_t)i * P, o, obs + mjmaze::OBS * (size_t)i, x + mjmaze::OBS * (size_t)i, h1 + (size_t)i * hidden,
                              h2 + (size_t)i * hidden, out + (size_t)i * n_out, action + mjmaze::ADIM * (size_t)i);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------- Deep-GA on MujocoPolicy (csrc/mujoco_ga.h)
+// maze_ga's bank for the two MujocoPolicy kinds: the halves hold T_max slots (dne_mujoco_ga_reserve), the roots of an evaluation get their
+// scratch slots behind them when the first one comes, and a root's scale is one value a column, computed from its own noise slice
+static int needs_mujoco(dne_handle *h, const char *call) {
+    return (h->pendulum || h->mjmaze) ? 0 : h->fail("%s needs a DNE_KIND_PENDULUM or DNE_KIND_MJMAZE engine (this one: kind %d)", call, h->L.kind);
+}
+
+static float *mjg_bank(dne_handle *h, int half) { return h->mzg_mem + (size_t)half * h->mjg_Tmax * h->base_stride; }
+static dim3 mjg_grid(dne_handle *h, int count) { return dim3(count, (h->mjg_L.P + 255) / 256); }
+
+extern "C" int dne_mujoco_ga_reserve(dne_handle *h, int T_max) {
+    DeviceGuard dg(h);
+    if (needs_mujoco(h, "dne_mujoco_ga_reserve")) return -1;
+    if (T_max < 1 || T_max > (1 << 20)) return h->fail("dne_mujoco_ga_reserve: T_max = %d outside [1, %d]", T_max, 1 << 20);
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, h->release(h->mzg_mem)); HCHECK(h, h->release(h->mzg_slot)); HCHECK(h, h->release(h->mzg_off)); HCHECK(h, h->release(h->mzg_scale));
+    HCHECK(h, h->release(h->mjg_sc)); HCHECK(h, h->release(h->mjg_root_idx));
+    // (the chain arrays too: chain_offs holds mjg_entries + 1 values, and mjg_entries follows T_max)
+    HCHECK(h, h->release(h->mzg_chain_offs)); HCHECK(h, h->release(h->mzg_seeds)); HCHECK(h, h->release(h->mzg_powers));
+    h->mzg_chain_cap = 0;
+    h->mzg_T = h->mzg_half = h->mjg_Tmax = 0; h->mjg_root_cap = 0;
+    h->mjg_L = mujoco_ga::layout(h->mjmaze ? (int)mjmaze::OBS : (int)pendulum::OBS, h->pd_hidden, h->cfg.n_actions);
+    if (h->mjg_L.P != h->L.P) return h->fail("dne_mujoco_ga_reserve: the layout holds %d parameters, the engine %d", h->mjg_L.P, (int)h->L.P);
+    h->mjg_sc_stride = (h->mjg_L.ncol + 15) / 16 * 16;
+    h->mjg_entries = (size_t)std::max(h->M, T_max);
+    const size_t E = h->mjg_entries, bank = 2 * (size_t)T_max * h->base_stride;
+    HCHECK(h, h->alloc(&h->mzg_slot, E, "mujoco_ga_slot")); HCHECK(h, h->alloc(&h->mzg_off, E, "mujoco_ga_off")); HCHECK(h, h->alloc(&h->mzg_scale, E, "mujoco_ga_scale"));
+    HCHECK(h, h->alloc(&h->mjg_sc, E * h->mjg_sc_stride, "mujoco_ga_colscale")); HCHECK(h, h->alloc(&h->mjg_root_idx, E, "mujoco_ga_root_idx"));
+    float *mem = nullptr;
+    HCHECK(h, h->alloc(&mem, bank, "mujoco_ga_bank"));
+    HCHECK(h, hipMemset(mem, 0, bank * sizeof(float)));
+    h->mzg_mem = mem; h->mjg_Tmax = T_max;
+    return 0;
+}
+
+// what every call that reads the table or the bank needs first; an evaluation also its maze and its statistics
+static int mjg_ready(dne_handle *h, const char *call, bool eval) {
+    if (!h->mzg_mem) return h->fail("%s: no bank (dne_mujoco_ga_reserve comes first)", call);
+    if (!h->noise) return h->fail("%s: noise table not uploaded (dne_noise_upload)", call);
+    if (eval && h->mjmaze && h->maze_nw < 1) return h->fail("%s: no maze loaded (dne_maze_set_walls comes before an evaluation)", call);
+    if (eval) return mujoco_stat_ready(h, h->mjmaze ? MJ_MAZE : MJ_PENDULUM, call);
+    return 0;
+}
+
+// the column scales of entries [0, n): root[e] the noise index of entry e's root, < 0 for an entry without one
+static int mjg_colscale(dne_handle *h, int n, const std::vector<int64_t> &root) {
+    HCHECK(h, hipMemcpyAsync(h->mjg_root_idx, root.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(mujoco_ga::k_mujoco_ga_colscale, dim3(n, (h->mjg_L.ncol + 63) / 64), dim3(64), 0, h->stream, (const float *)h->noise, h->mjg_L,
+                       (const int64_t *)h->mjg_root_idx, h->mjg_sc, h->mjg_sc_stride);
+    HCHECK(h, hipGetLastError());
+    return 0;
+}
+
+extern "C" int dne_mujoco_ga_build(dne_handle *h, int T, const int32_t *chain_offsets, const int64_t *seeds, const float *powers) {
+    DeviceGuard dg(h);
+    if (needs_mujoco(h, "dne_mujoco_ga_build")) return -1;
+    if (mjg_ready(h, "dne_mujoco_ga_build", false)) return -1;
+    if (T < 1 || T > h->mjg_Tmax) return h->fail("dne_mujoco_ga_build: T = %d outside [1, T_max = %d]", T, h->mjg_Tmax);
+    if (!chain_offsets || !seeds || !powers) return h->fail("dne_mujoco_ga_build: a buffer is missing");
+    if (chain_offsets[0] != 0) return h->fail("dne_mujoco_ga_build: chain_offsets starts at %d, not 0", chain_offsets[0]);
+    const std::string bad = mujoco_ga::check_genomes(T, h->mjg_L.P, chain_offsets, seeds, h->noise_count);
+    if (!bad.empty()) return h->fail("dne_mujoco_ga_build: %s", bad.c_str());
+    const size_t total = (size_t)chain_offsets[T];
+    if (total > h->mzg_chain_cap || !h->mzg_chain_offs) {
+        HCHECK(h, hipStreamSynchronize(h->stream));
+        HCHECK(h, h->release(h->mzg_chain_offs)); HCHECK(h, h->release(h->mzg_seeds)); HCHECK(h, h->release(h->mzg_powers));
+        h->mzg_chain_cap = std::max<size_t>(2 * total, 4096);
+        HCHECK(h, h->alloc(&h->mzg_chain_offs, h->mjg_entries + 1, "mujoco_ga_chain_offs"));
+        HCHECK(h, h->alloc(&h->mzg_seeds, h->mzg_chain_cap, "mujoco_ga_seeds")); HCHECK(h, h->alloc(&h->mzg_powers, h->mzg_chain_cap, "mujoco_ga_powers"));
+    }
+    std::vector<int64_t> &root = h->mjg_host_root;
+    root.resize(T);
+    for (int j = 0; j < T; j++) root[j] = seeds[chain_offsets[j]];
+    HCHECK(h, hipMemcpyAsync(h->mzg_chain_offs, chain_offsets, ((size_t)T + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HCHECK(h, hipMemcpyAsync(h->mzg_seeds, seeds, total * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    HCHECK(h, hipMemcpyAsync(h->mzg_powers, powers, total * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (mjg_colscale(h, T, root)) return -1;
+    const int other = 1 - h->mzg_half;
+    hipLaunchKernelGGL(mujoco_ga::k_mujoco_ga_build, mjg_grid(h, T), dim3(256), 0, h->stream, (const float *)h->noise, h->mjg_L, (const float *)h->mjg_sc,
+                       h->mjg_sc_stride, (const int32_t *)h->mzg_chain_offs, (const int64_t *)h->mzg_seeds, (const float *)h->mzg_powers, mjg_bank(h, other),
+                       h->base_stride);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipStreamSynchronize(h->stream));   // the caller's arrays may go away
+    h->mzg_half = other; h->mzg_T = T;
+    return 0;
+}
+
+extern "C" int dne_mujoco_ga_promote(dne_handle *h, int T_new, const int32_t *parent, const int64_t *idx, const float *power) {
+    DeviceGuard dg(h);
+    if (needs_mujoco(h, "dne_mujoco_ga_promote")) return -1;
+    if (mjg_ready(h, "dne_mujoco_ga_promote", false)) return -1;
+    if (T_new < 1 || T_new > h->mjg_Tmax) return h->fail("dne_mujoco_ga_promote: T = %d outside [1, T_max = %d]", T_new, h->mjg_Tmax);
+    if (!parent || !idx || !power) return h->fail("dne_mujoco_ga_promote: a buffer is missing");
+    std::vector<int64_t> &root = h->mjg_host_root;
+    root.resize(T_new);
+    bool roots = false;
+    for (int j = 0; j < T_new; j++) {
+        const std::string bad = mujoco_ga::check_member(j, h->mzg_T, h->mjg_L.P, h->noise_count, parent[j], idx[j], true);
+        if (!bad.empty()) return h->fail("dne_mujoco_ga_promote: %s", bad.c_str());
+        root[j] = parent[j] < 0 ? idx[j] : -1;
+        roots = roots || parent[j] < 0;
+    }
+    if (mzg_upload_members(h, T_new, parent, idx, power)) return -1;
+    if (roots && mjg_colscale(h, T_new, root)) return -1;
+    const int other = 1 - h->mzg_half;
+    hipLaunchKernelGGL(mujoco_ga::k_mujoco_ga_promote, mjg_grid(h, T_new), dim3(256), 0, h->stream, (const float *)h->noise, h->mjg_L, (const float *)h->mjg_sc,
+                       h->mjg_sc_stride, (const float *)mjg_bank(h, h->mzg_half), mjg_bank(h, other), h->base_stride, (const int32_t *)h->mzg_slot,
+                       (const int64_t *)h->mzg_off, (const float *)h->mzg_scale);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    h->mzg_half = other; h->mzg_T = T_new;
+    return 0;
+}
+
+// the scratch slots of an evaluation's roots, behind the two halves of the bank: `need` of them, the bank carried over when they grow
+static int mjg_root_slots(dne_handle *h, size_t need) {
+    if (need <= h->mjg_root_cap) return 0;
+    const size_t bank = 2 * (size_t)h->mjg_Tmax * h->base_stride, all = bank + need * h->base_stride;
+    float *mem = nullptr;
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, h->alloc(&mem, all, "mujoco_ga_bank"));
+    HCHECK(h, hipMemcpy(mem, h->mzg_mem, bank * sizeof(float), hipMemcpyDeviceToDevice));
+    HCHECK(h, hipMemset(mem + bank, 0, (all - bank) * sizeof(float)));
+    HCHECK(h, h->release(h->mzg_mem));
+    h->mzg_mem = mem; h->mjg_root_cap = need;
+    return 0;
+}
+
+extern "C" int dne_mujoco_ga_eval(dne_handle *h, int n, const int32_t *parent, const int64_t *idx, const float *power, const uint32_t *env_seed, int tslimit,
+                                  float *returns, float *signreturns, int32_t *lengths) {
+    DeviceGuard dg(h);
+    if (needs_mujoco(h, "dne_mujoco_ga_eval")) return -1;
+    if (mjg_ready(h, "dne_mujoco_ga_eval", true)) return -1;
+    if (n < 1 || n > h->M) return h->fail("dne_mujoco_ga_eval: n = %d outside [1, max_members = %d]", n, h->M);
+    if (!parent || !idx || !power || !returns || !lengths) return h->fail("dne_mujoco_ga_eval: a buffer is missing");
+    if (tslimit <= 0) return h->fail("dne_mujoco_ga_eval: timestep limit must be positive");
+    if (h->pendulum && !env_seed) return h->fail("dne_mujoco_ga_eval: a DNE_KIND_PENDULUM engine resets every member from its environment seed, env_seed is NULL");
+    // a child is the rollout kernel's own member: (its parent's bank slot, idx, power); a root runs from scratch slot 2 T_max + i at scale 0
+    const int bank0 = h->mzg_half * h->mjg_Tmax, root0 = 2 * h->mjg_Tmax;
+    std::vector<int32_t> &slot = h->mzg_host_slot;
+    std::vector<float> &scale = h->mzg_host_scale;
+    std::vector<int64_t> &rootidx = h->mjg_host_root;
+    slot.resize(n); scale.resize(n); rootidx.resize(n);
+    bool roots = false;
+    for (int i = 0; i < n; i++) {
+        const std::string bad = mujoco_ga::check_member(i, h->mzg_T, h->mjg_L.P, h->noise_count, parent[i], idx[i], false);
+        if (!bad.empty()) return h->fail("dne_mujoco_ga_eval: %s", bad.c_str());
+        const bool root = parent[i] < 0;
+        slot[i] = root ? root0 + i : bank0 + parent[i];
+        scale[i] = root ? 0.0f : power[i];
+        rootidx[i] = root ? idx[i] : -1;
+        roots = roots || root;
+    }
+    if (mujoco_options_ready(h, h->mjmaze ? MJ_MAZE : MJ_PENDULUM, "dne_mujoco_ga_eval", n)) return -1;
+    if (roots && mjg_root_slots(h, (size_t)n)) return -1;
+    if (mzg_upload_members(h, n, slot.data(), idx, scale.data())) return -1;
+    if (roots) {
+        if (mjg_colscale(h, n, rootidx)) return -1;
+        hipLaunchKernelGGL(mujoco_ga::k_mujoco_ga_roots, mjg_grid(h, n), dim3(256), 0, h->stream, (const float *)h->noise, h->mjg_L, (const float *)h->mjg_sc,
+                           h->mjg_sc_stride, (const int32_t *)h->mzg_slot, (const int64_t *)h->mzg_off, root0, h->mzg_mem, h->base_stride);
+        HCHECK(h, hipGetLastError());
+    }
+    const MazeMembers M{h->mzg_mem, h->mzg_slot, h->mzg_off, h->mzg_scale};
+    if (h->pendulum) return pendulum_eval(h, M, "dne_mujoco_ga_eval", n, tslimit, env_seed, returns, signreturns, lengths, nullptr);
+    return mjmaze_eval(h, M, "dne_mujoco_ga_eval", n, tslimit, returns, signreturns, lengths, nullptr);
+}
+
+extern "C" int dne_mujoco_ga_parents(dne_handle *h) {
+    if (needs_mujoco(h, "dne_mujoco_ga_parents")) return -1;
+    return h->mzg_T;
+}
+
+extern "C" int dne_mujoco_ga_get_parent(dne_handle *h, int j, float *out) {
+    DeviceGuard dg(h);
+    if (needs_mujoco(h, "dne_mujoco_ga_get_parent")) return -1;
+    if (!h->mzg_mem) return h->fail("dne_mujoco_ga_get_parent: no bank (dne_mujoco_ga_reserve comes first)");
+    if (j < 0 || j >= h->mzg_T) return h->fail("dne_mujoco_ga_get_parent: parent %d, the bank holds %d", j, h->mzg_T);
+    if (!out) return h->fail("dne_mujoco_ga_get_parent: no output buffer");
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    HCHECK(h, hipMemcpy(out, mjg_bank(h, h->mzg_half) + (size_t)j * h->base_stride, (size_t)h->mjg_L.P * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the same header on the CPU: no handle, no GPU
+static int mjg_host_layout(const char *call, int kind, int hidden, int n_out, const float *noise, size_t count, mujoco_ga::Layout *L) {
+    const std::string c(call);
+    if (kind != DNE_KIND_PENDULUM && kind != DNE_KIND_MJMAZE) {
+        g_create_error = c + ": kind " + std::to_string(kind) + " runs no MujocoPolicy (DNE_KIND_PENDULUM (6) and DNE_KIND_MJMAZE (7) do)";
+        return -1;
+    }
+    const int obs = kind == DNE_KIND_MJMAZE ? (int)mjmaze::OBS : (int)pendulum::OBS;
+    if (!mujoco_ga::shape_ok(obs, hidden, n_out)) {
+        g_create_error = c + ": hidden width " + std::to_string(hidden) + " with " + std::to_string(n_out) + " outputs is not a shape csrc/" +
+                         (kind == DNE_KIND_MJMAZE ? "mjmaze.h" : "pendulum.h") + " builds";
+        return -1;
+    }
+    *L = mujoco_ga::layout(obs, hidden, n_out);
+    if (!noise) { g_create_error = c + ": a buffer is missing"; return -1; }
+    if (count < (size_t)L->P) { g_create_error = c + ": a table of " + std::to_string(count) + " floats holds no P = " + std::to_string(L->P) + " parameters"; return -1; }
+    return 0;
+}
+
+extern "C" int dne_mujoco_ga_colscale_host(const float *noise, size_t count, int kind, int hidden, int n_out, int64_t idx0, float *out) {
+    mujoco_ga::Layout L;
+    if (mjg_host_layout("dne_mujoco_ga_colscale_host", kind, hidden, n_out, noise, count, &L)) return -1;
+    if (!out) { g_create_error = "dne_mujoco_ga_colscale_host: a buffer is missing"; return -1; }
+    if (!dense_ga::in_table(idx0, L.P, count)) {
+        g_create_error = "dne_mujoco_ga_colscale_host: " + dense_ga::fmt("noise index %lld + P = %lld outside the table of %lld", (long long)idx0, L.P, (long long)count);
+        return -1;
+    }
+    mujoco_ga::colscale_host(noise, L, idx0, out);
+    return 0;
+}
+
+extern "C" int dne_mujoco_ga_theta_host(const float *noise, size_t count, int kind, int hidden, int n_out, const int64_t *seeds, const float *powers, int nseeds,
+                                        float *out) {
+    mujoco_ga::Layout L;
+    if (mjg_host_layout("dne_mujoco_ga_theta_host", kind, hidden, n_out, noise, count, &L)) return -1;
+    if (!seeds || !powers || !out) { g_create_error = "dne_mujoco_ga_theta_host: a buffer is missing"; return -1; }
+    const int32_t co[2] = {0, nseeds};
+    const std::string bad = mujoco_ga::check_genomes(1, L.P, co, seeds, count);
+    if (!bad.empty()) { g_create_error = "dne_mujoco_ga_theta_host: " + bad; return -1; }
+    mujoco_ga::genome_host(noise, L, seeds, powers, nseeds, out);
+    return 0;
+}
+
+extern "C" int dne_mujoco_ga_members_host(const float *noise, size_t count, int kind, int hidden, int n_out, const float *bank, int T, const int32_t *parent,
+                                          const int64_t *idx, const float *power, int n, float *out) {
+    mujoco_ga::Layout L;
+    if (mjg_host_layout("dne_mujoco_ga_members_host", kind, hidden, n_out, noise, count, &L)) return -1;
+    if (n < 1) { g_create_error = "dne_mujoco_ga_members_host: n = " + std::to_string(n) + ", at least one member is needed"; return -1; }
+    if (T < 0 || (T > 0 && !bank)) { g_create_error = "dne_mujoco_ga_members_host: T = " + std::to_string(T) + " parents without a bank"; return -1; }
+    if (!parent || !idx || !power || !out) { g_create_error = "dne_mujoco_ga_members_host: a buffer is missing"; return -1; }
+    for (int i = 0; i < n; i++) {
+        const std::string bad = mujoco_ga::check_member(i, T, L.P, count, parent[i], idx[i], true);
+        if (!bad.empty()) { g_create_error = "dne_mujoco_ga_members_host: " + bad; return -1; }
+    }
+    mujoco_ga::members_host(noise, L, bank, parent, idx, power, n, out);
     return 0;
 }
 
@@ -4226,8 +4476,8 @@ static int episodic_eval(dne_handle *h, const char *call, int n, int tslimit, co
     if (h->maze) return maze_eval_members(h, maze_set_members(h), n, tslimit, returns, signreturns, lengths, bc);
     if (h->dense) return dense_eval(h, maze_set_members(h), call, n, tslimit, env_seed, returns, signreturns, lengths, bc);
     if (h->cartpole) return cartpole_eval(h, call, n, tslimit, env_seed, returns, signreturns, lengths, bc);
-    if (h->pendulum) return pendulum_eval(h, call, n, tslimit, env_seed, returns, signreturns, lengths, bc);
-    return mjmaze_eval(h, call, n, tslimit, returns, signreturns, lengths, bc);
+    if (h->pendulum) return pendulum_eval(h, maze_set_members(h), call, n, tslimit, env_seed, returns, signreturns, lengths, bc);
+    return mjmaze_eval(h, maze_set_members(h), call, n, tslimit, returns, signreturns, lengths, bc);
 }
 
 extern "C" int dne_es_eval(dne_handle *h, const int64_t *idx, int n, float sigma, int tslimit, const uint32_t *env_seed,

@@ -92,7 +92,7 @@ class Profile(C.Structure):
 
 def build(force=False):
     """Compile libdne_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h", "cartpole.h", "pendulum.h", "mjmaze.h", "step_env.h", "dense.h", "dense_ga.h", "dense_novelty.h", "ram_novelty.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "plan.h", "forward.h", "forward_variants.h", "forward_large.h", "reduce.h", "novelty.h", "env_synth.h", "maze.h", "maze_novelty.h", "maze_ga.h", "cartpole.h", "pendulum.h", "mjmaze.h", "step_env.h", "dense.h", "dense_ga.h", "mujoco_ga.h", "dense_novelty.h", "ram_novelty.h")]
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "dne_hip.h"))
     if os.environ.get("DNE_LIB_PATH"):
         # another build of the same ABI was asked for by name: `make` only knows the in-tree library, so running it here would
@@ -118,8 +118,22 @@ def load():
         lib.dne_last_error.restype = C.c_char_p
         lib.dne_last_error.argtypes = [C.c_void_p]
         lib.dne_destroy.restype = None
+        _mujoco_ga_argtypes(lib)
         _lib = lib
     return _lib
+
+
+def _mujoco_ga_argtypes(lib):
+    """dne_mujoco_ga_* (include/dne_hip.h): every argument typed, so that a wrong one is a ctypes.ArgumentError and not a wild pointer"""
+    P = C.POINTER
+    h, i32, i64, f32, u32 = C.c_void_p, P(C.c_int32), P(C.c_int64), P(C.c_float), P(C.c_uint32)
+    table = [f32, C.c_size_t, C.c_int, C.c_int, C.c_int]   # noise, count, kind, hidden, n_out
+    for name, args in (("reserve", [h, C.c_int]), ("build", [h, C.c_int, i32, i64, f32]),
+                       ("eval", [h, C.c_int, i32, i64, f32, u32, C.c_int, f32, f32, i32]), ("promote", [h, C.c_int, i32, i64, f32]),
+                       ("parents", [h]), ("get_parent", [h, C.c_int, f32]), ("colscale_host", table + [C.c_int64, f32]),
+                       ("theta_host", table + [i64, f32, C.c_int, f32]), ("members_host", table + [f32, C.c_int, i32, i64, f32, C.c_int, f32])):
+        fn = getattr(lib, "dne_mujoco_ga_" + name)
+        fn.argtypes, fn.restype = args, C.c_int
 
 
 def num_params(kind, nact=18):
@@ -740,6 +754,47 @@ def dense_ga_members_host(noise, scale_by, bank, parent, idx, power):
 
 
 # ---- novelty over final states on a dense policy (csrc/dense_novelty.h) ---------------------------------------------------------------------------
+# ---- Deep-GA on MujocoPolicy (csrc/mujoco_ga.h): es_distributed/ga.py's genome, the root reinitialised on its noise slice -------------------------
+def _mujoco_ga_table(who, noise, kind, hidden, n_out):
+    kind, hidden, n_out = int(kind), int(hidden), int(n_out)
+    P = pendulum_num_params(hidden, n_out) if kind == KIND_PENDULUM else mjmaze_num_params(hidden, n_out) if kind == KIND_MJMAZE else -1
+    if P < 0:
+        raise DneError("%s: kind %d, hidden width %d with %d outputs is not a MujocoPolicy shape csrc/pendulum.h or csrc/mjmaze.h builds" % (who, kind, hidden, n_out))
+    noise = _arr(noise, np.float32).reshape(-1)
+    return noise, (_ptr(noise, C.c_float), noise.size, kind, hidden, n_out), P
+
+
+def mujoco_ga_colscale_host(noise, kind, hidden, n_out, idx0):
+    """dne_mujoco_ga_colscale_host: the 2 H + O column scales 1 / sqrt(sum of squares) of the slice noise[idx0:idx0 + P] in the layout of `kind`
+    (KIND_PENDULUM or KIND_MJMAZE): the H columns of l0/w, the H of l1/w, the O of out/w, each summed in numpy's order"""
+    noise, table, P = _mujoco_ga_table("mujoco_ga_colscale_host", noise, kind, hidden, n_out)
+    out = np.empty(2 * int(hidden) + int(n_out), np.float32)
+    _ck_host(load().dne_mujoco_ga_colscale_host(*table, int(idx0), _ptr(out, C.c_float)))
+    return out
+
+
+def mujoco_ga_theta_host(noise, kind, hidden, n_out, genome):
+    """dne_mujoco_ga_theta_host: csrc/mujoco_ga.h on the CPU (no GPU, no handle): theta [P] of one genome (idx0, (idx1, power1), ...) -- the
+    policy reinitialised on noise[idx0:idx0 + P], then theta += fl(power_j * noise[idx_j:idx_j + P]) per further seed"""
+    noise, table, P = _mujoco_ga_table("mujoco_ga_theta_host", noise, kind, hidden, n_out)
+    idx, pw = split_genome(genome)
+    out = np.empty(P, np.float32)
+    _ck_host(load().dne_mujoco_ga_theta_host(*table, _ptr(idx, C.c_int64), _ptr(pw, C.c_float), int(idx.size), _ptr(out, C.c_float)))
+    return out
+
+
+def mujoco_ga_members_host(noise, kind, hidden, n_out, bank, parent, idx, power):
+    """dne_mujoco_ga_members_host: the theta [n][P] of n member descriptors (parent, idx, power) against a host bank [T][P] (None: empty):
+    parent -1 a root at idx, idx < 0 the parent itself, otherwise bank[parent] + fl(power * noise[idx:idx + P])"""
+    noise, table, P = _mujoco_ga_table("mujoco_ga_members_host", noise, kind, hidden, n_out)
+    bank = np.zeros((0, P), np.float32) if bank is None else _arr(bank, np.float32).reshape(-1, P)
+    parent, idx, power = _maze_ga_members(parent, idx, power)
+    out = np.empty((parent.size, P), np.float32)
+    _ck_host(load().dne_mujoco_ga_members_host(*table, _ptr(bank, C.c_float) if bank.shape[0] else None, int(bank.shape[0]), _ptr(parent, C.c_int32),
+                                               _ptr(idx, C.c_int64), _ptr(power, C.c_float), int(parent.size), _ptr(out, C.c_float)))
+    return out
+
+
 def dense_bc_dim(env_kind):
     """D of an environment's behaviour characterisation: the cart-pole 4 (x, x_dot, theta, theta_dot), the acrobot 4 (theta1, theta2, omega1,
     omega2), the maze (x, y) and the pendulum (theta, theta_dot) 2"""
@@ -1473,6 +1528,46 @@ class Engine:
     def dense_ga_get_parent(self, j):
         out = np.empty(self.P, np.float32)
         self._ck(self.lib.dne_dense_ga_get_parent(self.h, int(j), _ptr(out, C.c_float)))
+        return out
+
+    # ---- Deep-GA on MujocoPolicy (csrc/mujoco_ga.h): the same surface on a KIND_PENDULUM or KIND_MJMAZE engine; a root is the policy
+    # reinitialised on its noise slice, so there is no init scale to set -- the bank is reserved for T_max parents instead
+    def mujoco_ga_reserve(self, T_max):
+        self._ck(self.lib.dne_mujoco_ga_reserve(self.h, int(T_max)))
+
+    def mujoco_ga_build(self, genomes):
+        """the bank = these genomes' thetas, parent j from genomes[j] = (idx0, (idx1, power1), ...)"""
+        T, co, flat, pw = self._pack_genomes(genomes)
+        self._ck(self.lib.dne_mujoco_ga_build(self.h, T, _ptr(co, C.c_int32), _ptr(flat, C.c_int64), _ptr(pw, C.c_float)))
+
+    def mujoco_ga_eval(self, parent, idx, power, tslimit, env_seed=None):
+        """one episode per member (parent -1: a root at idx; otherwise bank[parent] + fl(power * noise[idx])), member i reset from env_seed[i]
+        (the pendulum needs it; the maze reads none) -> (returns, signs, lengths).  set_rollout_options applies, ob_stats / final_state follow"""
+        parent, idx, power = _maze_ga_members(parent, idx, power)
+        n = parent.size
+        seeds = None if env_seed is None else _arr(env_seed, np.uint32).reshape(-1)
+        if seeds is not None and seeds.size != n:
+            raise DneError("mujoco_ga_eval: %d members, %d environment seeds" % (n, seeds.size))
+        ret = np.empty(n, np.float32); sg = np.empty(n, np.float32); ln = np.empty(n, np.int32)
+        self._ck(self.lib.dne_mujoco_ga_eval(self.h, n, _ptr(parent, C.c_int32), _ptr(idx, C.c_int64), _ptr(power, C.c_float), _ptr(seeds, C.c_uint32),
+                                             int(tslimit), _ptr(ret, C.c_float), _ptr(sg, C.c_float), _ptr(ln, C.c_int32)))
+        self._last_eval_n = n
+        return ret, sg, ln
+
+    def mujoco_ga_promote(self, parent, idx, power):
+        """new parent j = the theta of descriptor j over the bank as it is (idx < 0: parent[j] itself), all at once"""
+        parent, idx, power = _maze_ga_members(parent, idx, power)
+        self._ck(self.lib.dne_mujoco_ga_promote(self.h, int(parent.size), _ptr(parent, C.c_int32), _ptr(idx, C.c_int64), _ptr(power, C.c_float)))
+
+    def mujoco_ga_parents(self):
+        n = self.lib.dne_mujoco_ga_parents(self.h)
+        if n < 0:
+            self._ck(n)
+        return n
+
+    def mujoco_ga_get_parent(self, j):
+        out = np.empty(self.P, np.float32)
+        self._ck(self.lib.dne_mujoco_ga_get_parent(self.h, int(j), _ptr(out, C.c_float)))
         return out
 
     # ---- gpu-tree genomes: ((idx0,), (idx1, power1), ...)

@@ -501,15 +501,17 @@ def mujoco_shape(ac_bins, nonlin_type, hidden_dims, connection_type, adim=1):
 def refuse_mujoco(exp, driver):
     """nses / ga with MujocoPolicy.  The reference's novelty vector for this policy is the final (x_pos, y_pos) of MuJoCo's centre of mass
     (policies.py:252-256, 292-299).  The pendulum has no position, so there the two drivers are refused.  The hard maze has one -- the
-    navigator's final (x, y) -- so nses lets 'HardMaze-v0' through (NS-ES and NSR-ES; nses.py's MujocoPolicy path); ga with this policy is not built."""
+    navigator's final (x, y) -- so nses lets 'HardMaze-v0' through (NS-ES and NSR-ES; nses.py's MujocoPolicy path); ga.py's own setup keeps
+    refusing the policy: its Deep GA has drivers of its own (ga_mujoco.py), which the message names."""
+    pointer = " -- its Deep GA is dne_hip.ga_mujoco (setup, run_master, run_worker), called directly" if driver == 'ga' else ""
     if exp['policy']['type'] == 'MujocoPolicy' and exp.get('env_id') == MJMAZE_ENV_ID:
         if driver == 'nses':
             return
         raise NotImplementedError("{} with MujocoPolicy is not built -- MujocoPolicy runs under es and nses (NS-ES, NSR-ES) on {} and under es "
-                                  "on {}".format(driver, MJMAZE_ENV_ID, PENDULUM_ENV_ID))
+                                  "on {}{}".format(driver, MJMAZE_ENV_ID, PENDULUM_ENV_ID, pointer))
     if exp['policy']['type'] == 'MujocoPolicy':
         raise NotImplementedError("{} with MujocoPolicy is not built: its behaviour characterisation is MuJoCo's centre of mass, and no simulator "
-                                  "runs here -- MujocoPolicy runs under es on {}".format(driver, PENDULUM_ENV_ID))
+                                  "runs here -- MujocoPolicy runs under es on {}{}".format(driver, PENDULUM_ENV_ID, pointer))
 
 
 def normc_flat(hidden, n_out, seed=0, n_obs=_lib.PENDULUM_OBS):
@@ -580,7 +582,20 @@ class MujocoPolicy(Policy):
         self.set_trainable_flat(normc_flat(self.hidden, self.n_out, seed, self.n_obs))
 
     def reinitialize(self):
-        raise NotImplementedError("MujocoPolicy.reinitialize is the GA's (ga.py), which is not built for this policy")
+        """policies.py:42-44 over tf_util.py:149-158: every weight column of the current flat vector scaled to norm 1 -- std 1.0 for all three
+        layers, `out` included: reinitialize never passes dense's own std --, every bias zero.  The arithmetic is csrc/mujoco_ga.h's host twin
+        (the root of a genome, with the current vector as its noise slice)."""
+        self.set_trainable_flat(_lib.mujoco_ga_theta_host(self.get_trainable_flat(), self.kind, self.hidden, self.n_out, (0, )))
+
+    def set_from_seeds(self, seeds, noise_stdev, noise):
+        """ga.py:152-158: the policy reinitialised on noise[seeds[0]], then v += noise_stdev * noise[seed] per further seed.  noise: the table
+        the seeds index (a SharedNoiseTable or its array; ga.py reads its module's `noise`, a policy here holds none); the host twin computes
+        it, bit for bit what the engine's bank holds for the same chain."""
+        table = getattr(noise, 'noise', noise)
+        seeds = [int(s) for s in seeds]
+        genome = (seeds[0], ) + tuple((s, float(noise_stdev)) for s in seeds[1:])
+        self.set_trainable_flat(_lib.mujoco_ga_theta_host(table, self.kind, self.hidden, self.n_out, genome))
+        return self.get_trainable_flat()
 
     def _shape_kw(self):
         return dict(hidden=self.hidden, mean=self.ob_mean, std=self.ob_std, n_out=self.n_out, ac_mode=self.ac_mode, nonlin=self.nonlin)

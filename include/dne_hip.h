@@ -624,6 +624,44 @@ int dne_dense_ga_theta_host(const float *noise, size_t count, const float *scale
 int dne_dense_ga_members_host(const float *noise, size_t count, const float *scale_by, int P, const float *bank /*[T][P]*/, int T,
                               const int32_t *parent, const int64_t *idx, const float *power, int n, float *out /*[n][P]*/);
 
+/* ---- Deep-GA on MujocoPolicy (DNE_KIND_PENDULUM and DNE_KIND_MJMAZE; csrc/mujoco_ga.h) ---------
+ * es_distributed/ga.py's genome for this policy: the root is the policy REINITIALISED on a noise slice (ga.py:256-260) -- every weight column
+ * of l0/w, l1/w and out/w scaled to norm 1 (std 1.0 for all three, `out` included), every bias +0 --, then per further seed
+ * theta += fl(sigma * noise[seed ..]).  The scale is one value a column, sc = 1.0f / sqrtf(sum_k fl(x * x)), the sum in numpy's order for
+ * np.square(x).sum(axis=0) on the [K][C] view: sequential in k for C >= 2, numpy's pairwise order for the one-column out/w [H][1].
+ * A bank of T <= T_max parents lives on the device, apart from the base slots; a member is (parent, idx, power):
+ *   root   parent == -1, idx >= 0      the root rule above                                        (power is not read)
+ *   child  0 <= parent < T, idx >= 0   theta_p = bank[parent][p] + fl(power * noise[idx + p])     (never fused)
+ *   kept   0 <= parent < T, idx < 0    bank[parent] bit for bit: dne_mujoco_ga_promote only
+ * dne_mujoco_ga_reserve allocates the bank (2 * T_max slots, a double buffer; empty) and the GA's own descriptor arrays; called again it
+ * starts over with an empty bank.  The scratch slots of an evaluation's roots are allocated by the first evaluation that has a root.
+ * dne_mujoco_ga_build fills the bank with T parents from their genomes (chain_offsets [T + 1] into seeds / powers, from 0; powers[0] of a
+ * chain is not read).  dne_mujoco_ga_eval runs one episode per root / child member in one k_pendulum_rollout / k_mjmaze_rollout launch;
+ * member i is reset from env_seed[i] on the pendulum (required there; the maze reads none, NULL is fine).  It honours
+ * dne_*_set_rollout_options and needs dne_*_set_ob_stat as dne_eval_members does; dne_*_ob_stats, dne_pendulum_final_state,
+ * dne_maze_final_state and dne_get_profile follow it.  dne_mujoco_ga_promote makes the theta of descriptor j the new parent j, for all
+ * T_new <= T_max at once and from the bank as it was: a kept parent may move and two descriptors may name one source.
+ * dne_mujoco_ga_parents returns T (-1 on another kind), dne_mujoco_ga_get_parent copies one parent [P] out.
+ * Refused by name, with the bank left bit for bit as it was: another kind, a call before dne_mujoco_ga_reserve, no noise table,
+ * (evaluation) no maze loaded, statistics unset, env_seed NULL on the pendulum, T outside [1, T_max], n outside [1, max_members], a parent
+ * on an empty bank, parent >= T, parent < -1, a root without an index, the kept form in an evaluation, idx + P past the table, an empty
+ * chain or chain_offsets[0] != 0, a missing buffer, tslimit <= 0.  None of these reads or writes the base slots or dne_set_members' members.
+ * The *_host calls are the same header on the CPU (no handle, no GPU; kind 6 or 7, hidden 64 / 128 / 256, n_out as dne_*_num_params takes
+ * it): the H + H + O column scales of the slice at idx0, the theta of one genome, and of n descriptors -- the kept form included -- against a
+ * host bank [T][P] (NULL when T == 0); errors through dne_last_error(NULL). */
+int dne_mujoco_ga_reserve(dne_handle *h, int T_max);
+int dne_mujoco_ga_build(dne_handle *h, int T, const int32_t *chain_offsets /*T+1*/, const int64_t *seeds, const float *powers);
+int dne_mujoco_ga_eval(dne_handle *h, int n, const int32_t *parent, const int64_t *idx, const float *power, const uint32_t *env_seed /*n or NULL*/,
+                       int tslimit, float *returns, float *signreturns /*or NULL*/, int32_t *lengths);
+int dne_mujoco_ga_promote(dne_handle *h, int T_new, const int32_t *parent, const int64_t *idx, const float *power);
+int dne_mujoco_ga_parents(dne_handle *h);
+int dne_mujoco_ga_get_parent(dne_handle *h, int j, float *out /*P*/);
+int dne_mujoco_ga_colscale_host(const float *noise, size_t count, int kind, int hidden, int n_out, int64_t idx0, float *out /*2 hidden + n_out*/);
+int dne_mujoco_ga_theta_host(const float *noise, size_t count, int kind, int hidden, int n_out, const int64_t *seeds, const float *powers, int nseeds,
+                             float *out /*P*/);
+int dne_mujoco_ga_members_host(const float *noise, size_t count, int kind, int hidden, int n_out, const float *bank /*[T][P]*/, int T,
+                               const int32_t *parent, const int64_t *idx, const float *power, int n, float *out /*[n][P]*/);
+
 /* ---- novelty on the hard maze (csrc/maze_novelty.h) -------------------------------------------
  * A behaviour characterisation is one float32 point (x, y): a navigator's final position.  nses.py:12-32 on such points: for member p and
  * archive point a, d = sqrt(dx*dx + dy*dy) in double with dx = (double)ax - (double)px (unfused, correctly rounded sqrt); novelty = the
